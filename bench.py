@@ -12,18 +12,28 @@ interleaved 16-row bands across the ranks, each rank renders all samples of its 
 one RCCL gather per step assembles the frame on rank 0 (inside the timed region).  Total
 work is fixed as N grows: "scaling": "strong".
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and
-`cpu_baseline` objects.  The CPU baseline runs the oracle (oracle/liboracle.so, a
-structure-faithful restatement of the reference's CPU path) on a bounded row subset.
+Prints ONE JSON line on rank 0: `metric`, `value` (Msamples/s), `unit`, `higher_is_better`,
+`dtype`, `ms_per_step` and the configuration.  A plain run does only what that line needs:
+set-up, warm-up, the `--steps` timed steps and, with `--dump-outputs DIR`, the frame of the
+last timed step as DIR/frame.npy (float64, H x W x 4, what `rt_render_device` hands its
+caller; the inputs are fixed by the arguments and `--seed`).
+
+`--full` adds what takes work of its own: the first warm-up step collects the traversal
+counters behind the `roofline` object, and rank 0 of a one-GPU run times the CPU baseline
+(`cpu_baseline`: the oracle, oracle/liboracle.so, a structure-faithful restatement of the
+reference's CPU path, on a bounded row subset; `--no-cpu-baseline` leaves it out).  Without
+`--full` both objects are null.
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import subprocess
 import sys
+import tempfile
 import time
 
 REPO = os.path.dirname(os.path.abspath(__file__))
@@ -59,38 +69,78 @@ WORKLOADS = {
 }
 
 
-def ensure_dragon():
-    path = os.path.join(REPO, "scenes", "resource", "dragon_high.obj")
+def _may_write(d: str) -> bool:
+    try:
+        os.makedirs(d, exist_ok=True)
+    except OSError:
+        return False
+    return os.access(d, os.W_OK)
+
+
+def _outside_checkout():
+    """Where the generated inputs go when the checkout may only be read: a per-user directory under the temporary directory,
+    and a key (digest of tools/gen_dragon.cpp) for the file names, so that the output of another generator is never used."""
+    d = os.path.join(tempfile.gettempdir(), f"rt_mi355_bench_{os.getuid()}")
+    os.makedirs(d, exist_ok=True)
+    with open(os.path.join(REPO, "tools", "gen_dragon.cpp"), "rb") as f:
+        return d, hashlib.sha256(f.read()).hexdigest()[:16]
+
+
+def _create(path: str, make) -> None:
+    """`make(tmp)` writes a temporary file that then replaces `path` in one step (concurrent ranks / runs); nothing when it exists."""
     if not os.path.exists(path):
-        tool = os.path.join(REPO, "tools", "gen_dragon")
-        if not os.path.exists(tool):
-            subprocess.run(["g++", "-std=c++17", "-O2", "-o", tool, tool + ".cpp"], check=True)
         tmp = path + f".tmp{os.getpid()}"
-        subprocess.run([tool, tmp], check=True)
+        make(tmp)
         os.replace(tmp, path)
+
+
+def _gen_mesh(obj: str, dims) -> None:
+    """tools/gen_dragon's deterministic stand-in surface (NU = NV = dims, or its default 871 200 triangles) as `obj`."""
+    src = os.path.join(REPO, "tools", "gen_dragon.cpp")
+    tool = os.path.join(REPO, "tools", "gen_dragon")  # built by build()
+    if not os.path.exists(tool) and not _may_write(os.path.dirname(tool)):
+        d, key = _outside_checkout()
+        tool = os.path.join(d, f"gen_dragon_{key}")
+    _create(tool, lambda tmp: subprocess.run(["g++", "-std=c++17", "-O2", "-o", tmp, src], check=True))
+    _create(obj, lambda tmp: subprocess.run([tool, tmp] + [str(x) for x in dims], check=True))
+
+
+def _scene_with_mesh(scene: str, obj_name: str) -> str:
+    """scenes/cornell_dragon as `scene`, with its mesh replaced by `obj_name` (a path relative to the scene file, like every asset)."""
+    text = open(os.path.join(REPO, "scenes", "cornell_dragon")).read().replace("resource/dragon_high.obj", obj_name)
+    tmp = scene + f".tmp{os.getpid()}"
+    with open(tmp, "w") as f:
+        f.write(text)
+    os.replace(tmp, scene)
+    return scene
+
+
+def ensure_dragon() -> str:
+    """The headline scene file.  Its 871 200-triangle mesh is generated (too large to commit): scenes/cornell_dragon with
+    scenes/resource/dragon_high.obj in the checkout, or, in a checkout this process may only read, a copy of the scene beside
+    a mesh generated outside it."""
+    res = os.path.join(REPO, "scenes", "resource")
+    if os.path.exists(os.path.join(res, "dragon_high.obj")) or _may_write(res):
+        _gen_mesh(os.path.join(res, "dragon_high.obj"), [])
+        return os.path.join(REPO, "scenes", "cornell_dragon")
+    d, key = _outside_checkout()
+    _gen_mesh(os.path.join(d, f"dragon_high_{key}.obj"), [])
+    return _scene_with_mesh(os.path.join(d, f"cornell_dragon_{key}"), f"dragon_high_{key}.obj")
 
 
 BIG_MESHES = {"c4_3m": ("3m", 1320), "c4_14m": ("14m", 2640), "c4_218k": ("218k", 330), "c4_54k": ("54k", 165)}
 
 
-def ensure_big_dragon(workload: str):
-    """build/bigmesh/cornell_dragon_<tag> + dragon_<tag>.obj: scenes/cornell_dragon with tools/gen_dragon's surface at NU = NV = n."""
+def ensure_big_dragon(workload: str) -> str:
+    """build/bigmesh/cornell_dragon_<tag> + dragon_<tag>.obj: scenes/cornell_dragon with tools/gen_dragon's surface at NU = NV = n
+    (outside the checkout, as in ensure_dragon, when this process may not write build/bigmesh/).  Returns the scene file."""
     tag, n = BIG_MESHES[workload]
     d = os.path.join(REPO, "build", "bigmesh")
-    os.makedirs(d, exist_ok=True)
-    obj = os.path.join(d, f"dragon_{tag}.obj")
-    if not os.path.exists(obj):
-        tool = os.path.join(REPO, "tools", "gen_dragon")
-        if not os.path.exists(tool):
-            subprocess.run(["g++", "-std=c++17", "-O2", "-o", tool, tool + ".cpp"], check=True)
-        tmp = obj + f".tmp{os.getpid()}"
-        subprocess.run([tool, tmp, str(n), str(n)], check=True)
-        os.replace(tmp, obj)
-    scene = os.path.join(d, f"cornell_dragon_{tag}")
-    text = open(os.path.join(REPO, "scenes", "cornell_dragon")).read().replace("resource/dragon_high.obj", f"dragon_{tag}.obj")
-    with open(scene + ".tmp", "w") as f:
-        f.write(text)
-    os.replace(scene + ".tmp", scene)
+    if not _may_write(d):
+        d, key = _outside_checkout()
+        tag = f"{tag}_{key}"
+    _gen_mesh(os.path.join(d, f"dragon_{tag}.obj"), [n, n])
+    return _scene_with_mesh(os.path.join(d, f"cornell_dragon_{tag}"), f"dragon_{tag}.obj")
 
 
 def cpu_model() -> str:
@@ -141,7 +191,7 @@ def _oracle_rows(hs, p, stride):
     return halves, tot
 
 
-def cpu_baseline(workload: str, seed: int):
+def cpu_baseline(args, seed: int):
     """Times the CPU oracle on a bounded sample of the same workload (rank 0, N=1 only).
 
     Exactly the workload's flags (same -t replicas = OS threads like the reference's -t, same s x s
@@ -155,7 +205,6 @@ def cpu_baseline(workload: str, seed: int):
     (-t=40: 40 x 5 x 5 = 1000), pinned to one hardware thread per physical core: what this CPU can really do."""
     from rust_raytracer_amd import api
 
-    args, _ = WORKLOADS[workload]
     avail = len(os.sched_getaffinity(0))
     saved_affinity = os.sched_getaffinity(0)
     cores = physical_cores()
@@ -395,7 +444,11 @@ def main():
     ap.add_argument("--pipeline", default="auto", choices=["auto", "mega", "wavefront"])
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--spp-divisor", type=int, default=1, help="debug: render spp/divisor (result is then labelled reduced)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline object (counters collected in the first warm-up step) and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the frame of the last timed step to DIR/frame.npy (float64, H x W x 4)")
     ap.add_argument("--frames-in-flight", type=int, default=0,
                     help="device scenes of the frame pipeline (api.FramePipeline): 1 (default, every N) = the timed frames strictly one after "
                          "the other, so that the N = 1 and N > 1 lines measure the same thing; 3 = frame k+1 starts under the tail of frame k "
@@ -405,9 +458,12 @@ def main():
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         raise SystemExit(launch_ranks(a.gpus))
 
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -436,13 +492,16 @@ def main():
     device = torch.device("cuda", local_rank)
     torch.cuda.set_device(device)
 
+    args, desc = WORKLOADS[a.workload]
+    args = list(args)  # the workload's flags; a generated mesh's scene file is found (or made) here
     if a.workload == "c4" or a.workload in BIG_MESHES:
+        scene_file = ensure_dragon if a.workload == "c4" else (lambda: ensure_big_dragon(a.workload))
         if rank == 0:
-            ensure_dragon() if a.workload == "c4" else ensure_big_dragon(a.workload)
+            args[0] = scene_file()
         if world > 1:
             dist.barrier()
-    args, desc = WORKLOADS[a.workload]
-    args = list(args)
+            args[0] = scene_file()  # rank 0 has generated the mesh: the other ranks only find it
+    workload_args = list(args)
     if a.spp_divisor > 1:
         s = int([x for x in args if x.startswith("-s=")][0][3:]) // a.spp_divisor
         args = [x for x in args if not x.startswith("-s=")] + [f"-s={s}"]
@@ -477,9 +536,10 @@ def main():
             frame_holder["frame"] = rtdist.gather_frame(outs[k], hs.height, hs.width)
         return stats
 
-    # Warmup; the first warmup step also collects the traversal counters (deterministic for a
+    # Warmup; with --full the first warmup step also collects the traversal counters (deterministic for a
     # given seed/config) that turn kernel time into algorithmic bytes.
-    counters = run(n_warm, collect_first=True)[0]  # --warmup 0 still gets the untimed counter-collecting step(s)
+    warm = run(n_warm, collect_first=a.full)  # --warmup 0 still renders the untimed step(s)
+    counters = warm[0] if a.full else None
     torch.cuda.synchronize(device)
     if world > 1:
         dist.barrier()
@@ -508,9 +568,16 @@ def main():
             roofline["note"] += (f"  {depth} frames are in flight on this rank: a kernel's HIP-event duration includes the time it shares the "
                                  "GPU with the neighbouring frames' tail launches; the N = 1 line has the undisturbed figures.")
 
+    if rank == 0 and a.dump_outputs:
+        frame = frame_holder["frame"].cpu().numpy()  # float64: the library renders into an f64 RGBA frame at every precision
+        if frame.nbytes > 64e6:
+            raise SystemExit(f"bench.py: --dump-outputs: the {frame.shape} frame is over 64 MB")
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "frame.npy"), frame)
+
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
-        cpu = cpu_baseline(a.workload, a.seed)
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline:
+        cpu = cpu_baseline(workload_args, a.seed)
 
     if rank == 0:
         if a.save_png and frame_holder.get("frame") is not None:

@@ -115,3 +115,25 @@ def test_bench_starts_its_own_ranks():
     bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "3", "--steps", "1", "--no-cpu-baseline"],
                          cwd=REPO, env=dict(env, WORLD_SIZE="2", RANK="0", LOCAL_RANK="0"), capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0 and "WORLD_SIZE=2" in (bad.stdout + bad.stderr)
+
+
+def test_bench_plain_run_dumps_its_last_frame_and_full_adds_the_roofline(tmp_path):
+    """A plain `bench.py` run reports the --steps it timed, leaves `roofline` / `cpu_baseline` null and, with --dump-outputs,
+    writes the frame of its last timed step; the same arguments give the same frame, and `--full` adds the roofline object."""
+    base = [sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--workload", "c2", "--spp-divisor", "16"]
+
+    def bench(extra, out_dir):
+        r = subprocess.run(base + extra + ["--dump-outputs", str(out_dir)], cwd=REPO, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0]), np.load(out_dir / "frame.npy")
+
+    res, frame = bench([], tmp_path / "plain")
+    w, h = res["config"]["image"]
+    assert res["steps"] == 3 and res["roofline"] is None and res["cpu_baseline"] is None
+    assert res["value"] * res["ms_per_step"] == pytest.approx(w * h * res["config"]["spp"] / 1e3, rel=1e-9)
+    assert frame.dtype == np.float64 and frame.shape == (h, w, 4) and np.nanmean(frame[..., :3]) > 0
+    full, frame_full = bench(["--full", "--no-cpu-baseline"], tmp_path / "full")
+    assert full["roofline"] is not None and full["cpu_baseline"] is None
+    assert np.array_equal(frame, frame_full, equal_nan=True)

@@ -9,8 +9,8 @@ for r in $(seq 1 $rounds); do
   for w in $workloads; do
     for lib in "$@"; do
       name=$(basename "$lib" .so); [ "$lib" == "-" ] && name=tree
-      if [ "$lib" == "-" ]; then step $tag/ab_${w}_${name}_$r 400 python bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline
-      else RT_DEVICE_LIB=$PWD/$lib step $tag/ab_${w}_${name}_$r 400 python bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline; fi
+      if [ "$lib" == "-" ]; then step $tag/ab_${w}_${name}_$r 400 python bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline
+      else RT_DEVICE_LIB=$PWD/$lib step $tag/ab_${w}_${name}_$r 400 python bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline; fi
     done
   done
 done

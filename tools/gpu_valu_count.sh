@@ -9,7 +9,7 @@ for lib in "$@"; do
   name=$(basename "$lib" .so); [ "$lib" == "-" ] && name=tree
   out=$R/gpurun_out/$tag/valu_$name
   if [ "$lib" == "-" ]; then unset RT_DEVICE_LIB; else export RT_DEVICE_LIB=$R/$lib; fi
-  timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU --output-format csv -d "$out" -- python3 "$R/bench.py" --steps 1 --warmup 1 --no-cpu-baseline $args > "$out.log" 2>&1
+  timeout -k 10 400 rocprofv3 --pmc SQ_INSTS_VALU --output-format csv -d "$out" -- python3 "$R/bench.py" --full --steps 1 --warmup 1 --no-cpu-baseline $args > "$out.log" 2>&1
   rc=$?; echo "valu $name rc=$rc"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then exit 1; fi
   python3 - "$out" "$name" <<'PY'
 import csv, glob, collections, sys
