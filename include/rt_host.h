@@ -24,7 +24,8 @@ typedef struct RtHost RtHost;
 
 /* argv[0] is skipped like env::args().skip(1) (config.rs:81).  Flags are the
  * reference's (README.md:21-43) plus --seed=<u64>, --gpus=<n>,
- * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device (unknown keys are
+ * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
+ * --checkpoint=<file>, --time-limit=<seconds> (unknown keys are
  * ignored by the reference, config.rs:146, so these are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
  * the reference (main.rs:43, golden_monkey.rs:77). */
@@ -35,6 +36,12 @@ const RtSceneDesc* rth_scene(const RtHost* host);
 const RtCameraDesc* rth_camera(const RtHost* host);
 const RtRenderParams* rth_params(const RtHost* host);
 uint32_t rth_gpus(const RtHost* host);            /* --gpus, default 1 */
+/* Progressive rendering (rt_accum_*): --progressive=<n> replicas per pass (0 = off), --checkpoint=<file> ("" = none),
+ * --time-limit=<seconds> (< 0 = none).  rth_load rejects n = 0, --checkpoint without --progressive, --time-limit without
+ * --checkpoint and --progressive with --gpus > 1. */
+uint32_t rth_progressive(const RtHost* host);
+const char* rth_checkpoint(const RtHost* host);
+double rth_time_limit(const RtHost* host);
 uint32_t rth_samples_per_pixel(const RtHost* host); /* Camera::samples_per_pixel() */
 /* Row partition of `rtrace --gpus=N` (replaces the per-thread full-frame buffers of src/camera.rs:243-255): band height
  * for `height` image rows over `n_parts` GPUs = the largest of 16, 8, 4, 2, 1 rows that gives the most loaded part as few
@@ -56,6 +63,8 @@ int rth_make_camera(uint32_t width, double aspect_ratio, double focal_length,
 int rth_tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb_out);
 /* The same followed by an 8-bit RGB PNG file (zlib deflate). */
 int rth_save_png(const char* path, const double* rgba, uint32_t w, uint32_t h);
+/* An 8-bit RGB PNG file of w*h*3 bytes that are already tone-mapped (rt_accum_preview_rgb8). */
+int rth_save_png_rgb8(const char* path, const uint8_t* rgb, uint32_t w, uint32_t h);
 
 /* Buffer::from_image (src/buffer.rs:30-48): decodes a PNG or baseline-JPEG file into w*h RGB f32
  * triples (8-bit: x/255, 16-bit: x/65535), row 0 first.  The caller frees with rth_free_image. */

@@ -305,6 +305,49 @@ int rt_scene_program(const RtSceneDesc* desc, int32_t* ops_out, uint32_t capacit
  * clears `*flag` before each render.  rust_raytracer_amd.api.FramePipeline and bench.py use it. */
 int rt_scene_set_tail_flag(RtScene* scene, int32_t* flag);
 
+/* ---- Progressive, resumable rendering ----------------------------------------------------------------------------
+ * A frame with T = thread_count replicas of S^2 = sqrt_spt^2 strata (spp = T S^2) is the ordered sum of per-replica means
+ * (camera.rs:229,247-253).  An accumulator holds, after k replicas,
+ *
+ *     sum_k[p] = sum_{t < k} (sum over the strata of replica t of the radiance) / spp      (f64, added in increasing t)
+ *
+ * in rt_render's output layout (owned_rows x width x 4 doubles, w = 0; the row partition of `params` is honoured).
+ * Every random stream is keyed by (seed, replica, pixel, stratum), so the replicas can be rendered in any number of calls:
+ * sum_T is, bit for bit, the frame rt_render returns for the same scene, camera and params, for any split into calls,
+ * either pipeline (calls may switch), any replica grouping inside a call, tail compaction on or off, f64 or f32 (within
+ * one precision), NaN pixels included.  The estimate at 0 < k <= T is sum_k * (double(T) / double(k)): the frame's
+ * expected value from the first k replicas; at k = T the factor is 1.0 and the estimate is the final frame.  At k = 0
+ * there is no estimate (RT_E_INVALID).
+ *
+ * The accumulator keeps its own device buffer: renders of the same RtScene between its calls do not disturb it.  The scene
+ * must outlive every call on it but rt_accum_destroy, which may come after rt_scene_destroy.  All calls are synchronous.                                                                        */
+typedef struct RtAccum RtAccum;
+int rt_accum_create(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, RtAccum** out);
+void rt_accum_destroy(RtAccum* acc);
+/* Renders the next n_replicas replicas (clamped to T - k; 0 is a no-op).  params_or_null may change pipeline and
+ * collect_stats for this call only; any other difference from the creation params is RT_E_INVALID.  rt_get_stats then
+ * reports this call (samples = npix * S^2 * n), and the scene's tail flag (rt_scene_set_tail_flag) is set as by
+ * rt_render_device, the call's last replica group being its tail.  On an error k is unchanged.                       */
+int rt_accum_render(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream);
+uint32_t rt_accum_replicas_done(const RtAccum* acc);
+int rt_accum_estimate(const RtAccum* acc, double* rgba_out);                           /* host copy of the estimate  */
+int rt_accum_estimate_device(const RtAccum* acc, double* d_rgba_out, void* stream);   /* into HBM (scene's device)   */
+/* The estimate through rt_tonemap_rgb8_device: owned_rows * width * 3 bytes on the host (a preview copies 3 B per pixel). */
+int rt_accum_preview_rgb8(const RtAccum* acc, uint8_t* rgb_out);
+/* State blob: a 48-byte little-endian header (magic "RTACCUM\0", u32 format version 1, precision, width, owned rows, T, k,
+ * u64 digest of the scene description's content, u64 digest of the camera and of the params fields that change the frame:
+ * all but pipeline and collect_stats), then sum_k as owned_rows * width * 4 doubles.  rt_accum_load_state refuses
+ * (RT_E_INVALID, a message naming the mismatch, the accumulator unchanged) a truncated blob, a wrong magic or version, and
+ * any digest, size, T or precision mismatch.  The scene digest is computed once by rt_scene_create over every array the
+ * description points at (texels and Perlin tables included), never over pointer values.                              */
+size_t rt_accum_state_size(const RtAccum* acc);
+int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size);
+int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size);
+/* The output stage of rth_tonemap_rgb8 (ACES fit, sRGB OETF, `(x * 255.999) as u8`) on device `device`: d_rgba holds
+ * width * height RGBA doubles, d_rgb receives width * height * 3 bytes; both in HBM.  Same operations as the host,
+ * uncontracted; only pow may differ in its last bit.  Enqueued on `stream` (NULL = the null stream), returns after it. */
+int rt_tonemap_rgb8_device(int device, const double* d_rgba, uint32_t width, uint32_t height, uint8_t* d_rgb, void* stream);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

@@ -221,6 +221,22 @@ def load_device_lib() -> C.CDLL:
         if hasattr(lib, "rt_scene_mesh_stats"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_scene_mesh_stats.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(C.c_uint64)]
             lib.rt_scene_mesh_stats.restype = C.c_int
+        if hasattr(lib, "rt_accum_create"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            for name, res, args in (
+                    ("rt_accum_create", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), C.POINTER(C.c_void_p)]),
+                    ("rt_accum_destroy", None, [C.c_void_p]),
+                    ("rt_accum_render", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(RtRenderParams), C.c_void_p]),
+                    ("rt_accum_replicas_done", C.c_uint32, [C.c_void_p]),
+                    ("rt_accum_estimate", C.c_int, [C.c_void_p, C.c_void_p]),
+                    ("rt_accum_estimate_device", C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+                    ("rt_accum_preview_rgb8", C.c_int, [C.c_void_p, C.c_void_p]),
+                    ("rt_accum_state_size", C.c_size_t, [C.c_void_p]),
+                    ("rt_accum_save_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+                    ("rt_accum_load_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+                    ("rt_tonemap_rgb8_device", C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
         lib.rt_last_error.argtypes = []
         lib.rt_last_error.restype = C.c_char_p
         _device_lib = lib
@@ -336,6 +352,15 @@ def tonemap_rgb8(rgba: np.ndarray) -> np.ndarray:
     return out
 
 
+def tonemap_rgb8_device(d_rgba: int, width: int, height: int, d_rgb: int, device: int = 0, stream: int = 0) -> None:
+    """rt_tonemap_rgb8_device: tonemap_rgb8 on the GPU, device pointers in and out (width*height RGBA doubles ->
+    width*height*3 bytes); returns when the output is written."""
+    lib = load_device_lib()
+    st = lib.rt_tonemap_rgb8_device(device, C.c_void_p(d_rgba), width, height, C.c_void_p(d_rgb), C.c_void_p(stream))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+
+
 def save_png(path: str, rgba: np.ndarray) -> None:
     lib = load_host_lib()
     rgba = np.ascontiguousarray(rgba, dtype=np.float64)
@@ -406,6 +431,80 @@ class DeviceScene:
     def close(self):
         if self._h:
             self._lib.rt_scene_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ProgressiveRender:
+    """A frame rendered in passes of replicas (rt_accum_*, include/rt_mi355.h): after every pass `estimate()` is the
+    frame's expected value from the replicas so far, and once all `thread_count` replicas are done it IS the frame
+    DeviceScene.render returns, bit for bit, however the passes were split.  `save_state()` / `load_state()` carry the
+    sums to another process (same scene description, camera and params)."""
+
+    def __init__(self, scene: DeviceScene, camera: RtCameraDesc, params: RtRenderParams):
+        lib = load_device_lib()
+        handle = C.c_void_p()
+        st = lib.rt_accum_create(scene._h, C.byref(camera), C.byref(params), C.byref(handle))
+        if st != RT_OK:
+            raise RtError(st, lib.rt_last_error().decode())
+        self._lib = lib
+        self._h = handle
+        self.scene = scene  # the device scene must outlive the accumulator
+        self.camera = camera
+        self.params = params.copy()
+        self.rows = lib.rt_owned_rows(camera.image_height, C.byref(params))
+        self.total = params.thread_count
+
+    def _check(self, st: int) -> None:
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def render(self, n: int, pipeline: Optional[int] = None, collect_stats: Optional[bool] = None) -> int:
+        """Renders the next n replicas (clamped to what is left); returns replicas_done."""
+        p = None
+        if pipeline is not None or collect_stats is not None:
+            p = self.params.copy()
+            if pipeline is not None:
+                p.pipeline = pipeline
+            if collect_stats is not None:
+                p.collect_stats = int(bool(collect_stats))
+        self._check(self._lib.rt_accum_render(self._h, n, C.byref(p) if p is not None else None, None))
+        return self.replicas_done
+
+    @property
+    def replicas_done(self) -> int:
+        return int(self._lib.rt_accum_replicas_done(self._h))
+
+    def estimate(self) -> np.ndarray:
+        out = np.empty((self.rows, self.camera.image_width, 4), dtype=np.float64)
+        self._check(self._lib.rt_accum_estimate(self._h, out.ctypes.data))
+        return out
+
+    def estimate_device(self, d_out_ptr: int, stream: int = 0) -> None:
+        self._check(self._lib.rt_accum_estimate_device(self._h, C.c_void_p(d_out_ptr), C.c_void_p(stream)))
+
+    def preview_rgb8(self) -> np.ndarray:
+        out = np.empty((self.rows, self.camera.image_width, 3), dtype=np.uint8)
+        self._check(self._lib.rt_accum_preview_rgb8(self._h, out.ctypes.data))
+        return out
+
+    def save_state(self) -> bytes:
+        n = self._lib.rt_accum_state_size(self._h)
+        buf = C.create_string_buffer(n)
+        self._check(self._lib.rt_accum_save_state(self._h, buf, n))
+        return buf.raw
+
+    def load_state(self, blob: bytes) -> None:
+        self._check(self._lib.rt_accum_load_state(self._h, blob, len(blob)))
+
+    def close(self):
+        if self._h:
+            self._lib.rt_accum_destroy(self._h)
             self._h = None
 
     def __del__(self):

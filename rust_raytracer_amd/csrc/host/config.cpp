@@ -178,8 +178,32 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             if (value == "host") cfg.bvh_on_device = false;
             else if (value == "device") cfg.bvh_on_device = true;
             else { *err = "BVH builder must be host or device"; return false; }
+        } else if (key == "-progressive") {  // new: progressive, resumable rendering (rt_accum_*)
+            if (!need_usize("Progressive pass size") || u == 0 || u > 0xFFFFFFFFu) {
+                *err = "Progressive pass size must be a positive integer (replicas per pass)";
+                return false;
+            }
+            cfg.progressive = uint32_t(u);
+        } else if (key == "-checkpoint") {  // new
+            cfg.checkpoint = value;
+        } else if (key == "-time-limit") {  // new
+            if (!need_f64("Time limit")) return false;
+            if (!(d >= 0.0)) { *err = "Time limit must be a number of seconds >= 0"; return false; }
+            cfg.time_limit = d;
         }
         // unknown keys: ignored (config.rs:146)
+    }
+    if (!cfg.checkpoint.empty() && cfg.progressive == 0) {
+        *err = "--checkpoint requires --progressive=<n>";
+        return false;
+    }
+    if (cfg.time_limit >= 0.0 && cfg.checkpoint.empty()) {
+        *err = "--time-limit requires --checkpoint=<file> (a stopped render must be resumable)";
+        return false;
+    }
+    if (cfg.progressive && cfg.gpus > 1) {
+        *err = "--progressive renders on one GPU: it cannot be combined with --gpus > 1";
+        return false;
     }
     if (cfg.thread_count == 0) {
         *err = "Thread count must be a positive integer";  // the reference divides by zero here

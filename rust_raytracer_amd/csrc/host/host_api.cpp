@@ -76,6 +76,9 @@ const RtSceneDesc* rth_scene(const RtHost* host) { return host->desc; }
 const RtCameraDesc* rth_camera(const RtHost* host) { return &host->camera; }
 const RtRenderParams* rth_params(const RtHost* host) { return &host->params; }
 uint32_t rth_gpus(const RtHost* host) { return host->config.gpus; }
+uint32_t rth_progressive(const RtHost* host) { return host->config.progressive; }
+const char* rth_checkpoint(const RtHost* host) { return host->config.checkpoint.c_str(); }
+double rth_time_limit(const RtHost* host) { return host->config.time_limit; }
 uint32_t rth_band_rows(uint32_t height, uint32_t n_parts) {
     if (n_parts <= 1) return 0;
     uint32_t band = 16, best_rows = 0xFFFFFFFFu;
@@ -114,6 +117,13 @@ int rth_make_camera(uint32_t width, double aspect_ratio, double focal_length, do
 int rth_tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb_out) {
     if (!rgba || !rgb_out) return fail("rth_tonemap_rgb8: NULL argument");
     rth::tonemap_rgb8(rgba, w, h, rgb_out);
+    return RT_OK;
+}
+
+int rth_save_png_rgb8(const char* path, const uint8_t* rgb, uint32_t w, uint32_t h) {
+    if (!path || !rgb) return fail("rth_save_png_rgb8: NULL argument");
+    std::string err;
+    if (!rth::write_png_rgb8(path, rgb, w, h, &err)) return fail(err);
     return RT_OK;
 }
 

@@ -34,6 +34,9 @@ struct Config {
     uint32_t precision = RT_PRECISION_F64;
     uint32_t pipeline = RT_PIPELINE_AUTO;
     bool bvh_on_device = false;  // --bvh=device: RT_SCENE_BVH_ON_DEVICE
+    uint32_t progressive = 0;    // --progressive=<n>: passes of n replicas (0: one-shot render)
+    std::string checkpoint;      // --checkpoint=<file>: state saved after every pass, resumed from at start-up
+    double time_limit = -1.0;    // --time-limit=<seconds>: stop after the first pass that ends past it (< 0: none)
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176
 

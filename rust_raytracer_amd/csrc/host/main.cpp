@@ -5,13 +5,22 @@
 //
 // New, optional flags (ignored by the reference's parser, so command lines stay compatible):
 //   --seed=<u64>  --gpus=<n>  --precision=f64|f32  --pipeline=auto|mega|wavefront  --bvh=host|device
+//   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>
+// With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
+// the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
+// --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
+// --time-limit stops after the first pass that ends past the limit (measured from the start of the process).
 // With --gpus=n the frame is row-tiled in interleaved bands (rth_band_rows: 16 rows, or finer when that balances the GPUs), one
 // host thread per GPU; the tiles are assembled on the host here (bench.py shows the RCCL gather path used for the
 // multi-process launch).  RT_RTRACE_ONE_DEVICE=1 (tests on a one-GPU box): every part renders on device 0.
 #include <chrono>
 #include <cstdio>
+#include <fstream>
+#include <iterator>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -25,6 +34,67 @@ static std::string fmt_duration(double seconds) {  // Rust `{:.2?}` of a Duratio
     else if (seconds >= 1e-6) std::snprintf(buf, sizeof buf, "%.2f\xC2\xB5s", seconds * 1e6);
     else std::snprintf(buf, sizeof buf, "%.2fns", seconds * 1e9);
     return buf;
+}
+
+static int fail(const char* msg) {
+    std::fprintf(stderr, "Error: %s\n", msg);
+    return 1;
+}
+
+// One GPU, passes of rth_progressive(host) replicas; returns the process exit status.
+static int render_progressive(RtHost* host, const std::function<double()>& since) {
+    const RtCameraDesc* cam = rth_camera(host);
+    const RtRenderParams* params = rth_params(host);
+    const uint32_t W = cam->image_width, H = cam->image_height, T = params->thread_count, n = rth_progressive(host);
+    const std::string ckpt = rth_checkpoint(host);
+    const double limit = rth_time_limit(host);
+    RtScene* scene = nullptr;
+    RtAccum* acc = nullptr;
+    if (rt_scene_create(rth_scene(host), 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    if (rt_accum_create(scene, cam, params, &acc) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtAccum, void (*)(RtAccum*)> acc_guard(acc, rt_accum_destroy);
+    std::vector<char> state(rt_accum_state_size(acc));
+    if (!ckpt.empty()) {
+        std::ifstream in(ckpt, std::ios::binary);
+        if (in) {
+            std::vector<char> blob((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            if (rt_accum_load_state(acc, blob.data(), blob.size()) != RT_OK) return fail((ckpt + ": " + rt_last_error()).c_str());
+            std::printf("Resumed from %s at %u/%u replicas\n", ckpt.c_str(), rt_accum_replicas_done(acc), T);
+        }
+    }
+    auto save = [&]() -> bool {
+        if (ckpt.empty()) return true;
+        if (rt_accum_save_state(acc, state.data(), state.size()) != RT_OK) { fail(rt_last_error()); return false; }
+        const std::string tmp = ckpt + ".tmp";
+        std::ofstream out(tmp, std::ios::binary | std::ios::trunc);
+        out.write(state.data(), std::streamsize(state.size()));
+        out.close();
+        if (!out || std::rename(tmp.c_str(), ckpt.c_str()) != 0) { fail(("cannot write " + ckpt).c_str()); return false; }
+        return true;
+    };
+    std::vector<uint8_t> rgb(size_t(W) * H * 3);
+    for (uint32_t pass = 1; rt_accum_replicas_done(acc) < T; pass++) {
+        const double ts = since();
+        if (rt_accum_render(acc, n, nullptr, nullptr) != RT_OK) return fail(rt_last_error());
+        const uint32_t k = rt_accum_replicas_done(acc);
+        std::printf("Pass %u: %u/%u replicas in %s\n", pass, k, T, fmt_duration(since() - ts).c_str());
+        std::fflush(stdout);
+        if (!save()) return 1;
+        if (k == T) break;  // the final image goes through the host output stage below
+        if (rt_accum_preview_rgb8(acc, rgb.data()) != RT_OK) return fail(rt_last_error());
+        if (rth_save_png_rgb8("out.png", rgb.data(), W, H) != RT_OK) return fail(rth_last_error());
+        if (limit >= 0.0 && since() > limit) {
+            std::printf("Stopped at %u/%u replicas\n", k, T);
+            return 0;
+        }
+    }
+    std::vector<double> frame(size_t(W) * H * 4);
+    if (rt_accum_estimate(acc, frame.data()) != RT_OK) return fail(rt_last_error());  // k = T: the frame itself
+    std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());
+    if (rth_save_png("out.png", frame.data(), W, H) != RT_OK) return fail(rth_last_error());
+    std::printf("Done! Took %s. Goodbye :)\n", fmt_duration(since()).c_str());
+    return 0;
 }
 
 int main(int argc, char** argv) {
@@ -51,6 +121,11 @@ int main(int argc, char** argv) {
     if (available < 1) {
         std::fprintf(stderr, "Error: no HIP device (the render path has no CPU fallback)\n");
         return 1;
+    }
+    if (rth_progressive(host)) {
+        const int rc = render_progressive(host, since);
+        rth_destroy(host);
+        return rc;
     }
     const char* one_dev = std::getenv("RT_RTRACE_ONE_DEVICE");
     const bool rehearsal = one_dev && std::atoi(one_dev) != 0;

@@ -32,10 +32,14 @@ template <typename R> RT_DEV uint32_t row_to_y(const ParamsView<R>& prm, uint32_
 // ended starts its next sample in the same trip, so the wave stays converged on
 // world_test -> shade and no lane idles while it still has samples.  Sums are accumulated
 // per pixel in the reference's order, so the result does not depend on scheduling.
+// One launch renders the replicas [t_first, t_first + n_rep) of the frame; with t_first > 0 the
+// pixel's sum starts from the running sum of [0, t_first) that `out` holds (progressive rendering,
+// RtAccum), so any split of [0, T) into launches gives the one-launch frame bit for bit.
 // ---------------------------------------------------------------------------------------------
 template <typename R, bool STATS, bool TEX>
 __global__ void __launch_bounds__(256) k_megakernel(SceneView<R> sc, CameraView<R> cam, ParamsView<R> prm,
-                                                    double* __restrict__ out, DeviceCounters* counters) {
+                                                    double* __restrict__ out, DeviceCounters* counters, uint32_t t_first,
+                                                    uint32_t n_rep) {
     extern __shared__ int lds_stack[];
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t tiles_x = (cam.width + 15u) / 16u;
@@ -49,11 +53,14 @@ __global__ void __launch_bounds__(256) k_megakernel(SceneView<R> sc, CameraView<
 
     const uint32_t S = cam.sqrt_spt;
     const uint32_t per_replica = S * S;
-    const uint32_t total = per_replica * cam.thread_count;
+    const uint32_t total = per_replica * n_rep;
     const uint64_t pixel_index = uint64_t(py) * cam.width + px;
+    double* o = out + (size_t(row) * cam.width + px) * 4;
 
     LaneCounters cnt;
     double acc[3] = {0.0, 0.0, 0.0};  // buf += thread_buf, camera.rs:247-253
+    if (t_first > 0)
+        for (int k = 0; k < 3; k++) acc[k] = o[k];
     double col[3] = {0.0, 0.0, 0.0};  // `color` of the current replica, camera.rs:215-229
     uint32_t sample = 0;              // next sample to start
     uint32_t in_replica = 0;
@@ -67,6 +74,7 @@ __global__ void __launch_bounds__(256) k_megakernel(SceneView<R> sc, CameraView<
             if (sample == total) break;
             uint32_t tid = sample / per_replica;
             uint32_t st = sample - tid * per_replica;
+            tid += t_first;
             uint32_t sy = st / S, sx = st - sy * S;
             rng.key(prm.seed, tid, pixel_index, st);
             ps.ray = get_ray(cam, px, py, sx, sy, rng);
@@ -101,7 +109,6 @@ __global__ void __launch_bounds__(256) k_megakernel(SceneView<R> sc, CameraView<
             }
         }
     }
-    double* o = out + (size_t(row) * cam.width + px) * 4;
     o[0] = acc[0];
     o[1] = acc[1];
     o[2] = acc[2];
@@ -547,6 +554,7 @@ struct RtScene {
     rt::DeviceCounters* d_counters = nullptr;
     RtRenderStats stats{};
     int32_t* tail_flag = nullptr;  // rt_scene_set_tail_flag: set to 1 when a render stops filling the GPU (frame pipelining)
+    uint64_t content_digest = 0;   // of everything the description points at (rt::scene_digest): checkpoints name their scene by it
     // wavefront pipeline resources (allocated on first use, reused between renders)
     struct Wavefront {
         uint32_t capacity = 0;
@@ -607,9 +615,12 @@ template <typename R> ParamsView<R> make_params_view(const RtRenderParams& p, ui
     return v;
 }
 
+// Both drivers render the replicas [t_first, t_first + n) of the frame `p` describes (T = p.thread_count) into d_out,
+// which holds the running sum of [0, t_first) on entry when t_first > 0 (include/rt_mi355.h, RtAccum); a whole frame is
+// t_first = 0, n = T.
 template <typename R>
 int render_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
-                 double* d_out, hipStream_t stream) {
+                 uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream) {
     CameraView<R> cv = make_camera_view<R>(cam, p);
     ParamsView<R> pv = make_params_view<R>(p, owned);
     const uint32_t tiles_x = (cam.image_width + 15u) / 16u, tiles_y = (owned + 15u) / 16u;
@@ -620,7 +631,7 @@ int render_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const 
     HIP_TRY(hipEventRecord(s->ev0, stream));
     // full-feature variant: texture interpreter (lerp / image / noise / channel / normal maps) and volumes
     const bool tex = s->compiled.needs_tex_interpreter || !s->compiled.volumes.empty();
-#define RT_LAUNCH_MEGA(ST, TX) hipLaunchKernelGGL((k_megakernel<R, ST, TX>), grid, block, lds, stream, ds.view, cv, pv, d_out, s->d_counters)
+#define RT_LAUNCH_MEGA(ST, TX) hipLaunchKernelGGL((k_megakernel<R, ST, TX>), grid, block, lds, stream, ds.view, cv, pv, d_out, s->d_counters, t_first, n)
     if (p.collect_stats) { if (tex) RT_LAUNCH_MEGA(true, true); else RT_LAUNCH_MEGA(true, false); }
     else { if (tex) RT_LAUNCH_MEGA(false, true); else RT_LAUNCH_MEGA(false, false); }
 #undef RT_LAUNCH_MEGA
@@ -637,7 +648,7 @@ int render_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const 
     st.traversal_kernel_ms = ms;
     st.n_launches = 1;
     st.pipeline_used = RT_PIPELINE_MEGAKERNEL;
-    st.samples = uint64_t(cam.image_width) * owned * uint64_t(pv.spp);
+    st.samples = uint64_t(cam.image_width) * owned * p.sqrt_spt * p.sqrt_spt * n;
     st.rays = hc.rays;
     st.mesh_rays = hc.mesh_rays;
     st.node_visits = hc.node_visits;
@@ -746,12 +757,13 @@ int wf_ensure(RtScene* s, uint32_t capacity) {
 
 template <typename R>
 int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
-                     double* d_out, hipStream_t stream) {
+                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream) {
     CameraView<R> cv = make_camera_view<R>(cam, p);
     ParamsView<R> pv = make_params_view<R>(p, owned);
     const uint64_t npix = uint64_t(cam.image_width) * owned;
     const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
     const uint32_t T = p.thread_count;
+    const uint32_t t_end = t_first + n;
     const uint64_t per_replica = uint64_t(strata) * npix;
     // Pool size.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
     // dependent fetches) and the streaming kernels run better in few large launches, so fewer, larger launches win; against that
@@ -762,6 +774,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     //   C3 0.96 G: 52 M 4841, 80 M 4907, 96 M 4977, 112 M 4890      C1 0.25 G: 26 M 1962, 48 M 2028, 64 M 2061-2079, 96 M 2120, 128 M 2129
     //   C2 0.16 G (no mesh): 16 M 1681, 22 M 1692, 32 M 1668, 44 M 1670      one of 8 ranks' share of C4: 23 M 157 ms, 46 M / 92 M 151, 128 M 153
     // -> 128 M slots at 1.44 G samples, with the square root of the work below it (within 1-3 % of each workload's best).
+    // Sized from the whole frame (T replicas), not from this call's n: progressive passes of any size keep the same pool.
     uint32_t capacity;
     {
         const double total_samples = double(per_replica) * double(T);
@@ -792,8 +805,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     size_t avail = free_b + w.sample_L_bytes;
     if (budget > avail / 2) budget = avail / 2;
     uint64_t bytes_per_replica = per_replica * 24ull;
-    uint32_t group = uint32_t(std::min<uint64_t>(T, std::max<uint64_t>(1, budget / bytes_per_replica)));
-    group = (T + (T + group - 1) / group - 1) / ((T + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
+    uint32_t group = uint32_t(std::min<uint64_t>(n, std::max<uint64_t>(1, budget / bytes_per_replica)));
+    group = (n + (n + group - 1) / group - 1) / ((n + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
     if (bytes_per_replica > avail) return set_err(RT_E_NOMEM, "per-sample radiance buffer of one replica does not fit in device memory");
     size_t need = size_t(bytes_per_replica) * group;
     if (w.sample_L_bytes < need) {
@@ -803,7 +816,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.sample_L), need));
         w.sample_L_bytes = need;
     }
-    const bool multi_group = group < T;
+    const bool multi_group = group < n;
     if (multi_group && w.acc_bytes < npix * 24) {
         if (w.acc) (void)hipFree(w.acc);
         w.acc = nullptr;
@@ -905,9 +918,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // after the mesh kernel, after shade); slot 0 = prims, 1 = traversal (mesh or combined intersect), 2 = shade
     double phase_ms[3] = {0.0, 0.0, 0.0};
     uint32_t isect_launches = 0, n_groups = 0;
-    for (uint32_t t0 = 0; t0 < T; t0 += group) {
+    for (uint32_t t0 = t_first; t0 < t_end; t0 += group) {
         n_groups++;
-        uint32_t nrep = std::min(group, T - t0);
+        uint32_t nrep = std::min(group, t_end - t0);
         WfGroup<R> grp{};
         grp.total = per_replica * nrep;
         grp.npix = npix;
@@ -949,8 +962,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     } while (0)
         for (;;) {
             size_t ev = 0;
-            // near the end of the last group the host looks after every second iteration, so that the tail is seen when it starts
-            const bool near_end = s->tail_flag && t0 + nrep >= T && w.h_ctr->next_sample + 4ull * pool.capacity >= grp.total;
+            // near the end of the call's last group the host looks after every second iteration, so that the tail is seen when it starts
+            const bool near_end = s->tail_flag && t0 + nrep >= t_end && w.h_ctr->next_sample + 4ull * pool.capacity >= grp.total;
             // tail compaction wants to see the queue length of every iteration once the samples have run out, and to notice
             // within two iterations that they have (a quarter of the slots restarts per iteration)
             const bool all_started = w.h_ctr->next_sample >= grp.total;
@@ -1018,9 +1031,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                                  double(a[5][k]), double(a[6][k]), double(a[7][k]), double(a[8][k]), double(a[9][k]), hpc[k], (unsigned long long)rngs[k]);
             }
             upper = w.h_ctr->n_in;
-            // every sample of the last group has been started and slots are running empty: from here on this render cannot
-            // fill the GPU any more, the next frame's render (another RtScene, another stream) may start underneath it
-            if (s->tail_flag && t0 + nrep >= T && upper < first) __atomic_store_n(s->tail_flag, 1, __ATOMIC_RELEASE);
+            // every sample of the call's last group has been started and slots are running empty: from here on this render
+            // cannot fill the GPU any more, the next frame's render (another RtScene, another stream) may start underneath it
+            if (s->tail_flag && t0 + nrep >= t_end && upper < first) __atomic_store_n(s->tail_flag, 1, __ATOMIC_RELEASE);
             if (upper == 0) break;
             // ---- tail compaction (rt_wavefront.h k_wf_compact): fewer than half of the addressed slots are alive and none will
             //      restart: the live paths move to slots 0 .. upper-1 of the other pool, which becomes the pool ----
@@ -1040,7 +1053,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 #undef RT_LAUNCH_MESH_V
 #undef RT_LAUNCH_MESH_M
         hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L, w.acc, npix, strata, nrep,
-                           pv.spp, int(t0 == 0), d_out, int(t0 + nrep >= T));
+                           pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, stream));
@@ -1079,7 +1092,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                      pct(hc.tri_tests, hc.tri_wave_iters), hc.refill_wave_iters, pct(hc.refill_lanes, hc.refill_wave_iters), hc.pops_culled);
     }
     st.pipeline_used = RT_PIPELINE_WAVEFRONT;
-    st.samples = npix * uint64_t(pv.spp);
+    st.samples = npix * strata * n;
     st.rays = hc.rays;
     st.mesh_rays = hc.mesh_rays;
     st.node_visits = hc.node_visits;
@@ -1137,6 +1150,153 @@ __global__ void k_debug_fuzzy_reflection(uint32_t n, const double* __restrict__ 
 }
 }  // namespace rt
 
+// ---------------------------------------------------------------------------------------------
+// Progressive rendering (RtAccum, include/rt_mi355.h): estimate scaling, device output stage, digests
+// ---------------------------------------------------------------------------------------------
+namespace rt {
+
+// estimate = sum_k * (T / k), every double of the (owned_rows x width x 4) layout (w stays 0)
+__global__ void __launch_bounds__(256) k_accum_estimate(const double* __restrict__ sum, uint64_t n, double scale, double* __restrict__ out) {
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = sum[i] * scale;
+}
+
+// The host output stage (csrc/host/output.cpp tonemap_rgb8: ACES fit, clamp, sRGB OETF, saturating u8) on the device,
+// operation for operation and without contraction (the host build never fuses a*b+c); only pow may differ from the host's
+// in the last bit.  Input pixel i is rgba[4 i ..] * scale: the estimate of an accumulator is tone-mapped without a second
+// pass over HBM (scale 1 for a plain frame: x * 1 == x, and a NaN maps to 0 whatever its payload).
+__global__ void __launch_bounds__(256) k_tonemap_rgb8(const double* __restrict__ rgba, uint64_t npix, double scale, uint8_t* __restrict__ rgb) {
+#pragma clang fp contract(off)
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const double kIn[9] = {0.59719, 0.35458, 0.04823, 0.07600, 0.90834, 0.01566, 0.02840, 0.13383, 0.83777};
+    const double kOut[9] = {1.60475, -0.53108, -0.07367, -0.10208, 1.10813, -0.00605, -0.00327, -0.07276, 1.07602};
+    const double gamma = 1.0 / 2.4;
+    double p[4], c[3], f[3];
+    for (int k = 0; k < 4; k++) p[k] = rgba[4 * i + k] * scale;
+    for (int r = 0; r < 3; r++) c[r] = kIn[3 * r] * p[0] + kIn[3 * r + 1] * p[1] + kIn[3 * r + 2] * p[2] + 0.0 * p[3];
+    for (int k = 0; k < 3; k++) {
+        const double a = c[k] * (c[k] + 0.0245786) - 0.000090537;
+        const double b = c[k] * (c[k] * 0.983729 + 0.4329510) + 0.238081;
+        f[k] = a / b;
+    }
+    for (int r = 0; r < 3; r++) {
+        double x = kOut[3 * r] * f[0] + kOut[3 * r + 1] * f[1] + kOut[3 * r + 2] * f[2] + 0.0 * 0.0;
+        if (x < 0.0) x = 0.0;  // clamp01: NaN stays NaN
+        if (x > 1.0) x = 1.0;
+        const double v = x < 0.0031308 ? x * 12.92 : pow(x, gamma) * 1.055 - 0.055;
+        const double q = v * 255.999;
+        rgb[3 * i + r] = !(q > 0.0) ? uint8_t(0) : (q >= 255.0 ? uint8_t(255) : uint8_t(q));  // saturating `as u8`, NaN -> 0
+    }
+}
+
+// 64-bit digest of byte strings (checkpoint identity, not security): 8-byte words through a multiply-rotate round
+struct Digest {
+    uint64_t h = 0x243F6A8885A308D3ull;
+    void word(uint64_t w) {
+        w *= 0x9E3779B97F4A7C15ull;
+        w ^= w >> 29;
+        h = ((h ^ w) * 0xBF58476D1CE4E5B9ull);
+        h = (h << 27) | (h >> 37);
+    }
+    void bytes(const void* p, size_t n) {
+        const unsigned char* b = static_cast<const unsigned char*>(p);
+        word(n);
+        if (!b) return;
+        for (; n >= 8; n -= 8, b += 8) { uint64_t w; std::memcpy(&w, b, 8); word(w); }
+        if (n) { uint64_t w = 0; std::memcpy(&w, b, n); word(w); }
+    }
+    template <typename T> void val(const T& v) { bytes(&v, sizeof v); }
+    uint64_t value() const { uint64_t x = h ^ (h >> 31); x *= 0x94D049BB133111EBull; return x ^ (x >> 29); }
+};
+
+// Everything an RtSceneDesc points at, field by field (never a pointer value, never padding).  Not the flags: the BVH
+// builder only culls, a frame does not depend on it.
+static uint64_t scene_digest(const RtSceneDesc& d) {
+    Digest g;
+    g.val(d.n_nodes); g.val(d.world_root); g.val(d.lights_root);
+    for (uint32_t i = 0; i < d.n_nodes; i++) {
+        const RtNode& n = d.nodes[i];
+        g.val(n.type); g.val(n.flags); g.val(n.material); g.val(n.mesh); g.val(n.transform); g.val(n.first_child);
+        g.val(n.n_children); g.val(n.bounds); g.val(n.p);
+    }
+    g.bytes(d.child_indices, size_t(d.n_child_indices) * 4);
+    g.bytes(d.transforms, size_t(d.n_transforms) * sizeof(RtTransform));
+    for (uint32_t i = 0; i < d.n_meshes; i++) {
+        const RtMesh& m = d.meshes[i];
+        g.val(m.n_positions); g.val(m.n_normals); g.val(m.n_uvs); g.val(m.n_triangles); g.val(m.flags);
+        g.bytes(m.positions, size_t(m.n_positions) * 24);
+        g.bytes(m.normals, size_t(m.n_normals) * 24);
+        g.bytes(m.uvs, m.uvs ? size_t(m.n_uvs) * 24 : 0);
+        g.bytes(m.tri_pos, size_t(m.n_triangles) * 12);
+        g.bytes(m.tri_nrm, size_t(m.n_triangles) * 12);
+        g.bytes(m.tri_uv, m.tri_uv ? size_t(m.n_triangles) * 12 : 0);
+    }
+    for (uint32_t i = 0; i < d.n_materials; i++) {
+        const RtMaterial& m = d.materials[i];
+        g.val(m.type); g.val(m.tex_a); g.val(m.tex_b); g.val(m.tex_c); g.val(m.ior);
+    }
+    for (uint32_t i = 0; i < d.n_textures; i++) {
+        const RtTexture& t = d.textures[i];
+        g.val(t.type); g.val(t.a); g.val(t.b); g.val(t.c); g.val(t.channel); g.val(t.samples); g.val(t.v); g.val(t.scale);
+        g.val(t.width); g.val(t.height);
+        g.bytes(t.texels, t.texels ? size_t(t.width) * t.height * 3 * sizeof(float) : 0);
+        g.bytes(t.perlin_vec, t.perlin_vec ? 256 * 3 * sizeof(double) : 0);
+        g.bytes(t.perlin_perm, t.perlin_perm ? 3 * 256 * sizeof(uint32_t) : 0);
+    }
+    return g.value();
+}
+
+// The camera and every params field that changes the frame (all but pipeline and collect_stats).
+static RtRenderParams frame_fields(const RtRenderParams& p) {
+    RtRenderParams q = p;
+    q.pipeline = 0;
+    q.collect_stats = 0;
+    return q;
+}
+static uint64_t frame_digest(const RtCameraDesc& c, const RtRenderParams& p) {
+    Digest g;
+    g.val(c.image_width); g.val(c.image_height); g.val(c.position); g.val(c.first_pixel); g.val(c.pixel_delta_u);
+    g.val(c.pixel_delta_v); g.val(c.basis_u); g.val(c.basis_v); g.val(c.has_aperture); g.val(c.aperture_radius);
+    const RtRenderParams q = frame_fields(p);
+    g.val(q.sqrt_spt); g.val(q.thread_count); g.val(q.max_depth); g.val(q.has_background); g.val(q.light_bias);
+    g.val(q.background); g.val(q.seed); g.val(q.band_rows); g.val(q.n_parts); g.val(q.part); g.val(q.precision);
+    return g.value();
+}
+
+// State blob: this header (little-endian), then owned_rows * width * 4 doubles of sum_k
+struct AccumHeader {
+    char magic[8];
+    uint32_t version, precision, width, owned_rows, thread_count, replicas_done;
+    uint64_t scene_digest, frame_digest;
+};
+static_assert(sizeof(AccumHeader) == 48, "state header layout");
+static const char kAccumMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
+static const uint32_t kAccumVersion = 1;
+
+static int tonemap_launch(const double* d_rgba, uint64_t npix, double scale, uint8_t* d_rgb, hipStream_t stream) {
+    if (npix == 0) return RT_OK;
+    hipLaunchKernelGGL(k_tonemap_rgb8, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, d_rgba, npix, scale, d_rgb);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+}  // namespace rt
+
+struct RtAccum {
+    RtScene* scene = nullptr;      // not owned: must outlive every call but rt_accum_destroy
+    int device = 0;                // the scene's device (rt_accum_destroy does not touch the scene)
+    RtCameraDesc camera{};
+    RtRenderParams params{};       // as created (pipeline / collect_stats: the defaults of rt_accum_render)
+    uint32_t owned = 0, T = 0, k = 0;
+    uint64_t frame_digest = 0;
+    double* d_sum = nullptr;       // sum_k, owned x width x 4 doubles: the accumulator's own buffer
+    double* d_est = nullptr;       // estimate scratch (lazy)
+    uint8_t* d_rgb = nullptr;      // preview scratch (lazy)
+    size_t n_doubles() const { return size_t(owned) * camera.image_width * 4; }
+};
+
 extern "C" {
 
 const char* rt_last_error(void) { return rt::g_err.c_str(); }
@@ -1168,6 +1328,7 @@ int rt_scene_create(const RtSceneDesc* desc, int device, RtScene** out) {
     }
     int st = compile_scene(desc, &s->compiled, &err, opt);
     if (st != RT_OK) return set_err(st, err);
+    s->content_digest = scene_digest(*desc);  // the description has been validated by the compiler
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_err(RT_E_DEVICE, "no HIP device available");
     if (device < 0 || device >= n) return set_err(RT_E_INVALID, "device index out of range");
     s->device = device;
@@ -1205,11 +1366,14 @@ uint32_t rt_owned_rows(uint32_t image_height, const RtRenderParams* params) {
     return rt::owned_rows(image_height, params);
 }
 
+// Renders the replicas [t_first, t_first + n) of the frame into d_rgba_out (running sum of [0, t_first) on entry):
+// rt_render_device is [0, T), rt_accum_render the next n of an accumulator.
 static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
-                              double* d_rgba_out, void* stream) {
+                              uint32_t t_first, uint32_t n, double* d_rgba_out, void* stream) {
     using namespace rt;
     if (!scene || !camera || !params || !d_rgba_out) return set_err(RT_E_INVALID, "rt_render_device: NULL argument");
     if (int v = validate_render_args(camera, params)) return v;
+    if (n == 0 || t_first + uint64_t(n) > params->thread_count) return set_err(RT_E_INVALID, "replica range outside [0, thread_count)");
     RtScene* s = const_cast<RtScene*>(scene);  // stats + lazily built tables; the scene data itself is immutable
     HIP_TRY(hipSetDevice(s->device));
     uint32_t owned = owned_rows(camera->image_height, params);
@@ -1228,8 +1392,8 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
             if (r != RT_OK) return r;
             s->f32 = std::move(ds);
         }
-        if (wavefront) return render_wavefront<float>(s, *s->f32, *camera, *params, owned, d_rgba_out, st);
-        return render_typed<float>(s, *s->f32, *camera, *params, owned, d_rgba_out, st);
+        if (wavefront) return render_wavefront<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st);
+        return render_typed<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st);
     }
     if (!s->f64) {
         auto ds = std::make_unique<DeviceScene<double>>();
@@ -1237,13 +1401,13 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
         if (r != RT_OK) return r;
         s->f64 = std::move(ds);
     }
-    if (wavefront) return render_wavefront<double>(s, *s->f64, *camera, *params, owned, d_rgba_out, st);
-    return render_typed<double>(s, *s->f64, *camera, *params, owned, d_rgba_out, st);
+    if (wavefront) return render_wavefront<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st);
+    return render_typed<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st);
 }
 
 int rt_render_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
                      double* d_rgba_out, void* stream) {
-    int r = render_device_impl(scene, camera, params, d_rgba_out, stream);
+    int r = render_device_impl(scene, camera, params, 0, params ? params->thread_count : 0, d_rgba_out, stream);
     // whoever waits for this render's tail (rt_scene_set_tail_flag) is released at the latest here, errors included
     if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
     return r;
@@ -1395,6 +1559,180 @@ int rt_scene_program(const RtSceneDesc* desc, int32_t* ops_out, uint32_t capacit
     info[5] = cs.volumes.size();
     info[6] = (plan.split ? 1u : 0u) | (plan.vol_prims ? 2u : 0u) | (plan.multi_mesh ? 4u : 0u) | (plan.groups ? 8u : 0u);
     info[7] = cs.group_prims.size();
+    return RT_OK;
+}
+
+int rt_accum_create(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, RtAccum** out) {
+    using namespace rt;
+    if (!out) return set_err(RT_E_INVALID, "rt_accum_create: out is NULL");
+    *out = nullptr;
+    if (!scene || !camera || !params) return set_err(RT_E_INVALID, "rt_accum_create: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    const uint32_t owned = owned_rows(camera->image_height, params);
+    if (owned == 0) return set_err(RT_E_INVALID, "rt_accum_create: the row partition gives this part no rows");
+    std::unique_ptr<RtAccum> a(new (std::nothrow) RtAccum);
+    if (!a) return set_err(RT_E_NOMEM, "out of memory");
+    a->scene = const_cast<RtScene*>(scene);
+    a->device = scene->device;
+    a->camera = *camera;
+    a->params = *params;
+    a->owned = owned;
+    a->T = params->thread_count;
+    a->frame_digest = frame_digest(*camera, *params);
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_sum), a->n_doubles() * sizeof(double)));
+    HIP_TRY(hipMemset(a->d_sum, 0, a->n_doubles() * sizeof(double)));
+    HIP_TRY(hipDeviceSynchronize());
+    *out = a.release();
+    return RT_OK;
+}
+
+void rt_accum_destroy(RtAccum* acc) {
+    if (!acc) return;
+    (void)hipSetDevice(acc->device);
+    if (acc->d_sum) (void)hipFree(acc->d_sum);
+    if (acc->d_est) (void)hipFree(acc->d_est);
+    if (acc->d_rgb) (void)hipFree(acc->d_rgb);
+    delete acc;
+}
+
+static int accum_render_impl(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream) {
+    using namespace rt;
+    if (!acc) return set_err(RT_E_INVALID, "rt_accum_render: NULL accumulator");
+    RtRenderParams p = acc->params;
+    if (params_or_null) {
+        const RtRenderParams a = frame_fields(acc->params), b = frame_fields(*params_or_null);
+        if (std::memcmp(&a, &b, sizeof a) != 0)
+            return set_err(RT_E_INVALID, "rt_accum_render: params differ from the accumulator's in more than pipeline / collect_stats");
+        p.pipeline = params_or_null->pipeline;
+        p.collect_stats = params_or_null->collect_stats;
+    }
+    const uint32_t n = std::min(n_replicas, acc->T - acc->k);
+    if (n == 0) return RT_OK;
+    const int r = render_device_impl(acc->scene, &acc->camera, &p, acc->k, n, acc->d_sum, stream);
+    if (r == RT_OK) acc->k += n;
+    return r;
+}
+
+int rt_accum_render(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream) {
+    const int r = accum_render_impl(acc, n_replicas, params_or_null, stream);
+    if (acc && acc->scene->tail_flag) __atomic_store_n(acc->scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device does
+    return r;
+}
+
+uint32_t rt_accum_replicas_done(const RtAccum* acc) { return acc ? acc->k : 0; }
+
+// The estimate of sum_k into the device buffer d_out (stream: NULL = the scene's stream; returns after it is complete).
+static int accum_estimate_to(const RtAccum* acc, double* d_out, hipStream_t stream) {
+    using namespace rt;
+    const size_t n = acc->n_doubles();
+    if (acc->k == acc->T) {  // factor 1: the estimate is the frame, bit for bit
+        HIP_TRY(hipMemcpyAsync(d_out, acc->d_sum, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    } else {
+        hipLaunchKernelGGL(k_accum_estimate, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, acc->d_sum, uint64_t(n),
+                           double(acc->T) / double(acc->k), d_out);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
+static int accum_check_estimate(const RtAccum* acc, const void* out, const char* who) {
+    if (!acc || !out) return rt::set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
+    if (acc->k == 0) return rt::set_err(RT_E_INVALID, std::string(who) + ": no replica rendered yet (k = 0)");
+    return RT_OK;
+}
+
+int rt_accum_estimate_device(const RtAccum* acc, double* d_rgba_out, void* stream) {
+    using namespace rt;
+    if (int v = accum_check_estimate(acc, d_rgba_out, "rt_accum_estimate_device")) return v;
+    HIP_TRY(hipSetDevice(acc->device));
+    return accum_estimate_to(acc, d_rgba_out, stream ? static_cast<hipStream_t>(stream) : acc->scene->stream);
+}
+
+static int accum_scratch(RtAccum* a) {
+    using namespace rt;
+    if (!a->d_est) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_est), a->n_doubles() * sizeof(double)));
+    if (!a->d_rgb) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_rgb), a->n_doubles() / 4 * 3));
+    return RT_OK;
+}
+
+int rt_accum_estimate(const RtAccum* acc, double* rgba_out) {
+    using namespace rt;
+    if (int v = accum_check_estimate(acc, rgba_out, "rt_accum_estimate")) return v;
+    HIP_TRY(hipSetDevice(acc->device));
+    RtAccum* a = const_cast<RtAccum*>(acc);  // scratch buffers only
+    if (int st = accum_scratch(a)) return st;
+    if (int st = accum_estimate_to(a, a->d_est, a->scene->stream)) return st;
+    HIP_TRY(hipMemcpy(rgba_out, a->d_est, a->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_preview_rgb8(const RtAccum* acc, uint8_t* rgb_out) {
+    using namespace rt;
+    if (int v = accum_check_estimate(acc, rgb_out, "rt_accum_preview_rgb8")) return v;
+    HIP_TRY(hipSetDevice(acc->device));
+    RtAccum* a = const_cast<RtAccum*>(acc);
+    if (int st = accum_scratch(a)) return st;
+    const double scale = a->k == a->T ? 1.0 : double(a->T) / double(a->k);  // the estimate, formed inside the kernel
+    if (int st = tonemap_launch(a->d_sum, a->n_doubles() / 4, scale, a->d_rgb, a->scene->stream)) return st;
+    HIP_TRY(hipMemcpy(rgb_out, a->d_rgb, a->n_doubles() / 4 * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_tonemap_rgb8_device(int device, const double* d_rgba, uint32_t width, uint32_t height, uint8_t* d_rgb, void* stream) {
+    using namespace rt;
+    if (!d_rgba || !d_rgb) return set_err(RT_E_INVALID, "rt_tonemap_rgb8_device: NULL argument");
+    HIP_TRY(hipSetDevice(device));
+    return tonemap_launch(d_rgba, uint64_t(width) * height, 1.0, d_rgb, static_cast<hipStream_t>(stream));
+}
+
+size_t rt_accum_state_size(const RtAccum* acc) {
+    return acc ? sizeof(rt::AccumHeader) + acc->n_doubles() * sizeof(double) : 0;
+}
+
+int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
+    using namespace rt;
+    if (!acc || !buf) return set_err(RT_E_INVALID, "rt_accum_save_state: NULL argument");
+    if (size < rt_accum_state_size(acc)) return set_err(RT_E_INVALID, "rt_accum_save_state: buffer smaller than rt_accum_state_size");
+    AccumHeader h{};
+    std::memcpy(h.magic, kAccumMagic, 8);
+    h.version = kAccumVersion;
+    h.precision = acc->params.precision;
+    h.width = acc->camera.image_width;
+    h.owned_rows = acc->owned;
+    h.thread_count = acc->T;
+    h.replicas_done = acc->k;
+    h.scene_digest = acc->scene->content_digest;
+    h.frame_digest = acc->frame_digest;
+    HIP_TRY(hipSetDevice(acc->device));
+    HIP_TRY(hipMemcpy(static_cast<char*>(buf) + sizeof h, acc->d_sum, acc->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
+    std::memcpy(buf, &h, sizeof h);
+    return RT_OK;
+}
+
+int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size) {
+    using namespace rt;
+    if (!acc || !buf) return set_err(RT_E_INVALID, "rt_accum_load_state: NULL argument");
+    AccumHeader h;
+    if (size < sizeof h) return set_err(RT_E_INVALID, "rt_accum_load_state: state truncated (shorter than its header)");
+    std::memcpy(&h, buf, sizeof h);
+    auto bad = [](const std::string& what) { return set_err(RT_E_INVALID, "rt_accum_load_state: " + what); };
+    if (std::memcmp(h.magic, kAccumMagic, 8) != 0) return bad("not an accumulator state (wrong magic)");
+    if (h.version != kAccumVersion) return bad("state format version " + std::to_string(h.version) + ", expected " + std::to_string(kAccumVersion));
+    if (h.precision != acc->params.precision) return bad("precision mismatch (state " + std::to_string(h.precision) + ", accumulator " + std::to_string(acc->params.precision) + ")");
+    if (h.width != acc->camera.image_width || h.owned_rows != acc->owned)
+        return bad("image size mismatch (state " + std::to_string(h.width) + " x " + std::to_string(h.owned_rows) + " rows, accumulator " +
+                   std::to_string(acc->camera.image_width) + " x " + std::to_string(acc->owned) + ")");
+    if (h.thread_count != acc->T) return bad("thread_count mismatch (state " + std::to_string(h.thread_count) + ", accumulator " + std::to_string(acc->T) + ")");
+    if (h.replicas_done > h.thread_count) return bad("state claims more replicas than thread_count");
+    if (h.scene_digest != acc->scene->content_digest) return bad("scene mismatch (the state was rendered from another scene description)");
+    if (h.frame_digest != acc->frame_digest) return bad("camera / render parameter mismatch (seed, camera, depth, light bias, background or row partition)");
+    if (size != rt_accum_state_size(acc)) return bad("state truncated or oversized (" + std::to_string(size) + " bytes, expected " + std::to_string(rt_accum_state_size(acc)) + ")");
+    HIP_TRY(hipSetDevice(acc->device));
+    HIP_TRY(hipMemcpy(acc->d_sum, static_cast<const char*>(buf) + sizeof h, acc->n_doubles() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());  // the render kernels run on a non-blocking stream, not ordered against this copy
+    acc->k = h.replicas_done;
     return RT_OK;
 }
 

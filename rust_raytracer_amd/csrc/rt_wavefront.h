@@ -1379,14 +1379,18 @@ __global__ void k_wf_advance(WfCounters* ctr) {
 // ---------------------------------------------------------------------------------------------
 // Resolve: ordered sums.  sample_L is indexed by the sample number s = ((tid_local * S*S + st) * npix + pix).
 // acc[pix] += (sum_st L) / spp for every replica of the group, in replica order (camera.rs:229,247-253).
+// A render call covers the replicas [t_first, t_end) in groups: its first group starts from 0, or (load_sum, t_first > 0)
+// from the running sum of [0, t_first) in `sum` (4 doubles per pixel, the output layout); its last group writes the new
+// running sum there; the groups between carry it in `acc` (3 doubles per pixel, scratch).  `sum` may be read and written
+// by the same group (one call, one group): each pixel's values are loaded before they are stored.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_wf_resolve(const double* __restrict__ sample_L, double* __restrict__ acc, uint64_t npix,
-                                                    uint32_t strata, uint32_t n_replicas, double spp, int first_group,
-                                                    double* __restrict__ out, int last_group) {
+                                                    uint32_t strata, uint32_t n_replicas, double spp, int first_group, int load_sum,
+                                                    double* sum, int last_group) {
     uint64_t pix = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (pix >= npix) return;
     double a[3];
-    for (int k = 0; k < 3; k++) a[k] = first_group ? 0.0 : acc[3 * pix + k];
+    for (int k = 0; k < 3; k++) a[k] = !first_group ? acc[3 * pix + k] : (load_sum ? sum[4 * pix + k] : 0.0);
     for (uint32_t t = 0; t < n_replicas; t++) {
         double col[3] = {0.0, 0.0, 0.0};
         for (uint32_t st = 0; st < strata; st++) {
@@ -1398,10 +1402,10 @@ __global__ void __launch_bounds__(256) k_wf_resolve(const double* __restrict__ s
         for (int k = 0; k < 3; k++) a[k] += col[k] / spp;
     }
     if (last_group) {
-        out[4 * pix + 0] = a[0];
-        out[4 * pix + 1] = a[1];
-        out[4 * pix + 2] = a[2];
-        out[4 * pix + 3] = 0.0;
+        sum[4 * pix + 0] = a[0];
+        sum[4 * pix + 1] = a[1];
+        sum[4 * pix + 2] = a[2];
+        sum[4 * pix + 3] = 0.0;
     } else {
         for (int k = 0; k < 3; k++) acc[3 * pix + k] = a[k];
     }
