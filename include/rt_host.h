@@ -25,7 +25,7 @@ typedef struct RtHost RtHost;
 /* argv[0] is skipped like env::args().skip(1) (config.rs:81).  Flags are the
  * reference's (README.md:21-43) plus --seed=<u64>, --gpus=<n>,
  * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
- * --checkpoint=<file>, --time-limit=<seconds> (unknown keys are
+ * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations> (unknown keys are
  * ignored by the reference, config.rs:146, so these are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
  * the reference (main.rs:43, golden_monkey.rs:77). */
@@ -42,6 +42,10 @@ uint32_t rth_gpus(const RtHost* host);            /* --gpus, default 1 */
 uint32_t rth_progressive(const RtHost* host);
 const char* rth_checkpoint(const RtHost* host);
 double rth_time_limit(const RtHost* host);
+/* --denoise=<iterations> (1 .. RT_DENOISE_MAX_ITERATIONS; 0 = off): rtrace also writes out_denoised.png, the frame (or,
+ * with --progressive, the estimate after every pass) filtered by rt_denoise with its first-hit AOVs.  rth_load rejects
+ * --denoise with --gpus > 1. */
+uint32_t rth_denoise(const RtHost* host);
 uint32_t rth_samples_per_pixel(const RtHost* host); /* Camera::samples_per_pixel() */
 /* Row partition of `rtrace --gpus=N` (replaces the per-thread full-frame buffers of src/camera.rs:243-255): band height
  * for `height` image rows over `n_parts` GPUs = the largest of 16, 8, 4, 2, 1 rows that gives the most loaded part as few

@@ -348,6 +348,60 @@ int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size);
  * uncontracted; only pow may differ in its last bit.  Enqueued on `stream` (NULL = the null stream), returns after it. */
 int rt_tonemap_rgb8_device(int device, const double* d_rgba, uint32_t width, uint32_t height, uint8_t* d_rgb, void* stream);
 
+/* ---- First-hit AOVs and the edge-avoiding a-trous denoiser ---------------------------------------------------------
+ * AOV image: owned_rows x width x 8 doubles per pixel (the row partition of `params` is honoured):
+ *     albedo r g b, normal x y z, depth, coverage
+ * each the mean over the first n_replicas replicas' samples (n_replicas * S^2 per pixel).  Every sample is keyed and
+ * its camera ray built exactly as the render does it, the closest hit is found with the render's own traversal (volume
+ * draws included), and no bounce is traced.  Sums are taken per replica, then in replica order; no atomics.
+ *   Surface hit:  normal = the shading normal (world space, facing the ray, normal map applied: what NormalDebug shows),
+ *                 depth = |hit position - ray origin|, coverage = 1, albedo by material: Lambertian / Metal / Glossy /
+ *                 Isotropic: their colour texture; Dielectric: (1, 1, 1); Emissive: its emission on a front face, 0
+ *                 on a back face; NormalDebug: the colour it emits.
+ *   Environment:  a miss, a Sky hit or a Sun hit.  Albedo = what the frame shows there: the background colour for a
+ *                 miss (0 without one), the emission of the Sky / Sun; normal, depth and coverage = 0.
+ * n_replicas must be in 1 .. thread_count (else RT_E_INVALID).  Neither call changes rt_get_stats or the tail flag.   */
+int rt_render_aov(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
+                  double* aov_out);
+int rt_render_aov_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
+                         double* d_aov_out, void* stream);  /* HBM output on the scene's device; stream NULL = the scene's */
+
+/* Edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) of an RGBA f64 image guided by its AOV image, both w x h.
+ * Iteration i = 0 .. iterations-1 filters with the 5 x 5 B3-spline taps (1,4,6,4,1)/16 spaced 2^i pixels apart; taps
+ * outside the image are skipped.  Tap weight (f32): h * w_c * w_n * w_a * w_z with
+ *     w_c = exp(-|c_q - c_p|^2 / (sigma_color^2 * 2^-i))      (1 when the centre colour is not finite)
+ *     w_n = exp(-|n_q - n_p|^2 / sigma_normal^2)      w_a = exp(-|a_q - a_p|^2 / sigma_albedo^2)
+ *     w_z = exp(-|z_q - z_p| / (sigma_depth * max(z_p, z_q) + 1e-30))
+ * The weighted colour and weight sums are f64.  A tap whose colour is not finite, or whose weight is not positive,
+ * contributes nothing; a pixel without a contributing tap keeps its value.  With RT_DENOISE_DEMODULATE the colour is
+ * divided by the albedo (per channel, where albedo > 1e-3) before the first iteration and multiplied by it after the
+ * last.  The guides are packed once per call into f32.  w (alpha) passes through.  iterations = 0: an exact copy.    */
+#define RT_DENOISE_DEMODULATE 1u
+#define RT_DENOISE_MAX_ITERATIONS 16u
+typedef struct RtDenoiseParams {
+    uint32_t iterations;          /* 0 .. RT_DENOISE_MAX_ITERATIONS                                                  */
+    uint32_t aov_replicas;        /* rt_accum_*_denoised: replicas of the AOV pass the accumulator caches (1 .. T)  */
+    uint32_t flags;               /* RT_DENOISE_*                                                                    */
+    uint32_t _reserved0;
+    double   sigma_color, sigma_normal, sigma_albedo, sigma_depth;  /* > 0 */
+    double   _reserved[4];        /* zero */
+} RtDenoiseParams;
+/* Fills in the defaults. */
+int rt_denoise_default_params(RtDenoiseParams* out);
+/* Host buffers: rgba w*h*4 doubles, aov w*h*8 doubles (rt_render_aov), out w*h*4 doubles (may be rgba).  dp NULL = the
+ * defaults.  Runs on device `device`.                                                                                  */
+int rt_denoise(int device, const double* rgba, const double* aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp,
+               double* rgba_out);
+/* The same on HBM buffers of device `device`, enqueued on `stream` (NULL = the null stream); returns after it.        */
+int rt_denoise_device(int device, const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h,
+                      const RtDenoiseParams* dp, double* d_rgba_out, void* stream);
+/* The accumulator's estimate, denoised (host copy), and the same tone-mapped on the device by rt_tonemap_rgb8_device
+ * (3 B per pixel).  On first use the accumulator renders its AOVs with dp->aov_replicas replicas and keeps them until
+ * rt_accum_destroy (a call with another aov_replicas renders them again).  The AOVs are not part of the state blob.
+ * An accumulator with a row partition is RT_E_INVALID: the filter needs contiguous rows.                             */
+int rt_accum_estimate_denoised(const RtAccum* acc, const RtDenoiseParams* dp, double* rgba_out);
+int rt_accum_preview_denoised_rgb8(const RtAccum* acc, const RtDenoiseParams* dp, uint8_t* rgb_out);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

@@ -22,6 +22,9 @@ RT_E_INVALID, RT_E_UNSUPPORTED, RT_E_DEVICE, RT_E_NOMEM = -1, -2, -3, -4
 RT_PRECISION_F64, RT_PRECISION_F32 = 0, 1
 RT_PIPELINE_AUTO, RT_PIPELINE_MEGAKERNEL, RT_PIPELINE_WAVEFRONT = 0, 1, 2
 RT_SCENE_BVH_ON_DEVICE = 1  # RtSceneDesc.flags
+RT_DENOISE_DEMODULATE = 1  # RtDenoiseParams.flags
+RT_DENOISE_MAX_ITERATIONS = 16
+AOV_CHANNELS = 8  # rt_render_aov: albedo rgb, normal xyz, depth, coverage
 
 (RT_NODE_SPHERE, RT_NODE_PLANE, RT_NODE_MESH, RT_NODE_LIST, RT_NODE_TRANSFORM, RT_NODE_BVH,
  RT_NODE_SKY, RT_NODE_SUN, RT_NODE_VOLUME, RT_NODE_NULL) = range(1, 11)
@@ -119,6 +122,21 @@ class RtRenderStats(C.Structure):
 
     def as_dict(self) -> dict:
         return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+class RtDenoiseParams(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("aov_replicas", C.c_uint32), ("flags", C.c_uint32),
+                ("_reserved0", C.c_uint32), ("sigma_color", C.c_double), ("sigma_normal", C.c_double),
+                ("sigma_albedo", C.c_double), ("sigma_depth", C.c_double), ("_reserved", C.c_double * 4)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "RtDenoiseParams":
+        """rt_denoise_default_params, then the given fields."""
+        dp = cls()
+        load_device_lib().rt_denoise_default_params(C.byref(dp))
+        for name, value in overrides.items():
+            setattr(dp, name, value)
+        return dp
 
 
 class RtError(RuntimeError):
@@ -234,6 +252,20 @@ def load_device_lib() -> C.CDLL:
                     ("rt_accum_save_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
                     ("rt_accum_load_state", C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
                     ("rt_tonemap_rgb8_device", C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
+        if hasattr(lib, "rt_render_aov"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            dp = C.POINTER(RtDenoiseParams)
+            for name, res, args in (
+                    ("rt_render_aov", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), C.c_uint32, C.c_void_p]),
+                    ("rt_render_aov_device", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), C.c_uint32,
+                                                       C.c_void_p, C.c_void_p]),
+                    ("rt_denoise_default_params", C.c_int, [dp]),
+                    ("rt_denoise", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, dp, C.c_void_p]),
+                    ("rt_denoise_device", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, dp, C.c_void_p, C.c_void_p]),
+                    ("rt_accum_estimate_denoised", C.c_int, [C.c_void_p, dp, C.c_void_p]),
+                    ("rt_accum_preview_denoised_rgb8", C.c_int, [C.c_void_p, dp, C.c_void_p])):
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
@@ -361,6 +393,36 @@ def tonemap_rgb8_device(d_rgba: int, width: int, height: int, d_rgb: int, device
         raise RtError(st, lib.rt_last_error().decode())
 
 
+def _dp_ref(dp: Optional[RtDenoiseParams]):
+    return C.byref(dp) if dp is not None else None
+
+
+def denoise(rgba: np.ndarray, aov: np.ndarray, dp: Optional[RtDenoiseParams] = None, device: int = 0) -> np.ndarray:
+    """rt_denoise: the (H, W, 4) f64 image filtered on the GPU, guided by its (H, W, 8) AOV image (DeviceScene.render_aov);
+    dp None = the defaults."""
+    lib = load_device_lib()
+    rgba = np.ascontiguousarray(rgba, dtype=np.float64)
+    aov = np.ascontiguousarray(aov, dtype=np.float64)
+    h, w = rgba.shape[:2]
+    if rgba.shape != (h, w, 4) or aov.shape != (h, w, AOV_CHANNELS):
+        raise ValueError(f"denoise: expected (H, W, 4) and (H, W, {AOV_CHANNELS}) arrays, got {rgba.shape} and {aov.shape}")
+    out = np.empty_like(rgba)
+    st = lib.rt_denoise(device, rgba.ctypes.data, aov.ctypes.data, w, h, _dp_ref(dp), out.ctypes.data)
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return out
+
+
+def denoise_device(d_rgba: int, d_aov: int, width: int, height: int, d_out: int, dp: Optional[RtDenoiseParams] = None,
+                   device: int = 0, stream: int = 0) -> None:
+    """rt_denoise_device: the same on device pointers (d_out may be d_rgba); returns when the output is written."""
+    lib = load_device_lib()
+    st = lib.rt_denoise_device(device, C.c_void_p(d_rgba), C.c_void_p(d_aov), width, height, _dp_ref(dp), C.c_void_p(d_out),
+                               C.c_void_p(stream))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+
+
 def save_png(path: str, rgba: np.ndarray) -> None:
     lib = load_host_lib()
     rgba = np.ascontiguousarray(rgba, dtype=np.float64)
@@ -408,6 +470,24 @@ class DeviceScene:
     def render_device(self, camera: RtCameraDesc, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
         st = self._lib.rt_render_device(self._h, C.byref(camera), C.byref(params),
                                         C.c_void_p(d_out_ptr), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def render_aov(self, camera: RtCameraDesc, params: RtRenderParams, n_replicas: Optional[int] = None) -> np.ndarray:
+        """rt_render_aov: (owned rows, W, 8) first-hit albedo rgb, normal xyz, depth, coverage over the first n_replicas
+        replicas (None = all thread_count of them)."""
+        n = params.thread_count if n_replicas is None else n_replicas
+        rows = self._lib.rt_owned_rows(camera.image_height, C.byref(params))
+        out = np.empty((rows, camera.image_width, AOV_CHANNELS), dtype=np.float64)
+        st = self._lib.rt_render_aov(self._h, C.byref(camera), C.byref(params), n, out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out
+
+    def render_aov_device(self, camera: RtCameraDesc, params: RtRenderParams, d_out_ptr: int, n_replicas: Optional[int] = None,
+                          stream: int = 0) -> None:
+        n = params.thread_count if n_replicas is None else n_replicas
+        st = self._lib.rt_render_aov_device(self._h, C.byref(camera), C.byref(params), n, C.c_void_p(d_out_ptr), C.c_void_p(stream))
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
 
@@ -491,6 +571,17 @@ class ProgressiveRender:
     def preview_rgb8(self) -> np.ndarray:
         out = np.empty((self.rows, self.camera.image_width, 3), dtype=np.uint8)
         self._check(self._lib.rt_accum_preview_rgb8(self._h, out.ctypes.data))
+        return out
+
+    def estimate_denoised(self, dp: Optional[RtDenoiseParams] = None) -> np.ndarray:
+        """The estimate through rt_denoise, guided by AOVs the accumulator renders on first use (dp.aov_replicas)."""
+        out = np.empty((self.rows, self.camera.image_width, 4), dtype=np.float64)
+        self._check(self._lib.rt_accum_estimate_denoised(self._h, _dp_ref(dp), out.ctypes.data))
+        return out
+
+    def preview_rgb8_denoised(self, dp: Optional[RtDenoiseParams] = None) -> np.ndarray:
+        out = np.empty((self.rows, self.camera.image_width, 3), dtype=np.uint8)
+        self._check(self._lib.rt_accum_preview_denoised_rgb8(self._h, _dp_ref(dp), out.ctypes.data))
         return out
 
     def save_state(self) -> bytes:

@@ -190,6 +190,12 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             if (!need_f64("Time limit")) return false;
             if (!(d >= 0.0)) { *err = "Time limit must be a number of seconds >= 0"; return false; }
             cfg.time_limit = d;
+        } else if (key == "-denoise") {  // new: also write out_denoised.png (first-hit AOVs + a-trous filter)
+            if (!parse_usize(value, &u) || u == 0 || u > RT_DENOISE_MAX_ITERATIONS) {
+                *err = "Denoise iterations must be an integer from 1 to " + std::to_string(RT_DENOISE_MAX_ITERATIONS);
+                return false;
+            }
+            cfg.denoise = uint32_t(u);
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -203,6 +209,10 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
     }
     if (cfg.progressive && cfg.gpus > 1) {
         *err = "--progressive renders on one GPU: it cannot be combined with --gpus > 1";
+        return false;
+    }
+    if (cfg.denoise && cfg.gpus > 1) {
+        *err = "--denoise filters the whole frame on one GPU: it cannot be combined with --gpus > 1";
         return false;
     }
     if (cfg.thread_count == 0) {

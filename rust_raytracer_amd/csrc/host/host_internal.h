@@ -37,6 +37,7 @@ struct Config {
     uint32_t progressive = 0;    // --progressive=<n>: passes of n replicas (0: one-shot render)
     std::string checkpoint;      // --checkpoint=<file>: state saved after every pass, resumed from at start-up
     double time_limit = -1.0;    // --time-limit=<seconds>: stop after the first pass that ends past it (< 0: none)
+    uint32_t denoise = 0;        // --denoise=<iterations>: also write out_denoised.png (0: off)
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176
 

@@ -5,11 +5,14 @@
 //
 // New, optional flags (ignored by the reference's parser, so command lines stay compatible):
 //   --seed=<u64>  --gpus=<n>  --precision=f64|f32  --pipeline=auto|mega|wavefront  --bvh=host|device
-//   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>
+//   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 // With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
 // the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
 // --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
 // --time-limit stops after the first pass that ends past the limit (measured from the start of the process).
+// --denoise=n also writes out_denoised.png: the frame (with --progressive: the estimate after every pass, and the final
+// frame) through the a-trous filter of rt_denoise with n iterations, guided by first-hit AOVs of one replica.  out.png
+// and the console lines are those of a run without the flag.
 // With --gpus=n the frame is row-tiled in interleaved bands (rth_band_rows: 16 rows, or finer when that balances the GPUs), one
 // host thread per GPU; the tiles are assembled on the host here (bench.py shows the RCCL gather path used for the
 // multi-process launch).  RT_RTRACE_ONE_DEVICE=1 (tests on a one-GPU box): every part renders on device 0.
@@ -48,12 +51,22 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
     const uint32_t W = cam->image_width, H = cam->image_height, T = params->thread_count, n = rth_progressive(host);
     const std::string ckpt = rth_checkpoint(host);
     const double limit = rth_time_limit(host);
+    RtDenoiseParams dp;
+    rt_denoise_default_params(&dp);
+    dp.iterations = rth_denoise(host);
+    std::vector<uint8_t> rgb_dn(dp.iterations ? size_t(W) * H * 3 : 0);
     RtScene* scene = nullptr;
     RtAccum* acc = nullptr;
     if (rt_scene_create(rth_scene(host), 0, &scene) != RT_OK) return fail(rt_last_error());
     std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
     if (rt_accum_create(scene, cam, params, &acc) != RT_OK) return fail(rt_last_error());
     std::unique_ptr<RtAccum, void (*)(RtAccum*)> acc_guard(acc, rt_accum_destroy);
+    auto save_denoised = [&]() -> bool {  // out_denoised.png from the accumulator's current estimate
+        if (!dp.iterations) return true;
+        if (rt_accum_preview_denoised_rgb8(acc, &dp, rgb_dn.data()) != RT_OK) { fail(rt_last_error()); return false; }
+        if (rth_save_png_rgb8("out_denoised.png", rgb_dn.data(), W, H) != RT_OK) { fail(rth_last_error()); return false; }
+        return true;
+    };
     std::vector<char> state(rt_accum_state_size(acc));
     if (!ckpt.empty()) {
         std::ifstream in(ckpt, std::ios::binary);
@@ -84,6 +97,7 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
         if (k == T) break;  // the final image goes through the host output stage below
         if (rt_accum_preview_rgb8(acc, rgb.data()) != RT_OK) return fail(rt_last_error());
         if (rth_save_png_rgb8("out.png", rgb.data(), W, H) != RT_OK) return fail(rth_last_error());
+        if (!save_denoised()) return 1;
         if (limit >= 0.0 && since() > limit) {
             std::printf("Stopped at %u/%u replicas\n", k, T);
             return 0;
@@ -93,6 +107,7 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
     if (rt_accum_estimate(acc, frame.data()) != RT_OK) return fail(rt_last_error());  // k = T: the frame itself
     std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());
     if (rth_save_png("out.png", frame.data(), W, H) != RT_OK) return fail(rth_last_error());
+    if (!save_denoised()) return 1;
     std::printf("Done! Took %s. Goodbye :)\n", fmt_duration(since()).c_str());
     return 0;
 }
@@ -133,6 +148,8 @@ int main(int argc, char** argv) {
     const uint32_t W = cam->image_width, H = cam->image_height;
     const uint32_t band = gpus > 1 ? rth_band_rows(H, gpus) : 16;  // interleaved row bands
     std::vector<double> frame(size_t(W) * H * 4, 0.0);  // camera.create_buffer(), main.rs:74
+    const uint32_t denoise = rth_denoise(host);         // one GPU (rth_load refuses --denoise with --gpus > 1)
+    std::vector<double> denoised(denoise ? frame.size() : 0);
     std::vector<std::string> errors(gpus);
     std::vector<std::thread> workers;
     for (uint32_t g = 0; g < gpus; g++) {
@@ -151,8 +168,8 @@ int main(int argc, char** argv) {
             }
             uint32_t rows = rt_owned_rows(H, &p);
             std::vector<double> part(size_t(rows) * W * 4);
+            std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
             if (rows && rt_render(scene, cam, &p, part.data()) != RT_OK) errors[g] = rt_last_error();
-            rt_scene_destroy(scene);
             if (!errors[g].empty()) return;
             uint32_t r = 0;
             for (uint32_t y = 0; y < H; y++) {
@@ -164,6 +181,15 @@ int main(int argc, char** argv) {
             // the reference prints one line per render thread (camera.rs:236); here: one per GPU
             std::printf("GPU %u finished in %s\n", g, fmt_duration(std::chrono::duration<double>(clock::now() - tg).count()).c_str());
             std::fflush(stdout);
+            if (denoise) {  // the whole frame: gpus == 1
+                RtDenoiseParams dp;
+                rt_denoise_default_params(&dp);
+                dp.iterations = denoise;
+                std::vector<double> aov(size_t(W) * H * 8);
+                if (rt_render_aov(scene, cam, &p, dp.aov_replicas, aov.data()) != RT_OK ||
+                    rt_denoise(rehearsal ? 0 : int(g), frame.data(), aov.data(), W, H, &dp, denoised.data()) != RT_OK)
+                    errors[g] = rt_last_error();
+            }
         });
     }
     for (auto& t : workers) t.join();
@@ -174,6 +200,10 @@ int main(int argc, char** argv) {
         }
     std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());  // main.rs:78
     if (rth_save_png("out.png", frame.data(), W, H) != RT_OK) {                           // main.rs:23,80-82
+        std::fprintf(stderr, "Error: %s\n", rth_last_error());
+        return 1;
+    }
+    if (denoise && rth_save_png("out_denoised.png", denoised.data(), W, H) != RT_OK) {
         std::fprintf(stderr, "Error: %s\n", rth_last_error());
         return 1;
     }

@@ -1028,6 +1028,13 @@ template <typename R, bool FULL> RT_DEV V3<R> lights_random(const SceneView<R>& 
     return light_random(sc, l, origin, rng);
 }
 
+// Packed owned row r -> image row y (RtRenderParams row partition).
+template <typename R> RT_DEV uint32_t row_to_y(const ParamsView<R>& prm, uint32_t r) {
+    if (prm.band_rows == 0 || prm.n_parts <= 1) return r;
+    uint32_t band = r / prm.band_rows;
+    return (band * prm.n_parts + prm.part) * prm.band_rows + (r % prm.band_rows);
+}
+
 // ------------------------------------------------------------------ camera.rs:260-280, 334-349
 template <typename R>
 RT_DEV void camera_ray(const CameraView<R>& cam, uint32_t px, uint32_t py, uint32_t sx, uint32_t sy, Rng& rng, V3<R>& origin_out, V3<R>& dir_out) {

@@ -13,18 +13,12 @@
 #include <type_traits>
 #include <vector>
 
+#include "rt_aov.h"
 #include "rt_compile.h"
 #include "rt_device.h"
 #include "rt_wavefront.h"
 
 namespace rt {
-
-// Packed owned row r -> image row y (RtRenderParams row partition).
-template <typename R> RT_DEV uint32_t row_to_y(const ParamsView<R>& prm, uint32_t r) {
-    if (prm.band_rows == 0 || prm.n_parts <= 1) return r;
-    uint32_t band = r / prm.band_rows;
-    return (band * prm.n_parts + prm.part) * prm.band_rows + (r % prm.band_rows);
-}
 
 // ---------------------------------------------------------------------------------------------
 // Megakernel: one lane owns one pixel and walks its samples in the reference's order
@@ -661,6 +655,18 @@ int render_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const 
     return RT_OK;
 }
 
+// First-hit AOVs of the replicas [0, n) (rt_aov.hip): same tables, views and kernel variant as render_typed, but no
+// counters, events or stats, so rt_get_stats still reports the last render.
+template <typename R>
+int aov_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned, uint32_t n,
+              double* d_out, hipStream_t stream) {
+    if (size_t(ds.view.stack_entries) * 256 * sizeof(int) > 160 * 1024) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the LDS traversal stack");
+    const bool tex = s->compiled.needs_tex_interpreter || !s->compiled.volumes.empty();
+    HIP_TRY(aov_launch<R>(ds.view, make_camera_view<R>(cam, p), make_params_view<R>(p, owned), tex, n, d_out, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return RT_OK;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Wavefront pipeline driver
 // ---------------------------------------------------------------------------------------------
@@ -1294,6 +1300,9 @@ struct RtAccum {
     double* d_sum = nullptr;       // sum_k, owned x width x 4 doubles: the accumulator's own buffer
     double* d_est = nullptr;       // estimate scratch (lazy)
     uint8_t* d_rgb = nullptr;      // preview scratch (lazy)
+    double* d_aov = nullptr;       // first-hit AOVs of the denoised previews (lazy, owned x width x 8; not in the state blob)
+    uint32_t aov_replicas = 0;     // replicas d_aov was rendered with (0: none yet)
+    rt::DenoiseScratch dn;         // denoiser scratch (lazy)
     size_t n_doubles() const { return size_t(owned) * camera.image_width * 4; }
 };
 
@@ -1593,6 +1602,8 @@ void rt_accum_destroy(RtAccum* acc) {
     if (acc->d_sum) (void)hipFree(acc->d_sum);
     if (acc->d_est) (void)hipFree(acc->d_est);
     if (acc->d_rgb) (void)hipFree(acc->d_rgb);
+    if (acc->d_aov) (void)hipFree(acc->d_aov);
+    rt::denoise_scratch_release(acc->dn);
     delete acc;
 }
 
@@ -1733,6 +1744,160 @@ int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size) {
     HIP_TRY(hipMemcpy(acc->d_sum, static_cast<const char*>(buf) + sizeof h, acc->n_doubles() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipDeviceSynchronize());  // the render kernels run on a non-blocking stream, not ordered against this copy
     acc->k = h.replicas_done;
+    return RT_OK;
+}
+
+// ---- First-hit AOVs and the denoiser (rt_aov.hip) ----------------------------------------------------------------
+static int render_aov_impl(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
+                           double* d_out, void* stream) {
+    using namespace rt;
+    if (!scene || !camera || !params || !d_out) return set_err(RT_E_INVALID, "rt_render_aov: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    if (n_replicas == 0 || n_replicas > params->thread_count) return set_err(RT_E_INVALID, "rt_render_aov: n_replicas must be in 1 .. thread_count");
+    RtScene* s = const_cast<RtScene*>(scene);  // lazily built tables only
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t owned = owned_rows(camera->image_height, params);
+    if (owned == 0) return RT_OK;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    if (params->precision == RT_PRECISION_F32) {
+        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
+        return aov_typed<float>(s, *s->f32, *camera, *params, owned, n_replicas, d_out, st);
+    }
+    if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
+    return aov_typed<double>(s, *s->f64, *camera, *params, owned, n_replicas, d_out, st);
+}
+
+int rt_render_aov_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
+                         double* d_aov_out, void* stream) {
+    return render_aov_impl(scene, camera, params, n_replicas, d_aov_out, stream);
+}
+
+int rt_render_aov(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
+                  double* aov_out) {
+    using namespace rt;
+    if (!scene || !camera || !params || !aov_out) return set_err(RT_E_INVALID, "rt_render_aov: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    HIP_TRY(hipSetDevice(scene->device));
+    const size_t bytes = size_t(owned_rows(camera->image_height, params)) * camera->image_width * kAovChannels * sizeof(double);
+    if (bytes == 0) return render_aov_impl(scene, camera, params, n_replicas, aov_out, nullptr);  // argument checks only
+    double* d_out = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), bytes));
+    int st = render_aov_impl(scene, camera, params, n_replicas, d_out, nullptr);
+    if (st == RT_OK) {
+        const hipError_t e = hipMemcpy(aov_out, d_out, bytes, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_out);
+    return st;
+}
+
+int rt_denoise_default_params(RtDenoiseParams* out) {
+    if (!out) return rt::set_err(RT_E_INVALID, "rt_denoise_default_params: NULL argument");
+    *out = RtDenoiseParams{};
+    out->iterations = 4;  // tuned on 1-replica estimates against the full frame
+    out->aov_replicas = 1;
+    out->flags = RT_DENOISE_DEMODULATE;
+    out->sigma_color = 8.0;
+    out->sigma_normal = 0.3;
+    out->sigma_albedo = 0.3;
+    out->sigma_depth = 0.1;
+    return RT_OK;
+}
+
+// dp (NULL = the defaults) -> *out, checked.
+static int denoise_params(const RtDenoiseParams* dp, RtDenoiseParams* out, const char* who) {
+    if (dp) *out = *dp;
+    else rt_denoise_default_params(out);
+    if (out->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return rt::set_err(RT_E_INVALID, std::string(who) + ": iterations must be at most " + std::to_string(RT_DENOISE_MAX_ITERATIONS));
+    for (double sg : {out->sigma_color, out->sigma_normal, out->sigma_albedo, out->sigma_depth})
+        if (!(sg > 0.0) || !std::isfinite(sg) || !std::isfinite(float(sg)) || !(float(sg) > 0.0f))
+            return rt::set_err(RT_E_INVALID, std::string(who) + ": every sigma must be a positive, finite f32 number");
+    return RT_OK;
+}
+
+// Runs the filter on HBM buffers of the current device and waits for it; scratch: the caller's, or (NULL) one of its own.
+static int denoise_run(const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams& dp,
+                       double* d_out, rt::DenoiseScratch* scratch, hipStream_t stream) {
+    using namespace rt;
+    DenoiseScratch own;
+    DenoiseScratch& scr = scratch ? *scratch : own;
+    hipError_t e = dp.iterations ? denoise_scratch_reserve(scr, size_t(w) * h) : hipSuccess;
+    if (e == hipSuccess) e = denoise_launch(d_rgba, d_aov, w, h, dp, d_out, scr, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    denoise_scratch_release(own);
+    if (e == hipErrorOutOfMemory) return set_err(RT_E_NOMEM, "denoiser scratch does not fit in device memory");
+    if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("denoise: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
+int rt_denoise_device(int device, const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp,
+                      double* d_rgba_out, void* stream) {
+    using namespace rt;
+    if (!d_rgba || !d_aov || !d_rgba_out) return set_err(RT_E_INVALID, "rt_denoise_device: NULL argument");
+    RtDenoiseParams p;
+    if (int v = denoise_params(dp, &p, "rt_denoise_device")) return v;
+    HIP_TRY(hipSetDevice(device));
+    return denoise_run(d_rgba, d_aov, w, h, p, d_rgba_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise(int device, const double* rgba, const double* aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp, double* rgba_out) {
+    using namespace rt;
+    if (!rgba || !aov || !rgba_out) return set_err(RT_E_INVALID, "rt_denoise: NULL argument");
+    RtDenoiseParams p;
+    if (int v = denoise_params(dp, &p, "rt_denoise")) return v;
+    const size_t npix = size_t(w) * h;
+    if (npix == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(device));
+    DeviceBuffers buf;
+    auto alloc = [&](size_t bytes, double** out) -> int { HIP_TRY(hipMalloc(reinterpret_cast<void**>(out), bytes)); buf.allocs.push_back(*out); return RT_OK; };
+    double *d_rgba = nullptr, *d_aov = nullptr;
+    if (int st = alloc(npix * 4 * sizeof(double), &d_rgba)) return st;
+    if (int st = alloc(npix * kAovChannels * sizeof(double), &d_aov)) return st;
+    HIP_TRY(hipMemcpy(d_rgba, rgba, npix * 4 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov, aov, npix * kAovChannels * sizeof(double), hipMemcpyHostToDevice));
+    if (int st = denoise_run(d_rgba, d_aov, w, h, p, d_rgba, nullptr, nullptr)) return st;  // in place
+    HIP_TRY(hipMemcpy(rgba_out, d_rgba, npix * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// The denoised estimate of `a` into a->d_est (scene's stream, complete on return).  Renders the AOVs on first use.
+static int accum_denoise(RtAccum* a, const RtDenoiseParams* dp, const char* who) {
+    using namespace rt;
+    RtDenoiseParams p;
+    if (int v = denoise_params(dp, &p, who)) return v;
+    if (a->params.band_rows != 0 && a->params.n_parts > 1)
+        return set_err(RT_E_INVALID, std::string(who) + ": the accumulator has a row partition (the filter needs contiguous rows)");
+    if (p.aov_replicas == 0 || p.aov_replicas > a->T) return set_err(RT_E_INVALID, std::string(who) + ": aov_replicas must be in 1 .. thread_count");
+    HIP_TRY(hipSetDevice(a->device));
+    if (int st = accum_scratch(a)) return st;
+    const uint32_t w = a->camera.image_width;
+    if (a->aov_replicas != p.aov_replicas) {
+        if (!a->d_aov) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_aov), size_t(a->owned) * w * kAovChannels * sizeof(double)));
+        a->aov_replicas = 0;
+        if (int st = render_aov_impl(a->scene, &a->camera, &a->params, p.aov_replicas, a->d_aov, nullptr)) return st;
+        a->aov_replicas = p.aov_replicas;
+    }
+    if (int st = accum_estimate_to(a, a->d_est, a->scene->stream)) return st;
+    return denoise_run(a->d_est, a->d_aov, w, a->owned, p, a->d_est, &a->dn, a->scene->stream);
+}
+
+int rt_accum_estimate_denoised(const RtAccum* acc, const RtDenoiseParams* dp, double* rgba_out) {
+    using namespace rt;
+    if (int v = accum_check_estimate(acc, rgba_out, "rt_accum_estimate_denoised")) return v;
+    RtAccum* a = const_cast<RtAccum*>(acc);  // scratch buffers and the AOV cache only
+    if (int st = accum_denoise(a, dp, "rt_accum_estimate_denoised")) return st;
+    HIP_TRY(hipMemcpy(rgba_out, a->d_est, a->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_preview_denoised_rgb8(const RtAccum* acc, const RtDenoiseParams* dp, uint8_t* rgb_out) {
+    using namespace rt;
+    if (int v = accum_check_estimate(acc, rgb_out, "rt_accum_preview_denoised_rgb8")) return v;
+    RtAccum* a = const_cast<RtAccum*>(acc);
+    if (int st = accum_denoise(a, dp, "rt_accum_preview_denoised_rgb8")) return st;
+    if (int st = tonemap_launch(a->d_est, a->n_doubles() / 4, 1.0, a->d_rgb, a->scene->stream)) return st;
+    HIP_TRY(hipMemcpy(rgb_out, a->d_rgb, a->n_doubles() / 4 * 3, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
