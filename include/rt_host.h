@@ -25,7 +25,8 @@ typedef struct RtHost RtHost;
 /* argv[0] is skipped like env::args().skip(1) (config.rs:81).  Flags are the
  * reference's (README.md:21-43) plus --seed=<u64>, --gpus=<n>,
  * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
- * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations> (unknown keys are
+ * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations>, --noise-threshold=<x>,
+ * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r> (unknown keys are
  * ignored by the reference, config.rs:146, so these are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
  * the reference (main.rs:43, golden_monkey.rs:77). */
@@ -46,6 +47,14 @@ double rth_time_limit(const RtHost* host);
  * with --progressive, the estimate after every pass) filtered by rt_denoise with its first-hit AOVs.  rth_load rejects
  * --denoise with --gpus > 1. */
 uint32_t rth_denoise(const RtHost* host);
+/* Adaptive sampling (rt_accum_set_adaptive): --noise-threshold=<x> (> 0; 0 = off) turns it on and implies passes (of
+ * --progressive=<n> replicas if given, else of check_interval); --adaptive-min=<k> (>= 2), --adaptive-check=<m> (>= 1),
+ * --adaptive-radius=<r> (0 .. 4): -1 = not given, the library's default.  rth_load rejects values outside these ranges,
+ * the three without --noise-threshold, and --noise-threshold with --gpus > 1 or --pipeline=mega. */
+double rth_noise_threshold(const RtHost* host);
+int32_t rth_adaptive_min(const RtHost* host);
+int32_t rth_adaptive_check(const RtHost* host);
+int32_t rth_adaptive_radius(const RtHost* host);
 uint32_t rth_samples_per_pixel(const RtHost* host); /* Camera::samples_per_pixel() */
 /* Row partition of `rtrace --gpus=N` (replaces the per-thread full-frame buffers of src/camera.rs:243-255): band height
  * for `height` image rows over `n_parts` GPUs = the largest of 16, 8, 4, 2, 1 rows that gives the most loaded part as few

@@ -327,7 +327,8 @@ void rt_accum_destroy(RtAccum* acc);
 /* Renders the next n_replicas replicas (clamped to T - k; 0 is a no-op).  params_or_null may change pipeline and
  * collect_stats for this call only; any other difference from the creation params is RT_E_INVALID.  rt_get_stats then
  * reports this call (samples = npix * S^2 * n), and the scene's tail flag (rt_scene_set_tail_flag) is set as by
- * rt_render_device, the call's last replica group being its tail.  On an error k is unchanged.                       */
+ * rt_render_device, the call's last replica group being its tail.  On an error k is unchanged.  (An adaptive
+ * accumulator, see "Adaptive sampling" below, renders only its active pixels and reports the samples it rendered.)    */
 int rt_accum_render(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream);
 uint32_t rt_accum_replicas_done(const RtAccum* acc);
 int rt_accum_estimate(const RtAccum* acc, double* rgba_out);                           /* host copy of the estimate  */
@@ -401,6 +402,49 @@ int rt_denoise_device(int device, const double* d_rgba, const double* d_aov, uin
  * An accumulator with a row partition is RT_E_INVALID: the filter needs contiguous rows.                             */
 int rt_accum_estimate_denoised(const RtAccum* acc, const RtDenoiseParams* dp, double* rgba_out);
 int rt_accum_preview_denoised_rgb8(const RtAccum* acc, const RtDenoiseParams* dp, uint8_t* rgb_out);
+
+/* ---- Adaptive sampling: stop converged pixels of a progressive render -----------------------
+ * An accumulator that opts in keeps, beside sum[p], the moments s1[p], s2[p] (f64) of the luminance of its per-replica
+ * contributions and n[p] (u32), the replicas in sum[p].  When replica t is added to pixel p, with c the three values the
+ * resolve step adds to sum[p] (unchanged):  y = double(T) * ((0.2126 c_r + 0.7152 c_g) + 0.0722 c_b),  s1 += y,  s2 += y y,
+ * n += 1, in replica order, f64, uncontracted.
+ * Decision points D = { k : min_replicas <= k < T, (k - min_replicas) mod check_interval = 0 }.  When the replica count k
+ * reaches one, for every active pixel (all have n = k):
+ *     mean = s1 / k;  num = max(s2 - s1 mean, 0);  se2 = num / (double(k) double(k - 1));  lim = threshold (mean + floor);
+ *     quiet = se2 <= lim lim          (false when anything is NaN: a pixel whose sums hold a NaN never stops)
+ * and a pixel STOPS iff it is quiet and every ACTIVE pixel with |dx|, |dy| <= radius inside the image is quiet too.  A
+ * stopped pixel never restarts and does not hold its neighbours.  Decisions depend on the sums alone, so the state does not
+ * depend on how the replicas are split into calls (rt_accum_render splits its range at decision points itself), on replica
+ * groups, pool size, tail compaction or a save / load in between.  For every pixel sum[p] is, bit for bit, the sum of a
+ * plain accumulator after n[p] replicas, n[p] in D or = T; without a decision point (min_replicas >= T) the final frame is
+ * rt_render's.  Estimate: sum[p] * (double(T) / double(n[p])).  The frame is finished when k = T or no pixel is active;
+ * rt_accum_render then renders nothing and returns RT_OK.  rt_get_stats().samples counts what the call really rendered.
+ * Adaptive passes run the wavefront scheduler: RT_PIPELINE_MEGAKERNEL or collect_stats in a render call, and max_depth = 0,
+ * are RT_E_UNSUPPORTED; a row partition is RT_E_INVALID (the window needs contiguous rows).  On an error inside a call the
+ * accumulator keeps the segments (up to a decision point each) that were completed.                                    */
+typedef struct RtAdaptiveParams {
+    double   threshold;           /* > 0: relative standard error of the luminance at which a pixel is quiet; no default */
+    double   floor;               /* > 0: added to the mean, so that dark pixels can converge                          */
+    uint32_t min_replicas;        /* >= 2: first decision point                                                         */
+    uint32_t check_interval;      /* >= 1: replicas between decision points                                             */
+    uint32_t radius;              /* 0 .. 4: half width of the window                                                   */
+    uint32_t _reserved0;
+    double   _reserved[4];        /* zero */
+} RtAdaptiveParams;
+/* floor 0.01, min_replicas 4, check_interval 2, radius 1; threshold 0: it must be set by the caller. */
+int rt_adaptive_default_params(RtAdaptiveParams* out);
+/* Opts in.  Only while no replica has been rendered and no state loaded (else RT_E_INVALID). */
+int rt_accum_set_adaptive(RtAccum* acc, const RtAdaptiveParams* params);
+uint32_t rt_accum_active_pixels(const RtAccum* acc);   /* plain accumulator: all pixels while k < T, then 0 */
+int rt_accum_finished(const RtAccum* acc);             /* 1: k = T or no active pixel */
+/* n[p], owned_rows * width values on the host (a plain accumulator: k everywhere). */
+int rt_accum_sample_counts(const RtAccum* acc, uint32_t* counts_out);
+/* Noise image sqrt(se2) / (mean + floor) per pixel at its n (0 while n < 2); adaptive accumulators only. */
+int rt_accum_noise(const RtAccum* acc, double* noise_out);
+/* State blob of an adaptive accumulator: format version 2 = the 48-byte header with version 2, 32 bytes of parameters
+ * (threshold, floor as f64; min_replicas, check_interval, radius, 0 as u32), then sum (4 f64), s1, s2 (f64) and n (u32)
+ * per pixel, array after array.  A plain accumulator still writes version 1.  rt_accum_load_state refuses a version-1
+ * blob for an adaptive accumulator, a version-2 blob for a plain one, and parameters that differ.                     */
 
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);

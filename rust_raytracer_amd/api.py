@@ -139,6 +139,21 @@ class RtDenoiseParams(C.Structure):
         return dp
 
 
+class RtAdaptiveParams(C.Structure):
+    _fields_ = [("threshold", C.c_double), ("floor", C.c_double), ("min_replicas", C.c_uint32),
+                ("check_interval", C.c_uint32), ("radius", C.c_uint32), ("_reserved0", C.c_uint32),
+                ("_reserved", C.c_double * 4)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "RtAdaptiveParams":
+        """rt_adaptive_default_params, then the given fields (`threshold` has no default and must be given)."""
+        ap = cls()
+        load_device_lib().rt_adaptive_default_params(C.byref(ap))
+        for name, value in overrides.items():
+            setattr(ap, name, value)
+        return ap
+
+
 class RtError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"rt status {status}: {message}")
@@ -266,6 +281,17 @@ def load_device_lib() -> C.CDLL:
                     ("rt_denoise_device", C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, dp, C.c_void_p, C.c_void_p]),
                     ("rt_accum_estimate_denoised", C.c_int, [C.c_void_p, dp, C.c_void_p]),
                     ("rt_accum_preview_denoised_rgb8", C.c_int, [C.c_void_p, dp, C.c_void_p])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
+        if hasattr(lib, "rt_accum_set_adaptive"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            for name, res, args in (
+                    ("rt_adaptive_default_params", C.c_int, [C.POINTER(RtAdaptiveParams)]),
+                    ("rt_accum_set_adaptive", C.c_int, [C.c_void_p, C.POINTER(RtAdaptiveParams)]),
+                    ("rt_accum_active_pixels", C.c_uint32, [C.c_void_p]),
+                    ("rt_accum_finished", C.c_int, [C.c_void_p]),
+                    ("rt_accum_sample_counts", C.c_int, [C.c_void_p, C.c_void_p]),
+                    ("rt_accum_noise", C.c_int, [C.c_void_p, C.c_void_p])):
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
@@ -524,9 +550,14 @@ class ProgressiveRender:
     """A frame rendered in passes of replicas (rt_accum_*, include/rt_mi355.h): after every pass `estimate()` is the
     frame's expected value from the replicas so far, and once all `thread_count` replicas are done it IS the frame
     DeviceScene.render returns, bit for bit, however the passes were split.  `save_state()` / `load_state()` carry the
-    sums to another process (same scene description, camera and params)."""
+    sums to another process (same scene description, camera and params).
 
-    def __init__(self, scene: DeviceScene, camera: RtCameraDesc, params: RtRenderParams):
+    `adaptive` (RtAdaptiveParams) opts into adaptive sampling (rt_accum_set_adaptive): pixels whose noise estimate, and
+    that of their neighbourhood, has fallen below the threshold stop receiving replicas; `sample_counts()` tells how
+    many each pixel got and `estimate()` scales every pixel by its own count."""
+
+    def __init__(self, scene: DeviceScene, camera: RtCameraDesc, params: RtRenderParams,
+                 adaptive: Optional[RtAdaptiveParams] = None):
         lib = load_device_lib()
         handle = C.c_void_p()
         st = lib.rt_accum_create(scene._h, C.byref(camera), C.byref(params), C.byref(handle))
@@ -539,6 +570,14 @@ class ProgressiveRender:
         self.params = params.copy()
         self.rows = lib.rt_owned_rows(camera.image_height, C.byref(params))
         self.total = params.thread_count
+        self.adaptive = None
+        if adaptive is not None:
+            st = lib.rt_accum_set_adaptive(handle, C.byref(adaptive))
+            if st != RT_OK:
+                msg = lib.rt_last_error().decode()
+                self.close()
+                raise RtError(st, msg)
+            self.adaptive = RtAdaptiveParams.from_buffer_copy(adaptive)
 
     def _check(self, st: int) -> None:
         if st != RT_OK:
@@ -559,6 +598,28 @@ class ProgressiveRender:
     @property
     def replicas_done(self) -> int:
         return int(self._lib.rt_accum_replicas_done(self._h))
+
+    @property
+    def active_pixels(self) -> int:
+        """Pixels that still receive replicas (0 once the frame is finished)."""
+        return int(self._lib.rt_accum_active_pixels(self._h))
+
+    @property
+    def finished(self) -> bool:
+        """All replicas done, or (adaptive) every pixel has stopped: render() renders nothing any more."""
+        return bool(self._lib.rt_accum_finished(self._h))
+
+    def sample_counts(self) -> np.ndarray:
+        """Replicas in each pixel's sum (uint32, rows x width)."""
+        out = np.empty((self.rows, self.camera.image_width), dtype=np.uint32)
+        self._check(self._lib.rt_accum_sample_counts(self._h, out.ctypes.data))
+        return out
+
+    def noise(self) -> np.ndarray:
+        """Relative standard error of each pixel's luminance at its replica count (adaptive accumulators only)."""
+        out = np.empty((self.rows, self.camera.image_width), dtype=np.float64)
+        self._check(self._lib.rt_accum_noise(self._h, out.ctypes.data))
+        return out
 
     def estimate(self) -> np.ndarray:
         out = np.empty((self.rows, self.camera.image_width, 4), dtype=np.float64)

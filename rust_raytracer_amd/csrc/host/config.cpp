@@ -196,10 +196,35 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
                 return false;
             }
             cfg.denoise = uint32_t(u);
+        } else if (key == "-noise-threshold") {  // new: adaptive sampling (rt_accum_set_adaptive)
+            if (!parse_f64(value, &d) || !(d > 0.0) || !std::isfinite(d)) { *err = "Noise threshold must be a number > 0"; return false; }
+            cfg.noise_threshold = d;
+        } else if (key == "-adaptive-min") {  // new
+            if (!parse_usize(value, &u) || u < 2 || u > 0x7FFFFFFFu) { *err = "Adaptive minimum must be an integer >= 2 (replicas before the first decision)"; return false; }
+            cfg.adaptive_min = int32_t(u);
+        } else if (key == "-adaptive-check") {  // new
+            if (!parse_usize(value, &u) || u < 1 || u > 0x7FFFFFFFu) { *err = "Adaptive check interval must be a positive integer (replicas between decisions)"; return false; }
+            cfg.adaptive_check = int32_t(u);
+        } else if (key == "-adaptive-radius") {  // new
+            if (!parse_usize(value, &u) || u > 4) { *err = "Adaptive radius must be an integer from 0 to 4"; return false; }
+            cfg.adaptive_radius = int32_t(u);
         }
         // unknown keys: ignored (config.rs:146)
     }
-    if (!cfg.checkpoint.empty() && cfg.progressive == 0) {
+    const bool adaptive = cfg.noise_threshold > 0.0;
+    if (!adaptive && (cfg.adaptive_min >= 0 || cfg.adaptive_check >= 0 || cfg.adaptive_radius >= 0)) {
+        *err = "--adaptive-min, --adaptive-check and --adaptive-radius require --noise-threshold=<x>";
+        return false;
+    }
+    if (adaptive && cfg.gpus > 1) {
+        *err = "--noise-threshold renders on one GPU: it cannot be combined with --gpus > 1";
+        return false;
+    }
+    if (adaptive && cfg.pipeline == RT_PIPELINE_MEGAKERNEL) {
+        *err = "--noise-threshold runs the wavefront scheduler: it cannot be combined with --pipeline=mega";
+        return false;
+    }
+    if (!cfg.checkpoint.empty() && cfg.progressive == 0 && !adaptive) {
         *err = "--checkpoint requires --progressive=<n>";
         return false;
     }

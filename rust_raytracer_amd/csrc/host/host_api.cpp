@@ -80,6 +80,10 @@ uint32_t rth_progressive(const RtHost* host) { return host->config.progressive; 
 const char* rth_checkpoint(const RtHost* host) { return host->config.checkpoint.c_str(); }
 double rth_time_limit(const RtHost* host) { return host->config.time_limit; }
 uint32_t rth_denoise(const RtHost* host) { return host->config.denoise; }
+double rth_noise_threshold(const RtHost* host) { return host->config.noise_threshold; }
+int32_t rth_adaptive_min(const RtHost* host) { return host->config.adaptive_min; }
+int32_t rth_adaptive_check(const RtHost* host) { return host->config.adaptive_check; }
+int32_t rth_adaptive_radius(const RtHost* host) { return host->config.adaptive_radius; }
 uint32_t rth_band_rows(uint32_t height, uint32_t n_parts) {
     if (n_parts <= 1) return 0;
     uint32_t band = 16, best_rows = 0xFFFFFFFFu;

@@ -38,6 +38,10 @@ struct Config {
     std::string checkpoint;      // --checkpoint=<file>: state saved after every pass, resumed from at start-up
     double time_limit = -1.0;    // --time-limit=<seconds>: stop after the first pass that ends past it (< 0: none)
     uint32_t denoise = 0;        // --denoise=<iterations>: also write out_denoised.png (0: off)
+    double noise_threshold = 0.0;  // --noise-threshold=<x>: adaptive sampling (rt_accum_set_adaptive; 0: off)
+    int32_t adaptive_min = -1;     // --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>: -1 = the library's default
+    int32_t adaptive_check = -1;
+    int32_t adaptive_radius = -1;
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176
 

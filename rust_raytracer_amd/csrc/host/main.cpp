@@ -6,6 +6,7 @@
 // New, optional flags (ignored by the reference's parser, so command lines stay compatible):
 //   --seed=<u64>  --gpus=<n>  --precision=f64|f32  --pipeline=auto|mega|wavefront  --bvh=host|device
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
+//   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 // With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
 // the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
 // --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
@@ -13,6 +14,10 @@
 // --denoise=n also writes out_denoised.png: the frame (with --progressive: the estimate after every pass, and the final
 // frame) through the a-trous filter of rt_denoise with n iterations, guided by first-hit AOVs of one replica.  out.png
 // and the console lines are those of a run without the flag.
+// --noise-threshold=x turns adaptive sampling on (rt_accum_set_adaptive): the frame is rendered in passes (of --progressive
+// replicas, else of the check interval) until every pixel has converged or all replicas are done; out.png is the final
+// estimate, out_samples.png shows each pixel's share n / T of the replicas in grey, and one more console line gives the
+// samples rendered and the pixels stopped.  Works with --checkpoint, --time-limit and --denoise.
 // With --gpus=n the frame is row-tiled in interleaved bands (rth_band_rows: 16 rows, or finer when that balances the GPUs), one
 // host thread per GPU; the tiles are assembled on the host here (bench.py shows the RCCL gather path used for the
 // multi-process launch).  RT_RTRACE_ONE_DEVICE=1 (tests on a one-GPU box): every part renders on device 0.
@@ -48,7 +53,17 @@ static int fail(const char* msg) {
 static int render_progressive(RtHost* host, const std::function<double()>& since) {
     const RtCameraDesc* cam = rth_camera(host);
     const RtRenderParams* params = rth_params(host);
-    const uint32_t W = cam->image_width, H = cam->image_height, T = params->thread_count, n = rth_progressive(host);
+    const uint32_t W = cam->image_width, H = cam->image_height, T = params->thread_count;
+    const bool adaptive = rth_noise_threshold(host) > 0.0;
+    RtAdaptiveParams ap;
+    rt_adaptive_default_params(&ap);
+    if (adaptive) {
+        ap.threshold = rth_noise_threshold(host);
+        if (rth_adaptive_min(host) >= 0) ap.min_replicas = uint32_t(rth_adaptive_min(host));
+        if (rth_adaptive_check(host) >= 0) ap.check_interval = uint32_t(rth_adaptive_check(host));
+        if (rth_adaptive_radius(host) >= 0) ap.radius = uint32_t(rth_adaptive_radius(host));
+    }
+    const uint32_t n = rth_progressive(host) ? rth_progressive(host) : ap.check_interval;
     const std::string ckpt = rth_checkpoint(host);
     const double limit = rth_time_limit(host);
     RtDenoiseParams dp;
@@ -61,6 +76,7 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
     std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
     if (rt_accum_create(scene, cam, params, &acc) != RT_OK) return fail(rt_last_error());
     std::unique_ptr<RtAccum, void (*)(RtAccum*)> acc_guard(acc, rt_accum_destroy);
+    if (adaptive && rt_accum_set_adaptive(acc, &ap) != RT_OK) return fail(rt_last_error());
     auto save_denoised = [&]() -> bool {  // out_denoised.png from the accumulator's current estimate
         if (!dp.iterations) return true;
         if (rt_accum_preview_denoised_rgb8(acc, &dp, rgb_dn.data()) != RT_OK) { fail(rt_last_error()); return false; }
@@ -87,14 +103,14 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
         return true;
     };
     std::vector<uint8_t> rgb(size_t(W) * H * 3);
-    for (uint32_t pass = 1; rt_accum_replicas_done(acc) < T; pass++) {
+    for (uint32_t pass = 1; !rt_accum_finished(acc); pass++) {
         const double ts = since();
         if (rt_accum_render(acc, n, nullptr, nullptr) != RT_OK) return fail(rt_last_error());
         const uint32_t k = rt_accum_replicas_done(acc);
         std::printf("Pass %u: %u/%u replicas in %s\n", pass, k, T, fmt_duration(since() - ts).c_str());
         std::fflush(stdout);
         if (!save()) return 1;
-        if (k == T) break;  // the final image goes through the host output stage below
+        if (rt_accum_finished(acc)) break;  // the final image goes through the host output stage below
         if (rt_accum_preview_rgb8(acc, rgb.data()) != RT_OK) return fail(rt_last_error());
         if (rth_save_png_rgb8("out.png", rgb.data(), W, H) != RT_OK) return fail(rth_last_error());
         if (!save_denoised()) return 1;
@@ -107,6 +123,21 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
     if (rt_accum_estimate(acc, frame.data()) != RT_OK) return fail(rt_last_error());  // k = T: the frame itself
     std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());
     if (rth_save_png("out.png", frame.data(), W, H) != RT_OK) return fail(rth_last_error());
+    if (adaptive) {  // where the samples went: n / T in grey
+        std::vector<uint32_t> counts(size_t(W) * H);
+        if (rt_accum_sample_counts(acc, counts.data()) != RT_OK) return fail(rt_last_error());
+        unsigned long long replicas = 0, stopped = 0;
+        for (size_t i = 0; i < counts.size(); i++) {
+            replicas += counts[i];
+            stopped += counts[i] < T ? 1u : 0u;
+            const uint8_t g = uint8_t(double(counts[i]) / double(T) * 255.0 + 0.5);
+            rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = g;
+        }
+        if (rth_save_png_rgb8("out_samples.png", rgb.data(), W, H) != RT_OK) return fail(rth_last_error());
+        const unsigned long long per_replica = rth_samples_per_pixel(host) / T;  // S^2
+        std::printf("Adaptive: %llu/%llu samples rendered, %llu/%llu pixels stopped\n", replicas * per_replica,
+                    (unsigned long long)counts.size() * T * per_replica, stopped, (unsigned long long)counts.size());
+    }
     if (!save_denoised()) return 1;
     std::printf("Done! Took %s. Goodbye :)\n", fmt_duration(since()).c_str());
     return 0;
@@ -137,7 +168,7 @@ int main(int argc, char** argv) {
         std::fprintf(stderr, "Error: no HIP device (the render path has no CPU fallback)\n");
         return 1;
     }
-    if (rth_progressive(host)) {
+    if (rth_progressive(host) || rth_noise_threshold(host) > 0.0) {
         const int rc = render_progressive(host, since);
         rth_destroy(host);
         return rc;

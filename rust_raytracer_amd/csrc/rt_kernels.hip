@@ -761,12 +761,26 @@ int wf_ensure(RtScene* s, uint32_t capacity) {
     return RT_OK;
 }
 
+// One segment of an adaptive accumulator's render (rt_accum_render): the resolve step goes through
+// k_wf_resolve_moments; sparse: the replica groups cover the n_active pixels of `active` instead of the frame.
+struct AdaptivePass {
+    const uint32_t* active = nullptr;
+    uint32_t n_active = 0;
+    bool sparse = false;
+    double *s1 = nullptr, *s2 = nullptr;
+    uint32_t* cnt = nullptr;
+};
+
 template <typename R>
 int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
-                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream) {
+                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr) {
     CameraView<R> cv = make_camera_view<R>(cam, p);
     ParamsView<R> pv = make_params_view<R>(p, owned);
-    const uint64_t npix = uint64_t(cam.image_width) * owned;
+    const uint64_t npix_frame = uint64_t(cam.image_width) * owned;
+    const bool sparse = ad && ad->sparse;
+    const uint64_t npix = sparse ? uint64_t(ad->n_active) : npix_frame;  // pixels a replica group covers
+    if (ad && p.collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
+    if (npix == 0) return set_err(RT_E_INVALID, "adaptive pass without active pixels");
     const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
     const uint32_t T = p.thread_count;
     const uint32_t t_end = t_first + n;
@@ -783,13 +797,13 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // Sized from the whole frame (T replicas), not from this call's n: progressive passes of any size keep the same pool.
     uint32_t capacity;
     {
-        const double total_samples = double(per_replica) * double(T);
+        const double total_samples = double(strata) * double(npix_frame) * double(T);  // the frame's, also for a sparse pass: one pool for all passes
         double c = 134217728.0 * std::sqrt(total_samples / 1.44e9);
         c = std::fmin(std::fmax(c, 1048576.0), 134217728.0);
         capacity = env_u32("RT_WF_POOL", uint32_t(c) & ~0xFFFFFu);
     }
     if (capacity > (1u << 28)) capacity = 1u << 28;  // the kernels address pool arrays through 32-bit byte offsets (rt_wavefront.h, at())
-    if (uint64_t(capacity) > per_replica * T) capacity = uint32_t(per_replica * T);
+    if (uint64_t(capacity) > uint64_t(strata) * npix_frame * T) capacity = uint32_t(uint64_t(strata) * npix_frame * T);
     if (capacity < 64) capacity = 64;
     // the pool is a matter of speed, not of correctness: when device memory is short (other scenes of a frame pipeline, other
     // processes on the card) a smaller one renders the same frame
@@ -822,7 +836,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.sample_L), need));
         w.sample_L_bytes = need;
     }
-    const bool multi_group = group < n;
+    const bool multi_group = group < n && !ad;  // adaptive: every group resolves into the accumulator's sums
     if (multi_group && w.acc_bytes < npix * 24) {
         if (w.acc) (void)hipFree(w.acc);
         w.acc = nullptr;
@@ -936,6 +950,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         grp.inv_width = 1.0 / double(cam.image_width);
         grp.tid0 = t0;
         grp.strata = strata;
+        WfGroupSparse<R> grp_s{};
+        static_cast<WfGroup<R>&>(grp_s) = grp;
+        grp_s.active = sparse ? ad->active : nullptr;
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
         uint32_t first = uint32_t(std::min<uint64_t>(capacity, grp.total));
         pool = pool_a;
@@ -950,7 +967,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         init.next_sample = first;
         *w.h_ctr = init;
         HIP_TRY(hipMemcpyAsync(w.d_ctr, w.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-        hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, w.queue[0]);
+        if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, w.queue[0]);
+        else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, w.queue[0]);
         int qi = 0;
         uint32_t upper = first;  // upper bound of the queue length (never grows: slots are reused in place)
 #define RT_LAUNCH_PRIMS(ST, L, VL, GR) hipLaunchKernelGGL((k_wf_prims<R, ST, L, VL, GR>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_prims) : size_t(0)) + (GR ? lds_groups : size_t(0)) + (WF_CHUNK + 4) * 4, stream, ds.view, pool, w.queue[qi], w.mesh_queue, w.d_ctr, s->d_counters, staged_prims, group_levels)
@@ -990,12 +1008,21 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 #undef RT_LAUNCH_ISECT
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 }
-#define RT_LAUNCH_SHADE(ST, L, TX) hipLaunchKernelGGL((k_wf_shade<R, ST, L, TX>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_shade) : size_t(0)) + kShadeListBytes + shade_lds_pad, stream, ds.view, cv, pv, pool, grp, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters, static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade)
-                if (tex) {  // interpreter variant: tables from global memory (rare scenes, fewer instantiations)
+#define RT_LAUNCH_SHADE_G(ST, L, TX, G, GRP) hipLaunchKernelGGL((k_wf_shade<R, ST, L, TX, G>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_shade) : size_t(0)) + kShadeListBytes + shade_lds_pad, stream, ds.view, cv, pv, pool, GRP, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters, static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade)
+#define RT_LAUNCH_SHADE(ST, L, TX) RT_LAUNCH_SHADE_G(ST, L, TX, WfGroup<R>, grp)
+#define RT_LAUNCH_SHADE_SPARSE(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupSparse<R>, grp_s)
+                if (sparse) {  // restarts through the active list (no counting variants)
+                    if (tex) RT_LAUNCH_SHADE_SPARSE(0, true);
+                    else if (lds_shade == 1) RT_LAUNCH_SHADE_SPARSE(1, false);
+                    else if (lds_shade == 2) RT_LAUNCH_SHADE_SPARSE(2, false);
+                    else RT_LAUNCH_SHADE_SPARSE(0, false);
+                } else if (tex) {  // interpreter variant: tables from global memory (rare scenes, fewer instantiations)
                     if (stats) RT_LAUNCH_SHADE(true, 0, true); else RT_LAUNCH_SHADE(false, 0, true);
                 } else if (stats) { if (lds_shade == 1) RT_LAUNCH_SHADE(true, 1, false); else if (lds_shade == 2) RT_LAUNCH_SHADE(true, 2, false); else RT_LAUNCH_SHADE(true, 0, false); }
                 else { if (lds_shade == 1) RT_LAUNCH_SHADE(false, 1, false); else if (lds_shade == 2) RT_LAUNCH_SHADE(false, 2, false); else RT_LAUNCH_SHADE(false, 0, false); }
+#undef RT_LAUNCH_SHADE_SPARSE
 #undef RT_LAUNCH_SHADE
+#undef RT_LAUNCH_SHADE_G
                 hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr);
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 qi ^= 1;
@@ -1058,8 +1085,14 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 #undef RT_LAUNCH_MESH
 #undef RT_LAUNCH_MESH_V
 #undef RT_LAUNCH_MESH_M
-        hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L, w.acc, npix, strata, nrep,
-                           pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
+        if (ad) {
+            const dim3 rgrid(uint32_t((npix + 255) / 256));
+            if (sparse) hipLaunchKernelGGL(k_wf_resolve_moments<true>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
+            else hipLaunchKernelGGL(k_wf_resolve_moments<false>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
+        } else {
+            hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L, w.acc, npix, strata, nrep,
+                               pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
+        }
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, stream));
@@ -1279,6 +1312,13 @@ struct AccumHeader {
 static_assert(sizeof(AccumHeader) == 48, "state header layout");
 static const char kAccumMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
 static const uint32_t kAccumVersion = 1;
+static const uint32_t kAccumVersionAdaptive = 2;  // header, AdaptiveBlobParams, sum, s1, s2, n
+struct AdaptiveBlobParams {
+    double threshold, floor;
+    uint32_t min_replicas, check_interval, radius, zero;
+};
+static_assert(sizeof(AdaptiveBlobParams) == 32, "state parameter block layout");
+static AdaptiveBlobParams blob_params(const RtAdaptiveParams& p) { return AdaptiveBlobParams{p.threshold, p.floor, p.min_replicas, p.check_interval, p.radius, 0u}; }
 
 static int tonemap_launch(const double* d_rgba, uint64_t npix, double scale, uint8_t* d_rgb, hipStream_t stream) {
     if (npix == 0) return RT_OK;
@@ -1303,7 +1343,20 @@ struct RtAccum {
     double* d_aov = nullptr;       // first-hit AOVs of the denoised previews (lazy, owned x width x 8; not in the state blob)
     uint32_t aov_replicas = 0;     // replicas d_aov was rendered with (0: none yet)
     rt::DenoiseScratch dn;         // denoiser scratch (lazy)
+    // adaptive mode (rt_accum_set_adaptive): moments, replica counts, the ascending list of active pixels (two buffers that
+    // take turns at a compaction) and the decision step's scratch
+    bool adaptive = false, touched = false;  // touched: a state has been loaded
+    RtAdaptiveParams ap{};
+    double *d_s1 = nullptr, *d_s2 = nullptr;
+    uint32_t* d_cnt = nullptr;
+    uint32_t* d_active[2] = {nullptr, nullptr};
+    int cur = 0;
+    uint32_t n_active = 0;
+    uint8_t *d_state = nullptr, *d_keep = nullptr;
+    uint32_t *d_block = nullptr, *d_n_out = nullptr;
     size_t n_doubles() const { return size_t(owned) * camera.image_width * 4; }
+    size_t npix() const { return size_t(owned) * camera.image_width; }
+    bool decision_point(uint32_t kk) const { return adaptive && kk >= ap.min_replicas && kk < T && (kk - ap.min_replicas) % ap.check_interval == 0; }
 };
 
 extern "C" {
@@ -1378,7 +1431,7 @@ uint32_t rt_owned_rows(uint32_t image_height, const RtRenderParams* params) {
 // Renders the replicas [t_first, t_first + n) of the frame into d_rgba_out (running sum of [0, t_first) on entry):
 // rt_render_device is [0, T), rt_accum_render the next n of an accumulator.
 static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
-                              uint32_t t_first, uint32_t n, double* d_rgba_out, void* stream) {
+                              uint32_t t_first, uint32_t n, double* d_rgba_out, void* stream, const rt::AdaptivePass* ad = nullptr) {
     using namespace rt;
     if (!scene || !camera || !params || !d_rgba_out) return set_err(RT_E_INVALID, "rt_render_device: NULL argument");
     if (int v = validate_render_args(camera, params)) return v;
@@ -1394,6 +1447,12 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
     bool wavefront = params->pipeline == RT_PIPELINE_WAVEFRONT ||
                      (params->pipeline == RT_PIPELINE_AUTO && (has_mesh || env_u32("RT_AUTO_MEGA_NO_MESH", 0) == 0));
     if (params->max_depth == 0) wavefront = false;  // every sample is black (camera.rs:290): nothing to schedule
+    if (ad) {  // adaptive passes exist in the wavefront scheduler only
+        if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "adaptive passes run the wavefront scheduler: RT_PIPELINE_MEGAKERNEL is not supported");
+        if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, "adaptive sampling with max_depth = 0");
+        if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
+        wavefront = true;
+    }
     if (params->precision == RT_PRECISION_F32) {
         if (!s->f32) {
             auto ds = std::make_unique<DeviceScene<float>>();
@@ -1401,7 +1460,7 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
             if (r != RT_OK) return r;
             s->f32 = std::move(ds);
         }
-        if (wavefront) return render_wavefront<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st);
+        if (wavefront) return render_wavefront<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st, ad);
         return render_typed<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st);
     }
     if (!s->f64) {
@@ -1410,7 +1469,7 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
         if (r != RT_OK) return r;
         s->f64 = std::move(ds);
     }
-    if (wavefront) return render_wavefront<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st);
+    if (wavefront) return render_wavefront<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st, ad);
     return render_typed<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st);
 }
 
@@ -1603,8 +1662,97 @@ void rt_accum_destroy(RtAccum* acc) {
     if (acc->d_est) (void)hipFree(acc->d_est);
     if (acc->d_rgb) (void)hipFree(acc->d_rgb);
     if (acc->d_aov) (void)hipFree(acc->d_aov);
+    for (void* q : {(void*)acc->d_s1, (void*)acc->d_s2, (void*)acc->d_cnt, (void*)acc->d_active[0], (void*)acc->d_active[1], (void*)acc->d_state,
+                    (void*)acc->d_keep, (void*)acc->d_block, (void*)acc->d_n_out})
+        if (q) (void)hipFree(q);
     rt::denoise_scratch_release(acc->dn);
     delete acc;
+}
+
+// Scan + scatter of the decision step: entries of `src` (n_src of them) with keep != 0 go, in order, to the other list, which
+// becomes the active list; 4 bytes come back to the host.
+static int adaptive_compact(RtAccum* a, const uint32_t* src, uint32_t n_src, hipStream_t st) {
+    using namespace rt;
+    const uint32_t n_blocks = (n_src + AD_CHUNK - 1) / AD_CHUNK;
+    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(64), 0, st, a->d_block, n_blocks, a->d_n_out);
+    hipLaunchKernelGGL(k_ad_scatter, dim3(n_blocks), dim3(256), 0, st, src, n_src, a->d_keep, a->d_block, a->d_active[a->cur ^ 1], a->d_state);
+    HIP_TRY(hipGetLastError());
+    uint32_t n_new = 0;
+    HIP_TRY(hipMemcpyAsync(&n_new, a->d_n_out, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_new > n_src) return set_err(RT_E_DEVICE, "adaptive compaction returned more pixels than it was given");
+    a->cur ^= 1;
+    a->n_active = n_new;
+    return RT_OK;
+}
+
+// The decision at k = acc->k (a decision point): quiet flags, window rule, compaction of the active list.
+static int adaptive_decide(RtAccum* a, hipStream_t st) {
+    using namespace rt;
+    if (a->n_active == 0) return RT_OK;
+    const uint32_t n = a->n_active, n_blocks = (n + AD_CHUNK - 1) / AD_CHUNK;
+    const uint32_t* list = a->d_active[a->cur];
+    hipLaunchKernelGGL(k_ad_quiet, dim3((n + 255) / 256), dim3(256), 0, st, list, n, a->d_s1, a->d_s2, a->k, a->ap.threshold, a->ap.floor, a->d_state);
+    hipLaunchKernelGGL(k_ad_window, dim3(n_blocks), dim3(256), 0, st, list, n, a->d_state, a->camera.image_width, a->owned, int(a->ap.radius), a->d_keep, a->d_block);
+    return adaptive_compact(a, list, n, st);
+}
+
+// Active list from the counts (after a state load): n[p] == k, then the decision at k again if k is a decision point - it sees
+// the sums it saw before the save, so it stops the same pixels.
+static int adaptive_rebuild(RtAccum* a, hipStream_t st) {
+    using namespace rt;
+    const uint32_t n = uint32_t(a->npix()), n_blocks = (n + AD_CHUNK - 1) / AD_CHUNK;
+    hipLaunchKernelGGL(k_ad_flags_from_counts, dim3(n_blocks), dim3(256), 0, st, a->d_cnt, n, a->k, a->d_active[a->cur], a->d_keep, a->d_state, a->d_block);
+    if (int r = adaptive_compact(a, a->d_active[a->cur], n, st)) return r;
+    if (a->decision_point(a->k)) return adaptive_decide(a, st);
+    return RT_OK;
+}
+
+static void stats_add(RtRenderStats& total, const RtRenderStats& part, bool first) {
+    if (first) { total = part; return; }
+    total.kernel_ms += part.kernel_ms; total.traversal_kernel_ms += part.traversal_kernel_ms;
+    total.prims_kernel_ms += part.prims_kernel_ms; total.shade_kernel_ms += part.shade_kernel_ms;
+    total.n_launches += part.n_launches; total.n_iterations += part.n_iterations; total.samples += part.samples;
+    total.n_replica_groups += part.n_replica_groups; total.n_tail_compactions += part.n_tail_compactions;
+}
+
+// rt_accum_render of an adaptive accumulator: segments that end at the decision points, a decision after each.
+static int accum_render_adaptive(RtAccum* acc, uint32_t n_replicas, RtRenderParams p, void* stream) {
+    using namespace rt;
+    if (p.pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "rt_accum_render: adaptive passes run the wavefront scheduler, RT_PIPELINE_MEGAKERNEL is not supported");
+    if (p.collect_stats) return set_err(RT_E_UNSUPPORTED, "rt_accum_render: collect_stats is not supported on an adaptive accumulator");
+    p.pipeline = RT_PIPELINE_WAVEFRONT;
+    RtScene* s = acc->scene;
+    HIP_TRY(hipSetDevice(acc->device));
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    uint32_t left = std::min(n_replicas, acc->T - acc->k);
+    RtRenderStats total{};
+    bool first = true;
+    int32_t* const flag = s->tail_flag;  // the call's end releases a waiting frame (rt_accum_render), not a segment's
+    s->tail_flag = nullptr;
+    int r = RT_OK;
+    while (left > 0 && acc->n_active > 0) {
+        uint32_t next = acc->T;
+        if (acc->k < acc->ap.min_replicas) next = std::min(acc->T, acc->ap.min_replicas);
+        else if (acc->k < acc->T) next = uint32_t(std::min<uint64_t>(acc->T, uint64_t(acc->k) + acc->ap.check_interval - (acc->k - acc->ap.min_replicas) % acc->ap.check_interval));
+        const uint32_t m = std::min(left, next - acc->k);
+        AdaptivePass ad;
+        ad.active = acc->d_active[acc->cur];
+        ad.n_active = acc->n_active;
+        ad.sparse = acc->n_active < acc->npix();
+        ad.s1 = acc->d_s1; ad.s2 = acc->d_s2; ad.cnt = acc->d_cnt;
+        r = render_device_impl(s, &acc->camera, &p, acc->k, m, acc->d_sum, st, &ad);
+        if (r != RT_OK) break;
+        stats_add(total, s->stats, first);
+        first = false;
+        acc->k += m;
+        left -= m;
+        if (acc->decision_point(acc->k) && (r = adaptive_decide(acc, st)) != RT_OK) break;
+    }
+    s->tail_flag = flag;
+    if (!first) s->stats = total;
+    else if (r == RT_OK) { s->stats = RtRenderStats{}; s->stats.pipeline_used = RT_PIPELINE_WAVEFRONT; }  // nothing rendered
+    return r;
 }
 
 static int accum_render_impl(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream) {
@@ -1618,6 +1766,7 @@ static int accum_render_impl(RtAccum* acc, uint32_t n_replicas, const RtRenderPa
         p.pipeline = params_or_null->pipeline;
         p.collect_stats = params_or_null->collect_stats;
     }
+    if (acc->adaptive) return accum_render_adaptive(acc, n_replicas, p, stream);
     const uint32_t n = std::min(n_replicas, acc->T - acc->k);
     if (n == 0) return RT_OK;
     const int r = render_device_impl(acc->scene, &acc->camera, &p, acc->k, n, acc->d_sum, stream);
@@ -1637,7 +1786,11 @@ uint32_t rt_accum_replicas_done(const RtAccum* acc) { return acc ? acc->k : 0; }
 static int accum_estimate_to(const RtAccum* acc, double* d_out, hipStream_t stream) {
     using namespace rt;
     const size_t n = acc->n_doubles();
-    if (acc->k == acc->T) {  // factor 1: the estimate is the frame, bit for bit
+    if (acc->adaptive) {
+        hipLaunchKernelGGL(k_accum_estimate_adaptive, dim3(uint32_t((n / 4 + 255) / 256)), dim3(256), 0, stream, acc->d_sum, acc->d_cnt, uint64_t(n / 4),
+                           double(acc->T), d_out);
+        HIP_TRY(hipGetLastError());
+    } else if (acc->k == acc->T) {  // factor 1: the estimate is the frame, bit for bit
         HIP_TRY(hipMemcpyAsync(d_out, acc->d_sum, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     } else {
         hipLaunchKernelGGL(k_accum_estimate, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, acc->d_sum, uint64_t(n),
@@ -1686,7 +1839,12 @@ int rt_accum_preview_rgb8(const RtAccum* acc, uint8_t* rgb_out) {
     RtAccum* a = const_cast<RtAccum*>(acc);
     if (int st = accum_scratch(a)) return st;
     const double scale = a->k == a->T ? 1.0 : double(a->T) / double(a->k);  // the estimate, formed inside the kernel
-    if (int st = tonemap_launch(a->d_sum, a->n_doubles() / 4, scale, a->d_rgb, a->scene->stream)) return st;
+    if (a->adaptive) {  // per-pixel factors: the estimate first
+        if (int st = accum_estimate_to(a, a->d_est, a->scene->stream)) return st;
+        if (int st = tonemap_launch(a->d_est, a->n_doubles() / 4, 1.0, a->d_rgb, a->scene->stream)) return st;
+    } else if (int st = tonemap_launch(a->d_sum, a->n_doubles() / 4, scale, a->d_rgb, a->scene->stream)) {
+        return st;
+    }
     HIP_TRY(hipMemcpy(rgb_out, a->d_rgb, a->n_doubles() / 4 * 3, hipMemcpyDeviceToHost));
     return RT_OK;
 }
@@ -1699,7 +1857,9 @@ int rt_tonemap_rgb8_device(int device, const double* d_rgba, uint32_t width, uin
 }
 
 size_t rt_accum_state_size(const RtAccum* acc) {
-    return acc ? sizeof(rt::AccumHeader) + acc->n_doubles() * sizeof(double) : 0;
+    if (!acc) return 0;
+    if (acc->adaptive) return sizeof(rt::AccumHeader) + sizeof(rt::AdaptiveBlobParams) + acc->npix() * (4 * 8 + 8 + 8 + 4);
+    return sizeof(rt::AccumHeader) + acc->n_doubles() * sizeof(double);
 }
 
 int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
@@ -1708,7 +1868,7 @@ int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
     if (size < rt_accum_state_size(acc)) return set_err(RT_E_INVALID, "rt_accum_save_state: buffer smaller than rt_accum_state_size");
     AccumHeader h{};
     std::memcpy(h.magic, kAccumMagic, 8);
-    h.version = kAccumVersion;
+    h.version = acc->adaptive ? kAccumVersionAdaptive : kAccumVersion;
     h.precision = acc->params.precision;
     h.width = acc->camera.image_width;
     h.owned_rows = acc->owned;
@@ -1717,7 +1877,20 @@ int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
     h.scene_digest = acc->scene->content_digest;
     h.frame_digest = acc->frame_digest;
     HIP_TRY(hipSetDevice(acc->device));
-    HIP_TRY(hipMemcpy(static_cast<char*>(buf) + sizeof h, acc->d_sum, acc->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
+    char* body = static_cast<char*>(buf) + sizeof h;
+    if (acc->adaptive) {
+        const AdaptiveBlobParams bp = blob_params(acc->ap);
+        std::memcpy(body, &bp, sizeof bp);
+        body += sizeof bp;
+    }
+    HIP_TRY(hipMemcpy(body, acc->d_sum, acc->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
+    if (acc->adaptive) {
+        const size_t np = acc->npix();
+        body += np * 32;
+        HIP_TRY(hipMemcpy(body, acc->d_s1, np * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(body + np * 8, acc->d_s2, np * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(body + np * 16, acc->d_cnt, np * 4, hipMemcpyDeviceToHost));
+    }
     std::memcpy(buf, &h, sizeof h);
     return RT_OK;
 }
@@ -1730,7 +1903,10 @@ int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size) {
     std::memcpy(&h, buf, sizeof h);
     auto bad = [](const std::string& what) { return set_err(RT_E_INVALID, "rt_accum_load_state: " + what); };
     if (std::memcmp(h.magic, kAccumMagic, 8) != 0) return bad("not an accumulator state (wrong magic)");
-    if (h.version != kAccumVersion) return bad("state format version " + std::to_string(h.version) + ", expected " + std::to_string(kAccumVersion));
+    const uint32_t want_version = acc->adaptive ? kAccumVersionAdaptive : kAccumVersion;
+    if (h.version != want_version)
+        return bad("state format version " + std::to_string(h.version) + ", expected " + std::to_string(want_version) +
+                   (acc->adaptive ? " (an adaptive accumulator)" : " (a plain accumulator)"));
     if (h.precision != acc->params.precision) return bad("precision mismatch (state " + std::to_string(h.precision) + ", accumulator " + std::to_string(acc->params.precision) + ")");
     if (h.width != acc->camera.image_width || h.owned_rows != acc->owned)
         return bad("image size mismatch (state " + std::to_string(h.width) + " x " + std::to_string(h.owned_rows) + " rows, accumulator " +
@@ -1740,10 +1916,30 @@ int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size) {
     if (h.scene_digest != acc->scene->content_digest) return bad("scene mismatch (the state was rendered from another scene description)");
     if (h.frame_digest != acc->frame_digest) return bad("camera / render parameter mismatch (seed, camera, depth, light bias, background or row partition)");
     if (size != rt_accum_state_size(acc)) return bad("state truncated or oversized (" + std::to_string(size) + " bytes, expected " + std::to_string(rt_accum_state_size(acc)) + ")");
+    const char* body = static_cast<const char*>(buf) + sizeof h;
+    const size_t np = acc->npix();
+    if (acc->adaptive) {
+        const AdaptiveBlobParams mine = blob_params(acc->ap);
+        if (std::memcmp(body, &mine, sizeof mine) != 0) return bad("adaptive parameter mismatch (threshold, floor, min_replicas, check_interval or radius)");
+        body += sizeof mine;
+        const char* cnt = body + np * 48;
+        for (size_t i = 0; i < np; i++) {
+            uint32_t c;
+            std::memcpy(&c, cnt + 4 * i, 4);
+            if (c > h.replicas_done || (c < h.replicas_done && !acc->decision_point(c))) return bad("a pixel's replica count is neither the state's nor a decision point");
+        }
+    }
     HIP_TRY(hipSetDevice(acc->device));
-    HIP_TRY(hipMemcpy(acc->d_sum, static_cast<const char*>(buf) + sizeof h, acc->n_doubles() * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(acc->d_sum, body, acc->n_doubles() * sizeof(double), hipMemcpyHostToDevice));
+    if (acc->adaptive) {
+        HIP_TRY(hipMemcpy(acc->d_s1, body + np * 32, np * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(acc->d_s2, body + np * 40, np * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(acc->d_cnt, body + np * 48, np * 4, hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipDeviceSynchronize());  // the render kernels run on a non-blocking stream, not ordered against this copy
     acc->k = h.replicas_done;
+    acc->touched = true;
+    if (acc->adaptive) return adaptive_rebuild(acc, acc->scene->stream);
     return RT_OK;
 }
 
@@ -1898,6 +2094,101 @@ int rt_accum_preview_denoised_rgb8(const RtAccum* acc, const RtDenoiseParams* dp
     if (int st = accum_denoise(a, dp, "rt_accum_preview_denoised_rgb8")) return st;
     if (int st = tonemap_launch(a->d_est, a->n_doubles() / 4, 1.0, a->d_rgb, a->scene->stream)) return st;
     HIP_TRY(hipMemcpy(rgb_out, a->d_rgb, a->n_doubles() / 4 * 3, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_adaptive_default_params(RtAdaptiveParams* out) {
+    if (!out) return rt::set_err(RT_E_INVALID, "rt_adaptive_default_params: NULL argument");
+    *out = RtAdaptiveParams{};
+    out->floor = 0.01;  // the values of the oracle experiment; the threshold has no default
+    out->min_replicas = 4;
+    out->check_interval = 2;
+    out->radius = 1;
+    return RT_OK;
+}
+
+int rt_accum_set_adaptive(RtAccum* acc, const RtAdaptiveParams* ap) {
+    using namespace rt;
+    if (!acc || !ap) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: NULL argument");
+    if (acc->adaptive) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: the accumulator is adaptive already");
+    if (acc->k != 0 || acc->touched) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: only before the first replica and before a state is loaded");
+    if (!(ap->threshold > 0.0) || !std::isfinite(ap->threshold)) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: threshold must be positive and finite (it has no default)");
+    if (!(ap->floor > 0.0) || !std::isfinite(ap->floor)) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: floor must be positive and finite");
+    if (ap->min_replicas < 2) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: min_replicas must be at least 2 (a variance needs two replicas)");
+    if (ap->check_interval < 1) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: check_interval must be at least 1");
+    if (ap->radius > 4) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: radius must be in 0 .. 4");
+    if (acc->params.band_rows != 0 && acc->params.n_parts > 1)
+        return set_err(RT_E_INVALID, "rt_accum_set_adaptive: the accumulator has a row partition (the window needs contiguous rows)");
+    if (acc->params.max_depth == 0) return set_err(RT_E_UNSUPPORTED, "rt_accum_set_adaptive: max_depth = 0 (adaptive passes run the wavefront scheduler)");
+    if (acc->npix() >= (1ull << 31)) return set_err(RT_E_UNSUPPORTED, "rt_accum_set_adaptive: more than 2^31 pixels");
+    HIP_TRY(hipSetDevice(acc->device));
+    const size_t np = acc->npix(), n_blocks = (np + AD_CHUNK - 1) / AD_CHUNK;
+    DeviceBuffers buf;  // frees what was allocated if a later allocation fails
+    auto alloc = [&](size_t bytes, void** q) -> int { HIP_TRY(hipMalloc(q, bytes)); buf.allocs.push_back(*q); HIP_TRY(hipMemset(*q, 0, bytes)); return RT_OK; };
+    void *s1 = nullptr, *s2 = nullptr, *cnt = nullptr, *a0 = nullptr, *a1 = nullptr, *state = nullptr, *keep = nullptr, *block = nullptr, *n_out = nullptr;
+    int st;
+    if ((st = alloc(np * 8, &s1)) || (st = alloc(np * 8, &s2)) || (st = alloc(np * 4, &cnt)) || (st = alloc(np * 4, &a0)) || (st = alloc(np * 4, &a1)) ||
+        (st = alloc(np, &state)) || (st = alloc(np, &keep)) || (st = alloc(n_blocks * 4, &block)) || (st = alloc(4, &n_out))) return st;
+    {  // every pixel is active, in ascending order
+        std::vector<uint32_t> identity(np);
+        for (size_t i = 0; i < np; i++) identity[i] = uint32_t(i);
+        HIP_TRY(hipMemcpy(a0, identity.data(), np * 4, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    buf.allocs.clear();
+    acc->d_s1 = static_cast<double*>(s1); acc->d_s2 = static_cast<double*>(s2); acc->d_cnt = static_cast<uint32_t*>(cnt);
+    acc->d_active[0] = static_cast<uint32_t*>(a0); acc->d_active[1] = static_cast<uint32_t*>(a1);
+    acc->d_state = static_cast<uint8_t*>(state); acc->d_keep = static_cast<uint8_t*>(keep);
+    acc->d_block = static_cast<uint32_t*>(block); acc->d_n_out = static_cast<uint32_t*>(n_out);
+    acc->cur = 0;
+    acc->n_active = uint32_t(np);  // all pixels: the dense kernels run until the first pixel stops (the list is not read)
+    acc->ap = *ap;
+    acc->adaptive = true;
+    return RT_OK;
+}
+
+uint32_t rt_accum_active_pixels(const RtAccum* acc) {
+    if (!acc) return 0;
+    if (acc->k >= acc->T) return 0;
+    return acc->adaptive ? acc->n_active : uint32_t(acc->npix());
+}
+
+int rt_accum_finished(const RtAccum* acc) {
+    if (!acc) return 0;
+    return (acc->k >= acc->T || (acc->adaptive && acc->n_active == 0)) ? 1 : 0;
+}
+
+int rt_accum_sample_counts(const RtAccum* acc, uint32_t* counts_out) {
+    using namespace rt;
+    if (!acc || !counts_out) return set_err(RT_E_INVALID, "rt_accum_sample_counts: NULL argument");
+    if (!acc->adaptive) {
+        std::fill(counts_out, counts_out + acc->npix(), acc->k);
+        return RT_OK;
+    }
+    HIP_TRY(hipSetDevice(acc->device));
+    HIP_TRY(hipMemcpy(counts_out, acc->d_cnt, acc->npix() * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int rt_accum_noise(const RtAccum* acc, double* noise_out) {
+    using namespace rt;
+    if (!acc || !noise_out) return set_err(RT_E_INVALID, "rt_accum_noise: NULL argument");
+    if (!acc->adaptive) return set_err(RT_E_INVALID, "rt_accum_noise: the accumulator keeps no moments (rt_accum_set_adaptive)");
+    HIP_TRY(hipSetDevice(acc->device));
+    const size_t np = acc->npix();
+    std::vector<double> s1(np), s2(np);
+    std::vector<uint32_t> cnt(np);
+    HIP_TRY(hipMemcpy(s1.data(), acc->d_s1, np * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(s2.data(), acc->d_s2, np * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cnt.data(), acc->d_cnt, np * 4, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < np; i++) {  // a few flops per pixel on 20 bytes that cross the bus anyway
+        const uint32_t k = cnt[i];
+        if (k < 2) { noise_out[i] = 0.0; continue; }
+        const double mean = s1[i] / double(k);
+        double num = s2[i] - s1[i] * mean;
+        if (num < 0.0) num = 0.0;
+        noise_out[i] = std::sqrt(num / (double(k) * double(k - 1))) / (mean + acc->ap.floor);
+    }
     return RT_OK;
 }
 

@@ -76,6 +76,18 @@ struct WfGroup {
     double inv_per_replica, inv_npix, inv_width;  // reciprocals rounded to nearest: quotient ESTIMATES, made exact in div_by
     uint32_t tid0;         // first replica of the group
     uint32_t strata;       // S*S
+    static constexpr bool kSparse = false;
+};
+
+// Replica group of an adaptive pass over a SUBSET of the pixels: `npix` counts the active pixels and
+// entry i of the group is owned pixel active[i].  The list is ascending, so neighbouring lanes keep neighbouring pixels and
+// the 4-byte gather is unit-stride.  Sample numbers, and with them the per-sample radiance buffer, are compact; the random
+// streams are keyed by the pixel itself, so a pixel receives the samples it receives in a dense group.  A type of its own,
+// not a run-time switch: the dense kernels keep their registers (k_wf_shade has none to spare).
+template <typename R>
+struct WfGroupSparse : WfGroup<R> {
+    const uint32_t* active;
+    static constexpr bool kSparse = true;
 };
 
 // floor(a / b) and the remainder for a < 2^51: the reciprocal estimate is off by at most one, the remainder test makes it
@@ -91,11 +103,12 @@ RT_DEV uint64_t div_by(uint64_t a, uint64_t b, double inv_b, uint64_t& rem) {
 }
 
 // Camera ray (origin, direction) and RNG state of sample s, in registers (camera.rs:260-280 through camera_ray).
-template <typename R>
-RT_DEV void wf_new_sample(uint64_t s, const WfGroup<R>& grp, const CameraView<R>& cam, const ParamsView<R>& prm, V3<R>& o, V3<R>& d, Rng& rng) {
+template <typename R, typename G>
+RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, const ParamsView<R>& prm, V3<R>& o, V3<R>& d, Rng& rng) {
     uint64_t rem, pix, px64;
     const uint32_t tid_local = uint32_t(div_by(s, grp.per_replica, grp.inv_per_replica, rem));
     const uint32_t st = uint32_t(div_by(rem, grp.npix, grp.inv_npix, pix));
+    if constexpr (G::kSparse) pix = grp.active[pix];
     const uint32_t row = uint32_t(div_by(pix, cam.width, grp.inv_width, px64));
     const uint32_t px = uint32_t(px64);
     uint32_t py;
@@ -107,8 +120,8 @@ RT_DEV void wf_new_sample(uint64_t s, const WfGroup<R>& grp, const CameraView<R>
     camera_ray(cam, px, py, sx, sy, rng, o, d);
 }
 
-template <typename R>
-__global__ void __launch_bounds__(256) k_wf_generate(WfPool<R> pool, uint32_t count, WfGroup<R> grp, CameraView<R> cam,
+template <typename R, typename G = WfGroup<R>>
+__global__ void __launch_bounds__(256) k_wf_generate(WfPool<R> pool, uint32_t count, G grp, CameraView<R> cam,
                                                      ParamsView<R> prm, uint32_t* __restrict__ queue) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
@@ -1208,8 +1221,9 @@ __device__ unsigned long long g_shade_stamps[16];
 #define RT_STAMP(k) do { } while (0)
 #endif
 
-template <typename R, bool STATS, int LDS, bool TEX>
-__global__ void RT_SHADE_BOUNDS k_wf_shade(SceneView<R> sc_g, CameraView<R> cam, ParamsView<R> prm, WfPool<R> pool, WfGroup<R> grp,
+// G: WfGroup<R>, or WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels
+template <typename R, bool STATS, int LDS, bool TEX, typename G = WfGroup<R>>
+__global__ void RT_SHADE_BOUNDS k_wf_shade(SceneView<R> sc_g, CameraView<R> cam, ParamsView<R> prm, WfPool<R> pool, G grp,
                                            const uint32_t* __restrict__ queue_in, uint32_t* __restrict__ queue_out,
                                            WfCounters* __restrict__ ctr, double* __restrict__ sample_L, DeviceCounters* counters,
                                            const WfPool<R>* __restrict__ pool_dev, uint32_t staged) {
@@ -1409,6 +1423,186 @@ __global__ void __launch_bounds__(256) k_wf_resolve(const double* __restrict__ s
     } else {
         for (int k = 0; k < 3; k++) acc[3 * pix + k] = a[k];
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Adaptive passes (include/rt_mi355.h).
+// ---------------------------------------------------------------------------------------------
+// Resolve with moments: k_wf_resolve's ordered sums for the `n_entries` pixels of the group (SPARSE: pixel active[i]), always
+// from and to the accumulator's `sum`, plus the luminance moments of the per-replica contributions and the replica count.
+template <bool SPARSE>
+__global__ void __launch_bounds__(256) k_wf_resolve_moments(const double* __restrict__ sample_L, uint64_t n_entries, uint32_t strata,
+                                                            uint32_t n_replicas, double spp, double T, const uint32_t* __restrict__ active,
+                                                            double* __restrict__ sum, double* __restrict__ s1, double* __restrict__ s2,
+                                                            uint32_t* __restrict__ cnt) {
+#pragma clang fp contract(off)
+    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n_entries) return;
+    const uint64_t p = SPARSE ? uint64_t(active[i]) : i;
+    double a[3] = {sum[4 * p + 0], sum[4 * p + 1], sum[4 * p + 2]};
+    double m1 = s1[p], m2 = s2[p];
+    for (uint32_t t = 0; t < n_replicas; t++) {
+        double col[3] = {0.0, 0.0, 0.0};
+        for (uint32_t st = 0; st < strata; st++) {
+            const uint64_t s = (uint64_t(t) * strata + st) * n_entries + i;
+            col[0] += sample_L[3 * s + 0];
+            col[1] += sample_L[3 * s + 1];
+            col[2] += sample_L[3 * s + 2];
+        }
+        double c[3];
+        for (int k = 0; k < 3; k++) {
+            c[k] = col[k] / spp;
+            a[k] += c[k];
+        }
+        const double y = T * ((0.2126 * c[0] + 0.7152 * c[1]) + 0.0722 * c[2]);
+        m1 += y;
+        m2 += y * y;
+    }
+    sum[4 * p + 0] = a[0];
+    sum[4 * p + 1] = a[1];
+    sum[4 * p + 2] = a[2];
+    s1[p] = m1;
+    s2[p] = m2;
+    cnt[p] += n_replicas;
+}
+
+// Pixel states of the decision step: a stopped pixel does not hold its neighbours, so it reads as quiet.
+constexpr uint8_t AD_NOISY = 0, AD_QUIET = 1, AD_STOPPED = 2;
+
+// se2 <= (threshold (mean + floor))^2 after k replicas; any NaN makes the comparison false.
+RT_DEV bool ad_quiet(double m1, double m2, uint32_t k, double threshold, double floor_) {
+#pragma clang fp contract(off)
+    const double mean = m1 / double(k);
+    double num = m2 - m1 * mean;
+    if (num < 0.0) num = 0.0;
+    const double se2 = num / (double(k) * double(k - 1u));
+    const double lim = threshold * (mean + floor_);
+    return se2 <= lim * lim;
+}
+
+// Decision, step 1: state[p] of every active pixel (every active pixel has n = k).
+__global__ void __launch_bounds__(256) k_ad_quiet(const uint32_t* __restrict__ active, uint32_t n_active, const double* __restrict__ s1,
+                                                  const double* __restrict__ s2, uint32_t k, double threshold, double floor_,
+                                                  uint8_t* __restrict__ state) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_active) return;
+    const uint32_t p = active[i];
+    state[p] = ad_quiet(s1[p], s2[p], k, threshold, floor_) ? AD_QUIET : AD_NOISY;
+}
+
+constexpr uint32_t AD_CHUNK = 2048;  // active-list entries per workgroup of the window and scatter kernels
+
+// Decision, step 2: entry i stays (keep[i] = 1) unless its pixel is quiet and no pixel of its window is noisy; per workgroup
+// the number of entries that stay.  Reads `state` only: the new states are written by k_ad_scatter.
+__global__ void __launch_bounds__(256) k_ad_window(const uint32_t* __restrict__ active, uint32_t n_active, const uint8_t* __restrict__ state,
+                                                   uint32_t width, uint32_t height, int radius, uint8_t* __restrict__ keep,
+                                                   uint32_t* __restrict__ block_count) {
+    __shared__ uint32_t total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const uint32_t begin = blockIdx.x * AD_CHUNK;
+    const uint32_t end = min(n_active, begin + AD_CHUNK);
+    uint32_t mine = 0;
+    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
+        const uint32_t p = active[i];
+        const int y = int(p / width), x = int(p - uint32_t(y) * width);
+        bool stop = state[p] == AD_QUIET;
+        for (int dy = -radius; stop && dy <= radius; dy++) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= int(height)) continue;
+            for (int dx = -radius; dx <= radius; dx++) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= int(width)) continue;
+                stop = stop && state[uint32_t(yy) * width + uint32_t(xx)] != AD_NOISY;
+            }
+        }
+        keep[i] = stop ? 0 : 1;
+        mine += stop ? 0u : 1u;
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
+    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(&total, mine);  // integer sum: the order does not matter
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// Decision, step 3: exclusive scan of the workgroup counts by one wave (in place), the total to *n_out.
+__global__ void __launch_bounds__(64) k_ad_scan(uint32_t* __restrict__ block_count, uint32_t n_blocks, uint32_t* __restrict__ n_out) {
+    const uint32_t lane = threadIdx.x;
+    uint32_t base = 0;
+    for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64) {
+        const uint32_t b = b0 + lane;
+        const uint32_t v = b < n_blocks ? block_count[b] : 0u;
+        uint32_t incl = v;
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(incl, off);
+            if (int(lane) >= off) incl += o;
+        }
+        if (b < n_blocks) block_count[b] = base + incl - v;
+        base += __shfl(incl, 63);
+    }
+    if (lane == 0) *n_out = base;
+}
+
+// Decision, step 4: order-preserving compaction of the active list (ballot prefix inside a wave, wave totals through LDS;
+// no atomic decides a position); the pixels that leave the list become AD_STOPPED.
+__global__ void __launch_bounds__(256) k_ad_scatter(const uint32_t* __restrict__ active, uint32_t n_active, const uint8_t* __restrict__ keep,
+                                                    const uint32_t* __restrict__ block_offset, uint32_t* __restrict__ active_out,
+                                                    uint8_t* __restrict__ state) {
+    __shared__ uint32_t wave_total[4];
+    const uint32_t begin = blockIdx.x * AD_CHUNK;
+    const uint32_t end = min(n_active, begin + AD_CHUNK);
+    const uint32_t wave = threadIdx.x >> 6;
+    uint32_t base = block_offset[blockIdx.x];
+    for (uint32_t i0 = begin; i0 < end; i0 += blockDim.x) {
+        const uint32_t i = i0 + threadIdx.x;
+        const bool in = i < end;
+        const uint32_t p = in ? active[i] : 0u;
+        const bool stay = in && keep[i] != 0;
+        const unsigned long long m = __ballot(stay);
+        if ((threadIdx.x & 63u) == 0) wave_total[wave] = uint32_t(__popcll(m));
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+        for (uint32_t w = 0; w < 4; w++) {
+            const uint32_t c = wave_total[w];
+            before += w < wave ? c : 0u;
+            all += c;
+        }
+        if (stay) active_out[base + before + lane_prefix(m)] = p;
+        else if (in) state[p] = AD_STOPPED;
+        base += all;
+        __syncthreads();
+    }
+}
+
+// Rebuilds the list after a state load: pixel p is active iff n[p] == k.  Same scan, flags from the counts.
+__global__ void __launch_bounds__(256) k_ad_flags_from_counts(const uint32_t* __restrict__ cnt, uint32_t npix, uint32_t k, uint32_t* __restrict__ identity,
+                                                              uint8_t* __restrict__ keep, uint8_t* __restrict__ state, uint32_t* __restrict__ block_count) {
+    __shared__ uint32_t total;
+    if (threadIdx.x == 0) total = 0;
+    __syncthreads();
+    const uint32_t begin = blockIdx.x * AD_CHUNK;
+    const uint32_t end = min(npix, begin + AD_CHUNK);
+    uint32_t mine = 0;
+    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
+        const bool on = cnt[i] == k;
+        identity[i] = i;
+        keep[i] = on ? 1 : 0;
+        state[i] = AD_NOISY;  // k_ad_scatter marks the others AD_STOPPED
+        mine += on ? 1u : 0u;
+    }
+    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
+    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
+}
+
+// estimate of an adaptive accumulator: sum[p] * (T / n[p]) (w stays 0; the factor is exactly 1 at n = T)
+__global__ void __launch_bounds__(256) k_accum_estimate_adaptive(const double* __restrict__ sum, const uint32_t* __restrict__ cnt, uint64_t npix,
+                                                                 double T, double* __restrict__ out) {
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    const double scale = T / double(cnt[p]);
+    for (int k = 0; k < 4; k++) out[4 * p + k] = sum[4 * p + k] * scale;
 }
 
 }  // namespace rt
