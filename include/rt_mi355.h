@@ -288,6 +288,15 @@ int rt_scene_info(const RtSceneDesc* desc, uint32_t* flags_out);
  * out[0] triangle records, out[1] BVH2 nodes, out[2] 4-wide nodes, out[3] BVH2 depth, out[4] worst-case 4-wide traversal stack,
  * out[5] scene-program ops, out[6] sphere / quad groups re-built as SAH trees, out[7] primitives in them. */
 int rt_scene_mesh_stats(const RtSceneDesc* desc, uint64_t out[8]);
+/* Same, for the back-face cones of k_wf_mesh (tests without a GPU): the 4-wide BVH of mesh instance `mesh` of the compiled scene
+ * (instances in program order).  children_out[4 i + k] = child k of node i, node 0 the root: >= 0 inner node, < 0 leaf with
+ * ~child = (first triangle << 3) | (count - 1), INT32_MIN no child - all relative to this mesh; cones_out[4 i + k] = that
+ * child's cone word, four signed bytes (ax, ay, az, w), built with the conditioning limits of the f64 kernels (f32 = 0) or
+ * the f32 kernels (f32 != 0); tris_out[9 t ..] = v0, e1, e2 of triangle t in leaf order (f64 records).  Up to
+ * `node_capacity` nodes and `tri_capacity` triangles are written; *n_nodes_out / *n_tris_out = the mesh's totals; the
+ * output arrays may be NULL. */
+int rt_scene_mesh_cones(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out,
+                        uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out, uint32_t tri_capacity, uint32_t* n_tris_out);
 /* Same, plus the compiled scene program itself (tests of the scene compiler without a GPU): ops_out[4 * i ..] = type, arg,
  * skip, chain of op i (rt_scene.h OpType; up to `capacity` ops are written, *n_ops_out = the program's length; ops_out may be
  * NULL).  info[0] mesh ops, [1] primitive groups with a 4-wide BVH, [2] their nodes, [3] their worst-case stack, [4] entries of

@@ -22,6 +22,7 @@ RT_E_INVALID, RT_E_UNSUPPORTED, RT_E_DEVICE, RT_E_NOMEM = -1, -2, -3, -4
 RT_PRECISION_F64, RT_PRECISION_F32 = 0, 1
 RT_PIPELINE_AUTO, RT_PIPELINE_MEGAKERNEL, RT_PIPELINE_WAVEFRONT = 0, 1, 2
 RT_SCENE_BVH_ON_DEVICE = 1  # RtSceneDesc.flags
+RT_MESH_HIT_BACK_FACES = 2  # RtMesh.flags
 RT_DENOISE_DEMODULATE = 1  # RtDenoiseParams.flags
 RT_DENOISE_MAX_ITERATIONS = 16
 AOV_CHANNELS = 8  # rt_render_aov: albedo rgb, normal xyz, depth, coverage
@@ -254,6 +255,10 @@ def load_device_lib() -> C.CDLL:
         if hasattr(lib, "rt_scene_mesh_stats"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_scene_mesh_stats.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(C.c_uint64)]
             lib.rt_scene_mesh_stats.restype = C.c_int
+        if hasattr(lib, "rt_scene_mesh_cones"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_scene_mesh_cones.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+            lib.rt_scene_mesh_cones.restype = C.c_int
         if hasattr(lib, "rt_accum_create"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             for name, res, args in (
                     ("rt_accum_create", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), C.POINTER(C.c_void_p)]),
@@ -323,6 +328,25 @@ def scene_mesh_stats(desc) -> dict:
         raise RtError(st, lib.rt_last_error().decode())
     return dict(zip(("triangles", "bvh2_nodes", "bvh4_nodes", "bvh2_depth", "bvh4_stack", "ops", "rebuilt_groups", "rebuilt_prims"),
                     [int(x) for x in out]))
+
+
+def scene_mesh_cones(desc, mesh: int = 0, f32: bool = False) -> tuple:
+    """rt_scene_mesh_cones: (children (n, 4) int32, cone words (n, 4, 4) int8 as (ax, ay, az, w), triangle records (t, 3, 3)
+    float64 as (v0, e1, e2) in leaf order) of mesh instance `mesh`; host only."""
+    import numpy as np
+    lib = load_device_lib()
+    nn, nt = C.c_uint32(), C.c_uint32()
+    st = lib.rt_scene_mesh_cones(desc, mesh, int(f32), None, None, 0, C.byref(nn), None, 0, C.byref(nt))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    children = np.zeros((nn.value, 4), dtype=np.int32)
+    cones = np.zeros((nn.value, 4), dtype=np.uint32)
+    tris = np.zeros((nt.value, 3, 3), dtype=np.float64)
+    st = lib.rt_scene_mesh_cones(desc, mesh, int(f32), children.ctypes.data, cones.ctypes.data, nn.value, C.byref(nn),
+                                 tris.ctypes.data, nt.value, C.byref(nt))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return children, cones.view(np.int8).reshape(-1, 4, 4), tris
 
 
 def scene_program(desc) -> tuple:

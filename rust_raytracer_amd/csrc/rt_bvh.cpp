@@ -256,4 +256,151 @@ BvhNBuild<W> collapse(const BvhBuild& b2) {
 
 Bvh4Build collapse_bvh4(const BvhBuild& b2) { return collapse<4>(b2); }
 
+
+// ---------------------------------------------------------------------------------------------
+// Back-face cones of the 4-wide mesh nodes.
+//
+// The triangle test of k_wf_mesh (the reference's, mesh.rs:62-107) computes det = e1 . (d x e2) = -d . (e1 x e2) and
+// rejects the triangle if det < EPSILON, unless the mesh hits back faces.  A child all of whose triangles face away from
+// the ray can therefore be skipped without changing the closest hit, the order of the remaining tests included.
+//
+// Per child: n_i = unit normals e1 x e2 of the triangles below it, a = q / |q| with q = round(127 x their normalised sum)
+// (the axis as the kernel sees it; for a leaf whose sum gives no cone, the bisector of its two normals farthest apart),
+// c = min_i a . n_i (the exact minimum over the triangles, not a merge of child cones), s = sqrt(1 - c^2),
+// w = ceil(|q| (s + d_dir + d_safe)); the word is (q, w), valid if c >= kConeMinCos and w <= 127.
+// The kernel packs D = (round(127 d / |d|), -127) and culls the child if D . (q, w) > 0 in integer arithmetic.
+//
+//  1. Every byte of D is within 0.5 + 1e-4 of 127 d^ (d^ = d / |d|; the 1e-4 covers normalising in f32), so
+//     127 d^ . q >= D_xyz . q - (sqrt(3) / 2 + 2e-4) |q| > 127 w - 127 d_dir |q| >= 127 |q| (s + d_safe), with
+//     d_dir = 0.00682 >= (sqrt(3) / 2 + 2e-4) / 127: cos(theta) = d^ . a > s + d_safe.
+//  2. Every n_i is within alpha = acos(c) of a, so d^ . n_i >= cos(theta + alpha) = cos(theta) c - sin(theta) s
+//     >= (s + d_safe) c - c s = d_safe c  (sin(theta) <= sqrt(1 - s^2) = c).  The host's own rounding in a, n_i and c is
+//     below 1e-14 and is charged to d_safe: 0.9 d_safe is what the next step uses.
+//  3. det_true = -|d| |e1 x e2| d^ . n_i <= -0.9 d_safe c sigma |d| |e1| |e2| for a well-conditioned triangle
+//     (|e1 x e2| >= sigma |e1| |e2|).
+//  4. The computed det: each component of d x e2 is fl(fl(ab) - fl(cd)), off by at most 3u (|ab| + |cd|) <= 3u |d| |e2|
+//     per component, 3 sqrt(3) u |d| |e2| as a vector; the three-term dot adds 3u |e1| |d x e2|; no contraction
+//     (-ffp-contract=off).  Together |det - det_true| <= gamma |d| |e1| |e2| with gamma = 10u (u = 2^-53: 1.1e-15).
+//     In f32 builds the records are the f64 edges rounded to f32, which moves e1 x e2 by at most 2u |e1| |e2|:
+//     gamma = 12u (u = 2^-24: 7.2e-7).
+//  5. With 0.9 d_safe c sigma > gamma the computed det is negative, `det < EPSILON` holds and the test returns "no hit".
+//     d_safe = 1e-3, c >= 1/8: f64, sigma = 2^-20: 1.07e-10 > 1.1e-15 (five orders to spare);
+//     f32, sigma = 2^-5: 3.5e-6 > 7.2e-7.
+//  6. Under- and overflow: edges outside [min_edge, max_edge] make a triangle ill-conditioned, and the kernel gives the
+//     never-culling direction word to rays with |d|^2 outside [1e-24, 1e24] (f32) / [1e-200, 1e200] (f64), so no product of
+//     step 4 overflows; an underflow moves det by less than the smallest normal number, far inside EPSILON.
+//     Non-finite directions and coordinates are excluded the same way: a NaN det PASSES `!(det < EPSILON)`.
+//     Meshes that hit back faces test |det|; the kernel never culls for them.
+//
+// A child above an ill-conditioned triangle, an empty child, a child whose cone is wider than acos(kConeMinCos) and (never seen:
+// both builders order the triangles subtree by subtree) a child whose triangles are not one run of slots get kNeutralCone.
+// ---------------------------------------------------------------------------------------------
+namespace {
+constexpr double kConeDirSlack = 0.00682;   // d_dir
+constexpr double kConeSafety = 0.001;       // d_safe
+constexpr double kConeMinCos = 0.125;       // c >= 1/8: wider cones cull next to nothing
+}  // namespace
+
+ConeLimits cone_limits(bool f32) {
+    if (f32) return ConeLimits{1.0 / 32.0, 1e-12, 1e12};
+    return ConeLimits{1.0 / 1048576.0, 1e-100, 1e100};
+}
+
+void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const ConeLimits& lim,
+                      std::vector<uint32_t>* out) {
+    const size_t n_tris = tris.size();
+    // unit normals; a triangle that is ill-conditioned has normal[3 t] = NaN
+    std::vector<double> normal(3 * n_tris);
+    const double kNaN = std::numeric_limits<double>::quiet_NaN();
+    for (size_t t = 0; t < n_tris; t++) {
+        const TriRec<double>& r = tris[t];
+        const double* a = r.e1;
+        const double* b = r.e2;
+        const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+        const double la = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), lb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+        const double lc = std::sqrt(cx * cx + cy * cy + cz * cz);
+        bool ok = std::isfinite(r.v0[0]) && std::isfinite(r.v0[1]) && std::isfinite(r.v0[2]);
+        ok = ok && la >= lim.min_edge && la <= lim.max_edge && lb >= lim.min_edge && lb <= lim.max_edge;  // false for NaN
+        ok = ok && lc >= lim.sigma * la * lb && lc > 0.0;
+        normal[3 * t] = ok ? cx / lc : kNaN;
+        normal[3 * t + 1] = ok ? cy / lc : kNaN;
+        normal[3 * t + 2] = ok ? cz / lc : kNaN;
+    }
+    // what lies below a child: the run of triangle slots [lo, hi), their number, the sum of their normals (NaN if one is bad)
+    struct Below {
+        uint32_t lo = UINT32_MAX, hi = 0, count = 0;
+        double sum[3] = {0.0, 0.0, 0.0};
+        void add(const Below& o) {
+            lo = std::min(lo, o.lo); hi = std::max(hi, o.hi); count += o.count;
+            for (int a = 0; a < 3; a++) sum[a] += o.sum[a];
+        }
+    };
+    // the word of the cone around `axis` (any length) that holds the normals of the run b, or kNeutralCone
+    auto cone_around = [&](const Below& b, const double* axis) -> uint32_t {
+        const double l = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+        if (!(l > 0.0) || !std::isfinite(l)) return kNeutralCone;  // NaN: an ill-conditioned triangle below
+        int q[3];
+        double al = 0.0;
+        for (int a = 0; a < 3; a++) { q[a] = int(std::lround(127.0 * axis[a] / l)); al += double(q[a]) * double(q[a]); }
+        al = std::sqrt(al);
+        if (!(al > 0.0)) return kNeutralCone;
+        const double ax = q[0] / al, ay = q[1] / al, az = q[2] / al;
+        double c = 1.0;
+        for (uint32_t t = b.lo; t < b.hi; t++) {
+            c = std::min(c, ax * normal[3 * size_t(t)] + ay * normal[3 * size_t(t) + 1] + az * normal[3 * size_t(t) + 2]);
+            if (c < kConeMinCos) return kNeutralCone;
+        }
+        if (!(c >= kConeMinCos)) return kNeutralCone;
+        const double s = std::sqrt(std::max(0.0, 1.0 - c * c));
+        const double w = std::ceil(al * (s + kConeDirSlack + kConeSafety));
+        if (!(w >= 1.0 && w <= 127.0)) return kNeutralCone;
+        return uint32_t(q[0] & 0xFF) | (uint32_t(q[1] & 0xFF) << 8) | (uint32_t(q[2] & 0xFF) << 16) | (uint32_t(w) << 24);
+    };
+    auto cone_word = [&](const Below& b) -> uint32_t {
+        if (b.count == 0 || b.hi - b.lo != b.count) return kNeutralCone;
+        uint32_t word = cone_around(b, b.sum);
+        if (word == kNeutralCone && b.count >= 2 && b.count <= 8 && std::isfinite(b.sum[0])) {
+            // A leaf over a fold: the sum leans towards the side with more triangles and loses the other one.  The bisector
+            // of the two normals farthest apart is the axis of the narrowest cone that holds those two.
+            uint32_t bi = b.lo, bj = b.lo;
+            double least = 2.0;
+            for (uint32_t i = b.lo; i < b.hi; i++)
+                for (uint32_t j = i + 1; j < b.hi; j++) {
+                    const double* ni = &normal[3 * size_t(i)];
+                    const double* nj = &normal[3 * size_t(j)];
+                    const double dij = ni[0] * nj[0] + ni[1] * nj[1] + ni[2] * nj[2];
+                    if (dij < least) { least = dij; bi = i; bj = j; }
+                }
+            const double mid[3] = {normal[3 * size_t(bi)] + normal[3 * size_t(bj)], normal[3 * size_t(bi) + 1] + normal[3 * size_t(bj) + 1],
+                                   normal[3 * size_t(bi) + 2] + normal[3 * size_t(bj) + 2]};
+            word = cone_around(b, mid);
+        }
+        return word;
+    };
+    out->assign(4 * nodes4.size(), kNeutralCone);
+    std::vector<Below> below(nodes4.size());  // per node: the union of its children
+    for (size_t i = nodes4.size(); i-- > 0;) {  // children stand behind their parent: bottom-up without recursion
+        const BuildNode4& nd = nodes4[i];
+        Below all;
+        for (int k = 0; k < 4; k++) {
+            const int32_t ch = nd.child[k];
+            if (ch == kEmptyChild) continue;
+            Below b;
+            if (ch >= 0) {
+                if (size_t(ch) <= i || size_t(ch) >= nodes4.size()) { all.sum[0] = kNaN; continue; }  // not a tree in that order: no cones above
+                b = below[size_t(ch)];
+            } else {
+                const uint32_t code = uint32_t(~ch), first = code >> 3, count = (code & 7u) + 1u;
+                if (size_t(first) + count > n_tris) { all.sum[0] = kNaN; continue; }
+                b.lo = first; b.hi = first + count; b.count = count;
+                for (uint32_t t = first; t < first + count; t++)
+                    for (int a = 0; a < 3; a++) b.sum[a] += normal[3 * size_t(t) + a];
+            }
+            (*out)[4 * i + size_t(k)] = cone_word(b);
+            all.add(b);
+        }
+        below[i] = all;
+    }
+}
+
 }  // namespace rt

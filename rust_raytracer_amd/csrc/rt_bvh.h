@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#include "rt_scene.h"
+
 namespace rt {
 
 struct BuildNode {
@@ -50,5 +52,22 @@ struct BvhNBuild {
 using BuildNode4 = BuildNodeN<4>;
 using Bvh4Build = BvhNBuild<4>;
 Bvh4Build collapse_bvh4(const BvhBuild& bvh2);
+
+// Back-face cones of the 4-wide mesh nodes (k_wf_mesh): one word of four signed bytes (ax, ay, az, w) per child, four
+// words per node, in node order.  With the ray's object-space direction packed as (round(127 d / |d|), -127), the integer
+// product `dir . cone > 0` proves that every triangle below the child faces away from the ray, so that the
+// reference's front-face rule (mesh.rs:77) rejects each of them: the child need not be entered.  kNeutralCone (rt_scene.h)
+// never culls.  The argument, with its numbers, stands beside the builder in rt_bvh.cpp.
+struct ConeLimits {
+    double sigma;     // a triangle is ill-conditioned if |e1 x e2| < sigma |e1| |e2|
+    double min_edge;  // ... or if an edge is shorter / longer than this (no under- or overflow in the determinant's products)
+    double max_edge;
+};
+// the limits for triangle tests in f64 (f32 = false) or in f32 on records rounded to f32
+ConeLimits cone_limits(bool f32);
+// nodes4: 4-wide nodes with ABSOLUTE child / triangle references (CompiledScene::nodes4), children behind their parent;
+// tris: the f64 records in leaf order.  out: 4 words per node.
+void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const ConeLimits& lim,
+                      std::vector<uint32_t>* out);
 
 }  // namespace rt

@@ -394,6 +394,15 @@ struct DeviceScene {
                 }
             }
         }
+        // back-face cone words of the mesh nodes' children, with the conditioning limits of this arithmetic type (rt_bvh.cpp)
+        std::vector<uint32_t> cone_words;
+        build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &cone_words);
+        std::vector<MeshNode4qc> nodes4qc(cs.nodes4.size());
+        for (size_t i = 0; i < nodes4qc.size(); i++) {
+            nodes4qc[i].node = nodes4q[i];
+            for (int k = 0; k < 4; k++) nodes4qc[i].cones.word[k] = cone_words[4 * i + size_t(k)];
+            for (uint32_t& x : nodes4qc[i]._pad) x = 0;
+        }
         std::vector<Bounds<R>> mesh_bounds(cs.mesh_bounds.size());
         for (size_t i = 0; i < mesh_bounds.size(); i++)
             for (int a = 0; a < 3; a++) {  // outward: this box only decides which rays are queued for the mesh
@@ -452,7 +461,7 @@ struct DeviceScene {
         if ((st = buf.upload(volumes, &view.volumes)) != RT_OK) return st;
         if ((st = buf.upload(nodes, &view.nodes)) != RT_OK) return st;
         if ((st = buf.upload(nodes4, &view.nodes4)) != RT_OK) return st;
-        if ((st = buf.upload(nodes4q, &view.nodes4q)) != RT_OK) return st;
+        if ((st = buf.upload(nodes4qc, &view.nodes4q)) != RT_OK) return st;
         if ((st = buf.upload(mesh_bounds, &view.mesh_bounds)) != RT_OK) return st;
         if ((st = buf.upload(cs.mesh_ops, &view.mesh_ops)) != RT_OK) return st;
         view.n_mesh_ops = int32_t(cs.mesh_ops.size());
@@ -864,6 +873,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // BVH node format of k_wf_mesh: 1 = 4-wide quantised (BvhNode4q, 64 B, default), 0 = 4-wide f32 (BvhNode4f, 128 B; A/B control).
     // An 8-wide quantised node (a third fewer visits) was slower: profiles/r02/ab/node_width_and_size.txt.
     const int node_kind = env_u32("RT_WF_NODES", 1) != 0 ? 1 : 0;
+    // Back-face cone test of the quantised node step: 0 = off (A/B control: the same code object, never-culling direction word).
+    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
     const int mesh_levels = int(s->compiled.max_bvh4_stack) + 1;
     const int lds_levels = std::min<int>(mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
     const size_t lds_mesh = size_t(lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
@@ -977,7 +988,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                                                       else { if (lds_prims == 2) RT_LAUNCH_PRIMS(false, 2, false, true); else if (lds_prims == 1) RT_LAUNCH_PRIMS(false, 1, false, true); else RT_LAUNCH_PRIMS(false, 0, false, true); } } \
                                    else if (stats) { if (lds_prims == 1) RT_LAUNCH_PRIMS(true, 1, false, false); else if (lds_prims == 2) RT_LAUNCH_PRIMS(true, 2, false, false); else RT_LAUNCH_PRIMS(true, 0, false, false); } \
                                    else { if (lds_prims == 1) RT_LAUNCH_PRIMS(false, 1, false, false); else if (lds_prims == 2) RT_LAUNCH_PRIMS(false, 2, false, false); else RT_LAUNCH_PRIMS(false, 0, false, false); } } while (0)
-#define RT_LAUNCH_MESH_M(ST, ND, MU, QUEUE, NPTR, CPTR) hipLaunchKernelGGL((k_wf_mesh<R, ST, ND, MU>), dim3(isect_blocks), dim3(256), lds_mesh, stream, ds.view, pool, QUEUE, w.d_ctr, s->d_counters, refill_min, inner_min, static_cast<uint2*>(w.mesh_spill), lds_levels, NPTR, CPTR)
+#define RT_LAUNCH_MESH_M(ST, ND, MU, QUEUE, NPTR, CPTR) hipLaunchKernelGGL((k_wf_mesh<R, ST, ND, MU>), dim3(isect_blocks), dim3(256), lds_mesh, stream, ds.view, pool, QUEUE, w.d_ctr, s->d_counters, refill_min, inner_min, static_cast<uint2*>(w.mesh_spill), lds_levels, NPTR, CPTR, cones_on)
 #define RT_LAUNCH_MESH_V(ST, ND, QUEUE, NPTR, CPTR) do { if (multi_mesh) RT_LAUNCH_MESH_M(ST, ND, true, QUEUE, NPTR, CPTR); else RT_LAUNCH_MESH_M(ST, ND, false, QUEUE, NPTR, CPTR); } while (0)
 #define RT_LAUNCH_MESH(QUEUE, NPTR, CPTR)                                                                                                         \
     do {                                                                                                                                          \
@@ -1600,6 +1611,47 @@ int rt_scene_mesh_stats(const RtSceneDesc* desc, uint64_t out[8]) {
     out[5] = cs.ops.size();
     out[6] = cs.n_rebuilt_groups;
     out[7] = cs.n_rebuilt_prims;
+    return RT_OK;
+}
+
+int rt_scene_mesh_cones(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out,
+                        uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out, uint32_t tri_capacity, uint32_t* n_tris_out) {
+    using namespace rt;
+    if (!desc || !n_nodes_out || !n_tris_out) return set_err(RT_E_INVALID, "rt_scene_mesh_cones: NULL argument");
+    CompiledScene cs;
+    std::string err;
+    int st = compile_scene(desc, &cs, &err, CompileOptions());
+    if (st != RT_OK) return set_err(st, err);
+    if (mesh >= cs.meshes.size()) return set_err(RT_E_INVALID, "rt_scene_mesh_cones: mesh index out of range");
+    const MeshInst& mi = cs.meshes[mesh];
+    size_t node_end = cs.nodes4.size();  // this mesh's nodes end where the next distinct mesh's begin
+    for (const MeshInst& o : cs.meshes)
+        if (o.node4_base > mi.node4_base) node_end = std::min(node_end, size_t(o.node4_base));
+    const size_t n_nodes = node_end - mi.node4_base;
+    *n_nodes_out = uint32_t(n_nodes);
+    *n_tris_out = mi.n_tris;
+    if (children_out && cones_out) {
+        std::vector<uint32_t> words;
+        build_mesh_cones(cs.nodes4, cs.tris, cone_limits(f32 != 0), &words);
+        for (size_t i = 0; i < n_nodes && i < node_capacity; i++)
+            for (int k = 0; k < 4; k++) {
+                int32_t ch = cs.nodes4[mi.node4_base + i].child[k];
+                if (ch != kEmptyChild) {
+                    if (ch >= 0) ch -= int32_t(mi.node4_base);
+                    else {
+                        const uint32_t code = uint32_t(~ch);
+                        ch = ~int32_t((((code >> 3) - mi.tri_base) << 3) | (code & 7u));
+                    }
+                }
+                children_out[4 * i + size_t(k)] = ch;
+                cones_out[4 * i + size_t(k)] = words[4 * (mi.node4_base + i) + size_t(k)];
+            }
+    }
+    if (tris_out)
+        for (size_t t = 0; t < mi.n_tris && t < tri_capacity; t++) {
+            const TriRec<double>& r = cs.tris[mi.tri_base + t];
+            for (int a = 0; a < 3; a++) { tris_out[9 * t + size_t(a)] = r.v0[a]; tris_out[9 * t + 3 + size_t(a)] = r.e1[a]; tris_out[9 * t + 6 + size_t(a)] = r.e2[a]; }
+        }
     return RT_OK;
 }
 

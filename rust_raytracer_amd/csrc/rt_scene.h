@@ -162,6 +162,25 @@ struct alignas(64) BvhNode4q {
 };
 static_assert(sizeof(BvhNode4q) == 64, "BvhNode4q must be 64 bytes");
 
+// Back-face cones of a mesh node's four children: per child one word of four signed bytes (ax, ay, az, w).  k_wf_mesh packs
+// the ray's object-space direction as (round(127 d / |d|), -127) and skips the child if the integer product of the two
+// words is positive: every triangle below it then faces away from the ray, and the reference's front-face rule
+// (mesh.rs:77) rejects each of them.  Builder and proof: rt_bvh.cpp.
+struct alignas(16) NodeCones4 {
+    uint32_t word[4];
+};
+// What k_wf_mesh reads per node visit: the unchanged 64-B node and the cone words in ONE 128-B line (64 + 16 bytes read, five
+// 16-B loads).  The cone words as a second array parallel to the nodes (a second line request per visit) were 2.5 % of the
+// kernel slower on the headline mesh and 5 % on the 3.5 M-triangle one: profiles/r04/ab/backface_cones.txt.
+struct alignas(128) MeshNode4qc {
+    BvhNode4q node;
+    NodeCones4 cones;
+    uint32_t _pad[12];
+};
+static_assert(sizeof(MeshNode4qc) == 128, "one cache line per mesh node");
+constexpr uint32_t kNeutralCone = 0x7F000000u;  // (0, 0, 0, 127): never culls
+constexpr uint32_t kNoCullDir = 0x81000000u;    // (0, 0, 0, -127): the direction word of a ray that culls nothing
+
 // Triangle record for the intersection test: v0 and the two edges (mesh.rs:69-70 computes the
 // edges per test; v1 - v0 done once on the host in the same arithmetic gives the same bits).
 template <typename R>
@@ -260,7 +279,7 @@ struct SceneView {
     const VolumeRec<R>* volumes;   // global memory (not in the LDS blob)
     const BvhNode<R>* nodes;
     const BvhNode4f* nodes4;       // 4-wide f32 nodes (k_wf_mesh with RT_WF_NODES=0: A/B control)
-    const BvhNode4q* nodes4q;      // the same nodes, quantised to 64 B (k_wf_mesh)
+    const MeshNode4qc* nodes4q;    // the same nodes, quantised to 64 B, each with its children's back-face cone words (k_wf_mesh)
     const Bounds<R>* mesh_bounds;  // per mesh instance: exact box of its triangles (object space)
     const int32_t* mesh_ops;       // pcs of the OP_MESH ops in program order: k_wf_prims defers them, k_wf_mesh serves them one after the other
     const MeshOpRec<R>* mesh_op_recs;  // the same ops as k_wf_mesh wants them

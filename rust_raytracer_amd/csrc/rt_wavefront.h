@@ -783,13 +783,18 @@ template <typename R> constexpr uint32_t kMeshWaveLds = 1024u + 3u * 64u * uint3
 // cursor, one op entered per trip with wave-uniform records).  false: the one mesh op's record sits in SGPRs for the whole
 // kernel and none of that bookkeeping exists - the general form costs the single-mesh headline scene 16 % more vector
 // instructions and 4 % of the kernel's time (profiles/r03/ab/multi_mesh_kernel.txt), so both are kept.
+// The f32 form with quantised nodes fitted 95-96 VGPRs = 5 waves per SIMD on its own before the cone test added two registers;
+// it now asks the allocator for those 5 waves (no scratch: tools/kernel_regs.py).  At 4 waves its kernel was 4 % slower with the
+// cones than without them.
 template <typename R, bool STATS, int NODE, bool MULTI>
-__global__ void __launch_bounds__(256, RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc, WfPool<R> pool, const uint32_t* __restrict__ mesh_queue,
+__global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ? 5 : RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc, WfPool<R> pool, const uint32_t* __restrict__ mesh_queue,
                                                                  WfCounters* __restrict__ ctr, DeviceCounters* counters,
                                                                  uint32_t refill_min, uint32_t inner_min,
                                                                  uint2* __restrict__ spill, int lds_levels,
-                                                                 const uint32_t* __restrict__ n_ptr, uint32_t* __restrict__ cursor_ptr) {
+                                                                 const uint32_t* __restrict__ n_ptr, uint32_t* __restrict__ cursor_ptr,
+                                                                 uint32_t cones_on) {
     // n_ptr / cursor_ptr: length and hand-out cursor of `mesh_queue` (&ctr->n_mesh / &ctr->cursor)
+    // cones_on: 0 = every ray gets the direction word that culls nothing (RT_WF_CONES=0, the A/B control)
     extern __shared__ uint2 lds_stack2[];
     MeshStack stk;
     stk.lds = (LdsU64*)(lds_stack2 + threadIdx.x);
@@ -806,7 +811,7 @@ __global__ void __launch_bounds__(256, RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc,
     const uint32_t n = *n_ptr;
     const R t_lo = R(0.001);
     const BvhNode4f* nodes = sc.nodes4;     // child references and leaf triangle slots are absolute: one table for every mesh
-    const BvhNode4q* nodesq = sc.nodes4q;
+    const MeshNode4qc* nodesq = sc.nodes4q;
     const TriRec<R>* tris = sc.tris;
     const uint32_t n_mesh_ops = uint32_t(sc.n_mesh_ops);
     const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
@@ -839,6 +844,9 @@ __global__ void __launch_bounds__(256, RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc,
     float ivx = 0.f, ivy = 0.f, ivz = 0.f, oix = 0.f, oiy = 0.f, oiz = 0.f, tmax32 = 0.f;
     int32_t node = 0;        // >= 0 inner node, < 0 leaf
     int sp = 0;
+    // object-space direction as four signed bytes (round(127 d / |d|), -127) for the back-face cone test of the node step
+    // (NODE == 1; rt_bvh.cpp has the argument); kNoCullDir for rays that must not cull
+    uint32_t dirq = kNoCullDir;
 
     // The lane has finished every mesh of its path: the closest triangle, if one beat the other primitives' hit, is the path's hit.
     auto finish_path = [&]() {
@@ -942,6 +950,17 @@ __global__ void __launch_bounds__(256, RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc,
         tmax32 = f32_at_least(t_max - t_shift);
         node = int32_t(rb.node4_base);
         sp = 0;
+        if constexpr (NODE == 1) {
+            // |d|^2 outside the range (or NaN: a non-finite component) and meshes that hit back faces: no culling
+            const R len2 = d.x * d.x + d.y * d.y + d.z * d.z;
+            const R len_lo = sizeof(R) == 8 ? R(1e-200) : R(1e-24), len_hi = sizeof(R) == 8 ? R(1e200) : R(1e24);
+            dirq = kNoCullDir;
+            if (cones_on != 0u && (rb.flags & RT_MESH_HIT_BACK_FACES) == 0u && len2 > len_lo && len2 < len_hi) {
+                const R sc127 = R(127) / sqrt(len2);
+                const int qx = int(rint(d.x * sc127)), qy = int(rint(d.y * sc127)), qz = int(rint(d.z * sc127));
+                dirq = (uint32_t(qx) & 0xFFu) | ((uint32_t(qy) & 0xFFu) << 8) | ((uint32_t(qz) & 0xFFu) << 16) | kNoCullDir;
+            }
+        }
         return true;
     };
 
@@ -1024,11 +1043,16 @@ __global__ void __launch_bounds__(256, RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc,
                 float nr[4];
                 int32_t ch[4];
                 if constexpr (NODE == 1) {
-                    // four 16-B loads; plane = org + q * cell, so t = q * (cell * iv) + (org * iv - o * iv)
+                    // five 16-B loads from one line; plane = org + q * cell, so t = q * (cell * iv) + (org * iv - o * iv)
                     const uint4* nd = reinterpret_cast<const uint4*>(nodesq + node);
                     const uint4 h0 = nd[0], h1 = nd[1], h2 = nd[2];
                     const int4 cc = *reinterpret_cast<const int4*>(nd + 3);
-                    ch[0] = cc.x; ch[1] = cc.y; ch[2] = cc.z; ch[3] = cc.w;
+                    // a child whose triangles all face away from the ray (dir . cone > 0) counts as empty
+                    const uint4 cn = nd[4];
+                    ch[0] = __builtin_amdgcn_sdot4(int(dirq), int(cn.x), 0, false) > 0 ? kEmptyChild : cc.x;
+                    ch[1] = __builtin_amdgcn_sdot4(int(dirq), int(cn.y), 0, false) > 0 ? kEmptyChild : cc.y;
+                    ch[2] = __builtin_amdgcn_sdot4(int(dirq), int(cn.z), 0, false) > 0 ? kEmptyChild : cc.z;
+                    ch[3] = __builtin_amdgcn_sdot4(int(dirq), int(cn.w), 0, false) > 0 ? kEmptyChild : cc.w;
                     const float ax = __uint_as_float(h0.w) * ivx, ay = __uint_as_float(h1.x) * ivy, az = __uint_as_float(h1.y) * ivz;
                     const float bx = fmaf(__uint_as_float(h0.x), ivx, -oix), by = fmaf(__uint_as_float(h0.y), ivy, -oiy), bz = fmaf(__uint_as_float(h0.z), ivz, -oiz);
                     // with lo <= hi the nearer plane of an axis is `lo` for a non-negative inverse direction, `hi` otherwise:
