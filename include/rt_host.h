@@ -26,8 +26,9 @@ typedef struct RtHost RtHost;
  * reference's (README.md:21-43) plus --seed=<u64>, --gpus=<n>,
  * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
  * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations>, --noise-threshold=<x>,
- * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r> (unknown keys are
- * ignored by the reference, config.rs:146, so these are compatible).
+ * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>, --light-groups[=<max>],
+ * --light-mix=<w0>,<w1>,... (unknown keys are ignored by the reference, config.rs:146, so these
+ * are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
  * the reference (main.rs:43, golden_monkey.rs:77). */
 int rth_load(int argc, const char* const* argv, RtHost** out);
@@ -47,6 +48,14 @@ double rth_time_limit(const RtHost* host);
  * with --progressive, the estimate after every pass) filtered by rt_denoise with its first-hit AOVs.  rth_load rejects
  * --denoise with --gpus > 1. */
 uint32_t rth_denoise(const RtHost* host);
+/* Light groups (rt_render_light_groups with rt_light_groups_auto): --light-groups[=<max>] (1 .. RT_LIGHT_GROUPS_MAX, the
+ * bare flag = RT_LIGHT_GROUPS_MAX; 0 = off): rtrace also writes out_light_<g>.png per group and one console line each.
+ * --light-mix=<w0>,<w1>,... (finite numbers, at most RT_LIGHT_GROUPS_MAX; groups without an entry weigh 1) also writes
+ * out_mixed.png.  rth_light_mix copies up to `capacity` weights and returns how many were given, -1 without the flag.
+ * rth_load rejects --light-mix without --light-groups, and --light-groups with --gpus > 1, --progressive,
+ * --noise-threshold or --pipeline=mega. */
+uint32_t rth_light_groups(const RtHost* host);
+int32_t rth_light_mix(const RtHost* host, double* weights_out, uint32_t capacity);
 /* Adaptive sampling (rt_accum_set_adaptive): --noise-threshold=<x> (> 0; 0 = off) turns it on and implies passes (of
  * --progressive=<n> replicas if given, else of check_interval); --adaptive-min=<k> (>= 2), --adaptive-check=<m> (>= 1),
  * --adaptive-radius=<r> (0 .. 4): -1 = not given, the library's default.  rth_load rejects values outside these ranges,

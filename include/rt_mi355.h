@@ -455,6 +455,60 @@ int rt_accum_noise(const RtAccum* acc, double* noise_out);
  * per pixel, array after array.  A plain accumulator still writes version 1.  rt_accum_load_state refuses a version-1
  * blob for an adaptive accumulator, a version-2 blob for a plain one, and parameters that differ.                     */
 
+/* ---- Light groups: one frame per emitter (set) from one render, re-mixed on the device ------
+ * A sample's value is one product W * T (weight of the path times the value of its terminal), and only an Emissive
+ * material, a NormalDebug material or the background colour give a non-zero T: every sample belongs to exactly one
+ * emitter.  A light-group description gives a group id in 0 .. n_groups-1 to every material (material_group[n_materials]),
+ * to the background (background_group) and to the black terminals (unlit_group).  The group of a sample is
+ *     material_group[m]   its path ends on material m of type Emissive (front or back face; Sky and Sun end on their
+ *                         embedded material) or NormalDebug;
+ *     background_group    its path misses the scene and the params have a background colour;
+ *     unlit_group         every other ending: Absorbed, depth exhausted, a miss WITHOUT a background colour, and a path
+ *                         the kernels end early because its weight is zero or NaN in every channel.
+ * Entries of material_group that belong to scattering materials are never read.  A non-finite sample goes to its
+ * terminal's group like any other.
+ * Group frame g = the ordered sum of the frame (per replica the strata in order, / spp, then the replicas in order:
+ * camera.rs:229,247-253) with every sample of another group replaced by +0.0: same additions, same order, no atomics.
+ * groups_out: n_groups x owned_rows x width x 4 doubles, group-major, w = 0; the row partition of `params` is honoured.
+ *   1. The ordinary frame of the same call (rgba_out, may be NULL) is rt_render's, bit for bit, f64 and f32.
+ *   2. Group frame g equals, bit for bit where that frame is finite, rt_render's frame of the scene in which every
+ *      emitter outside g emits zero - in f64 and f32, for any replica grouping, pool size, tail compaction on or off.
+ *   3. Where every sample is >= 0 and the pixel finite, sum_g frame_g (added in group order) differs from the frame by
+ *      at most (S^2 + T + G + 2) 2^-52 relative per channel; the union of the groups' non-finite masks is the frame's.
+ * Wavefront scheduler only: RT_PIPELINE_MEGAKERNEL, collect_stats and max_depth = 0 are RT_E_UNSUPPORTED.  n_groups outside
+ * 1 .. RT_LIGHT_GROUPS_MAX, a NULL table, n_materials other than the scene's and a group id >= n_groups are RT_E_INVALID
+ * with a message naming the field; the outputs are then untouched.  rt_get_stats and the tail flag: as rt_render_device.
+ * The per-sample buffer takes 25 B per sample (24 B of radiance + the group byte).                                      */
+#define RT_LIGHT_GROUPS_MAX 16u
+typedef struct RtLightGroups {
+    uint32_t n_groups;              /* 1 .. RT_LIGHT_GROUPS_MAX                    */
+    uint32_t n_materials;           /* must equal the scene's                      */
+    const uint8_t* material_group;  /* n_materials ids                             */
+    uint32_t background_group, unlit_group;
+    uint32_t _reserved[4];          /* zero */
+} RtLightGroups;
+/* Automatic assignment (host only, needs no device; deterministic).  Group 0 is the unlit group and takes every
+ * material that does not emit and NormalDebug.  Each Emissive material that a node reachable from `world_root`
+ * references (Sky / Sun: their embedded material) gets the next id, in ascending material index; with has_background the
+ * background gets the id after the last of them (else *background_group_out = 0).  Ids that would reach max_groups or
+ * more all become max_groups - 1.  material_group_out: n_materials bytes.  *n_groups_out = highest id used + 1.
+ * max_groups outside 1 .. RT_LIGHT_GROUPS_MAX: RT_E_INVALID.                                                          */
+int rt_light_groups_auto(const RtSceneDesc* desc, uint32_t max_groups, int has_background, uint8_t* material_group_out,
+                         uint32_t* background_group_out, uint32_t* n_groups_out);
+int rt_render_light_groups(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
+                           const RtLightGroups* groups, double* groups_out, double* rgba_out_or_null);
+/* Outputs in HBM on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_render_light_groups_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
+                                  const RtLightGroups* groups, double* d_groups_out, double* d_rgba_out_or_null, void* stream);
+/* Re-mix: out = (((tint_0 * f_0) + tint_1 * f_1) + ...) per channel (f64, uncontracted, in group order), w = 0.
+ * groups: n_groups x h x w x 4 doubles (group-major), tints: n_groups x 3 doubles ON THE HOST in both forms, out: h x w x 4.
+ * A tint of exactly 0 switches its group off: its term is +0.0, the product is not formed (0 * inf and 0 * NaN would
+ * be NaN).  The result goes through rt_tonemap_rgb8_device for previews.                                              */
+int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w, uint32_t h, const double* tints,
+                 double* rgba_out);
+int rt_light_mix_device(int device, const double* d_groups, uint32_t n_groups, uint32_t w, uint32_t h, const double* tints,
+                        double* d_rgba_out, void* stream);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

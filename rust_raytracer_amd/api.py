@@ -155,6 +155,29 @@ class RtAdaptiveParams(C.Structure):
         return ap
 
 
+RT_LIGHT_GROUPS_MAX = 16
+
+
+class RtLightGroups(C.Structure):
+    """include/rt_mi355.h RtLightGroups; `make` keeps the byte table alive with the structure."""
+    _fields_ = [("n_groups", C.c_uint32), ("n_materials", C.c_uint32), ("material_group", C.POINTER(C.c_uint8)),
+                ("background_group", C.c_uint32), ("unlit_group", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
+
+    @classmethod
+    def make(cls, n_groups: int, material_group, background_group: int = 0, unlit_group: int = 0) -> "RtLightGroups":
+        table = np.ascontiguousarray(material_group, dtype=np.uint8).copy()
+        g = cls()
+        g.n_groups, g.n_materials = n_groups, table.size
+        g.material_group = table.ctypes.data_as(C.POINTER(C.c_uint8))
+        g.background_group, g.unlit_group = background_group, unlit_group
+        g._table = table
+        return g
+
+    @property
+    def table(self) -> np.ndarray:
+        return self._table
+
+
 class RtError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"rt status {status}: {message}")
@@ -300,6 +323,21 @@ def load_device_lib() -> C.CDLL:
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
+        if hasattr(lib, "rt_render_light_groups"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lg = C.POINTER(RtLightGroups)
+            for name, res, args in (
+                    ("rt_light_groups_auto", C.c_int, [C.POINTER(RtSceneDesc), C.c_uint32, C.c_int, C.c_void_p, C.POINTER(C.c_uint32),
+                                                       C.POINTER(C.c_uint32)]),
+                    ("rt_render_light_groups", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), lg, C.c_void_p,
+                                                         C.c_void_p]),
+                    ("rt_render_light_groups_device", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), lg,
+                                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+                    ("rt_light_mix", C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+                    ("rt_light_mix_device", C.c_int, [C.c_int, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                      C.c_void_p])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
         lib.rt_last_error.argtypes = []
         lib.rt_last_error.restype = C.c_char_p
         _device_lib = lib
@@ -368,6 +406,39 @@ def scene_program(desc) -> tuple:
     return ops, {"mesh_ops": int(info[0]), "groups": int(info[1]), "group_nodes": int(info[2]), "group_stack": int(info[3]),
                  "lights": int(info[4]), "volumes": int(info[5]), "group_prims": int(info[7]),
                  "split": bool(plan & 1), "vol_prims": bool(plan & 2), "multi_mesh": bool(plan & 4), "group_bvh": bool(plan & 8)}
+
+
+def light_groups_auto(desc, max_groups: int = RT_LIGHT_GROUPS_MAX, has_background: bool = False) -> RtLightGroups:
+    """rt_light_groups_auto (host only): group 0 = unlit and everything that does not emit, one group per Emissive material
+    of `world` in material order, then the background; ids beyond max_groups - 1 share that id."""
+    lib = load_device_lib()
+    d = desc.contents if hasattr(desc, "contents") else desc
+    table = np.zeros(d.n_materials, dtype=np.uint8)
+    bg, n = C.c_uint32(), C.c_uint32()
+    st = lib.rt_light_groups_auto(desc, max_groups, int(bool(has_background)), table.ctypes.data, C.byref(bg), C.byref(n))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return RtLightGroups.make(n.value, table, bg.value, 0)
+
+
+def light_mix(groups: np.ndarray, tints, device: int = 0) -> np.ndarray:
+    """rt_light_mix: (G, H, W, 4) group frames and G x 3 tints (or G scalars) -> the (H, W, 4) re-mixed frame, on the GPU."""
+    lib = load_device_lib()
+    groups = np.ascontiguousarray(groups, dtype=np.float64)
+    if groups.ndim != 4 or groups.shape[3] != 4:
+        raise ValueError(f"light_mix: expected a (G, H, W, 4) array, got {groups.shape}")
+    g, h, w = groups.shape[:3]
+    tints = np.asarray(tints, dtype=np.float64)
+    if tints.ndim == 1:
+        tints = np.repeat(tints[:, None], 3, axis=1)
+    tints = np.ascontiguousarray(tints)
+    if tints.shape != (g, 3):
+        raise ValueError(f"light_mix: expected {g} x 3 tints, got {tints.shape}")
+    out = np.empty((h, w, 4), dtype=np.float64)
+    st = lib.rt_light_mix(device, groups.ctypes.data, g, w, h, tints.ctypes.data, out.ctypes.data)
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return out
 
 
 def owned_rows(height: int, params: RtRenderParams) -> list:
@@ -520,6 +591,24 @@ class DeviceScene:
     def render_device(self, camera: RtCameraDesc, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
         st = self._lib.rt_render_device(self._h, C.byref(camera), C.byref(params),
                                         C.c_void_p(d_out_ptr), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def render_light_groups(self, camera: RtCameraDesc, params: RtRenderParams, groups: RtLightGroups) -> tuple:
+        """rt_render_light_groups: ((G, owned rows, W, 4) group frames, (owned rows, W, 4) ordinary frame) from one render."""
+        rows = self._lib.rt_owned_rows(camera.image_height, C.byref(params))
+        out_g = np.empty((groups.n_groups, rows, camera.image_width, 4), dtype=np.float64)
+        out = np.empty((rows, camera.image_width, 4), dtype=np.float64)
+        st = self._lib.rt_render_light_groups(self._h, C.byref(camera), C.byref(params), C.byref(groups), out_g.ctypes.data,
+                                              out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out_g, out
+
+    def render_light_groups_device(self, camera: RtCameraDesc, params: RtRenderParams, groups: RtLightGroups, d_groups_ptr: int,
+                                   d_out_ptr: int = 0, stream: int = 0) -> None:
+        st = self._lib.rt_render_light_groups_device(self._h, C.byref(camera), C.byref(params), C.byref(groups),
+                                                     C.c_void_p(d_groups_ptr), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
 

@@ -109,6 +109,10 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             cfg.scene_name = arg;  // config.rs:150 (last one wins)
             continue;
         }
+        if (arg == "--light-groups") {  // new: the one flag without a value (= as many groups as the library allows)
+            cfg.light_groups = RT_LIGHT_GROUPS_MAX;
+            continue;
+        }
         std::string key, value;
         if (!split_key_value(arg.substr(1), &key, &value)) continue;  // no regex match: ignored
         double d;
@@ -208,6 +212,25 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
         } else if (key == "-adaptive-radius") {  // new
             if (!parse_usize(value, &u) || u > 4) { *err = "Adaptive radius must be an integer from 0 to 4"; return false; }
             cfg.adaptive_radius = int32_t(u);
+        } else if (key == "-light-groups") {  // new: one frame per emitter (rt_render_light_groups, automatic assignment)
+            if (!parse_usize(value, &u) || u < 1 || u > RT_LIGHT_GROUPS_MAX) {
+                *err = "Light group count must be an integer from 1 to " + std::to_string(RT_LIGHT_GROUPS_MAX);
+                return false;
+            }
+            cfg.light_groups = uint32_t(u);
+        } else if (key == "-light-mix") {  // new: one weight per group, comma separated; missing entries are 1
+            cfg.light_mix.clear();
+            size_t pos = 0;
+            for (;;) {
+                const size_t comma = value.find(',', pos);
+                const std::string item = value.substr(pos, comma == std::string::npos ? std::string::npos : comma - pos);
+                if (!parse_f64(item, &d) || !std::isfinite(d)) { *err = "Light mix must be a comma-separated list of numbers"; return false; }
+                cfg.light_mix.push_back(d);
+                if (comma == std::string::npos) break;
+                pos = comma + 1;
+            }
+            if (cfg.light_mix.size() > RT_LIGHT_GROUPS_MAX) { *err = "Light mix has more than " + std::to_string(RT_LIGHT_GROUPS_MAX) + " weights"; return false; }
+            cfg.has_light_mix = true;
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -234,6 +257,18 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
     }
     if (cfg.progressive && cfg.gpus > 1) {
         *err = "--progressive renders on one GPU: it cannot be combined with --gpus > 1";
+        return false;
+    }
+    if (cfg.has_light_mix && !cfg.light_groups) {
+        *err = "--light-mix requires --light-groups";
+        return false;
+    }
+    if (cfg.light_groups && (cfg.gpus > 1 || cfg.progressive || adaptive)) {
+        *err = "--light-groups renders whole frames on one GPU: it cannot be combined with --gpus > 1, --progressive or --noise-threshold";
+        return false;
+    }
+    if (cfg.light_groups && cfg.pipeline == RT_PIPELINE_MEGAKERNEL) {
+        *err = "--light-groups runs the wavefront scheduler: it cannot be combined with --pipeline=mega";
         return false;
     }
     if (cfg.denoise && cfg.gpus > 1) {

@@ -80,6 +80,13 @@ uint32_t rth_progressive(const RtHost* host) { return host->config.progressive; 
 const char* rth_checkpoint(const RtHost* host) { return host->config.checkpoint.c_str(); }
 double rth_time_limit(const RtHost* host) { return host->config.time_limit; }
 uint32_t rth_denoise(const RtHost* host) { return host->config.denoise; }
+uint32_t rth_light_groups(const RtHost* host) { return host->config.light_groups; }
+int32_t rth_light_mix(const RtHost* host, double* weights_out, uint32_t capacity) {
+    if (!host->config.has_light_mix) return -1;
+    const auto& w = host->config.light_mix;
+    for (uint32_t k = 0; k < capacity && k < w.size(); k++) weights_out[k] = w[k];
+    return int32_t(w.size());
+}
 double rth_noise_threshold(const RtHost* host) { return host->config.noise_threshold; }
 int32_t rth_adaptive_min(const RtHost* host) { return host->config.adaptive_min; }
 int32_t rth_adaptive_check(const RtHost* host) { return host->config.adaptive_check; }

@@ -38,6 +38,9 @@ struct Config {
     std::string checkpoint;      // --checkpoint=<file>: state saved after every pass, resumed from at start-up
     double time_limit = -1.0;    // --time-limit=<seconds>: stop after the first pass that ends past it (< 0: none)
     uint32_t denoise = 0;        // --denoise=<iterations>: also write out_denoised.png (0: off)
+    uint32_t light_groups = 0;   // --light-groups[=<max>]: also write out_light_<g>.png (0: off)
+    bool has_light_mix = false;  // --light-mix=<w0>,<w1>,...: also write out_mixed.png
+    std::vector<double> light_mix;
     double noise_threshold = 0.0;  // --noise-threshold=<x>: adaptive sampling (rt_accum_set_adaptive; 0: off)
     int32_t adaptive_min = -1;     // --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>: -1 = the library's default
     int32_t adaptive_check = -1;

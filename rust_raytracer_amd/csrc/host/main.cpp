@@ -7,6 +7,7 @@
 //   --seed=<u64>  --gpus=<n>  --precision=f64|f32  --pipeline=auto|mega|wavefront  --bvh=host|device
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
+//   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...
 // With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
 // the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
 // --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
@@ -18,6 +19,11 @@
 // replicas, else of the check interval) until every pixel has converged or all replicas are done; out.png is the final
 // estimate, out_samples.png shows each pixel's share n / T of the replicas in grey, and one more console line gives the
 // samples rendered and the pixels stopped.  Works with --checkpoint, --time-limit and --denoise.
+// --light-groups[=max] also writes out_light_<g>.png, one frame per light group of the automatic assignment
+// (rt_light_groups_auto: group 0 = everything that does not emit, then one group per Emissive material, then the background),
+// all from the one render that gives out.png (rt_render_light_groups), and prints one line per group.  --light-mix=w0,w1,...
+// also writes out_mixed.png = sum_g w_g * group g (rt_light_mix; groups without a weight count once).  out.png and the other
+// console lines are those of a run without the flags.
 // With --gpus=n the frame is row-tiled in interleaved bands (rth_band_rows: 16 rows, or finer when that balances the GPUs), one
 // host thread per GPU; the tiles are assembled on the host here (bench.py shows the RCCL gather path used for the
 // multi-process launch).  RT_RTRACE_ONE_DEVICE=1 (tests on a one-GPU box): every part renders on device 0.
@@ -181,6 +187,20 @@ int main(int argc, char** argv) {
     std::vector<double> frame(size_t(W) * H * 4, 0.0);  // camera.create_buffer(), main.rs:74
     const uint32_t denoise = rth_denoise(host);         // one GPU (rth_load refuses --denoise with --gpus > 1)
     std::vector<double> denoised(denoise ? frame.size() : 0);
+    // light groups: one GPU, whole frames (rth_load refuses the other combinations)
+    const uint32_t max_groups = rth_light_groups(host);
+    const RtSceneDesc* desc = rth_scene(host);
+    std::vector<uint8_t> material_group(max_groups ? desc->n_materials : 0);
+    RtLightGroups lg{};
+    std::vector<double> group_frames, mixed;
+    if (max_groups) {
+        if (rt_light_groups_auto(desc, max_groups, int(params->has_background), material_group.data(), &lg.background_group, &lg.n_groups) != RT_OK)
+            return fail(rt_last_error());
+        lg.n_materials = desc->n_materials;
+        lg.material_group = material_group.data();
+        lg.unlit_group = 0;
+        group_frames.resize(frame.size() * lg.n_groups);
+    }
     std::vector<std::string> errors(gpus);
     std::vector<std::thread> workers;
     for (uint32_t g = 0; g < gpus; g++) {
@@ -200,7 +220,9 @@ int main(int argc, char** argv) {
             uint32_t rows = rt_owned_rows(H, &p);
             std::vector<double> part(size_t(rows) * W * 4);
             std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
-            if (rows && rt_render(scene, cam, &p, part.data()) != RT_OK) errors[g] = rt_last_error();
+            if (max_groups) {  // the group frames and the frame itself from one render
+                if (rt_render_light_groups(scene, cam, &p, &lg, group_frames.data(), part.data()) != RT_OK) errors[g] = rt_last_error();
+            } else if (rows && rt_render(scene, cam, &p, part.data()) != RT_OK) errors[g] = rt_last_error();
             if (!errors[g].empty()) return;
             uint32_t r = 0;
             for (uint32_t y = 0; y < H; y++) {
@@ -212,6 +234,14 @@ int main(int argc, char** argv) {
             // the reference prints one line per render thread (camera.rs:236); here: one per GPU
             std::printf("GPU %u finished in %s\n", g, fmt_duration(std::chrono::duration<double>(clock::now() - tg).count()).c_str());
             std::fflush(stdout);
+            double weights[RT_LIGHT_GROUPS_MAX];
+            const int32_t n_weights = max_groups ? rth_light_mix(host, weights, RT_LIGHT_GROUPS_MAX) : -1;
+            if (n_weights >= 0) {
+                double tints[3 * RT_LIGHT_GROUPS_MAX];
+                for (uint32_t k = 0; k < lg.n_groups; k++) tints[3 * k] = tints[3 * k + 1] = tints[3 * k + 2] = int32_t(k) < n_weights ? weights[k] : 1.0;
+                mixed.resize(frame.size());
+                if (rt_light_mix(rehearsal ? 0 : int(g), group_frames.data(), lg.n_groups, W, H, tints, mixed.data()) != RT_OK) errors[g] = rt_last_error();
+            }
             if (denoise) {  // the whole frame: gpus == 1
                 RtDenoiseParams dp;
                 rt_denoise_default_params(&dp);
@@ -229,11 +259,28 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "Error: %s\n", e.c_str());
             return 1;
         }
+    for (uint32_t k = 0; k < (max_groups ? lg.n_groups : 0u); k++) {  // id, what it holds, mean luminance over the finite pixels
+        std::string holds = k == 0 ? "unlit" : "";
+        for (uint32_t m = 0; m < lg.n_materials; m++)
+            if (material_group[m] == k && desc->materials[m].type == RT_MAT_EMISSIVE) holds += (holds.empty() ? "material " : ", material ") + std::to_string(m);
+        if (params->has_background && lg.background_group == k) holds += holds.empty() ? "background" : ", background";
+        const double* f = &group_frames[size_t(k) * frame.size()];
+        double sum = 0.0;
+        size_t finite = 0;
+        for (size_t i = 0; i < size_t(W) * H; i++) {
+            const double y = (0.2126 * f[4 * i] + 0.7152 * f[4 * i + 1]) + 0.0722 * f[4 * i + 2];
+            if (y - y == 0.0) { sum += y; finite++; }
+        }
+        std::printf("Light group %u: %s, mean luminance %.6g\n", k, holds.c_str(), finite ? sum / double(finite) : 0.0);
+    }
     std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());  // main.rs:78
     if (rth_save_png("out.png", frame.data(), W, H) != RT_OK) {                           // main.rs:23,80-82
         std::fprintf(stderr, "Error: %s\n", rth_last_error());
         return 1;
     }
+    for (uint32_t k = 0; k < (max_groups ? lg.n_groups : 0u); k++)
+        if (rth_save_png(("out_light_" + std::to_string(k) + ".png").c_str(), &group_frames[size_t(k) * frame.size()], W, H) != RT_OK) return fail(rth_last_error());
+    if (!mixed.empty() && rth_save_png("out_mixed.png", mixed.data(), W, H) != RT_OK) return fail(rth_last_error());
     if (denoise && rth_save_png("out_denoised.png", denoised.data(), W, H) != RT_OK) {
         std::fprintf(stderr, "Error: %s\n", rth_last_error());
         return 1;

@@ -577,6 +577,14 @@ struct RtScene {
         size_t sample_L_bytes = 0;
         double* acc = nullptr;
         size_t acc_bytes = 0;
+        // light-group renders (rt_render_light_groups): group byte per sample, running sums per (group, pixel), terminal table
+        uint8_t* sample_G = nullptr;
+        size_t sample_G_bytes = 0;
+        double* acc_g = nullptr;
+        size_t acc_g_bytes = 0;
+        uint8_t* lg_table = nullptr;
+        size_t lg_table_bytes = 0;
+        hipEvent_t ev_res[2] = {nullptr, nullptr};
         std::vector<hipEvent_t> events;
     } wf;
 };
@@ -780,9 +788,19 @@ struct AdaptivePass {
     uint32_t* cnt = nullptr;
 };
 
+// A light-group render (rt_render_light_groups): k_wf_shade records the group of every terminal and
+// k_wf_resolve_groups sums per group.  `table` (host): n_materials + 2 bytes as WfGroupLG describes them.  d_out (the
+// ordinary frame, through the unchanged k_wf_resolve) may be NULL.
+struct LightGroupPass {
+    uint32_t n_groups = 0, n_materials = 0;
+    const uint8_t* table = nullptr;
+    double* d_groups_out = nullptr;
+};
+
 template <typename R>
 int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
-                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr) {
+                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr,
+                     const LightGroupPass* lg = nullptr) {
     CameraView<R> cv = make_camera_view<R>(cam, p);
     ParamsView<R> pv = make_params_view<R>(p, owned);
     const uint64_t npix_frame = uint64_t(cam.image_width) * owned;
@@ -790,6 +808,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     const uint64_t npix = sparse ? uint64_t(ad->n_active) : npix_frame;  // pixels a replica group covers
     if (ad && p.collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
     if (npix == 0) return set_err(RT_E_INVALID, "adaptive pass without active pixels");
+    if (lg && (ad || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "light groups have no adaptive or counting kernels (collect_stats)");
     const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
     const uint32_t T = p.thread_count;
     const uint32_t t_end = t_first + n;
@@ -831,19 +850,49 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     size_t budget = size_t(env_u32("RT_WF_SAMPLE_GB", 64)) << 30;
-    size_t avail = free_b + w.sample_L_bytes;
+    size_t avail = free_b + w.sample_L_bytes + (lg ? w.sample_G_bytes : size_t(0));
     if (budget > avail / 2) budget = avail / 2;
-    uint64_t bytes_per_replica = per_replica * 24ull;
+    uint64_t bytes_per_replica = per_replica * (lg ? 25ull : 24ull);  // radiance, + the group byte of a light-group render
     uint32_t group = uint32_t(std::min<uint64_t>(n, std::max<uint64_t>(1, budget / bytes_per_replica)));
     group = (n + (n + group - 1) / group - 1) / ((n + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
     if (bytes_per_replica > avail) return set_err(RT_E_NOMEM, "per-sample radiance buffer of one replica does not fit in device memory");
-    size_t need = size_t(bytes_per_replica) * group;
+    size_t need = size_t(per_replica) * 24 * group;
     if (w.sample_L_bytes < need) {
         if (w.sample_L) (void)hipFree(w.sample_L);
         w.sample_L = nullptr;
         w.sample_L_bytes = 0;
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.sample_L), need));
         w.sample_L_bytes = need;
+    }
+    if (lg) {
+        const size_t need_g = size_t(per_replica) * group;
+        if (w.sample_G_bytes < need_g) {
+            if (w.sample_G) (void)hipFree(w.sample_G);
+            w.sample_G = nullptr;
+            w.sample_G_bytes = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.sample_G), need_g));
+            w.sample_G_bytes = need_g;
+        }
+        const size_t need_acc = group < n ? size_t(npix) * 24 * lg->n_groups : size_t(0);
+        if (w.acc_g_bytes < need_acc) {
+            if (w.acc_g) (void)hipFree(w.acc_g);
+            w.acc_g = nullptr;
+            w.acc_g_bytes = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.acc_g), need_acc));
+            w.acc_g_bytes = need_acc;
+        }
+        const size_t need_t = size_t(lg->n_materials) + 2;
+        if (w.lg_table_bytes < need_t) {
+            if (w.lg_table) (void)hipFree(w.lg_table);
+            w.lg_table = nullptr;
+            w.lg_table_bytes = 0;
+            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.lg_table), need_t));
+            w.lg_table_bytes = need_t;
+        }
+        HIP_TRY(hipMemcpyAsync(w.lg_table, lg->table, need_t, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // the host table may be the caller's stack
+        for (hipEvent_t& e : w.ev_res)
+            if (!e) HIP_TRY(hipEventCreate(&e));
     }
     const bool multi_group = group < n && !ad;  // adaptive: every group resolves into the accumulator's sums
     if (multi_group && w.acc_bytes < npix * 24) {
@@ -948,6 +997,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // HIP-event sums per kernel of the iteration loop: 4 events per iteration (before prims / intersect, after it,
     // after the mesh kernel, after shade); slot 0 = prims, 1 = traversal (mesh or combined intersect), 2 = shade
     double phase_ms[3] = {0.0, 0.0, 0.0};
+    double resolve_ms = 0.0;  // light-group renders: both resolve kernels
     uint32_t isect_launches = 0, n_groups = 0;
     for (uint32_t t0 = t_first; t0 < t_end; t0 += group) {
         n_groups++;
@@ -964,6 +1014,11 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         WfGroupSparse<R> grp_s{};
         static_cast<WfGroup<R>&>(grp_s) = grp;
         grp_s.active = sparse ? ad->active : nullptr;
+        WfGroupLG<R> grp_lg{};
+        static_cast<WfGroup<R>&>(grp_lg) = grp;
+        grp_lg.sample_G = w.sample_G;
+        grp_lg.table = w.lg_table;
+        grp_lg.n_materials = lg ? lg->n_materials : 0u;
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
         uint32_t first = uint32_t(std::min<uint64_t>(capacity, grp.total));
         pool = pool_a;
@@ -1022,7 +1077,13 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 #define RT_LAUNCH_SHADE_G(ST, L, TX, G, GRP) hipLaunchKernelGGL((k_wf_shade<R, ST, L, TX, G>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_shade) : size_t(0)) + kShadeListBytes + shade_lds_pad, stream, ds.view, cv, pv, pool, GRP, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters, static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade)
 #define RT_LAUNCH_SHADE(ST, L, TX) RT_LAUNCH_SHADE_G(ST, L, TX, WfGroup<R>, grp)
 #define RT_LAUNCH_SHADE_SPARSE(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupSparse<R>, grp_s)
-                if (sparse) {  // restarts through the active list (no counting variants)
+#define RT_LAUNCH_SHADE_LG(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupLG<R>, grp_lg)
+                if (lg) {  // the terminal's light group beside the radiance (no counting variants)
+                    if (tex) RT_LAUNCH_SHADE_LG(0, true);
+                    else if (lds_shade == 1) RT_LAUNCH_SHADE_LG(1, false);
+                    else if (lds_shade == 2) RT_LAUNCH_SHADE_LG(2, false);
+                    else RT_LAUNCH_SHADE_LG(0, false);
+                } else if (sparse) {  // restarts through the active list (no counting variants)
                     if (tex) RT_LAUNCH_SHADE_SPARSE(0, true);
                     else if (lds_shade == 1) RT_LAUNCH_SHADE_SPARSE(1, false);
                     else if (lds_shade == 2) RT_LAUNCH_SHADE_SPARSE(2, false);
@@ -1031,6 +1092,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                     if (stats) RT_LAUNCH_SHADE(true, 0, true); else RT_LAUNCH_SHADE(false, 0, true);
                 } else if (stats) { if (lds_shade == 1) RT_LAUNCH_SHADE(true, 1, false); else if (lds_shade == 2) RT_LAUNCH_SHADE(true, 2, false); else RT_LAUNCH_SHADE(true, 0, false); }
                 else { if (lds_shade == 1) RT_LAUNCH_SHADE(false, 1, false); else if (lds_shade == 2) RT_LAUNCH_SHADE(false, 2, false); else RT_LAUNCH_SHADE(false, 0, false); }
+#undef RT_LAUNCH_SHADE_LG
 #undef RT_LAUNCH_SHADE_SPARSE
 #undef RT_LAUNCH_SHADE
 #undef RT_LAUNCH_SHADE_G
@@ -1101,8 +1163,21 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
             if (sparse) hipLaunchKernelGGL(k_wf_resolve_moments<true>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
             else hipLaunchKernelGGL(k_wf_resolve_moments<false>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
         } else {
-            hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L, w.acc, npix, strata, nrep,
-                               pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
+            if (lg) HIP_TRY(hipEventRecord(w.ev_res[0], stream));
+            if (d_out)
+                hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L, w.acc, npix, strata, nrep,
+                                   pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
+            if (lg) {
+                const uint64_t blocks = ((npix + 63) / 64) * ((lg->n_groups + 3u) / 4u);
+                if (blocks > 0x7FFFFFFFull) return set_err(RT_E_UNSUPPORTED, "frame too large for the light-group resolve");
+                hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, stream, w.sample_L, w.sample_G, w.acc_g, npix,
+                                   lg->n_groups, strata, nrep, pv.spp, int(t0 == t_first), lg->d_groups_out, int(t0 + nrep >= t_end));
+                HIP_TRY(hipEventRecord(w.ev_res[1], stream));
+                HIP_TRY(hipStreamSynchronize(stream));
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, w.ev_res[0], w.ev_res[1]));
+                resolve_ms += ms;
+            }
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1133,6 +1208,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     st.n_iterations = isect_launches;
     st.n_replica_groups = n_groups;
     st.n_tail_compactions = n_compactions;
+    if (lg && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
+        std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", lg->n_groups, resolve_ms,
+                     w.sample_G_bytes, w.acc_g_bytes);
     if (stats && split && env_u32("RT_WF_DEBUG", 0)) {
         auto pct = [](unsigned long long lanes, unsigned long long waves) { return waves ? 100.0 * double(lanes) / (64.0 * double(waves)) : 0.0; };
         std::fprintf(stderr,
@@ -1425,6 +1503,11 @@ void rt_scene_destroy(RtScene* s) {
     if (s->wf.h_ctr) (void)hipHostFree(s->wf.h_ctr);
     if (s->wf.sample_L) (void)hipFree(s->wf.sample_L);
     if (s->wf.acc) (void)hipFree(s->wf.acc);
+    if (s->wf.sample_G) (void)hipFree(s->wf.sample_G);
+    if (s->wf.acc_g) (void)hipFree(s->wf.acc_g);
+    if (s->wf.lg_table) (void)hipFree(s->wf.lg_table);
+    for (hipEvent_t e : s->wf.ev_res)
+        if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : s->wf.events)
         if (e) (void)hipEventDestroy(e);
     if (s->d_counters) (void)hipFree(s->d_counters);
@@ -2242,6 +2325,166 @@ int rt_accum_noise(const RtAccum* acc, double* noise_out) {
         noise_out[i] = std::sqrt(num / (double(k) * double(k - 1))) / (mean + acc->ap.floor);
     }
     return RT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Light groups (include/rt_mi355.h)
+// ---------------------------------------------------------------------------------------------
+int rt_light_groups_auto(const RtSceneDesc* desc, uint32_t max_groups, int has_background, uint8_t* material_group_out,
+                         uint32_t* background_group_out, uint32_t* n_groups_out) {
+    using namespace rt;
+    if (!desc || !background_group_out || !n_groups_out || (desc->n_materials && !material_group_out))
+        return set_err(RT_E_INVALID, "rt_light_groups_auto: NULL argument");
+    if (max_groups < 1 || max_groups > RT_LIGHT_GROUPS_MAX) return set_err(RT_E_INVALID, "rt_light_groups_auto: max_groups outside 1 .. RT_LIGHT_GROUPS_MAX");
+    if ((desc->n_nodes && !desc->nodes) || (desc->n_child_indices && !desc->child_indices) || (desc->n_materials && !desc->materials))
+        return set_err(RT_E_INVALID, "scene description has NULL tables");
+    if (desc->world_root >= desc->n_nodes) return set_err(RT_E_INVALID, "world root out of range");
+    // materials that a node of `world` references (Sky / Sun: the embedded Emissive), each node visited once
+    std::vector<uint8_t> seen(desc->n_nodes, 0), used(desc->n_materials, 0);
+    std::vector<uint32_t> todo{desc->world_root};
+    seen[desc->world_root] = 1;
+    while (!todo.empty()) {
+        const RtNode& n = desc->nodes[todo.back()];
+        todo.pop_back();
+        if (n.material >= 0) {
+            if (uint32_t(n.material) >= desc->n_materials) return set_err(RT_E_INVALID, "material index out of range");
+            used[n.material] = 1;
+        }
+        if (n.n_children && uint64_t(n.first_child) + n.n_children > desc->n_child_indices) return set_err(RT_E_INVALID, "child range out of bounds");
+        for (uint32_t k = 0; k < n.n_children; k++) {
+            const uint32_t c = desc->child_indices[n.first_child + k];
+            if (c >= desc->n_nodes) return set_err(RT_E_INVALID, "child index out of range");
+            if (!seen[c]) { seen[c] = 1; todo.push_back(c); }
+        }
+    }
+    uint32_t next = 1, highest = 0;
+    auto take = [&]() { const uint32_t id = std::min(next++, max_groups - 1u); highest = std::max(highest, id); return id; };
+    for (uint32_t m = 0; m < desc->n_materials; m++)
+        material_group_out[m] = (used[m] && desc->materials[m].type == RT_MAT_EMISSIVE) ? uint8_t(take()) : uint8_t(0);
+    *background_group_out = has_background ? take() : 0u;
+    *n_groups_out = highest + 1u;
+    return RT_OK;
+}
+
+static int light_groups_impl(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, const RtLightGroups* groups,
+                             double* d_groups_out, double* d_rgba_out, void* stream) {
+    using namespace rt;
+    if (!scene || !camera || !params || !groups || !d_groups_out) return set_err(RT_E_INVALID, "rt_render_light_groups: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    RtScene* s = const_cast<RtScene*>(scene);
+    const uint32_t G = groups->n_groups, M = uint32_t(s->compiled.materials.size());
+    if (G < 1 || G > RT_LIGHT_GROUPS_MAX) return set_err(RT_E_INVALID, "RtLightGroups: n_groups outside 1 .. RT_LIGHT_GROUPS_MAX");
+    if (groups->n_materials != M) return set_err(RT_E_INVALID, "RtLightGroups: n_materials differs from the scene's (" + std::to_string(M) + ")");
+    if (M && !groups->material_group) return set_err(RT_E_INVALID, "RtLightGroups: material_group is NULL");
+    if (groups->background_group >= G) return set_err(RT_E_INVALID, "RtLightGroups: background_group >= n_groups");
+    if (groups->unlit_group >= G) return set_err(RT_E_INVALID, "RtLightGroups: unlit_group >= n_groups");
+    for (uint32_t m = 0; m < M; m++)
+        if (groups->material_group[m] >= G) return set_err(RT_E_INVALID, "RtLightGroups: material_group[" + std::to_string(m) + "] >= n_groups");
+    if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "light groups run the wavefront scheduler: RT_PIPELINE_MEGAKERNEL is not supported");
+    if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, "light groups with max_depth = 0");
+    if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, "light groups have no counting kernels (collect_stats)");
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t owned = owned_rows(camera->image_height, params);
+    if (owned == 0) return RT_OK;
+    // group of a path that ends on material m, of a miss, of an exhausted depth (rt_wavefront.h WfGroupLG)
+    std::vector<uint8_t> table(size_t(M) + 2);
+    for (uint32_t m = 0; m < M; m++) {
+        const int32_t t = s->compiled.materials[m].type;
+        table[m] = (t == RT_MAT_EMISSIVE || t == RT_MAT_NORMAL_DEBUG) ? groups->material_group[m] : uint8_t(groups->unlit_group);
+    }
+    table[M] = uint8_t(params->has_background ? groups->background_group : groups->unlit_group);
+    table[M + 1] = uint8_t(groups->unlit_group);
+    LightGroupPass lg;
+    lg.n_groups = G;
+    lg.n_materials = M;
+    lg.table = table.data();
+    lg.d_groups_out = d_groups_out;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    const uint32_t T = params->thread_count;
+    if (params->precision == RT_PRECISION_F32) {
+        if (!s->f32) {
+            auto ds = std::make_unique<DeviceScene<float>>();
+            int r = ds->build(s->compiled);
+            if (r != RT_OK) return r;
+            s->f32 = std::move(ds);
+        }
+        return render_wavefront<float>(s, *s->f32, *camera, *params, owned, 0, T, d_rgba_out, st, nullptr, &lg);
+    }
+    if (!s->f64) {
+        auto ds = std::make_unique<DeviceScene<double>>();
+        int r = ds->build(s->compiled);
+        if (r != RT_OK) return r;
+        s->f64 = std::move(ds);
+    }
+    return render_wavefront<double>(s, *s->f64, *camera, *params, owned, 0, T, d_rgba_out, st, nullptr, &lg);
+}
+
+int rt_render_light_groups_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, const RtLightGroups* groups,
+                                  double* d_groups_out, double* d_rgba_out_or_null, void* stream) {
+    int r = light_groups_impl(scene, camera, params, groups, d_groups_out, d_rgba_out_or_null, stream);
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
+    return r;
+}
+
+int rt_render_light_groups(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, const RtLightGroups* groups,
+                           double* groups_out, double* rgba_out_or_null) {
+    using namespace rt;
+    if (!scene || !camera || !params || !groups || !groups_out) return set_err(RT_E_INVALID, "rt_render_light_groups: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    if (groups->n_groups < 1 || groups->n_groups > RT_LIGHT_GROUPS_MAX) return set_err(RT_E_INVALID, "RtLightGroups: n_groups outside 1 .. RT_LIGHT_GROUPS_MAX");
+    HIP_TRY(hipSetDevice(scene->device));
+    const size_t frame = size_t(owned_rows(camera->image_height, params)) * camera->image_width * 4 * sizeof(double);
+    if (frame == 0) return RT_OK;
+    double* d_buf = nullptr;  // the group frames, then the ordinary frame
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_buf), frame * (size_t(groups->n_groups) + 1)));
+    double* d_frame = d_buf + (frame / sizeof(double)) * groups->n_groups;
+    int st = rt_render_light_groups_device(scene, camera, params, groups, d_buf, rgba_out_or_null ? d_frame : nullptr, nullptr);
+    if (st == RT_OK) {
+        hipError_t e = hipMemcpy(groups_out, d_buf, frame * groups->n_groups, hipMemcpyDeviceToHost);
+        if (e == hipSuccess && rgba_out_or_null) e = hipMemcpy(rgba_out_or_null, d_frame, frame, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_buf);
+    return st;
+}
+
+int rt_light_mix_device(int device, const double* d_groups, uint32_t n_groups, uint32_t w, uint32_t h, const double* tints,
+                        double* d_rgba_out, void* stream) {
+    using namespace rt;
+    if (!d_groups || !tints || !d_rgba_out) return set_err(RT_E_INVALID, "rt_light_mix: NULL argument");
+    if (n_groups < 1 || n_groups > RT_LIGHT_GROUPS_MAX) return set_err(RT_E_INVALID, "rt_light_mix: n_groups outside 1 .. RT_LIGHT_GROUPS_MAX");
+    const uint64_t npix = uint64_t(w) * h;
+    if (npix == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(device));
+    LightMixTints t{};
+    for (uint32_t k = 0; k < 3 * n_groups; k++) t.v[k] = tints[k];
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_light_mix, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, st, d_groups, n_groups, npix, t, d_rgba_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w, uint32_t h, const double* tints, double* rgba_out) {
+    using namespace rt;
+    if (!groups || !tints || !rgba_out) return set_err(RT_E_INVALID, "rt_light_mix: NULL argument");
+    if (n_groups < 1 || n_groups > RT_LIGHT_GROUPS_MAX) return set_err(RT_E_INVALID, "rt_light_mix: n_groups outside 1 .. RT_LIGHT_GROUPS_MAX");
+    const size_t frame = size_t(w) * h * 4 * sizeof(double);
+    if (frame == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(device));
+    double* d_buf = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_buf), frame * (size_t(n_groups) + 1)));
+    double* d_out = d_buf + (frame / sizeof(double)) * n_groups;
+    int st = RT_OK;
+    hipError_t e = hipMemcpy(d_buf, groups, frame * n_groups, hipMemcpyHostToDevice);
+    if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    if (st == RT_OK) st = rt_light_mix_device(device, d_buf, n_groups, w, h, tints, d_out, nullptr);
+    if (st == RT_OK) {
+        e = hipMemcpy(rgba_out, d_out, frame, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    }
+    (void)hipFree(d_buf);
+    return st;
 }
 
 int rt_get_stats(const RtScene* scene, RtRenderStats* out) {

@@ -77,6 +77,7 @@ struct WfGroup {
     uint32_t tid0;         // first replica of the group
     uint32_t strata;       // S*S
     static constexpr bool kSparse = false;
+    static constexpr bool kLightGroups = false;
 };
 
 // Replica group of an adaptive pass over a SUBSET of the pixels: `npix` counts the active pixels and
@@ -88,6 +89,21 @@ template <typename R>
 struct WfGroupSparse : WfGroup<R> {
     const uint32_t* active;
     static constexpr bool kSparse = true;
+    static constexpr bool kLightGroups = false;
+};
+
+// Replica group of a light-group render (include/rt_mi355.h): k_wf_shade also stores the group of every
+// sample's terminal, one byte beside the 24 B of sample_L.  `table` holds, per material, the group of a path that ENDS on it
+// (material_group[m] for Emissive / NormalDebug, the unlit group for every scattering material: Absorbed, zero / NaN weight),
+// then at [n_materials] the group of a miss and at [n_materials + 1] the unlit group (depth exhausted).  A type of its own
+// for the reason WfGroupSparse is one: the existing instantiations of k_wf_shade keep their code and their registers.
+template <typename R>
+struct WfGroupLG : WfGroup<R> {
+    uint8_t* sample_G;
+    const uint8_t* table;
+    uint32_t n_materials;
+    static constexpr bool kSparse = false;
+    static constexpr bool kLightGroups = true;
 };
 
 // floor(a / b) and the remainder for a < 2^51: the reciprocal estimate is off by at most one, the remainder test makes it
@@ -1229,7 +1245,12 @@ constexpr uint32_t kShadeListBytes = 2u * WF_CHUNK * 2u + 8u * 4u;  // k_wf_shad
 #ifndef RT_SHADE_WAVES
 #define RT_SHADE_WAVES 5
 #endif
-#define RT_SHADE_BOUNDS __launch_bounds__(256, TEX ? 1 : (!STATS ? RT_SHADE_WAVES : 4))
+// The light-group variant (G = WfGroupLG<R>) keeps the terminal's material index alive across shade_hit: one VGPR more than the
+// f64 kernel has at 5 waves (96 VGPRs + 16 B of scratch there), so f64 asks for 4 (no scratch); f32 fits 5.
+#ifndef RT_SHADE_WAVES_LG
+#define RT_SHADE_WAVES_LG (sizeof(R) == 8 ? 4 : RT_SHADE_WAVES)
+#endif
+#define RT_SHADE_BOUNDS __launch_bounds__(256, TEX ? 1 : (STATS ? 4 : (G::kLightGroups ? RT_SHADE_WAVES_LG : RT_SHADE_WAVES)))
 
 // Diagnostic build (-DRT_SHADE_STAMPS, tools/gpu_shade_stamps.sh): where a wave of k_wf_shade spends its cycles.  s_memtime stamps
 // around the sections of a trip, summed per wave and added to g_shade_stamps at the end; never compiled into the product.
@@ -1245,7 +1266,8 @@ __device__ unsigned long long g_shade_stamps[16];
 #define RT_STAMP(k) do { } while (0)
 #endif
 
-// G: WfGroup<R>, or WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels
+// G: WfGroup<R>, WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels, or WfGroupLG<R> to record the
+// light group of every terminal
 template <typename R, bool STATS, int LDS, bool TEX, typename G = WfGroup<R>>
 __global__ void RT_SHADE_BOUNDS k_wf_shade(SceneView<R> sc_g, CameraView<R> cam, ParamsView<R> prm, WfPool<R> pool, G grp,
                                            const uint32_t* __restrict__ queue_in, uint32_t* __restrict__ queue_out,
@@ -1324,6 +1346,10 @@ __global__ void RT_SHADE_BOUNDS k_wf_shade(SceneView<R> sc_g, CameraView<R> cam,
                 sample_L[3 * s + 0] = double(ps.radiance.x);
                 sample_L[3 * s + 1] = double(ps.radiance.y);
                 sample_L[3 * s + 2] = double(ps.radiance.z);
+                if constexpr (G::kLightGroups) {  // miss / depth exhausted / the material the path ended on (see WfGroupLG)
+                    const uint32_t m = best.pc < 0 ? grp.n_materials : (cont ? grp.n_materials + 1u : uint32_t(hit.material));
+                    grp.sample_G[s] = grp.table[m];
+                }
                 // This slot restarts in phase 2 on a new camera sample.  The part of that state which does not depend on the
                 // sample is stored HERE, by the same store instructions as the surviving lanes' values: those arrays then get
                 // their 128-byte lines whole in one go.  (Round 2 wrote every array in two parts - 70 % of a line's slots
@@ -1447,6 +1473,75 @@ __global__ void __launch_bounds__(256) k_wf_resolve(const double* __restrict__ s
     } else {
         for (int k = 0; k < 3; k++) acc[3 * pix + k] = a[k];
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Light groups (include/rt_mi355.h).
+// ---------------------------------------------------------------------------------------------
+// Resolve per light group: k_wf_resolve's ordered sums with every sample of another group replaced by +0.0 (a select, so
+// that the additions and their order are the frame's).  One thread per (pixel, group): a WAVE is 64 neighbouring pixels of
+// one group - it reads 3 x 512 B of radiance and 64 B of group bytes per stratum, all unit stride - and a thread keeps one
+// group's three sums in registers: no array indexed by the group, hence no scratch.  The four waves of a workgroup are
+// four groups of the SAME 64 pixels and the workgroups of the remaining groups follow directly in the grid, so the G-fold
+// re-reads of a line meet in the CU's vector cache or in the L2 / MALL rather than in HBM (DESIGN.md section 12 has the
+// measurement and the alternative that was weighed).
+// Carrying between replica groups as in k_wf_resolve: `acc` holds 3 doubles per (group, pixel), `out` 4 (the output layout).
+__global__ void __launch_bounds__(256) k_wf_resolve_groups(const double* __restrict__ sample_L, const uint8_t* __restrict__ sample_G,
+                                                           double* __restrict__ acc, uint64_t npix, uint32_t n_light_groups, uint32_t strata,
+                                                           uint32_t n_replicas, double spp, int first_group, double* __restrict__ out,
+                                                           int last_group) {
+    const uint32_t quads = (n_light_groups + 3u) / 4u;  // workgroups per block of 64 pixels
+    const uint32_t pix_block = blockIdx.x / quads;
+    const uint32_t g = (blockIdx.x - pix_block * quads) * 4u + (threadIdx.x >> 6);
+    const uint64_t pix = uint64_t(pix_block) * 64u + (threadIdx.x & 63u);
+    if (pix >= npix || g >= n_light_groups) return;
+    const uint64_t gp = uint64_t(g) * npix + pix;
+    double a[3];
+    for (int k = 0; k < 3; k++) a[k] = !first_group ? acc[3 * gp + k] : 0.0;
+    for (uint32_t t = 0; t < n_replicas; t++) {
+        double col[3] = {0.0, 0.0, 0.0};
+        for (uint32_t st = 0; st < strata; st++) {
+            const uint64_t s = (uint64_t(t) * strata + st) * npix + pix;
+            const bool mine = uint32_t(sample_G[s]) == g;
+            const double l0 = sample_L[3 * s + 0], l1 = sample_L[3 * s + 1], l2 = sample_L[3 * s + 2];
+            col[0] += mine ? l0 : 0.0;
+            col[1] += mine ? l1 : 0.0;
+            col[2] += mine ? l2 : 0.0;
+        }
+        for (int k = 0; k < 3; k++) a[k] += col[k] / spp;
+    }
+    if (last_group) {
+        out[4 * gp + 0] = a[0];
+        out[4 * gp + 1] = a[1];
+        out[4 * gp + 2] = a[2];
+        out[4 * gp + 3] = 0.0;
+    } else {
+        for (int k = 0; k < 3; k++) acc[3 * gp + k] = a[k];
+    }
+}
+
+// Re-mix of group frames: out = ((term_0 + term_1) + ...) per channel with term_g = tint_g * f_g, or +0.0 where tint_g is
+// exactly 0 (a group that is switched off takes its infinities and NaNs with it); w = 0.  One thread per pixel, the G frames
+// read as G unit-stride streams of 32 B per lane; the tints (<= 48 doubles) travel as a kernel argument.
+struct LightMixTints { double v[3 * 16]; };
+__global__ void __launch_bounds__(256) k_light_mix(const double* __restrict__ groups, uint32_t n_groups, uint64_t npix, LightMixTints tints,
+                                                   double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (p >= npix) return;
+    double a[3] = {0.0, 0.0, 0.0};
+    for (uint32_t g = 0; g < n_groups; g++) {
+        const double* f = groups + 4 * (uint64_t(g) * npix + p);
+        for (int k = 0; k < 3; k++) {
+            const double tint = tints.v[3 * g + k];
+            const double term = tint == 0.0 ? 0.0 : tint * f[k];
+            a[k] = g == 0 ? term : a[k] + term;
+        }
+    }
+    out[4 * p + 0] = a[0];
+    out[4 * p + 1] = a[1];
+    out[4 * p + 2] = a[2];
+    out[4 * p + 3] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------
