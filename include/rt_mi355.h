@@ -208,7 +208,8 @@ typedef struct RtRenderParams {
 typedef struct RtRenderStats {
     double   kernel_ms;           /* HIP-event time of all render kernels of the call (their own stream) */
     double   traversal_kernel_ms; /* of which: dominant kernel (megakernel, or wavefront intersect)      */
-    uint32_t n_launches;          /* launches of the dominant kernel                                     */
+    uint32_t n_launches;          /* stand-alone launches of the search kernel that opens an iteration (k_wf_prims /
+                                     k_wf_intersect; the megakernel: 1): n_iterations unless k_wf_shade runs the search */
     uint32_t pipeline_used;       /* RtPipeline actually run                                             */
     uint64_t samples;             /* W * owned_rows * spp                                                */
     uint64_t rays;                /* world.test() calls (closest-hit casts); valid if collect_stats      */
@@ -222,8 +223,8 @@ typedef struct RtRenderStats {
     uint64_t bytes_state;         /* bytes of path state the traversal kernel moves per ray it handles (0: megakernel) */
     /* wavefront scheduler only (0 otherwise): HIP-event sums per kernel of the iteration loop, and the
      * algorithmic path-state bytes (read + written) per ray that passes through each of them              */
-    double   prims_kernel_ms;     /* k_wf_prims: scene program over spheres / quads / sky / sun            */
-    double   shade_kernel_ms;     /* k_wf_shade: scatter, pdf, regeneration, queue compaction              */
+    double   prims_kernel_ms;     /* k_wf_prims (stand-alone launches): scene program over spheres / quads / sky / sun */
+    double   shade_kernel_ms;     /* k_wf_shade: scatter, pdf, regeneration, queue compaction (+ the search when fused) */
     uint64_t bytes_state_prims;
     uint64_t bytes_state_shade;
     uint32_t n_iterations;        /* wavefront iterations (one bounce of every live path each)             */

@@ -991,12 +991,26 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     const uint32_t check_every = trace_pool ? 1u : std::min<uint32_t>(32u, std::max<uint32_t>(1u, env_u32("RT_WF_CHECK", 8)));  // 4 timing events per iteration, 128 events
     const bool tex = s->compiled.needs_tex_interpreter;
     const size_t shade_lds_pad = env_u32("RT_WF_SHADE_LDS_PAD", 0);  // experiments: fewer resident blocks of the shade kernel
+    // k_wf_prims as phase 4 of k_wf_shade (rt_wavefront.h): the lean dense variant with BOTH table sets staged whole in LDS, the
+    // prims set within what the shade kernel may ask for at five workgroups per CU.  With the tables in global memory the fused
+    // kernel needs scratch (f64 32 B, f32 80 B; tools/kernel_regs.py), so those scenes - and volumes, re-built groups, the texture
+    // interpreter, sparse adaptive passes, light-group renders and the counting variants - keep the stand-alone kernel.
+    // Programs with more than one mesh op keep it too: tests/scenes/two_meshes lost 2.4 % of its frame fused (DESIGN.md section 6,
+    // round 5).  RT_WF_FUSE=0: the unfused pipeline (A/B control, reference of the tests); 2: fused wherever the kernel exists,
+    // whatever the plan says (tests, A/B).
+    const uint32_t fuse_mode = env_u32("RT_WF_FUSE", 1);
+    const bool fusable = (split || prims_only) && !vol && !groups && !tex && !lg && !sparse && lds_prims == 1 && lds_shade == 1 &&
+                         staged_prims <= shade_tables_max && fuse_mode != 0 && (!plan.multi_mesh || fuse_mode == 2);
+    const bool fuse = fusable && !stats;
+    const size_t shade_tables_lds = lds_shade == 0 ? size_t(0) : (fuse ? size_t(std::max(staged_shade, staged_prims)) : size_t(staged_shade));
 
     HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DeviceCounters), stream));
     HIP_TRY(hipEventRecord(s->ev0, stream));
     // HIP-event sums per kernel of the iteration loop: 4 events per iteration (before prims / intersect, after it,
     // after the mesh kernel, after shade); slot 0 = prims, 1 = traversal (mesh or combined intersect), 2 = shade
     double phase_ms[3] = {0.0, 0.0, 0.0};
+    uint32_t search_launches = 0;  // stand-alone k_wf_prims / k_wf_intersect launches
+    bool prims_ran[32];            // per iteration of a batch (check_every <= 32): k_wf_prims was launched
     double resolve_ms = 0.0;  // light-group renders: both resolve kernels
     uint32_t isect_launches = 0, n_groups = 0;
     for (uint32_t t0 = t_first; t0 < t_end; t0 += group) {
@@ -1036,6 +1050,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, w.queue[0]);
         else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, w.queue[0]);
         int qi = 0;
+        bool hits_ready = false;  // the hit records and the mesh queue of the current queue exist already (phase 4 of a fused k_wf_shade)
         uint32_t upper = first;  // upper bound of the queue length (never grows: slots are reused in place)
 #define RT_LAUNCH_PRIMS(ST, L, VL, GR) hipLaunchKernelGGL((k_wf_prims<R, ST, L, VL, GR>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_prims) : size_t(0)) + (GR ? lds_groups : size_t(0)) + (WF_CHUNK + 4) * 4, stream, ds.view, pool, w.queue[qi], w.mesh_queue, w.d_ctr, s->d_counters, staged_prims, group_levels)
 #define RT_LAUNCH_PRIMS_ANY() do { if (vol) { if (stats) RT_LAUNCH_PRIMS(true, 0, true, false); else RT_LAUNCH_PRIMS(false, 0, true, false); } \
@@ -1061,8 +1076,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
             const uint32_t check_now = (compact_tail && all_started) ? 1u : ((near_end || closing) ? std::min<uint32_t>(check_every, 2u) : check_every);
             for (uint32_t k = 0; k < check_now; k++) {
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
+                prims_ran[k] = (split || prims_only) && !hits_ready;
                 if (split || prims_only) {
-                    RT_LAUNCH_PRIMS_ANY();
+                    if (!hits_ready) { RT_LAUNCH_PRIMS_ANY(); search_launches++; }
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                     if (!prims_only) RT_LAUNCH_MESH(w.mesh_queue, &w.d_ctr->n_mesh, &w.d_ctr->cursor);
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
@@ -1072,13 +1088,18 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                     if (stats) { if (vol) RT_LAUNCH_ISECT(true, true); else RT_LAUNCH_ISECT(true, false); }
                     else { if (vol) RT_LAUNCH_ISECT(false, true); else RT_LAUNCH_ISECT(false, false); }
 #undef RT_LAUNCH_ISECT
+                    search_launches++;
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 }
-#define RT_LAUNCH_SHADE_G(ST, L, TX, G, GRP) hipLaunchKernelGGL((k_wf_shade<R, ST, L, TX, G>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_shade) : size_t(0)) + kShadeListBytes + shade_lds_pad, stream, ds.view, cv, pv, pool, GRP, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters, static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade)
+#define RT_LAUNCH_SHADE_F(ST, L, TX, G, GRP, FU) hipLaunchKernelGGL((k_wf_shade<R, ST, L, TX, G, FU>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), shade_tables_lds + kShadeListBytes + shade_lds_pad, stream, ds.view, cv, pv, pool, GRP, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters, static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade, w.mesh_queue)
+#define RT_LAUNCH_SHADE_G(ST, L, TX, G, GRP) RT_LAUNCH_SHADE_F(ST, L, TX, G, GRP, false)
 #define RT_LAUNCH_SHADE(ST, L, TX) RT_LAUNCH_SHADE_G(ST, L, TX, WfGroup<R>, grp)
 #define RT_LAUNCH_SHADE_SPARSE(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupSparse<R>, grp_s)
 #define RT_LAUNCH_SHADE_LG(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupLG<R>, grp_lg)
-                if (lg) {  // the terminal's light group beside the radiance (no counting variants)
+                if (fuse) {  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
+                    RT_LAUNCH_SHADE_F(false, 1, false, WfGroup<R>, grp, true);
+                    hits_ready = true;
+                } else if (lg) {  // the terminal's light group beside the radiance (no counting variants)
                     if (tex) RT_LAUNCH_SHADE_LG(0, true);
                     else if (lds_shade == 1) RT_LAUNCH_SHADE_LG(1, false);
                     else if (lds_shade == 2) RT_LAUNCH_SHADE_LG(2, false);
@@ -1096,6 +1117,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 #undef RT_LAUNCH_SHADE_SPARSE
 #undef RT_LAUNCH_SHADE
 #undef RT_LAUNCH_SHADE_G
+#undef RT_LAUNCH_SHADE_F
                 hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr);
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 qi ^= 1;
@@ -1109,6 +1131,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                 for (int ph = 0; ph < 3; ph++) {
                     it_ms[ph] = 0.f;
                     HIP_TRY(hipEventElapsedTime(&it_ms[ph], w.events[e + ph], w.events[e + ph + 1]));
+                    if (ph == 0 && (split || prims_only) && !prims_ran[e / 4]) it_ms[ph] = 0.f;  // no launch between the two events
                     phase_ms[ph] += it_ms[ph];
                 }
                 if (iter_log)  // RT_WF_ITER_LOG=1 (with RT_WF_CHECK=1 the queue length printed is the one of this very iteration)
@@ -1151,6 +1174,10 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                 pool.capacity = upper;  // n_in == capacity: the kernels address slot i for entry i again
                 pool_dev_cur = on_b ? w.pool2_dev : w.pool_dev;
                 n_compactions++;
+                if (hits_ready) {  // the hit records stayed behind and the mesh queue names the old slots: stand-alone k_wf_prims next
+                    HIP_TRY(hipMemsetAsync(&w.d_ctr->n_mesh, 0, sizeof(uint32_t), stream));
+                    hits_ready = false;
+                }
             }
         }
 #undef RT_LAUNCH_PRIMS_ANY
@@ -1204,7 +1231,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     st.traversal_kernel_ms = prims_only ? 0.0 : phase_ms[1];
     st.prims_kernel_ms = (split || prims_only) ? phase_ms[0] : 0.0;
     st.shade_kernel_ms = phase_ms[2];
-    st.n_launches = isect_launches;
+    st.n_launches = search_launches;
     st.n_iterations = isect_launches;
     st.n_replica_groups = n_groups;
     st.n_tail_compactions = n_compactions;
@@ -1236,6 +1263,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // sample index in, ray + throughput + rng + depth out (a path that ends writes 24 B of radiance instead and restarts)
     st.bytes_state_prims = 6 * sizeof(R) + 3 * sizeof(R) + 8;
     st.bytes_state_shade = (6 + 3 + 3) * sizeof(R) + 8 + 8 + 4 + 8 + (6 + 3) * sizeof(R) + 8 + 4;
+    // the lean renders of this scene run the search inside k_wf_shade: its bytes per ray are then the kernel's (a counting
+    // render is never fused, but it reports what the timed renders beside it move)
+    if (fusable) st.bytes_state_shade += st.bytes_state_prims;
     if (!split) st.mesh_rays = hc.rays;  // combined kernel: every ray's state passes through it
     return RT_OK;
 }

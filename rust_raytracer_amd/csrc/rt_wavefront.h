@@ -64,6 +64,7 @@ struct WfCounters {
     uint32_t cursor;      // next queue entry to hand out (persistent intersect / mesh kernel)
     uint32_t n_mesh;      // entries of the mesh queue (paths whose ray enters a deferred mesh's box)
     unsigned long long next_sample;  // next sample (within the group) to start
+    uint32_t n_mesh_next; // fused shade + prims: entries of the NEXT iteration's mesh queue (k_wf_advance moves it to n_mesh); 0 otherwise
 };
 
 // Sample s of a replica group -> (replica, stratum, owned pixel).  Pixels run fastest so that a
@@ -1268,17 +1269,22 @@ __device__ unsigned long long g_shade_stamps[16];
 
 // G: WfGroup<R>, WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels, or WfGroupLG<R> to record the
 // light group of every terminal
-template <typename R, bool STATS, int LDS, bool TEX, typename G = WfGroup<R>>
+// FUSED: the workgroup then runs k_wf_prims' search over the slots it has just put into the next queue (phase 4 below), so that
+// the next iteration starts at k_wf_mesh.  The prims tables are staged whole over the shade tables.  The two codes share no
+// live value: the kernel needs the larger of the two register counts, not their sum (the round-2 fusion inlined the search
+// into each lane's shading flow: 208 VGPRs, 2 waves).
+template <typename R, bool STATS, int LDS, bool TEX, typename G = WfGroup<R>, bool FUSED = false>
 __global__ void RT_SHADE_BOUNDS k_wf_shade(SceneView<R> sc_g, CameraView<R> cam, ParamsView<R> prm, WfPool<R> pool, G grp,
                                            const uint32_t* __restrict__ queue_in, uint32_t* __restrict__ queue_out,
                                            WfCounters* __restrict__ ctr, double* __restrict__ sample_L, DeviceCounters* counters,
-                                           const WfPool<R>* __restrict__ pool_dev, uint32_t staged) {
+                                           const WfPool<R>* __restrict__ pool_dev, uint32_t staged, uint32_t* __restrict__ mesh_queue) {
+    static_assert(!FUSED || (!STATS && !TEX && LDS == 1), "only the lean variant with staged tables is fused");
     extern __shared__ __align__(16) char lds_raw[];
     // the lists hold positions inside this workgroup's chunk (16 bits): 8 KB instead of 16, so that up to 23 KB of tables fit the
     // 32 KB that five workgroups per CU leave each other
     uint16_t* alive_list = reinterpret_cast<uint16_t*>(lds_raw);  // [WF_CHUNK] entries that go to the next queue
     uint16_t* dead_list = alive_list + WF_CHUNK;                 // [WF_CHUNK] entries whose path ended
-    uint32_t* lc = reinterpret_cast<uint32_t*>(dead_list + WF_CHUNK);  // [0] n_alive [1] n_dead [2,3] sample base [4] queue base
+    uint32_t* lc = reinterpret_cast<uint32_t*>(dead_list + WF_CHUNK);  // [0] n_alive [1] n_dead [2,3] sample base [4] queue base [5] n_mesh-list [6] mesh queue base (FUSED)
     char* tables = reinterpret_cast<char*>(lc + 8);
     if (threadIdx.x < 8) lc[threadIdx.x] = 0;
     SceneView<R> sc = sc_g;
@@ -1415,6 +1421,39 @@ __global__ void RT_SHADE_BOUNDS k_wf_shade(SceneView<R> sc_g, CameraView<R> cam,
     const uint32_t qb = lc[4];
     for (uint32_t j = threadIdx.x; j < n_alive; j += blockDim.x) queue_out[qb + j] = full ? begin + alive_list[j] : queue_in[begin + alive_list[j]];
     RT_STAMP(6);
+    // ---- phase 4 (FUSED): k_wf_prims' search for the slots of alive_list - the survivors and the restarts, i.e. this
+    //      workgroup's part of the next queue; their rays were written above by this workgroup (made visible by the barriers
+    //      behind phases 1 and 2).  The slots that also have to visit a mesh go to the NEXT iteration's mesh queue (counted in
+    //      n_mesh_next: n_mesh is still the length of the queue k_wf_mesh has just served).  The list of those slots reuses
+    //      dead_list, which nobody reads after phase 2; nobody reads the shade tables after phase 1. ----
+    if constexpr (FUSED) {
+        uint16_t* mesh_list = dead_list;
+        const SceneView<R> scp = scene_tables_to_lds<R, true>(sc_g, sc_g.lay, sc_g.small_blob, tables, sc_g.lay.total_bytes);
+        // every entry alive again (the steady state): chunk order, so that the loads stay unit-stride
+        const bool in_order = begin < end && n_alive == end - begin;
+        LaneCounters cnt4;
+        for (uint32_t j0 = 0; j0 < n_alive; j0 += blockDim.x) {
+            const uint32_t j = j0 + threadIdx.x;
+            bool to_mesh = false;
+            uint16_t entry = 0;
+            if (j < n_alive) {
+                entry = in_order ? uint16_t(j) : alive_list[j];
+                const uint32_t slot = full ? begin + entry : queue_in[begin + entry];
+                const Ray<R> wray = make_ray(mk<R>(at(pool.ox, slot), at(pool.oy, slot), at(pool.oz, slot)), mk<R>(at(pool.dx, slot), at(pool.dy, slot), at(pool.dz, slot)));
+                Best<R> best;
+                to_mesh = prims_search<R, false, false, false>(scp, wray, best, cnt4);
+                at(pool.ht, slot) = best.t; at(pool.hu, slot) = best.u; at(pool.hv, slot) = best.v;
+                at(pool.hpc, slot) = best.pc; at(pool.htri, slot) = best.tri;
+            }
+            lds_append(to_mesh, entry, mesh_list, &lc[5]);
+        }
+        __syncthreads();
+        const uint32_t n_list = lc[5];
+        if (threadIdx.x == 0 && n_list) lc[6] = atomicAdd(&ctr->n_mesh_next, n_list);  // ONE global atomic per workgroup
+        __syncthreads();
+        const uint32_t mb = lc[6];
+        for (uint32_t j = threadIdx.x; j < n_list; j += blockDim.x) mesh_queue[mb + j] = full ? begin + mesh_list[j] : queue_in[begin + mesh_list[j]];
+    }
 #ifdef RT_SHADE_STAMPS
     if ((threadIdx.x & 63u) == 0) {
         for (int k = 0; k < 7; k++) atomicAdd(&g_shade_stamps[k], stamp_acc[k]);
@@ -1437,7 +1476,8 @@ __global__ void k_wf_advance(WfCounters* ctr) {
     ctr->n_in = ctr->n_out;
     ctr->n_out = 0;
     ctr->cursor = 0;
-    ctr->n_mesh = 0;
+    ctr->n_mesh = ctr->n_mesh_next;  // what phase 4 of a fused k_wf_shade queued for the next k_wf_mesh; 0 after a plain k_wf_shade
+    ctr->n_mesh_next = 0;
 }
 
 // ---------------------------------------------------------------------------------------------
