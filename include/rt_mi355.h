@@ -244,6 +244,55 @@ int rt_device_count(void);
 int rt_scene_create(const RtSceneDesc* desc, int device, RtScene** out);
 void rt_scene_destroy(RtScene* scene);
 
+/* ---- Updating a scene in place: same structure, new numbers ------------------------------------------
+ * rt_scene_update gives `scene` the numbers of `desc`, which must describe the same structure as the description the
+ * scene holds: equal counts, roots, child_indices; per node type / flags / material / mesh / transform / first_child /
+ * n_children; per mesh the four counts, flags, the contents of tri_pos / tri_nrm / tri_uv and which arrays are present;
+ * per material type / tex_a / tex_b / tex_c; per texture type / a / b / c / channel / samples / width / height and which
+ * tables are present.  Free to change: RtNode.bounds and .p, every RtTransform, the meshes' positions / normals / uvs,
+ * RtMaterial.ior, RtTexture.v / .scale / texels / noise tables.  desc->flags is ignored (nothing is built).
+ * Anything else is RT_E_INVALID with a message naming the first field that differs; a description rt_scene_create
+ * refuses is refused with the same status (mesh coordinates that are not finite or beyond 1e37: RT_E_UNSUPPORTED); in
+ * both cases the scene is unchanged: everything the host can check is checked before device state is touched.
+ * After RT_OK every entry point behaves as for a scene freshly created from `desc`, in both precisions and pipelines
+ * (frames equal bit for bit, up to ties between two triangles hit at exactly equal t, which two different trees may
+ * resolve differently).  The mesh BVHs keep their trees: per mesh whose vertex arrays differ bytewise from the scene's,
+ * only those arrays are copied to the device, and kernels rewrite the triangle records, the boxes of every node format
+ * and the back-face cones in place; meshes whose arrays are equal cost nothing.  The scene program, primitive groups,
+ * lights, materials and textures are recompiled on the host and uploaded again.  A tree refitted far from the shape it
+ * was built for culls worse (never wrongly): re-create the scene when that matters.
+ * Synchronous, on the scene's own stream; must not overlap a render of the same scene.  Accumulators created before the
+ * update belong to the old scene: every call on them but rt_accum_destroy returns RT_E_INVALID.  An RT_E_DEVICE from
+ * the refit kernels themselves leaves the mesh tables undefined: destroy the scene.                                    */
+typedef struct RtSceneUpdateInfo {
+    uint32_t n_meshes_refit;      /* distinct meshes whose positions / normals / uvs differed from the scene's current ones */
+    uint32_t n_triangles_refit;
+    uint64_t bytes_uploaded;      /* vertex arrays + (first time a mesh moves) its index arrays + small tables + texels */
+    double   refit_kernel_ms;     /* HIP-event time of the refit kernels (0 when no mesh changed or nothing is on the device yet) */
+    double   total_ms;            /* host clock around the whole call, device synchronise included */
+    uint32_t _reserved[4];        /* zero */
+} RtSceneUpdateInfo;
+int rt_scene_update(RtScene* scene, const RtSceneDesc* desc, RtSceneUpdateInfo* info_or_null);
+/* Host only: RT_OK if `b` has the structure of `a`, else RT_E_INVALID with the message rt_scene_update would give. */
+int rt_scene_update_check(const RtSceneDesc* a, const RtSceneDesc* b);
+/* Host only: the refit restated on the CPU.  The tree rt_scene_create(a) builds for mesh INSTANCE `mesh`, carrying the
+ * geometry of `b` (same structure as `a`): outputs as rt_scene_mesh_cones (children relative to the mesh, cone words),
+ * plus boxes_out[24 i + 6 k ..] = the decoded quantised box of child k of node i as six floats (org + q cell: lo xyz,
+ * hi xyz; an empty child has lo > hi), tris_out = the records in the kernels' arithmetic type widened to double, and
+ * tri_order_out[slot] = the original triangle of leaf slot `slot`.  Any output pointer may be NULL.                 */
+int rt_scene_refit_mesh(const RtSceneDesc* a, const RtSceneDesc* b, uint32_t mesh, uint32_t f32, int32_t* children_out,
+                        uint32_t* cones_out, float* boxes_out, uint32_t node_capacity, uint32_t* n_nodes_out,
+                        double* tris_out, uint32_t* tri_order_out, uint32_t tri_capacity, uint32_t* n_tris_out);
+/* The same outputs, downloaded from what k_wf_mesh reads on the device for that precision (materialised if needed). */
+int rt_debug_scene_mesh(const RtScene* scene, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out,
+                        float* boxes_out, uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out,
+                        uint32_t* tri_order_out, uint32_t tri_capacity, uint32_t* n_tris_out);
+/* Diagnostic: digests of the mesh tables as they stand on the device for one precision (materialised if needed):
+ * out[0..6] = BvhNode, BvhNode4f, quantised nodes + cones, triangle records, attributes, mesh boxes, mesh op records;
+ * out[7] = number of updates so far.  A scene refitted by kernels and one whose tables the host derived from the same
+ * tree and vertices give equal digests.                                                                               */
+int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[8]);
+
 /* Number of rows the partition in `params` assigns to this part. */
 uint32_t rt_owned_rows(uint32_t image_height, const RtRenderParams* params);
 

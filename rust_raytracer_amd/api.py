@@ -178,6 +178,12 @@ class RtLightGroups(C.Structure):
         return self._table
 
 
+class RtSceneUpdateInfo(C.Structure):
+    """include/rt_mi355.h RtSceneUpdateInfo: what an rt_scene_update did."""
+    _fields_ = [("n_meshes_refit", C.c_uint32), ("n_triangles_refit", C.c_uint32), ("bytes_uploaded", C.c_uint64),
+                ("refit_kernel_ms", C.c_double), ("total_ms", C.c_double), ("_reserved", C.c_uint32 * 4)]
+
+
 class RtError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"rt status {status}: {message}")
@@ -338,6 +344,18 @@ def load_device_lib() -> C.CDLL:
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
+        if hasattr(lib, "rt_scene_update"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            mesh_out = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_uint32,
+                        C.POINTER(C.c_uint32)]
+            for name, res, args in (
+                    ("rt_scene_update", C.c_int, [C.c_void_p, C.POINTER(RtSceneDesc), C.POINTER(RtSceneUpdateInfo)]),
+                    ("rt_scene_update_check", C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(RtSceneDesc)]),
+                    ("rt_scene_refit_mesh", C.c_int, [C.POINTER(RtSceneDesc), C.POINTER(RtSceneDesc), C.c_uint32, C.c_uint32] + mesh_out),
+                    ("rt_debug_scene_mesh", C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32] + mesh_out),
+                    ("rt_debug_scene_mesh_digest", C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
         lib.rt_last_error.argtypes = []
         lib.rt_last_error.restype = C.c_char_p
         _device_lib = lib
@@ -385,6 +403,44 @@ def scene_mesh_cones(desc, mesh: int = 0, f32: bool = False) -> tuple:
     if st != RT_OK:
         raise RtError(st, lib.rt_last_error().decode())
     return children, cones.view(np.int8).reshape(-1, 4, 4), tris
+
+
+def scene_update_check(a, b) -> None:
+    """rt_scene_update_check: raises RtError (RT_E_INVALID, naming the first field that differs) unless description `b` has
+    the structure of `a`, i.e. unless DeviceScene(a).update(b) would be accepted as far as the structure goes; host only."""
+    lib = load_device_lib()
+    st = lib.rt_scene_update_check(a, b)
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+
+
+def _mesh_export(call) -> dict:
+    """The outputs shared by rt_scene_refit_mesh and rt_debug_scene_mesh; call(children, cones, boxes, node capacity, n_nodes,
+    tris, order, triangle capacity, n_tris) -> status."""
+    lib = load_device_lib()
+    nn, nt = C.c_uint32(), C.c_uint32()
+    st = call(None, None, None, 0, C.byref(nn), None, None, 0, C.byref(nt))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    children = np.zeros((nn.value, 4), dtype=np.int32)
+    cones = np.zeros((nn.value, 4), dtype=np.uint32)
+    boxes = np.zeros((nn.value, 4, 2, 3), dtype=np.float32)
+    tris = np.zeros((nt.value, 3, 3), dtype=np.float64)
+    order = np.zeros(nt.value, dtype=np.uint32)
+    st = call(children.ctypes.data, cones.ctypes.data, boxes.ctypes.data, nn.value, C.byref(nn), tris.ctypes.data, order.ctypes.data,
+              nt.value, C.byref(nt))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return {"children": children, "cones": cones.view(np.int8).reshape(-1, 4, 4), "boxes": boxes, "tris": tris, "order": order}
+
+
+def scene_refit_mesh(a, b, mesh: int = 0, f32: bool = False) -> dict:
+    """rt_scene_refit_mesh: the refit restated on the CPU (host only): the tree DeviceScene(a) builds for mesh instance
+    `mesh`, carrying the geometry of `b`.  {"children" (n, 4) int32, "cones" (n, 4, 4) int8, "boxes" (n, 4, 2, 3) float32
+    decoded quantised child boxes (lo, hi; empty child: lo > hi), "tris" (t, 3, 3) float64 (v0, e1, e2 in the kernels'
+    arithmetic type), "order" (t,) uint32 leaf slot -> original triangle}."""
+    lib = load_device_lib()
+    return _mesh_export(lambda *out: lib.rt_scene_refit_mesh(a, b, mesh, int(f32), *out))
 
 
 def scene_program(desc) -> tuple:
@@ -639,6 +695,31 @@ class DeviceScene:
         if n < 0:
             raise RtError(n, self._lib.rt_last_error().decode())
         return np.array(list(rgb)), np.array(list(tr)).reshape(max_bounces, 17)[:min(n, max_bounces)]
+
+    def update(self, desc) -> dict:
+        """rt_scene_update: gives the scene the numbers of `desc` (same structure: see include/rt_mi355.h); the mesh BVHs keep
+        their trees and are refitted on the device.  Returns RtSceneUpdateInfo as a dict.  Accumulators (ProgressiveRender)
+        created before raise the library's error from then on."""
+        info = RtSceneUpdateInfo()
+        st = self._lib.rt_scene_update(self._h, desc, C.byref(info))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return {"n_meshes_refit": info.n_meshes_refit, "n_triangles_refit": info.n_triangles_refit, "bytes_uploaded": info.bytes_uploaded,
+                "refit_kernel_ms": info.refit_kernel_ms, "total_ms": info.total_ms}
+
+    def debug_mesh(self, mesh: int = 0, f32: bool = False) -> dict:
+        """rt_debug_scene_mesh: what k_wf_mesh reads on the device for mesh instance `mesh`, in the form of
+        api.scene_refit_mesh (the precision is materialised if needed)."""
+        return _mesh_export(lambda *out: self._lib.rt_debug_scene_mesh(self._h, mesh, int(f32), *out))
+
+    def debug_mesh_digest(self, f32: bool = False) -> tuple:
+        """rt_debug_scene_mesh_digest: digests of the seven mesh tables on the device (BVH2 nodes, 4-wide f32 nodes, quantised
+        nodes + cones, records, attributes, mesh boxes, mesh op records) and the number of updates so far."""
+        out = (C.c_uint64 * 8)()
+        st = self._lib.rt_debug_scene_mesh_digest(self._h, int(f32), out)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return tuple(int(x) for x in out)
 
     def stats(self) -> RtRenderStats:
         s = RtRenderStats()

@@ -7,7 +7,7 @@
 //   --seed=<u64>  --gpus=<n>  --precision=f64|f32  --pipeline=auto|mega|wavefront  --bvh=host|device
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
-//   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...
+//   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]
 // With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
 // the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
 // --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
@@ -24,9 +24,14 @@
 // all from the one render that gives out.png (rt_render_light_groups), and prints one line per group.  --light-mix=w0,w1,...
 // also writes out_mixed.png = sum_g w_g * group g (rt_light_mix; groups without a weight count once).  out.png and the other
 // console lines are those of a run without the flags.
+// --sequence=<scene1>[,<scene2>...] renders <scene> to out.png as without the flag, then gives the SAME device scene the numbers of
+// each following scene file (rt_scene_update: same structure, other transforms / colours / lights / vertex positions; mesh BVHs
+// are refitted on the device, not rebuilt) and writes out_0001.png, out_0002.png, ... with one console line per frame (meshes
+// refit, triangles, update time).  A file of another structure stops the run with the library's message.  One GPU, whole frames.
 // With --gpus=n the frame is row-tiled in interleaved bands (rth_band_rows: 16 rows, or finer when that balances the GPUs), one
 // host thread per GPU; the tiles are assembled on the host here (bench.py shows the RCCL gather path used for the
 // multi-process launch).  RT_RTRACE_ONE_DEVICE=1 (tests on a one-GPU box): every part renders on device 0.
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <fstream>
@@ -149,10 +154,55 @@ static int render_progressive(RtHost* host, const std::function<double()>& since
     return 0;
 }
 
+// --sequence: one device scene, updated in place from one scene file to the next; returns the process exit status.
+static int render_sequence(RtHost* host, int argc, char** argv, const std::vector<std::string>& files, const std::function<double()>& since) {
+    const RtCameraDesc* cam = rth_camera(host);
+    RtScene* scene = nullptr;
+    if (rt_scene_create(rth_scene(host), 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    std::vector<double> frame(size_t(cam->image_width) * cam->image_height * 4, 0.0);
+    if (rt_render(scene, cam, rth_params(host), frame.data()) != RT_OK) return fail(rt_last_error());
+    std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());
+    if (rth_save_png("out.png", frame.data(), cam->image_width, cam->image_height) != RT_OK) return fail(rth_last_error());
+    for (size_t k = 0; k < files.size(); k++) {
+        // the same command line with this file as the scene (the last scene name wins)
+        std::vector<char*> args(argv, argv + argc);
+        std::string name = files[k];
+        args.push_back(&name[0]);
+        RtHost* next = nullptr;
+        if (rth_load(int(args.size()), args.data(), &next) != RT_OK) return fail((files[k] + ": " + rth_last_error()).c_str());
+        std::unique_ptr<RtHost, void (*)(RtHost*)> next_guard(next, rth_destroy);
+        RtSceneUpdateInfo info;
+        if (rt_scene_update(scene, rth_scene(next), &info) != RT_OK) return fail((files[k] + ": " + rt_last_error()).c_str());
+        const RtCameraDesc* c = rth_camera(next);
+        frame.assign(size_t(c->image_width) * c->image_height * 4, 0.0);
+        const double ts = since();
+        if (rt_render(scene, c, rth_params(next), frame.data()) != RT_OK) return fail(rt_last_error());
+        char out[32];
+        std::snprintf(out, sizeof out, "out_%04zu.png", k + 1);
+        std::printf("Frame %zu (%s): %u meshes refit, %u triangles, update %s, render %s\n", k + 1, out, info.n_meshes_refit, info.n_triangles_refit,
+                    fmt_duration(info.total_ms * 1e-3).c_str(), fmt_duration(since() - ts).c_str());
+        std::fflush(stdout);
+        if (rth_save_png(out, frame.data(), c->image_width, c->image_height) != RT_OK) return fail(rth_last_error());
+    }
+    std::printf("Done! Took %s. Goodbye :)\n", fmt_duration(since()).c_str());
+    return 0;
+}
+
 int main(int argc, char** argv) {
     using clock = std::chrono::steady_clock;
     auto t0 = clock::now();
     auto since = [&]() { return std::chrono::duration<double>(clock::now() - t0).count(); };
+    std::vector<std::string> sequence;  // --sequence=<scene1>[,<scene2>...] (the scene loader ignores the flag)
+    for (int i = 1; i < argc; i++)
+        if (!std::strncmp(argv[i], "--sequence=", 11)) {
+            std::string rest = argv[i] + 11;
+            for (size_t at = 0; at <= rest.size();) {
+                const size_t comma = std::min(rest.find(',', at), rest.size());
+                if (comma > at) sequence.push_back(rest.substr(at, comma - at));
+                at = comma + 1;
+            }
+        }
 
     RtHost* host = nullptr;
     if (rth_load(argc, argv, &host) != RT_OK) {
@@ -173,6 +223,14 @@ int main(int argc, char** argv) {
     if (available < 1) {
         std::fprintf(stderr, "Error: no HIP device (the render path has no CPU fallback)\n");
         return 1;
+    }
+    if (!sequence.empty()) {
+        if (gpus > 1 || rth_progressive(host) || rth_noise_threshold(host) > 0.0 || rth_light_groups(host) || rth_denoise(host))
+            return fail("--sequence renders whole frames on one GPU: it cannot be combined with --gpus > 1, --progressive, --noise-threshold, "
+                        "--light-groups or --denoise");
+        const int rc = render_sequence(host, argc, argv, sequence, since);
+        rth_destroy(host);
+        return rc;
     }
     if (rth_progressive(host) || rth_noise_threshold(host) > 0.0) {
         const int rc = render_progressive(host, since);

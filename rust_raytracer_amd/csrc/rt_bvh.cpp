@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <limits>
 
+#include "rt_refit.h"
 #include "rt_scene.h"
 
 namespace rt {
@@ -295,11 +296,8 @@ Bvh4Build collapse_bvh4(const BvhBuild& b2) { return collapse<4>(b2); }
 // A child above an ill-conditioned triangle, an empty child, a child whose cone is wider than acos(kConeMinCos) and (never seen:
 // both builders order the triangles subtree by subtree) a child whose triangles are not one run of slots get kNeutralCone.
 // ---------------------------------------------------------------------------------------------
-namespace {
-constexpr double kConeDirSlack = 0.00682;   // d_dir
-constexpr double kConeSafety = 0.001;       // d_safe
-constexpr double kConeMinCos = 0.125;       // c >= 1/8: wider cones cull next to nothing
-}  // namespace
+// d_dir, d_safe and the bound on c (kConeDirSlack, kConeSafety, kConeMinCos) and the per-child formulas stand in rt_refit.h:
+// the refit kernels of rt_scene_update evaluate the same functions on the device.
 
 ConeLimits cone_limits(bool f32) {
     if (f32) return ConeLimits{1.0 / 32.0, 1e-12, 1e12};
@@ -312,20 +310,7 @@ void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<T
     // unit normals; a triangle that is ill-conditioned has normal[3 t] = NaN
     std::vector<double> normal(3 * n_tris);
     const double kNaN = std::numeric_limits<double>::quiet_NaN();
-    for (size_t t = 0; t < n_tris; t++) {
-        const TriRec<double>& r = tris[t];
-        const double* a = r.e1;
-        const double* b = r.e2;
-        const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
-        const double la = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), lb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
-        const double lc = std::sqrt(cx * cx + cy * cy + cz * cz);
-        bool ok = std::isfinite(r.v0[0]) && std::isfinite(r.v0[1]) && std::isfinite(r.v0[2]);
-        ok = ok && la >= lim.min_edge && la <= lim.max_edge && lb >= lim.min_edge && lb <= lim.max_edge;  // false for NaN
-        ok = ok && lc >= lim.sigma * la * lb && lc > 0.0;
-        normal[3 * t] = ok ? cx / lc : kNaN;
-        normal[3 * t + 1] = ok ? cy / lc : kNaN;
-        normal[3 * t + 2] = ok ? cz / lc : kNaN;
-    }
+    for (size_t t = 0; t < n_tris; t++) rf_tri_normal(tris[t].v0, tris[t].e1, tris[t].e2, lim, &normal[3 * t]);
     // what lies below a child: the run of triangle slots [lo, hi), their number, the sum of their normals (NaN if one is bad)
     struct Below {
         uint32_t lo = UINT32_MAX, hi = 0, count = 0;
@@ -335,48 +320,7 @@ void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<T
             for (int a = 0; a < 3; a++) sum[a] += o.sum[a];
         }
     };
-    // the word of the cone around `axis` (any length) that holds the normals of the run b, or kNeutralCone
-    auto cone_around = [&](const Below& b, const double* axis) -> uint32_t {
-        const double l = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
-        if (!(l > 0.0) || !std::isfinite(l)) return kNeutralCone;  // NaN: an ill-conditioned triangle below
-        int q[3];
-        double al = 0.0;
-        for (int a = 0; a < 3; a++) { q[a] = int(std::lround(127.0 * axis[a] / l)); al += double(q[a]) * double(q[a]); }
-        al = std::sqrt(al);
-        if (!(al > 0.0)) return kNeutralCone;
-        const double ax = q[0] / al, ay = q[1] / al, az = q[2] / al;
-        double c = 1.0;
-        for (uint32_t t = b.lo; t < b.hi; t++) {
-            c = std::min(c, ax * normal[3 * size_t(t)] + ay * normal[3 * size_t(t) + 1] + az * normal[3 * size_t(t) + 2]);
-            if (c < kConeMinCos) return kNeutralCone;
-        }
-        if (!(c >= kConeMinCos)) return kNeutralCone;
-        const double s = std::sqrt(std::max(0.0, 1.0 - c * c));
-        const double w = std::ceil(al * (s + kConeDirSlack + kConeSafety));
-        if (!(w >= 1.0 && w <= 127.0)) return kNeutralCone;
-        return uint32_t(q[0] & 0xFF) | (uint32_t(q[1] & 0xFF) << 8) | (uint32_t(q[2] & 0xFF) << 16) | (uint32_t(w) << 24);
-    };
-    auto cone_word = [&](const Below& b) -> uint32_t {
-        if (b.count == 0 || b.hi - b.lo != b.count) return kNeutralCone;
-        uint32_t word = cone_around(b, b.sum);
-        if (word == kNeutralCone && b.count >= 2 && b.count <= 8 && std::isfinite(b.sum[0])) {
-            // A leaf over a fold: the sum leans towards the side with more triangles and loses the other one.  The bisector
-            // of the two normals farthest apart is the axis of the narrowest cone that holds those two.
-            uint32_t bi = b.lo, bj = b.lo;
-            double least = 2.0;
-            for (uint32_t i = b.lo; i < b.hi; i++)
-                for (uint32_t j = i + 1; j < b.hi; j++) {
-                    const double* ni = &normal[3 * size_t(i)];
-                    const double* nj = &normal[3 * size_t(j)];
-                    const double dij = ni[0] * nj[0] + ni[1] * nj[1] + ni[2] * nj[2];
-                    if (dij < least) { least = dij; bi = i; bj = j; }
-                }
-            const double mid[3] = {normal[3 * size_t(bi)] + normal[3 * size_t(bj)], normal[3 * size_t(bi) + 1] + normal[3 * size_t(bj) + 1],
-                                   normal[3 * size_t(bi) + 2] + normal[3 * size_t(bj) + 2]};
-            word = cone_around(b, mid);
-        }
-        return word;
-    };
+    auto cone_word = [&](const Below& b) -> uint32_t { return rf_cone_word(normal.data(), b.lo, b.hi, b.count, b.sum); };
     out->assign(4 * nodes4.size(), kNeutralCone);
     std::vector<Below> below(nodes4.size());  // per node: the union of its children
     for (size_t i = nodes4.size(); i-- > 0;) {  // children stand behind their parent: bottom-up without recursion

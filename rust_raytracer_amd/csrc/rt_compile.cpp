@@ -2,6 +2,7 @@
 // reference's recursive `test()` calls visit it — and emits the linear scene program plus the
 // primitive / mesh / material / light tables of rt_scene.h.  Host, one-shot, f64.
 #include "rt_compile.h"
+#include "rt_refit.h"
 
 #include <chrono>
 #include <cmath>
@@ -419,6 +420,7 @@ struct Compiler {
             if (m.tri_pos[i] >= m.n_positions || m.tri_nrm[i] >= m.n_normals) return fail(RT_E_INVALID, "triangle index out of range");
             if (m.tri_uv && m.tri_uv[i] >= 0 && (uint32_t(m.tri_uv[i]) >= m.n_uvs || !m.uvs)) return fail(RT_E_INVALID, "uv index out of range");
         }
+        if (opt.reuse) return mesh_geometry_reused(mi, m, node_base, tri_base, depth, node4_base, box);
         uint32_t max_leaf = 4;  // triangles per leaf (1..8); RT_BVH_MAX_LEAF overrides for experiments
         if (const char* e = std::getenv("RT_BVH_MAX_LEAF")) { int v = std::atoi(e); if (v >= 1 && v <= 8) max_leaf = uint32_t(v); }
         const bool timing = std::getenv("RT_COMPILE_DEBUG") != nullptr;
@@ -489,9 +491,46 @@ struct Compiler {
             }
             out.attrs.push_back(at);
         }
+        out.tri_order.insert(out.tri_order.end(), bvh.tri_order.begin(), bvh.tri_order.end());
+        out.mesh_geoms.push_back(CompiledScene::MeshGeom{mi, *node_base, uint32_t(bvh.nodes.size()), *node4_base, uint32_t(bvh4.nodes.size()), *tri_base,
+                                                         m.n_triangles, bvh.max_depth, bvh4.max_stack});
         mesh_geometry[mi] = {*node_base, *tri_base};
         mesh_depth[mi] = bvh.max_depth;
         if (bvh.max_depth > out.max_bvh_depth) out.max_bvh_depth = bvh.max_depth;
+        return true;
+    }
+
+    // rt_scene_update: the trees of opt.reuse, carrying this description's vertices
+    bool mesh_geometry_reused(int32_t mi, const RtMesh& m, uint32_t* node_base, uint32_t* tri_base, uint32_t* depth, uint32_t* node4_base, Bounds<double>* box) {
+        const CompiledScene& prev = *opt.reuse;
+        const size_t gi = out.mesh_geoms.size();
+        if (gi >= prev.mesh_geoms.size()) return fail(RT_E_INVALID, "scene update: the description has another structure (meshes)");
+        const CompiledScene::MeshGeom g = prev.mesh_geoms[gi];
+        if (g.mesh != mi || g.n_tris != m.n_triangles || g.node_base != out.nodes.size() || g.node4_base != out.nodes4.size() || g.tri_base != out.tris.size())
+            return fail(RT_E_INVALID, "scene update: the description has another structure (meshes)");
+        out.nodes.insert(out.nodes.end(), prev.nodes.begin() + g.node_base, prev.nodes.begin() + g.node_base + g.n_nodes);
+        out.nodes4.insert(out.nodes4.end(), prev.nodes4.begin() + g.node4_base, prev.nodes4.begin() + g.node4_base + g.n_nodes4);
+        out.tris.insert(out.tris.end(), prev.tris.begin() + g.tri_base, prev.tris.begin() + g.tri_base + g.n_tris);
+        out.attrs.insert(out.attrs.end(), prev.attrs.begin() + g.tri_base, prev.attrs.begin() + g.tri_base + g.n_tris);
+        out.tri_order.insert(out.tri_order.end(), prev.tri_order.begin() + g.tri_base, prev.tri_order.begin() + g.tri_base + g.n_tris);
+        out.mesh_geoms.push_back(g);
+        if (g.max_stack > out.max_bvh4_stack) out.max_bvh4_stack = g.max_stack;
+        if (g.max_depth > out.max_bvh_depth) out.max_bvh_depth = g.max_depth;
+        const bool changed = !opt.mesh_changed || (size_t(mi) < opt.mesh_changed->size() && (*opt.mesh_changed)[size_t(mi)]);
+        if (changed) {
+            *box = refit_mesh_tables(out, g, m);
+        } else {
+            for (size_t i = 0; i < prev.meshes.size(); i++)  // any instance of the mesh carries its box
+                if (prev.meshes[i].node4_base == g.node4_base) { *box = prev.mesh_bounds[i]; break; }
+        }
+        *node_base = g.node_base;
+        *tri_base = g.tri_base;
+        *depth = g.max_depth;
+        *node4_base = g.node4_base;
+        mesh_node4_base[mi] = g.node4_base;
+        mesh_box[mi] = *box;
+        mesh_geometry[mi] = {g.node_base, g.tri_base};
+        mesh_depth[mi] = g.max_depth;
         return true;
     }
 
@@ -955,6 +994,94 @@ WavefrontPlan plan_wavefront(const CompiledScene& cs) {
     p.multi_mesh = cs.mesh_ops.size() > 1;
     p.groups = p.split && !vol && !cs.group_nodes4.empty() && cs.max_group_stack <= 16 && cs.group_nodes4.size() * 64 <= 24u * 1024u;
     return p;
+}
+
+Bounds<double> refit_mesh_tables(CompiledScene& cs, const CompiledScene::MeshGeom& g, const RtMesh& m) {
+    const double kInf = std::numeric_limits<double>::infinity();
+    struct B6 { double lo[3], hi[3]; };
+    const B6 kEmpty{{kInf, kInf, kInf}, {-kInf, -kInf, -kInf}};
+    auto grow = [](B6& b, const double* lo, const double* hi) {
+        for (int a = 0; a < 3; a++) { b.lo[a] = rf_min(b.lo[a], lo[a]); b.hi[a] = rf_max(b.hi[a], hi[a]); }
+    };
+    std::vector<B6> tri_box(g.n_tris);
+    for (uint32_t slot = 0; slot < g.n_tris; slot++) {
+        const uint32_t t = cs.tri_order[g.tri_base + slot];
+        const double* p0 = m.positions + 3 * size_t(m.tri_pos[3 * size_t(t)]);
+        const double* p1 = m.positions + 3 * size_t(m.tri_pos[3 * size_t(t) + 1]);
+        const double* p2 = m.positions + 3 * size_t(m.tri_pos[3 * size_t(t) + 2]);
+        TriRec<double> r{};
+        B6 b;
+        for (int a = 0; a < 3; a++) {
+            r.v0[a] = p0[a];
+            r.e1[a] = p1[a] - p0[a];  // mesh.rs:69
+            r.e2[a] = p2[a] - p0[a];  // mesh.rs:70
+            b.lo[a] = rf_min(p0[a], rf_min(p1[a], p2[a]));
+            b.hi[a] = rf_max(p0[a], rf_max(p1[a], p2[a]));
+        }
+        tri_box[slot] = b;
+        cs.tris[g.tri_base + slot] = r;
+        TriAttr<double> at{};
+        const double* n0 = m.normals + 3 * size_t(m.tri_nrm[3 * size_t(t)]);
+        const double* n1 = m.normals + 3 * size_t(m.tri_nrm[3 * size_t(t) + 1]);
+        const double* n2 = m.normals + 3 * size_t(m.tri_nrm[3 * size_t(t) + 2]);
+        for (int a = 0; a < 3; a++) { at.n0[a] = n0[a]; at.n1[a] = n1[a]; at.n2[a] = n2[a]; }
+        const bool has_uv = m.tri_uv && m.tri_uv[3 * size_t(t)] >= 0 && m.tri_uv[3 * size_t(t) + 1] >= 0 && m.tri_uv[3 * size_t(t) + 2] >= 0;
+        at.has_uv = has_uv ? 1 : 0;
+        if (has_uv) {
+            const double* a0 = m.uvs + 3 * size_t(m.tri_uv[3 * size_t(t)]);
+            const double* a1 = m.uvs + 3 * size_t(m.tri_uv[3 * size_t(t) + 1]);
+            const double* a2 = m.uvs + 3 * size_t(m.tri_uv[3 * size_t(t) + 2]);
+            at.uv0[0] = a0[0]; at.uv0[1] = a0[1];
+            at.uv1[0] = a1[0]; at.uv1[1] = a1[1];
+            at.uv2[0] = a2[0]; at.uv2[1] = a2[1];
+        }
+        cs.attrs[g.tri_base + slot] = at;
+    }
+    auto leaf_box = [&](uint32_t first, uint32_t count) {  // first: slot inside the mesh
+        B6 b = kEmpty;
+        for (uint32_t s = first; s < first + count; s++) grow(b, tri_box[s].lo, tri_box[s].hi);
+        return b;
+    };
+    // children stand behind their parent in both trees: bottom-up = back to front
+    for (uint32_t i = g.n_nodes; i-- > 0;) {
+        BuildNode& nd = cs.nodes[g.node_base + i];
+        auto child_box = [&](int32_t c) {
+            if (c == kEmptyChild) return kEmpty;
+            if (c < 0) { const uint32_t code = uint32_t(~c); return leaf_box(code >> 3, (code & 7u) + 1u); }
+            const BuildNode& ch = cs.nodes[g.node_base + uint32_t(c)];
+            B6 b = kEmpty;
+            if (ch.c0 != kEmptyChild) grow(b, ch.lo0, ch.hi0);
+            if (ch.c1 != kEmptyChild) grow(b, ch.lo1, ch.hi1);
+            return b;
+        };
+        const B6 b0 = child_box(nd.c0), b1 = child_box(nd.c1);
+        for (int a = 0; a < 3; a++) { nd.lo0[a] = b0.lo[a]; nd.hi0[a] = b0.hi[a]; nd.lo1[a] = b1.lo[a]; nd.hi1[a] = b1.hi[a]; }
+    }
+    for (uint32_t i = g.n_nodes4; i-- > 0;) {
+        BuildNode4& nd = cs.nodes4[g.node4_base + i];
+        for (int k = 0; k < 4; k++) {
+            const int32_t c = nd.child[k];
+            B6 b = kEmpty;
+            if (c != kEmptyChild && c < 0) {
+                const uint32_t code = uint32_t(~c);
+                b = leaf_box((code >> 3) - g.tri_base, (code & 7u) + 1u);
+            } else if (c != kEmptyChild) {
+                const BuildNode4& ch = cs.nodes4[size_t(c)];
+                for (int j = 0; j < 4; j++)
+                    if (ch.child[j] != kEmptyChild) grow(b, ch.lo[j], ch.hi[j]);
+            }
+            for (int a = 0; a < 3; a++) { nd.lo[k][a] = b.lo[a]; nd.hi[k][a] = b.hi[a]; }
+        }
+    }
+    Bounds<double> box;  // as collapse<4> forms root_lo / root_hi
+    for (int a = 0; a < 3; a++) { box.lo[a] = kInf; box.hi[a] = -kInf; }
+    if (g.n_nodes4) {
+        const BuildNode4& r = cs.nodes4[g.node4_base];
+        for (int k = 0; k < 4; k++)
+            if (r.child[k] != kEmptyChild)
+                for (int a = 0; a < 3; a++) { box.lo[a] = std::min(box.lo[a], r.lo[k][a]); box.hi[a] = std::max(box.hi[a], r.hi[k][a]); }
+    }
+    return box;
 }
 
 int compile_scene(const RtSceneDesc* desc, CompiledScene* out, std::string* err, const CompileOptions& opt) {

@@ -51,12 +51,33 @@ struct CompiledScene {
     std::vector<GroupPrimRef> group_prims;
     std::vector<int32_t> group_guards;
     uint32_t max_group_stack = 0;
+    // Per DISTINCT mesh, in the order the compiler first met it: where its tables stand.  rt_scene_update keeps a mesh's
+    // tree and rewrites what depends on the vertex positions (rt_refit.h), so the leaf order is kept too.
+    struct MeshGeom {
+        int32_t mesh;                      // RtSceneDesc::meshes index
+        uint32_t node_base, n_nodes;       // BVH2 nodes in `nodes`
+        uint32_t node4_base, n_nodes4;     // 4-wide nodes in `nodes4`
+        uint32_t tri_base, n_tris;         // records in `tris` / `attrs` / `tri_order`
+        uint32_t max_depth, max_stack;
+    };
+    std::vector<MeshGeom> mesh_geoms;
+    std::vector<uint32_t> tri_order;       // per record of `tris`: the mesh's original triangle (leaf slot -> triangle)
 };
 
 struct CompileOptions {
     bool bvh_on_device = false;  // build mesh BVHs with rt_bvh_device.hip (the HIP device must already be selected)
     bool rebuild_prim_groups = true;  // re-build sphere / quad subtrees of >= 12 primitives (RT_PRIM_REBUILD=0 keeps the reference's tree)
+    // rt_scene_update: keep the mesh trees of `reuse` (a scene compiled from a description of the same structure) instead of
+    // building them.  A mesh whose entry in `mesh_changed` (per RtSceneDesc::meshes index) is set gets its records and exact
+    // boxes refitted to the new vertices (refit_mesh_tables); the others are copied.
+    const CompiledScene* reuse = nullptr;
+    const std::vector<bool>* mesh_changed = nullptr;
 };
+
+// The refit on the host, in exact f64: the triangle records, attributes and the exact child boxes of both trees of the
+// mesh `g` of `cs`, from the vertex arrays of `m` through cs.tri_order.  Min / max only: the boxes are those a bottom-up
+// pass in any order gives.  Returns the mesh's box.
+Bounds<double> refit_mesh_tables(CompiledScene& cs, const CompiledScene::MeshGeom& g, const RtMesh& m);
 
 // Which kernels the wavefront scheduler runs for a compiled scene (rt_kernels.hip render_wavefront; also reported by
 // rt_scene_program so that the choice is testable without a GPU).

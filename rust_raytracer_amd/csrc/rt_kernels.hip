@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +17,7 @@
 #include "rt_aov.h"
 #include "rt_compile.h"
 #include "rt_device.h"
+#include "rt_refit.h"
 #include "rt_wavefront.h"
 
 namespace rt {
@@ -178,6 +180,14 @@ static int set_err(int st, const std::string& msg) {
 
 struct DeviceBuffers {
     std::vector<void*> allocs;
+    uint64_t uploaded_bytes = 0;
+    // takes over an allocation of `from` (rt_scene_update: the mesh tables stay where they are)
+    void adopt(DeviceBuffers& from, const void* p) {
+        auto it = std::find(from.allocs.begin(), from.allocs.end(), const_cast<void*>(p));
+        if (it == from.allocs.end()) return;
+        allocs.push_back(*it);
+        from.allocs.erase(it);
+    }
     ~DeviceBuffers() {
         for (void* p : allocs) (void)hipFree(p);
     }
@@ -188,25 +198,11 @@ struct DeviceBuffers {
         HIP_TRY(hipMalloc(&p, bytes));
         allocs.push_back(p);
         if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        uploaded_bytes += v.size() * sizeof(T);
         *out = static_cast<const T*>(p);
         return RT_OK;
     }
 };
-
-template <typename R> R round_down(double x);
-template <typename R> R round_up(double x);
-template <> double round_down<double>(double x) { return x; }
-template <> double round_up<double>(double x) { return x; }
-template <> float round_down<float>(double x) {
-    float f = float(x);
-    if (double(f) > x) f = nextafterf(f, -INFINITY);
-    return f;
-}
-template <> float round_up<float>(double x) {
-    float f = float(x);
-    if (double(f) < x) f = nextafterf(f, INFINITY);
-    return f;
-}
 
 template <typename R, size_t N> void cast_arr(R (&dst)[N], const double (&src)[N]) {
     for (size_t i = 0; i < N; i++) dst[i] = R(src[i]);
@@ -218,7 +214,11 @@ struct DeviceScene {
     DeviceBuffers buf;
     SceneView<R> view{};
 
-    int build(const CompiledScene& cs) {
+    // keep != NULL (rt_scene_update): the mesh tables (BVH nodes of every format, triangle records, attributes) are not
+    // derived and uploaded but stay the arrays of `keep`, which the refit kernels rewrite; take_mesh_tables() moves their
+    // ownership over once the update is certain.
+    int build(const CompiledScene& cs, const DeviceScene<R>* keep = nullptr) {
+        const bool mesh_tables = keep == nullptr;
         std::vector<Bounds<R>> bounds(cs.bounds.size());
         for (size_t i = 0; i < bounds.size(); i++) {
             // list/bvh bounds are part of the reference's semantics (inverted boxes cull, B-8): nearest rounding
@@ -253,37 +253,27 @@ struct DeviceScene {
             suns[i].material = cs.suns[i].material;
             suns[i]._pad = 0;
         }
-        std::vector<BvhNode<R>> nodes(cs.nodes.size());
+        std::vector<BvhNode<R>> nodes(mesh_tables ? cs.nodes.size() : 0);
         for (size_t i = 0; i < nodes.size(); i++) {
             const BuildNode& s = cs.nodes[i];
             BvhNode<R>& n = nodes[i];
             // Conservative boxes: outward rounding plus a few ulps so that the slab arithmetic
             // never culls a triangle the exact test would hit.
-            auto pad = [](double lo, double hi, R* olo, R* ohi) {
-                if (!(lo <= hi)) { *olo = R(lo); *ohi = R(hi); return; }  // empty child box
-                double m = std::fmax(std::fabs(lo), std::fabs(hi));
-                double e = 8.0 * double(std::numeric_limits<R>::epsilon()) * std::fmax(m, hi - lo);
-                *olo = round_down<R>(lo - e);
-                *ohi = round_up<R>(hi + e);
-            };
-            for (int a = 0; a < 3; a++) {
-                pad(s.lo0[a], s.hi0[a], &n.lo0[a], &n.hi0[a]);
-                pad(s.lo1[a], s.hi1[a], &n.lo1[a], &n.hi1[a]);
+            for (int a = 0; a < 3; a++) {  // the formula: rt_refit.h
+                rf_pad_box2<R>(s.lo0[a], s.hi0[a], &n.lo0[a], &n.hi0[a]);
+                rf_pad_box2<R>(s.lo1[a], s.hi1[a], &n.lo1[a], &n.hi1[a]);
             }
             n.c0 = s.c0;
             n.c1 = s.c1;
         }
         // 4-wide f32 nodes: pad by 2^-19 x (largest |coordinate| of the mesh), round outward
-        std::vector<BvhNode4f> nodes4(cs.nodes4.size());
+        std::vector<BvhNode4f> nodes4(mesh_tables ? cs.nodes4.size() : 0);
         {
             size_t inst = 0;
             std::vector<std::pair<uint32_t, double>> pads;  // (node4_base, pad) per distinct mesh, ascending base
             for (const MeshInst& mi : cs.meshes) {
                 const Bounds<double>& b = cs.mesh_bounds[inst++];
-                double S = 0.0;
-                for (int a = 0; a < 3; a++) S = std::fmax(S, std::fmax(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
-                if (!std::isfinite(S)) S = 0.0;
-                pads.emplace_back(mi.node4_base, S * (1.0 / 524288.0));
+                pads.emplace_back(mi.node4_base, rf_pad_of_box(b.lo, b.hi));
             }
             std::sort(pads.begin(), pads.end());
             size_t pi = 0;
@@ -295,10 +285,7 @@ struct DeviceScene {
                 for (int k = 0; k < 4; k++) {
                     float* lo[3] = {&dn.lox[k], &dn.loy[k], &dn.loz[k]};
                     float* hi[3] = {&dn.hix[k], &dn.hiy[k], &dn.hiz[k]};
-                    for (int a = 0; a < 3; a++) {
-                        if (!(sn.lo[k][a] <= sn.hi[k][a])) { *lo[a] = INFINITY; *hi[a] = -INFINITY; }
-                        else { *lo[a] = round_down<float>(sn.lo[k][a] - m); *hi[a] = round_up<float>(sn.hi[k][a] + m); }
-                    }
+                    for (int a = 0; a < 3; a++) rf_pad_box4f(sn.lo[k][a], sn.hi[k][a], m, lo[a], hi[a]);
                     dn.child[k] = sn.child[k];
                     dn._pad[k] = 0;
                 }
@@ -308,7 +295,7 @@ struct DeviceScene {
         // grid, rounded outward on the grid.  k_wf_mesh evaluates t = fma(q, cell * iv, fma(org, iv, -o * iv)): cell is a
         // power of two (cell * iv exact), so against the f32-node test (fma(plane, iv, -o * iv)) there is one more rounding,
         // of a value bounded by 2 S |iv|; with it the error is < 2.5 x 2^-23 S |iv| per plane, inside the padding.
-        std::vector<BvhNode4q> nodes4q(cs.nodes4.size());
+        std::vector<BvhNode4q> nodes4q(mesh_tables ? cs.nodes4.size() : 0);
         std::vector<BvhNode4q> group_nodes;
         {
             auto pad_of = [&]() {
@@ -316,58 +303,15 @@ struct DeviceScene {
                 size_t inst = 0;
                 for (const MeshInst& mi : cs.meshes) {
                     const Bounds<double>& b = cs.mesh_bounds[inst++];
-                    double S = 0.0;
-                    for (int a = 0; a < 3; a++) S = std::fmax(S, std::fmax(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
-                    if (!std::isfinite(S)) S = 0.0;
-                    pads.emplace_back(mi.node4_base, S * (1.0 / 524288.0));
+                    pads.emplace_back(mi.node4_base, rf_pad_of_box(b.lo, b.hi));
                 }
                 std::sort(pads.begin(), pads.end());
                 return pads;
             };
-            // one node: W children, words = W / 4 grid words per axis
-            auto quantise = [](int W, const double (*lo)[3], const double (*hi)[3], const int32_t* child, double m, float* org_out,
-                               float* cell_out, uint32_t* qlo, uint32_t* qhi, int32_t* child_out) -> bool {
-                const int words = W / 4;
-                for (int a = 0; a < 3; a++) {
-                    double flo[8], fhi[8];
-                    bool real[8];
-                    double lo_min = INFINITY, hi_max = -INFINITY;
-                    for (int k = 0; k < W; k++) {
-                        real[k] = child[k] != kEmptyChild && lo[k][a] <= hi[k][a];
-                        if (!real[k]) continue;
-                        flo[k] = double(round_down<float>(lo[k][a] - m));
-                        fhi[k] = double(round_up<float>(hi[k][a] + m));
-                        lo_min = std::fmin(lo_min, flo[k]);
-                        hi_max = std::fmax(hi_max, fhi[k]);
-                    }
-                    const bool any = lo_min <= hi_max && std::isfinite(lo_min) && std::isfinite(hi_max);
-                    const double org = any ? lo_min : 0.0;  // an f32 value
-                    const double ext = any ? hi_max - org : 0.0;
-                    int e = -100;
-                    if (ext > 0.0) {
-                        e = int(std::ceil(std::log2(ext / 255.0)));
-                        while (ext / std::ldexp(1.0, e) > 255.0) e++;
-                        while (e > -100 && ext / std::ldexp(1.0, e - 1) <= 255.0) e--;
-                        e = std::max(-100, std::min(e, 120));
-                    }
-                    const double cell = std::ldexp(1.0, e);
-                    org_out[a] = float(org);
-                    cell_out[a] = float(cell);
-                    for (int w = 0; w < words; w++) { qlo[a * words + w] = 0; qhi[a * words + w] = 0; }
-                    for (int k = 0; k < W; k++) {
-                        uint32_t ql = 255u, qh = 0u;  // empty child: lo > hi, never entered
-                        if (any && real[k]) {
-                            double l = std::floor((flo[k] - org) / cell), h = std::ceil((fhi[k] - org) / cell);
-                            ql = uint32_t(std::max(0.0, std::min(l, 255.0)));
-                            qh = uint32_t(std::max(0.0, std::min(h, 255.0)));
-                            if (!(org + ql * cell <= flo[k] && org + qh * cell >= fhi[k])) return false;  // e > 120: coordinates beyond 1e38
-                        }
-                        qlo[a * words + (k >> 2)] |= ql << (8 * (k & 3));
-                        qhi[a * words + (k >> 2)] |= qh << (8 * (k & 3));
-                    }
-                }
-                for (int k = 0; k < W; k++) child_out[k] = child[k];
-                return true;
+            // one node (the formula: rt_refit.h)
+            auto quantise = [](const BuildNode4& sn, double m, BvhNode4q& qn) -> bool {
+                for (int k = 0; k < 4; k++) qn.child[k] = sn.child[k];
+                return rf_quantise4(sn.lo, sn.hi, sn.child, m, qn.org, qn.cell, qn.qlo, qn.qhi);
             };
             const auto pads4 = pad_of();
             size_t pi = 0;
@@ -375,7 +319,7 @@ struct DeviceScene {
                 while (pi + 1 < pads4.size() && pads4[pi + 1].first <= i) pi++;
                 const BuildNode4& sn = cs.nodes4[i];
                 BvhNode4q& qn = nodes4q[i];
-                if (!quantise(4, sn.lo, sn.hi, sn.child, pads4.empty() ? 0.0 : pads4[pi].second, qn.org, qn.cell, qn.qlo, qn.qhi, qn.child))
+                if (!quantise(sn, pads4.empty() ? 0.0 : pads4[pi].second, qn))
                     return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
             }
             // the primitive groups' BVHs: same node format, same padding rule (2^-19 x the largest |coordinate| of the group's box)
@@ -389,15 +333,15 @@ struct DeviceScene {
                 for (size_t i = gr.root; i < end; i++) {
                     const BuildNode4& sn = cs.group_nodes4[i];
                     BvhNode4q& qn = group_nodes[i];
-                    if (!quantise(4, sn.lo, sn.hi, sn.child, S * (1.0 / 524288.0), qn.org, qn.cell, qn.qlo, qn.qhi, qn.child))
+                    if (!quantise(sn, S * (1.0 / 524288.0), qn))
                         return set_err(RT_E_UNSUPPORTED, "group BVH node does not fit the 8-bit grid");
                 }
             }
         }
         // back-face cone words of the mesh nodes' children, with the conditioning limits of this arithmetic type (rt_bvh.cpp)
         std::vector<uint32_t> cone_words;
-        build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &cone_words);
-        std::vector<MeshNode4qc> nodes4qc(cs.nodes4.size());
+        if (mesh_tables) build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &cone_words);
+        std::vector<MeshNode4qc> nodes4qc(mesh_tables ? cs.nodes4.size() : 0);
         for (size_t i = 0; i < nodes4qc.size(); i++) {
             nodes4qc[i].node = nodes4q[i];
             for (int k = 0; k < 4; k++) nodes4qc[i].cones.word[k] = cone_words[4 * i + size_t(k)];
@@ -409,12 +353,12 @@ struct DeviceScene {
                 mesh_bounds[i].lo[a] = round_down<R>(cs.mesh_bounds[i].lo[a]);
                 mesh_bounds[i].hi[a] = round_up<R>(cs.mesh_bounds[i].hi[a]);
             }
-        std::vector<TriRec<R>> tris(cs.tris.size());
+        std::vector<TriRec<R>> tris(mesh_tables ? cs.tris.size() : 0);
         for (size_t i = 0; i < tris.size(); i++) {
             cast_arr(tris[i].v0, cs.tris[i].v0); cast_arr(tris[i].e1, cs.tris[i].e1); cast_arr(tris[i].e2, cs.tris[i].e2);
             tris[i]._pad = R(0);
         }
-        std::vector<TriAttr<R>> attrs(cs.attrs.size());
+        std::vector<TriAttr<R>> attrs(mesh_tables ? cs.attrs.size() : 0);
         for (size_t i = 0; i < attrs.size(); i++) {
             const auto& s = cs.attrs[i];
             cast_arr(attrs[i].n0, s.n0); cast_arr(attrs[i].n1, s.n1); cast_arr(attrs[i].n2, s.n2);
@@ -459,9 +403,16 @@ struct DeviceScene {
         if ((st = buf.upload(suns, &view.suns)) != RT_OK) return st;
         if ((st = buf.upload(cs.meshes, &view.meshes)) != RT_OK) return st;
         if ((st = buf.upload(volumes, &view.volumes)) != RT_OK) return st;
-        if ((st = buf.upload(nodes, &view.nodes)) != RT_OK) return st;
-        if ((st = buf.upload(nodes4, &view.nodes4)) != RT_OK) return st;
-        if ((st = buf.upload(nodes4qc, &view.nodes4q)) != RT_OK) return st;
+        if (mesh_tables) {
+            if ((st = buf.upload(nodes, &view.nodes)) != RT_OK) return st;
+            if ((st = buf.upload(nodes4, &view.nodes4)) != RT_OK) return st;
+            if ((st = buf.upload(nodes4qc, &view.nodes4q)) != RT_OK) return st;
+            if ((st = buf.upload(tris, &view.tris)) != RT_OK) return st;
+            if ((st = buf.upload(attrs, &view.attrs)) != RT_OK) return st;
+        } else {
+            view.nodes = keep->view.nodes; view.nodes4 = keep->view.nodes4; view.nodes4q = keep->view.nodes4q;
+            view.tris = keep->view.tris; view.attrs = keep->view.attrs;
+        }
         if ((st = buf.upload(mesh_bounds, &view.mesh_bounds)) != RT_OK) return st;
         if ((st = buf.upload(cs.mesh_ops, &view.mesh_ops)) != RT_OK) return st;
         view.n_mesh_ops = int32_t(cs.mesh_ops.size());
@@ -490,8 +441,6 @@ struct DeviceScene {
         if ((st = buf.upload(cs.group_guards, &view.group_guards)) != RT_OK) return st;
         view.n_group_nodes = int32_t(group_nodes.size());
         view.group_stack_levels = int32_t(cs.max_group_stack);
-        if ((st = buf.upload(tris, &view.tris)) != RT_OK) return st;
-        if ((st = buf.upload(attrs, &view.attrs)) != RT_OK) return st;
         if ((st = buf.upload(cs.materials, &view.materials)) != RT_OK) return st;
         if ((st = buf.upload(mparams, &view.material_params)) != RT_OK) return st;
         if ((st = buf.upload(textures, &view.textures)) != RT_OK) return st;
@@ -542,7 +491,123 @@ struct DeviceScene {
         HIP_TRY(hipDeviceSynchronize());
         return RT_OK;
     }
+    void take_mesh_tables(DeviceScene<R>& from) {
+        for (const void* p : {(const void*)view.nodes, (const void*)view.nodes4, (const void*)view.nodes4q, (const void*)view.tris, (const void*)view.attrs})
+            buf.adopt(from.buf, p);
+    }
 };
+
+// The description a scene currently holds, as far as rt_scene_update needs it: every structural field, and the meshes'
+// arrays (the index arrays belong to the structure, the vertex arrays tell which meshes an update moves).  Texel and noise
+// tables are not kept, only whether they are there: they are uploaded again with the small tables at every update.
+struct HeldDesc {
+    RtSceneDesc d{};
+    std::vector<RtNode> nodes;
+    std::vector<uint32_t> child_indices;
+    std::vector<RtMesh> meshes;
+    std::vector<RtMaterial> materials;
+    std::vector<RtTexture> textures;
+    struct Arrays {
+        std::vector<double> positions, normals, uvs;
+        std::vector<uint32_t> tri_pos, tri_nrm;
+        std::vector<int32_t> tri_uv;
+    };
+    std::vector<Arrays> arrays;
+    void relink() {
+        d.nodes = nodes.data(); d.child_indices = child_indices.data(); d.transforms = nullptr; d.meshes = meshes.data();
+        d.materials = materials.data(); d.textures = textures.data();
+        for (size_t i = 0; i < meshes.size(); i++) {
+            RtMesh& m = meshes[i];
+            const Arrays& a = arrays[i];
+            if (m.positions) m.positions = a.positions.data();
+            if (m.normals) m.normals = a.normals.data();
+            if (m.uvs) m.uvs = a.uvs.data();
+            if (m.tri_pos) m.tri_pos = a.tri_pos.data();
+            if (m.tri_nrm) m.tri_nrm = a.tri_nrm.data();
+            if (m.tri_uv) m.tri_uv = a.tri_uv.data();
+        }
+    }
+    // a copy of `s` (validated by the compiler); the arrays of mesh i are taken from `old` instead if keep[i]
+    void assign(const RtSceneDesc& s, HeldDesc* old = nullptr, const std::vector<bool>* keep = nullptr) {
+        static const float kThere = 0.f;
+        d = s;
+        nodes.assign(s.nodes, s.nodes + s.n_nodes);
+        child_indices.assign(s.child_indices, s.child_indices + s.n_child_indices);
+        materials.assign(s.materials, s.materials + s.n_materials);
+        textures.assign(s.textures, s.textures + s.n_textures);
+        for (RtTexture& t : textures) {  // presence only
+            if (t.texels) t.texels = &kThere;
+            if (t.perlin_vec) t.perlin_vec = reinterpret_cast<const double*>(&kThere);
+            if (t.perlin_perm) t.perlin_perm = reinterpret_cast<const uint32_t*>(&kThere);
+        }
+        std::vector<Arrays> na(s.n_meshes);
+        for (uint32_t i = 0; i < s.n_meshes; i++) {
+            const RtMesh& m = s.meshes[i];
+            if (old && keep && (*keep)[i]) { na[i] = std::move(old->arrays[i]); continue; }
+            Arrays& a = na[i];
+            if (m.positions) a.positions.assign(m.positions, m.positions + 3 * size_t(m.n_positions));
+            if (m.normals) a.normals.assign(m.normals, m.normals + 3 * size_t(m.n_normals));
+            if (m.uvs) a.uvs.assign(m.uvs, m.uvs + 3 * size_t(m.n_uvs));
+            if (m.tri_pos) a.tri_pos.assign(m.tri_pos, m.tri_pos + 3 * size_t(m.n_triangles));
+            if (m.tri_nrm) a.tri_nrm.assign(m.tri_nrm, m.tri_nrm + 3 * size_t(m.n_triangles));
+            if (m.tri_uv) a.tri_uv.assign(m.tri_uv, m.tri_uv + 3 * size_t(m.n_triangles));
+        }
+        meshes.assign(s.meshes, s.meshes + s.n_meshes);
+        arrays = std::move(na);
+        relink();
+    }
+};
+
+// "Same structure, new numbers" (include/rt_mi355.h, rt_scene_update): empty if `b` has the structure of `a`, else a message
+// that names the first field that differs.
+static std::string update_mismatch(const RtSceneDesc& a, const RtSceneDesc& b) {
+    auto idx = [](const char* table, uint32_t i, const char* field) { return std::string(table) + "[" + std::to_string(i) + "]." + field; };
+#define RT_SAME(field) if (a.field != b.field) return std::string(#field)
+    RT_SAME(n_nodes); RT_SAME(n_child_indices); RT_SAME(n_transforms); RT_SAME(n_meshes); RT_SAME(n_materials); RT_SAME(n_textures);
+    RT_SAME(world_root); RT_SAME(lights_root);
+#undef RT_SAME
+    if ((b.n_nodes && !b.nodes) || (b.n_child_indices && !b.child_indices) || (b.n_transforms && !b.transforms) || (b.n_meshes && !b.meshes) ||
+        (b.n_materials && !b.materials) || (b.n_textures && !b.textures))
+        return "a table pointer is NULL";
+    if (a.n_child_indices && std::memcmp(a.child_indices, b.child_indices, size_t(a.n_child_indices) * 4) != 0) return "child_indices";
+#define RT_SAME(table, field) if (x.field != y.field) return idx(table, i, #field)
+    for (uint32_t i = 0; i < a.n_nodes; i++) {
+        const RtNode &x = a.nodes[i], &y = b.nodes[i];
+        RT_SAME("nodes", type); RT_SAME("nodes", flags); RT_SAME("nodes", material); RT_SAME("nodes", mesh); RT_SAME("nodes", transform);
+        RT_SAME("nodes", first_child); RT_SAME("nodes", n_children);
+    }
+    for (uint32_t i = 0; i < a.n_meshes; i++) {
+        const RtMesh &x = a.meshes[i], &y = b.meshes[i];
+        RT_SAME("meshes", n_positions); RT_SAME("meshes", n_normals); RT_SAME("meshes", n_uvs); RT_SAME("meshes", n_triangles); RT_SAME("meshes", flags);
+        if (!x.positions != !y.positions) return idx("meshes", i, "positions");
+        if (!x.normals != !y.normals) return idx("meshes", i, "normals");
+        if (!x.uvs != !y.uvs) return idx("meshes", i, "uvs");
+        if (!x.tri_pos != !y.tri_pos) return idx("meshes", i, "tri_pos");
+        if (!x.tri_nrm != !y.tri_nrm) return idx("meshes", i, "tri_nrm");
+        if (!x.tri_uv != !y.tri_uv) return idx("meshes", i, "tri_uv");
+        const size_t nb = size_t(x.n_triangles) * 12;
+        if (x.tri_pos && std::memcmp(x.tri_pos, y.tri_pos, nb) != 0) return idx("meshes", i, "tri_pos");
+        if (x.tri_nrm && std::memcmp(x.tri_nrm, y.tri_nrm, nb) != 0) return idx("meshes", i, "tri_nrm");
+        if (x.tri_uv && std::memcmp(x.tri_uv, y.tri_uv, nb) != 0) return idx("meshes", i, "tri_uv");
+    }
+    for (uint32_t i = 0; i < a.n_materials; i++) {
+        const RtMaterial &x = a.materials[i], &y = b.materials[i];
+        RT_SAME("materials", type); RT_SAME("materials", tex_a); RT_SAME("materials", tex_b); RT_SAME("materials", tex_c);
+    }
+    for (uint32_t i = 0; i < a.n_textures; i++) {
+        const RtTexture &x = a.textures[i], &y = b.textures[i];
+        RT_SAME("textures", type); RT_SAME("textures", a); RT_SAME("textures", b); RT_SAME("textures", c); RT_SAME("textures", channel);
+        RT_SAME("textures", samples); RT_SAME("textures", width); RT_SAME("textures", height);
+        if (!x.texels != !y.texels) return idx("textures", i, "texels");
+        if (!x.perlin_vec != !y.perlin_vec) return idx("textures", i, "perlin_vec");
+        if (!x.perlin_perm != !y.perlin_perm) return idx("textures", i, "perlin_perm");
+    }
+#undef RT_SAME
+    return std::string();
+}
+static std::string update_mismatch_message(const std::string& field) {
+    return "scene update: the description has another structure than the scene (first difference: " + field + ")";
+}
 
 }  // namespace rt
 
@@ -558,6 +623,11 @@ struct RtScene {
     RtRenderStats stats{};
     int32_t* tail_flag = nullptr;  // rt_scene_set_tail_flag: set to 1 when a render stops filling the GPU (frame pipelining)
     uint64_t content_digest = 0;   // of everything the description points at (rt::scene_digest): checkpoints name their scene by it
+    // rt_scene_update: the description the scene holds, a counter of its updates (accumulators belong to one generation) and
+    // the device-side refit state per distinct mesh (CompiledScene::mesh_geoms order; empty until a mesh is first moved)
+    rt::HeldDesc held;
+    uint64_t generation = 0;
+    std::vector<rt::RefitMesh> refit;
     // wavefront pipeline resources (allocated on first use, reused between renders)
     struct Wavefront {
         uint32_t capacity = 0;
@@ -1451,6 +1521,7 @@ static int tonemap_launch(const double* d_rgba, uint64_t npix, double scale, uin
 
 struct RtAccum {
     RtScene* scene = nullptr;      // not owned: must outlive every call but rt_accum_destroy
+    uint64_t generation = 0;       // RtScene::generation at rt_accum_create: an accumulator does not outlive an rt_scene_update
     int device = 0;                // the scene's device (rt_accum_destroy does not touch the scene)
     RtCameraDesc camera{};
     RtRenderParams params{};       // as created (pipeline / collect_stats: the defaults of rt_accum_render)
@@ -1477,6 +1548,107 @@ struct RtAccum {
     size_t npix() const { return size_t(owned) * camera.image_width; }
     bool decision_point(uint32_t kk) const { return adaptive && kk >= ap.min_replicas && kk < T && (kk - ap.min_replicas) % ap.check_interval == 0; }
 };
+
+namespace rt {
+// What k_wf_mesh reads of one mesh instance, in the form of rt_scene_refit_mesh / rt_debug_scene_mesh: per node the four
+// child references (relative to the mesh), cone words and decoded quantised boxes (org + q cell in f32: lo xyz, hi xyz; an
+// empty child has lo > hi), per slot the record widened to double and the original triangle.
+struct MeshExportOut {
+    int32_t* children; uint32_t* cones; float* boxes; uint32_t node_capacity; uint32_t* n_nodes;
+    double* tris; uint32_t* tri_order; uint32_t tri_capacity; uint32_t* n_tris;
+};
+static bool mesh_export_range(const CompiledScene& cs, uint32_t mesh, const CompiledScene::MeshGeom** g_out) {
+    if (mesh >= cs.meshes.size()) return false;
+    for (const CompiledScene::MeshGeom& g : cs.mesh_geoms)
+        if (g.node4_base == cs.meshes[mesh].node4_base) { *g_out = &g; return true; }
+    return false;
+}
+template <typename R>
+static void mesh_export(const CompiledScene::MeshGeom& g, const MeshNode4qc* nodes, const TriRec<R>* tris, const uint32_t* order, const MeshExportOut& o) {
+    *o.n_nodes = g.n_nodes4;
+    *o.n_tris = g.n_tris;
+    for (uint32_t i = 0; i < g.n_nodes4 && i < o.node_capacity; i++) {
+        const MeshNode4qc& n = nodes[i];
+        for (int k = 0; k < 4; k++) {
+            int32_t ch = n.node.child[k];
+            if (ch != kEmptyChild) {
+                if (ch >= 0) ch -= int32_t(g.node4_base);
+                else { const uint32_t code = uint32_t(~ch); ch = ~int32_t((((code >> 3) - g.tri_base) << 3) | (code & 7u)); }
+            }
+            if (o.children) o.children[4 * size_t(i) + size_t(k)] = ch;
+            if (o.cones) o.cones[4 * size_t(i) + size_t(k)] = n.cones.word[k];
+            if (o.boxes)
+                for (int a = 0; a < 3; a++) {
+                    o.boxes[24 * size_t(i) + 6 * size_t(k) + size_t(a)] = n.node.org[a] + float((n.node.qlo[a] >> (8 * k)) & 255u) * n.node.cell[a];
+                    o.boxes[24 * size_t(i) + 6 * size_t(k) + 3 + size_t(a)] = n.node.org[a] + float((n.node.qhi[a] >> (8 * k)) & 255u) * n.node.cell[a];
+                }
+        }
+    }
+    for (uint32_t t = 0; t < g.n_tris && t < o.tri_capacity; t++) {
+        if (o.tris)
+            for (int a = 0; a < 3; a++) {
+                o.tris[9 * size_t(t) + size_t(a)] = double(tris[t].v0[a]);
+                o.tris[9 * size_t(t) + 3 + size_t(a)] = double(tris[t].e1[a]);
+                o.tris[9 * size_t(t) + 6 + size_t(a)] = double(tris[t].e2[a]);
+            }
+        if (o.tri_order) o.tri_order[t] = order[t];
+    }
+}
+// The host builder's tables of one mesh in arithmetic type R (as DeviceScene<R>::build derives them)
+template <typename R>
+static int mesh_export_host(const CompiledScene& cs, const CompiledScene::MeshGeom& g, uint32_t mesh, const MeshExportOut& o) {
+    std::vector<uint32_t> words;
+    build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &words);
+    const double pad = rf_pad_of_box(cs.mesh_bounds[mesh].lo, cs.mesh_bounds[mesh].hi);
+    std::vector<MeshNode4qc> nodes(g.n_nodes4);
+    for (uint32_t i = 0; i < g.n_nodes4; i++) {
+        const BuildNode4& sn = cs.nodes4[g.node4_base + i];
+        BvhNode4q& q = nodes[i].node;
+        if (!rf_quantise4(sn.lo, sn.hi, sn.child, pad, q.org, q.cell, q.qlo, q.qhi)) return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
+        for (int k = 0; k < 4; k++) { q.child[k] = sn.child[k]; nodes[i].cones.word[k] = words[4 * size_t(g.node4_base + i) + size_t(k)]; }
+    }
+    std::vector<TriRec<R>> tris(g.n_tris);
+    for (uint32_t t = 0; t < g.n_tris; t++) {
+        const TriRec<double>& r = cs.tris[g.tri_base + t];
+        cast_arr(tris[t].v0, r.v0); cast_arr(tris[t].e1, r.e1); cast_arr(tris[t].e2, r.e2);
+    }
+    mesh_export<R>(g, nodes.data(), tris.data(), cs.tri_order.data() + g.tri_base, o);
+    return RT_OK;
+}
+template <typename R>
+static int mesh_export_device(const CompiledScene& cs, const CompiledScene::MeshGeom& g, const DeviceScene<R>& ds, const MeshExportOut& o) {
+    std::vector<MeshNode4qc> nodes(g.n_nodes4);
+    std::vector<TriRec<R>> tris(g.n_tris);
+    if (g.n_nodes4) HIP_TRY(hipMemcpy(nodes.data(), ds.view.nodes4q + g.node4_base, nodes.size() * sizeof(MeshNode4qc), hipMemcpyDeviceToHost));
+    if (g.n_tris) HIP_TRY(hipMemcpy(tris.data(), ds.view.tris + g.tri_base, tris.size() * sizeof(TriRec<R>), hipMemcpyDeviceToHost));
+    mesh_export<R>(g, nodes.data(), tris.data(), cs.tri_order.data() + g.tri_base, o);
+    return RT_OK;
+}
+
+// The refit kernels of one arithmetic type over every moved mesh, enqueued on the scene's stream; `ds` holds the mesh tables.
+template <typename R>
+static int refit_typed(RtScene* s, const CompiledScene& cs, const std::vector<uint32_t>& moved, DeviceScene<R>& ds) {
+    for (uint32_t gi : moved) {
+        const CompiledScene::MeshGeom& g = cs.mesh_geoms[gi];
+        RefitTarget<R> t{};
+        t.nodes = const_cast<BvhNode<R>*>(ds.view.nodes) + g.node_base;
+        t.nodes4 = const_cast<BvhNode4f*>(ds.view.nodes4) + g.node4_base;
+        t.nodes4q = const_cast<MeshNode4qc*>(ds.view.nodes4q) + g.node4_base;
+        t.tris = const_cast<TriRec<R>*>(ds.view.tris) + g.tri_base;
+        t.attrs = const_cast<TriAttr<R>*>(ds.view.attrs) + g.tri_base;
+        t.pad4 = 0.0;
+        for (size_t i = 0; i < cs.meshes.size(); i++)  // any instance of the mesh carries its box
+            if (cs.meshes[i].node4_base == g.node4_base) { t.pad4 = rf_pad_of_box(cs.mesh_bounds[i].lo, cs.mesh_bounds[i].hi); break; }
+        std::string err;
+        if (!refit_mesh_launch<R>(s->refit[gi], t, s->stream, &err)) return set_err(RT_E_DEVICE, err);
+    }
+    return RT_OK;
+}
+}  // namespace rt
+
+// An accumulator belongs to the scene as it was when the accumulator was created.
+static bool accum_is_stale(const RtAccum* acc) { return acc->generation != acc->scene->generation; }
+static int accum_stale_error() { return rt::set_err(RT_E_INVALID, "the scene was updated after this accumulator was created"); }
 
 extern "C" {
 
@@ -1510,6 +1682,7 @@ int rt_scene_create(const RtSceneDesc* desc, int device, RtScene** out) {
     int st = compile_scene(desc, &s->compiled, &err, opt);
     if (st != RT_OK) return set_err(st, err);
     s->content_digest = scene_digest(*desc);  // the description has been validated by the compiler
+    s->held.assign(*desc);
     if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_err(RT_E_DEVICE, "no HIP device available");
     if (device < 0 || device >= n) return set_err(RT_E_INVALID, "device index out of range");
     s->device = device;
@@ -1527,6 +1700,7 @@ void rt_scene_destroy(RtScene* s) {
     (void)hipSetDevice(s->device);
     s->f64.reset();
     s->f32.reset();
+    for (rt::RefitMesh& rm : s->refit) rm.release();
     rt::wf_release_pool(s->wf);
     if (s->wf.mesh_spill) (void)hipFree(s->wf.mesh_spill);
     if (s->wf.d_ctr) (void)hipFree(s->wf.d_ctr);
@@ -1695,6 +1869,195 @@ int rt_debug_trace_sample(const RtScene* scene, const RtCameraDesc* camera, cons
     return int(n);
 }
 
+int rt_scene_update_check(const RtSceneDesc* a, const RtSceneDesc* b) {
+    using namespace rt;
+    if (!a || !b) return set_err(RT_E_INVALID, "rt_scene_update_check: NULL argument");
+    const std::string field = update_mismatch(*a, *b);
+    if (!field.empty()) return set_err(RT_E_INVALID, update_mismatch_message(field));
+    return RT_OK;
+}
+
+int rt_scene_update(RtScene* s, const RtSceneDesc* desc, RtSceneUpdateInfo* info) {
+    using namespace rt;
+    const auto t_begin = std::chrono::steady_clock::now();
+    if (info) *info = RtSceneUpdateInfo{};
+    if (!s || !desc) return set_err(RT_E_INVALID, "rt_scene_update: NULL argument");
+    // ---- host only: everything that can refuse the description, before any device state is touched ----
+    const std::string field = update_mismatch(s->held.d, *desc);
+    if (!field.empty()) return set_err(RT_E_INVALID, update_mismatch_message(field));
+    std::vector<bool> changed(desc->n_meshes, false), same(desc->n_meshes, true);
+    for (uint32_t i = 0; i < desc->n_meshes; i++) {
+        const RtMesh &o = s->held.meshes[i], &m = desc->meshes[i];
+        auto differs = [](const double* x, const double* y, size_t n) { return x && n && std::memcmp(x, y, n * sizeof(double)) != 0; };
+        changed[i] = differs(o.positions, m.positions, 3 * size_t(m.n_positions)) || differs(o.normals, m.normals, 3 * size_t(m.n_normals)) ||
+                     differs(o.uvs, m.uvs, 3 * size_t(m.n_uvs));
+        same[i] = !changed[i];
+        if (!changed[i] || !m.positions) continue;
+        for (size_t k = 0; k < 3 * size_t(m.n_positions); k++)
+            if (!(std::fabs(m.positions[k]) <= 1e37))  // also NaN
+                return set_err(RT_E_UNSUPPORTED, "scene update: meshes[" + std::to_string(i) + "].positions: coordinates beyond the f32 grid");
+    }
+    CompileOptions opt;
+    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // as rt_scene_create
+    opt.reuse = &s->compiled;
+    opt.mesh_changed = &changed;
+    CompiledScene cs;
+    std::string err;
+    int st = compile_scene(desc, &cs, &err, opt);
+    if (st != RT_OK) return set_err(st, err);
+    if (cs.mesh_geoms.size() != s->compiled.mesh_geoms.size() || cs.nodes.size() != s->compiled.nodes.size() ||
+        cs.nodes4.size() != s->compiled.nodes4.size() || cs.tris.size() != s->compiled.tris.size())
+        return set_err(RT_E_INVALID, update_mismatch_message("mesh tables"));
+    std::vector<uint32_t> moved;  // distinct meshes of the compiled scene whose vertices differ
+    uint32_t n_tris_moved = 0;
+    for (uint32_t gi = 0; gi < cs.mesh_geoms.size(); gi++)
+        if (changed[size_t(cs.mesh_geoms[gi].mesh)]) { moved.push_back(gi); n_tris_moved += cs.mesh_geoms[gi].n_tris; }
+    // ---- device ----
+    HIP_TRY(hipSetDevice(s->device));
+    uint64_t bytes = 0;
+    float kernel_ms = 0.f;
+    std::unique_ptr<DeviceScene<double>> n64;
+    std::unique_ptr<DeviceScene<float>> n32;
+    const bool on_device = s->f64 || s->f32;
+    if (on_device && !moved.empty()) {
+        s->refit.resize(cs.mesh_geoms.size());
+        for (uint32_t gi : moved) {
+            const CompiledScene::MeshGeom& g = cs.mesh_geoms[gi];
+            std::vector<int32_t> child2(2 * size_t(g.n_nodes)), child4(4 * size_t(g.n_nodes4));
+            if (!s->refit[gi].tri_order) {  // relative references, once
+                for (uint32_t i = 0; i < g.n_nodes; i++) { child2[2 * size_t(i)] = cs.nodes[g.node_base + i].c0; child2[2 * size_t(i) + 1] = cs.nodes[g.node_base + i].c1; }
+                for (uint32_t i = 0; i < g.n_nodes4; i++)
+                    for (int k = 0; k < 4; k++) {
+                        int32_t c = cs.nodes4[g.node4_base + i].child[k];
+                        if (c != kEmptyChild) {
+                            if (c >= 0) c -= int32_t(g.node4_base);
+                            else { const uint32_t code = uint32_t(~c); c = ~int32_t((((code >> 3) - g.tri_base) << 3) | (code & 7u)); }
+                        }
+                        child4[4 * size_t(i) + size_t(k)] = c;
+                    }
+            }
+            if (!refit_mesh_upload(s->refit[gi], desc->meshes[g.mesh], cs.tri_order.data() + g.tri_base, child2.data(), g.n_nodes, child4.data(), g.n_nodes4,
+                                   s->stream, &bytes, &err))
+                return set_err(RT_E_DEVICE, err);
+        }
+    }
+    if (on_device) {
+        HIP_TRY(hipStreamSynchronize(s->stream));  // the vertex copies; DeviceScene::build uses the null stream and synchronises the device
+        // The small tables first, uploaded afresh beside the old ones (a failure here leaves the scene as it was) ...
+        if (s->f64) {
+            n64 = std::make_unique<DeviceScene<double>>();
+            if ((st = n64->build(cs, s->f64.get())) != RT_OK) return st;
+            bytes += n64->buf.uploaded_bytes;
+        }
+        if (s->f32) {
+            n32 = std::make_unique<DeviceScene<float>>();
+            if ((st = n32->build(cs, s->f32.get())) != RT_OK) return st;
+            bytes += n32->buf.uploaded_bytes;
+        }
+        // ... then the kernels.  From here on a device error leaves the mesh tables half written: the scene can only be destroyed.
+        if (!moved.empty()) {
+            HIP_TRY(hipEventRecord(s->ev0, s->stream));
+            if (s->f64 && (st = refit_typed<double>(s, cs, moved, *s->f64)) != RT_OK) return st;
+            if (s->f32 && (st = refit_typed<float>(s, cs, moved, *s->f32)) != RT_OK) return st;
+            HIP_TRY(hipEventRecord(s->ev1, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            HIP_TRY(hipEventElapsedTime(&kernel_ms, s->ev0, s->ev1));
+        }
+    }
+    // ---- commit ----
+    if (n64) { n64->take_mesh_tables(*s->f64); s->f64 = std::move(n64); }
+    if (n32) { n32->take_mesh_tables(*s->f32); s->f32 = std::move(n32); }
+    s->compiled = std::move(cs);
+    HeldDesc old = std::move(s->held);
+    s->held.assign(*desc, &old, &same);
+    s->content_digest = scene_digest(*desc);
+    s->generation++;
+    if (info) {
+        info->n_meshes_refit = uint32_t(moved.size());
+        info->n_triangles_refit = n_tris_moved;
+        info->bytes_uploaded = bytes;
+        info->refit_kernel_ms = double(kernel_ms);
+        info->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    }
+    return RT_OK;
+}
+
+int rt_scene_refit_mesh(const RtSceneDesc* a, const RtSceneDesc* b, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out,
+                        float* boxes_out, uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out, uint32_t* tri_order_out,
+                        uint32_t tri_capacity, uint32_t* n_tris_out) {
+    using namespace rt;
+    if (!a || !b || !n_nodes_out || !n_tris_out) return set_err(RT_E_INVALID, "rt_scene_refit_mesh: NULL argument");
+    const std::string field = update_mismatch(*a, *b);
+    if (!field.empty()) return set_err(RT_E_INVALID, update_mismatch_message(field));
+    CompiledScene ca, cb;
+    std::string err;
+    int st = compile_scene(a, &ca, &err, CompileOptions());
+    if (st != RT_OK) return set_err(st, err);
+    CompileOptions opt;
+    opt.reuse = &ca;  // every mesh refitted, whether it moved or not
+    st = compile_scene(b, &cb, &err, opt);
+    if (st != RT_OK) return set_err(st, err);
+    const CompiledScene::MeshGeom* g = nullptr;
+    if (!mesh_export_range(cb, mesh, &g)) return set_err(RT_E_INVALID, "rt_scene_refit_mesh: mesh index out of range");
+    const MeshExportOut o{children_out, cones_out, boxes_out, node_capacity, n_nodes_out, tris_out, tri_order_out, tri_capacity, n_tris_out};
+    return f32 ? mesh_export_host<float>(cb, *g, mesh, o) : mesh_export_host<double>(cb, *g, mesh, o);
+}
+
+int rt_debug_scene_mesh(const RtScene* scene, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out, float* boxes_out,
+                        uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out, uint32_t* tri_order_out, uint32_t tri_capacity,
+                        uint32_t* n_tris_out) {
+    using namespace rt;
+    if (!scene || !n_nodes_out || !n_tris_out) return set_err(RT_E_INVALID, "rt_debug_scene_mesh: NULL argument");
+    RtScene* s = const_cast<RtScene*>(scene);
+    HIP_TRY(hipSetDevice(s->device));
+    const CompiledScene::MeshGeom* g = nullptr;
+    if (!mesh_export_range(s->compiled, mesh, &g)) return set_err(RT_E_INVALID, "rt_debug_scene_mesh: mesh index out of range");
+    const MeshExportOut o{children_out, cones_out, boxes_out, node_capacity, n_nodes_out, tris_out, tri_order_out, tri_capacity, n_tris_out};
+    if (f32) {
+        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
+        return mesh_export_device<float>(s->compiled, *g, *s->f32, o);
+    }
+    if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
+    return mesh_export_device<double>(s->compiled, *g, *s->f64, o);
+}
+
+int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[8]) {
+    using namespace rt;
+    if (!scene || !out) return set_err(RT_E_INVALID, "rt_debug_scene_mesh_digest: NULL argument");
+    RtScene* s = const_cast<RtScene*>(scene);
+    HIP_TRY(hipSetDevice(s->device));
+    const CompiledScene& cs = s->compiled;
+    std::vector<char> h;
+    auto digest_of = [&](const void* d_ptr, size_t bytes, uint64_t* o) -> int {
+        h.resize(bytes);
+        if (bytes) HIP_TRY(hipMemcpy(h.data(), d_ptr, bytes, hipMemcpyDeviceToHost));
+        Digest g;
+        g.bytes(h.data(), bytes);
+        *o = g.value();
+        return RT_OK;
+    };
+    for (int k = 0; k < 8; k++) out[k] = 0;
+    int st;
+#define RT_DIGEST_TABLES(DS, R)                                                                                     \
+    if ((st = digest_of(DS.view.nodes, cs.nodes.size() * sizeof(BvhNode<R>), &out[0])) != RT_OK) return st;        \
+    if ((st = digest_of(DS.view.nodes4, cs.nodes4.size() * sizeof(BvhNode4f), &out[1])) != RT_OK) return st;       \
+    if ((st = digest_of(DS.view.nodes4q, cs.nodes4.size() * sizeof(MeshNode4qc), &out[2])) != RT_OK) return st;    \
+    if ((st = digest_of(DS.view.tris, cs.tris.size() * sizeof(TriRec<R>), &out[3])) != RT_OK) return st;           \
+    if ((st = digest_of(DS.view.attrs, cs.attrs.size() * sizeof(TriAttr<R>), &out[4])) != RT_OK) return st;        \
+    if ((st = digest_of(DS.view.mesh_bounds, cs.mesh_bounds.size() * sizeof(Bounds<R>), &out[5])) != RT_OK) return st; \
+    if ((st = digest_of(DS.view.mesh_op_recs, cs.mesh_ops.size() * sizeof(MeshOpRec<R>), &out[6])) != RT_OK) return st;
+    if (f32) {
+        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
+        RT_DIGEST_TABLES((*s->f32), float)
+    } else {
+        if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
+        RT_DIGEST_TABLES((*s->f64), double)
+    }
+#undef RT_DIGEST_TABLES
+    out[7] = s->generation;
+    return RT_OK;
+}
+
 int rt_scene_info(const RtSceneDesc* desc, uint32_t* flags_out) {
     using namespace rt;
     if (!desc || !flags_out) return set_err(RT_E_INVALID, "rt_scene_info: NULL argument");
@@ -1806,6 +2169,7 @@ int rt_accum_create(const RtScene* scene, const RtCameraDesc* camera, const RtRe
     std::unique_ptr<RtAccum> a(new (std::nothrow) RtAccum);
     if (!a) return set_err(RT_E_NOMEM, "out of memory");
     a->scene = const_cast<RtScene*>(scene);
+    a->generation = scene->generation;
     a->device = scene->device;
     a->camera = *camera;
     a->params = *params;
@@ -1923,6 +2287,7 @@ static int accum_render_adaptive(RtAccum* acc, uint32_t n_replicas, RtRenderPara
 static int accum_render_impl(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream) {
     using namespace rt;
     if (!acc) return set_err(RT_E_INVALID, "rt_accum_render: NULL accumulator");
+    if (accum_is_stale(acc)) return accum_stale_error();
     RtRenderParams p = acc->params;
     if (params_or_null) {
         const RtRenderParams a = frame_fields(acc->params), b = frame_fields(*params_or_null);
@@ -1968,6 +2333,7 @@ static int accum_estimate_to(const RtAccum* acc, double* d_out, hipStream_t stre
 
 static int accum_check_estimate(const RtAccum* acc, const void* out, const char* who) {
     if (!acc || !out) return rt::set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
+    if (accum_is_stale(acc)) return accum_stale_error();
     if (acc->k == 0) return rt::set_err(RT_E_INVALID, std::string(who) + ": no replica rendered yet (k = 0)");
     return RT_OK;
 }
@@ -2030,6 +2396,7 @@ size_t rt_accum_state_size(const RtAccum* acc) {
 int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
     using namespace rt;
     if (!acc || !buf) return set_err(RT_E_INVALID, "rt_accum_save_state: NULL argument");
+    if (accum_is_stale(acc)) return accum_stale_error();
     if (size < rt_accum_state_size(acc)) return set_err(RT_E_INVALID, "rt_accum_save_state: buffer smaller than rt_accum_state_size");
     AccumHeader h{};
     std::memcpy(h.magic, kAccumMagic, 8);
@@ -2063,6 +2430,7 @@ int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
 int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size) {
     using namespace rt;
     if (!acc || !buf) return set_err(RT_E_INVALID, "rt_accum_load_state: NULL argument");
+    if (accum_is_stale(acc)) return accum_stale_error();
     AccumHeader h;
     if (size < sizeof h) return set_err(RT_E_INVALID, "rt_accum_load_state: state truncated (shorter than its header)");
     std::memcpy(&h, buf, sizeof h);
@@ -2275,6 +2643,7 @@ int rt_adaptive_default_params(RtAdaptiveParams* out) {
 int rt_accum_set_adaptive(RtAccum* acc, const RtAdaptiveParams* ap) {
     using namespace rt;
     if (!acc || !ap) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: NULL argument");
+    if (accum_is_stale(acc)) return accum_stale_error();
     if (acc->adaptive) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: the accumulator is adaptive already");
     if (acc->k != 0 || acc->touched) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: only before the first replica and before a state is loaded");
     if (!(ap->threshold > 0.0) || !std::isfinite(ap->threshold)) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: threshold must be positive and finite (it has no default)");
@@ -2326,6 +2695,7 @@ int rt_accum_finished(const RtAccum* acc) {
 int rt_accum_sample_counts(const RtAccum* acc, uint32_t* counts_out) {
     using namespace rt;
     if (!acc || !counts_out) return set_err(RT_E_INVALID, "rt_accum_sample_counts: NULL argument");
+    if (accum_is_stale(acc)) return accum_stale_error();
     if (!acc->adaptive) {
         std::fill(counts_out, counts_out + acc->npix(), acc->k);
         return RT_OK;
@@ -2338,6 +2708,7 @@ int rt_accum_sample_counts(const RtAccum* acc, uint32_t* counts_out) {
 int rt_accum_noise(const RtAccum* acc, double* noise_out) {
     using namespace rt;
     if (!acc || !noise_out) return set_err(RT_E_INVALID, "rt_accum_noise: NULL argument");
+    if (accum_is_stale(acc)) return accum_stale_error();
     if (!acc->adaptive) return set_err(RT_E_INVALID, "rt_accum_noise: the accumulator keeps no moments (rt_accum_set_adaptive)");
     HIP_TRY(hipSetDevice(acc->device));
     const size_t np = acc->npix();

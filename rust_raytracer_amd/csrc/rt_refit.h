@@ -1,0 +1,242 @@
+// rt_refit.h — what the kernels' mesh tables are, as functions of (tree topology, vertex positions).
+//
+// The reader formats of a mesh BVH (BvhNode<R>, BvhNode4f, BvhNode4q, the back-face cone words) are derived from the exact
+// f64 child boxes and the triangle records by the per-node formulas below.  They are written ONCE, __host__ __device__:
+// DeviceScene<R>::build and build_mesh_cones (the host builder) and the refit kernels of rt_refit.hip (rt_scene_update)
+// call the same functions, compiled with -ffp-contract=off on both sides, in f64 with IEEE operations only (+ - * /
+// sqrt, floor / ceil / lround, frexp / ldexp), so the two sides give the same bits.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <limits>
+#include <string>
+#include <vector>
+
+#include "../../include/rt_mi355.h"
+#include "rt_bvh.h"
+#include "rt_scene.h"
+
+#if defined(__HIP__)
+#include <hip/hip_runtime.h>
+#define RT_HD __host__ __device__
+#else
+#define RT_HD
+#endif
+
+namespace rt {
+
+// min / max that pick the same operand on both sides when the two compare equal (-0 and +0) or one is NaN
+RT_HD inline double rf_min(double a, double b) { return b < a ? b : a; }
+RT_HD inline double rf_max(double a, double b) { return b > a ? b : a; }
+
+RT_HD inline float rf_float_below(float f) {  // nextafterf(f, -inf) for every f that float(x) > x can give
+    uint32_t b;
+    memcpy(&b, &f, 4);
+    if ((b << 1) == 0u) b = 0x80000001u;  // +-0 -> the smallest negative number
+    else if (b >> 31) b += 1u;
+    else b -= 1u;
+    memcpy(&f, &b, 4);
+    return f;
+}
+RT_HD inline float rf_float_above(float f) {
+    uint32_t b;
+    memcpy(&b, &f, 4);
+    if ((b << 1) == 0u) b = 0x00000001u;
+    else if (b >> 31) b -= 1u;
+    else b += 1u;
+    memcpy(&f, &b, 4);
+    return f;
+}
+
+template <typename R> RT_HD inline R round_down(double x);
+template <typename R> RT_HD inline R round_up(double x);
+template <> RT_HD inline double round_down<double>(double x) { return x; }
+template <> RT_HD inline double round_up<double>(double x) { return x; }
+template <> RT_HD inline float round_down<float>(double x) {
+    float f = float(x);
+    if (double(f) > x) f = rf_float_below(f);
+    return f;
+}
+template <> RT_HD inline float round_up<float>(double x) {
+    float f = float(x);
+    if (double(f) < x) f = rf_float_above(f);
+    return f;
+}
+
+// BvhNode<R>: conservative boxes, outward rounding plus a few ulps so that the slab arithmetic never culls a triangle the
+// exact test would hit.
+template <typename R> RT_HD inline void rf_pad_box2(double lo, double hi, R* olo, R* ohi) {
+    if (!(lo <= hi)) { *olo = R(lo); *ohi = R(hi); return; }  // empty child box
+    const double m = std::fmax(std::fabs(lo), std::fabs(hi));
+    const double e = 8.0 * double(std::numeric_limits<R>::epsilon()) * std::fmax(m, hi - lo);
+    *olo = round_down<R>(lo - e);
+    *ohi = round_up<R>(hi + e);
+}
+
+// The pad of the 4-wide nodes of a mesh (or primitive group) whose box is (lo, hi): 2^-19 x its largest |coordinate|.
+RT_HD inline double rf_pad_of_box(const double* lo, const double* hi) {
+    double S = 0.0;
+    for (int a = 0; a < 3; a++) S = std::fmax(S, std::fmax(std::fabs(lo[a]), std::fabs(hi[a])));
+    if (!std::isfinite(S)) S = 0.0;
+    return S * (1.0 / 524288.0);
+}
+
+// BvhNode4f: one plane pair of child k, padded by m and rounded outward.
+RT_HD inline void rf_pad_box4f(double lo, double hi, double m, float* olo, float* ohi) {
+    if (!(lo <= hi)) { *olo = INFINITY; *ohi = -INFINITY; }
+    else { *olo = round_down<float>(lo - m); *ohi = round_up<float>(hi + m); }
+}
+
+// BvhNode4q: the padded child boxes (as in BvhNode4f) on a per-node 8-bit grid, rounded outward on the grid.  The cell is
+// the smallest power of two with extent / cell <= 255.  False: the node does not fit the grid (coordinates beyond 1e38).
+RT_HD inline bool rf_quantise4(const double (*lo)[3], const double (*hi)[3], const int32_t* child, double m, float* org_out, float* cell_out,
+                               uint32_t* qlo, uint32_t* qhi) {
+    for (int a = 0; a < 3; a++) {
+        double flo[4], fhi[4];
+        bool real[4];
+        double lo_min = INFINITY, hi_max = -INFINITY;
+        for (int k = 0; k < 4; k++) {
+            real[k] = child[k] != kEmptyChild && lo[k][a] <= hi[k][a];
+            if (!real[k]) continue;
+            flo[k] = double(round_down<float>(lo[k][a] - m));
+            fhi[k] = double(round_up<float>(hi[k][a] + m));
+            lo_min = std::fmin(lo_min, flo[k]);
+            hi_max = std::fmax(hi_max, fhi[k]);
+        }
+        const bool any = lo_min <= hi_max && std::isfinite(lo_min) && std::isfinite(hi_max);
+        const double org = any ? lo_min : 0.0;  // an f32 value
+        const double ext = any ? hi_max - org : 0.0;
+        int e = -100;
+        if (ext > 0.0) {
+            (void)std::frexp(ext / 255.0, &e);  // ext / 255 = f 2^e, f in [1/2, 1): 2^e is the cell or twice the cell
+            while (ext / std::ldexp(1.0, e) > 255.0) e++;
+            while (e > -100 && ext / std::ldexp(1.0, e - 1) <= 255.0) e--;
+            e = e < -100 ? -100 : (e > 120 ? 120 : e);
+        }
+        const double cell = std::ldexp(1.0, e);
+        org_out[a] = float(org);
+        cell_out[a] = float(cell);
+        qlo[a] = 0;
+        qhi[a] = 0;
+        for (int k = 0; k < 4; k++) {
+            uint32_t ql = 255u, qh = 0u;  // empty child: lo > hi, never entered
+            if (any && real[k]) {
+                const double l = std::floor((flo[k] - org) / cell), h = std::ceil((fhi[k] - org) / cell);
+                const double lc = 255.0 < l ? 255.0 : l, hc = 255.0 < h ? 255.0 : h;  // clamped to [0, 255]
+                ql = uint32_t(0.0 < lc ? lc : 0.0);
+                qh = uint32_t(0.0 < hc ? hc : 0.0);
+                if (!(org + ql * cell <= flo[k] && org + qh * cell >= fhi[k])) return false;  // e > 120: coordinates beyond 1e38
+            }
+            qlo[a] |= ql << (8 * k);
+            qhi[a] |= qh << (8 * k);
+        }
+    }
+    return true;
+}
+
+// ---- back-face cones (the argument stands in rt_bvh.cpp) ----
+constexpr double kConeDirSlack = 0.00682;   // d_dir
+constexpr double kConeSafety = 0.001;       // d_safe
+constexpr double kConeMinCos = 0.125;       // c >= 1/8: wider cones cull next to nothing
+
+// The unit normal e1 x e2 of a triangle record, or NaN in out[0..2] if the triangle is ill-conditioned.
+RT_HD inline void rf_tri_normal(const double* v0, const double* a, const double* b, const ConeLimits& lim, double* out) {
+    const double cx = a[1] * b[2] - a[2] * b[1], cy = a[2] * b[0] - a[0] * b[2], cz = a[0] * b[1] - a[1] * b[0];
+    const double la = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]), lb = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+    const double lc = std::sqrt(cx * cx + cy * cy + cz * cz);
+    bool ok = std::isfinite(v0[0]) && std::isfinite(v0[1]) && std::isfinite(v0[2]);
+    ok = ok && la >= lim.min_edge && la <= lim.max_edge && lb >= lim.min_edge && lb <= lim.max_edge;  // false for NaN
+    ok = ok && lc >= lim.sigma * la * lb && lc > 0.0;
+    const double kNaN = std::numeric_limits<double>::quiet_NaN();
+    out[0] = ok ? cx / lc : kNaN;
+    out[1] = ok ? cy / lc : kNaN;
+    out[2] = ok ? cz / lc : kNaN;
+}
+
+// The word of the cone around `axis` (any length) that holds the normals of the slots [lo, hi), or kNeutralCone.
+RT_HD inline uint32_t rf_cone_around(const double* normal, uint32_t lo, uint32_t hi, const double* axis) {
+    const double l = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!(l > 0.0) || !std::isfinite(l)) return kNeutralCone;  // NaN: an ill-conditioned triangle below
+    int q[3];
+    double al = 0.0;
+    for (int a = 0; a < 3; a++) { q[a] = int(std::lround(127.0 * axis[a] / l)); al += double(q[a]) * double(q[a]); }
+    al = std::sqrt(al);
+    if (!(al > 0.0)) return kNeutralCone;
+    const double ax = q[0] / al, ay = q[1] / al, az = q[2] / al;
+    double c = 1.0;
+    for (uint32_t t = lo; t < hi; t++) {
+        const double d = ax * normal[3 * size_t(t)] + ay * normal[3 * size_t(t) + 1] + az * normal[3 * size_t(t) + 2];
+        c = d < c ? d : c;  // std::min(c, d)
+        if (c < kConeMinCos) return kNeutralCone;
+    }
+    if (!(c >= kConeMinCos)) return kNeutralCone;
+    const double s = std::sqrt(std::fmax(0.0, 1.0 - c * c));
+    const double w = std::ceil(al * (s + kConeDirSlack + kConeSafety));
+    if (!(w >= 1.0 && w <= 127.0)) return kNeutralCone;
+    return uint32_t(q[0] & 0xFF) | (uint32_t(q[1] & 0xFF) << 8) | (uint32_t(q[2] & 0xFF) << 16) | (uint32_t(w) << 24);
+}
+
+// The cone word of a child over the slots [lo, hi), `count` triangles, the sum of whose normals is `sum`.
+RT_HD inline uint32_t rf_cone_word(const double* normal, uint32_t lo, uint32_t hi, uint32_t count, const double* sum) {
+    if (count == 0 || hi - lo != count) return kNeutralCone;
+    uint32_t word = rf_cone_around(normal, lo, hi, sum);
+    if (word == kNeutralCone && count >= 2 && count <= 8 && std::isfinite(sum[0])) {
+        // A leaf over a fold: the sum leans towards the side with more triangles and loses the other one.  The bisector
+        // of the two normals farthest apart is the axis of the narrowest cone that holds those two.
+        uint32_t bi = lo, bj = lo;
+        double least = 2.0;
+        for (uint32_t i = lo; i < hi; i++)
+            for (uint32_t j = i + 1; j < hi; j++) {
+                const double* ni = &normal[3 * size_t(i)];
+                const double* nj = &normal[3 * size_t(j)];
+                const double dij = ni[0] * nj[0] + ni[1] * nj[1] + ni[2] * nj[2];
+                if (dij < least) { least = dij; bi = i; bj = j; }
+            }
+        const double mid[3] = {normal[3 * size_t(bi)] + normal[3 * size_t(bj)], normal[3 * size_t(bi) + 1] + normal[3 * size_t(bj) + 1],
+                               normal[3 * size_t(bi) + 2] + normal[3 * size_t(bj) + 2]};
+        word = rf_cone_around(normal, lo, hi, mid);
+    }
+    return word;
+}
+
+#if defined(__HIP__)
+// ---- the device refit (rt_refit.hip) ----
+// Everything one distinct mesh needs on the device to be refitted again and again: the leaf order, the index arrays and the
+// relative child references of both trees (uploaded once, at the first update that moves the mesh), the vertex arrays of the
+// last update and the scratch of the passes.  Shared by both arithmetic types.
+struct RefitMesh {
+    uint32_t n_tris = 0, n_nodes = 0, n_nodes4 = 0, n_positions = 0, n_normals = 0, n_uvs = 0;
+    uint32_t *tri_order = nullptr, *tri_pos = nullptr, *tri_nrm = nullptr;
+    int32_t* tri_uv = nullptr;             // NULL: the mesh has none
+    int32_t *child2 = nullptr, *child4 = nullptr;    // 2 / 4 per node; inner: node inside the mesh; leaf: ~(slot inside the mesh << 3 | count - 1)
+    int32_t *parent2 = nullptr, *parent4 = nullptr;  // -1: root
+    uint32_t *inner2 = nullptr, *inner4 = nullptr;   // inner children per node
+    uint32_t *arrived2 = nullptr, *arrived4 = nullptr;
+    double *positions = nullptr, *normals = nullptr, *uvs = nullptr;
+    double *tri_box = nullptr, *tri_normal = nullptr;  // per slot: lo xyz hi xyz / unit normal or NaN
+    double *box2 = nullptr, *box4 = nullptr;           // per node and child: lo xyz hi xyz (exact)
+    double* sum4 = nullptr;                            // per node and child: sum of the normals below
+    uint32_t* run4 = nullptr;                          // per node and child: first slot, end slot, count
+    void release();
+};
+
+// Where the mesh's reader tables stand in the scene's device arrays of arithmetic type R.
+template <typename R>
+struct RefitTarget {
+    BvhNode<R>* nodes;      // the mesh's first BVH2 node
+    BvhNode4f* nodes4;      // its first 4-wide node
+    MeshNode4qc* nodes4q;
+    TriRec<R>* tris;        // its first record
+    TriAttr<R>* attrs;
+    double pad4;            // rf_pad_of_box of the mesh's new box
+};
+
+// Uploads the once-only arrays of the mesh (first call) and the vertex arrays of `m`.  *bytes += what went to the device.
+bool refit_mesh_upload(RefitMesh& rm, const RtMesh& m, const uint32_t* tri_order, const int32_t* child2, uint32_t n_nodes, const int32_t* child4,
+                       uint32_t n_nodes4, hipStream_t stream, uint64_t* bytes, std::string* err);
+// The three passes for one arithmetic type, enqueued on `stream`.
+template <typename R> bool refit_mesh_launch(RefitMesh& rm, const RefitTarget<R>& t, hipStream_t stream, std::string* err);
+#endif  // __HIP__
+
+}  // namespace rt

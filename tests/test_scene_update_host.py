@@ -1,0 +1,127 @@
+"""rt_scene_update without a GPU: the structure check (rt_scene_update_check) and the refit restated on the CPU
+(rt_scene_refit_mesh): the tree of description a carrying the geometry of description b.  With b = a the restatement must give
+the host builder's own tables bit for bit; with b != a the tree stays, the records are b's, every decoded child box holds what
+lies below it and every cone passes the brute-force back-face check of tests/test_mesh_cones.py."""
+import os
+
+import numpy as np
+import pytest
+
+import test_mesh_cones as cones_ref
+from rust_raytracer_amd import api
+from scene_update_cases import (GRID_CASES, MONKEY, displaced_obj, grid_host_scene, grid_vertices, mesh_arrays, two_meshes_variant)
+
+EMPTY = cones_ref.EMPTY
+
+
+# ---- H1 ----
+def test_update_check_accepts_numeric_variants(tmp_path):
+    a = api.HostScene(["tests/scenes/two_meshes", "-w=64", "-s=16", "--seed=32"])
+    api.scene_update_check(a.desc, a.desc)
+    b = two_meshes_variant(tmp_path, "numbers")
+    api.scene_update_check(a.desc, b.desc)
+    da, db = a.desc.contents, b.desc.contents
+    assert any(da.materials[k].ior != db.materials[k].ior for k in range(da.n_materials))      # ior is among the numbers
+    assert any(bytes(da.transforms[k]) != bytes(db.transforms[k]) for k in range(da.n_transforms))
+    displaced_obj(MONKEY, tmp_path / "moved.obj")
+    c = two_meshes_variant(tmp_path, "moved", numeric=False, m2=tmp_path / "moved.obj")
+    api.scene_update_check(a.desc, c.desc)
+    d = two_meshes_variant(tmp_path, "both", numeric=True, m1=tmp_path / "moved.obj")
+    api.scene_update_check(a.desc, d.desc)
+    pa, _ = mesh_arrays(a.desc, 1)
+    pc, _ = mesh_arrays(c.desc, 1)
+    assert pa.shape == pc.shape and (pa != pc).any()
+
+
+def _first_node(d, node_type):
+    return next(i for i in range(d.n_nodes) if d.nodes[i].type == node_type)
+
+
+def _edit_triangle_fewer(d): d.meshes[0].n_triangles -= 1
+def _edit_tri_pos(d): d.meshes[0].tri_pos[7] = (d.meshes[0].tri_pos[7] + 1) % d.meshes[0].n_positions
+def _edit_node_type(d): d.nodes[_first_node(d, api.RT_NODE_PLANE)].type = api.RT_NODE_SPHERE
+def _edit_material_type(d): d.materials[0].type = api.RT_MAT_METAL if d.materials[0].type != api.RT_MAT_METAL else api.RT_MAT_LAMBERTIAN
+def _edit_texture_width(d): d.textures[0].width += 1
+def _edit_child_index(d): d.child_indices[0], d.child_indices[1] = d.child_indices[1], d.child_indices[0]
+def _edit_world_root(d): d.world_root = d.lights_root
+def _edit_mesh_flags(d): d.meshes[1].flags ^= api.RT_MESH_HIT_BACK_FACES
+def _edit_uvs_dropped(d): d.meshes[0].uvs = None
+
+
+@pytest.mark.parametrize("edit,field", [
+    (_edit_triangle_fewer, "meshes[0].n_triangles"), (_edit_tri_pos, "meshes[0].tri_pos"), (_edit_node_type, "].type"),
+    (_edit_material_type, "materials[0].type"), (_edit_texture_width, "textures[0].width"), (_edit_child_index, "child_indices"),
+    (_edit_world_root, "world_root"), (_edit_mesh_flags, "meshes[1].flags"), (_edit_uvs_dropped, "meshes[0].uvs")],
+    ids=["triangle_fewer", "tri_pos", "node_type", "material_type", "texture_width", "child_index", "world_root", "mesh_flags", "uvs_dropped"])
+def test_update_check_refuses_structural_edits(edit, field):
+    a = api.HostScene(["tests/scenes/two_meshes", "-w=64", "-s=16", "--seed=32"])
+    b = api.HostScene(["tests/scenes/two_meshes", "-w=64", "-s=16", "--seed=32"])
+    api.scene_update_check(a.desc, b.desc)
+    assert b.desc.contents.meshes[0].uvs, "the test mesh has uvs to drop"
+    edit(b.desc.contents)
+    with pytest.raises(api.RtError) as e:
+        api.scene_update_check(a.desc, b.desc)
+    assert e.value.status == api.RT_E_INVALID
+    assert field in str(e.value), str(e.value)
+
+
+# ---- H2 ----
+def _same_as_builder(desc, f32):
+    children, cones, tris = api.scene_mesh_cones(desc, 0, f32)
+    r = api.scene_refit_mesh(desc, desc, 0, f32)
+    np.testing.assert_array_equal(r["children"], children)
+    np.testing.assert_array_equal(r["cones"], cones)
+    kernel_tris = tris.astype(np.float32).astype(np.float64) if f32 else tris
+    assert (r["tris"].view(np.uint64) == kernel_tris.view(np.uint64)).all()
+    assert sorted(r["order"].tolist()) == list(range(len(tris)))
+    return r
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+def test_refit_onto_itself_is_the_builder_suzanne(tmp_path, f32):
+    hs = cones_ref.mesh_scene(tmp_path, MONKEY)
+    r = _same_as_builder(hs.desc, f32)
+    assert not (r["cones"] == cones_ref.NEUTRAL).all(axis=-1)[r["children"] != EMPTY].all()
+
+
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+def test_refit_onto_itself_is_the_builder_grid(tmp_path, f32):
+    hs = grid_host_scene(tmp_path, "base")
+    _same_as_builder(hs.desc, f32)
+
+
+# ---- H3 ----
+@pytest.mark.parametrize("f32", [False, True], ids=["f64", "f32"])
+@pytest.mark.parametrize("case", GRID_CASES)
+def test_refit_to_other_geometry(tmp_path, monkeypatch, case, f32):
+    a = grid_host_scene(tmp_path, "base")
+    b = grid_host_scene(tmp_path, case)
+    children_a, _, _ = api.scene_mesh_cones(a.desc, 0, f32)
+    r = api.scene_refit_mesh(a.desc, b.desc, 0, f32)
+    np.testing.assert_array_equal(r["children"], children_a)      # the tree is a's
+    pos, tri = mesh_arrays(b.desc)
+    np.testing.assert_array_equal(pos, grid_vertices(case))       # the loader kept the vertices as written
+    # records: v0, e1, e2 of b's triangle order[slot], subtracted in f64, rounded for f32
+    t = tri[r["order"]]
+    want = np.stack([pos[t[:, 0]], pos[t[:, 1]] - pos[t[:, 0]], pos[t[:, 2]] - pos[t[:, 0]]], axis=1)
+    if f32:
+        want = want.astype(np.float32).astype(np.float64)
+    assert (r["tris"].view(np.uint64) == want.view(np.uint64)).all()
+    # boxes: every child's decoded box holds every vertex of every triangle below it
+    below = cones_ref.triangles_below(r["children"])
+    boxes = r["boxes"].astype(np.float64)
+    for i in range(len(below)):
+        for k in range(4):
+            if r["children"][i, k] == EMPTY:
+                assert (boxes[i, k, 0] > boxes[i, k, 1]).any()
+                continue
+            v = pos[t[below[i][k]]].reshape(-1, 3)
+            assert (boxes[i, k, 0] <= v.min(axis=0)).all() and (boxes[i, k, 1] >= v.max(axis=0)).all(), f"child {k} of node {i}"
+    # cones: the brute-force check of tests/test_mesh_cones.py on the refitted words (it judges conditioning on the f64 records)
+    tris64 = api.scene_refit_mesh(a.desc, b.desc, 0, False)["tris"]
+    monkeypatch.setattr(api, "scene_mesh_cones", lambda desc, mesh=0, f32=False: (r["children"], r["cones"], tris64))
+    stats = cones_ref.check_mesh(b.desc, "f32" if f32 else "f64", expect_full_coverage=False)
+    if case in ("phase", "far"):
+        assert stats["leaf_cones"] > 0.5 and stats["inner_cones"] > 0.0   # the cones survive the refit
+    if case == "collapsed":
+        assert stats["bad"] >= 12
