@@ -64,6 +64,11 @@ double rth_noise_threshold(const RtHost* host);
 int32_t rth_adaptive_min(const RtHost* host);
 int32_t rth_adaptive_check(const RtHost* host);
 int32_t rth_adaptive_radius(const RtHost* host);
+/* Ray queries (rt_trace_rays): --pick=<x>,<y>[:<x>,<y>...] names pixels; rtrace then casts the ray through the centre of each
+ * (first_pixel + x * pixel_delta_u + y * pixel_delta_v - position from position: no lens, no jitter) and prints one line per
+ * pixel - node, node type, material, triangle, t, position - INSTEAD of rendering.  rth_load rejects malformed lists and
+ * pixels outside the frame.  rth_pick copies up to `capacity` (x, y) pairs and returns how many were given (0: no flag). */
+uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity);
 uint32_t rth_samples_per_pixel(const RtHost* host); /* Camera::samples_per_pixel() */
 /* Row partition of `rtrace --gpus=N` (replaces the per-thread full-frame buffers of src/camera.rs:243-255): band height
  * for `height` image rows over `n_parts` GPUs = the largest of 16, 8, 4, 2, 1 rows that gives the most loaded part as few

@@ -559,6 +559,58 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
 int rt_light_mix_device(int device, const double* d_groups, uint32_t n_groups, uint32_t w, uint32_t h, const double* tints,
                         double* d_rgba_out, void* stream);
 
+/* ---- Ray queries: closest hit and occlusion for rays of the caller's own ----------------------
+ * Picking, visibility and occlusion baking, line-of-sight tests, collision probes: n rays against the scene as it stands
+ * (after rt_scene_update: the new numbers).  General rules: n = 0 is a no-op; a NULL array is RT_E_INVALID; a precision
+ * other than RT_PRECISION_F64 / _F32 is RT_E_INVALID; a scene whose program contains volumes (RT_SCENE_INFO_VOLUMES) is
+ * RT_E_UNSUPPORTED (a medium gives no deterministic surface: Volume::test draws from a path's generator).  Non-finite ray
+ * components are not an error: the result for such a ray is whatever the arithmetic gives.  Synchronous, like the renders;
+ * must not overlap a render or an update of the same scene.  rt_get_stats and the tail flag are left alone.  The workspace
+ * (a path pool of RT_RQ_CHUNK rays, environment variable, default 2^22; larger batches run in chunks) belongs to the scene,
+ * is allocated by the first query, is separate from the render's pool and is freed by rt_scene_destroy.                  */
+#define RT_RAY_HIT          1u   /* something was hit (surface or environment) */
+#define RT_RAY_FRONT_FACE   2u   /* HitRecord::front_face */
+#define RT_RAY_ENVIRONMENT  4u   /* the hit is a Sky (t = +inf) or a Sun (t = DBL_MAX), as the reference reports them */
+typedef struct RtRayHit {        /* 96 bytes */
+    double   t;                  /* miss: +inf, flags = 0, ids = -1, the other reals 0 */
+    double   pos[3], normal[3];  /* HitRecord::hit_pos / ::normal as the reference leaves them after Transform::test:
+                                    world space, facing against the ray, BEFORE any normal map */
+    double   u, v;               /* HitRecord::u, ::v, always computed (not only when the material reads them) */
+    int32_t  material;           /* index into RtSceneDesc.materials */
+    int32_t  node;               /* index into RtSceneDesc.nodes of the Sphere / Plane / Mesh / Sky / Sun node that was hit */
+    int32_t  prim;               /* Mesh: triangle index in RtMesh.tri_pos order (NOT the leaf slot); else -1 */
+    uint32_t flags;              /* RT_RAY_* */
+    uint64_t _reserved;          /* zero */
+} RtRayHit;
+typedef struct RtRayQueryStats {
+    double   kernel_ms;          /* HIP-event time of the query's kernels, all chunks (copies of the host variants excluded) */
+    uint64_t rays;
+    uint32_t n_chunks, precision;
+    uint32_t _reserved[4];
+} RtRayQueryStats;
+
+/* Closest hit of world.test(ray, Interval(0.001, inf)) - the interval every ray of the render is cast with - for n caller
+ * rays: origins / dirs = n x 3 doubles; directions need not be unit length, t is in units of |dir|.  The scene's own search
+ * kernels run, chosen as a render chooses them, so ties are the render's (equal t: the primitive the reference visits
+ * first; two triangles at exactly equal t: either).                                                                   */
+int rt_trace_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* hits_out);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_trace_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, uint32_t precision,
+                         RtRayHit* d_hits_out, void* stream);
+/* out[i] = 1 iff a Sphere, Plane or mesh triangle is hit inside Interval(t_min[i], t_max[i]) (both ends excluded); Sky and
+ * Sun never occlude.  t_min NULL = 0.001 for every ray, t_max NULL = +inf.  The hit is not identified and need not be the
+ * nearest: the answer is 1 iff some primitive's own reference test accepts inside the interval and every reference
+ * ancestor box of that primitive passes the reference's box test with that same interval.                             */
+int rt_occluded(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
+                uint32_t precision, uint8_t* out);
+int rt_occluded_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const double* d_t_min,
+                       const double* d_t_max, uint32_t precision, uint8_t* d_out, void* stream);
+int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out);   /* of the last query on this scene */
+/* Host only, needs no device: nodes_out[pc] = RtSceneDesc.nodes index that op pc of the compiled program came from (-1 for
+ * ops that belong to no single node), laid out like rt_scene_program's ops: up to `capacity` entries are written,
+ * *n_ops_out = the program's length; nodes_out may be NULL.                                                            */
+int rt_scene_op_nodes(const RtSceneDesc* desc, int32_t* nodes_out, uint32_t capacity, uint32_t* n_ops_out);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

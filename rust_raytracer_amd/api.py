@@ -184,6 +184,18 @@ class RtSceneUpdateInfo(C.Structure):
                 ("refit_kernel_ms", C.c_double), ("total_ms", C.c_double), ("_reserved", C.c_uint32 * 4)]
 
 
+class RtRayQueryStats(C.Structure):
+    _fields_ = [("kernel_ms", C.c_double), ("rays", C.c_uint64), ("n_chunks", C.c_uint32), ("precision", C.c_uint32),
+                ("_reserved", C.c_uint32 * 4)]
+
+
+# RtRayHit (include/rt_mi355.h) as a numpy structured dtype: DeviceScene.trace_rays returns an array of it
+RT_RAY_HIT, RT_RAY_FRONT_FACE, RT_RAY_ENVIRONMENT = 1, 2, 4
+RtRayHit = np.dtype([("t", "<f8"), ("pos", "<f8", (3,)), ("normal", "<f8", (3,)), ("u", "<f8"), ("v", "<f8"), ("material", "<i4"),
+                     ("node", "<i4"), ("prim", "<i4"), ("flags", "<u4"), ("_reserved", "<u8")])
+assert RtRayHit.itemsize == 96
+
+
 class RtError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"rt status {status}: {message}")
@@ -220,6 +232,8 @@ def load_host_lib() -> C.CDLL:
         lib.rth_band_rows.restype = C.c_uint32
         lib.rth_samples_per_pixel.argtypes = [C.c_void_p]
         lib.rth_samples_per_pixel.restype = C.c_uint32
+        lib.rth_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.rth_pick.restype = C.c_uint32
         lib.rth_log.argtypes = [C.c_void_p]
         lib.rth_log.restype = C.c_char_p
         lib.rth_make_camera.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -356,6 +370,18 @@ def load_device_lib() -> C.CDLL:
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
+        if hasattr(lib, "rt_trace_rays"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            for name, res, args in (
+                    ("rt_trace_rays", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+                    ("rt_trace_rays_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+                    ("rt_occluded", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+                    ("rt_occluded_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                     C.c_void_p, C.c_void_p]),
+                    ("rt_ray_query_stats", C.c_int, [C.c_void_p, C.POINTER(RtRayQueryStats)]),
+                    ("rt_scene_op_nodes", C.c_int, [C.POINTER(RtSceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
         lib.rt_last_error.argtypes = []
         lib.rt_last_error.restype = C.c_char_p
         _device_lib = lib
@@ -464,6 +490,21 @@ def scene_program(desc) -> tuple:
                  "split": bool(plan & 1), "vol_prims": bool(plan & 2), "multi_mesh": bool(plan & 4), "group_bvh": bool(plan & 8)}
 
 
+def scene_op_nodes(desc) -> np.ndarray:
+    """rt_scene_op_nodes: per op of the compiled program (api.scene_program order) the RtSceneDesc.nodes index it came from,
+    -1 for ops that belong to no single node; host only."""
+    lib = load_device_lib()
+    n = C.c_uint32()
+    st = lib.rt_scene_op_nodes(desc, None, 0, C.byref(n))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    nodes = np.full(n.value, -1, dtype=np.int32)
+    st = lib.rt_scene_op_nodes(desc, nodes.ctypes.data, n.value, C.byref(n))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return nodes
+
+
 def light_groups_auto(desc, max_groups: int = RT_LIGHT_GROUPS_MAX, has_background: bool = False) -> RtLightGroups:
     """rt_light_groups_auto (host only): group 0 = unlit and everything that does not emit, one group per Emissive material
     of `world` in material order, then the background; ids beyond max_groups - 1 share that id."""
@@ -528,6 +569,9 @@ class HostScene:
         self.gpus = lib.rth_gpus(handle)
         self.spp = lib.rth_samples_per_pixel(handle)
         self.log = lib.rth_log(handle).decode()
+        xy = np.zeros((lib.rth_pick(handle, None, 0), 2), dtype=np.uint32)
+        lib.rth_pick(handle, xy.ctypes.data, len(xy))
+        self.pick = [(int(x), int(y)) for x, y in xy]  # --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
 
     @property
     def width(self) -> int:
@@ -720,6 +764,65 @@ class DeviceScene:
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
         return tuple(int(x) for x in out)
+
+    @staticmethod
+    def _rays(origins, dirs) -> tuple:
+        """(n, 3) float64 C-contiguous origins and directions, broadcast against each other."""
+        o, d = np.asarray(origins, dtype=np.float64), np.asarray(dirs, dtype=np.float64)
+        if o.shape[-1:] != (3,) or d.shape[-1:] != (3,):
+            raise ValueError("origins and dirs must have a last axis of 3")
+        o, d = np.broadcast_arrays(np.atleast_2d(o), np.atleast_2d(d))
+        if o.ndim != 2:
+            raise ValueError("origins and dirs must be (n, 3) or (3,)")
+        return np.ascontiguousarray(o), np.ascontiguousarray(d)
+
+    def trace_rays(self, origins, dirs, precision: int = RT_PRECISION_F64) -> np.ndarray:
+        """rt_trace_rays: the closest hit of every ray over (0.001, inf) as an (n,) array of api.RtRayHit.  origins / dirs:
+        (n, 3) or (3,) (broadcast); directions need not be unit length."""
+        o, d = self._rays(origins, dirs)
+        out = np.zeros(len(o), dtype=RtRayHit)
+        st = self._lib.rt_trace_rays(self._h, len(o), o.ctypes.data, d.ctypes.data, precision, out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out
+
+    def trace_rays_device(self, n: int, d_origins_ptr: int, d_dirs_ptr: int, d_hits_ptr: int, precision: int = RT_PRECISION_F64,
+                          stream: int = 0) -> None:
+        """rt_trace_rays_device: n x 3 doubles each in HBM -> n RtRayHit records (96 B each) in HBM."""
+        st = self._lib.rt_trace_rays_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None), precision,
+                                            C.c_void_p(d_hits_ptr or None), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def occluded(self, origins, dirs, t_min=None, t_max=None, precision: int = RT_PRECISION_F64) -> np.ndarray:
+        """rt_occluded: (n,) bool, True where a sphere, quad or triangle is hit inside (t_min, t_max).  t_min / t_max: None
+        (0.001 / inf), a scalar or (n,)."""
+        o, d = self._rays(origins, dirs)
+        n = len(o)
+        lo = None if t_min is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=np.float64), (n,)))
+        hi = None if t_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n,)))
+        out = np.zeros(n, dtype=np.uint8)
+        st = self._lib.rt_occluded(self._h, n, o.ctypes.data, d.ctypes.data, None if lo is None else lo.ctypes.data,
+                                   None if hi is None else hi.ctypes.data, precision, out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out.astype(bool)
+
+    def occluded_device(self, n: int, d_origins_ptr: int, d_dirs_ptr: int, d_out_ptr: int, d_t_min_ptr: int = 0, d_t_max_ptr: int = 0,
+                        precision: int = RT_PRECISION_F64, stream: int = 0) -> None:
+        """rt_occluded_device: n bytes (0 / 1) in HBM; d_t_min_ptr / d_t_max_ptr 0 = the defaults."""
+        st = self._lib.rt_occluded_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None),
+                                          C.c_void_p(d_t_min_ptr or None), C.c_void_p(d_t_max_ptr or None), precision,
+                                          C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def ray_query_stats(self) -> RtRayQueryStats:
+        s = RtRayQueryStats()
+        st = self._lib.rt_ray_query_stats(self._h, C.byref(s))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return s
 
     def stats(self) -> RtRenderStats:
         s = RtRenderStats()

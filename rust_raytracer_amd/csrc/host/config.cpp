@@ -231,6 +231,23 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             }
             if (cfg.light_mix.size() > RT_LIGHT_GROUPS_MAX) { *err = "Light mix has more than " + std::to_string(RT_LIGHT_GROUPS_MAX) + " weights"; return false; }
             cfg.has_light_mix = true;
+        } else if (key == "-pick") {  // new: ray queries through pixel centres (rt_trace_rays) instead of a render
+            cfg.pick.clear();
+            size_t pos = 0;
+            for (;;) {
+                const size_t colon = value.find(':', pos);
+                const std::string item = value.substr(pos, colon == std::string::npos ? std::string::npos : colon - pos);
+                const size_t comma = item.find(',');
+                size_t x = 0, y = 0;
+                if (comma == std::string::npos || !parse_usize(item.substr(0, comma), &x) || !parse_usize(item.substr(comma + 1), &y) ||
+                    x > 0xFFFFFFFFu || y > 0xFFFFFFFFu) {
+                    *err = "Pick must be a list of pixels <x>,<y>[:<x>,<y>...] (non-negative integers)";
+                    return false;
+                }
+                cfg.pick.emplace_back(uint32_t(x), uint32_t(y));
+                if (colon == std::string::npos) break;
+                pos = colon + 1;
+            }
         }
         // unknown keys: ignored (config.rs:146)
     }

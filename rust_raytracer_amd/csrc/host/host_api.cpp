@@ -46,6 +46,10 @@ int rth_load(int argc, const char* const* argv, RtHost** out) {
     // SceneConfig::merge(scene defaults, CLI) then Camera::new (scene.rs:144-150, golden_monkey.rs:35-46)
     rth::SceneConfig merged = rth::merge(host->scene.scene_config, host->config.scene);
     rth::make_camera(merged, &host->camera);
+    for (const auto& px : host->config.pick)  // the frame's size is known only now (scene file and flags merged)
+        if (px.first >= host->camera.image_width || px.second >= host->camera.image_height)
+            return fail("Pick pixel " + std::to_string(px.first) + "," + std::to_string(px.second) + " is outside the " +
+                        std::to_string(host->camera.image_width) + "x" + std::to_string(host->camera.image_height) + " frame");
     host->desc = host->scene.builder.finish(host->scene.world, host->scene.lights,
                                             host->config.bvh_on_device ? RT_SCENE_BVH_ON_DEVICE : 0u);
 
@@ -86,6 +90,11 @@ int32_t rth_light_mix(const RtHost* host, double* weights_out, uint32_t capacity
     const auto& w = host->config.light_mix;
     for (uint32_t k = 0; k < capacity && k < w.size(); k++) weights_out[k] = w[k];
     return int32_t(w.size());
+}
+uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity) {
+    const auto& p = host->config.pick;
+    for (uint32_t k = 0; k < capacity && k < p.size(); k++) { xy_out[2 * k] = p[k].first; xy_out[2 * k + 1] = p[k].second; }
+    return uint32_t(p.size());
 }
 double rth_noise_threshold(const RtHost* host) { return host->config.noise_threshold; }
 int32_t rth_adaptive_min(const RtHost* host) { return host->config.adaptive_min; }

@@ -3,6 +3,7 @@
 #include <memory>
 #include <optional>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../../../include/rt_host.h"
@@ -45,6 +46,7 @@ struct Config {
     int32_t adaptive_min = -1;     // --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>: -1 = the library's default
     int32_t adaptive_check = -1;
     int32_t adaptive_radius = -1;
+    std::vector<std::pair<uint32_t, uint32_t>> pick;  // --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176
 

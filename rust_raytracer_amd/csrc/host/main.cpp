@@ -7,7 +7,9 @@
 //   --seed=<u64>  --gpus=<n>  --precision=f64|f32  --pipeline=auto|mega|wavefront  --bvh=host|device
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
-//   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]
+//   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
+// --pick=<x>,<y>[:...] renders nothing: the ray through the centre of each named pixel (no lens, no jitter) is cast with
+// rt_trace_rays and one line per pixel is printed: node, node type, material, triangle, t, position.
 // With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
 // the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
 // --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
@@ -189,6 +191,38 @@ static int render_sequence(RtHost* host, int argc, char** argv, const std::vecto
     return 0;
 }
 
+// --pick: closest hits of the rays through the named pixels' centres, one line each; returns the process exit status.
+static int pick_pixels(RtHost* host) {
+    const RtCameraDesc* cam = rth_camera(host);
+    const RtSceneDesc* desc = rth_scene(host);
+    const uint32_t n = rth_pick(host, nullptr, 0);
+    std::vector<uint32_t> xy(2 * size_t(n));
+    rth_pick(host, xy.data(), n);
+    std::vector<double> o(3 * size_t(n)), d(3 * size_t(n));
+    for (uint32_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) {
+            o[3 * size_t(i) + a] = cam->position[a];
+            d[3 * size_t(i) + a] = cam->first_pixel[a] + double(xy[2 * i]) * cam->pixel_delta_u[a] + double(xy[2 * i + 1]) * cam->pixel_delta_v[a] - cam->position[a];
+        }
+    RtScene* scene = nullptr;
+    if (rt_scene_create(desc, 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    std::vector<RtRayHit> hits(n);
+    if (rt_trace_rays(scene, n, o.data(), d.data(), rth_params(host)->precision, hits.data()) != RT_OK) return fail(rt_last_error());
+    static const char* const kTypes[] = {"?", "sphere", "plane", "mesh", "list", "transform", "bvh", "sky", "sun", "volume", "null"};
+    for (uint32_t i = 0; i < n; i++) {
+        const RtRayHit& h = hits[i];
+        if (!(h.flags & RT_RAY_HIT)) {
+            std::printf("Pick %u,%u: miss\n", xy[2 * i], xy[2 * i + 1]);
+            continue;
+        }
+        const uint32_t type = h.node >= 0 && uint32_t(h.node) < desc->n_nodes ? desc->nodes[h.node].type : 0u;
+        std::printf("Pick %u,%u: node %d (%s) material %d triangle %d t %.17g position %.17g %.17g %.17g\n", xy[2 * i], xy[2 * i + 1], h.node,
+                    type <= 10u ? kTypes[type] : "?", h.material, h.prim, h.t, h.pos[0], h.pos[1], h.pos[2]);
+    }
+    return 0;
+}
+
 int main(int argc, char** argv) {
     using clock = std::chrono::steady_clock;
     auto t0 = clock::now();
@@ -223,6 +257,11 @@ int main(int argc, char** argv) {
     if (available < 1) {
         std::fprintf(stderr, "Error: no HIP device (the render path has no CPU fallback)\n");
         return 1;
+    }
+    if (rth_pick(host, nullptr, 0) != 0) {
+        const int rc = pick_pixels(host);
+        rth_destroy(host);
+        return rc;
     }
     if (!sequence.empty()) {
         if (gpus > 1 || rth_progressive(host) || rth_noise_threshold(host) > 0.0 || rth_light_groups(host) || rth_denoise(host))

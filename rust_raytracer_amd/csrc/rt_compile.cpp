@@ -61,13 +61,15 @@ struct Compiler {
     }
 
     int32_t next_rank = 1;  // reference visiting order of the hit-producing ops (Op::skip)
-    void emit(int32_t type, int32_t arg) {
+    // node: the RtSceneDesc node a hit-producing op came from (CompiledScene::op_node); -1 for ops of no single node
+    void emit(int32_t type, int32_t arg, int32_t node = -1) {
         int32_t rank = 0;
         switch (type) {
             case OP_SPHERE: case OP_PLANE: case OP_MESH: case OP_SKY: case OP_SUN: case OP_VOL_END: rank = next_rank++; break;
             default: break;
         }
         out.ops.push_back({type, arg, rank, chain_id()});
+        out.op_node.push_back(node);
     }
 
     // ---- primitive groups: an object-BVH / list subtree made of spheres and quads only is re-built ----
@@ -227,8 +229,8 @@ struct Compiler {
                 std::vector<size_t> guard_ops;
                 for (int32_t gb : p.guards) { guard_ops.push_back(out.ops.size()); emit(OP_BOUNDS, gb); }
                 const RtNode& nd = d.nodes[p.node];
-                if (nd.type == RT_NODE_SPHERE) emit(OP_SPHERE, sphere_index(p.node));
-                else emit(OP_PLANE, plane_index(p.node));
+                if (nd.type == RT_NODE_SPHERE) emit(OP_SPHERE, sphere_index(p.node), int32_t(p.node));
+                else emit(OP_PLANE, plane_index(p.node), int32_t(p.node));
                 out.ops.back().skip = rank_base + p.rank_order;  // the reference's visiting order, not the emission order
                 prim_pc[idx[i]] = int32_t(out.ops.size()) - 1;
                 for (size_t go : guard_ops) out.ops[go].skip = int32_t(out.ops.size());
@@ -547,23 +549,23 @@ struct Compiler {
             case RT_NODE_SPHERE: {
                 int32_t i = sphere_index(node);
                 if (i < 0) return false;
-                emit(OP_SPHERE, i);
+                emit(OP_SPHERE, i, int32_t(node));
                 return true;
             }
             case RT_NODE_PLANE: {
                 int32_t i = plane_index(node);
                 if (i < 0) return false;
-                emit(OP_PLANE, i);
+                emit(OP_PLANE, i, int32_t(node));
                 return true;
             }
             case RT_NODE_SKY:
                 if (!check_material(n.material)) return false;
-                emit(OP_SKY, n.material);
+                emit(OP_SKY, n.material, int32_t(node));
                 return true;
             case RT_NODE_SUN: {
                 int32_t i = sun_index(node);
                 if (i < 0) return false;
-                emit(OP_SUN, i);
+                emit(OP_SUN, i, int32_t(node));
                 return true;
             }
             case RT_NODE_MESH: {
@@ -578,7 +580,7 @@ struct Compiler {
                 if (d.meshes[n.mesh].tri_uv) mi.flags |= MESH_HAS_UV;
                 mi.n_tris = d.meshes[n.mesh].n_triangles;
                 out.meshes.push_back(mi);
-                emit(OP_MESH, int32_t(out.meshes.size()) - 1);
+                emit(OP_MESH, int32_t(out.meshes.size()) - 1, int32_t(node));
                 return true;
             }
             case RT_NODE_LIST:
@@ -1101,6 +1103,7 @@ int compile_scene(const RtSceneDesc* desc, CompiledScene* out, std::string* err,
     if (!c.compile_node(desc->world_root, 0)) return c.status;
     c.chain.clear();
     out->ops.push_back({OP_END, 0, 0, c.chain_id()});
+    out->op_node.push_back(-1);
     for (size_t pc = 0; pc < out->ops.size(); pc++)
         if (out->ops[pc].type == OP_MESH) out->mesh_ops.push_back(int32_t(pc));
     if (!c.compile_lights()) return c.status;

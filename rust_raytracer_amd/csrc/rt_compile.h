@@ -12,6 +12,7 @@ namespace rt {
 
 struct CompiledScene {
     std::vector<Op> ops;
+    std::vector<int32_t> op_node;            // per op: the RtSceneDesc node a hit-producing op came from, else -1 (ray queries, rt_scene_op_nodes)
     std::vector<Bounds<double>> bounds;
     std::vector<int32_t> chain_offsets, chain_items;
     std::vector<Xform<double>> xforms;

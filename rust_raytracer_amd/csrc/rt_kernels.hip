@@ -17,6 +17,7 @@
 #include "rt_aov.h"
 #include "rt_compile.h"
 #include "rt_device.h"
+#include "rt_query.h"
 #include "rt_refit.h"
 #include "rt_wavefront.h"
 
@@ -657,6 +658,27 @@ struct RtScene {
         hipEvent_t ev_res[2] = {nullptr, nullptr};
         std::vector<hipEvent_t> events;
     } wf;
+    // ray queries (rt_trace_rays / rt_occluded): a workspace of their own, allocated by the first query, so that a query
+    // between two progressive passes never makes wf_ensure re-allocate the render's pool
+    struct Query {
+        uint32_t capacity = 0;         // slots of the pool (grows only)
+        size_t real_size = 0;          // sizeof(R) the pool was allocated for
+        std::vector<void*> allocs;     // the pool's arrays, queue, mesh queue
+        void* pool_view = nullptr;     // host copy of WfPool<R>: ray and hit-record arrays only (the search kernels read nothing else)
+        uint32_t* queue = nullptr;
+        uint32_t* mesh_queue = nullptr;
+        void* mesh_spill = nullptr;
+        size_t mesh_spill_bytes = 0;
+        rt::WfCounters* d_ctr = nullptr;
+        rt::WfCounters* h_ctr = nullptr;   // pinned
+        int32_t* op_node = nullptr;        // CompiledScene::op_node / ::tri_order of generation `tables_generation`
+        uint32_t* tri_order = nullptr;
+        uint64_t tables_generation = ~0ull;
+        void* staging = nullptr;           // host variants: rays, intervals and results of one chunk
+        size_t staging_bytes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        RtRayQueryStats stats{};
+    } rq;
 };
 
 namespace rt {
@@ -1340,6 +1362,294 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     return RT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ray queries (include/rt_mi355.h; kernels in rt_query.hip)
+// ---------------------------------------------------------------------------------------------
+static void rq_release(RtScene::Query& q) {
+    for (void* p : q.allocs) (void)hipFree(p);
+    q.allocs.clear();
+    ::operator delete(q.pool_view);
+    q.pool_view = nullptr;
+    q.queue = nullptr;
+    q.mesh_queue = nullptr;
+    q.capacity = 0;
+    q.real_size = 0;
+}
+static void rq_destroy(RtScene::Query& q) {
+    rq_release(q);
+    if (q.mesh_spill) (void)hipFree(q.mesh_spill);
+    if (q.d_ctr) (void)hipFree(q.d_ctr);
+    if (q.h_ctr) (void)hipHostFree(q.h_ctr);
+    if (q.op_node) (void)hipFree(q.op_node);
+    if (q.tri_order) (void)hipFree(q.tri_order);
+    if (q.staging) (void)hipFree(q.staging);
+    if (q.ev0) (void)hipEventDestroy(q.ev0);
+    if (q.ev1) (void)hipEventDestroy(q.ev1);
+    q = RtScene::Query{};
+}
+
+static uint32_t rq_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(64u, env_u32("RT_RQ_CHUNK", 1u << 22))); }
+
+// Events, counters and (closest hit: `pool`) a pool of at least `capacity` slots in R.
+template <typename R>
+int rq_ensure(RtScene* s, uint32_t capacity, bool pool) {
+    RtScene::Query& q = s->rq;
+    if (!q.ev0) HIP_TRY(hipEventCreate(&q.ev0));
+    if (!q.ev1) HIP_TRY(hipEventCreate(&q.ev1));
+    if (!q.d_ctr) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q.d_ctr), sizeof(WfCounters)));
+    if (!q.h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&q.h_ctr), sizeof(WfCounters)));
+    if (!pool || (q.capacity >= capacity && q.real_size == sizeof(R))) return RT_OK;
+    rq_release(q);
+    auto* pl = new WfPool<R>();  // value-initialised: the arrays a query does not use stay NULL
+    q.pool_view = pl;
+    auto alloc = [&](size_t bytes, void** out) -> int {
+        const hipError_t e = hipMalloc(out, bytes);
+        if (e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            return set_err(RT_E_NOMEM, "ray-query pool does not fit in device memory (RT_RQ_CHUNK sets its size)");
+        }
+        HIP_TRY(e);
+        q.allocs.push_back(*out);
+        return RT_OK;
+    };
+    auto build = [&]() -> int {
+        R** reals[] = {&pl->ox, &pl->oy, &pl->oz, &pl->dx, &pl->dy, &pl->dz, &pl->ht, &pl->hu, &pl->hv};
+        for (R** r : reals)
+            if (int st = alloc(size_t(capacity) * sizeof(R), reinterpret_cast<void**>(r))) return st;
+        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&pl->hpc))) return st;
+        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&pl->htri))) return st;
+        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&q.queue))) return st;
+        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&q.mesh_queue))) return st;
+        return RT_OK;
+    };
+    if (int st = build()) {
+        rq_release(q);
+        return st;
+    }
+    pl->capacity = capacity;
+    q.capacity = capacity;
+    q.real_size = sizeof(R);
+    return RT_OK;
+}
+
+// op -> node and leaf slot -> triangle tables of the scene as it stands (uploaded again after an rt_scene_update)
+static int rq_tables(RtScene* s, hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    if (q.tables_generation == s->generation && q.op_node) return RT_OK;
+    if (q.op_node) (void)hipFree(q.op_node);
+    if (q.tri_order) (void)hipFree(q.tri_order);
+    q.op_node = nullptr;
+    q.tri_order = nullptr;
+    const CompiledScene& cs = s->compiled;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q.op_node), std::max<size_t>(1, cs.op_node.size()) * 4));
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q.tri_order), std::max<size_t>(1, cs.tri_order.size()) * 4));
+    if (!cs.op_node.empty()) HIP_TRY(hipMemcpyAsync(q.op_node, cs.op_node.data(), cs.op_node.size() * 4, hipMemcpyHostToDevice, stream));
+    if (!cs.tri_order.empty()) HIP_TRY(hipMemcpyAsync(q.tri_order, cs.tri_order.data(), cs.tri_order.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    q.tables_generation = s->generation;
+    return RT_OK;
+}
+
+static int rq_staging(RtScene::Query& q, size_t bytes) {
+    if (q.staging_bytes >= bytes) return RT_OK;
+    if (q.staging) (void)hipFree(q.staging);
+    q.staging = nullptr;
+    q.staging_bytes = 0;
+    HIP_TRY(hipMalloc(&q.staging, bytes));
+    q.staging_bytes = bytes;
+    return RT_OK;
+}
+
+// One pass of the scene's search kernels over slots 0 .. m-1 of the query pool: the kernels render_wavefront launches at
+// the head of an iteration for a lean (no counters), volume-free render, chosen by the same plan and the same switches
+// (RT_WF_SPLIT / _GROUPS / _NODES / _MESH_MULTI / _CONES, RT_LDS_*), with the query workspace's queues and counters.
+template <typename R>
+int query_search_pass(RtScene* s, DeviceScene<R>& ds, const WfPool<R>& pool, uint32_t m, hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    const size_t lds = size_t(ds.view.stack_entries) * 256 * sizeof(int);
+    if (lds > 160 * 1024) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the LDS traversal stack");
+    int n_cu = 0, blocks_per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device));
+    const WavefrontPlan plan = plan_wavefront(s->compiled);
+    const int n_mesh_ops = int(s->compiled.mesh_ops.size());
+    const bool use_split = env_u32("RT_WF_SPLIT", 1) != 0 && plan.split;
+    const bool prims_only = use_split && n_mesh_ops == 0;
+    const bool split = use_split && n_mesh_ops > 0;
+    const bool multi_mesh = plan.multi_mesh || env_u32("RT_WF_MESH_MULTI", 0) != 0;
+    const int node_kind = env_u32("RT_WF_NODES", 1) != 0 ? 1 : 0;
+    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    const int mesh_levels = int(s->compiled.max_bvh4_stack) + 1;
+    const int lds_levels = std::min<int>(mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
+    const size_t lds_mesh = size_t(lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
+    if (split) {
+        if (node_kind == 1) {
+            if (multi_mesh) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 1, true>, 256, lds_mesh));
+            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 1, false>, 256, lds_mesh));
+        } else {
+            if (multi_mesh) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 0, true>, 256, lds_mesh));
+            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 0, false>, 256, lds_mesh));
+        }
+        blocks_per_cu = std::min<int>(std::max(blocks_per_cu, 1), int(env_u32("RT_WF_MESH_BLOCKS", 64)));
+    } else {
+        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_intersect<R, false, false>, 256, lds));
+    }
+    if (blocks_per_cu < 1) blocks_per_cu = 1;
+    const uint32_t isect_blocks = uint32_t(n_cu) * uint32_t(blocks_per_cu);
+    if (split) {
+        const size_t need = size_t(std::max(mesh_levels - lds_levels, 1)) * isect_blocks * 256 * sizeof(uint2);
+        if (need > q.mesh_spill_bytes) {
+            if (q.mesh_spill) (void)hipFree(q.mesh_spill);
+            q.mesh_spill = nullptr;
+            q.mesh_spill_bytes = 0;
+            HIP_TRY(hipMalloc(&q.mesh_spill, need));
+            q.mesh_spill_bytes = need;
+        }
+    }
+    const uint32_t refill_min = env_u32("RT_WF_REFILL", 32);
+    const uint32_t inner_min = env_u32("RT_WF_INNER_MIN", 16);
+    const bool lds_tables = env_u32("RT_LDS_TABLES", 1) != 0;
+    const uint32_t lds_budget = env_u32("RT_LDS_BUDGET", 32u * 1024u);
+    uint32_t staged_prims = 0;  // the longest prefix of whole tables that fits the budget, as render_wavefront stages it
+    if (lds_tables) {
+        const SmallLayout& L = ds.view.lay;
+        if (L.total_bytes <= lds_budget) staged_prims = L.total_bytes;
+        else {
+            uint32_t best = 0;
+            for (int k = 0; k < ST_COUNT; k++)
+                if (L.end[k] <= lds_budget && L.end[k] > best) best = L.end[k];
+            staged_prims = (best + 15u) & ~15u;
+        }
+    }
+    const uint32_t group_levels = uint32_t(ds.view.group_stack_levels);
+    const size_t group_node_bytes = size_t(ds.view.n_group_nodes) * sizeof(BvhNode4q);
+    const bool groups = (split || prims_only) && plan.groups && env_u32("RT_WF_GROUPS", 1) != 0;
+    const size_t lds_groups = groups ? size_t(group_levels) * 256 * 8 + group_node_bytes : 0;
+    if (groups && lds_groups + staged_prims > 44u * 1024u) staged_prims = 0;
+    const int lds_prims = staged_prims == 0 ? 0 : (staged_prims == ds.view.lay.total_bytes ? 1 : 2);
+
+    WfCounters init{};
+    init.n_in = m;
+    *q.h_ctr = init;
+    HIP_TRY(hipMemcpyAsync(q.d_ctr, q.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
+    if (split || prims_only) {
+#define RT_RQ_PRIMS(L, GR) hipLaunchKernelGGL((k_wf_prims<R, false, L, false, GR>), dim3((m + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_prims) : size_t(0)) + (GR ? lds_groups : size_t(0)) + (WF_CHUNK + 4) * 4, stream, ds.view, pool, q.queue, q.mesh_queue, q.d_ctr, s->d_counters, staged_prims, group_levels)
+        if (groups) { if (lds_prims == 2) RT_RQ_PRIMS(2, true); else if (lds_prims == 1) RT_RQ_PRIMS(1, true); else RT_RQ_PRIMS(0, true); }
+        else { if (lds_prims == 1) RT_RQ_PRIMS(1, false); else if (lds_prims == 2) RT_RQ_PRIMS(2, false); else RT_RQ_PRIMS(0, false); }
+#undef RT_RQ_PRIMS
+        if (!prims_only) {
+#define RT_RQ_MESH(ND, MU) hipLaunchKernelGGL((k_wf_mesh<R, false, ND, MU>), dim3(isect_blocks), dim3(256), lds_mesh, stream, ds.view, pool, q.mesh_queue, q.d_ctr, s->d_counters, refill_min, inner_min, static_cast<uint2*>(q.mesh_spill), lds_levels, &q.d_ctr->n_mesh, &q.d_ctr->cursor, cones_on)
+            if (node_kind == 1) { if (multi_mesh) RT_RQ_MESH(1, true); else RT_RQ_MESH(1, false); }
+            else { if (multi_mesh) RT_RQ_MESH(0, true); else RT_RQ_MESH(0, false); }
+#undef RT_RQ_MESH
+        }
+    } else {
+        hipLaunchKernelGGL((k_wf_intersect<R, false, false>), dim3(isect_blocks), dim3(256), lds, stream, ds.view, pool, q.queue, q.d_ctr, s->d_counters, refill_min);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+// n rays in chunks: (host variant: through the staging buffer) k_rq_load -> search pass -> k_rq_resolve.
+template <typename R>
+int trace_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, RtRayHit* out, bool host,
+                     hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    const uint32_t chunk = rq_chunk();
+    const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
+    if (int st = rq_ensure<R>(s, cap, true)) return st;
+    if (int st = rq_tables(s, stream)) return st;
+    if (host)
+        if (int st = rq_staging(q, size_t(cap) * (48 + sizeof(RtRayHit)))) return st;
+    const WfPool<R> full = *static_cast<WfPool<R>*>(q.pool_view);
+    const RqPool<R> rp{full.ox, full.oy, full.oz, full.dx, full.dy, full.dz, full.ht, full.hu, full.hv, full.hpc, full.htri};
+    const RqTables tb{q.op_node, q.tri_order};
+    double total_ms = 0.0;
+    uint32_t n_chunks = 0;
+    for (uint64_t off = 0; off < n; off += chunk) {
+        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
+        const double *d_o = origins + 3 * off, *d_d = dirs + 3 * off;
+        RtRayHit* d_out = out + off;
+        if (host) {
+            double* st_o = static_cast<double*>(q.staging);
+            double* st_d = st_o + 3 * size_t(cap);
+            HIP_TRY(hipMemcpyAsync(st_o, d_o, size_t(m) * 24, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(st_d, d_d, size_t(m) * 24, hipMemcpyHostToDevice, stream));
+            d_o = st_o;
+            d_d = st_d;
+            d_out = reinterpret_cast<RtRayHit*>(st_d + 3 * size_t(cap));
+        }
+        WfPool<R> pool = full;
+        pool.capacity = m;  // every slot is queued: the kernels address slot i for entry i
+        HIP_TRY(hipEventRecord(q.ev0, stream));
+        HIP_TRY(rq_load_launch<R>(rp, d_o, d_d, m, q.queue, stream));
+        if (int st = query_search_pass<R>(s, ds, pool, m, stream)) return st;
+        HIP_TRY(rq_resolve_launch<R>(ds.view, rp, tb, m, d_out, stream));
+        HIP_TRY(hipEventRecord(q.ev1, stream));
+        if (host) HIP_TRY(hipMemcpyAsync(out + off, d_out, size_t(m) * sizeof(RtRayHit), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, q.ev0, q.ev1));
+        total_ms += ms;
+        n_chunks++;
+    }
+    q.stats = RtRayQueryStats{};
+    q.stats.kernel_ms = total_ms;
+    q.stats.rays = n;
+    q.stats.n_chunks = n_chunks;
+    q.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+    return RT_OK;
+}
+
+template <typename R>
+int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const double* t_min,
+                   const double* t_max, uint8_t* out, bool host, hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
+    if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the occlusion kernel's LDS traversal stack");
+    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    const uint32_t chunk = rq_chunk();
+    const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
+    if (int st = rq_ensure<R>(s, cap, false)) return st;
+    if (host)
+        if (int st = rq_staging(q, size_t(cap) * (48 + 16 + 1))) return st;
+    double total_ms = 0.0;
+    uint32_t n_chunks = 0;
+    for (uint64_t off = 0; off < n; off += chunk) {
+        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
+        const double *d_o = origins + 3 * off, *d_d = dirs + 3 * off;
+        const double *d_lo = t_min ? t_min + off : nullptr, *d_hi = t_max ? t_max + off : nullptr;
+        uint8_t* d_out = out + off;
+        if (host) {
+            double* st_o = static_cast<double*>(q.staging);
+            double* st_d = st_o + 3 * size_t(cap);
+            double* st_lo = st_d + 3 * size_t(cap);
+            double* st_hi = st_lo + size_t(cap);
+            HIP_TRY(hipMemcpyAsync(st_o, d_o, size_t(m) * 24, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(st_d, d_d, size_t(m) * 24, hipMemcpyHostToDevice, stream));
+            if (d_lo) { HIP_TRY(hipMemcpyAsync(st_lo, d_lo, size_t(m) * 8, hipMemcpyHostToDevice, stream)); d_lo = st_lo; }
+            if (d_hi) { HIP_TRY(hipMemcpyAsync(st_hi, d_hi, size_t(m) * 8, hipMemcpyHostToDevice, stream)); d_hi = st_hi; }
+            d_o = st_o;
+            d_d = st_d;
+            d_out = reinterpret_cast<uint8_t*>(st_hi + size_t(cap));
+        }
+        HIP_TRY(hipEventRecord(q.ev0, stream));
+        HIP_TRY(rq_occluded_launch<R>(ds.view, d_o, d_d, d_lo, d_hi, m, levels, cones_on, d_out, stream));
+        HIP_TRY(hipEventRecord(q.ev1, stream));
+        if (host) HIP_TRY(hipMemcpyAsync(out + off, d_out, size_t(m), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, q.ev0, q.ev1));
+        total_ms += ms;
+        n_chunks++;
+    }
+    q.stats = RtRayQueryStats{};
+    q.stats.kernel_ms = total_ms;
+    q.stats.rays = n;
+    q.stats.n_chunks = n_chunks;
+    q.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+    return RT_OK;
+}
+
 static int validate_render_args(const RtCameraDesc* camera, const RtRenderParams* params) {
     if (params->sqrt_spt == 0 || params->thread_count == 0) return set_err(RT_E_INVALID, "sqrt_spt and thread_count must be positive");
     if (params->band_rows != 0 && params->n_parts > 1 && params->part >= params->n_parts) return set_err(RT_E_INVALID, "part >= n_parts");
@@ -1701,6 +2011,7 @@ void rt_scene_destroy(RtScene* s) {
     s->f64.reset();
     s->f32.reset();
     for (rt::RefitMesh& rm : s->refit) rm.release();
+    rt::rq_destroy(s->rq);
     rt::wf_release_pool(s->wf);
     if (s->wf.mesh_spill) (void)hipFree(s->wf.mesh_spill);
     if (s->wf.d_ctr) (void)hipFree(s->wf.d_ctr);
@@ -2886,6 +3197,84 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
     }
     (void)hipFree(d_buf);
     return st;
+}
+
+// ---- Ray queries (rt_query.hip) -----------------------------------------------------------------------------------------
+// Argument checks shared by the four entry points; *s_out = the scene with its tables of `precision` on the device.
+static int ray_query_begin(const RtScene* scene, uint32_t precision, const char* who, RtScene** s_out) {
+    using namespace rt;
+    if (!scene) return set_err(RT_E_INVALID, std::string(who) + ": NULL scene");
+    if (precision != RT_PRECISION_F64 && precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, std::string(who) + ": precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
+    if (!scene->compiled.volumes.empty())
+        return set_err(RT_E_UNSUPPORTED, std::string(who) + ": ray queries do not support scenes with volumes (a medium gives no deterministic surface)");
+    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
+    HIP_TRY(hipSetDevice(s->device));
+    if (precision == RT_PRECISION_F32) {
+        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
+    } else {
+        if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
+    }
+    *s_out = s;
+    return RT_OK;
+}
+
+static int trace_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* out,
+                           bool host, void* stream, const char* who) {
+    using namespace rt;
+    RtScene* s = nullptr;
+    if (int st = ray_query_begin(scene, precision, who, &s)) return st;
+    if (n == 0) return RT_OK;
+    if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    if (precision == RT_PRECISION_F32) return trace_rays_typed<float>(s, *s->f32, n, origins, dirs, out, host, st);
+    return trace_rays_typed<double>(s, *s->f64, n, origins, dirs, out, host, st);
+}
+
+static int occluded_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
+                         uint32_t precision, uint8_t* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    RtScene* s = nullptr;
+    if (int st = ray_query_begin(scene, precision, who, &s)) return st;
+    if (n == 0) return RT_OK;
+    if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    if (precision == RT_PRECISION_F32) return occluded_typed<float>(s, *s->f32, n, origins, dirs, t_min, t_max, out, host, st);
+    return occluded_typed<double>(s, *s->f64, n, origins, dirs, t_min, t_max, out, host, st);
+}
+
+int rt_trace_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* hits_out) {
+    return trace_rays_impl(scene, n, origins, dirs, precision, hits_out, true, nullptr, "rt_trace_rays");
+}
+int rt_trace_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, uint32_t precision,
+                         RtRayHit* d_hits_out, void* stream) {
+    return trace_rays_impl(scene, n, d_origins, d_dirs, precision, d_hits_out, false, stream, "rt_trace_rays_device");
+}
+int rt_occluded(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
+                uint32_t precision, uint8_t* out) {
+    return occluded_impl(scene, n, origins, dirs, t_min, t_max, precision, out, true, nullptr, "rt_occluded");
+}
+int rt_occluded_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const double* d_t_min,
+                       const double* d_t_max, uint32_t precision, uint8_t* d_out, void* stream) {
+    return occluded_impl(scene, n, d_origins, d_dirs, d_t_min, d_t_max, precision, d_out, false, stream, "rt_occluded_device");
+}
+int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out) {
+    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_ray_query_stats: NULL argument");
+    *out = scene->rq.stats;
+    return RT_OK;
+}
+int rt_scene_op_nodes(const RtSceneDesc* desc, int32_t* nodes_out, uint32_t capacity, uint32_t* n_ops_out) {
+    using namespace rt;
+    if (!desc || !n_ops_out) return set_err(RT_E_INVALID, "rt_scene_op_nodes: NULL argument");
+    CompiledScene cs;
+    std::string err;
+    CompileOptions opt;
+    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // as rt_scene_program
+    int st = compile_scene(desc, &cs, &err, opt);
+    if (st != RT_OK) return set_err(st, err);
+    *n_ops_out = uint32_t(cs.op_node.size());
+    if (nodes_out)
+        for (size_t i = 0; i < cs.op_node.size() && i < capacity; i++) nodes_out[i] = cs.op_node[i];
+    return RT_OK;
 }
 
 int rt_get_stats(const RtScene* scene, RtRenderStats* out) {
