@@ -80,8 +80,8 @@ struct CompileOptions {
 // pass in any order gives.  Returns the mesh's box.
 Bounds<double> refit_mesh_tables(CompiledScene& cs, const CompiledScene::MeshGeom& g, const RtMesh& m);
 
-// Which kernels the wavefront scheduler runs for a compiled scene (rt_kernels.hip render_wavefront; also reported by
-// rt_scene_program so that the choice is testable without a GPU).
+// Which kernels the wavefront scheduler runs for a compiled scene (rt_kernels.hip make_search_setup, for renders and ray
+// queries alike; also reported by rt_scene_program so that the choice is testable without a GPU).
 struct WavefrontPlan {
     bool split;        // k_wf_prims (+ k_wf_mesh when the program has mesh ops) instead of the combined k_wf_intersect
     bool vol_prims;    // ... with the volumes inside k_wf_prims<VOL>

@@ -785,6 +785,191 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
     return uint32_t(std::strtoul(v, nullptr, 10));
 }
 
+// A grow-only device buffer (pointer and size of a workspace): at least `need` bytes afterwards, contents not kept.  The
+// old buffer is released and the pair cleared BEFORE hipMalloc, so a failed allocation leaves (NULL, 0) behind and never a
+// size without its memory.
+template <typename T>
+static int grow_buffer(T*& p, size_t& bytes, size_t need) {
+    if (bytes >= need) return RT_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), need));
+    bytes = need;
+    return RT_OK;
+}
+
+// ---- Kernel selection.  Taking a kernel's address instantiates it, so each selector names exactly the variants the
+// library ships (tools/kernel_regs.py lists them) and a combination outside that set cannot be asked for.  Whoever needs a
+// kernel twice (occupancy query and launch, render and ray query) keeps the pointer a selector returned. ----
+template <typename R> using IntersectKernel = decltype(&k_wf_intersect<R, false, false>);
+template <typename R> using PrimsKernel = decltype(&k_wf_prims<R, false, 0, false, false>);
+template <typename R> using MeshKernel = decltype(&k_wf_mesh<R, false, 1, false>);
+template <typename R, typename G> using ShadeKernel = decltype(&k_wf_shade<R, false, 0, false, G, false>);
+
+template <typename R>
+IntersectKernel<R> pick_intersect(bool stats, bool vol) {
+    if (stats) return vol ? &k_wf_intersect<R, true, true> : &k_wf_intersect<R, true, false>;
+    return vol ? &k_wf_intersect<R, false, true> : &k_wf_intersect<R, false, false>;
+}
+
+// lds: 0 = tables from global memory, 1 = all staged, 2 = a prefix.  Volumes: no staged tables, no group BVHs.
+template <typename R, bool ST>
+PrimsKernel<R> pick_prims_st(bool vol, bool groups, int lds) {
+    if (vol) return &k_wf_prims<R, ST, 0, true, false>;
+    if (groups) return lds == 2 ? &k_wf_prims<R, ST, 2, false, true> : (lds == 1 ? &k_wf_prims<R, ST, 1, false, true> : &k_wf_prims<R, ST, 0, false, true>);
+    return lds == 2 ? &k_wf_prims<R, ST, 2, false, false> : (lds == 1 ? &k_wf_prims<R, ST, 1, false, false> : &k_wf_prims<R, ST, 0, false, false>);
+}
+template <typename R>
+PrimsKernel<R> pick_prims(bool stats, bool vol, bool groups, int lds) {
+    return stats ? pick_prims_st<R, true>(vol, groups, lds) : pick_prims_st<R, false>(vol, groups, lds);
+}
+
+template <typename R, bool ST>
+MeshKernel<R> pick_mesh_st(int node_kind, bool multi) {
+    if (node_kind == 1) return multi ? &k_wf_mesh<R, ST, 1, true> : &k_wf_mesh<R, ST, 1, false>;
+    return multi ? &k_wf_mesh<R, ST, 0, true> : &k_wf_mesh<R, ST, 0, false>;
+}
+template <typename R>
+MeshKernel<R> pick_mesh(bool stats, int node_kind, bool multi) {
+    return stats ? pick_mesh_st<R, true>(node_kind, multi) : pick_mesh_st<R, false>(node_kind, multi);
+}
+
+// The lean k_wf_shade of any group type (WfGroup, WfGroupSparse: restarts through the active list, WfGroupLG: the terminal's
+// light group beside the radiance).  Interpreter variant: tables from global memory (rare scenes, fewer instantiations).
+template <typename R, typename G>
+ShadeKernel<R, G> pick_shade_lean(int lds, bool tex) {
+    if (tex) return &k_wf_shade<R, false, 0, true, G>;
+    return lds == 1 ? &k_wf_shade<R, false, 1, false, G> : (lds == 2 ? &k_wf_shade<R, false, 2, false, G> : &k_wf_shade<R, false, 0, false, G>);
+}
+// Dense groups also have the counting variants and the one fused kernel (+ k_wf_prims' search as phase 4).
+template <typename R>
+ShadeKernel<R, WfGroup<R>> pick_shade(bool stats, int lds, bool tex, bool fuse) {
+    if (fuse) return &k_wf_shade<R, false, 1, false, WfGroup<R>, true>;
+    if (!stats) return pick_shade_lean<R, WfGroup<R>>(lds, tex);
+    if (tex) return &k_wf_shade<R, true, 0, true>;
+    return lds == 1 ? &k_wf_shade<R, true, 1, false> : (lds == 2 ? &k_wf_shade<R, true, 2, false> : &k_wf_shade<R, true, 0, false>);
+}
+
+// ---- Search setup: which of k_wf_prims / k_wf_mesh / k_wf_intersect serve a scene, and with which grid, LDS and
+// arguments.  Built by make_search_setup for renders and ray queries alike, which is what makes a query's answers the
+// render's hits; every switch below is read there and nowhere else. ----
+template <typename R>
+struct SearchSetup {
+    WavefrontPlan plan;
+    bool stats, vol;
+    bool use_split, prims_only, split;  // split: k_wf_prims + k_wf_mesh; prims_only: no mesh ops; neither: k_wf_intersect
+    bool multi_mesh;
+    int node_kind;
+    uint32_t cones_on;
+    int mesh_levels, lds_levels;        // k_wf_mesh's stack: levels in all / in LDS (the rest in the workspace's spill buffer)
+    uint32_t refill_min, inner_min;
+    bool lds_tables;                    // RT_LDS_TABLES / RT_LDS_BUDGET, for staged_prefix of the shade kernel's layout too
+    uint32_t lds_budget;
+    bool groups;
+    uint32_t group_levels;
+    size_t lds_groups;
+    uint32_t staged_prims;
+    int lds_prims;                      // kernel variant: none / all / prefix
+    size_t lds_isect, lds_mesh, lds_prims_launch;  // dynamic LDS of each launch
+    uint32_t isect_blocks;              // persistent grid of k_wf_mesh / k_wf_intersect
+    size_t spill_bytes;                 // what the workspace's mesh_spill must hold (0: no k_wf_mesh)
+    IntersectKernel<R> k_intersect;
+    PrimsKernel<R> k_prims;
+    MeshKernel<R> k_mesh;
+};
+
+// small tables staged in LDS by the prims / shade kernels: the longest prefix of whole tables (in the kernel's own table order)
+// that fits the budget; 32 KB keeps four workgroups per CU resident next to the queue lists
+static uint32_t staged_prefix(const SmallLayout& L, bool lds_tables, uint32_t lds_budget) {
+    if (!lds_tables) return 0u;
+    if (L.total_bytes <= lds_budget) return L.total_bytes;
+    uint32_t best = 0;  // tables are packed back to back in staging order: a table fits iff its end does
+    for (int k = 0; k < ST_COUNT; k++)
+        if (L.end[k] <= lds_budget && L.end[k] > best) best = L.end[k];
+    return (best + 15u) & ~15u;
+}
+
+// vol: volume ops (combined intersect kernel or k_wf_prims, VOL variant); ray queries have none.
+template <typename R>
+int make_search_setup(RtScene* s, DeviceScene<R>& ds, bool stats, bool vol, SearchSetup<R>* out) {
+    SearchSetup<R>& su = *out;
+    su.stats = stats;
+    su.vol = vol;
+    su.lds_isect = size_t(ds.view.stack_entries) * 256 * sizeof(int);
+    if (su.lds_isect > 160 * 1024) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the LDS traversal stack");
+    // which kernels serve this scene (rt_compile.cpp plan_wavefront); RT_WF_SPLIT=0 (tests): the combined kernel for every scene
+    su.plan = plan_wavefront(s->compiled);
+    const int n_mesh_ops = int(s->compiled.mesh_ops.size());
+    su.use_split = env_u32("RT_WF_SPLIT", 1) != 0 && su.plan.split;
+    su.prims_only = su.use_split && n_mesh_ops == 0;
+    su.split = su.use_split && n_mesh_ops > 0;
+    su.multi_mesh = su.plan.multi_mesh || env_u32("RT_WF_MESH_MULTI", 0) != 0;  // the general form of k_wf_mesh (env: A/B on single-mesh scenes, tests)
+    // k_wf_mesh keeps (child, entry distance) pairs: a shallow LDS part (occupancy) + a global spill part
+    // BVH node format of k_wf_mesh: 1 = 4-wide quantised (BvhNode4q, 64 B, default), 0 = 4-wide f32 (BvhNode4f, 128 B; A/B control).
+    // An 8-wide quantised node (a third fewer visits) was slower: profiles/r02/ab/node_width_and_size.txt.
+    su.node_kind = env_u32("RT_WF_NODES", 1) != 0 ? 1 : 0;
+    // Back-face cone test of the quantised node step: 0 = off (A/B control: the same code object, never-culling direction word).
+    su.cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    su.mesh_levels = int(s->compiled.max_bvh4_stack) + 1;
+    su.lds_levels = std::min<int>(su.mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
+    su.lds_mesh = size_t(su.lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
+    su.refill_min = env_u32("RT_WF_REFILL", 32);  // measured optimum (64 = no refill: -20 %)
+    su.inner_min = env_u32("RT_WF_INNER_MIN", 16);
+    su.lds_tables = env_u32("RT_LDS_TABLES", 1) != 0;
+    su.lds_budget = env_u32("RT_LDS_BUDGET", 32u * 1024u);
+    // re-built primitive groups as 4-wide BVHs inside k_wf_prims (OP_GROUP): nodes + a per-lane stack in LDS; scenes whose
+    // groups need more than that LDS (> 24 KB of nodes, > 16 stack levels) keep the op form.  RT_WF_GROUPS=0: A/B, tests.
+    su.group_levels = uint32_t(ds.view.group_stack_levels);
+    const size_t group_node_bytes = size_t(ds.view.n_group_nodes) * sizeof(BvhNode4q);
+    su.groups = (su.split || su.prims_only) && su.plan.groups && env_u32("RT_WF_GROUPS", 1) != 0;
+    su.lds_groups = su.groups ? size_t(su.group_levels) * 256 * 8 + group_node_bytes : 0;
+    su.staged_prims = staged_prefix(ds.view.lay, su.lds_tables, su.lds_budget);
+    if (su.groups && su.lds_groups + su.staged_prims > 44u * 1024u) su.staged_prims = 0;  // three workgroups per CU with the group data: tables from global memory
+    su.lds_prims = su.staged_prims == 0 ? 0 : (su.staged_prims == ds.view.lay.total_bytes ? 1 : 2);
+    su.lds_prims_launch = (vol ? size_t(0) : size_t(su.staged_prims) + su.lds_groups) + (WF_CHUNK + 4) * 4;
+    su.k_intersect = pick_intersect<R>(stats, vol);
+    su.k_prims = pick_prims<R>(stats, vol, su.groups, su.lds_prims);
+    su.k_mesh = pick_mesh<R>(stats, su.node_kind, su.multi_mesh);
+    // persistent grids: as many workgroups as stay resident.  The combined kernel's grid is the lean variant's at either
+    // setting of `stats`; k_wf_mesh's is the launched variant's own.
+    int n_cu = 0, blocks_per_cu = 0;
+    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device));
+    if (su.split) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, su.k_mesh, 256, su.lds_mesh));
+    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, pick_intersect<R>(false, vol), 256, su.lds_isect));
+    if (blocks_per_cu < 1) blocks_per_cu = 1;
+    if (su.split) blocks_per_cu = std::min<int>(blocks_per_cu, int(env_u32("RT_WF_MESH_BLOCKS", 64)));  // experiments: occupancy scaling
+    su.isect_blocks = uint32_t(n_cu) * uint32_t(blocks_per_cu);
+    su.spill_bytes = su.split ? size_t(std::max(su.mesh_levels - su.lds_levels, 1)) * su.isect_blocks * 256 * sizeof(uint2) : size_t(0);
+    return RT_OK;
+}
+
+// The search launches of one pass over a queue, on a workspace's queues and counters (RtScene::Wavefront or ::Query).
+struct SearchQueues {
+    const uint32_t* queue;
+    uint32_t* mesh_queue;
+    void* mesh_spill;
+    WfCounters* ctr;
+    DeviceCounters* counters;
+    hipStream_t stream;
+};
+// k_wf_prims over the first n_queued entries (an upper bound) of sq.queue; fills sq.mesh_queue
+template <typename R>
+void launch_prims(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq, uint32_t n_queued) {
+    hipLaunchKernelGGL(su.k_prims, dim3((n_queued + WF_CHUNK - 1) / WF_CHUNK), dim3(256), su.lds_prims_launch, sq.stream, ds.view, pool, sq.queue,
+                       sq.mesh_queue, sq.ctr, sq.counters, su.staged_prims, su.group_levels);
+}
+template <typename R>
+void launch_mesh(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq) {
+    hipLaunchKernelGGL(su.k_mesh, dim3(su.isect_blocks), dim3(256), su.lds_mesh, sq.stream, ds.view, pool, sq.mesh_queue, sq.ctr, sq.counters,
+                       su.refill_min, su.inner_min, static_cast<uint2*>(sq.mesh_spill), su.lds_levels, &sq.ctr->n_mesh, &sq.ctr->cursor, su.cones_on);
+}
+template <typename R>
+void launch_intersect(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq) {
+    hipLaunchKernelGGL(su.k_intersect, dim3(su.isect_blocks), dim3(256), su.lds_isect, sq.stream, ds.view, pool, sq.queue, sq.ctr, sq.counters,
+                       su.refill_min);
+}
+
 // Releases the path pool and its queues and marks the pool as absent, so that a failed re-allocation can never be
 // mistaken for a valid pool by a later render (and nothing is freed twice by rt_scene_destroy).
 static void wf_release_pool(RtScene::Wavefront& w) {
@@ -949,126 +1134,29 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     group = (n + (n + group - 1) / group - 1) / ((n + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
     if (bytes_per_replica > avail) return set_err(RT_E_NOMEM, "per-sample radiance buffer of one replica does not fit in device memory");
     size_t need = size_t(per_replica) * 24 * group;
-    if (w.sample_L_bytes < need) {
-        if (w.sample_L) (void)hipFree(w.sample_L);
-        w.sample_L = nullptr;
-        w.sample_L_bytes = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.sample_L), need));
-        w.sample_L_bytes = need;
-    }
+    if (int st = grow_buffer(w.sample_L, w.sample_L_bytes, need)) return st;
     if (lg) {
         const size_t need_g = size_t(per_replica) * group;
-        if (w.sample_G_bytes < need_g) {
-            if (w.sample_G) (void)hipFree(w.sample_G);
-            w.sample_G = nullptr;
-            w.sample_G_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.sample_G), need_g));
-            w.sample_G_bytes = need_g;
-        }
+        if (int st = grow_buffer(w.sample_G, w.sample_G_bytes, need_g)) return st;
         const size_t need_acc = group < n ? size_t(npix) * 24 * lg->n_groups : size_t(0);
-        if (w.acc_g_bytes < need_acc) {
-            if (w.acc_g) (void)hipFree(w.acc_g);
-            w.acc_g = nullptr;
-            w.acc_g_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.acc_g), need_acc));
-            w.acc_g_bytes = need_acc;
-        }
+        if (int st = grow_buffer(w.acc_g, w.acc_g_bytes, need_acc)) return st;
         const size_t need_t = size_t(lg->n_materials) + 2;
-        if (w.lg_table_bytes < need_t) {
-            if (w.lg_table) (void)hipFree(w.lg_table);
-            w.lg_table = nullptr;
-            w.lg_table_bytes = 0;
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.lg_table), need_t));
-            w.lg_table_bytes = need_t;
-        }
+        if (int st = grow_buffer(w.lg_table, w.lg_table_bytes, need_t)) return st;
         HIP_TRY(hipMemcpyAsync(w.lg_table, lg->table, need_t, hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));  // the host table may be the caller's stack
         for (hipEvent_t& e : w.ev_res)
             if (!e) HIP_TRY(hipEventCreate(&e));
     }
     const bool multi_group = group < n && !ad;  // adaptive: every group resolves into the accumulator's sums
-    if (multi_group && w.acc_bytes < npix * 24) {
-        if (w.acc) (void)hipFree(w.acc);
-        w.acc = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.acc), npix * 24));
-        w.acc_bytes = npix * 24;
-    }
+    if (multi_group)
+        if (int st = grow_buffer(w.acc, w.acc_bytes, size_t(npix) * 24)) return st;
 
-    const size_t lds = size_t(ds.view.stack_entries) * 256 * sizeof(int);
-    if (lds > 160 * 1024) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the LDS traversal stack");
-    int n_cu = 0, blocks_per_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device));
     const bool stats = p.collect_stats != 0;
     const bool vol = !s->compiled.volumes.empty();  // volume ops: combined intersect kernel, VOL variant
-    if (vol) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_intersect<R, false, true>, 256, lds));
-    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_intersect<R, false, false>, 256, lds));
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    // which kernels serve this scene (rt_compile.cpp plan_wavefront); RT_WF_SPLIT=0 (tests): the combined kernel for every scene
-    const WavefrontPlan plan = plan_wavefront(s->compiled);
-    const int n_mesh_ops = int(s->compiled.mesh_ops.size());
-    const bool use_split = env_u32("RT_WF_SPLIT", 1) != 0 && plan.split;
-    const bool prims_only = use_split && n_mesh_ops == 0;
-    const bool split = use_split && n_mesh_ops > 0;
-    const bool multi_mesh = plan.multi_mesh || env_u32("RT_WF_MESH_MULTI", 0) != 0;  // the general form of k_wf_mesh (env: A/B on single-mesh scenes, tests)
-    // k_wf_mesh keeps (child, entry distance) pairs: a shallow LDS part (occupancy) + a global spill part
-    // BVH node format of k_wf_mesh: 1 = 4-wide quantised (BvhNode4q, 64 B, default), 0 = 4-wide f32 (BvhNode4f, 128 B; A/B control).
-    // An 8-wide quantised node (a third fewer visits) was slower: profiles/r02/ab/node_width_and_size.txt.
-    const int node_kind = env_u32("RT_WF_NODES", 1) != 0 ? 1 : 0;
-    // Back-face cone test of the quantised node step: 0 = off (A/B control: the same code object, never-culling direction word).
-    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
-    const int mesh_levels = int(s->compiled.max_bvh4_stack) + 1;
-    const int lds_levels = std::min<int>(mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
-    const size_t lds_mesh = size_t(lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
-    if (split) {
-#define RT_MESH_OCC(ST, ND) do { if (multi_mesh) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, ST, ND, true>, 256, lds_mesh)); \
-                                 else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, ST, ND, false>, 256, lds_mesh)); } while (0)
-        if (stats) { if (node_kind == 1) RT_MESH_OCC(true, 1); else RT_MESH_OCC(true, 0); }
-        else { if (node_kind == 1) RT_MESH_OCC(false, 1); else RT_MESH_OCC(false, 0); }
-#undef RT_MESH_OCC
-        if (blocks_per_cu < 1) blocks_per_cu = 1;
-        blocks_per_cu = std::min<int>(blocks_per_cu, int(env_u32("RT_WF_MESH_BLOCKS", 64)));  // experiments: occupancy scaling
-    }
-    const uint32_t isect_blocks = uint32_t(n_cu) * uint32_t(blocks_per_cu);
-    if (split) {
-        size_t need = size_t(std::max(mesh_levels - lds_levels, 1)) * isect_blocks * 256 * sizeof(uint2);
-        if (need > w.mesh_spill_bytes) {
-            if (w.mesh_spill) (void)hipFree(w.mesh_spill);
-            w.mesh_spill = nullptr;
-            w.mesh_spill_bytes = 0;
-            HIP_TRY(hipMalloc(&w.mesh_spill, need));
-            w.mesh_spill_bytes = need;
-        }
-    }
-    const uint32_t refill_min = env_u32("RT_WF_REFILL", 32);  // measured optimum (64 = no refill: -20 %)
-    const uint32_t inner_min = env_u32("RT_WF_INNER_MIN", 16);
-    // small tables staged in LDS by the prims / shade kernels when they fit
-    // small tables staged in LDS by the prims / shade kernels: the longest prefix of whole tables (in the kernel's own table order)
-    // that fits the budget; 32 KB keeps four workgroups per CU resident next to the queue lists
-    const bool lds_tables = env_u32("RT_LDS_TABLES", 1) != 0;
-    const uint32_t lds_budget = env_u32("RT_LDS_BUDGET", 32u * 1024u);
-    auto staged_prefix = [&](const SmallLayout& L) -> uint32_t {
-        if (!lds_tables) return 0u;
-        if (L.total_bytes <= lds_budget) return L.total_bytes;
-        uint32_t best = 0;  // tables are packed back to back in staging order: a table fits iff its end does
-        for (int k = 0; k < ST_COUNT; k++) {
-            bool prefix_ok = L.end[k] <= lds_budget;
-            if (prefix_ok && L.end[k] > best) {
-                // every table that starts before this one ends must fit as well (it does: ends are monotone along the order)
-                best = L.end[k];
-            }
-        }
-        return (best + 15u) & ~15u;
-    };
-    // re-built primitive groups as 4-wide BVHs inside k_wf_prims (OP_GROUP): nodes + a per-lane stack in LDS; scenes whose
-    // groups need more than that LDS (> 24 KB of nodes, > 16 stack levels) keep the op form.  RT_WF_GROUPS=0: A/B, tests.
-    const uint32_t group_levels = uint32_t(ds.view.group_stack_levels);
-    const size_t group_node_bytes = size_t(ds.view.n_group_nodes) * sizeof(BvhNode4q);
-    const bool groups = (split || prims_only) && plan.groups && env_u32("RT_WF_GROUPS", 1) != 0;
-    const size_t lds_groups = groups ? size_t(group_levels) * 256 * 8 + group_node_bytes : 0;
-    uint32_t staged_prims = staged_prefix(ds.view.lay);
-    const uint32_t staged_shade = staged_prefix(ds.view.lay_shade);
-    if (groups && lds_groups + staged_prims > 44u * 1024u) staged_prims = 0;  // three workgroups per CU with the group data: tables from global memory
-    const int lds_prims = staged_prims == 0 ? 0 : (staged_prims == ds.view.lay.total_bytes ? 1 : 2);          // kernel variant: none / all / prefix
+    SearchSetup<R> su;
+    if (int st = make_search_setup<R>(s, ds, stats, vol, &su)) return st;
+    if (int st = grow_buffer(w.mesh_spill, w.mesh_spill_bytes, su.spill_bytes)) return st;
+    const uint32_t staged_shade = staged_prefix(ds.view.lay_shade, su.lds_tables, su.lds_budget);
     // k_wf_shade: all or nothing (a staged prefix read through flat instructions was 3 % slower than global memory on the default scene),
     // and only while five workgroups still fit a CU's 160 KB next to its lists (<= 23 KB of tables; RT_LDS_SHADE_MAX overrides)
     const uint32_t shade_tables_max = env_u32("RT_LDS_SHADE_MAX", 32u * 1024u - kShadeListBytes);
@@ -1091,10 +1179,14 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // round 5).  RT_WF_FUSE=0: the unfused pipeline (A/B control, reference of the tests); 2: fused wherever the kernel exists,
     // whatever the plan says (tests, A/B).
     const uint32_t fuse_mode = env_u32("RT_WF_FUSE", 1);
-    const bool fusable = (split || prims_only) && !vol && !groups && !tex && !lg && !sparse && lds_prims == 1 && lds_shade == 1 &&
-                         staged_prims <= shade_tables_max && fuse_mode != 0 && (!plan.multi_mesh || fuse_mode == 2);
+    const bool fusable = (su.split || su.prims_only) && !vol && !su.groups && !tex && !lg && !sparse && su.lds_prims == 1 && lds_shade == 1 &&
+                         su.staged_prims <= shade_tables_max && fuse_mode != 0 && (!su.plan.multi_mesh || fuse_mode == 2);
     const bool fuse = fusable && !stats;
-    const size_t shade_tables_lds = lds_shade == 0 ? size_t(0) : (fuse ? size_t(std::max(staged_shade, staged_prims)) : size_t(staged_shade));
+    const size_t shade_tables_lds = lds_shade == 0 ? size_t(0) : (fuse ? size_t(std::max(staged_shade, su.staged_prims)) : size_t(staged_shade));
+    // the shade kernel of each group type (a render uses one of them; all exist in the library anyway)
+    const ShadeKernel<R, WfGroup<R>> shade_dense = pick_shade<R>(stats, lds_shade, tex, fuse);
+    const ShadeKernel<R, WfGroupSparse<R>> shade_sparse = pick_shade_lean<R, WfGroupSparse<R>>(lds_shade, tex);
+    const ShadeKernel<R, WfGroupLG<R>> shade_lg = pick_shade_lean<R, WfGroupLG<R>>(lds_shade, tex);
 
     HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DeviceCounters), stream));
     HIP_TRY(hipEventRecord(s->ev0, stream));
@@ -1144,19 +1236,11 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         int qi = 0;
         bool hits_ready = false;  // the hit records and the mesh queue of the current queue exist already (phase 4 of a fused k_wf_shade)
         uint32_t upper = first;  // upper bound of the queue length (never grows: slots are reused in place)
-#define RT_LAUNCH_PRIMS(ST, L, VL, GR) hipLaunchKernelGGL((k_wf_prims<R, ST, L, VL, GR>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_prims) : size_t(0)) + (GR ? lds_groups : size_t(0)) + (WF_CHUNK + 4) * 4, stream, ds.view, pool, w.queue[qi], w.mesh_queue, w.d_ctr, s->d_counters, staged_prims, group_levels)
-#define RT_LAUNCH_PRIMS_ANY() do { if (vol) { if (stats) RT_LAUNCH_PRIMS(true, 0, true, false); else RT_LAUNCH_PRIMS(false, 0, true, false); } \
-                                   else if (groups) { if (stats) { if (lds_prims == 2) RT_LAUNCH_PRIMS(true, 2, false, true); else if (lds_prims == 1) RT_LAUNCH_PRIMS(true, 1, false, true); else RT_LAUNCH_PRIMS(true, 0, false, true); } \
-                                                      else { if (lds_prims == 2) RT_LAUNCH_PRIMS(false, 2, false, true); else if (lds_prims == 1) RT_LAUNCH_PRIMS(false, 1, false, true); else RT_LAUNCH_PRIMS(false, 0, false, true); } } \
-                                   else if (stats) { if (lds_prims == 1) RT_LAUNCH_PRIMS(true, 1, false, false); else if (lds_prims == 2) RT_LAUNCH_PRIMS(true, 2, false, false); else RT_LAUNCH_PRIMS(true, 0, false, false); } \
-                                   else { if (lds_prims == 1) RT_LAUNCH_PRIMS(false, 1, false, false); else if (lds_prims == 2) RT_LAUNCH_PRIMS(false, 2, false, false); else RT_LAUNCH_PRIMS(false, 0, false, false); } } while (0)
-#define RT_LAUNCH_MESH_M(ST, ND, MU, QUEUE, NPTR, CPTR) hipLaunchKernelGGL((k_wf_mesh<R, ST, ND, MU>), dim3(isect_blocks), dim3(256), lds_mesh, stream, ds.view, pool, QUEUE, w.d_ctr, s->d_counters, refill_min, inner_min, static_cast<uint2*>(w.mesh_spill), lds_levels, NPTR, CPTR, cones_on)
-#define RT_LAUNCH_MESH_V(ST, ND, QUEUE, NPTR, CPTR) do { if (multi_mesh) RT_LAUNCH_MESH_M(ST, ND, true, QUEUE, NPTR, CPTR); else RT_LAUNCH_MESH_M(ST, ND, false, QUEUE, NPTR, CPTR); } while (0)
-#define RT_LAUNCH_MESH(QUEUE, NPTR, CPTR)                                                                                                         \
-    do {                                                                                                                                          \
-        if (stats) { if (node_kind == 1) RT_LAUNCH_MESH_V(true, 1, QUEUE, NPTR, CPTR); else RT_LAUNCH_MESH_V(true, 0, QUEUE, NPTR, CPTR); } \
-        else { if (node_kind == 1) RT_LAUNCH_MESH_V(false, 1, QUEUE, NPTR, CPTR); else RT_LAUNCH_MESH_V(false, 0, QUEUE, NPTR, CPTR); }       \
-    } while (0)
+        auto launch_shade = [&](auto kernel, const auto& g) {
+            hipLaunchKernelGGL(kernel, dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), shade_tables_lds + kShadeListBytes + shade_lds_pad, stream,
+                               ds.view, cv, pv, pool, g, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters,
+                               static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade, w.mesh_queue);
+        };
         for (;;) {
             size_t ev = 0;
             // near the end of the call's last group the host looks after every second iteration, so that the tail is seen when it starts
@@ -1168,48 +1252,23 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
             const uint32_t check_now = (compact_tail && all_started) ? 1u : ((near_end || closing) ? std::min<uint32_t>(check_every, 2u) : check_every);
             for (uint32_t k = 0; k < check_now; k++) {
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                prims_ran[k] = (split || prims_only) && !hits_ready;
-                if (split || prims_only) {
-                    if (!hits_ready) { RT_LAUNCH_PRIMS_ANY(); search_launches++; }
+                const SearchQueues sq{w.queue[qi], w.mesh_queue, w.mesh_spill, w.d_ctr, s->d_counters, stream};
+                prims_ran[k] = (su.split || su.prims_only) && !hits_ready;
+                if (su.split || su.prims_only) {
+                    if (!hits_ready) { launch_prims(su, ds, pool, sq, upper); search_launches++; }
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                    if (!prims_only) RT_LAUNCH_MESH(w.mesh_queue, &w.d_ctr->n_mesh, &w.d_ctr->cursor);
+                    if (su.split) launch_mesh(su, ds, pool, sq);
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 } else {
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
-#define RT_LAUNCH_ISECT(ST, VL) hipLaunchKernelGGL((k_wf_intersect<R, ST, VL>), dim3(isect_blocks), dim3(256), lds, stream, ds.view, pool, w.queue[qi], w.d_ctr, s->d_counters, refill_min)
-                    if (stats) { if (vol) RT_LAUNCH_ISECT(true, true); else RT_LAUNCH_ISECT(true, false); }
-                    else { if (vol) RT_LAUNCH_ISECT(false, true); else RT_LAUNCH_ISECT(false, false); }
-#undef RT_LAUNCH_ISECT
+                    launch_intersect(su, ds, pool, sq);
                     search_launches++;
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 }
-#define RT_LAUNCH_SHADE_F(ST, L, TX, G, GRP, FU) hipLaunchKernelGGL((k_wf_shade<R, ST, L, TX, G, FU>), dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), shade_tables_lds + kShadeListBytes + shade_lds_pad, stream, ds.view, cv, pv, pool, GRP, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters, static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade, w.mesh_queue)
-#define RT_LAUNCH_SHADE_G(ST, L, TX, G, GRP) RT_LAUNCH_SHADE_F(ST, L, TX, G, GRP, false)
-#define RT_LAUNCH_SHADE(ST, L, TX) RT_LAUNCH_SHADE_G(ST, L, TX, WfGroup<R>, grp)
-#define RT_LAUNCH_SHADE_SPARSE(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupSparse<R>, grp_s)
-#define RT_LAUNCH_SHADE_LG(L, TX) RT_LAUNCH_SHADE_G(false, L, TX, WfGroupLG<R>, grp_lg)
-                if (fuse) {  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
-                    RT_LAUNCH_SHADE_F(false, 1, false, WfGroup<R>, grp, true);
-                    hits_ready = true;
-                } else if (lg) {  // the terminal's light group beside the radiance (no counting variants)
-                    if (tex) RT_LAUNCH_SHADE_LG(0, true);
-                    else if (lds_shade == 1) RT_LAUNCH_SHADE_LG(1, false);
-                    else if (lds_shade == 2) RT_LAUNCH_SHADE_LG(2, false);
-                    else RT_LAUNCH_SHADE_LG(0, false);
-                } else if (sparse) {  // restarts through the active list (no counting variants)
-                    if (tex) RT_LAUNCH_SHADE_SPARSE(0, true);
-                    else if (lds_shade == 1) RT_LAUNCH_SHADE_SPARSE(1, false);
-                    else if (lds_shade == 2) RT_LAUNCH_SHADE_SPARSE(2, false);
-                    else RT_LAUNCH_SHADE_SPARSE(0, false);
-                } else if (tex) {  // interpreter variant: tables from global memory (rare scenes, fewer instantiations)
-                    if (stats) RT_LAUNCH_SHADE(true, 0, true); else RT_LAUNCH_SHADE(false, 0, true);
-                } else if (stats) { if (lds_shade == 1) RT_LAUNCH_SHADE(true, 1, false); else if (lds_shade == 2) RT_LAUNCH_SHADE(true, 2, false); else RT_LAUNCH_SHADE(true, 0, false); }
-                else { if (lds_shade == 1) RT_LAUNCH_SHADE(false, 1, false); else if (lds_shade == 2) RT_LAUNCH_SHADE(false, 2, false); else RT_LAUNCH_SHADE(false, 0, false); }
-#undef RT_LAUNCH_SHADE_LG
-#undef RT_LAUNCH_SHADE_SPARSE
-#undef RT_LAUNCH_SHADE
-#undef RT_LAUNCH_SHADE_G
-#undef RT_LAUNCH_SHADE_F
+                if (lg) launch_shade(shade_lg, grp_lg);
+                else if (sparse) launch_shade(shade_sparse, grp_s);
+                else launch_shade(shade_dense, grp);
+                if (fuse) hits_ready = true;  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
                 hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr);
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 qi ^= 1;
@@ -1223,7 +1282,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                 for (int ph = 0; ph < 3; ph++) {
                     it_ms[ph] = 0.f;
                     HIP_TRY(hipEventElapsedTime(&it_ms[ph], w.events[e + ph], w.events[e + ph + 1]));
-                    if (ph == 0 && (split || prims_only) && !prims_ran[e / 4]) it_ms[ph] = 0.f;  // no launch between the two events
+                    if (ph == 0 && (su.split || su.prims_only) && !prims_ran[e / 4]) it_ms[ph] = 0.f;  // no launch between the two events
                     phase_ms[ph] += it_ms[ph];
                 }
                 if (iter_log)  // RT_WF_ITER_LOG=1 (with RT_WF_CHECK=1 the queue length printed is the one of this very iteration)
@@ -1272,11 +1331,6 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                 }
             }
         }
-#undef RT_LAUNCH_PRIMS_ANY
-#undef RT_LAUNCH_PRIMS
-#undef RT_LAUNCH_MESH
-#undef RT_LAUNCH_MESH_V
-#undef RT_LAUNCH_MESH_M
         if (ad) {
             const dim3 rgrid(uint32_t((npix + 255) / 256));
             if (sparse) hipLaunchKernelGGL(k_wf_resolve_moments<true>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
@@ -1320,8 +1374,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     RtRenderStats& st = s->stats;
     st = RtRenderStats{};
     st.kernel_ms = ms;
-    st.traversal_kernel_ms = prims_only ? 0.0 : phase_ms[1];
-    st.prims_kernel_ms = (split || prims_only) ? phase_ms[0] : 0.0;
+    st.traversal_kernel_ms = su.prims_only ? 0.0 : phase_ms[1];
+    st.prims_kernel_ms = (su.split || su.prims_only) ? phase_ms[0] : 0.0;
     st.shade_kernel_ms = phase_ms[2];
     st.n_launches = search_launches;
     st.n_iterations = isect_launches;
@@ -1330,7 +1384,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     if (lg && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
         std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", lg->n_groups, resolve_ms,
                      w.sample_G_bytes, w.acc_g_bytes);
-    if (stats && split && env_u32("RT_WF_DEBUG", 0)) {
+    if (stats && su.split && env_u32("RT_WF_DEBUG", 0)) {
         auto pct = [](unsigned long long lanes, unsigned long long waves) { return waves ? 100.0 * double(lanes) / (64.0 * double(waves)) : 0.0; };
         std::fprintf(stderr,
                      "[k_wf_mesh] rays %llu  node code: %llu wave iterations, %.1f %% lanes active;  triangle code: %llu, %.1f %%;  "
@@ -1345,7 +1399,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     st.node_visits = hc.node_visits;
     st.tri_tests = hc.tri_tests;
     st.prim_tests = hc.prim_tests;
-    st.bytes_node = split ? (node_kind == 0 ? sizeof(BvhNode4f) : sizeof(BvhNode4q)) : sizeof(BvhNode<R>);
+    st.bytes_node = su.split ? (su.node_kind == 0 ? sizeof(BvhNode4f) : sizeof(BvhNode4q)) : sizeof(BvhNode<R>);
     st.bytes_tri = sizeof(TriRec<R>);
     st.bytes_attr = sizeof(TriAttr<R>);
     // path state moved by the DOMINANT kernel per ray it traverses: ray (6 R) + bound/op read (R + 4)
@@ -1358,7 +1412,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // the lean renders of this scene run the search inside k_wf_shade: its bytes per ray are then the kernel's (a counting
     // render is never fused, but it reports what the timed renders beside it move)
     if (fusable) st.bytes_state_shade += st.bytes_state_prims;
-    if (!split) st.mesh_rays = hc.rays;  // combined kernel: every ray's state passes through it
+    if (!su.split) st.mesh_rays = hc.rays;  // combined kernel: every ray's state passes through it
     return RT_OK;
 }
 
@@ -1450,103 +1504,37 @@ static int rq_tables(RtScene* s, hipStream_t stream) {
     return RT_OK;
 }
 
-static int rq_staging(RtScene::Query& q, size_t bytes) {
-    if (q.staging_bytes >= bytes) return RT_OK;
-    if (q.staging) (void)hipFree(q.staging);
-    q.staging = nullptr;
-    q.staging_bytes = 0;
-    HIP_TRY(hipMalloc(&q.staging, bytes));
-    q.staging_bytes = bytes;
-    return RT_OK;
-}
-
-// One pass of the scene's search kernels over slots 0 .. m-1 of the query pool: the kernels render_wavefront launches at
-// the head of an iteration for a lean (no counters), volume-free render, chosen by the same plan and the same switches
-// (RT_WF_SPLIT / _GROUPS / _NODES / _MESH_MULTI / _CONES, RT_LDS_*), with the query workspace's queues and counters.
+// One pass of the scene's search kernels over slots 0 .. m-1 of the query pool: what render_wavefront launches at the head
+// of an iteration of a lean (no counters), volume-free render, from the same make_search_setup and through the same launch
+// helpers, with the query workspace's queues, counters and spill buffer.
 template <typename R>
 int query_search_pass(RtScene* s, DeviceScene<R>& ds, const WfPool<R>& pool, uint32_t m, hipStream_t stream) {
     RtScene::Query& q = s->rq;
-    const size_t lds = size_t(ds.view.stack_entries) * 256 * sizeof(int);
-    if (lds > 160 * 1024) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the LDS traversal stack");
-    int n_cu = 0, blocks_per_cu = 0;
-    HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, s->device));
-    const WavefrontPlan plan = plan_wavefront(s->compiled);
-    const int n_mesh_ops = int(s->compiled.mesh_ops.size());
-    const bool use_split = env_u32("RT_WF_SPLIT", 1) != 0 && plan.split;
-    const bool prims_only = use_split && n_mesh_ops == 0;
-    const bool split = use_split && n_mesh_ops > 0;
-    const bool multi_mesh = plan.multi_mesh || env_u32("RT_WF_MESH_MULTI", 0) != 0;
-    const int node_kind = env_u32("RT_WF_NODES", 1) != 0 ? 1 : 0;
-    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
-    const int mesh_levels = int(s->compiled.max_bvh4_stack) + 1;
-    const int lds_levels = std::min<int>(mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
-    const size_t lds_mesh = size_t(lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
-    if (split) {
-        if (node_kind == 1) {
-            if (multi_mesh) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 1, true>, 256, lds_mesh));
-            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 1, false>, 256, lds_mesh));
-        } else {
-            if (multi_mesh) HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 0, true>, 256, lds_mesh));
-            else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_mesh<R, false, 0, false>, 256, lds_mesh));
-        }
-        blocks_per_cu = std::min<int>(std::max(blocks_per_cu, 1), int(env_u32("RT_WF_MESH_BLOCKS", 64)));
-    } else {
-        HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu, k_wf_intersect<R, false, false>, 256, lds));
-    }
-    if (blocks_per_cu < 1) blocks_per_cu = 1;
-    const uint32_t isect_blocks = uint32_t(n_cu) * uint32_t(blocks_per_cu);
-    if (split) {
-        const size_t need = size_t(std::max(mesh_levels - lds_levels, 1)) * isect_blocks * 256 * sizeof(uint2);
-        if (need > q.mesh_spill_bytes) {
-            if (q.mesh_spill) (void)hipFree(q.mesh_spill);
-            q.mesh_spill = nullptr;
-            q.mesh_spill_bytes = 0;
-            HIP_TRY(hipMalloc(&q.mesh_spill, need));
-            q.mesh_spill_bytes = need;
-        }
-    }
-    const uint32_t refill_min = env_u32("RT_WF_REFILL", 32);
-    const uint32_t inner_min = env_u32("RT_WF_INNER_MIN", 16);
-    const bool lds_tables = env_u32("RT_LDS_TABLES", 1) != 0;
-    const uint32_t lds_budget = env_u32("RT_LDS_BUDGET", 32u * 1024u);
-    uint32_t staged_prims = 0;  // the longest prefix of whole tables that fits the budget, as render_wavefront stages it
-    if (lds_tables) {
-        const SmallLayout& L = ds.view.lay;
-        if (L.total_bytes <= lds_budget) staged_prims = L.total_bytes;
-        else {
-            uint32_t best = 0;
-            for (int k = 0; k < ST_COUNT; k++)
-                if (L.end[k] <= lds_budget && L.end[k] > best) best = L.end[k];
-            staged_prims = (best + 15u) & ~15u;
-        }
-    }
-    const uint32_t group_levels = uint32_t(ds.view.group_stack_levels);
-    const size_t group_node_bytes = size_t(ds.view.n_group_nodes) * sizeof(BvhNode4q);
-    const bool groups = (split || prims_only) && plan.groups && env_u32("RT_WF_GROUPS", 1) != 0;
-    const size_t lds_groups = groups ? size_t(group_levels) * 256 * 8 + group_node_bytes : 0;
-    if (groups && lds_groups + staged_prims > 44u * 1024u) staged_prims = 0;
-    const int lds_prims = staged_prims == 0 ? 0 : (staged_prims == ds.view.lay.total_bytes ? 1 : 2);
-
+    SearchSetup<R> su;
+    if (int st = make_search_setup<R>(s, ds, false, false, &su)) return st;
+    if (int st = grow_buffer(q.mesh_spill, q.mesh_spill_bytes, su.spill_bytes)) return st;
     WfCounters init{};
     init.n_in = m;
     *q.h_ctr = init;
     HIP_TRY(hipMemcpyAsync(q.d_ctr, q.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-    if (split || prims_only) {
-#define RT_RQ_PRIMS(L, GR) hipLaunchKernelGGL((k_wf_prims<R, false, L, false, GR>), dim3((m + WF_CHUNK - 1) / WF_CHUNK), dim3(256), (L ? size_t(staged_prims) : size_t(0)) + (GR ? lds_groups : size_t(0)) + (WF_CHUNK + 4) * 4, stream, ds.view, pool, q.queue, q.mesh_queue, q.d_ctr, s->d_counters, staged_prims, group_levels)
-        if (groups) { if (lds_prims == 2) RT_RQ_PRIMS(2, true); else if (lds_prims == 1) RT_RQ_PRIMS(1, true); else RT_RQ_PRIMS(0, true); }
-        else { if (lds_prims == 1) RT_RQ_PRIMS(1, false); else if (lds_prims == 2) RT_RQ_PRIMS(2, false); else RT_RQ_PRIMS(0, false); }
-#undef RT_RQ_PRIMS
-        if (!prims_only) {
-#define RT_RQ_MESH(ND, MU) hipLaunchKernelGGL((k_wf_mesh<R, false, ND, MU>), dim3(isect_blocks), dim3(256), lds_mesh, stream, ds.view, pool, q.mesh_queue, q.d_ctr, s->d_counters, refill_min, inner_min, static_cast<uint2*>(q.mesh_spill), lds_levels, &q.d_ctr->n_mesh, &q.d_ctr->cursor, cones_on)
-            if (node_kind == 1) { if (multi_mesh) RT_RQ_MESH(1, true); else RT_RQ_MESH(1, false); }
-            else { if (multi_mesh) RT_RQ_MESH(0, true); else RT_RQ_MESH(0, false); }
-#undef RT_RQ_MESH
-        }
+    const SearchQueues sq{q.queue, q.mesh_queue, q.mesh_spill, q.d_ctr, s->d_counters, stream};
+    if (su.split || su.prims_only) {
+        launch_prims(su, ds, pool, sq, m);
+        if (su.split) launch_mesh(su, ds, pool, sq);
     } else {
-        hipLaunchKernelGGL((k_wf_intersect<R, false, false>), dim3(isect_blocks), dim3(256), lds, stream, ds.view, pool, q.queue, q.d_ctr, s->d_counters, refill_min);
+        launch_intersect(su, ds, pool, sq);
     }
     HIP_TRY(hipGetLastError());
     return RT_OK;
+}
+
+template <typename R>
+static void rq_record_stats(RtScene::Query& q, double kernel_ms, uint64_t n, uint32_t n_chunks) {
+    q.stats = RtRayQueryStats{};
+    q.stats.kernel_ms = kernel_ms;
+    q.stats.rays = n;
+    q.stats.n_chunks = n_chunks;
+    q.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
 }
 
 // n rays in chunks: (host variant: through the staging buffer) k_rq_load -> search pass -> k_rq_resolve.
@@ -1559,7 +1547,7 @@ int trace_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* o
     if (int st = rq_ensure<R>(s, cap, true)) return st;
     if (int st = rq_tables(s, stream)) return st;
     if (host)
-        if (int st = rq_staging(q, size_t(cap) * (48 + sizeof(RtRayHit)))) return st;
+        if (int st = grow_buffer(q.staging, q.staging_bytes, size_t(cap) * (48 + sizeof(RtRayHit)))) return st;
     const WfPool<R> full = *static_cast<WfPool<R>*>(q.pool_view);
     const RqPool<R> rp{full.ox, full.oy, full.oz, full.dx, full.dy, full.dz, full.ht, full.hu, full.hv, full.hpc, full.htri};
     const RqTables tb{q.op_node, q.tri_order};
@@ -1592,11 +1580,7 @@ int trace_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* o
         total_ms += ms;
         n_chunks++;
     }
-    q.stats = RtRayQueryStats{};
-    q.stats.kernel_ms = total_ms;
-    q.stats.rays = n;
-    q.stats.n_chunks = n_chunks;
-    q.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+    rq_record_stats<R>(q, total_ms, n, n_chunks);
     return RT_OK;
 }
 
@@ -1611,7 +1595,7 @@ int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* ori
     const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
     if (int st = rq_ensure<R>(s, cap, false)) return st;
     if (host)
-        if (int st = rq_staging(q, size_t(cap) * (48 + 16 + 1))) return st;
+        if (int st = grow_buffer(q.staging, q.staging_bytes, size_t(cap) * (48 + 16 + 1))) return st;
     double total_ms = 0.0;
     uint32_t n_chunks = 0;
     for (uint64_t off = 0; off < n; off += chunk) {
@@ -1642,11 +1626,7 @@ int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* ori
         total_ms += ms;
         n_chunks++;
     }
-    q.stats = RtRayQueryStats{};
-    q.stats.kernel_ms = total_ms;
-    q.stats.rays = n;
-    q.stats.n_chunks = n_chunks;
-    q.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+    rq_record_stats<R>(q, total_ms, n, n_chunks);
     return RT_OK;
 }
 
@@ -1954,6 +1934,13 @@ static int refit_typed(RtScene* s, const CompiledScene& cs, const std::vector<ui
     }
     return RT_OK;
 }
+
+// The scene compiler's switches (every entry point that compiles a description reads them the same way).
+static CompileOptions compile_options_from_env() {
+    CompileOptions opt;
+    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // A/B, tests
+    return opt;
+}
 }  // namespace rt
 
 // An accumulator belongs to the scene as it was when the accumulator was created.
@@ -1977,12 +1964,11 @@ int rt_scene_create(const RtSceneDesc* desc, int device, RtScene** out) {
     std::unique_ptr<RtScene> s(new (std::nothrow) RtScene);
     if (!s) return set_err(RT_E_NOMEM, "out of memory");
     std::string err;
-    CompileOptions opt;
+    CompileOptions opt = compile_options_from_env();
     const char* builder = std::getenv("RT_BVH_BUILDER");  // "device" / "host" override the scene's flag
     opt.bvh_on_device = desc && (desc->flags & RT_SCENE_BVH_ON_DEVICE) != 0;
     if (builder && !std::strcmp(builder, "device")) opt.bvh_on_device = true;
     if (builder && !std::strcmp(builder, "host")) opt.bvh_on_device = false;
-    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // A/B, tests
     int n = 0;
     if (opt.bvh_on_device) {  // the device builder needs its device before the scene is compiled
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_err(RT_E_DEVICE, "no HIP device available");
@@ -2208,8 +2194,7 @@ int rt_scene_update(RtScene* s, const RtSceneDesc* desc, RtSceneUpdateInfo* info
             if (!(std::fabs(m.positions[k]) <= 1e37))  // also NaN
                 return set_err(RT_E_UNSUPPORTED, "scene update: meshes[" + std::to_string(i) + "].positions: coordinates beyond the f32 grid");
     }
-    CompileOptions opt;
-    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // as rt_scene_create
+    CompileOptions opt = compile_options_from_env();  // as rt_scene_create
     opt.reuse = &s->compiled;
     opt.mesh_changed = &changed;
     CompiledScene cs;
@@ -2386,8 +2371,7 @@ int rt_scene_mesh_stats(const RtSceneDesc* desc, uint64_t out[8]) {
     if (!desc || !out) return set_err(RT_E_INVALID, "rt_scene_mesh_stats: NULL argument");
     CompiledScene cs;
     std::string err;
-    CompileOptions opt;
-    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;
+    const CompileOptions opt = compile_options_from_env();
     int st = compile_scene(desc, &cs, &err, opt);
     if (st != RT_OK) return set_err(st, err);
     out[0] = cs.tris.size();
@@ -2447,8 +2431,7 @@ int rt_scene_program(const RtSceneDesc* desc, int32_t* ops_out, uint32_t capacit
     if (!desc || !n_ops_out || !info) return set_err(RT_E_INVALID, "rt_scene_program: NULL argument");
     CompiledScene cs;
     std::string err;
-    CompileOptions opt;
-    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;
+    const CompileOptions opt = compile_options_from_env();
     int st = compile_scene(desc, &cs, &err, opt);
     if (st != RT_OK) return set_err(st, err);
     *n_ops_out = uint32_t(cs.ops.size());
@@ -3267,8 +3250,7 @@ int rt_scene_op_nodes(const RtSceneDesc* desc, int32_t* nodes_out, uint32_t capa
     if (!desc || !n_ops_out) return set_err(RT_E_INVALID, "rt_scene_op_nodes: NULL argument");
     CompiledScene cs;
     std::string err;
-    CompileOptions opt;
-    if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // as rt_scene_program
+    const CompileOptions opt = compile_options_from_env();
     int st = compile_scene(desc, &cs, &err, opt);
     if (st != RT_OK) return set_err(st, err);
     *n_ops_out = uint32_t(cs.op_node.size());

@@ -55,14 +55,20 @@ def oracle_hits(desc, origins, dirs, t_min=T_MIN, t_max=float("inf")):
     return out
 
 
+def camera_rays(hs):
+    """Ray set (a): origins and directions, (n, 3) each."""
+    cam, prm = hs.camera, hs.params
+    rays = np.array([pyoracle.get_ray(cam, prm, 0, x, y, 0, 0) for y in range(cam.image_height) for x in range(cam.image_width)])
+    return np.ascontiguousarray(rays[:, :3]), np.ascontiguousarray(rays[:, 3:])
+
+
 class Cases:
     """The three ray sets of a scene with the oracle's answers."""
 
     def __init__(self, hs):
         self.hs = hs
         cam, prm = hs.camera, hs.params
-        rays = np.array([pyoracle.get_ray(cam, prm, 0, x, y, 0, 0) for y in range(cam.image_height) for x in range(cam.image_width)])
-        self.cam_o, self.cam_d = np.ascontiguousarray(rays[:, :3]), np.ascontiguousarray(rays[:, 3:])
+        self.cam_o, self.cam_d = camera_rays(hs)
         self.cam_hits = oracle_hits(hs.desc, self.cam_o, self.cam_d)
         rng = np.random.default_rng(31)
         P = self.cam_hits["pos"][self.cam_hits["klass"] == SURFACE]
