@@ -347,6 +347,14 @@ int rt_scene_mesh_stats(const RtSceneDesc* desc, uint64_t out[8]);
  * output arrays may be NULL. */
 int rt_scene_mesh_cones(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out,
                         uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out, uint32_t tri_capacity, uint32_t* n_tris_out);
+/* The hand-out policy of the persistent search kernels (csrc/rt_handout.h), replayed on the host (tests without a GPU): `waves`
+ * waves share a queue of `n` entries and ask for ranges in the order `order` (wave indices; walked round and round, every
+ * wave must appear) until each has been told that the queue is exhausted and has asked once more after that.  policy = {mode,
+ * left256, left128} or NULL for the default.  asks_out[3 i ..] = wave, first entry, end of the range handed out at ask i
+ * (both 0xFFFFFFFF: "exhausted"); up to `capacity` asks are written, *n_asks_out = their number.  atomics_out[0] = atomics on the
+ * cursor that the kernel makes, atomics_out[1] = those of the asks after "exhausted" (the kernel makes none). */
+int rt_debug_handout_replay(const uint32_t* policy, uint32_t n, uint32_t waves, const uint32_t* order, uint32_t n_order, uint32_t* asks_out,
+                            uint32_t capacity, uint32_t* n_asks_out, uint32_t* atomics_out);
 /* Same, plus the compiled scene program itself (tests of the scene compiler without a GPU): ops_out[4 * i ..] = type, arg,
  * skip, chain of op i (rt_scene.h OpType; up to `capacity` ops are written, *n_ops_out = the program's length; ops_out may be
  * NULL).  info[0] mesh ops, [1] primitive groups with a 4-wide BVH, [2] their nodes, [3] their worst-case stack, [4] entries of

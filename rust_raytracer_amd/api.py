@@ -302,6 +302,10 @@ def load_device_lib() -> C.CDLL:
             lib.rt_scene_mesh_cones.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
             lib.rt_scene_mesh_cones.restype = C.c_int
+        if hasattr(lib, "rt_debug_handout_replay"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_debug_handout_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                    C.POINTER(C.c_uint32), C.c_void_p]
+            lib.rt_debug_handout_replay.restype = C.c_int
         if hasattr(lib, "rt_accum_create"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             for name, res, args in (
                     ("rt_accum_create", C.c_int, [C.c_void_p, C.POINTER(RtCameraDesc), C.POINTER(RtRenderParams), C.POINTER(C.c_void_p)]),
@@ -410,6 +414,27 @@ def scene_mesh_stats(desc) -> dict:
         raise RtError(st, lib.rt_last_error().decode())
     return dict(zip(("triangles", "bvh2_nodes", "bvh4_nodes", "bvh2_depth", "bvh4_stack", "ops", "rebuilt_groups", "rebuilt_prims"),
                     [int(x) for x in out]))
+
+
+def handout_replay(n: int, waves: int, order, policy=None, out=None) -> tuple:
+    """rt_debug_handout_replay: the ranges the persistent search kernels' hand-out policy gives `waves` waves that ask in `order`
+    (walked round and round) for a queue of n entries -> (asks (k, 3) uint32: wave, first, end; 0xFFFFFFFF twice = "exhausted",
+    atomics of the kernel, atomics of the asks after "exhausted").  `out`: a (cap, 3) uint32 array to reuse."""
+    lib = load_device_lib()
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    pol = None if policy is None else np.asarray(policy, dtype=np.uint32)
+    cap = n // 64 + 4 * waves + 16
+    if out is None or out.shape[0] < cap:
+        out = np.empty((cap, 3), dtype=np.uint32)
+    n_asks = C.c_uint32(0)
+    atomics = np.zeros(2, dtype=np.uint32)
+    st = lib.rt_debug_handout_replay(None if pol is None else pol.ctypes.data, n, waves, order.ctypes.data, order.size, out.ctypes.data,
+                                     out.shape[0], C.byref(n_asks), atomics.ctypes.data)
+    if st != 0:
+        raise RuntimeError(f"rt_debug_handout_replay: {lib.rt_last_error().decode()}")
+    if n_asks.value > out.shape[0]:
+        raise RuntimeError(f"rt_debug_handout_replay: {n_asks.value} asks for n = {n}, {waves} waves")
+    return out[:n_asks.value], int(atomics[0]), int(atomics[1])
 
 
 def scene_mesh_cones(desc, mesh: int = 0, f32: bool = False) -> tuple:

@@ -864,6 +864,7 @@ struct SearchSetup {
     uint32_t cones_on;
     int mesh_levels, lds_levels;        // k_wf_mesh's stack: levels in all / in LDS (the rest in the workspace's spill buffer)
     uint32_t refill_min, inner_min;
+    HandoutPolicy handout;              // how the persistent kernels' waves share their queue (rt_handout.h)
     bool lds_tables;                    // RT_LDS_TABLES / RT_LDS_BUDGET, for staged_prefix of the shade kernel's layout too
     uint32_t lds_budget;
     bool groups;
@@ -873,6 +874,7 @@ struct SearchSetup {
     int lds_prims;                      // kernel variant: none / all / prefix
     size_t lds_isect, lds_mesh, lds_prims_launch;  // dynamic LDS of each launch
     uint32_t isect_blocks;              // persistent grid of k_wf_mesh / k_wf_intersect
+    int blocks_per_cu;                  // ... what the occupancy query gave for it
     size_t spill_bytes;                 // what the workspace's mesh_spill must hold (0: no k_wf_mesh)
     IntersectKernel<R> k_intersect;
     PrimsKernel<R> k_prims;
@@ -915,7 +917,12 @@ int make_search_setup(RtScene* s, DeviceScene<R>& ds, bool stats, bool vol, Sear
     su.lds_levels = std::min<int>(su.mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
     su.lds_mesh = size_t(su.lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
     su.refill_min = env_u32("RT_WF_REFILL", 32);  // measured optimum (64 = no refill: -20 %)
-    su.inner_min = env_u32("RT_WF_INNER_MIN", 16);
+    su.inner_min = env_u32("RT_WF_INNER_MIN", 24);  // 16 / 24 / 32: 982 / 973 / 1013 ms on the headline, 766 / 758 / 784 in f32 (profiles/mesh_handout/sweep_inner_min.txt)
+    // RT_WF_HANDOUT: 0 = 256 entries per atomic from the first on (A/B control, the same code object), 1 = static first range +
+    // shrinking ranges, 2 = 1 + queue entries staged in LDS by k_wf_mesh.  RT_WF_HANDOUT_256 / _128: the policy's thresholds (sweeps).
+    su.handout.mode = std::min<uint32_t>(env_u32("RT_WF_HANDOUT", 2), 2u);
+    su.handout.left256 = env_u32("RT_WF_HANDOUT_256", kHandoutLeft256);
+    su.handout.left128 = std::min<uint32_t>(env_u32("RT_WF_HANDOUT_128", kHandoutLeft128), su.handout.left256);
     su.lds_tables = env_u32("RT_LDS_TABLES", 1) != 0;
     su.lds_budget = env_u32("RT_LDS_BUDGET", 32u * 1024u);
     // re-built primitive groups as 4-wide BVHs inside k_wf_prims (OP_GROUP): nodes + a per-lane stack in LDS; scenes whose
@@ -940,6 +947,8 @@ int make_search_setup(RtScene* s, DeviceScene<R>& ds, bool stats, bool vol, Sear
     if (blocks_per_cu < 1) blocks_per_cu = 1;
     if (su.split) blocks_per_cu = std::min<int>(blocks_per_cu, int(env_u32("RT_WF_MESH_BLOCKS", 64)));  // experiments: occupancy scaling
     su.isect_blocks = uint32_t(n_cu) * uint32_t(blocks_per_cu);
+    su.blocks_per_cu = blocks_per_cu;
+    if (const uint32_t grid = env_u32("RT_WF_MESH_GRID", 0)) su.isect_blocks = std::min<uint32_t>(grid, 16384u);  // tests, A/B: the persistent grid outright
     su.spill_bytes = su.split ? size_t(std::max(su.mesh_levels - su.lds_levels, 1)) * su.isect_blocks * 256 * sizeof(uint2) : size_t(0);
     return RT_OK;
 }
@@ -962,12 +971,12 @@ void launch_prims(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPo
 template <typename R>
 void launch_mesh(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq) {
     hipLaunchKernelGGL(su.k_mesh, dim3(su.isect_blocks), dim3(256), su.lds_mesh, sq.stream, ds.view, pool, sq.mesh_queue, sq.ctr, sq.counters,
-                       su.refill_min, su.inner_min, static_cast<uint2*>(sq.mesh_spill), su.lds_levels, &sq.ctr->n_mesh, &sq.ctr->cursor, su.cones_on);
+                       su.refill_min, su.inner_min, static_cast<uint2*>(sq.mesh_spill), su.lds_levels, &sq.ctr->n_mesh, &sq.ctr->cursor, su.cones_on, su.handout.mode, su.handout.left256, su.handout.left128);
 }
 template <typename R>
 void launch_intersect(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq) {
     hipLaunchKernelGGL(su.k_intersect, dim3(su.isect_blocks), dim3(256), su.lds_isect, sq.stream, ds.view, pool, sq.queue, sq.ctr, sq.counters,
-                       su.refill_min);
+                       su.refill_min, su.handout.mode, su.handout.left256, su.handout.left128);
 }
 
 // Releases the path pool and its queues and marks the pool as absent, so that a failed re-allocation can never be
@@ -1385,6 +1394,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", lg->n_groups, resolve_ms,
                      w.sample_G_bytes, w.acc_g_bytes);
     if (stats && su.split && env_u32("RT_WF_DEBUG", 0)) {
+        std::fprintf(stderr, "[k_wf_mesh] grid %u workgroups, %d per CU, %zu B of LDS each; hand-out mode %u, 256 / 128 entries above %u / %u left per wave\n",
+                     su.isect_blocks, su.blocks_per_cu, su.lds_mesh, su.handout.mode, su.handout.left256, su.handout.left128);
         auto pct = [](unsigned long long lanes, unsigned long long waves) { return waves ? 100.0 * double(lanes) / (64.0 * double(waves)) : 0.0; };
         std::fprintf(stderr,
                      "[k_wf_mesh] rays %llu  node code: %llu wave iterations, %.1f %% lanes active;  triangle code: %llu, %.1f %%;  "
@@ -2382,6 +2393,52 @@ int rt_scene_mesh_stats(const RtSceneDesc* desc, uint64_t out[8]) {
     out[5] = cs.ops.size();
     out[6] = cs.n_rebuilt_groups;
     out[7] = cs.n_rebuilt_prims;
+    return RT_OK;
+}
+
+int rt_debug_handout_replay(const uint32_t* policy, uint32_t n, uint32_t waves, const uint32_t* order, uint32_t n_order, uint32_t* asks_out,
+                            uint32_t capacity, uint32_t* n_asks_out, uint32_t* atomics_out) {
+    using namespace rt;
+    if (!order || !n_asks_out || !atomics_out || (!asks_out && capacity)) return set_err(RT_E_INVALID, "rt_debug_handout_replay: NULL argument");
+    if (waves == 0u || waves > 65536u || n_order == 0u) return set_err(RT_E_INVALID, "rt_debug_handout_replay: 1..65536 waves and a non-empty order");
+    std::vector<uint8_t> seen(waves, 0);
+    for (uint32_t i = 0; i < n_order; i++) {
+        if (order[i] >= waves) return set_err(RT_E_INVALID, "rt_debug_handout_replay: wave index out of range");
+        seen[order[i]] = 1;
+    }
+    for (uint32_t g = 0; g < waves; g++)
+        if (!seen[g]) return set_err(RT_E_INVALID, "rt_debug_handout_replay: every wave must appear in the order");
+    HandoutPolicy hp{2u, kHandoutLeft256, kHandoutLeft128};
+    if (policy) hp = HandoutPolicy{policy[0], policy[1], policy[2]};
+    // per wave what WaveRange keeps; state 0: before the static range, 1: serving, 2: told "exhausted", 3: ... and asked once more
+    struct Wave { uint32_t end = 0; uint8_t state = 0; };
+    std::vector<Wave> ws(waves);
+    const uint32_t s0 = handout_first(hp, n, waves), start = waves * s0;
+    uint32_t cursor = 0, n_asks = 0, open = waves;
+    atomics_out[0] = atomics_out[1] = 0;
+    auto record = [&](uint32_t g, uint32_t base, uint32_t end) {
+        if (n_asks < capacity) { asks_out[3 * size_t(n_asks)] = g; asks_out[3 * size_t(n_asks) + 1] = base; asks_out[3 * size_t(n_asks) + 2] = end; }
+        n_asks++;
+    };
+    for (uint32_t i = 0; open != 0u; i = (i + 1u) % n_order) {
+        const uint32_t g = order[i];
+        Wave& w = ws[g];
+        if (w.state == 3) continue;
+        if (w.state == 0) {  // WaveRange::start; an empty static range sends the first fetch on to the cursor, as in wave_fetch
+            uint32_t cur = 0;
+            handout_static(n, s0, g, &cur, &w.end);
+            w.state = 1;
+            if (cur < w.end) { record(g, cur, w.end); continue; }
+        }
+        uint32_t base = 0, end = 0;
+        uint32_t& atomics = atomics_out[w.state == 2 ? 1 : 0];
+        const bool got = handout_next(hp, n, waves, start, w.end, [&](uint32_t size) { atomics++; const uint32_t old = cursor; cursor += size; return old; }, &base, &end);
+        if (got) { w.end = end; record(g, base, end); }
+        else record(g, 0xFFFFFFFFu, 0xFFFFFFFFu);
+        if (w.state == 2) { w.state = 3; open--; }
+        else if (!got) w.state = 2;
+    }
+    *n_asks_out = n_asks;
     return RT_OK;
 }
 

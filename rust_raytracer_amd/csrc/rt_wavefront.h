@@ -19,6 +19,7 @@
 // depend on scheduling: bit-identical between runs, partitions and pipelines.
 #pragma once
 #include "rt_device.h"
+#include "rt_handout.h"
 
 // Minimum waves per SIMD requested from the register allocator (second __launch_bounds__
 // argument); tuned on MI355X, see DESIGN.md.
@@ -200,31 +201,85 @@ template <typename T> RT_DEV void lds_append(bool pred, T value, T* list, uint32
     }
 }
 
-// Wave-level queue reader of the persistent kernels: hands out entries [cur, end) of a reserved batch.
+// Wave-level queue reader of the persistent kernels: hands out entries [cur, end) of a reserved range; which ranges a wave
+// gets is the policy of rt_handout.h.  Every member is wave-uniform (SGPRs).
 struct WaveRange {
     uint32_t cur = 0, end = 0;
+    bool staged = false;  // k_wf_mesh, staged hand-out: the entries of [.., end) stand in the wave's LDS area
+    // where the cursor's entries begin: W * s0 (recomputed per reservation: an SGPR less for the whole kernel)
+    static RT_DEV uint32_t cursor_start(HandoutPolicy hp, uint32_t n) {
+        const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+        return waves * handout_first(hp, n, waves);
+    }
+    // wave g of gridDim.x * 4 starts on its static range (empty with hp.mode == 0: the first fetch goes to the cursor)
+    RT_DEV void init(HandoutPolicy hp, uint32_t n) {
+        const uint32_t waves = gridDim.x * (blockDim.x >> 6);
+        handout_static(n, handout_first(hp, n, waves), uint32_t(__builtin_amdgcn_readfirstlane(int(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)))), &cur, &end);
+    }
+    // the range is used up: the next one, or false = the queue has been handed out
+    RT_DEV bool next(HandoutPolicy hp, unsigned long long idle, uint32_t* cursor, uint32_t n) {
+        const int leader = __ffsll((long long)idle) - 1;
+        uint32_t base = 0, e = 0;
+        const bool got = handout_next(hp, n, gridDim.x * (blockDim.x >> 6), cursor_start(hp, n), end, [&](uint32_t size) {
+            uint32_t old = 0;
+            if (int(threadIdx.x & 63u) == leader) old = atomicAdd(cursor, size);
+            return uint32_t(__builtin_amdgcn_readfirstlane(int(__shfl(old, leader))));
+        }, &base, &e);
+        if (got) { cur = base; end = e; }
+        return got;
+    }
 };
 // Gives every idle lane (bit set in `idle`) a queue index if one is available; returns true in
 // `take` lanes.  Sets `exhausted` when the queue has been handed out completely.
-RT_DEV bool wave_fetch(WaveRange& r, unsigned long long idle, uint32_t* cursor, uint32_t n, bool& exhausted, uint32_t& my) {
+RT_DEV bool wave_fetch(WaveRange& r, unsigned long long idle, uint32_t* cursor, uint32_t n, HandoutPolicy hp, bool& exhausted, uint32_t& my) {
     const uint32_t lane = threadIdx.x & 63u;
-    if (r.cur >= r.end) {
-        uint32_t base = 0;
-        int leader = __ffsll((long long)idle) - 1;
-        if (int(lane) == leader) base = atomicAdd(cursor, WF_BATCH);
-        base = __shfl(base, leader);
-        if (base >= n) {
-            exhausted = true;
-            return false;
-        }
-        r.cur = base;
-        r.end = min(base + WF_BATCH, n);
+    if (r.cur >= r.end && !r.next(hp, idle, cursor, n)) {
+        exhausted = true;
+        return false;
     }
     uint32_t avail = r.end - r.cur;
     uint32_t rank = lane_prefix(idle);
     bool take = ((idle >> lane) & 1ull) && rank < avail;
     my = r.cur + rank;
     uint32_t n_idle = uint32_t(__popcll(idle));
+    r.cur += n_idle < avail ? n_idle : avail;
+    return take;
+}
+// k_wf_mesh: the same, and the lane's queue ENTRY instead of its index.  With hp.mode == 2 and STAGE != 0 a wave loads the
+// entries of a range when it reserves it, with coalesced loads (one per 64 entries), into its LDS area `stage` (STAGE >= the
+// largest range; entry i at i mod STAGE), and the refills read them from there: one memory round trip (the path's state
+// through the entry) where the queue load made it two.
+template <uint32_t STAGE>
+RT_DEV bool wave_fetch_entry(WaveRange& r, unsigned long long idle, uint32_t* cursor, uint32_t n, HandoutPolicy hp, bool& exhausted,
+                             const uint32_t* __restrict__ queue, uint32_t* stage, uint32_t& entry) {
+    static_assert(STAGE == 0u || (STAGE >= kHandoutMax && (STAGE & (STAGE - 1u)) == 0u), "a whole range is staged at once");
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool staged = STAGE != 0u && hp.mode >= 2u;
+    bool fresh = !r.staged;  // the static range is staged at the first fetch
+    if (r.cur >= r.end) {
+        if (!r.next(hp, idle, cursor, n)) {
+            exhausted = true;
+            return false;
+        }
+        fresh = true;
+    }
+    if constexpr (STAGE != 0u) {
+        if (staged && fresh) {
+            r.staged = true;
+            __builtin_amdgcn_wave_barrier();  // the LDS reads of the previous range are done
+            uint32_t v[STAGE / 64u];
+#pragma unroll
+            for (uint32_t k = 0; k < STAGE / 64u; k++) v[k] = r.cur + lane + 64u * k < r.end ? queue[r.cur + lane + 64u * k] : 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < STAGE / 64u; k++) stage[(r.cur + lane + 64u * k) & (STAGE - 1u)] = v[k];
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+    const uint32_t avail = r.end - r.cur;
+    const uint32_t rank = lane_prefix(idle);
+    const bool take = ((idle >> lane) & 1ull) && rank < avail;
+    if (take) entry = staged ? stage[(r.cur + rank) & (STAGE != 0u ? STAGE - 1u : 0u)] : queue[r.cur + rank];
+    const uint32_t n_idle = uint32_t(__popcll(idle));
     r.cur += n_idle < avail ? n_idle : avail;
     return take;
 }
@@ -237,8 +292,10 @@ RT_DEV bool wave_fetch(WaveRange& r, unsigned long long idle, uint32_t* cursor, 
 // free-flight distance in the middle of it, volume.rs:47) and a second search state for the boundary tests.
 template <typename R, bool STATS, bool VOL>
 __global__ void __launch_bounds__(256, VOL ? 2 : RT_ISECT_WAVES) k_wf_intersect(SceneView<R> sc, WfPool<R> pool, const uint32_t* __restrict__ queue,
-                                                      WfCounters* __restrict__ ctr, DeviceCounters* counters, uint32_t refill_min) {
+                                                      WfCounters* __restrict__ ctr, DeviceCounters* counters, uint32_t refill_min,
+                                                      uint32_t handout_mode, uint32_t handout_256, uint32_t handout_128) {
     extern __shared__ int lds_stack[];
+    const HandoutPolicy handout{handout_mode, handout_256, handout_128};  // rt_handout.h
     int* stack = lds_stack + threadIdx.x;
     const int stride = int(blockDim.x);
     const uint32_t n = ctr->n_in;
@@ -253,6 +310,7 @@ __global__ void __launch_bounds__(256, VOL ? 2 : RT_ISECT_WAVES) k_wf_intersect(
     bool in_mesh = false;    // ... and is inside a mesh BVH
     bool exhausted = false;  // wave-uniform: the queue has been handed out completely
     WaveRange range;
+    range.init(handout, n);
     uint32_t slot = 0;
     Ray<R> wray{}, cur{};
     Best<R> best{};
@@ -272,7 +330,7 @@ __global__ void __launch_bounds__(256, VOL ? 2 : RT_ISECT_WAVES) k_wf_intersect(
         uint32_t n_idle = uint32_t(__popcll(idle));
         if (!exhausted && n_idle >= refill_min) {
             uint32_t my = 0;
-            if (wave_fetch(range, idle, &ctr->cursor, n, exhausted, my)) {
+            if (wave_fetch(range, idle, &ctr->cursor, n, handout, exhausted, my)) {
                 slot = n == pool.capacity ? my : queue[my];  // full pool: identity order (see k_wf_shade)
                 wray = make_ray(mk<R>(at(pool.ox, slot), at(pool.oy, slot), at(pool.oz, slot)), mk<R>(at(pool.dx, slot), at(pool.dy, slot), at(pool.dz, slot)));
                 cur = wray;
@@ -793,7 +851,12 @@ struct MeshStack {
     }
 };
 
-template <typename R> constexpr uint32_t kMeshWaveLds = 1024u + 3u * 64u * uint32_t(sizeof(R));  // per wave, see k_wf_mesh
+// Queue entries a wave of k_wf_mesh stages (wave_fetch_entry).  f64: four resident workgroups leave 40 960 B each, 12 stack
+// levels + 4 wave areas are 38 912 B with the staged range.  f32 stages nothing: five workgroups leave 32 768 B each and 64
+// entries per wave would fill them to the byte - with those the kernel ran 15 % slower at every RT_WF_HANDOUT
+// (profiles/mesh_handout/ab_c4_f32_staged64.txt).
+template <typename R> constexpr uint32_t kMeshStage = sizeof(R) == 8 ? kHandoutMax : 0u;
+template <typename R> constexpr uint32_t kMeshWaveLds = 1024u + 3u * 64u * uint32_t(sizeof(R)) + 4u * kMeshStage<R>;  // per wave, see k_wf_mesh
 
 // NODE: 0 = 4-wide f32 nodes (BvhNode4f, 128 B), 1 = 4-wide quantised nodes (BvhNode4q, 64 B)
 // MULTI: the program has more than one mesh op: a lane serves the mesh ops of its path one after the other (per-lane mesh
@@ -809,19 +872,21 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
                                                                  uint32_t refill_min, uint32_t inner_min,
                                                                  uint2* __restrict__ spill, int lds_levels,
                                                                  const uint32_t* __restrict__ n_ptr, uint32_t* __restrict__ cursor_ptr,
-                                                                 uint32_t cones_on) {
+                                                                 uint32_t cones_on, uint32_t handout_mode, uint32_t handout_256, uint32_t handout_128) {
+    const HandoutPolicy handout{handout_mode, handout_256, handout_128};  // how the waves share the queue: rt_handout.h
     // n_ptr / cursor_ptr: length and hand-out cursor of `mesh_queue` (&ctr->n_mesh / &ctr->cursor)
     // cones_on: 0 = every ray gets the direction word that culls nothing (RT_WF_CONES=0, the A/B control)
     extern __shared__ uint2 lds_stack2[];
     MeshStack stk;
     stk.lds = (LdsU64*)(lds_stack2 + threadIdx.x);
-    // wave-private LDS behind the stack: pair table (512 x u16) + one result slot per lane (t, u, v)
+    // wave-private LDS behind the stack: pair table (512 x u16) + one result slot per lane (t, u, v) + staged queue entries
     const uint32_t lane = threadIdx.x & 63u;
     char* wave_area = reinterpret_cast<char*>(lds_stack2 + size_t(lds_levels) * 256) + (threadIdx.x >> 6) * kMeshWaveLds<R>;
     uint16_t* pair_tbl = reinterpret_cast<uint16_t*>(wave_area);
     R* res_t = reinterpret_cast<R*>(wave_area + 1024);
     R* res_u = res_t + 64;
     R* res_v = res_u + 64;
+    uint32_t* stage = reinterpret_cast<uint32_t*>(res_v + 64);
     stk.spill = spill + (size_t(blockIdx.x) * blockDim.x + threadIdx.x);
     stk.lds_levels = lds_levels;
     stk.spill_stride = gridDim.x * blockDim.x;
@@ -850,6 +915,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     bool pending = false;    // this lane holds a path whose mesh op `mcur` has not been entered yet
     bool exhausted = false;
     WaveRange range;
+    range.init(handout, n);
     uint32_t slot = 0;
     // bits 0-14: index into sc.mesh_ops of the mesh being traversed / tried next; bits 15-29: 1 + index of the mesh op that holds
     // the closest triangle found for this path so far (0: none); bit 31: the current mesh hits back faces
@@ -989,11 +1055,9 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
             if ((uint32_t(__popcll(idle)) >= refill_min && (!exhausted || waiting != 0ull)) || (waiting != 0ull && idle == ~0ull)) {
                 const unsigned long long want = __ballot(!has && !pending);
                 if (!exhausted && want != 0ull) {
-                    uint32_t my = 0;
                     if (STATS) w_refill++;
-                    if (wave_fetch(range, want, cursor_ptr, n, exhausted, my)) {
+                    if (wave_fetch_entry<kMeshStage<R>>(range, want, cursor_ptr, n, handout, exhausted, mesh_queue, stage, slot)) {
                         if (STATS) l_refill++;
-                        slot = mesh_queue[my];
                         mcur = 0;
                         hit_tri = -1;
                         pending = true;
@@ -1031,11 +1095,9 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
             // ---- refill ----
             const unsigned long long idle = __ballot(!has);
             if (!exhausted && uint32_t(__popcll(idle)) >= refill_min) {
-                uint32_t my = 0;
                 if (STATS) w_refill++;
-                if (wave_fetch(range, idle, cursor_ptr, n, exhausted, my)) {
+                if (wave_fetch_entry<kMeshStage<R>>(range, idle, cursor_ptr, n, handout, exhausted, mesh_queue, stage, slot)) {
                     if (STATS) l_refill++;
-                    slot = mesh_queue[my];
                     hit_tri = -1;
                     enter_mesh(rb0);
                     has = true;

@@ -7,7 +7,8 @@ binding), each renders bench.py's workload into its own device frame; after one 
 timed frames each.  Per side: median / min / max wall time of a frame, the HIP-event sums of the kernels (rt_get_stats), and
 whether every frame equals the parent's bit for bit.  `verdict` applies the criterion: the medians differ by more than three
 times the larger min-max spread of the two sides.  Extra sides: --env=NAME=VALUE renders the new library once more with that
-variable set (e.g. RT_WF_FUSE=0, the new library's own unfused pipeline)."""
+variable set (e.g. RT_WF_FUSE=0, the new library's own unfused pipeline); several variables of one side are joined with a
+comma (--env=RT_WF_HANDOUT_256=512,RT_WF_HANDOUT_128=128)."""
 import importlib.util
 import os
 import sys
@@ -38,7 +39,7 @@ def main():
     for a in sys.argv[1:]:
         k, _, v = a.lstrip("-").partition("=")
         if k == "env":
-            envs.append(tuple(v.split("=", 1)))
+            envs.append((v, dict(kv.split("=", 1) for kv in v.split(","))))
         else:
             opt[k] = v
     if not os.path.exists(opt["parent"]):
@@ -57,9 +58,9 @@ def main():
             sc = api.DeviceScene(hs.desc, 0)
             out = torch.empty((hs.height, hs.width, 4), dtype=torch.float64, device="cuda:0")
             sides.append([name, hs, p, sc, out, {}])
-        for name, v in envs:
+        for label, env in envs:
             n, hs, p, sc, _, _ = sides[1]
-            sides.append([f"this commit, {name}={v}", hs, p, sc, torch.empty_like(sides[1][4]), {name: v}])
+            sides.append([f"this commit, {label}", hs, p, sc, torch.empty_like(sides[1][4]), env])
         hs = sides[0][1]
         samples = hs.width * hs.height * hs.spp
         print(f"{wl} {hs.width}x{hs.height} @{hs.spp}spp {opt['precision']} = {samples / 1e6:.0f} Msamples per frame; {steps} timed frames per side "
