@@ -202,6 +202,10 @@ template <typename R> RT_DEV Ray<R> make_ray(V3<R> o, V3<R> d) {  // ray.rs:19-3
 }
 template <typename R> RT_DEV V3<R> ray_at(const Ray<R>& r, R t) { return r.o + (r.d * t); }  // ray.rs:35
 
+}  // namespace rt
+#include "rt_traverse.h"  // the steps of a BVH search, in terms of V3 / Lim / Ray above
+namespace rt {
+
 // aabb.rs:50-87, Williams et al.; `sign[i] = inv_dir[i] < 0` (ray.rs:21-25)
 template <typename R> RT_DEV bool test_bounding_box(const Bounds<R>& b, const Ray<R>& ray, R t_lo, R t_hi) {
     bool sx = ray.inv.x < R(0), sy = ray.inv.y < R(0), sz = ray.inv.z < R(0);
@@ -283,76 +287,40 @@ struct LaneCounters {
     uint32_t rays = 0, mesh_rays = 0, node_visits = 0, tri_tests = 0, prim_tests = 0;
 };
 
-// mesh.rs:62-107 Moeller-Trumbore with the reference's cull and interval rules
+// Closest hit of one mesh instance over its BVH2 (the megakernel pipeline): mesh.rs:62-107 with the reference's interval rule
 template <typename R, bool STATS>
 RT_DEV void mesh_traverse(const SceneView<R>& sc, const MeshInst& mi, const Ray<R>& ray, R t_lo, Best<R>& best, int32_t pc,
                           int* stack, int stride, LaneCounters& cnt) {
     const BvhNode<R>* nodes = sc.nodes + mi.node_base;
     const TriRec<R>* tris = sc.tris + mi.tri_base;
     const bool hit_back = (mi.flags & RT_MESH_HIT_BACK_FACES) != 0;
-    // Slab tests as t = b * inv - o * inv (culling only, any conservative test is admissible).
-    // A zero direction component gives inv = +-inf and inf - inf = NaN in that form, so the
-    // inverse used HERE is clamped to a huge finite value: a ray parallel to a slab is then
-    // "inside forever" or "outside forever", which is exact.
-    const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
-    const V3<R> inv = {fabs(ray.inv.x) > big ? copysign(big, ray.inv.x) : ray.inv.x,
-                       fabs(ray.inv.y) > big ? copysign(big, ray.inv.y) : ray.inv.y,
-                       fabs(ray.inv.z) > big ? copysign(big, ray.inv.z) : ray.inv.z};
+    const V3<R> inv = clamped_inv(ray);
     const V3<R> oi = ray.o * inv;
     int sp = 0;
     int32_t cur = 0;
     if (STATS) cnt.mesh_rays++;
     for (;;) {
         if (cur >= 0) {
-            const BvhNode<R>& n = nodes[cur];
             if (STATS) cnt.node_visits++;
-            R t0x = n.lo0[0] * inv.x - oi.x, t1x = n.hi0[0] * inv.x - oi.x;
-            R t0y = n.lo0[1] * inv.y - oi.y, t1y = n.hi0[1] * inv.y - oi.y;
-            R t0z = n.lo0[2] * inv.z - oi.z, t1z = n.hi0[2] * inv.z - oi.z;
-            R near0 = fmax(fmax(fmin(t0x, t1x), fmin(t0y, t1y)), fmax(fmin(t0z, t1z), t_lo));
-            R far0 = fmin(fmin(fmax(t0x, t1x), fmax(t0y, t1y)), fmin(fmax(t0z, t1z), best.t));
-            R s0x = n.lo1[0] * inv.x - oi.x, s1x = n.hi1[0] * inv.x - oi.x;
-            R s0y = n.lo1[1] * inv.y - oi.y, s1y = n.hi1[1] * inv.y - oi.y;
-            R s0z = n.lo1[2] * inv.z - oi.z, s1z = n.hi1[2] * inv.z - oi.z;
-            R near1 = fmax(fmax(fmin(s0x, s1x), fmin(s0y, s1y)), fmax(fmin(s0z, s1z), t_lo));
-            R far1 = fmin(fmin(fmax(s0x, s1x), fmax(s0y, s1y)), fmin(fmax(s0z, s1z), best.t));
-            int32_t c0 = n.c0, c1 = n.c1;
-            bool h0 = (near0 <= far0) && c0 != kEmptyChild;
-            bool h1 = (near1 <= far1) && c1 != kEmptyChild;
-            if (h0 && h1) {
-                bool first0 = near0 <= near1;
-                stack[sp * stride] = first0 ? c1 : c0;
-                sp++;
-                cur = first0 ? c0 : c1;
+            int32_t first, second;
+            if (node2_step(nodes[cur], inv, oi, t_lo, best.t, first, second)) {
+                if (second != kEmptyChild) { stack[sp * stride] = second; sp++; }
+                cur = first;
                 continue;
             }
-            if (h0) { cur = c0; continue; }
-            if (h1) { cur = c1; continue; }
         } else {
             uint32_t code = uint32_t(~cur);
             uint32_t first = code >> 3, count = (code & 7u) + 1u;
             for (uint32_t i = 0; i < count; i++) {
-                const TriRec<R>& tr = tris[first + i];
                 if (STATS) cnt.tri_tests++;
-                V3<R> edge1 = ld3(tr.e1), edge2 = ld3(tr.e2);
-                V3<R> ray_x_edge2 = cross(ray.d, edge2);
-                R det = dot(edge1, ray_x_edge2);
-                R dd = hit_back ? fabs(det) : det;
-                if (dd < Lim<R>::eps()) continue;
-                R inv_det = R(1) / det;
-                V3<R> b = ray.o - ld3(tr.v0);
-                R u = dot(b, ray_x_edge2) * inv_det;
-                if (u < R(0) || u > R(1)) continue;
-                V3<R> b_x_edge1 = cross(b, edge1);
-                R v = dot(ray.d, b_x_edge1) * inv_det;
-                if (v < R(0) || u + v > R(1)) continue;
-                R t = dot(edge2, b_x_edge1) * inv_det;
-                if (t <= t_lo || best.t <= t) continue;
-                best.t = t;
-                best.pc = pc;
-                best.tri = int32_t(mi.tri_base + first + i);
-                best.u = u;
-                best.v = v;
+                R t = R(0), u = R(0), v = R(0);
+                if (tri_test(tris[first + i], ray.o, ray.d, hit_back, t, u, v) && !(t <= t_lo || best.t <= t)) {
+                    best.t = t;
+                    best.pc = pc;
+                    best.tri = int32_t(mi.tri_base + first + i);
+                    best.u = u;
+                    best.v = v;
+                }
             }
         }
         if (sp == 0) break;

@@ -142,11 +142,6 @@ __global__ void __launch_bounds__(256) k_rq_resolve(SceneView<R> sc, RqPool<R> p
 // the strict ends; a mesh op is searched by mesh_any_hit.  The lane leaves at the first accepted primitive.  Sky and Sun
 // never occlude.
 // ---------------------------------------------------------------------------------------------
-RT_DEV float rq_f32_at_least(double x) {  // f32 value that is certainly >= x: round to nearest, then a 2^-20 relative margin
-    float f = float(x);
-    return f + fabsf(f) * 9.5367431640625e-7f + 1e-30f;
-}
-
 // Any-hit search of one mesh instance over its 4-wide quantised nodes (MeshNode4qc), k_wf_mesh's node step without the
 // ordering: the segment is fixed, so no entry distances are kept and a stack entry is the 4-B child reference (half of
 // k_wf_mesh's LDS per level).  The f32 culling ray starts where the segment enters the mesh's box (the nodes' padding covers
@@ -157,72 +152,31 @@ template <typename R>
 RT_DEV bool mesh_any_hit(const SceneView<R>& sc, const MeshInst& mi, const Bounds<R>& rb, const Ray<R>& ray, R t_lo, R t_hi, int* stack,
                          int levels, uint32_t cones_on) {
     if (!(rb.lo[0] <= rb.hi[0])) return false;  // a mesh without triangles
-    const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
-    const V3<R> o = ray.o, d = ray.d;
-    const V3<R> inv = mk<R>(R(fabs(ray.inv.x) > big ? copysign(big, ray.inv.x) : ray.inv.x),
-                            R(fabs(ray.inv.y) > big ? copysign(big, ray.inv.y) : ray.inv.y),
-                            R(fabs(ray.inv.z) > big ? copysign(big, ray.inv.z) : ray.inv.z));
-    // the part of the segment inside the mesh's box; a miss only if it is one with a few ulps of slack on both ends
-    // (a NaN compares false: the mesh is entered), like k_wf_mesh<MULTI>
-    const R e0x = (rb.lo[0] - o.x) * inv.x, e1x = (rb.hi[0] - o.x) * inv.x;
-    const R e0y = (rb.lo[1] - o.y) * inv.y, e1y = (rb.hi[1] - o.y) * inv.y;
-    const R e0z = (rb.lo[2] - o.z) * inv.z, e1z = (rb.hi[2] - o.z) * inv.z;
-    R t_shift = fmax(fmax(fmin(e0x, e1x), fmin(e0y, e1y)), fmax(fmin(e0z, e1z), t_lo));
-    const R t_exit = fmin(fmin(fmax(e0x, e1x), fmax(e0y, e1y)), fmax(e0z, e1z));
-    const R eps = Lim<R>::eps() * R(16);
-    if ((t_shift - fabs(t_shift) * eps > t_exit + fabs(t_exit) * eps) || (t_shift - fabs(t_shift) * eps > t_hi)) return false;
-    if (!(fabs(t_shift) < Lim<R>::inf())) t_shift = R(0);
-    const V3<R> oc = o + d * t_shift;
-    const float big32 = 1e18f;
-    float ivx = 1.0f / float(d.x), ivy = 1.0f / float(d.y), ivz = 1.0f / float(d.z);
-    ivx = fabsf(ivx) > big32 ? copysignf(big32, ivx) : ivx;
-    ivy = fabsf(ivy) > big32 ? copysignf(big32, ivy) : ivy;
-    ivz = fabsf(ivz) > big32 ? copysignf(big32, ivz) : ivz;
-    const float oix = float(oc.x) * ivx, oiy = float(oc.y) * ivy, oiz = float(oc.z) * ivz;
-    const float tmax32 = rq_f32_at_least(double(t_hi - t_shift));
+    // the part of the segment inside the mesh's box, like k_wf_mesh<MULTI>
+    R t_enter, t_exit;
+    const CullRay<R> cr = make_cull_ray(ray, rb.lo, rb.hi, t_lo, t_enter, t_exit);
+    if (span_misses(t_enter, t_exit, t_hi)) return false;
+    const float tmax32 = f32_at_least(t_hi - cr.t_shift);
     const bool hit_back = (mi.flags & RT_MESH_HIT_BACK_FACES) != 0u;
-    // object-space direction as four signed bytes for the cone test (rt_bvh.cpp); |d|^2 outside the range (or NaN) and
-    // meshes that hit back faces: no culling
-    uint32_t dirq = kNoCullDir;
-    {
-        const R len2 = d.x * d.x + d.y * d.y + d.z * d.z;
-        const R len_lo = sizeof(R) == 8 ? R(1e-200) : R(1e-24), len_hi = sizeof(R) == 8 ? R(1e200) : R(1e24);
-        if (cones_on != 0u && !hit_back && len2 > len_lo && len2 < len_hi) {
-            const R sc127 = R(127) / sqrt(len2);
-            const int qx = int(rint(d.x * sc127)), qy = int(rint(d.y * sc127)), qz = int(rint(d.z * sc127));
-            dirq = (uint32_t(qx) & 0xFFu) | ((uint32_t(qy) & 0xFFu) << 8) | ((uint32_t(qz) & 0xFFu) << 16) | kNoCullDir;
-        }
-    }
+    const uint32_t dirq = quantise_dir(ray.d, cones_on != 0u && !hit_back);
     const MeshNode4qc* nodesq = sc.nodes4q;
     const TriRec<R>* tris = sc.tris;  // leaf codes hold absolute triangle slots
-    const bool negx = ivx < 0.0f, negy = ivy < 0.0f, negz = ivz < 0.0f;
     int32_t node = int32_t(mi.node4_base);
     int sp = 0;
     for (;;) {
         if (node >= 0) {
-            // five 16-B loads from one line; plane = org + q * cell, so t = q * (cell * iv) + (org * iv - o * iv)
+            // five 16-B loads from one line
             const uint4* nd = reinterpret_cast<const uint4*>(nodesq + node);
             const uint4 h0 = nd[0], h1 = nd[1], h2 = nd[2];
             const int4 cc = *reinterpret_cast<const int4*>(nd + 3);
-            const uint4 cn = nd[4];
             int32_t ch[4];
-            ch[0] = __builtin_amdgcn_sdot4(int(dirq), int(cn.x), 0, false) > 0 ? kEmptyChild : cc.x;
-            ch[1] = __builtin_amdgcn_sdot4(int(dirq), int(cn.y), 0, false) > 0 ? kEmptyChild : cc.y;
-            ch[2] = __builtin_amdgcn_sdot4(int(dirq), int(cn.z), 0, false) > 0 ? kEmptyChild : cc.z;
-            ch[3] = __builtin_amdgcn_sdot4(int(dirq), int(cn.w), 0, false) > 0 ? kEmptyChild : cc.w;
-            const float ax = __uint_as_float(h0.w) * ivx, ay = __uint_as_float(h1.x) * ivy, az = __uint_as_float(h1.y) * ivz;
-            const float bx = fmaf(__uint_as_float(h0.x), ivx, -oix), by = fmaf(__uint_as_float(h0.y), ivy, -oiy), bz = fmaf(__uint_as_float(h0.z), ivz, -oiz);
-            const uint32_t qnx = negx ? h2.y : h1.z, qfx = negx ? h1.z : h2.y;
-            const uint32_t qny = negy ? h2.z : h1.w, qfy = negy ? h1.w : h2.z;
-            const uint32_t qnz = negz ? h2.w : h2.x, qfz = negz ? h2.x : h2.w;
+            float nr[4];
+            node4q_cull_cones(dirq, nd[4], cc, ch);
+            const uint32_t entered = node4q_entries(h0, h1, h2, cr, tmax32, ch, nr);
             int32_t next = kEmptyChild;
 #pragma unroll
             for (int k = 0; k < 4; k++) {
-                const float nxk = float((qnx >> (8 * k)) & 0xFFu), nyk = float((qny >> (8 * k)) & 0xFFu), nzk = float((qnz >> (8 * k)) & 0xFFu);
-                const float fxk = float((qfx >> (8 * k)) & 0xFFu), fyk = float((qfy >> (8 * k)) & 0xFFu), fzk = float((qfz >> (8 * k)) & 0xFFu);
-                const float tn = fmaxf(fmaxf(fmaf(nxk, ax, bx), fmaf(nyk, ay, by)), fmaxf(fmaf(nzk, az, bz), 0.0f));
-                const float tf = fminf(fminf(fmaf(fxk, ax, bx), fmaf(fyk, ay, by)), fminf(fmaf(fzk, az, bz), tmax32));
-                if ((tn <= tf) && ch[k] != kEmptyChild) {
+                if ((entered >> k) & 1u) {
                     if (next != kEmptyChild && sp < levels) { stack[sp * 256] = next; sp++; }  // sp < levels always: the bound is the tree's worst case
                     next = ch[k];
                 }
@@ -231,23 +185,9 @@ RT_DEV bool mesh_any_hit(const SceneView<R>& sc, const MeshInst& mi, const Bound
         } else {
             const uint32_t code = uint32_t(~node);
             const uint32_t first = code >> 3, count = (code & 7u) + 1u;
-            for (uint32_t k = 0; k < count; k++) {  // mesh.rs:62-107
-                const TriRec<R>& tr = tris[first + k];
-                V3<R> edge1 = ld3(tr.e1), edge2 = ld3(tr.e2);
-                V3<R> ray_x_edge2 = cross(d, edge2);
-                R det = dot(edge1, ray_x_edge2);
-                R dd = hit_back ? fabs(det) : det;
-                if (dd < Lim<R>::eps()) continue;
-                R inv_det = R(1) / det;
-                V3<R> b = o - ld3(tr.v0);
-                R u = dot(b, ray_x_edge2) * inv_det;
-                if (u < R(0) || u > R(1)) continue;
-                V3<R> b_x_edge1 = cross(b, edge1);
-                R v = dot(d, b_x_edge1) * inv_det;
-                if (v < R(0) || u + v > R(1)) continue;
-                R t = dot(edge2, b_x_edge1) * inv_det;
-                if (t <= t_lo || t_hi <= t) continue;
-                return true;
+            for (uint32_t k = 0; k < count; k++) {
+                R t = R(0), u = R(0), v = R(0);
+                if (tri_test(tris[first + k], ray.o, ray.d, hit_back, t, u, v) && !(t <= t_lo || t_hi <= t)) return true;
             }
         }
         if (sp == 0) return false;

@@ -363,10 +363,7 @@ __global__ void __launch_bounds__(256, VOL ? 2 : RT_ISECT_WAVES) k_wf_intersect(
                     tris = sc.tris + mi.tri_base;
                     tri_base = mi.tri_base;
                     hit_back = (mi.flags & RT_MESH_HIT_BACK_FACES) != 0;
-                    const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);  // see mesh_traverse
-                    inv = {fabs(cur.inv.x) > big ? copysign(big, cur.inv.x) : cur.inv.x,
-                           fabs(cur.inv.y) > big ? copysign(big, cur.inv.y) : cur.inv.y,
-                           fabs(cur.inv.z) > big ? copysign(big, cur.inv.z) : cur.inv.z};
+                    inv = clamped_inv(cur);
                     oi = cur.o * inv;
                     node = 0;
                     sp = 0;
@@ -441,50 +438,22 @@ __global__ void __launch_bounds__(256, VOL ? 2 : RT_ISECT_WAVES) k_wf_intersect(
             if (in_mesh) {
                 bool pop = true;
                 if (node >= 0) {
-                    const BvhNode<R>& nd = nodes[node];
                     if (STATS) cnt.node_visits++;
-                    R t0x = nd.lo0[0] * inv.x - oi.x, t1x = nd.hi0[0] * inv.x - oi.x;
-                    R t0y = nd.lo0[1] * inv.y - oi.y, t1y = nd.hi0[1] * inv.y - oi.y;
-                    R t0z = nd.lo0[2] * inv.z - oi.z, t1z = nd.hi0[2] * inv.z - oi.z;
-                    R near0 = fmax(fmax(fmin(t0x, t1x), fmin(t0y, t1y)), fmax(fmin(t0z, t1z), t_lo));
-                    R far0 = fmin(fmin(fmax(t0x, t1x), fmax(t0y, t1y)), fmin(fmax(t0z, t1z), best.t));
-                    R s0x = nd.lo1[0] * inv.x - oi.x, s1x = nd.hi1[0] * inv.x - oi.x;
-                    R s0y = nd.lo1[1] * inv.y - oi.y, s1y = nd.hi1[1] * inv.y - oi.y;
-                    R s0z = nd.lo1[2] * inv.z - oi.z, s1z = nd.hi1[2] * inv.z - oi.z;
-                    R near1 = fmax(fmax(fmin(s0x, s1x), fmin(s0y, s1y)), fmax(fmin(s0z, s1z), t_lo));
-                    R far1 = fmin(fmin(fmax(s0x, s1x), fmax(s0y, s1y)), fmin(fmax(s0z, s1z), best.t));
-                    int32_t c0 = nd.c0, c1 = nd.c1;
-                    bool h0 = (near0 <= far0) && c0 != kEmptyChild;
-                    bool h1 = (near1 <= far1) && c1 != kEmptyChild;
-                    if (h0 && h1) {
-                        bool first0 = near0 <= near1;
-                        stack[sp * stride] = first0 ? c1 : c0;
-                        sp++;
-                        node = first0 ? c0 : c1;
+                    int32_t first = 0, second;  // first initialised: 2 VGPRs, and 8 B of scratch in the f64 counting variant, otherwise
+                    if (node2_step(nodes[node], inv, oi, t_lo, best.t, first, second)) {
+                        if (second != kEmptyChild) { stack[sp * stride] = second; sp++; }
+                        node = first;
                         pop = false;
-                    } else if (h0) { node = c0; pop = false; }
-                    else if (h1) { node = c1; pop = false; }
+                    }
                 } else {
                     uint32_t code = uint32_t(~node);
                     uint32_t first = code >> 3, count = (code & 7u) + 1u;
                     for (uint32_t i = 0; i < count; i++) {
-                        const TriRec<R>& tr = tris[first + i];
                         if (STATS) cnt.tri_tests++;
-                        V3<R> edge1 = ld3(tr.e1), edge2 = ld3(tr.e2);
-                        V3<R> ray_x_edge2 = cross(cur.d, edge2);
-                        R det = dot(edge1, ray_x_edge2);
-                        R dd = hit_back ? fabs(det) : det;
-                        if (dd < Lim<R>::eps()) continue;
-                        R inv_det = R(1) / det;
-                        V3<R> b = cur.o - ld3(tr.v0);
-                        R u = dot(b, ray_x_edge2) * inv_det;
-                        if (u < R(0) || u > R(1)) continue;
-                        V3<R> b_x_edge1 = cross(b, edge1);
-                        R v = dot(cur.d, b_x_edge1) * inv_det;
-                        if (v < R(0) || u + v > R(1)) continue;
-                        R t = dot(edge2, b_x_edge1) * inv_det;
-                        if (t <= t_lo || best.t <= t) continue;
-                        best.t = t; best.pc = pc; best.tri = int32_t(tri_base + first + i); best.u = u; best.v = v;
+                        R t = R(0), u = R(0), v = R(0);
+                        if (tri_test(tris[first + i], cur.o, cur.d, hit_back, t, u, v) && !(t <= t_lo || best.t <= t)) {
+                            best.t = t; best.pc = pc; best.tri = int32_t(tri_base + first + i); best.u = u; best.v = v;
+                        }
                     }
                 }
                 if (pop) {
@@ -520,13 +489,6 @@ __global__ void __launch_bounds__(256, VOL ? 2 : RT_ISECT_WAVES) k_wf_intersect(
 // Closest-hit semantics are those of the in-order program: the nearest t wins and, at exactly equal
 // t, the op that comes first in the reference's visiting order (its tests use strict `t < closest`).
 // ---------------------------------------------------------------------------------------------
-// f32 value that is certainly >= x (x finite or +inf): round to nearest, then add a relative margin.
-RT_DEV float f32_at_least(double x) {
-    float f = float(x);
-    return f + fabsf(f) * 9.5367431640625e-7f + 1e-30f;  // 2^-20 relative
-}
-RT_DEV float f32_at_least(float x) { return x + fabsf(x) * 9.5367431640625e-7f + 1e-30f; }
-
 typedef __attribute__((address_space(3))) unsigned long long LdsU64;
 
 // ---------------------------------------------------------------------------------------------
@@ -544,65 +506,28 @@ struct GroupCtx {
 
 template <typename R, bool STATS>
 RT_DEV void group_search(const SceneView<R>& sc, const GroupCtx& gc, const GroupRec<R>& g, const Ray<R>& cur, R t_lo, Best<R>& best, LaneCounters& cnt) {
-    const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
-    const V3<R> inv = {fabs(cur.inv.x) > big ? copysign(big, cur.inv.x) : cur.inv.x,
-                       fabs(cur.inv.y) > big ? copysign(big, cur.inv.y) : cur.inv.y,
-                       fabs(cur.inv.z) > big ? copysign(big, cur.inv.z) : cur.inv.z};
-    // entry into the group's box (>= 0) and exit; the culling origin is o + d * t_shift, so that its f32 image is no larger than the box
-    const R e0x = (g.lo[0] - cur.o.x) * inv.x, e1x = (g.hi[0] - cur.o.x) * inv.x;
-    const R e0y = (g.lo[1] - cur.o.y) * inv.y, e1y = (g.hi[1] - cur.o.y) * inv.y;
-    const R e0z = (g.lo[2] - cur.o.z) * inv.z, e1z = (g.hi[2] - cur.o.z) * inv.z;
-    R t_shift = fmax(fmax(fmin(e0x, e1x), fmin(e0y, e1y)), fmax(fmin(e0z, e1z), R(0)));
-    const R t_exit = fmin(fmin(fmax(e0x, e1x), fmax(e0y, e1y)), fmax(e0z, e1z));
-    const R eps = Lim<R>::eps() * R(16);  // a miss only if it is one with a few ulps of slack (a NaN compares false: the group is searched)
-    if ((t_shift - fabs(t_shift) * eps > t_exit + fabs(t_exit) * eps) || (t_shift - fabs(t_shift) * eps > best.t)) return;
-    if (!(t_shift < Lim<R>::inf())) t_shift = R(0);
-    const V3<R> oc = cur.o + cur.d * t_shift;
-    const float big32 = 1e18f;
-    float ivx = 1.0f / float(cur.d.x), ivy = 1.0f / float(cur.d.y), ivz = 1.0f / float(cur.d.z);
-    ivx = fabsf(ivx) > big32 ? copysignf(big32, ivx) : ivx;
-    ivy = fabsf(ivy) > big32 ? copysignf(big32, ivy) : ivy;
-    ivz = fabsf(ivz) > big32 ? copysignf(big32, ivz) : ivz;
-    const float oix = float(oc.x) * ivx, oiy = float(oc.y) * ivy, oiz = float(oc.z) * ivz;
-    const bool negx = ivx < 0.0f, negy = ivy < 0.0f, negz = ivz < 0.0f;
-    float tmax32 = f32_at_least(best.t - t_shift);
+    R t_enter, t_exit;  // of the group's box, entry >= 0
+    const CullRay<R> cr = make_cull_ray(cur, g.lo, g.hi, R(0), t_enter, t_exit);
+    if (span_misses(t_enter, t_exit, best.t)) return;
+    float tmax32 = f32_at_least(best.t - cr.t_shift);
     int32_t node = int32_t(g.root);
     int sp = 0;
     for (;;) {
         bool pop = false;
         if (node >= 0) {
             if (STATS) cnt.node_visits++;
-            const float miss = __builtin_huge_valf();
             const uint4* nd = reinterpret_cast<const uint4*>(gc.nodes + node);
             const uint4 h0 = nd[0], h1 = nd[1], h2 = nd[2];
             const int4 cc = *reinterpret_cast<const int4*>(nd + 3);
             float nr[4];
             int32_t ch[4] = {cc.x, cc.y, cc.z, cc.w};
-            const float ax = __uint_as_float(h0.w) * ivx, ay = __uint_as_float(h1.x) * ivy, az = __uint_as_float(h1.y) * ivz;
-            const float bx = fmaf(__uint_as_float(h0.x), ivx, -oix), by = fmaf(__uint_as_float(h0.y), ivy, -oiy), bz = fmaf(__uint_as_float(h0.z), ivz, -oiz);
-            const uint32_t qnx = negx ? h2.y : h1.z, qfx = negx ? h1.z : h2.y;
-            const uint32_t qny = negy ? h2.z : h1.w, qfy = negy ? h1.w : h2.z;
-            const uint32_t qnz = negz ? h2.w : h2.x, qfz = negz ? h2.x : h2.w;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const float nxk = float((qnx >> (8 * k)) & 0xFFu), nyk = float((qny >> (8 * k)) & 0xFFu), nzk = float((qnz >> (8 * k)) & 0xFFu);
-                const float fxk = float((qfx >> (8 * k)) & 0xFFu), fyk = float((qfy >> (8 * k)) & 0xFFu), fzk = float((qfz >> (8 * k)) & 0xFFu);
-                const float tn = fmaxf(fmaxf(fmaf(nxk, ax, bx), fmaf(nyk, ay, by)), fmaxf(fmaf(nzk, az, bz), 0.0f));
-                const float tf = fminf(fminf(fmaf(fxk, ax, bx), fmaf(fyk, ay, by)), fminf(fmaf(fzk, az, bz), tmax32));
-                nr[k] = ((tn <= tf) && ch[k] != kEmptyChild) ? tn : miss;
-            }
-#define RT_CE(a, b)                                                   \
-    if (nr[a] > nr[b]) {                                              \
-        float tn_ = nr[a]; nr[a] = nr[b]; nr[b] = tn_;                \
-        int32_t tc_ = ch[a]; ch[a] = ch[b]; ch[b] = tc_;              \
-    }
-            RT_CE(0, 1) RT_CE(2, 3) RT_CE(0, 2) RT_CE(1, 3) RT_CE(1, 2)
-#undef RT_CE
-            if (nr[0] < miss) {
+            node4q_entries(h0, h1, h2, cr, tmax32, ch, nr);
+            RT_SORT4_NEAREST_FIRST(nr, ch)
+            if (nr[0] < kNoEntry) {
                 // farthest first, so that the nearest remaining child is popped first
-                if (nr[3] < miss) { gc.stack[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(nr[3])) << 32) | uint32_t(ch[3]); sp++; }
-                if (nr[2] < miss) { gc.stack[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(nr[2])) << 32) | uint32_t(ch[2]); sp++; }
-                if (nr[1] < miss) { gc.stack[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(nr[1])) << 32) | uint32_t(ch[1]); sp++; }
+                if (nr[3] < kNoEntry) { gc.stack[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(nr[3])) << 32) | uint32_t(ch[3]); sp++; }
+                if (nr[2] < kNoEntry) { gc.stack[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(nr[2])) << 32) | uint32_t(ch[2]); sp++; }
+                if (nr[1] < kNoEntry) { gc.stack[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(nr[1])) << 32) | uint32_t(ch[1]); sp++; }
                 node = ch[0];
             } else {
                 pop = true;
@@ -626,7 +551,7 @@ RT_DEV void group_search(const SceneView<R>& sc, const GroupCtx& gc, const Group
                     if (plane_test<R, true>(sc.planes[pop_.arg], cur, t_lo, best.t, t, u, v) && hit_takes_over(sc, t, pop_, best)) { best.t = t; best.pc = ref.pc; best.u = u; best.v = v; }
                 }
             }
-            tmax32 = f32_at_least(best.t - t_shift);
+            tmax32 = f32_at_least(best.t - cr.t_shift);
             pop = true;
         }
         if (pop) {
@@ -717,10 +642,7 @@ RT_DEV bool prims_search(const SceneView<R>& sc, const Ray<R>& wray, Best<R>& be
                 // the mesh can only shorten the interval, and the test only culls: conservative), so that no copy of the
                 // object-space ray has to stay alive to the end of the program.
                 const Bounds<R>& rb = sc.mesh_bounds[op.arg];
-                const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
-                V3<R> inv = {fabs(cur.inv.x) > big ? copysign(big, cur.inv.x) : cur.inv.x,
-                             fabs(cur.inv.y) > big ? copysign(big, cur.inv.y) : cur.inv.y,
-                             fabs(cur.inv.z) > big ? copysign(big, cur.inv.z) : cur.inv.z};
+                const V3<R> inv = clamped_inv(cur);
                 // a few ulps of slack on the box: this test must never be stricter than the traversal
                 const R eps = Lim<R>::eps() * R(16);
                 R t0x = (rb.lo[0] - fabs(rb.lo[0]) * eps - cur.o.x) * inv.x, t1x = (rb.hi[0] + fabs(rb.hi[0]) * eps - cur.o.x) * inv.x;
@@ -896,7 +818,6 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     const MeshNode4qc* nodesq = sc.nodes4q;
     const TriRec<R>* tris = sc.tris;
     const uint32_t n_mesh_ops = uint32_t(sc.n_mesh_ops);
-    const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
     const MeshOpRec<R>* mrecs = sc.mesh_op_recs;
     // Loads record m (wave-uniform index) with scalar loads, field by field (no copy constructor from an address space).
     auto load_rec = [&](uint32_t m, MeshOpRec<R>& rb) {
@@ -921,15 +842,13 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     // the closest triangle found for this path so far (0: none); bit 31: the current mesh hits back faces
     uint32_t mcur = 0;
     V3<R> o{}, d{};          // object-space ray, exact: used by the triangle tests
-    R t_max = R(0), hit_u = R(0), hit_v = R(0), t_shift = R(0);
+    R t_max = R(0), hit_u = R(0), hit_v = R(0);
     int32_t hit_tri = -1;
-    // f32 culling ray: origin moved onto the mesh box (so |origin| <= mesh extent), t measured from there
-    float ivx = 0.f, ivy = 0.f, ivz = 0.f, oix = 0.f, oiy = 0.f, oiz = 0.f, tmax32 = 0.f;
+    CullRay<R> cr{};         // origin moved onto the mesh box
+    float tmax32 = 0.f;      // t_max in its terms
     int32_t node = 0;        // >= 0 inner node, < 0 leaf
     int sp = 0;
-    // object-space direction as four signed bytes (round(127 d / |d|), -127) for the back-face cone test of the node step
-    // (NODE == 1; rt_bvh.cpp has the argument); kNoCullDir for rays that must not cull
-    uint32_t dirq = kNoCullDir;
+    uint32_t dirq = kNoCullDir;  // NODE == 1: quantise_dir of d
 
     // The lane has finished every mesh of its path: the closest triangle, if one beat the other primitives' hit, is the path's hit.
     auto finish_path = [&]() {
@@ -999,9 +918,6 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
         else ray = ray_in_chain_uniform(sc, wray, rb.chain);
         o = ray.o;
         d = ray.d;
-        V3<R> inv = mk<R>(R(fabs(ray.inv.x) > big ? copysign(big, ray.inv.x) : ray.inv.x),
-                          R(fabs(ray.inv.y) > big ? copysign(big, ray.inv.y) : ray.inv.y),
-                          R(fabs(ray.inv.z) > big ? copysign(big, ray.inv.z) : ray.inv.z));
         // The other primitives' closest hit bounds the search.  At exactly equal t the op that comes first in
         // program order wins: if that is this mesh, t == bound must be accepted.  A triangle of an EARLIER mesh
         // always wins a tie (strict bound, like the reference's shrinking interval: list.rs:58-74).
@@ -1010,40 +926,15 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
         const R excl = (bpc > mpc && bound < Lim<R>::inf()) ? nextafter(bound, Lim<R>::inf()) : bound;
         if constexpr (MULTI) t_max = ((mcur >> 15) & 0x7FFFu) != 0u ? fmin(t_max, excl) : excl;
         else t_max = excl;
-        // entry into the mesh box (>= 0) and exit; the culling origin is o + d * t_shift
-        R e0x = (rb.lo[0] - o.x) * inv.x, e1x = (rb.hi[0] - o.x) * inv.x;
-        R e0y = (rb.lo[1] - o.y) * inv.y, e1y = (rb.hi[1] - o.y) * inv.y;
-        R e0z = (rb.lo[2] - o.z) * inv.z, e1z = (rb.hi[2] - o.z) * inv.z;
-        t_shift = fmax(fmax(fmin(e0x, e1x), fmin(e0y, e1y)), fmax(fmin(e0z, e1z), R(0)));
+        R t_enter, t_exit;  // of the mesh box, entry >= 0
+        cr = make_cull_ray(ray, rb.lo, rb.hi, R(0), t_enter, t_exit);
         if constexpr (MULTI) {
-            R t_exit = fmin(fmin(fmax(e0x, e1x), fmax(e0y, e1y)), fmax(e0z, e1z));
-            // a miss only if it is one with a few ulps of slack on both ends (a NaN compares false: the mesh is entered)
-            const R eps = Lim<R>::eps() * R(16);
-            if ((t_shift - fabs(t_shift) * eps > t_exit + fabs(t_exit) * eps) || (t_shift - fabs(t_shift) * eps > t_max) || !(rb.lo[0] <= rb.hi[0])) return false;
+            if (span_misses(t_enter, t_exit, t_max) || !(rb.lo[0] <= rb.hi[0])) return false;
         }
-        if (!(t_shift < Lim<R>::inf())) t_shift = R(0);
-        V3<R> oc = o + d * t_shift;
-        const float big32 = 1e18f;
-        float dx32 = float(d.x), dy32 = float(d.y), dz32 = float(d.z);
-        ivx = 1.0f / dx32; ivy = 1.0f / dy32; ivz = 1.0f / dz32;
-        ivx = fabsf(ivx) > big32 ? copysignf(big32, ivx) : ivx;
-        ivy = fabsf(ivy) > big32 ? copysignf(big32, ivy) : ivy;
-        ivz = fabsf(ivz) > big32 ? copysignf(big32, ivz) : ivz;
-        oix = float(oc.x) * ivx; oiy = float(oc.y) * ivy; oiz = float(oc.z) * ivz;
-        tmax32 = f32_at_least(t_max - t_shift);
+        tmax32 = f32_at_least(t_max - cr.t_shift);
         node = int32_t(rb.node4_base);
         sp = 0;
-        if constexpr (NODE == 1) {
-            // |d|^2 outside the range (or NaN: a non-finite component) and meshes that hit back faces: no culling
-            const R len2 = d.x * d.x + d.y * d.y + d.z * d.z;
-            const R len_lo = sizeof(R) == 8 ? R(1e-200) : R(1e-24), len_hi = sizeof(R) == 8 ? R(1e200) : R(1e24);
-            dirq = kNoCullDir;
-            if (cones_on != 0u && (rb.flags & RT_MESH_HIT_BACK_FACES) == 0u && len2 > len_lo && len2 < len_hi) {
-                const R sc127 = R(127) / sqrt(len2);
-                const int qx = int(rint(d.x * sc127)), qy = int(rint(d.y * sc127)), qz = int(rint(d.z * sc127));
-                dirq = (uint32_t(qx) & 0xFFu) | ((uint32_t(qy) & 0xFFu) << 8) | ((uint32_t(qz) & 0xFFu) << 16) | kNoCullDir;
-            }
-        }
+        if constexpr (NODE == 1) dirq = quantise_dir(d, cones_on != 0u && (rb.flags & RT_MESH_HIT_BACK_FACES) == 0u);
         return true;
     };
 
@@ -1118,40 +1009,18 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
             if (STATS) w_node++;
             if (has && node >= 0) {
                 if (STATS) cnt.node_visits++;
-                const float miss = __builtin_huge_valf();
                 float nr[4];
                 int32_t ch[4];
                 if constexpr (NODE == 1) {
-                    // five 16-B loads from one line; plane = org + q * cell, so t = q * (cell * iv) + (org * iv - o * iv)
+                    // five 16-B loads from one line
                     const uint4* nd = reinterpret_cast<const uint4*>(nodesq + node);
                     const uint4 h0 = nd[0], h1 = nd[1], h2 = nd[2];
                     const int4 cc = *reinterpret_cast<const int4*>(nd + 3);
-                    // a child whose triangles all face away from the ray (dir . cone > 0) counts as empty
-                    const uint4 cn = nd[4];
-                    ch[0] = __builtin_amdgcn_sdot4(int(dirq), int(cn.x), 0, false) > 0 ? kEmptyChild : cc.x;
-                    ch[1] = __builtin_amdgcn_sdot4(int(dirq), int(cn.y), 0, false) > 0 ? kEmptyChild : cc.y;
-                    ch[2] = __builtin_amdgcn_sdot4(int(dirq), int(cn.z), 0, false) > 0 ? kEmptyChild : cc.z;
-                    ch[3] = __builtin_amdgcn_sdot4(int(dirq), int(cn.w), 0, false) > 0 ? kEmptyChild : cc.w;
-                    const float ax = __uint_as_float(h0.w) * ivx, ay = __uint_as_float(h1.x) * ivy, az = __uint_as_float(h1.y) * ivz;
-                    const float bx = fmaf(__uint_as_float(h0.x), ivx, -oix), by = fmaf(__uint_as_float(h0.y), ivy, -oiy), bz = fmaf(__uint_as_float(h0.z), ivz, -oiz);
-                    // with lo <= hi the nearer plane of an axis is `lo` for a non-negative inverse direction, `hi` otherwise:
-                    // lo * iv vs hi * iv are then already ordered and the per-box min/max disappear
-                    const bool negx = ivx < 0.0f, negy = ivy < 0.0f, negz = ivz < 0.0f;
-                    const uint32_t qnx = negx ? h2.y : h1.z, qfx = negx ? h1.z : h2.y;
-                    const uint32_t qny = negy ? h2.z : h1.w, qfy = negy ? h1.w : h2.z;
-                    const uint32_t qnz = negz ? h2.w : h2.x, qfz = negz ? h2.x : h2.w;
-#pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        const float nxk = float((qnx >> (8 * k)) & 0xFFu), nyk = float((qny >> (8 * k)) & 0xFFu), nzk = float((qnz >> (8 * k)) & 0xFFu);
-                        const float fxk = float((qfx >> (8 * k)) & 0xFFu), fyk = float((qfy >> (8 * k)) & 0xFFu), fzk = float((qfz >> (8 * k)) & 0xFFu);
-                        float tn = fmaxf(fmaxf(fmaf(nxk, ax, bx), fmaf(nyk, ay, by)), fmaxf(fmaf(nzk, az, bz), 0.0f));
-                        float tf = fminf(fminf(fmaf(fxk, ax, bx), fmaf(fyk, ay, by)), fminf(fmaf(fzk, az, bz), tmax32));
-                        bool h = (tn <= tf) && ch[k] != kEmptyChild;
-                        nr[k] = h ? tn : miss;
-                    }
+                    node4q_cull_cones(dirq, nd[4], cc, ch);
+                    node4q_entries(h0, h1, h2, cr, tmax32, ch, nr);
                 } else {
                     const float4* nd = reinterpret_cast<const float4*>(nodes + node);
-                    const uint32_t nearx = ivx < 0.0f ? 3u : 0u, neary = ivy < 0.0f ? 4u : 1u, nearz = ivz < 0.0f ? 5u : 2u;  // float4 index of the near planes
+                    const uint32_t nearx = cr.negx() ? 3u : 0u, neary = cr.negy() ? 4u : 1u, nearz = cr.negz() ? 5u : 2u;  // float4 index of the near planes
                     const float4 nx = nd[nearx], fx = nd[3u - nearx];
                     const float4 ny = nd[neary], fy = nd[5u - neary];
                     const float4 nz = nd[nearz], fz = nd[7u - nearz];
@@ -1162,27 +1031,19 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
                     const float nza[4] = {nz.x, nz.y, nz.z, nz.w}, fza[4] = {fz.x, fz.y, fz.z, fz.w};
 #pragma unroll
                     for (int k = 0; k < 4; k++) {
-                        // explicit FMAs: the translation unit is built with -ffp-contract=off for the f64 parity arithmetic, but
-                        // this f32 test only culls (its rounding is inside the boxes' padding either way): 24 fewer instructions
-                        float tn = fmaxf(fmaxf(fmaf(nxa[k], ivx, -oix), fmaf(nya[k], ivy, -oiy)), fmaxf(fmaf(nza[k], ivz, -oiz), 0.0f));
-                        float tf = fminf(fminf(fmaf(fxa[k], ivx, -oix), fmaf(fya[k], ivy, -oiy)), fminf(fmaf(fza[k], ivz, -oiz), tmax32));
+                        // explicit FMAs, as in node4q_entries: 24 fewer instructions
+                        float tn = fmaxf(fmaxf(fmaf(nxa[k], cr.ivx, -cr.oix), fmaf(nya[k], cr.ivy, -cr.oiy)), fmaxf(fmaf(nza[k], cr.ivz, -cr.oiz), 0.0f));
+                        float tf = fminf(fminf(fmaf(fxa[k], cr.ivx, -cr.oix), fmaf(fya[k], cr.ivy, -cr.oiy)), fminf(fmaf(fza[k], cr.ivz, -cr.oiz), tmax32));
                         bool h = (tn <= tf) && ch[k] != kEmptyChild;
-                        nr[k] = h ? tn : miss;
+                        nr[k] = h ? tn : kNoEntry;
                     }
                 }
-                // sort the four (entry distance, child) pairs, nearest first (5 compare-exchanges)
-#define RT_CE(a, b)                                                   \
-    if (nr[a] > nr[b]) {                                              \
-        float tn_ = nr[a]; nr[a] = nr[b]; nr[b] = tn_;                \
-        int32_t tc_ = ch[a]; ch[a] = ch[b]; ch[b] = tc_;              \
-    }
-                RT_CE(0, 1) RT_CE(2, 3) RT_CE(0, 2) RT_CE(1, 3) RT_CE(1, 2)
-#undef RT_CE
-                if (nr[0] < miss) {
+                RT_SORT4_NEAREST_FIRST(nr, ch)
+                if (nr[0] < kNoEntry) {
                     // farthest first, so that the nearest remaining child is popped first
-                    if (nr[3] < miss) { stk.put(sp, ch[3], nr[3]); sp++; }
-                    if (nr[2] < miss) { stk.put(sp, ch[2], nr[2]); sp++; }
-                    if (nr[1] < miss) { stk.put(sp, ch[1], nr[1]); sp++; }
+                    if (nr[3] < kNoEntry) { stk.put(sp, ch[3], nr[3]); sp++; }
+                    if (nr[2] < kNoEntry) { stk.put(sp, ch[2], nr[2]); sp++; }
+                    if (nr[1] < kNoEntry) { stk.put(sp, ch[1], nr[1]); sp++; }
                     node = ch[0];
                 } else {
                     pop_next();
@@ -1233,26 +1094,8 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
                     }
                     R rt = Lim<R>::inf(), ru = R(0), rv = R(0);  // t = +inf: "no hit" (fails `t_max <= t` at the owner)
                     if (act) {
-                        const TriRec<R>& tr = tris[pfirst + k];
                         if (STATS) cnt.tri_tests++;
-                        V3<R> edge1 = ld3(tr.e1), edge2 = ld3(tr.e2);
-                        V3<R> ray_x_edge2 = cross(pd, edge2);
-                        R det = dot(edge1, ray_x_edge2);
-                        R dd = hit_back ? fabs(det) : det;
-                        if (!(dd < Lim<R>::eps())) {
-                            R inv_det = R(1) / det;
-                            V3<R> b = po - ld3(tr.v0);
-                            R u = dot(b, ray_x_edge2) * inv_det;
-                            if (!(u < R(0) || u > R(1))) {
-                                V3<R> b_x_edge1 = cross(b, edge1);
-                                R v = dot(pd, b_x_edge1) * inv_det;
-                                if (!(v < R(0) || u + v > R(1))) {
-                                    rt = dot(edge2, b_x_edge1) * inv_det;
-                                    ru = u;
-                                    rv = v;
-                                }
-                            }
-                        }
+                        tri_test(tris[pfirst + k], po, pd, hit_back, rt, ru, rv);
                     }
                     res_t[lane] = rt; res_u[lane] = ru; res_v[lane] = rv;
                     __builtin_amdgcn_wave_barrier();
@@ -1271,7 +1114,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
                     __builtin_amdgcn_wave_barrier();
                 }
                 if (leaf) {
-                    tmax32 = f32_at_least(t_max - t_shift);
+                    tmax32 = f32_at_least(t_max - cr.t_shift);
                     pop_next();
                 }
             }
