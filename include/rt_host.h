@@ -69,6 +69,12 @@ int32_t rth_adaptive_radius(const RtHost* host);
  * pixel - node, node type, material, triangle, t, position - INSTEAD of rendering.  rth_load rejects malformed lists and
  * pixels outside the frame.  rth_pick copies up to `capacity` (x, y) pairs and returns how many were given (0: no flag). */
 uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity);
+/* Ambient occlusion (rt_bake_visibility_hits_device): --ao=<samples>[:<max_distance>] (1 .. 4096 samples; a distance > 0,
+ * default unlimited): after the render rtrace casts the --pick ray of every pixel (rt_trace_rays_device), bakes the
+ * visibility of every first hit with the run's seed and also writes out_ao.png, grey = visibility through the sRGB curve
+ * (no ACES); the hit records stay on the device.  rth_load rejects malformed values, and --ao with --gpus > 1,
+ * --progressive, --noise-threshold or --pick; rtrace refuses a scene with volumes before it renders anything.  rth_ao returns the samples (0: no flag) and the distance (+inf: unlimited). */
+uint32_t rth_ao(const RtHost* host, double* max_distance_out);
 uint32_t rth_samples_per_pixel(const RtHost* host); /* Camera::samples_per_pixel() */
 /* Row partition of `rtrace --gpus=N` (replaces the per-thread full-frame buffers of src/camera.rs:243-255): band height
  * for `height` image rows over `n_parts` GPUs = the largest of 16, 8, 4, 2, 1 rows that gives the most loaded part as few
@@ -90,6 +96,9 @@ int rth_make_camera(uint32_t width, double aspect_ratio, double focal_length,
 int rth_tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb_out);
 /* The same followed by an 8-bit RGB PNG file (zlib deflate). */
 int rth_save_png(const char* path, const double* rgba, uint32_t w, uint32_t h);
+/* An 8-bit RGB PNG file of w*h values that are no radiance (rtrace --ao: visibilities in [0, 1]): grey = the value through
+ * the clamp, sRGB OETF and quantisation of rth_save_png, WITHOUT the ACES fit. */
+int rth_save_png_grey(const char* path, const double* values, uint32_t w, uint32_t h);
 /* An 8-bit RGB PNG file of w*h*3 bytes that are already tone-mapped (rt_accum_preview_rgb8). */
 int rth_save_png_rgb8(const char* path, const uint8_t* rgb, uint32_t w, uint32_t h);
 

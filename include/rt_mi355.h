@@ -619,6 +619,49 @@ int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out);   /* of the 
  * *n_ops_out = the program's length; nodes_out may be NULL.                                                            */
 int rt_scene_op_nodes(const RtSceneDesc* desc, int32_t* nodes_out, uint32_t capacity, uint32_t* n_ops_out);
 
+/* ---- Ambient occlusion at surface points --------------------------------------------------------
+ * For point i with position p_i and normal n_i, and sample s = 0 .. samples-1:
+ *     generator keyed (seed, 0, i, s) as a render keys (seed, replica, pixel, stratum);
+ *     w = n_i / |n_i|, (u, v) the reference's basis about w (utils.rs:17-28), d = u x + v y + w z for the reference's
+ *     cosine-weighted (x, y, z) (vec4.rs:50-61, two uniforms);
+ *     visible(i, s) = no Sphere, Plane or mesh triangle is hit by p_i + t d inside Interval(bias, max_distance), both ends
+ *     excluded: the answer rt_occluded gives for that segment, negated.
+ * out[i].visibility = (number of visible samples) / samples, exact; out[i].bent = (sum of d over the visible samples) /
+ * samples: the unnormalised bent normal, of length <= 1, 0 for a fully occluded point.  The sum is formed in a fixed order
+ * (DESIGN.md section 15), so a call's answer depends on nothing but its arguments and the scene; point i's answer does not
+ * depend on n or on the chunk size.  One kernel draws the directions in registers, walks the scene and reduces: no ray is
+ * written to memory.  A zero or non-finite normal is not an error: the result is whatever the arithmetic gives.
+ * Rules as for the ray queries: n = 0 is a no-op; a NULL array, samples outside 1 .. 4096, a bad precision, a negative or
+ * NaN bias, or max_distance <= bias (or NaN) is RT_E_INVALID; a scene with volumes is RT_E_UNSUPPORTED.  Synchronous; must
+ * not overlap a render or an update of the same scene; sees the scene as rt_scene_update left it.  rt_get_stats,
+ * rt_ray_query_stats and the tail flag are left alone.  Points run in chunks of RT_BAKE_CHUNK (environment variable,
+ * default 2^20 points); the host variant's staging buffer belongs to the scene, grows only and is freed by
+ * rt_scene_destroy.                                                                                                    */
+typedef struct RtBakeParams {    /* NULL = defaults */
+    uint32_t samples;            /* per point, 1 .. 4096; default 64 */
+    uint32_t precision;          /* RT_PRECISION_F64 / _F32 */
+    uint64_t seed;
+    double   bias;               /* t_min of every ray, default 0.001 */
+    double   max_distance;       /* t_max (directions are unit length); +inf = unlimited (default) */
+    uint32_t _reserved[4];
+} RtBakeParams;
+typedef struct RtBakeResult {    /* 32 bytes */
+    double   visibility;
+    double   bent[3];
+} RtBakeResult;
+/* positions / normals: n x 3 doubles each; out: n results. */
+int rt_bake_visibility(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtBakeParams* params,
+                       RtBakeResult* out);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernel completes. */
+int rt_bake_visibility_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals,
+                              const RtBakeParams* params, RtBakeResult* d_out, void* stream);
+/* The points are hit records on the device (rt_trace_rays_device): pos and normal of record i.  A record without RT_RAY_HIT
+ * or with RT_RAY_ENVIRONMENT has no surface point: visibility = 1, bent = 0.                                           */
+int rt_bake_visibility_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtBakeParams* params,
+                                   RtBakeResult* d_out, void* stream);
+/* Of the last bake on this scene: rays = n * samples (skipped records included), kernel_ms of the bake kernel alone. */
+int rt_bake_stats(const RtScene* scene, RtRayQueryStats* out);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

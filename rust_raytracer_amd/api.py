@@ -196,6 +196,23 @@ RtRayHit = np.dtype([("t", "<f8"), ("pos", "<f8", (3,)), ("normal", "<f8", (3,))
 assert RtRayHit.itemsize == 96
 
 
+class RtBakeParams(C.Structure):
+    _fields_ = [("samples", C.c_uint32), ("precision", C.c_uint32), ("seed", C.c_uint64), ("bias", C.c_double),
+                ("max_distance", C.c_double), ("_reserved", C.c_uint32 * 4)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "RtBakeParams":
+        p = cls(samples=64, precision=RT_PRECISION_F64, seed=0, bias=1e-3, max_distance=float("inf"))
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+
+# RtBakeResult (include/rt_mi355.h) as a numpy structured dtype: DeviceScene.bake_visibility returns an array of it
+RtBakeResult = np.dtype([("visibility", "<f8"), ("bent", "<f8", (3,))])
+assert RtBakeResult.itemsize == 32
+
+
 class RtError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"rt status {status}: {message}")
@@ -234,6 +251,8 @@ def load_host_lib() -> C.CDLL:
         lib.rth_samples_per_pixel.restype = C.c_uint32
         lib.rth_pick.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         lib.rth_pick.restype = C.c_uint32
+        lib.rth_ao.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.rth_ao.restype = C.c_uint32
         lib.rth_log.argtypes = [C.c_void_p]
         lib.rth_log.restype = C.c_char_p
         lib.rth_make_camera.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -383,6 +402,17 @@ def load_device_lib() -> C.CDLL:
                                                      C.c_void_p, C.c_void_p]),
                     ("rt_ray_query_stats", C.c_int, [C.c_void_p, C.POINTER(RtRayQueryStats)]),
                     ("rt_scene_op_nodes", C.c_int, [C.POINTER(RtSceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
+        if hasattr(lib, "rt_bake_visibility"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            for name, res, args in (
+                    ("rt_bake_visibility", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtBakeParams), C.c_void_p]),
+                    ("rt_bake_visibility_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtBakeParams),
+                                                            C.c_void_p, C.c_void_p]),
+                    ("rt_bake_visibility_hits_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtBakeParams), C.c_void_p,
+                                                                 C.c_void_p]),
+                    ("rt_bake_stats", C.c_int, [C.c_void_p, C.POINTER(RtRayQueryStats)])):
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
@@ -597,6 +627,8 @@ class HostScene:
         xy = np.zeros((lib.rth_pick(handle, None, 0), 2), dtype=np.uint32)
         lib.rth_pick(handle, xy.ctypes.data, len(xy))
         self.pick = [(int(x), int(y)) for x, y in xy]  # --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
+        dist = C.c_double()
+        self.ao = (int(lib.rth_ao(handle, C.byref(dist))), dist.value)  # --ao=<samples>[:<max_distance>]: (0, inf) without the flag
 
     @property
     def width(self) -> int:
@@ -845,6 +877,46 @@ class DeviceScene:
     def ray_query_stats(self) -> RtRayQueryStats:
         s = RtRayQueryStats()
         st = self._lib.rt_ray_query_stats(self._h, C.byref(s))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return s
+
+    def bake_visibility(self, positions, normals, samples: int = 64, seed: int = 0, bias: float = 1e-3,
+                        max_distance: float = float("inf"), precision: int = RT_PRECISION_F64) -> np.ndarray:
+        """rt_bake_visibility: ambient occlusion at surface points as an (n,) array of api.RtBakeResult: `visibility` = the
+        share of `samples` cosine-weighted directions about the normal that are free over (bias, max_distance), `bent` = the
+        sum of the free directions / samples.  positions / normals: (n, 3) or (3,) (a single normal broadcasts)."""
+        p, nr = self._rays(positions, normals)
+        out = np.zeros(len(p), dtype=RtBakeResult)
+        bp = RtBakeParams.defaults(samples=samples, seed=seed, bias=bias, max_distance=max_distance, precision=precision)
+        st = self._lib.rt_bake_visibility(self._h, len(p), p.ctypes.data, nr.ctypes.data, C.byref(bp), out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out
+
+    def bake_visibility_device(self, n: int, d_positions_ptr: int, d_normals_ptr: int, d_out_ptr: int,
+                               params: Optional[RtBakeParams] = None, stream: int = 0) -> None:
+        """rt_bake_visibility_device: n x 3 doubles each in HBM -> n RtBakeResult records (32 B each) in HBM."""
+        st = self._lib.rt_bake_visibility_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.c_void_p(d_normals_ptr or None),
+                                                 C.byref(params) if params is not None else None, C.c_void_p(d_out_ptr or None),
+                                                 C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def bake_visibility_hits_device(self, n: int, d_hits_ptr: int, d_out_ptr: int, params: Optional[RtBakeParams] = None,
+                                    stream: int = 0) -> None:
+        """rt_bake_visibility_hits_device: n RtRayHit records in HBM (trace_rays_device) -> n RtBakeResult records in HBM;
+        a miss or an environment hit gives (1, 0, 0, 0)."""
+        st = self._lib.rt_bake_visibility_hits_device(self._h, n, C.c_void_p(d_hits_ptr or None),
+                                                      C.byref(params) if params is not None else None, C.c_void_p(d_out_ptr or None),
+                                                      C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def bake_stats(self) -> RtRayQueryStats:
+        """rt_bake_stats: of the last bake (rays = n * samples); ray_query_stats() is not touched by a bake."""
+        s = RtRayQueryStats()
+        st = self._lib.rt_bake_stats(self._h, C.byref(s))
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
         return s

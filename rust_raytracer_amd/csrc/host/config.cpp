@@ -248,6 +248,17 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
                 if (colon == std::string::npos) break;
                 pos = colon + 1;
             }
+        } else if (key == "-ao") {  // new: also write out_ao.png (rt_bake_visibility_hits_device at every pixel's first hit)
+            const size_t colon = value.find(':');
+            size_t samples = 0;
+            double dist = HUGE_VAL;
+            if (!parse_usize(value.substr(0, colon), &samples) || samples < 1 || samples > 4096 ||
+                (colon != std::string::npos && (!parse_f64(value.substr(colon + 1), &dist) || !(dist > 0.0)))) {
+                *err = "Ambient occlusion must be <samples>[:<max_distance>] (1 to 4096 samples, a distance > 0)";
+                return false;
+            }
+            cfg.ao_samples = uint32_t(samples);
+            cfg.ao_max_distance = dist;
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -290,6 +301,11 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
     }
     if (cfg.denoise && cfg.gpus > 1) {
         *err = "--denoise filters the whole frame on one GPU: it cannot be combined with --gpus > 1";
+        return false;
+    }
+    if (cfg.ao_samples && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty())) {
+        *err = "--ao bakes the whole frame on one GPU after a one-shot render: it cannot be combined with --gpus > 1, --progressive, "
+               "--noise-threshold or --pick";
         return false;
     }
     if (cfg.thread_count == 0) {

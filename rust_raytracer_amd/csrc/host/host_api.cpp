@@ -96,6 +96,10 @@ uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity) {
     for (uint32_t k = 0; k < capacity && k < p.size(); k++) { xy_out[2 * k] = p[k].first; xy_out[2 * k + 1] = p[k].second; }
     return uint32_t(p.size());
 }
+uint32_t rth_ao(const RtHost* host, double* max_distance_out) {
+    if (max_distance_out) *max_distance_out = host->config.ao_max_distance;
+    return host->config.ao_samples;
+}
 double rth_noise_threshold(const RtHost* host) { return host->config.noise_threshold; }
 int32_t rth_adaptive_min(const RtHost* host) { return host->config.adaptive_min; }
 int32_t rth_adaptive_check(const RtHost* host) { return host->config.adaptive_check; }
@@ -148,6 +152,14 @@ int rth_save_png_rgb8(const char* path, const uint8_t* rgb, uint32_t w, uint32_t
     return RT_OK;
 }
 
+int rth_save_png_grey(const char* path, const double* values, uint32_t w, uint32_t h) {
+    if (!path || !values) return fail("rth_save_png_grey: NULL argument");
+    std::vector<uint8_t> rgb(size_t(w) * h * 3);
+    rth::grey_rgb8(values, w, h, rgb.data());
+    std::string err;
+    if (!rth::write_png_rgb8(path, rgb.data(), w, h, &err)) return fail(err);
+    return RT_OK;
+}
 int rth_save_png(const char* path, const double* rgba, uint32_t w, uint32_t h) {
     if (!path || !rgba) return fail("rth_save_png: NULL argument");
     std::vector<uint8_t> rgb(size_t(w) * h * 3);

@@ -1,5 +1,6 @@
 // Internal declarations shared by the host-side translation units.
 #pragma once
+#include <cmath>
 #include <memory>
 #include <optional>
 #include <string>
@@ -47,6 +48,8 @@ struct Config {
     int32_t adaptive_check = -1;
     int32_t adaptive_radius = -1;
     std::vector<std::pair<uint32_t, uint32_t>> pick;  // --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
+    uint32_t ao_samples = 0;                          // --ao=<samples>[:<max_distance>]: also write out_ao.png (0: off)
+    double ao_max_distance = HUGE_VAL;                // +inf: unlimited
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176
 
@@ -75,6 +78,7 @@ bool load_dsl_scene(const std::string& file_path, const std::string& asset_path,
 bool load_default_scene(SceneRng& rng, LoadedScene* out, std::string* log, std::string* err);
 
 void tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb);  // output.rs + aces.rs
+void grey_rgb8(const double* values, uint32_t w, uint32_t h, uint8_t* rgb);   // the sRGB curve of tonemap_rgb8 alone, no ACES
 bool write_png_rgb8(const std::string& path, const uint8_t* rgb, uint32_t w, uint32_t h, std::string* err);
 
 }  // namespace rth

@@ -8,8 +8,13 @@
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 //   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
+//   --ao=<samples>[:<max_distance>]
 // --pick=<x>,<y>[:...] renders nothing: the ray through the centre of each named pixel (no lens, no jitter) is cast with
 // rt_trace_rays and one line per pixel is printed: node, node type, material, triangle, t, position.
+// --ao=<samples>[:<max_distance>] also writes out_ao.png: the --pick ray of every pixel is cast on the device
+// (rt_trace_rays_device), the visibility of every first hit is baked with the run's seed (rt_bake_visibility_hits_device; the
+// hit records never leave the device) and written as grey through the sRGB curve, without ACES; a pixel that sees no surface is
+// white.  A scene with volumes is refused before anything is rendered.  One more console line; out.png and the other console lines are those of a run without the flag.
 // With --progressive=n the frame is rendered in passes of n replicas (rt_accum_*, one GPU); after each pass out.png shows
 // the estimate so far (tone-mapped on the device), the final out.png is the one a run without the flag writes.
 // --checkpoint saves the accumulator after every pass (<file>.tmp, then renamed) and resumes from <file> at start-up;
@@ -45,6 +50,8 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "../../../include/rt_host.h"
 
@@ -223,6 +230,57 @@ static int pick_pixels(RtHost* host) {
     return 0;
 }
 
+// --ao: visibility of every pixel's first hit (w * h values, row-major; 1 where the pixel sees no surface); false with *err
+// set on failure.
+static bool bake_ao(const RtScene* scene, const RtCameraDesc* cam, const RtRenderParams* params, uint32_t samples, double max_distance,
+                    std::vector<double>* visibility, double* mean_out, std::string* err) {
+    const uint32_t W = cam->image_width, H = cam->image_height;
+    const size_t n = size_t(W) * H;
+    std::vector<double> rays(6 * n);  // origins, then directions: the --pick ray of every pixel, row-major
+    for (uint32_t y = 0; y < H; y++)
+        for (uint32_t x = 0; x < W; x++)
+            for (int a = 0; a < 3; a++) {
+                const size_t i = size_t(y) * W + x;
+                rays[3 * i + a] = cam->position[a];
+                rays[3 * (n + i) + a] = cam->first_pixel[a] + double(x) * cam->pixel_delta_u[a] + double(y) * cam->pixel_delta_v[a] - cam->position[a];
+            }
+    void *d_rays = nullptr, *d_hits = nullptr, *d_out = nullptr;
+    std::vector<RtBakeResult> out(n);
+    auto hip_ok = [&](hipError_t e) {
+        if (e != hipSuccess) *err = std::string("--ao: ") + hipGetErrorString(e);
+        return e == hipSuccess;
+    };
+    auto rt_ok = [&](int st) {
+        if (st != RT_OK) *err = rt_last_error();
+        return st == RT_OK;
+    };
+    RtBakeParams bp{};
+    bp.samples = samples;
+    bp.precision = params->precision;
+    bp.seed = params->seed;
+    bp.bias = 0.001;
+    bp.max_distance = max_distance;
+    const bool ok = hip_ok(hipMalloc(&d_rays, rays.size() * sizeof(double))) && hip_ok(hipMalloc(&d_hits, n * sizeof(RtRayHit))) &&
+                    hip_ok(hipMalloc(&d_out, n * sizeof(RtBakeResult))) &&
+                    hip_ok(hipMemcpy(d_rays, rays.data(), rays.size() * sizeof(double), hipMemcpyHostToDevice)) &&
+                    rt_ok(rt_trace_rays_device(scene, n, static_cast<const double*>(d_rays), static_cast<const double*>(d_rays) + 3 * n,
+                                               params->precision, static_cast<RtRayHit*>(d_hits), nullptr)) &&
+                    rt_ok(rt_bake_visibility_hits_device(scene, n, static_cast<const RtRayHit*>(d_hits), &bp, static_cast<RtBakeResult*>(d_out), nullptr)) &&
+                    hip_ok(hipMemcpy(out.data(), d_out, n * sizeof(RtBakeResult), hipMemcpyDeviceToHost));
+    (void)hipFree(d_rays);
+    (void)hipFree(d_hits);
+    (void)hipFree(d_out);
+    if (!ok) return false;
+    visibility->resize(n);
+    double sum = 0.0;
+    for (size_t i = 0; i < n; i++) {
+        (*visibility)[i] = out[i].visibility;
+        sum += out[i].visibility;
+    }
+    *mean_out = n ? sum / double(n) : 0.0;
+    return true;
+}
+
 int main(int argc, char** argv) {
     using clock = std::chrono::steady_clock;
     auto t0 = clock::now();
@@ -264,9 +322,9 @@ int main(int argc, char** argv) {
         return rc;
     }
     if (!sequence.empty()) {
-        if (gpus > 1 || rth_progressive(host) || rth_noise_threshold(host) > 0.0 || rth_light_groups(host) || rth_denoise(host))
+        if (gpus > 1 || rth_progressive(host) || rth_noise_threshold(host) > 0.0 || rth_light_groups(host) || rth_denoise(host) || rth_ao(host, nullptr))
             return fail("--sequence renders whole frames on one GPU: it cannot be combined with --gpus > 1, --progressive, --noise-threshold, "
-                        "--light-groups or --denoise");
+                        "--light-groups, --denoise or --ao");
         const int rc = render_sequence(host, argc, argv, sequence, since);
         rth_destroy(host);
         return rc;
@@ -298,6 +356,15 @@ int main(int argc, char** argv) {
         lg.unlit_group = 0;
         group_frames.resize(frame.size() * lg.n_groups);
     }
+    double ao_distance = 0.0;
+    const uint32_t ao_samples = rth_ao(host, &ao_distance);  // one GPU (rth_load refuses --ao with --gpus > 1)
+    if (ao_samples) {  // refused BEFORE the render: a bake that fails afterwards would throw the frame away
+        uint32_t info = 0;
+        if (rt_scene_info(rth_scene(host), &info) != RT_OK) return fail(rt_last_error());
+        if (info & RT_SCENE_INFO_VOLUMES) return fail("--ao does not support scenes with volumes (a medium gives no deterministic surface)");
+    }
+    std::vector<double> ao_visibility;
+    double ao_mean = 0.0, ao_seconds = 0.0;
     std::vector<std::string> errors(gpus);
     std::vector<std::thread> workers;
     for (uint32_t g = 0; g < gpus; g++) {
@@ -348,6 +415,11 @@ int main(int argc, char** argv) {
                     rt_denoise(rehearsal ? 0 : int(g), frame.data(), aov.data(), W, H, &dp, denoised.data()) != RT_OK)
                     errors[g] = rt_last_error();
             }
+            if (ao_samples && errors[g].empty()) {
+                auto ta = clock::now();
+                if (!bake_ao(scene, cam, &p, ao_samples, ao_distance, &ao_visibility, &ao_mean, &errors[g])) return;
+                ao_seconds = std::chrono::duration<double>(clock::now() - ta).count();
+            }
         });
     }
     for (auto& t : workers) t.join();
@@ -378,6 +450,10 @@ int main(int argc, char** argv) {
     for (uint32_t k = 0; k < (max_groups ? lg.n_groups : 0u); k++)
         if (rth_save_png(("out_light_" + std::to_string(k) + ".png").c_str(), &group_frames[size_t(k) * frame.size()], W, H) != RT_OK) return fail(rth_last_error());
     if (!mixed.empty() && rth_save_png("out_mixed.png", mixed.data(), W, H) != RT_OK) return fail(rth_last_error());
+    if (ao_samples) {
+        if (rth_save_png_grey("out_ao.png", ao_visibility.data(), W, H) != RT_OK) return fail(rth_last_error());
+        std::printf("Ambient occlusion: %u samples per pixel, mean visibility %.6g, baked in %s\n", ao_samples, ao_mean, fmt_duration(ao_seconds).c_str());
+    }
     if (denoise && rth_save_png("out_denoised.png", denoised.data(), W, H) != RT_OK) {
         std::fprintf(stderr, "Error: %s\n", rth_last_error());
         return 1;

@@ -31,8 +31,14 @@ static inline uint8_t to_u8(double x) {
     return uint8_t(s);
 }
 
-void tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb) {
+// clamp, sRGB OETF, 8 bits: output.rs:42-49, the ONE definition of the curve (tonemap_rgb8 and grey_rgb8)
+static inline uint8_t srgb_u8(double v) {
     const double gamma = 1.0 / 2.4;  // output.rs:7
+    const double x = clamp01(v);
+    return to_u8(x < 0.0031308 ? x * 12.92 : std::pow(x, gamma) * 1.055 - 0.055);
+}
+
+void tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb) {
     for (size_t i = 0; i < size_t(w) * h; i++) {
         const double* p = rgba + 4 * i;
         double c[3], f[3], o[3];
@@ -45,12 +51,13 @@ void tonemap_rgb8(const double* rgba, uint32_t w, uint32_t h, uint8_t* rgb) {
         }
         for (int r = 0; r < 3; r++)
             o[r] = kAcesOut[3 * r] * f[0] + kAcesOut[3 * r + 1] * f[1] + kAcesOut[3 * r + 2] * f[2] + 0.0 * 0.0;
-        for (int k = 0; k < 3; k++) {
-            double x = clamp01(o[k]);
-            double s = x < 0.0031308 ? x * 12.92 : std::pow(x, gamma) * 1.055 - 0.055;  // output.rs:42-49
-            rgb[3 * i + k] = to_u8(s);
-        }
+        for (int k = 0; k < 3; k++) rgb[3 * i + k] = srgb_u8(o[k]);
     }
+}
+
+// The same curve and quantisation without the ACES fit, for values that are no radiance (a visibility in [0, 1]): grey.
+void grey_rgb8(const double* values, uint32_t w, uint32_t h, uint8_t* rgb) {
+    for (size_t i = 0; i < size_t(w) * h; i++) rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = srgb_u8(values[i]);
 }
 
 static void put_u32(std::vector<uint8_t>& v, uint32_t x) {

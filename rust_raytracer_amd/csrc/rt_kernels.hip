@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rt_aov.h"
+#include "rt_bake.h"
 #include "rt_compile.h"
 #include "rt_device.h"
 #include "rt_query.h"
@@ -679,6 +680,14 @@ struct RtScene {
         hipEvent_t ev0 = nullptr, ev1 = nullptr;
         RtRayQueryStats stats{};
     } rq;
+    // ambient-occlusion bakes (rt_bake_visibility): stats of their own (rt_ray_query_stats is not theirs to change) and the
+    // host variant's staging buffer (positions, normals and results of one chunk; grows only)
+    struct Bake {
+        void* staging = nullptr;
+        size_t staging_bytes = 0;
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        RtRayQueryStats stats{};
+    } bake;
 };
 
 namespace rt {
@@ -1641,6 +1650,81 @@ int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* ori
     return RT_OK;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Ambient-occlusion bake (include/rt_mi355.h; kernel in rt_bake.hip)
+// ---------------------------------------------------------------------------------------------
+static void bake_destroy(RtScene::Bake& b) {
+    if (b.staging) (void)hipFree(b.staging);
+    if (b.ev0) (void)hipEventDestroy(b.ev0);
+    if (b.ev1) (void)hipEventDestroy(b.ev1);
+    b = RtScene::Bake{};
+}
+
+// points per launch; the default is a guess, not a measurement
+static uint32_t bake_chunk() { return std::min<uint32_t>(1u << 26, std::max<uint32_t>(1u, env_u32("RT_BAKE_CHUNK", 1u << 20))); }
+
+// n points in chunks.  hits: the points are RtRayHit records on the device (positions = the records, normals unused);
+// host: positions / normals / out are host arrays, staged chunk by chunk.
+template <typename R>
+int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
+               const RtBakeParams& bp, RtBakeResult* out, bool host, hipStream_t stream) {
+    RtScene::Bake& b = s->bake;
+    const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
+    if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the bake kernel's LDS traversal stack");
+    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    const uint32_t chunk = bake_chunk();
+    const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
+    if (!b.ev0) HIP_TRY(hipEventCreate(&b.ev0));
+    if (!b.ev1) HIP_TRY(hipEventCreate(&b.ev1));
+    if (host)
+        if (int st = grow_buffer(b.staging, b.staging_bytes, size_t(cap) * (48 + sizeof(RtBakeResult)))) return st;
+    double total_ms = 0.0;
+    uint32_t n_chunks = 0;
+    for (uint64_t off = 0; off < n; off += chunk) {
+        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
+        BakePoints pts{};
+        pts.n = m;
+        pts.first = off;
+        RtBakeResult* d_out = out + off;
+        if (hits) {
+            const unsigned char* base = reinterpret_cast<const unsigned char*>(hits + off);
+            pts.pos = base + offsetof(RtRayHit, pos);
+            pts.nrm = base + offsetof(RtRayHit, normal);
+            pts.flags = base + offsetof(RtRayHit, flags);
+            pts.pos_stride = pts.nrm_stride = pts.flags_stride = uint32_t(sizeof(RtRayHit));
+        } else {
+            const double *d_p = positions + 3 * off, *d_n = normals + 3 * off;
+            if (host) {
+                double* st_p = static_cast<double*>(b.staging);
+                double* st_n = st_p + 3 * size_t(cap);
+                HIP_TRY(hipMemcpyAsync(st_p, d_p, size_t(m) * 24, hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(st_n, d_n, size_t(m) * 24, hipMemcpyHostToDevice, stream));
+                d_p = st_p;
+                d_n = st_n;
+                d_out = reinterpret_cast<RtBakeResult*>(st_n + 3 * size_t(cap));
+            }
+            pts.pos = reinterpret_cast<const unsigned char*>(d_p);
+            pts.nrm = reinterpret_cast<const unsigned char*>(d_n);
+            pts.pos_stride = pts.nrm_stride = 24u;
+        }
+        HIP_TRY(hipEventRecord(b.ev0, stream));
+        HIP_TRY(bake_visibility_launch<R>(ds.view, pts, bp.samples, bp.seed, bp.bias, bp.max_distance, levels, cones_on, d_out, stream));
+        HIP_TRY(hipEventRecord(b.ev1, stream));
+        if (host) HIP_TRY(hipMemcpyAsync(out + off, d_out, size_t(m) * sizeof(RtBakeResult), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
+        total_ms += ms;
+        n_chunks++;
+    }
+    b.stats = RtRayQueryStats{};
+    b.stats.kernel_ms = total_ms;
+    b.stats.rays = n * bp.samples;
+    b.stats.n_chunks = n_chunks;
+    b.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+    return RT_OK;
+}
+
 static int validate_render_args(const RtCameraDesc* camera, const RtRenderParams* params) {
     if (params->sqrt_spt == 0 || params->thread_count == 0) return set_err(RT_E_INVALID, "sqrt_spt and thread_count must be positive");
     if (params->band_rows != 0 && params->n_parts > 1 && params->part >= params->n_parts) return set_err(RT_E_INVALID, "part >= n_parts");
@@ -2009,6 +2093,7 @@ void rt_scene_destroy(RtScene* s) {
     s->f32.reset();
     for (rt::RefitMesh& rm : s->refit) rm.release();
     rt::rq_destroy(s->rq);
+    rt::bake_destroy(s->bake);
     rt::wf_release_pool(s->wf);
     if (s->wf.mesh_spill) (void)hipFree(s->wf.mesh_spill);
     if (s->wf.d_ctr) (void)hipFree(s->wf.d_ctr);
@@ -3300,6 +3385,51 @@ int rt_occluded_device(const RtScene* scene, uint64_t n, const double* d_origins
 int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out) {
     if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_ray_query_stats: NULL argument");
     *out = scene->rq.stats;
+    return RT_OK;
+}
+
+// ---- Ambient-occlusion bake (rt_bake.hip) -------------------------------------------------------------------------------
+static int bake_impl(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
+                     const RtBakeParams* params, RtBakeResult* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    RtBakeParams bp{};
+    if (params) {
+        bp = *params;
+    } else {
+        bp.samples = 64;
+        bp.precision = RT_PRECISION_F64;
+        bp.bias = 0.001;
+        bp.max_distance = HUGE_VAL;
+    }
+    RtScene* s = nullptr;
+    if (int st = ray_query_begin(scene, bp.precision, who, &s)) return st;
+    if (bp.samples < 1 || bp.samples > 4096) return set_err(RT_E_INVALID, std::string(who) + ": samples must be in 1 .. 4096");
+    if (!(bp.bias >= 0.0)) return set_err(RT_E_INVALID, std::string(who) + ": bias must be >= 0");
+    if (!(bp.max_distance > bp.bias)) return set_err(RT_E_INVALID, std::string(who) + ": max_distance must be greater than bias");
+    if (n == 0) return RT_OK;
+    if (!out || (hits ? false : (!positions || !normals))) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    if (bp.precision == RT_PRECISION_F32) return bake_typed<float>(s, *s->f32, n, positions, normals, hits, bp, out, host, st);
+    return bake_typed<double>(s, *s->f64, n, positions, normals, hits, bp, out, host, st);
+}
+
+int rt_bake_visibility(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtBakeParams* params,
+                       RtBakeResult* out) {
+    return bake_impl(scene, n, positions, normals, nullptr, params, out, true, nullptr, "rt_bake_visibility");
+}
+int rt_bake_visibility_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals,
+                              const RtBakeParams* params, RtBakeResult* d_out, void* stream) {
+    return bake_impl(scene, n, d_positions, d_normals, nullptr, params, d_out, false, stream, "rt_bake_visibility_device");
+}
+int rt_bake_visibility_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtBakeParams* params,
+                                   RtBakeResult* d_out, void* stream) {
+    using namespace rt;
+    if (n != 0 && !d_hits) return set_err(RT_E_INVALID, "rt_bake_visibility_hits_device: NULL array");
+    return bake_impl(scene, n, nullptr, nullptr, d_hits, params, d_out, false, stream, "rt_bake_visibility_hits_device");
+}
+int rt_bake_stats(const RtScene* scene, RtRayQueryStats* out) {
+    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_bake_stats: NULL argument");
+    *out = scene->bake.stats;
     return RT_OK;
 }
 int rt_scene_op_nodes(const RtSceneDesc* desc, int32_t* nodes_out, uint32_t capacity, uint32_t* n_ops_out) {

@@ -1,7 +1,7 @@
 // rt_traverse.h — the steps of a BVH search, each written ONCE: the clamped inverse direction, the exact triangle test, the
 // two-child node step, the f32 culling ray, and the decode, cone cull and ordering of a 4-wide node's children.  This is the only
 // place that reads a BvhNode4q / MeshNode4qc header or a TriRec for intersection; a change of a node format starts here.
-// Users: mesh_traverse (rt_device.h), k_wf_intersect, group_search and k_wf_mesh (rt_wavefront.h), mesh_any_hit (rt_query.hip).
+// Users: mesh_traverse (rt_device.h), k_wf_intersect, group_search and k_wf_mesh (rt_wavefront.h), mesh_any_hit (rt_query.h).
 // The stacks and the loops around the steps stay with the kernels: they differ for measured reasons given there.
 //
 // Included by rt_device.h behind V3 / Lim / Ray, which everything here is written in.
