@@ -755,21 +755,50 @@ __global__ void __launch_bounds__(256, VOL ? 2 : (GROUPS ? 3 : RT_PRIMS_WAVES)) 
 // The LDS part is addressed through an LDS-qualified pointer: with plain (generic) pointers hipcc merges the two stores of
 // `put` into one store through a selected pointer and then fails in the backend ("Illegal instruction detected:
 // V_CMP_NE_U32 0, src_shared_base") once a node step has more than a few puts (the 8-wide node has seven).
+// Round 6: the lane's stack pointer IS an address.  The LDS part grows DOWNWARDS, one level kLevel = 2048 B below the other, and
+// `top` = (lds_levels - entries) * kLevel + 8 * threadIdx.x is the LDS byte address of the top entry while that lies in LDS:
+//   top >= empty (= lds_levels * kLevel)   the stack is empty
+//   top >= 0                               the top entry (and every one below it) is in LDS
+//   top >= 3 * kLevel                      three more entries fit the LDS part: the pushes of a node step are stores at
+//                                          top' + 0 / 2048 / 4096 from the ONE new top' (push3), without a spill test
+//   top < 0                                -(top >> 11) entries are in the spill part
+// A wave takes the forms without a spill test (push3, pop_lds) when a ballot says that every lane taking part qualifies, and
+// put / get otherwise; both keep the same entries in the same order.
+typedef __attribute__((address_space(3))) char LdsByte;
 struct MeshStack {
-    LdsU64* lds;       // + threadIdx.x
+    static constexpr int32_t kLevel = 256 * int32_t(sizeof(uint2));
+    static constexpr int kLevelShift = 11;  // top >> kLevelShift (arithmetic) = lds_levels - entries
+    static_assert(kLevel == 1 << kLevelShift, "a level is one entry per lane of the workgroup");
+    LdsByte* lds;      // the workgroup's LDS stack
     uint2* spill;      // + global lane
-    int lds_levels;
+    int32_t empty;     // lds_levels * kLevel
     uint32_t spill_stride;
-    RT_DEV void put(int sp, int32_t child, float dist) const {
-        if (sp < lds_levels) lds[sp * 256] = (static_cast<unsigned long long>(__float_as_uint(dist)) << 32) | uint32_t(child);
-        else spill[size_t(sp - lds_levels) * spill_stride] = make_uint2(uint32_t(child), __float_as_uint(dist));
+    RT_DEV static unsigned long long pack(int32_t child, float dist) { return (static_cast<unsigned long long>(__float_as_uint(dist)) << 32) | uint32_t(child); }
+    RT_DEV LdsU64& at(int32_t addr) const { return *(LdsU64*)(lds + addr); }
+    RT_DEV void put(int32_t& top, int32_t child, float dist) const {
+        if (top >= kLevel) at(top - kLevel) = pack(child, dist);
+        else spill[size_t(uint32_t(-(top >> kLevelShift))) * spill_stride] = make_uint2(uint32_t(child), __float_as_uint(dist));
+        top -= kLevel;
     }
-    RT_DEV uint2 get(int sp) const {
-        if (sp < lds_levels) {
-            unsigned long long e = lds[sp * 256];
-            return make_uint2(uint32_t(e), uint32_t(e >> 32));
+    RT_DEV uint2 get(int32_t& top) const {  // the stack is not empty
+        uint2 r;
+        if (top >= 0) {
+            unsigned long long e = at(top);
+            r = make_uint2(uint32_t(e), uint32_t(e >> 32));
+        } else {
+            r = spill[size_t(uint32_t(-(top >> kLevelShift)) - 1u) * spill_stride];
         }
-        return spill[size_t(sp - lds_levels) * spill_stride];
+        top += kLevel;
+        return r;
+    }
+    // Children ch[1 .. n) of a sorted node step, n >= 2, farthest deepest; the caller has checked top >= 3 * kLevel.
+    RT_DEV void push3(int32_t& top, const int32_t* ch, const float* nr, float no_entry) const {
+        top -= kLevel * (1 + int32_t(nr[2] < no_entry) + int32_t(nr[3] < no_entry));
+        at(top) = pack(ch[1], nr[1]);
+        if (nr[2] < no_entry) {
+            at(top + kLevel) = pack(ch[2], nr[2]);
+            if (nr[3] < no_entry) at(top + 2 * kLevel) = pack(ch[3], nr[3]);
+        }
     }
 };
 
@@ -800,7 +829,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     // cones_on: 0 = every ray gets the direction word that culls nothing (RT_WF_CONES=0, the A/B control)
     extern __shared__ uint2 lds_stack2[];
     MeshStack stk;
-    stk.lds = (LdsU64*)(lds_stack2 + threadIdx.x);
+    stk.lds = (LdsByte*)lds_stack2;
     // wave-private LDS behind the stack: pair table (512 x u16) + one result slot per lane (t, u, v) + staged queue entries
     const uint32_t lane = threadIdx.x & 63u;
     char* wave_area = reinterpret_cast<char*>(lds_stack2 + size_t(lds_levels) * 256) + (threadIdx.x >> 6) * kMeshWaveLds<R>;
@@ -810,7 +839,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     R* res_v = res_u + 64;
     uint32_t* stage = reinterpret_cast<uint32_t*>(res_v + 64);
     stk.spill = spill + (size_t(blockIdx.x) * blockDim.x + threadIdx.x);
-    stk.lds_levels = lds_levels;
+    stk.empty = lds_levels * MeshStack::kLevel;
     stk.spill_stride = gridDim.x * blockDim.x;
     const uint32_t n = *n_ptr;
     const R t_lo = R(0.001);
@@ -847,7 +876,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     CullRay<R> cr{};         // origin moved onto the mesh box
     float tmax32 = 0.f;      // t_max in its terms
     int32_t node = 0;        // >= 0 inner node, < 0 leaf
-    int sp = 0;
+    int32_t top = 0;         // stack pointer, see MeshStack
     uint32_t dirq = kNoCullDir;  // NODE == 1: quantise_dir of d
 
     // The lane has finished every mesh of its path: the closest triangle, if one beat the other primitives' hit, is the path's hit.
@@ -869,39 +898,42 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
     // bound); a lane whose stack runs empty has finished this mesh and goes on to the path's next mesh op.
     // (The end-of-mesh bookkeeping stands BEHIND the pop loop: inside it, it was if-converted into every trip of the loop -
     // 3.3 G culled pops per headline step - and cost the kernel 12 % more vector instructions than the single-mesh form.)
-    auto pop_next = [&]() {
-        if constexpr (MULTI) {
-            bool found_entry = false;
-            while (sp > 0) {
-                sp--;
-                const uint2 e = stk.get(sp);
-                if (__uint_as_float(e.y) <= tmax32) {
-                    node = int32_t(e.x);
-                    found_entry = true;
-                    break;
-                }
-                if (STATS) l_culled++;
+    // pop_lds: the form for a stack that lies in LDS as a whole: no spill test, one read per entry.  (Two levels per round trip,
+    // one ds_read2st64_b64 with the cull tests as selects, was 40 instructions per trip against 26 and did not pay beyond the
+    // spread on the headline: profiles/mesh_stack/ab_c4_single_read_pop.txt.)
+    auto pop_lds = [&]() -> bool {
+        while (top < stk.empty) {
+            const unsigned long long e = stk.at(top);
+            top += MeshStack::kLevel;
+            if (__uint_as_float(uint32_t(e >> 32)) <= tmax32) {
+                node = int32_t(uint32_t(e));
+                return true;
             }
-            if (!found_entry) {
-                has = false;
+            if (STATS) l_culled++;
+        }
+        return false;
+    };
+    auto pop_any = [&]() -> bool {
+        while (top < stk.empty) {
+            const uint2 e = stk.get(top);
+            if (__uint_as_float(e.y) <= tmax32) {
+                node = int32_t(e.x);
+                return true;
+            }
+            if (STATS) l_culled++;
+        }
+        return false;
+    };
+    auto pop_next = [&]() {
+        const bool found_entry = __ballot(top < 0) == 0ull ? pop_lds() : pop_any();
+        if (!found_entry) {
+            has = false;
+            if constexpr (MULTI) {
                 mcur = (mcur & 0x7FFFFFFFu) + 1u;
                 if ((mcur & 0x7FFFu) < n_mesh_ops) pending = true;
                 else finish_path();
-            }
-        } else {
-            for (;;) {
-                if (sp == 0) {
-                    has = false;
-                    finish_path();
-                    return;
-                }
-                sp--;
-                const uint2 e = stk.get(sp);
-                if (__uint_as_float(e.y) <= tmax32) {
-                    node = int32_t(e.x);
-                    return;
-                }
-                if (STATS) l_culled++;
+            } else {
+                finish_path();
             }
         }
     };
@@ -933,7 +965,7 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
         }
         tmax32 = f32_at_least(t_max - cr.t_shift);
         node = int32_t(rb.node4_base);
-        sp = 0;
+        top = stk.empty + int32_t(threadIdx.x * uint32_t(sizeof(uint2)));
         if constexpr (NODE == 1) dirq = quantise_dir(d, cones_on != 0u && (rb.flags & RT_MESH_HIT_BACK_FACES) == 0u);
         return true;
     };
@@ -1040,10 +1072,14 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
                 }
                 RT_SORT4_NEAREST_FIRST(nr, ch)
                 if (nr[0] < kNoEntry) {
-                    // farthest first, so that the nearest remaining child is popped first
-                    if (nr[3] < kNoEntry) { stk.put(sp, ch[3], nr[3]); sp++; }
-                    if (nr[2] < kNoEntry) { stk.put(sp, ch[2], nr[2]); sp++; }
-                    if (nr[1] < kNoEntry) { stk.put(sp, ch[1], nr[1]); sp++; }
+                    // farthest first, so that the nearest remaining child is popped first (sorted: the entered ones are ch[0 .. n))
+                    if (__ballot(top < 3 * MeshStack::kLevel) == 0ull) {
+                        if (nr[1] < kNoEntry) stk.push3(top, ch, nr, kNoEntry);
+                    } else {
+                        if (nr[3] < kNoEntry) stk.put(top, ch[3], nr[3]);
+                        if (nr[2] < kNoEntry) stk.put(top, ch[2], nr[2]);
+                        if (nr[1] < kNoEntry) stk.put(top, ch[1], nr[1]);
+                    }
                     node = ch[0];
                 } else {
                     pop_next();
