@@ -26,12 +26,17 @@ template <typename R> struct Lim;
 template <> struct Lim<double> {
     static RT_DEV double inf() { return __builtin_huge_val(); }
     static RT_DEV double max() { return DBL_MAX; }
-    static RT_DEV double eps() { return DBL_EPSILON; }  // f64::EPSILON (mesh.rs:77, plane.rs:74)
+    static RT_DEV double eps() { return DBL_EPSILON; }
+    static RT_DEV double det_eps() { return DBL_EPSILON; }  // f64::EPSILON (mesh.rs:77, plane.rs:74)
 };
 template <> struct Lim<float> {
     static RT_DEV float inf() { return __builtin_huge_valf(); }
     static RT_DEV float max() { return FLT_MAX; }
-    static RT_DEV float eps() { return FLT_EPSILON; }
+    static RT_DEV float eps() { return FLT_EPSILON; }  // relative rounding slack (span_misses, the group search)
+    // The determinant rule of tri_test / plane_test is an ABSOLUTE threshold on |d| * 2 area * cos in object space, directions
+    // are not normalised and transforms scale them: FLT_EPSILON there dropped every small or briefly-aimed-at triangle that
+    // the reference hits.  The reference's own constant, rounded: a normal float, 1 / det stays finite.
+    static RT_DEV float det_eps() { return float(DBL_EPSILON); }
 };
 
 template <typename R> RT_DEV R pi() { return R(3.14159265358979323846264338327950288); }
@@ -249,7 +254,7 @@ template <typename R, bool INCL = false> RT_DEV bool plane_test(const PlanePrim<
     V3<R> normal = ld3(p.normal);
     R dot_ray_normal = dot(normal, ray.d);
     R dd = p.backface ? fabs(dot_ray_normal) : -dot_ray_normal;
-    if (dd < Lim<R>::eps()) return false;
+    if (dd < Lim<R>::det_eps()) return false;
     V3<R> corner = ld3(p.corner);
     R hit_t = dot(normal, corner - ray.o) / dot_ray_normal;
     if (hit_t <= t_lo || (INCL ? t_hi < hit_t : t_hi <= hit_t)) return false;

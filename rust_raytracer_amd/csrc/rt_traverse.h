@@ -29,7 +29,7 @@ template <typename R> RT_DEV bool tri_test(const TriRec<R>& tr, V3<R> o, V3<R> d
     V3<R> ray_x_edge2 = cross(d, edge2);
     R det = dot(edge1, ray_x_edge2);
     R dd = hit_back ? fabs(det) : det;
-    if (!(dd < Lim<R>::eps())) {
+    if (!(dd < Lim<R>::det_eps())) {
         R inv_det = R(1) / det;
         V3<R> b = o - ld3(tr.v0);
         R uu = dot(b, ray_x_edge2) * inv_det;
