@@ -416,6 +416,9 @@ def load_device_lib() -> C.CDLL:
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
+        if hasattr(lib, "rt_debug_live_resources"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
+            lib.rt_debug_live_resources.restype = C.c_int
         lib.rt_last_error.argtypes = []
         lib.rt_last_error.restype = C.c_char_p
         _device_lib = lib
@@ -444,6 +447,17 @@ def scene_mesh_stats(desc) -> dict:
         raise RtError(st, lib.rt_last_error().decode())
     return dict(zip(("triangles", "bvh2_nodes", "bvh4_nodes", "bvh2_depth", "bvh4_stack", "ops", "rebuilt_groups", "rebuilt_prims"),
                     [int(x) for x in out]))
+
+
+def live_resources() -> tuple:
+    """rt_debug_live_resources: (live device buffers, their bytes, live pinned host buffers, live events + streams) that the
+    library holds in this process."""
+    lib = load_device_lib()
+    out = (C.c_uint64 * 4)()
+    st = lib.rt_debug_live_resources(out)
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return tuple(int(x) for x in out)
 
 
 def handout_replay(n: int, waves: int, order, policy=None, out=None) -> tuple:

@@ -6,6 +6,7 @@
 #include <cstddef>
 
 #include "../../include/rt_mi355.h"
+#include "rt_owned.h"
 #include "rt_scene.h"
 
 namespace rt {
@@ -21,13 +22,13 @@ hipError_t aov_launch(const SceneView<R>& sc, const CameraView<R>& cam, const Pa
 // Device scratch of the denoiser for up to `npix` pixels: the packed guides and one colour buffer (the output buffer is
 // the other one of the ping-pong pair).
 struct DenoiseScratch {
-    float4* guide_az = nullptr;  // albedo rgb, depth
-    float4* guide_nc = nullptr;  // normal xyz, coverage
-    double* color = nullptr;     // 4 doubles per pixel
+    DevBuf<float4> guide_az;  // albedo rgb, depth
+    DevBuf<float4> guide_nc;  // normal xyz, coverage
+    DevBuf<double> color;     // 4 doubles per pixel
     size_t npix = 0;
 };
-hipError_t denoise_scratch_reserve(DenoiseScratch& s, size_t npix);
-void denoise_scratch_release(DenoiseScratch& s);
+// RT_OK, or RT_E_NOMEM / RT_E_DEVICE with the message set; a failure leaves the scratch empty.
+int denoise_scratch_reserve(DenoiseScratch& s, size_t npix);
 
 // d_rgba (w*h*4 doubles) guided by d_aov (w*h*8) -> d_out (w*h*4, may be d_rgba); dp already validated.  Enqueued on
 // `stream`; the caller synchronises.

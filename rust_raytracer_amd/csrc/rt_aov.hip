@@ -180,25 +180,16 @@ __global__ void __launch_bounds__(256) k_dn_atrous(const double* __restrict__ in
     out[4 * p + 3] = c3;
 }
 
-void denoise_scratch_release(DenoiseScratch& s) {
-    if (s.guide_az) (void)hipFree(s.guide_az);
-    if (s.guide_nc) (void)hipFree(s.guide_nc);
-    if (s.color) (void)hipFree(s.color);
+int denoise_scratch_reserve(DenoiseScratch& s, size_t npix) {
+    if (s.npix >= npix && s.color) return RT_OK;
     s = DenoiseScratch{};
-}
-
-hipError_t denoise_scratch_reserve(DenoiseScratch& s, size_t npix) {
-    if (s.npix >= npix && s.color) return hipSuccess;
-    denoise_scratch_release(s);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&s.guide_az), npix * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s.guide_nc), npix * sizeof(float4));
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s.color), npix * 4 * sizeof(double));
-    if (e != hipSuccess) {
-        denoise_scratch_release(s);
-        return e;
-    }
-    s.npix = npix;
-    return hipSuccess;
+    const char* nomem = "denoiser scratch does not fit in device memory";
+    int st = s.guide_az.reserve(npix * sizeof(float4), nomem);
+    if (st == RT_OK) st = s.guide_nc.reserve(npix * sizeof(float4), nomem);
+    if (st == RT_OK) st = s.color.reserve(npix * 4 * sizeof(double), nomem);
+    if (st != RT_OK) s = DenoiseScratch{};
+    else s.npix = npix;
+    return st;
 }
 
 hipError_t denoise_launch(const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams& dp,
@@ -209,15 +200,15 @@ hipError_t denoise_launch(const double* d_rgba, const double* d_aov, uint32_t w,
     if (n == 0) return d_out == d_rgba ? hipSuccess : hipMemcpyAsync(d_out, d_rgba, npix * 4 * sizeof(double), hipMemcpyDeviceToDevice, stream);
     if (scratch.npix < npix || !scratch.color) return hipErrorInvalidValue;
     // ping-pong between the scratch colour buffer and d_out, arranged so that iteration n - 1 writes d_out
-    auto buf = [&](uint32_t i) { return (n - i) % 2 == 0 ? d_out : scratch.color; };
+    auto buf = [&](uint32_t i) { return (n - i) % 2 == 0 ? d_out : scratch.color.get(); };
     const uint32_t demod = (dp.flags & RT_DENOISE_DEMODULATE) ? 1u : 0u;
     hipLaunchKernelGGL(k_dn_prep, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, d_rgba, d_aov, uint64_t(npix), demod,
-                       scratch.guide_az, scratch.guide_nc, buf(0));
+                       scratch.guide_az.get(), scratch.guide_nc.get(), buf(0));
     const float sc = float(dp.sigma_color), sn = float(dp.sigma_normal), sa = float(dp.sigma_albedo), sz = float(dp.sigma_depth);
     const dim3 grid((w + 15u) / 16u, (h + 15u) / 16u);
     for (uint32_t i = 0; i < n; i++) {
         const float den_c = sc * sc * std::ldexp(1.0f, -int(i));  // sigma_c^2 2^-i (exact scaling by a power of two)
-        hipLaunchKernelGGL(k_dn_atrous, grid, dim3(256), 0, stream, buf(i), scratch.guide_az, scratch.guide_nc, w, h, 1u << i,
+        hipLaunchKernelGGL(k_dn_atrous, grid, dim3(256), 0, stream, buf(i), scratch.guide_az.get(), scratch.guide_nc.get(), w, h, 1u << i,
                            den_c, sn * sn, sa * sa, sz, (i + 1 == n) ? demod : 0u, buf(i + 1));
     }
     return hipGetLastError();

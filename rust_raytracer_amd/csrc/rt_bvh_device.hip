@@ -25,6 +25,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "rt_bvh.h"
+#include "rt_owned.h"
 #include "rt_scene.h"
 
 namespace rt {
@@ -171,15 +172,13 @@ __global__ void k_fit_boxes(const Box6* __restrict__ tri_boxes, const uint32_t* 
     }
 }
 
+// n elements (at least one) of scratch that live until build_bvh_device returns
 template <typename T>
-struct DevBuf {
-    T* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(size_t n, std::string* err) {
-        BVH_TRY(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)));
-        return true;
-    }
-};
+bool dev_alloc(DevBuf<T>& b, size_t n, std::string* err) {
+    if (b.reserve(std::max<size_t>(n, 1) * sizeof(T)) == RT_OK) return true;
+    *err = "device BVH build: " + g_err;
+    return false;
+}
 
 }  // namespace
 
@@ -199,38 +198,38 @@ bool build_bvh_device(const double* positions, uint32_t n_positions, const uint3
     DevBuf<int> d_parent_int, d_parent_leaf;
     DevBuf<unsigned int> d_arrived;
     DevBuf<char> d_temp;
-    if (!d_pos.alloc(size_t(n_positions) * 3, err) || !d_tri.alloc(size_t(n) * 3, err) || !d_ids.alloc(n, err) || !d_ids_sorted.alloc(n, err) ||
-        !d_tri_boxes.alloc(n, err) || !d_node_boxes.alloc(n, err) || !d_leaf_boxes.alloc(n, err) || !d_mesh_box.alloc(6, err) ||
-        !d_codes.alloc(n, err) || !d_codes_sorted.alloc(n, err) || !d_children.alloc(n, err) || !d_ranges.alloc(n, err) ||
-        !d_parent_int.alloc(n, err) || !d_parent_leaf.alloc(n, err) || !d_arrived.alloc(n, err))
+    if (!dev_alloc(d_pos, size_t(n_positions) * 3, err) || !dev_alloc(d_tri, size_t(n) * 3, err) || !dev_alloc(d_ids, n, err) || !dev_alloc(d_ids_sorted, n, err) ||
+        !dev_alloc(d_tri_boxes, n, err) || !dev_alloc(d_node_boxes, n, err) || !dev_alloc(d_leaf_boxes, n, err) || !dev_alloc(d_mesh_box, 6, err) ||
+        !dev_alloc(d_codes, n, err) || !dev_alloc(d_codes_sorted, n, err) || !dev_alloc(d_children, n, err) || !dev_alloc(d_ranges, n, err) ||
+        !dev_alloc(d_parent_int, n, err) || !dev_alloc(d_parent_leaf, n, err) || !dev_alloc(d_arrived, n, err))
         return false;
-    BVH_TRY(hipMemcpy(d_pos.p, positions, size_t(n_positions) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    BVH_TRY(hipMemcpy(d_tri.p, tri_pos, size_t(n) * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
+    BVH_TRY(hipMemcpy(d_pos.get(), positions, size_t(n_positions) * 3 * sizeof(double), hipMemcpyHostToDevice));
+    BVH_TRY(hipMemcpy(d_tri.get(), tri_pos, size_t(n) * 3 * sizeof(uint32_t), hipMemcpyHostToDevice));
     unsigned long long init_box[6];
     for (int a = 0; a < 3; a++) { init_box[a] = ~0ull; init_box[3 + a] = 0ull; }
-    BVH_TRY(hipMemcpy(d_mesh_box.p, init_box, sizeof init_box, hipMemcpyHostToDevice));
-    BVH_TRY(hipMemset(d_arrived.p, 0, size_t(n) * sizeof(unsigned int)));
+    BVH_TRY(hipMemcpy(d_mesh_box.get(), init_box, sizeof init_box, hipMemcpyHostToDevice));
+    BVH_TRY(hipMemset(d_arrived.get(), 0, size_t(n) * sizeof(unsigned int)));
     const dim3 block(256), grid((n + 255) / 256);
-    hipLaunchKernelGGL(k_tri_bounds, grid, block, 0, 0, d_pos.p, d_tri.p, uint32_t(n), d_tri_boxes.p, d_mesh_box.p);
-    hipLaunchKernelGGL(k_morton, grid, block, 0, 0, d_tri_boxes.p, uint32_t(n), d_mesh_box.p, d_codes.p, d_ids.p);
+    hipLaunchKernelGGL(k_tri_bounds, grid, block, 0, 0, d_pos.get(), d_tri.get(), uint32_t(n), d_tri_boxes.get(), d_mesh_box.get());
+    hipLaunchKernelGGL(k_morton, grid, block, 0, 0, d_tri_boxes.get(), uint32_t(n), d_mesh_box.get(), d_codes.get(), d_ids.get());
     size_t temp_bytes = 0;
-    BVH_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_codes.p, d_codes_sorted.p, d_ids.p, d_ids_sorted.p, size_t(n), 0, 63, hipStream_t(0)));
-    if (!d_temp.alloc(temp_bytes, err)) return false;
-    BVH_TRY(rocprim::radix_sort_pairs(d_temp.p, temp_bytes, d_codes.p, d_codes_sorted.p, d_ids.p, d_ids_sorted.p, size_t(n), 0, 63, hipStream_t(0)));
-    hipLaunchKernelGGL(k_radix_tree, grid, block, 0, 0, d_codes_sorted.p, n, d_children.p, d_ranges.p, d_parent_int.p, d_parent_leaf.p);
-    hipLaunchKernelGGL(k_fit_boxes, grid, block, 0, 0, d_tri_boxes.p, d_ids_sorted.p, n, d_children.p, d_parent_int.p, d_parent_leaf.p,
-                       d_node_boxes.p, d_leaf_boxes.p, d_arrived.p);
+    BVH_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, d_codes.get(), d_codes_sorted.get(), d_ids.get(), d_ids_sorted.get(), size_t(n), 0, 63, hipStream_t(0)));
+    if (!dev_alloc(d_temp, temp_bytes, err)) return false;
+    BVH_TRY(rocprim::radix_sort_pairs(d_temp.get(), temp_bytes, d_codes.get(), d_codes_sorted.get(), d_ids.get(), d_ids_sorted.get(), size_t(n), 0, 63, hipStream_t(0)));
+    hipLaunchKernelGGL(k_radix_tree, grid, block, 0, 0, d_codes_sorted.get(), n, d_children.get(), d_ranges.get(), d_parent_int.get(), d_parent_leaf.get());
+    hipLaunchKernelGGL(k_fit_boxes, grid, block, 0, 0, d_tri_boxes.get(), d_ids_sorted.get(), n, d_children.get(), d_parent_int.get(), d_parent_leaf.get(),
+                       d_node_boxes.get(), d_leaf_boxes.get(), d_arrived.get());
     BVH_TRY(hipGetLastError());
     BVH_TRY(hipDeviceSynchronize());
 
     std::vector<int2> children(size_t(n) - 1), ranges(size_t(n) - 1);
     std::vector<Box6> node_boxes(size_t(n) - 1), leaf_boxes(n);
     std::vector<uint32_t> order(n);
-    BVH_TRY(hipMemcpy(children.data(), d_children.p, children.size() * sizeof(int2), hipMemcpyDeviceToHost));
-    BVH_TRY(hipMemcpy(ranges.data(), d_ranges.p, ranges.size() * sizeof(int2), hipMemcpyDeviceToHost));
-    BVH_TRY(hipMemcpy(node_boxes.data(), d_node_boxes.p, node_boxes.size() * sizeof(Box6), hipMemcpyDeviceToHost));
-    BVH_TRY(hipMemcpy(leaf_boxes.data(), d_leaf_boxes.p, leaf_boxes.size() * sizeof(Box6), hipMemcpyDeviceToHost));
-    BVH_TRY(hipMemcpy(order.data(), d_ids_sorted.p, order.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    BVH_TRY(hipMemcpy(children.data(), d_children.get(), children.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    BVH_TRY(hipMemcpy(ranges.data(), d_ranges.get(), ranges.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    BVH_TRY(hipMemcpy(node_boxes.data(), d_node_boxes.get(), node_boxes.size() * sizeof(Box6), hipMemcpyDeviceToHost));
+    BVH_TRY(hipMemcpy(leaf_boxes.data(), d_leaf_boxes.get(), leaf_boxes.size() * sizeof(Box6), hipMemcpyDeviceToHost));
+    BVH_TRY(hipMemcpy(order.data(), d_ids_sorted.get(), order.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
 
     // ---- host: fold small subtrees into leaves, number the rest depth-first (root = 0) ----
     auto count_of = [&](int ref) { return ref >= 0 ? ranges[size_t(ref)].y - ranges[size_t(ref)].x + 1 : 1; };

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -12,12 +13,14 @@
 #include <new>
 #include <string>
 #include <type_traits>
+#include <variant>
 #include <vector>
 
 #include "rt_aov.h"
 #include "rt_bake.h"
 #include "rt_compile.h"
 #include "rt_device.h"
+#include "rt_owned.h"
 #include "rt_query.h"
 #include "rt_refit.h"
 #include "rt_wavefront.h"
@@ -168,40 +171,31 @@ __global__ void k_trace_sample(SceneView<R> sc, CameraView<R> cam, ParamsView<R>
 // ---------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------
-static thread_local std::string g_err;
-static int set_err(int st, const std::string& msg) {
-    g_err = msg;
-    return st;
-}
-#define HIP_TRY(expr)                                                                              \
-    do {                                                                                           \
-        hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
-            return set_err(RT_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));        \
-    } while (0)
-
+// Device copies of host tables; every table is a buffer of its own, so that rt_scene_update can move the mesh tables over.
 struct DeviceBuffers {
-    std::vector<void*> allocs;
+    std::vector<DevBuf<char>> allocs;
     uint64_t uploaded_bytes = 0;
     // takes over an allocation of `from` (rt_scene_update: the mesh tables stay where they are)
     void adopt(DeviceBuffers& from, const void* p) {
-        auto it = std::find(from.allocs.begin(), from.allocs.end(), const_cast<void*>(p));
+        auto it = std::find_if(from.allocs.begin(), from.allocs.end(), [p](const DevBuf<char>& b) { return b.get() == p; });
         if (it == from.allocs.end()) return;
-        allocs.push_back(*it);
+        allocs.push_back(std::move(*it));
         from.allocs.erase(it);
     }
-    ~DeviceBuffers() {
-        for (void* p : allocs) (void)hipFree(p);
+    // `bytes` of device memory that live as long as this object
+    template <typename T> int alloc(size_t bytes, T** out) {
+        allocs.emplace_back();
+        if (int st = allocs.back().reserve(bytes)) return st;
+        *out = reinterpret_cast<T*>(allocs.back().get());
+        return RT_OK;
     }
     template <typename T> int upload(const std::vector<T>& v, const T** out) {
         *out = nullptr;
-        size_t bytes = (v.empty() ? 1 : v.size()) * sizeof(T);
-        void* p = nullptr;
-        HIP_TRY(hipMalloc(&p, bytes));
-        allocs.push_back(p);
+        T* p = nullptr;
+        if (int st = alloc((v.empty() ? 1 : v.size()) * sizeof(T), &p)) return st;
         if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         uploaded_bytes += v.size() * sizeof(T);
-        *out = static_cast<const T*>(p);
+        *out = p;
         return RT_OK;
     }
 };
@@ -213,6 +207,7 @@ template <typename R, size_t N> void cast_arr(R (&dst)[N], const double (&src)[N
 // Scene tables in arithmetic type R on the device.
 template <typename R>
 struct DeviceScene {
+    using Real = R;
     DeviceBuffers buf;
     SceneView<R> view{};
 
@@ -611,17 +606,38 @@ static std::string update_mismatch_message(const std::string& field) {
     return "scene update: the description has another structure than the scene (first difference: " + field + ")";
 }
 
+// The arrays of a WfPool<R> and the queues over its slots (build_pool).  A render works on a pair of them (the second one,
+// 3/4 of the slots, is the destination of the first tail compaction, after which the two take turns), a ray query on the
+// first of a pair; the arithmetic type a workspace's pools were built for is the alternative its variant holds.
+template <typename R>
+struct PathPool {
+    WfPool<R> view{};                             // array bases and capacity, as the kernels take them
+    WfPool<R>* dev = nullptr;                     // the same descriptor in device memory (k_wf_shade re-reads the array bases from it)
+    uint32_t* queue[2] = {nullptr, nullptr};
+    uint32_t* mesh_queue = nullptr;
+    std::vector<DevBuf<char>> owned;              // what all of the above point at
+};
+template <typename R> using PoolPair = std::array<PathPool<R>, 2>;
+using AnyPools = std::variant<std::monostate, PoolPair<float>, PoolPair<double>>;
+
+// What run_chunks keeps between calls: the host variants' staging buffer (inputs and results of one chunk; grows only) and
+// the pair of events that times a chunk.
+struct ChunkStage {
+    DevBuf<char> staging;
+    Event ev0, ev1;
+};
+
 }  // namespace rt
 
 struct RtScene {
-    int device = 0;
+    int device = -1;  // set once rt_scene_create has chosen it; nothing is allocated before
     rt::CompiledScene compiled;
-    // Both precisions are materialised lazily on first use.
+    // Both precisions are materialised lazily on first use (with_tables).
     std::unique_ptr<rt::DeviceScene<double>> f64;
     std::unique_ptr<rt::DeviceScene<float>> f32;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    rt::DeviceCounters* d_counters = nullptr;
+    rt::Stream stream;
+    rt::Event ev0, ev1;
+    rt::DevBuf<rt::DeviceCounters> d_counters;
     RtRenderStats stats{};
     int32_t* tail_flag = nullptr;  // rt_scene_set_tail_flag: set to 1 when a render stops filling the GPU (frame pipelining)
     uint64_t content_digest = 0;   // of everything the description points at (rt::scene_digest): checkpoints name their scene by it
@@ -632,62 +648,36 @@ struct RtScene {
     std::vector<rt::RefitMesh> refit;
     // wavefront pipeline resources (allocated on first use, reused between renders)
     struct Wavefront {
-        uint32_t capacity = 0;
-        size_t real_size = 0;          // sizeof(R) the pool was allocated for
-        std::vector<void*> allocs;
-        void* pool_view = nullptr;     // host copy of WfPool<R>
-        void* pool_dev = nullptr;      // the same descriptor in device memory (k_wf_shade re-reads the array bases from it)
-        void* pool2_view = nullptr;    // the second pool, 3/4 of the slots: destination of the first tail compaction (k_wf_compact),
-        void* pool2_dev = nullptr;     // after which the two take turns
-        uint32_t* queue[2] = {nullptr, nullptr};
-        uint32_t* mesh_queue = nullptr;
-        void* mesh_spill = nullptr;        // k_wf_mesh: stack levels beyond the LDS part
-        size_t mesh_spill_bytes = 0;
-        rt::WfCounters* d_ctr = nullptr;
-        rt::WfCounters* h_ctr = nullptr;   // pinned
-        double* sample_L = nullptr;
-        size_t sample_L_bytes = 0;
-        double* acc = nullptr;
-        size_t acc_bytes = 0;
+        rt::AnyPools pools;
+        rt::DevBuf<uint2> mesh_spill;      // k_wf_mesh: stack levels beyond the LDS part
+        rt::DevBuf<rt::WfCounters> d_ctr;
+        rt::PinnedBuf<rt::WfCounters> h_ctr;
+        rt::DevBuf<double> sample_L, acc;
         // light-group renders (rt_render_light_groups): group byte per sample, running sums per (group, pixel), terminal table
-        uint8_t* sample_G = nullptr;
-        size_t sample_G_bytes = 0;
-        double* acc_g = nullptr;
-        size_t acc_g_bytes = 0;
-        uint8_t* lg_table = nullptr;
-        size_t lg_table_bytes = 0;
-        hipEvent_t ev_res[2] = {nullptr, nullptr};
-        std::vector<hipEvent_t> events;
+        rt::DevBuf<uint8_t> sample_G, lg_table;
+        rt::DevBuf<double> acc_g;
+        rt::Event ev_res[2];
+        std::vector<rt::Event> events;
     } wf;
     // ray queries (rt_trace_rays / rt_occluded): a workspace of their own, allocated by the first query, so that a query
     // between two progressive passes never makes wf_ensure re-allocate the render's pool
     struct Query {
-        uint32_t capacity = 0;         // slots of the pool (grows only)
-        size_t real_size = 0;          // sizeof(R) the pool was allocated for
-        std::vector<void*> allocs;     // the pool's arrays, queue, mesh queue
-        void* pool_view = nullptr;     // host copy of WfPool<R>: ray and hit-record arrays only (the search kernels read nothing else)
-        uint32_t* queue = nullptr;
-        uint32_t* mesh_queue = nullptr;
-        void* mesh_spill = nullptr;
-        size_t mesh_spill_bytes = 0;
-        rt::WfCounters* d_ctr = nullptr;
-        rt::WfCounters* h_ctr = nullptr;   // pinned
-        int32_t* op_node = nullptr;        // CompiledScene::op_node / ::tri_order of generation `tables_generation`
-        uint32_t* tri_order = nullptr;
+        rt::AnyPools pools;                // [0]: ray and hit-record arrays only (the search kernels read nothing else); grows only
+        rt::DevBuf<uint2> mesh_spill;
+        rt::DevBuf<rt::WfCounters> d_ctr;
+        rt::PinnedBuf<rt::WfCounters> h_ctr;
+        rt::DevBuf<int32_t> op_node;       // CompiledScene::op_node / ::tri_order of generation `tables_generation`
+        rt::DevBuf<uint32_t> tri_order;
         uint64_t tables_generation = ~0ull;
-        void* staging = nullptr;           // host variants: rays, intervals and results of one chunk
-        size_t staging_bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        rt::ChunkStage stage;
         RtRayQueryStats stats{};
     } rq;
-    // ambient-occlusion bakes (rt_bake_visibility): stats of their own (rt_ray_query_stats is not theirs to change) and the
-    // host variant's staging buffer (positions, normals and results of one chunk; grows only)
+    // ambient-occlusion bakes (rt_bake_visibility): stats of their own (rt_ray_query_stats is not theirs to change)
     struct Bake {
-        void* staging = nullptr;
-        size_t staging_bytes = 0;
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        rt::ChunkStage stage;
         RtRayQueryStats stats{};
     } bake;
+    ~RtScene() { if (device >= 0) (void)hipSetDevice(device); }  // before the members go: the owners do not switch devices
 };
 
 namespace rt {
@@ -743,7 +733,7 @@ int render_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const 
     HIP_TRY(hipEventRecord(s->ev0, stream));
     // full-feature variant: texture interpreter (lerp / image / noise / channel / normal maps) and volumes
     const bool tex = s->compiled.needs_tex_interpreter || !s->compiled.volumes.empty();
-#define RT_LAUNCH_MEGA(ST, TX) hipLaunchKernelGGL((k_megakernel<R, ST, TX>), grid, block, lds, stream, ds.view, cv, pv, d_out, s->d_counters, t_first, n)
+#define RT_LAUNCH_MEGA(ST, TX) hipLaunchKernelGGL((k_megakernel<R, ST, TX>), grid, block, lds, stream, ds.view, cv, pv, d_out, s->d_counters.get(), t_first, n)
     if (p.collect_stats) { if (tex) RT_LAUNCH_MEGA(true, true); else RT_LAUNCH_MEGA(true, false); }
     else { if (tex) RT_LAUNCH_MEGA(false, true); else RT_LAUNCH_MEGA(false, false); }
 #undef RT_LAUNCH_MEGA
@@ -792,20 +782,6 @@ static uint32_t env_u32(const char* name, uint32_t dflt) {
     const char* v = std::getenv(name);
     if (!v || !*v) return dflt;
     return uint32_t(std::strtoul(v, nullptr, 10));
-}
-
-// A grow-only device buffer (pointer and size of a workspace): at least `need` bytes afterwards, contents not kept.  The
-// old buffer is released and the pair cleared BEFORE hipMalloc, so a failed allocation leaves (NULL, 0) behind and never a
-// size without its memory.
-template <typename T>
-static int grow_buffer(T*& p, size_t& bytes, size_t need) {
-    if (bytes >= need) return RT_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), need));
-    bytes = need;
-    return RT_OK;
 }
 
 // ---- Kernel selection.  Taking a kernel's address instantiates it, so each selector names exactly the variants the
@@ -988,88 +964,61 @@ void launch_intersect(const SearchSetup<R>& su, const DeviceScene<R>& ds, const 
                        su.refill_min, su.handout.mode, su.handout.left256, su.handout.left128);
 }
 
-// Releases the path pool and its queues and marks the pool as absent, so that a failed re-allocation can never be
-// mistaken for a valid pool by a later render (and nothing is freed twice by rt_scene_destroy).
-static void wf_release_pool(RtScene::Wavefront& w) {
-    w.capacity = 0;
-    w.real_size = 0;
-    for (void* p : w.allocs) (void)hipFree(p);
-    w.allocs.clear();
-    ::operator delete(w.pool_view);
-    w.pool_view = nullptr;
-    ::operator delete(w.pool2_view);
-    w.pool2_view = nullptr;
-    if (w.pool_dev) (void)hipFree(w.pool_dev);
-    w.pool_dev = nullptr;
-    if (w.pool2_dev) (void)hipFree(w.pool2_dev);
-    w.pool2_dev = nullptr;
-    for (int q = 0; q < 2; q++) {
-        if (w.queue[q]) (void)hipFree(w.queue[q]);
-        w.queue[q] = nullptr;
+// Builds `pl` for `capacity` slots: rays and hit records, `full`: + the rest of the path state and the descriptor's device
+// copy; n_queues queues and (with any queue) the mesh queue.  Every allocation maps out-of-memory to RT_E_NOMEM with the
+// message `nomem`; a failure leaves an empty pool behind and never a half-built one.  RT_WF_FAKE_OOM_ABOVE (tests): above
+// that many slots the LAST allocation fails like hipErrorOutOfMemory, with everything before it in place.
+template <typename R>
+int build_pool(PathPool<R>& pl, uint32_t capacity, bool full, int n_queues, const char* nomem) {
+    pl = PathPool<R>{};
+    WfPool<R>& v = pl.view;
+    v.capacity = capacity;
+    std::vector<std::pair<void**, size_t>> want;  // where the pointer goes, bytes
+    auto per_slot = [&](auto** at, size_t each) { want.emplace_back(reinterpret_cast<void**>(at), size_t(capacity) * each); };
+    for (R** r : {&v.ox, &v.oy, &v.oz, &v.dx, &v.dy, &v.dz, &v.ht, &v.hu, &v.hv}) per_slot(r, sizeof(R));
+    per_slot(&v.hpc, 4);
+    per_slot(&v.htri, 4);
+    if (full) {
+        for (R** r : {&v.tr, &v.tg, &v.tb}) per_slot(r, sizeof(R));
+        per_slot(&v.rng, 8);
+        per_slot(&v.sample, 8);
+        per_slot(&v.depth, 4);
     }
-    if (w.mesh_queue) (void)hipFree(w.mesh_queue);
-    w.mesh_queue = nullptr;
+    for (int q = 0; q < n_queues; q++) per_slot(&pl.queue[q], 4);
+    if (n_queues) per_slot(&pl.mesh_queue, 4);
+    if (full) want.emplace_back(reinterpret_cast<void**>(&pl.dev), sizeof(WfPool<R>));
+    const uint32_t limit = env_u32("RT_WF_FAKE_OOM_ABOVE", 0);
+    int st = RT_OK;
+    for (size_t i = 0; i < want.size() && st == RT_OK; i++) {
+        pl.owned.emplace_back();
+        if (limit && capacity > limit && i + 1 == want.size()) st = set_err(RT_E_NOMEM, std::string(nomem) + " (RT_WF_FAKE_OOM_ABOVE)");
+        else st = pl.owned.back().reserve(want[i].second, nomem);
+        *want[i].first = pl.owned.back().get();
+    }
+    if (st == RT_OK && full)
+        if (const hipError_t e = hipMemcpy(pl.dev, &v, sizeof v, hipMemcpyHostToDevice); e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    if (st != RT_OK) pl = PathPool<R>{};
+    return st;
 }
 
+// The render's pools of exactly `capacity` slots in R, its counters and its timing events.
 template <typename R>
 int wf_ensure(RtScene* s, uint32_t capacity) {
     RtScene::Wavefront& w = s->wf;
-    if (w.capacity == capacity && w.real_size == sizeof(R)) return RT_OK;
-    if (const uint32_t limit = env_u32("RT_WF_FAKE_OOM_ABOVE", 0); limit && capacity > limit)  // tests: the out-of-memory path of render_wavefront
-        return set_err(RT_E_NOMEM, "path pool does not fit in device memory (RT_WF_FAKE_OOM_ABOVE)");
-    wf_release_pool(w);
-    auto* pool = new WfPool<R>();
-    w.pool_view = pool;
-    pool->capacity = capacity;
-    auto* pool2 = new WfPool<R>();
-    w.pool2_view = pool2;
-    pool2->capacity = std::max<uint32_t>(64u, uint32_t((uint64_t(capacity) * 3 + 3) / 4));  // a compaction happens below RT_WF_COMPACT_PCT <= 75 % of the addressed slots
-    auto alloc = [&](size_t bytes, void** out) -> int {
-        const hipError_t e = hipMalloc(out, bytes);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();  // not sticky: the caller retries with a smaller pool
-            return set_err(RT_E_NOMEM, "path pool does not fit in device memory");
-        }
-        HIP_TRY(e);
-        w.allocs.push_back(*out);
-        return RT_OK;
-    };
-    auto build_pool = [&](WfPool<R>* pl) -> int {
-        const size_t cap = pl->capacity;
-        R** reals[] = {&pl->ox, &pl->oy, &pl->oz, &pl->dx, &pl->dy, &pl->dz, &pl->tr, &pl->tg, &pl->tb, &pl->ht, &pl->hu, &pl->hv};
-        for (R** r : reals)
-            if (int st = alloc(cap * sizeof(R), reinterpret_cast<void**>(r))) return st;
-        if (int st = alloc(cap * 8, reinterpret_cast<void**>(&pl->rng))) return st;
-        if (int st = alloc(cap * 8, reinterpret_cast<void**>(&pl->sample))) return st;
-        if (int st = alloc(cap * 4, reinterpret_cast<void**>(&pl->depth))) return st;
-        if (int st = alloc(cap * 4, reinterpret_cast<void**>(&pl->hpc))) return st;
-        if (int st = alloc(cap * 4, reinterpret_cast<void**>(&pl->htri))) return st;
-        return RT_OK;
-    };
-    auto build = [&]() -> int {
-        if (int st = build_pool(pool)) return st;
-        if (int st = build_pool(pool2)) return st;
-        HIP_TRY(hipMalloc(&w.pool2_dev, sizeof(WfPool<R>)));
-        HIP_TRY(hipMemcpy(w.pool2_dev, pool2, sizeof(WfPool<R>), hipMemcpyHostToDevice));
-        for (int q = 0; q < 2; q++) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.queue[q]), size_t(capacity) * 4));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.mesh_queue), size_t(capacity) * 4));
-        HIP_TRY(hipMalloc(&w.pool_dev, sizeof(WfPool<R>)));
-        HIP_TRY(hipMemcpy(w.pool_dev, pool, sizeof(WfPool<R>), hipMemcpyHostToDevice));
-        if (!w.d_ctr) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&w.d_ctr), sizeof(WfCounters)));
-        if (!w.h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&w.h_ctr), sizeof(WfCounters)));
-        if (w.events.empty()) {
-            w.events.resize(136);  // 4 per iteration, up to 32 iterations between host checks, + 2 for the stand-alone prims launch
-            for (auto& e : w.events) e = nullptr;
-            for (auto& e : w.events) HIP_TRY(hipEventCreate(&e));
-        }
-        return RT_OK;
-    };
-    if (int st = build()) {
-        wf_release_pool(w);  // e.g. out of memory half way: leave no half-built pool behind
-        return st;
-    }
-    w.capacity = capacity;
-    w.real_size = sizeof(R);
+    const auto* have = std::get_if<PoolPair<R>>(&w.pools);
+    if (have && (*have)[0].view.capacity == capacity) return RT_OK;
+    w.pools = std::monostate{};  // released before the new ones are built; a failure below leaves the pool absent
+    const char* nomem = "path pool does not fit in device memory";
+    if (int st = w.d_ctr.reserve(sizeof(WfCounters), nomem)) return st;
+    if (int st = w.h_ctr.reserve(sizeof(WfCounters), nomem)) return st;
+    w.events.resize(136);  // 4 per iteration, up to 32 iterations between host checks, + 2 for the stand-alone prims launch
+    for (Event& e : w.events)
+        if (int st = e.ensure()) return st;
+    PoolPair<R> pp;
+    if (int st = build_pool(pp[0], capacity, true, 2, nomem)) return st;
+    // a compaction happens below RT_WF_COMPACT_PCT <= 75 % of the addressed slots
+    if (int st = build_pool(pp[1], std::max<uint32_t>(64u, uint32_t((uint64_t(capacity) * 3 + 3) / 4)), true, 0, nomem)) return st;
+    w.pools = std::move(pp);
     return RT_OK;
 }
 
@@ -1092,6 +1041,145 @@ struct LightGroupPass {
     double* d_groups_out = nullptr;
 };
 
+// Pool size of a render.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
+// dependent fetches) and the streaming kernels run better in few large launches, so fewer, larger launches win; against that
+// stands the tail: the pool is what drains at the end of a replica group, over ~20 ever smaller iterations.  Round 2 (tail at
+// 2.5 x its work's worth): best size 64 M slots at 1.44 G samples, growing with the square root of the work.  Round 3's tail
+// compaction (k_wf_compact) halved the tail's price and moved the optimum up - Msamples/s, same box (profiles/r03/tail_compaction.txt):
+//   C4 1.44 G samples:  64 M 1256-1287, 96 M 1289-1293, 128 M 1312-1332, 160 M 1319-1338, 192 M 1326-1337, 256 M 1300-1311
+//   C3 0.96 G: 52 M 4841, 80 M 4907, 96 M 4977, 112 M 4890      C1 0.25 G: 26 M 1962, 48 M 2028, 64 M 2061-2079, 96 M 2120, 128 M 2129
+//   C2 0.16 G (no mesh): 16 M 1681, 22 M 1692, 32 M 1668, 44 M 1670      one of 8 ranks' share of C4: 23 M 157 ms, 46 M / 92 M 151, 128 M 153
+// -> 128 M slots at 1.44 G samples, with the square root of the work below it (within 1-3 % of each workload's best).
+// Sized from the whole frame (T replicas), not from this call's n: progressive passes of any size keep the same pool.
+static uint32_t wf_pool_capacity(uint32_t strata, uint64_t npix_frame, uint32_t T) {
+    const double total_samples = double(strata) * double(npix_frame) * double(T);  // the frame's, also for a sparse pass: one pool for all passes
+    double c = 134217728.0 * std::sqrt(total_samples / 1.44e9);
+    c = std::fmin(std::fmax(c, 1048576.0), 134217728.0);
+    uint32_t capacity = env_u32("RT_WF_POOL", uint32_t(c) & ~0xFFFFFu);
+    if (capacity > (1u << 28)) capacity = 1u << 28;  // the kernels address pool arrays through 32-bit byte offsets (rt_wavefront.h, at())
+    if (uint64_t(capacity) > uint64_t(strata) * npix_frame * T) capacity = uint32_t(uint64_t(strata) * npix_frame * T);
+    return std::max<uint32_t>(capacity, 64u);
+}
+
+// The per-sample radiance buffer of a call that renders n replicas of per_replica samples each: *group_out = replicas per
+// group, as many as the memory budget allows, and every buffer the resolve kernels need for that (grow only).
+static int wf_plan_samples(RtScene::Wavefront& w, uint64_t per_replica, uint64_t npix, uint32_t n, bool adaptive, const LightGroupPass* lg,
+                           hipStream_t stream, uint32_t* group_out) {
+    size_t free_b = 0, total_b = 0;
+    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+    size_t budget = size_t(env_u32("RT_WF_SAMPLE_GB", 64)) << 30;
+    size_t avail = free_b + w.sample_L.bytes() + (lg ? w.sample_G.bytes() : size_t(0));
+    if (budget > avail / 2) budget = avail / 2;
+    uint64_t bytes_per_replica = per_replica * (lg ? 25ull : 24ull);  // radiance, + the group byte of a light-group render
+    uint32_t group = uint32_t(std::min<uint64_t>(n, std::max<uint64_t>(1, budget / bytes_per_replica)));
+    group = (n + (n + group - 1) / group - 1) / ((n + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
+    if (bytes_per_replica > avail) return set_err(RT_E_NOMEM, "per-sample radiance buffer of one replica does not fit in device memory");
+    if (int st = w.sample_L.reserve(size_t(per_replica) * 24 * group)) return st;
+    if (lg) {
+        if (int st = w.sample_G.reserve(size_t(per_replica) * group)) return st;
+        if (int st = w.acc_g.reserve(group < n ? size_t(npix) * 24 * lg->n_groups : size_t(0))) return st;
+        const size_t need_t = size_t(lg->n_materials) + 2;
+        if (int st = w.lg_table.reserve(need_t)) return st;
+        HIP_TRY(hipMemcpyAsync(w.lg_table, lg->table, need_t, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // the host table may be the caller's stack
+        for (Event& e : w.ev_res)
+            if (int st = e.ensure()) return st;
+    }
+    if (group < n && !adaptive)  // several groups: running sums between them (adaptive: every group resolves into the accumulator's sums)
+        if (int st = w.acc.reserve(size_t(npix) * 24)) return st;
+    *group_out = group;
+    return RT_OK;
+}
+
+// RT_WF_TRACE=n (debug): the queue and the first n slots of the pool after an iteration, on stderr.
+template <typename R>
+int wf_trace_dump(const WfPool<R>& pool, uint32_t first, const uint32_t* queue, uint32_t n_in, uint32_t iteration) {
+    const uint32_t n = std::min<uint32_t>(std::min(first, pool.capacity), env_u32("RT_WF_TRACE", 0));
+    std::vector<R> a[12];
+    R* src[12] = {pool.ox, pool.oy, pool.oz, pool.dx, pool.dy, pool.dz, pool.tr, pool.tg, pool.tb, pool.ht, pool.hu, pool.hv};
+    for (int k = 0; k < 12; k++) { a[k].resize(n); HIP_TRY(hipMemcpy(a[k].data(), src[k], n * sizeof(R), hipMemcpyDeviceToHost)); }
+    std::vector<uint64_t> rngs(n), smp(n);
+    std::vector<uint32_t> dep(n), qn(first);
+    std::vector<int32_t> hpc(n);
+    HIP_TRY(hipMemcpy(rngs.data(), pool.rng, n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(smp.data(), pool.sample, n * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dep.data(), pool.depth, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hpc.data(), pool.hpc, n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(qn.data(), queue, size_t(n_in) * 4, hipMemcpyDeviceToHost));
+    std::fprintf(stderr, "[wf trace] iteration %u: %u paths queued:", iteration, n_in);
+    for (uint32_t k = 0; k < n_in && k < 64; k++) std::fprintf(stderr, " %u", qn[k]);
+    std::fprintf(stderr, "\n");
+    for (uint32_t k = 0; k < n; k++)
+        std::fprintf(stderr, "  slot %u sample %llu depth %u o %.17g %.17g %.17g d %.17g %.17g %.17g thr %.6g %.6g %.6g hit t %.17g pc %d rng %016llx\n", k,
+                     (unsigned long long)smp[k], dep[k], double(a[0][k]), double(a[1][k]), double(a[2][k]), double(a[3][k]), double(a[4][k]),
+                     double(a[5][k]), double(a[6][k]), double(a[7][k]), double(a[8][k]), double(a[9][k]), hpc[k], (unsigned long long)rngs[k]);
+    return RT_OK;
+}
+
+// What the loop of render_wavefront counts and times.  phase_ms: HIP-event sums per kernel, 4 events per iteration (before
+// prims / intersect, after it, after the mesh kernel, after shade); slot 0 = prims, 1 = traversal (mesh or combined
+// intersect), 2 = shade.
+struct WfTally {
+    double phase_ms[3];
+    double resolve_ms;           // light-group renders: both resolve kernels
+    uint32_t search_launches;    // stand-alone k_wf_prims / k_wf_intersect launches
+    uint32_t iterations, n_groups, n_compactions;
+};
+
+// RtRenderStats of a wavefront render that has ended (ev0 .. ev1 of the scene span it), and its debug lines.
+template <typename R>
+int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, const LightGroupPass* lg, bool fusable, uint64_t samples) {
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
+    DeviceCounters hc{};
+    HIP_TRY(hipMemcpy(&hc, s->d_counters, sizeof hc, hipMemcpyDeviceToHost));
+    RtRenderStats& st = s->stats;
+    st = RtRenderStats{};
+    st.kernel_ms = ms;
+    st.traversal_kernel_ms = su.prims_only ? 0.0 : ty.phase_ms[1];
+    st.prims_kernel_ms = (su.split || su.prims_only) ? ty.phase_ms[0] : 0.0;
+    st.shade_kernel_ms = ty.phase_ms[2];
+    st.n_launches = ty.search_launches;
+    st.n_iterations = ty.iterations;
+    st.n_replica_groups = ty.n_groups;
+    st.n_tail_compactions = ty.n_compactions;
+    if (lg && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
+        std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", lg->n_groups, ty.resolve_ms,
+                     s->wf.sample_G.bytes(), s->wf.acc_g.bytes());
+    if (su.stats && su.split && env_u32("RT_WF_DEBUG", 0)) {
+        std::fprintf(stderr, "[k_wf_mesh] grid %u workgroups, %d per CU, %zu B of LDS each; hand-out mode %u, 256 / 128 entries above %u / %u left per wave\n",
+                     su.isect_blocks, su.blocks_per_cu, su.lds_mesh, su.handout.mode, su.handout.left256, su.handout.left128);
+        auto pct = [](unsigned long long lanes, unsigned long long waves) { return waves ? 100.0 * double(lanes) / (64.0 * double(waves)) : 0.0; };
+        std::fprintf(stderr,
+                     "[k_wf_mesh] rays %llu  node code: %llu wave iterations, %.1f %% lanes active;  triangle code: %llu, %.1f %%;  "
+                     "refill: %llu, %.1f %%;  stack entries culled on pop %llu\n",
+                     hc.mesh_rays, hc.node_wave_iters, pct(hc.node_visits, hc.node_wave_iters), hc.tri_wave_iters,
+                     pct(hc.tri_tests, hc.tri_wave_iters), hc.refill_wave_iters, pct(hc.refill_lanes, hc.refill_wave_iters), hc.pops_culled);
+    }
+    st.pipeline_used = RT_PIPELINE_WAVEFRONT;
+    st.samples = samples;
+    st.rays = hc.rays;
+    st.mesh_rays = hc.mesh_rays;
+    st.node_visits = hc.node_visits;
+    st.tri_tests = hc.tri_tests;
+    st.prim_tests = hc.prim_tests;
+    st.bytes_node = su.split ? (su.node_kind == 0 ? sizeof(BvhNode4f) : sizeof(BvhNode4q)) : sizeof(BvhNode<R>);
+    st.bytes_tri = sizeof(TriRec<R>);
+    st.bytes_attr = sizeof(TriAttr<R>);
+    // path state moved by the DOMINANT kernel per ray it traverses: ray (6 R) + bound/op read (R + 4)
+    // + hit written when a triangle wins (3 R + 8) + queue entry (4)
+    st.bytes_state = 6 * sizeof(R) + sizeof(R) + 4 + 3 * sizeof(R) + 8 + 4;
+    // k_wf_prims per ray: ray in (6 R), closest hit out (3 R + 8); k_wf_shade per ray: ray + hit + throughput + rng + depth +
+    // sample index in, ray + throughput + rng + depth out (a path that ends writes 24 B of radiance instead and restarts)
+    st.bytes_state_prims = 6 * sizeof(R) + 3 * sizeof(R) + 8;
+    st.bytes_state_shade = (6 + 3 + 3) * sizeof(R) + 8 + 8 + 4 + 8 + (6 + 3) * sizeof(R) + 8 + 4;
+    // the lean renders of this scene run the search inside k_wf_shade: its bytes per ray are then the kernel's (a counting
+    // render is never fused, but it reports what the timed renders beside it move)
+    if (fusable) st.bytes_state_shade += st.bytes_state_prims;
+    if (!su.split) st.mesh_rays = hc.rays;  // combined kernel: every ray's state passes through it
+    return RT_OK;
+}
+
 template <typename R>
 int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
                      uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr,
@@ -1108,26 +1196,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     const uint32_t T = p.thread_count;
     const uint32_t t_end = t_first + n;
     const uint64_t per_replica = uint64_t(strata) * npix;
-    // Pool size.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
-    // dependent fetches) and the streaming kernels run better in few large launches, so fewer, larger launches win; against that
-    // stands the tail: the pool is what drains at the end of a replica group, over ~20 ever smaller iterations.  Round 2 (tail at
-    // 2.5 x its work's worth): best size 64 M slots at 1.44 G samples, growing with the square root of the work.  Round 3's tail
-    // compaction (k_wf_compact) halved the tail's price and moved the optimum up - Msamples/s, same box (profiles/r03/tail_compaction.txt):
-    //   C4 1.44 G samples:  64 M 1256-1287, 96 M 1289-1293, 128 M 1312-1332, 160 M 1319-1338, 192 M 1326-1337, 256 M 1300-1311
-    //   C3 0.96 G: 52 M 4841, 80 M 4907, 96 M 4977, 112 M 4890      C1 0.25 G: 26 M 1962, 48 M 2028, 64 M 2061-2079, 96 M 2120, 128 M 2129
-    //   C2 0.16 G (no mesh): 16 M 1681, 22 M 1692, 32 M 1668, 44 M 1670      one of 8 ranks' share of C4: 23 M 157 ms, 46 M / 92 M 151, 128 M 153
-    // -> 128 M slots at 1.44 G samples, with the square root of the work below it (within 1-3 % of each workload's best).
-    // Sized from the whole frame (T replicas), not from this call's n: progressive passes of any size keep the same pool.
-    uint32_t capacity;
-    {
-        const double total_samples = double(strata) * double(npix_frame) * double(T);  // the frame's, also for a sparse pass: one pool for all passes
-        double c = 134217728.0 * std::sqrt(total_samples / 1.44e9);
-        c = std::fmin(std::fmax(c, 1048576.0), 134217728.0);
-        capacity = env_u32("RT_WF_POOL", uint32_t(c) & ~0xFFFFFu);
-    }
-    if (capacity > (1u << 28)) capacity = 1u << 28;  // the kernels address pool arrays through 32-bit byte offsets (rt_wavefront.h, at())
-    if (uint64_t(capacity) > uint64_t(strata) * npix_frame * T) capacity = uint32_t(uint64_t(strata) * npix_frame * T);
-    if (capacity < 64) capacity = 64;
+    uint32_t capacity = wf_pool_capacity(strata, npix_frame, T);
     // the pool is a matter of speed, not of correctness: when device memory is short (other scenes of a frame pipeline, other
     // processes on the card) a smaller one renders the same frame
     for (;;) {
@@ -1137,43 +1206,21 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         capacity = std::max<uint32_t>(1u << 20, (capacity / 2) & ~0xFFFFFu);
     }
     RtScene::Wavefront& w = s->wf;
-    WfPool<R> pool = *static_cast<WfPool<R>*>(w.pool_view);   // the pool the kernels are working on (changes at a tail compaction)
-    const WfPool<R> pool_a = pool, pool_b = *static_cast<WfPool<R>*>(w.pool2_view);
-    const void* pool_dev_cur = w.pool_dev;
+    const PoolPair<R>& pools = std::get<PoolPair<R>>(w.pools);
+    const WfPool<R> pool_a = pools[0].view, pool_b = pools[1].view;
+    WfPool<R> pool = pool_a;  // the pool the kernels are working on (changes at a tail compaction)
+    const WfPool<R>* pool_dev_cur = pools[0].dev;
+    uint32_t* const queue[2] = {pools[0].queue[0], pools[0].queue[1]};
+    uint32_t* const mesh_queue = pools[0].mesh_queue;
 
-    // per-sample radiance buffer: as many replicas per group as the memory budget allows
-    size_t free_b = 0, total_b = 0;
-    HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-    size_t budget = size_t(env_u32("RT_WF_SAMPLE_GB", 64)) << 30;
-    size_t avail = free_b + w.sample_L_bytes + (lg ? w.sample_G_bytes : size_t(0));
-    if (budget > avail / 2) budget = avail / 2;
-    uint64_t bytes_per_replica = per_replica * (lg ? 25ull : 24ull);  // radiance, + the group byte of a light-group render
-    uint32_t group = uint32_t(std::min<uint64_t>(n, std::max<uint64_t>(1, budget / bytes_per_replica)));
-    group = (n + (n + group - 1) / group - 1) / ((n + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
-    if (bytes_per_replica > avail) return set_err(RT_E_NOMEM, "per-sample radiance buffer of one replica does not fit in device memory");
-    size_t need = size_t(per_replica) * 24 * group;
-    if (int st = grow_buffer(w.sample_L, w.sample_L_bytes, need)) return st;
-    if (lg) {
-        const size_t need_g = size_t(per_replica) * group;
-        if (int st = grow_buffer(w.sample_G, w.sample_G_bytes, need_g)) return st;
-        const size_t need_acc = group < n ? size_t(npix) * 24 * lg->n_groups : size_t(0);
-        if (int st = grow_buffer(w.acc_g, w.acc_g_bytes, need_acc)) return st;
-        const size_t need_t = size_t(lg->n_materials) + 2;
-        if (int st = grow_buffer(w.lg_table, w.lg_table_bytes, need_t)) return st;
-        HIP_TRY(hipMemcpyAsync(w.lg_table, lg->table, need_t, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));  // the host table may be the caller's stack
-        for (hipEvent_t& e : w.ev_res)
-            if (!e) HIP_TRY(hipEventCreate(&e));
-    }
-    const bool multi_group = group < n && !ad;  // adaptive: every group resolves into the accumulator's sums
-    if (multi_group)
-        if (int st = grow_buffer(w.acc, w.acc_bytes, size_t(npix) * 24)) return st;
+    uint32_t group = 0;  // replicas per group
+    if (int st = wf_plan_samples(w, per_replica, npix, n, ad != nullptr, lg, stream, &group)) return st;
 
     const bool stats = p.collect_stats != 0;
     const bool vol = !s->compiled.volumes.empty();  // volume ops: combined intersect kernel, VOL variant
     SearchSetup<R> su;
     if (int st = make_search_setup<R>(s, ds, stats, vol, &su)) return st;
-    if (int st = grow_buffer(w.mesh_spill, w.mesh_spill_bytes, su.spill_bytes)) return st;
+    if (int st = w.mesh_spill.reserve(su.spill_bytes)) return st;
     const uint32_t staged_shade = staged_prefix(ds.view.lay_shade, su.lds_tables, su.lds_budget);
     // k_wf_shade: all or nothing (a staged prefix read through flat instructions was 3 % slower than global memory on the default scene),
     // and only while five workgroups still fit a CU's 160 KB next to its lists (<= 23 KB of tables; RT_LDS_SHADE_MAX overrides)
@@ -1183,7 +1230,6 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     const bool compact_tail = env_u32("RT_WF_COMPACT", 1) != 0;
     const uint32_t compact_min = std::max<uint32_t>(1u, env_u32("RT_WF_COMPACT_MIN", 1024));
     const uint32_t compact_pct = std::min<uint32_t>(75u, std::max<uint32_t>(1u, env_u32("RT_WF_COMPACT_PCT", 50)));  // ... when at most this share of the addressed slots is alive.  50 / 62 / 75: the tail's iterations of C2 take 13.0 / 12.4 / 11.9 ms, but the paths thin out by ~22 % per iteration, so 75 compacts after nearly every one (13 copies of 0.3 ms per C2 frame, 6 with 50); whole frames are equal within the noise
-    uint32_t n_compactions = 0;
     const bool iter_log = env_u32("RT_WF_ITER_LOG", 0) != 0;
     const bool trace_pool = env_u32("RT_WF_TRACE", 0) != 0;  // debug: dump the first pool slots after every iteration
     const uint32_t check_every = trace_pool ? 1u : std::min<uint32_t>(32u, std::max<uint32_t>(1u, env_u32("RT_WF_CHECK", 8)));  // 4 timing events per iteration, 128 events
@@ -1208,15 +1254,10 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 
     HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DeviceCounters), stream));
     HIP_TRY(hipEventRecord(s->ev0, stream));
-    // HIP-event sums per kernel of the iteration loop: 4 events per iteration (before prims / intersect, after it,
-    // after the mesh kernel, after shade); slot 0 = prims, 1 = traversal (mesh or combined intersect), 2 = shade
-    double phase_ms[3] = {0.0, 0.0, 0.0};
-    uint32_t search_launches = 0;  // stand-alone k_wf_prims / k_wf_intersect launches
-    bool prims_ran[32];            // per iteration of a batch (check_every <= 32): k_wf_prims was launched
-    double resolve_ms = 0.0;  // light-group renders: both resolve kernels
-    uint32_t isect_launches = 0, n_groups = 0;
+    WfTally ty{};
+    bool prims_ran[32];  // per iteration of a batch (check_every <= 32): k_wf_prims was launched
     for (uint32_t t0 = t_first; t0 < t_end; t0 += group) {
-        n_groups++;
+        ty.n_groups++;
         uint32_t nrep = std::min(group, t_end - t0);
         WfGroup<R> grp{};
         grp.total = per_replica * nrep;
@@ -1238,7 +1279,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
         uint32_t first = uint32_t(std::min<uint64_t>(capacity, grp.total));
         pool = pool_a;
-        pool_dev_cur = w.pool_dev;
+        pool_dev_cur = pools[0].dev;
         bool on_b = false;
         pool.capacity = first;  // slots in use by this group: the kernels address slots directly while all of them are queued
         WfCounters init{};
@@ -1249,15 +1290,15 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         init.next_sample = first;
         *w.h_ctr = init;
         HIP_TRY(hipMemcpyAsync(w.d_ctr, w.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-        if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, w.queue[0]);
-        else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, w.queue[0]);
+        if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, queue[0]);
+        else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, queue[0]);
         int qi = 0;
         bool hits_ready = false;  // the hit records and the mesh queue of the current queue exist already (phase 4 of a fused k_wf_shade)
         uint32_t upper = first;  // upper bound of the queue length (never grows: slots are reused in place)
         auto launch_shade = [&](auto kernel, const auto& g) {
             hipLaunchKernelGGL(kernel, dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), shade_tables_lds + kShadeListBytes + shade_lds_pad, stream,
-                               ds.view, cv, pv, pool, g, w.queue[qi], w.queue[qi ^ 1], w.d_ctr, w.sample_L, s->d_counters,
-                               static_cast<const WfPool<R>*>(pool_dev_cur), staged_shade, w.mesh_queue);
+                               ds.view, cv, pv, pool, g, queue[qi], queue[qi ^ 1], w.d_ctr.get(), w.sample_L.get(), s->d_counters.get(),
+                               pool_dev_cur, staged_shade, mesh_queue);
         };
         for (;;) {
             size_t ev = 0;
@@ -1270,27 +1311,27 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
             const uint32_t check_now = (compact_tail && all_started) ? 1u : ((near_end || closing) ? std::min<uint32_t>(check_every, 2u) : check_every);
             for (uint32_t k = 0; k < check_now; k++) {
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                const SearchQueues sq{w.queue[qi], w.mesh_queue, w.mesh_spill, w.d_ctr, s->d_counters, stream};
+                const SearchQueues sq{queue[qi], mesh_queue, w.mesh_spill, w.d_ctr, s->d_counters, stream};
                 prims_ran[k] = (su.split || su.prims_only) && !hits_ready;
                 if (su.split || su.prims_only) {
-                    if (!hits_ready) { launch_prims(su, ds, pool, sq, upper); search_launches++; }
+                    if (!hits_ready) { launch_prims(su, ds, pool, sq, upper); ty.search_launches++; }
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                     if (su.split) launch_mesh(su, ds, pool, sq);
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 } else {
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                     launch_intersect(su, ds, pool, sq);
-                    search_launches++;
+                    ty.search_launches++;
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 }
                 if (lg) launch_shade(shade_lg, grp_lg);
                 else if (sparse) launch_shade(shade_sparse, grp_s);
                 else launch_shade(shade_dense, grp);
                 if (fuse) hits_ready = true;  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
-                hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr);
+                hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr.get());
                 HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 qi ^= 1;
-                isect_launches++;
+                ty.iterations++;
             }
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipMemcpyAsync(w.h_ctr, w.d_ctr, sizeof(WfCounters), hipMemcpyDeviceToHost, stream));
@@ -1301,33 +1342,14 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                     it_ms[ph] = 0.f;
                     HIP_TRY(hipEventElapsedTime(&it_ms[ph], w.events[e + ph], w.events[e + ph + 1]));
                     if (ph == 0 && (su.split || su.prims_only) && !prims_ran[e / 4]) it_ms[ph] = 0.f;  // no launch between the two events
-                    phase_ms[ph] += it_ms[ph];
+                    ty.phase_ms[ph] += it_ms[ph];
                 }
                 if (iter_log)  // RT_WF_ITER_LOG=1 (with RT_WF_CHECK=1 the queue length printed is the one of this very iteration)
-                    std::fprintf(stderr, "[wf iter] group %u: <= %u paths queued: prims %.3f ms, traversal %.3f ms, shade %.3f ms\n", n_groups, upper,
+                    std::fprintf(stderr, "[wf iter] group %u: <= %u paths queued: prims %.3f ms, traversal %.3f ms, shade %.3f ms\n", ty.n_groups, upper,
                                  it_ms[0], it_ms[1], it_ms[2]);
             }
-            if (trace_pool) {
-                const uint32_t n = std::min<uint32_t>(std::min(first, pool.capacity), env_u32("RT_WF_TRACE", 0));
-                std::vector<R> a[12];
-                R* src[12] = {pool.ox, pool.oy, pool.oz, pool.dx, pool.dy, pool.dz, pool.tr, pool.tg, pool.tb, pool.ht, pool.hu, pool.hv};
-                for (int k = 0; k < 12; k++) { a[k].resize(n); HIP_TRY(hipMemcpy(a[k].data(), src[k], n * sizeof(R), hipMemcpyDeviceToHost)); }
-                std::vector<uint64_t> rngs(n), smp(n);
-                std::vector<uint32_t> dep(n), qn(first);
-                std::vector<int32_t> hpc(n);
-                HIP_TRY(hipMemcpy(rngs.data(), pool.rng, n * 8, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(smp.data(), pool.sample, n * 8, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(dep.data(), pool.depth, n * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(hpc.data(), pool.hpc, n * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(qn.data(), w.queue[qi], size_t(w.h_ctr->n_in) * 4, hipMemcpyDeviceToHost));
-                std::fprintf(stderr, "[wf trace] iteration %u: %u paths queued:", isect_launches, w.h_ctr->n_in);
-                for (uint32_t k = 0; k < w.h_ctr->n_in && k < 64; k++) std::fprintf(stderr, " %u", qn[k]);
-                std::fprintf(stderr, "\n");
-                for (uint32_t k = 0; k < n; k++)
-                    std::fprintf(stderr, "  slot %u sample %llu depth %u o %.17g %.17g %.17g d %.17g %.17g %.17g thr %.6g %.6g %.6g hit t %.17g pc %d rng %016llx\n", k,
-                                 (unsigned long long)smp[k], dep[k], double(a[0][k]), double(a[1][k]), double(a[2][k]), double(a[3][k]), double(a[4][k]),
-                                 double(a[5][k]), double(a[6][k]), double(a[7][k]), double(a[8][k]), double(a[9][k]), hpc[k], (unsigned long long)rngs[k]);
-            }
+            if (trace_pool)
+                if (int st = wf_trace_dump(pool, first, queue[qi], w.h_ctr->n_in, ty.iterations)) return st;
             upper = w.h_ctr->n_in;
             // every sample of the call's last group has been started and slots are running empty: from here on this render
             // cannot fill the GPU any more, the next frame's render (another RtScene, another stream) may start underneath it
@@ -1337,12 +1359,12 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
             //      restart: the live paths move to slots 0 .. upper-1 of the other pool, which becomes the pool ----
             if (compact_tail && w.h_ctr->next_sample >= grp.total && upper >= compact_min && uint64_t(upper) * 100 <= uint64_t(pool.capacity) * compact_pct) {
                 WfPool<R> dst = on_b ? pool_a : pool_b;
-                hipLaunchKernelGGL((k_wf_compact<R>), dim3((upper + 255) / 256), dim3(256), 0, stream, pool, dst, w.queue[qi], upper);
+                hipLaunchKernelGGL((k_wf_compact<R>), dim3((upper + 255) / 256), dim3(256), 0, stream, pool, dst, queue[qi], upper);
                 on_b = !on_b;
                 pool = dst;
                 pool.capacity = upper;  // n_in == capacity: the kernels address slot i for entry i again
-                pool_dev_cur = on_b ? w.pool2_dev : w.pool_dev;
-                n_compactions++;
+                pool_dev_cur = pools[on_b ? 1 : 0].dev;
+                ty.n_compactions++;
                 if (hits_ready) {  // the hit records stayed behind and the mesh queue names the old slots: stand-alone k_wf_prims next
                     HIP_TRY(hipMemsetAsync(&w.d_ctr->n_mesh, 0, sizeof(uint32_t), stream));
                     hits_ready = false;
@@ -1351,23 +1373,23 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         }
         if (ad) {
             const dim3 rgrid(uint32_t((npix + 255) / 256));
-            if (sparse) hipLaunchKernelGGL(k_wf_resolve_moments<true>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
-            else hipLaunchKernelGGL(k_wf_resolve_moments<false>, rgrid, dim3(256), 0, stream, w.sample_L, npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
+            if (sparse) hipLaunchKernelGGL(k_wf_resolve_moments<true>, rgrid, dim3(256), 0, stream, w.sample_L.get(), npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
+            else hipLaunchKernelGGL(k_wf_resolve_moments<false>, rgrid, dim3(256), 0, stream, w.sample_L.get(), npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
         } else {
             if (lg) HIP_TRY(hipEventRecord(w.ev_res[0], stream));
             if (d_out)
-                hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L, w.acc, npix, strata, nrep,
+                hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L.get(), w.acc.get(), npix, strata, nrep,
                                    pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
             if (lg) {
                 const uint64_t blocks = ((npix + 63) / 64) * ((lg->n_groups + 3u) / 4u);
                 if (blocks > 0x7FFFFFFFull) return set_err(RT_E_UNSUPPORTED, "frame too large for the light-group resolve");
-                hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, stream, w.sample_L, w.sample_G, w.acc_g, npix,
+                hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, stream, w.sample_L.get(), w.sample_G.get(), w.acc_g.get(), npix,
                                    lg->n_groups, strata, nrep, pv.spp, int(t0 == t_first), lg->d_groups_out, int(t0 + nrep >= t_end));
                 HIP_TRY(hipEventRecord(w.ev_res[1], stream));
                 HIP_TRY(hipStreamSynchronize(stream));
                 float ms = 0.f;
                 HIP_TRY(hipEventElapsedTime(&ms, w.ev_res[0], w.ev_res[1]));
-                resolve_ms += ms;
+                ty.resolve_ms += ms;
             }
         }
     }
@@ -1385,124 +1407,26 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         for (int k = 0; k < 7; k++) std::fprintf(stderr, "  %-40s %10.0f clk per wave-trip\n", names[k], double(h[k]) / trips);
     }
 #endif
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
-    DeviceCounters hc{};
-    HIP_TRY(hipMemcpy(&hc, s->d_counters, sizeof hc, hipMemcpyDeviceToHost));
-    RtRenderStats& st = s->stats;
-    st = RtRenderStats{};
-    st.kernel_ms = ms;
-    st.traversal_kernel_ms = su.prims_only ? 0.0 : phase_ms[1];
-    st.prims_kernel_ms = (su.split || su.prims_only) ? phase_ms[0] : 0.0;
-    st.shade_kernel_ms = phase_ms[2];
-    st.n_launches = search_launches;
-    st.n_iterations = isect_launches;
-    st.n_replica_groups = n_groups;
-    st.n_tail_compactions = n_compactions;
-    if (lg && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
-        std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", lg->n_groups, resolve_ms,
-                     w.sample_G_bytes, w.acc_g_bytes);
-    if (stats && su.split && env_u32("RT_WF_DEBUG", 0)) {
-        std::fprintf(stderr, "[k_wf_mesh] grid %u workgroups, %d per CU, %zu B of LDS each; hand-out mode %u, 256 / 128 entries above %u / %u left per wave\n",
-                     su.isect_blocks, su.blocks_per_cu, su.lds_mesh, su.handout.mode, su.handout.left256, su.handout.left128);
-        auto pct = [](unsigned long long lanes, unsigned long long waves) { return waves ? 100.0 * double(lanes) / (64.0 * double(waves)) : 0.0; };
-        std::fprintf(stderr,
-                     "[k_wf_mesh] rays %llu  node code: %llu wave iterations, %.1f %% lanes active;  triangle code: %llu, %.1f %%;  "
-                     "refill: %llu, %.1f %%;  stack entries culled on pop %llu\n",
-                     hc.mesh_rays, hc.node_wave_iters, pct(hc.node_visits, hc.node_wave_iters), hc.tri_wave_iters,
-                     pct(hc.tri_tests, hc.tri_wave_iters), hc.refill_wave_iters, pct(hc.refill_lanes, hc.refill_wave_iters), hc.pops_culled);
-    }
-    st.pipeline_used = RT_PIPELINE_WAVEFRONT;
-    st.samples = npix * strata * n;
-    st.rays = hc.rays;
-    st.mesh_rays = hc.mesh_rays;
-    st.node_visits = hc.node_visits;
-    st.tri_tests = hc.tri_tests;
-    st.prim_tests = hc.prim_tests;
-    st.bytes_node = su.split ? (su.node_kind == 0 ? sizeof(BvhNode4f) : sizeof(BvhNode4q)) : sizeof(BvhNode<R>);
-    st.bytes_tri = sizeof(TriRec<R>);
-    st.bytes_attr = sizeof(TriAttr<R>);
-    // path state moved by the DOMINANT kernel per ray it traverses: ray (6 R) + bound/op read (R + 4)
-    // + hit written when a triangle wins (3 R + 8) + queue entry (4)
-    st.bytes_state = 6 * sizeof(R) + sizeof(R) + 4 + 3 * sizeof(R) + 8 + 4;
-    // k_wf_prims per ray: ray in (6 R), closest hit out (3 R + 8); k_wf_shade per ray: ray + hit + throughput + rng + depth +
-    // sample index in, ray + throughput + rng + depth out (a path that ends writes 24 B of radiance instead and restarts)
-    st.bytes_state_prims = 6 * sizeof(R) + 3 * sizeof(R) + 8;
-    st.bytes_state_shade = (6 + 3 + 3) * sizeof(R) + 8 + 8 + 4 + 8 + (6 + 3) * sizeof(R) + 8 + 4;
-    // the lean renders of this scene run the search inside k_wf_shade: its bytes per ray are then the kernel's (a counting
-    // render is never fused, but it reports what the timed renders beside it move)
-    if (fusable) st.bytes_state_shade += st.bytes_state_prims;
-    if (!su.split) st.mesh_rays = hc.rays;  // combined kernel: every ray's state passes through it
-    return RT_OK;
+    return wf_fill_stats(s, su, ty, lg, fusable, npix * strata * n);
 }
 
 // ---------------------------------------------------------------------------------------------
 // Ray queries (include/rt_mi355.h; kernels in rt_query.hip)
 // ---------------------------------------------------------------------------------------------
-static void rq_release(RtScene::Query& q) {
-    for (void* p : q.allocs) (void)hipFree(p);
-    q.allocs.clear();
-    ::operator delete(q.pool_view);
-    q.pool_view = nullptr;
-    q.queue = nullptr;
-    q.mesh_queue = nullptr;
-    q.capacity = 0;
-    q.real_size = 0;
-}
-static void rq_destroy(RtScene::Query& q) {
-    rq_release(q);
-    if (q.mesh_spill) (void)hipFree(q.mesh_spill);
-    if (q.d_ctr) (void)hipFree(q.d_ctr);
-    if (q.h_ctr) (void)hipHostFree(q.h_ctr);
-    if (q.op_node) (void)hipFree(q.op_node);
-    if (q.tri_order) (void)hipFree(q.tri_order);
-    if (q.staging) (void)hipFree(q.staging);
-    if (q.ev0) (void)hipEventDestroy(q.ev0);
-    if (q.ev1) (void)hipEventDestroy(q.ev1);
-    q = RtScene::Query{};
-}
-
 static uint32_t rq_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(64u, env_u32("RT_RQ_CHUNK", 1u << 22))); }
 
-// Events, counters and (closest hit: `pool`) a pool of at least `capacity` slots in R.
+// Counters and (closest hit: `pool`) a pool of at least `capacity` slots in R.
 template <typename R>
 int rq_ensure(RtScene* s, uint32_t capacity, bool pool) {
     RtScene::Query& q = s->rq;
-    if (!q.ev0) HIP_TRY(hipEventCreate(&q.ev0));
-    if (!q.ev1) HIP_TRY(hipEventCreate(&q.ev1));
-    if (!q.d_ctr) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q.d_ctr), sizeof(WfCounters)));
-    if (!q.h_ctr) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&q.h_ctr), sizeof(WfCounters)));
-    if (!pool || (q.capacity >= capacity && q.real_size == sizeof(R))) return RT_OK;
-    rq_release(q);
-    auto* pl = new WfPool<R>();  // value-initialised: the arrays a query does not use stay NULL
-    q.pool_view = pl;
-    auto alloc = [&](size_t bytes, void** out) -> int {
-        const hipError_t e = hipMalloc(out, bytes);
-        if (e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            return set_err(RT_E_NOMEM, "ray-query pool does not fit in device memory (RT_RQ_CHUNK sets its size)");
-        }
-        HIP_TRY(e);
-        q.allocs.push_back(*out);
-        return RT_OK;
-    };
-    auto build = [&]() -> int {
-        R** reals[] = {&pl->ox, &pl->oy, &pl->oz, &pl->dx, &pl->dy, &pl->dz, &pl->ht, &pl->hu, &pl->hv};
-        for (R** r : reals)
-            if (int st = alloc(size_t(capacity) * sizeof(R), reinterpret_cast<void**>(r))) return st;
-        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&pl->hpc))) return st;
-        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&pl->htri))) return st;
-        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&q.queue))) return st;
-        if (int st = alloc(size_t(capacity) * 4, reinterpret_cast<void**>(&q.mesh_queue))) return st;
-        return RT_OK;
-    };
-    if (int st = build()) {
-        rq_release(q);
-        return st;
-    }
-    pl->capacity = capacity;
-    q.capacity = capacity;
-    q.real_size = sizeof(R);
+    if (int st = q.d_ctr.reserve(sizeof(WfCounters))) return st;
+    if (int st = q.h_ctr.reserve(sizeof(WfCounters))) return st;
+    const auto* have = std::get_if<PoolPair<R>>(&q.pools);
+    if (!pool || (have && (*have)[0].view.capacity >= capacity)) return RT_OK;
+    q.pools = std::monostate{};
+    PoolPair<R> pp;  // the arrays a query does not use stay NULL
+    if (int st = build_pool(pp[0], capacity, false, 1, "ray-query pool does not fit in device memory (RT_RQ_CHUNK sets its size)")) return st;
+    q.pools = std::move(pp);
     return RT_OK;
 }
 
@@ -1510,13 +1434,11 @@ int rq_ensure(RtScene* s, uint32_t capacity, bool pool) {
 static int rq_tables(RtScene* s, hipStream_t stream) {
     RtScene::Query& q = s->rq;
     if (q.tables_generation == s->generation && q.op_node) return RT_OK;
-    if (q.op_node) (void)hipFree(q.op_node);
-    if (q.tri_order) (void)hipFree(q.tri_order);
-    q.op_node = nullptr;
-    q.tri_order = nullptr;
+    q.op_node.reset();
+    q.tri_order.reset();
     const CompiledScene& cs = s->compiled;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q.op_node), std::max<size_t>(1, cs.op_node.size()) * 4));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&q.tri_order), std::max<size_t>(1, cs.tri_order.size()) * 4));
+    if (int st = q.op_node.reserve(std::max<size_t>(1, cs.op_node.size()) * 4)) return st;
+    if (int st = q.tri_order.reserve(std::max<size_t>(1, cs.tri_order.size()) * 4)) return st;
     if (!cs.op_node.empty()) HIP_TRY(hipMemcpyAsync(q.op_node, cs.op_node.data(), cs.op_node.size() * 4, hipMemcpyHostToDevice, stream));
     if (!cs.tri_order.empty()) HIP_TRY(hipMemcpyAsync(q.tri_order, cs.tri_order.data(), cs.tri_order.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1528,16 +1450,18 @@ static int rq_tables(RtScene* s, hipStream_t stream) {
 // of an iteration of a lean (no counters), volume-free render, from the same make_search_setup and through the same launch
 // helpers, with the query workspace's queues, counters and spill buffer.
 template <typename R>
-int query_search_pass(RtScene* s, DeviceScene<R>& ds, const WfPool<R>& pool, uint32_t m, hipStream_t stream) {
+int query_search_pass(RtScene* s, DeviceScene<R>& ds, const PathPool<R>& pl, uint32_t m, hipStream_t stream) {
     RtScene::Query& q = s->rq;
     SearchSetup<R> su;
     if (int st = make_search_setup<R>(s, ds, false, false, &su)) return st;
-    if (int st = grow_buffer(q.mesh_spill, q.mesh_spill_bytes, su.spill_bytes)) return st;
+    if (int st = q.mesh_spill.reserve(su.spill_bytes)) return st;
+    WfPool<R> pool = pl.view;
+    pool.capacity = m;  // every slot is queued: the kernels address slot i for entry i
     WfCounters init{};
     init.n_in = m;
     *q.h_ctr = init;
     HIP_TRY(hipMemcpyAsync(q.d_ctr, q.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-    const SearchQueues sq{q.queue, q.mesh_queue, q.mesh_spill, q.d_ctr, s->d_counters, stream};
+    const SearchQueues sq{pl.queue[0], pl.mesh_queue, q.mesh_spill, q.d_ctr, s->d_counters, stream};
     if (su.split || su.prims_only) {
         launch_prims(su, ds, pool, sq, m);
         if (su.split) launch_mesh(su, ds, pool, sq);
@@ -1548,13 +1472,58 @@ int query_search_pass(RtScene* s, DeviceScene<R>& ds, const WfPool<R>& pool, uin
     return RT_OK;
 }
 
+// n items in chunks of at most `chunk`: launch(off, m, d_in, d_out) enqueues the kernels of the m items from `off` on.
+// `in` / out: the arrays and their bytes per item; an input array may be NULL.  host: they are host arrays and go through
+// the staging buffer, which is sized by the largest chunk and laid out inputs first, then the output (a NULL input keeps its
+// place); otherwise the kernels work on them where they are.  One synchronise per chunk; the events span the launches, not
+// the copies.
+struct ChunkArray { const void* p; size_t each; };
+struct ChunkTimes { double ms = 0.0; uint32_t n_chunks = 0; };
+template <typename F>
+int run_chunks(ChunkStage& cs, uint64_t n, uint32_t chunk, bool host, const std::vector<ChunkArray>& in, void* out, size_t out_each,
+               hipStream_t stream, F&& launch, ChunkTimes* times) {
+    const size_t cap = size_t(std::min<uint64_t>(n, chunk));
+    size_t each_all = out_each;
+    for (const ChunkArray& a : in) each_all += a.each;
+    if (host)
+        if (int st = cs.staging.reserve(cap * each_all)) return st;
+    if (int st = cs.ev0.ensure()) return st;
+    if (int st = cs.ev1.ensure()) return st;
+    std::vector<const void*> d_in(in.size());
+    for (uint64_t off = 0; off < n; off += chunk) {
+        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
+        char* const h_out = static_cast<char*>(out) + off * out_each;
+        size_t at = 0;  // in the staging buffer
+        for (size_t i = 0; i < in.size(); i++) {
+            const char* src = in[i].p ? static_cast<const char*>(in[i].p) + off * in[i].each : nullptr;
+            if (host && src) {
+                HIP_TRY(hipMemcpyAsync(cs.staging + at, src, size_t(m) * in[i].each, hipMemcpyHostToDevice, stream));
+                src = cs.staging + at;
+            }
+            d_in[i] = src;
+            at += cap * in[i].each;
+        }
+        char* const d_out = host ? cs.staging + at : h_out;
+        HIP_TRY(hipEventRecord(cs.ev0, stream));
+        if (int st = launch(off, m, d_in.data(), static_cast<void*>(d_out))) return st;
+        HIP_TRY(hipEventRecord(cs.ev1, stream));
+        if (host) HIP_TRY(hipMemcpyAsync(h_out, d_out, size_t(m) * out_each, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, cs.ev0, cs.ev1));
+        times->ms += ms;
+        times->n_chunks++;
+    }
+    return RT_OK;
+}
+
 template <typename R>
-static void rq_record_stats(RtScene::Query& q, double kernel_ms, uint64_t n, uint32_t n_chunks) {
-    q.stats = RtRayQueryStats{};
-    q.stats.kernel_ms = kernel_ms;
-    q.stats.rays = n;
-    q.stats.n_chunks = n_chunks;
-    q.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+static void record_query_stats(RtRayQueryStats& stats, const ChunkTimes& t, uint64_t rays) {
+    stats = RtRayQueryStats{};
+    stats.kernel_ms = t.ms;
+    stats.rays = rays;
+    stats.n_chunks = t.n_chunks;
+    stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
 }
 
 // n rays in chunks: (host variant: through the staging buffer) k_rq_load -> search pass -> k_rq_resolve.
@@ -1563,44 +1532,21 @@ int trace_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* o
                      hipStream_t stream) {
     RtScene::Query& q = s->rq;
     const uint32_t chunk = rq_chunk();
-    const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
-    if (int st = rq_ensure<R>(s, cap, true)) return st;
+    if (int st = rq_ensure<R>(s, uint32_t(std::min<uint64_t>(n, chunk)), true)) return st;
     if (int st = rq_tables(s, stream)) return st;
-    if (host)
-        if (int st = grow_buffer(q.staging, q.staging_bytes, size_t(cap) * (48 + sizeof(RtRayHit)))) return st;
-    const WfPool<R> full = *static_cast<WfPool<R>*>(q.pool_view);
+    const PathPool<R>& pl = std::get<PoolPair<R>>(q.pools)[0];
+    const WfPool<R>& full = pl.view;
     const RqPool<R> rp{full.ox, full.oy, full.oz, full.dx, full.dy, full.dz, full.ht, full.hu, full.hv, full.hpc, full.htri};
     const RqTables tb{q.op_node, q.tri_order};
-    double total_ms = 0.0;
-    uint32_t n_chunks = 0;
-    for (uint64_t off = 0; off < n; off += chunk) {
-        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
-        const double *d_o = origins + 3 * off, *d_d = dirs + 3 * off;
-        RtRayHit* d_out = out + off;
-        if (host) {
-            double* st_o = static_cast<double*>(q.staging);
-            double* st_d = st_o + 3 * size_t(cap);
-            HIP_TRY(hipMemcpyAsync(st_o, d_o, size_t(m) * 24, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(st_d, d_d, size_t(m) * 24, hipMemcpyHostToDevice, stream));
-            d_o = st_o;
-            d_d = st_d;
-            d_out = reinterpret_cast<RtRayHit*>(st_d + 3 * size_t(cap));
-        }
-        WfPool<R> pool = full;
-        pool.capacity = m;  // every slot is queued: the kernels address slot i for entry i
-        HIP_TRY(hipEventRecord(q.ev0, stream));
-        HIP_TRY(rq_load_launch<R>(rp, d_o, d_d, m, q.queue, stream));
-        if (int st = query_search_pass<R>(s, ds, pool, m, stream)) return st;
-        HIP_TRY(rq_resolve_launch<R>(ds.view, rp, tb, m, d_out, stream));
-        HIP_TRY(hipEventRecord(q.ev1, stream));
-        if (host) HIP_TRY(hipMemcpyAsync(out + off, d_out, size_t(m) * sizeof(RtRayHit), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, q.ev0, q.ev1));
-        total_ms += ms;
-        n_chunks++;
-    }
-    rq_record_stats<R>(q, total_ms, n, n_chunks);
+    ChunkTimes t;
+    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
+        HIP_TRY(rq_load_launch<R>(rp, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), m, pl.queue[0], stream));
+        if (int st = query_search_pass<R>(s, ds, pl, m, stream)) return st;
+        HIP_TRY(rq_resolve_launch<R>(ds.view, rp, tb, m, static_cast<RtRayHit*>(d_out), stream));
+        return RT_OK;
+    };
+    if (int st = run_chunks(q.stage, n, chunk, host, {{origins, 24}, {dirs, 24}}, out, sizeof(RtRayHit), stream, launch, &t)) return st;
+    record_query_stats<R>(q.stats, t, n);
     return RT_OK;
 }
 
@@ -1612,54 +1558,21 @@ int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* ori
     if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the occlusion kernel's LDS traversal stack");
     const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
     const uint32_t chunk = rq_chunk();
-    const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
-    if (int st = rq_ensure<R>(s, cap, false)) return st;
-    if (host)
-        if (int st = grow_buffer(q.staging, q.staging_bytes, size_t(cap) * (48 + 16 + 1))) return st;
-    double total_ms = 0.0;
-    uint32_t n_chunks = 0;
-    for (uint64_t off = 0; off < n; off += chunk) {
-        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
-        const double *d_o = origins + 3 * off, *d_d = dirs + 3 * off;
-        const double *d_lo = t_min ? t_min + off : nullptr, *d_hi = t_max ? t_max + off : nullptr;
-        uint8_t* d_out = out + off;
-        if (host) {
-            double* st_o = static_cast<double*>(q.staging);
-            double* st_d = st_o + 3 * size_t(cap);
-            double* st_lo = st_d + 3 * size_t(cap);
-            double* st_hi = st_lo + size_t(cap);
-            HIP_TRY(hipMemcpyAsync(st_o, d_o, size_t(m) * 24, hipMemcpyHostToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(st_d, d_d, size_t(m) * 24, hipMemcpyHostToDevice, stream));
-            if (d_lo) { HIP_TRY(hipMemcpyAsync(st_lo, d_lo, size_t(m) * 8, hipMemcpyHostToDevice, stream)); d_lo = st_lo; }
-            if (d_hi) { HIP_TRY(hipMemcpyAsync(st_hi, d_hi, size_t(m) * 8, hipMemcpyHostToDevice, stream)); d_hi = st_hi; }
-            d_o = st_o;
-            d_d = st_d;
-            d_out = reinterpret_cast<uint8_t*>(st_hi + size_t(cap));
-        }
-        HIP_TRY(hipEventRecord(q.ev0, stream));
-        HIP_TRY(rq_occluded_launch<R>(ds.view, d_o, d_d, d_lo, d_hi, m, levels, cones_on, d_out, stream));
-        HIP_TRY(hipEventRecord(q.ev1, stream));
-        if (host) HIP_TRY(hipMemcpyAsync(out + off, d_out, size_t(m), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, q.ev0, q.ev1));
-        total_ms += ms;
-        n_chunks++;
-    }
-    rq_record_stats<R>(q, total_ms, n, n_chunks);
+    if (int st = rq_ensure<R>(s, uint32_t(std::min<uint64_t>(n, chunk)), false)) return st;
+    ChunkTimes t;
+    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
+        HIP_TRY(rq_occluded_launch<R>(ds.view, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), static_cast<const double*>(d_in[2]),
+                                      static_cast<const double*>(d_in[3]), m, levels, cones_on, static_cast<uint8_t*>(d_out), stream));
+        return RT_OK;
+    };
+    if (int st = run_chunks(q.stage, n, chunk, host, {{origins, 24}, {dirs, 24}, {t_min, 8}, {t_max, 8}}, out, 1, stream, launch, &t)) return st;
+    record_query_stats<R>(q.stats, t, n);
     return RT_OK;
 }
 
 // ---------------------------------------------------------------------------------------------
 // Ambient-occlusion bake (include/rt_mi355.h; kernel in rt_bake.hip)
 // ---------------------------------------------------------------------------------------------
-static void bake_destroy(RtScene::Bake& b) {
-    if (b.staging) (void)hipFree(b.staging);
-    if (b.ev0) (void)hipEventDestroy(b.ev0);
-    if (b.ev1) (void)hipEventDestroy(b.ev1);
-    b = RtScene::Bake{};
-}
-
 // points per launch; the default is a guess, not a measurement
 static uint32_t bake_chunk() { return std::min<uint32_t>(1u << 26, std::max<uint32_t>(1u, env_u32("RT_BAKE_CHUNK", 1u << 20))); }
 
@@ -1672,20 +1585,11 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
     const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
     if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the bake kernel's LDS traversal stack");
     const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
-    const uint32_t chunk = bake_chunk();
-    const uint32_t cap = uint32_t(std::min<uint64_t>(n, chunk));
-    if (!b.ev0) HIP_TRY(hipEventCreate(&b.ev0));
-    if (!b.ev1) HIP_TRY(hipEventCreate(&b.ev1));
-    if (host)
-        if (int st = grow_buffer(b.staging, b.staging_bytes, size_t(cap) * (48 + sizeof(RtBakeResult)))) return st;
-    double total_ms = 0.0;
-    uint32_t n_chunks = 0;
-    for (uint64_t off = 0; off < n; off += chunk) {
-        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
+    ChunkTimes t;
+    auto launch = [&](uint64_t off, uint32_t m, const void* const* d_in, void* d_out) -> int {
         BakePoints pts{};
         pts.n = m;
         pts.first = off;
-        RtBakeResult* d_out = out + off;
         if (hits) {
             const unsigned char* base = reinterpret_cast<const unsigned char*>(hits + off);
             pts.pos = base + offsetof(RtRayHit, pos);
@@ -1693,36 +1597,54 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
             pts.flags = base + offsetof(RtRayHit, flags);
             pts.pos_stride = pts.nrm_stride = pts.flags_stride = uint32_t(sizeof(RtRayHit));
         } else {
-            const double *d_p = positions + 3 * off, *d_n = normals + 3 * off;
-            if (host) {
-                double* st_p = static_cast<double*>(b.staging);
-                double* st_n = st_p + 3 * size_t(cap);
-                HIP_TRY(hipMemcpyAsync(st_p, d_p, size_t(m) * 24, hipMemcpyHostToDevice, stream));
-                HIP_TRY(hipMemcpyAsync(st_n, d_n, size_t(m) * 24, hipMemcpyHostToDevice, stream));
-                d_p = st_p;
-                d_n = st_n;
-                d_out = reinterpret_cast<RtBakeResult*>(st_n + 3 * size_t(cap));
-            }
-            pts.pos = reinterpret_cast<const unsigned char*>(d_p);
-            pts.nrm = reinterpret_cast<const unsigned char*>(d_n);
+            pts.pos = static_cast<const unsigned char*>(d_in[0]);
+            pts.nrm = static_cast<const unsigned char*>(d_in[1]);
             pts.pos_stride = pts.nrm_stride = 24u;
         }
-        HIP_TRY(hipEventRecord(b.ev0, stream));
-        HIP_TRY(bake_visibility_launch<R>(ds.view, pts, bp.samples, bp.seed, bp.bias, bp.max_distance, levels, cones_on, d_out, stream));
-        HIP_TRY(hipEventRecord(b.ev1, stream));
-        if (host) HIP_TRY(hipMemcpyAsync(out + off, d_out, size_t(m) * sizeof(RtBakeResult), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, b.ev0, b.ev1));
-        total_ms += ms;
-        n_chunks++;
-    }
-    b.stats = RtRayQueryStats{};
-    b.stats.kernel_ms = total_ms;
-    b.stats.rays = n * bp.samples;
-    b.stats.n_chunks = n_chunks;
-    b.stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
+        HIP_TRY(bake_visibility_launch<R>(ds.view, pts, bp.samples, bp.seed, bp.bias, bp.max_distance, levels, cones_on, static_cast<RtBakeResult*>(d_out), stream));
+        return RT_OK;
+    };
+    const std::vector<ChunkArray> in = hits ? std::vector<ChunkArray>{} : std::vector<ChunkArray>{{positions, 24}, {normals, 24}};
+    if (int st = run_chunks(b.stage, n, bake_chunk(), host, in, out, sizeof(RtBakeResult), stream, launch, &t)) return st;
+    record_query_stats<R>(b.stats, t, n * bp.samples);
     return RT_OK;
+}
+
+// Makes sure the scene's tables in the arithmetic of `precision` are on the device (built on first use), then f(tables).
+template <typename F>
+int with_tables(RtScene* s, uint32_t precision, F&& f) {
+    auto go = [&](auto& slot) -> int {
+        if (!slot) {
+            auto ds = std::make_unique<typename std::decay_t<decltype(slot)>::element_type>();
+            if (int r = ds->build(s->compiled)) return r;
+            slot = std::move(ds);
+        }
+        return f(*slot);
+    };
+    return precision == RT_PRECISION_F32 ? go(s->f32) : go(s->f64);
+}
+
+// Argument checks shared by the entry points, then run(scene, tables of `precision` on the device).
+template <typename F>
+static int ray_query_run(const RtScene* scene, uint32_t precision, const char* who, F&& run) {
+    if (!scene) return set_err(RT_E_INVALID, std::string(who) + ": NULL scene");
+    if (precision != RT_PRECISION_F64 && precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, std::string(who) + ": precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
+    if (!scene->compiled.volumes.empty())
+        return set_err(RT_E_UNSUPPORTED, std::string(who) + ": ray queries do not support scenes with volumes (a medium gives no deterministic surface)");
+    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
+    HIP_TRY(hipSetDevice(s->device));
+    return with_tables(s, precision, [&](auto& ds) -> int { return run(s, ds); });
+}
+
+// A device buffer of `bytes` for the length of one call of a host variant: run(d) works on it, then (on success) `bytes_back`
+// bytes from its start go to `host_out`.
+template <typename F>
+int with_device_frame(size_t bytes, void* host_out, size_t bytes_back, F&& run) {
+    DevBuf<double> d;
+    if (int st = d.reserve(bytes)) return st;
+    if (int st = run(d.get())) return st;
+    const hipError_t e = hipMemcpy(host_out, d, bytes_back, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? int(RT_OK) : set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
 }
 
 static int validate_render_args(const RtCameraDesc* camera, const RtRenderParams* params) {
@@ -1912,23 +1834,23 @@ struct RtAccum {
     RtRenderParams params{};       // as created (pipeline / collect_stats: the defaults of rt_accum_render)
     uint32_t owned = 0, T = 0, k = 0;
     uint64_t frame_digest = 0;
-    double* d_sum = nullptr;       // sum_k, owned x width x 4 doubles: the accumulator's own buffer
-    double* d_est = nullptr;       // estimate scratch (lazy)
-    uint8_t* d_rgb = nullptr;      // preview scratch (lazy)
-    double* d_aov = nullptr;       // first-hit AOVs of the denoised previews (lazy, owned x width x 8; not in the state blob)
+    rt::DevBuf<double> d_sum;      // sum_k, owned x width x 4 doubles: the accumulator's own buffer
+    rt::DevBuf<double> d_est;      // estimate scratch (lazy)
+    rt::DevBuf<uint8_t> d_rgb;     // preview scratch (lazy)
+    rt::DevBuf<double> d_aov;      // first-hit AOVs of the denoised previews (lazy, owned x width x 8; not in the state blob)
     uint32_t aov_replicas = 0;     // replicas d_aov was rendered with (0: none yet)
     rt::DenoiseScratch dn;         // denoiser scratch (lazy)
     // adaptive mode (rt_accum_set_adaptive): moments, replica counts, the ascending list of active pixels (two buffers that
     // take turns at a compaction) and the decision step's scratch
     bool adaptive = false, touched = false;  // touched: a state has been loaded
     RtAdaptiveParams ap{};
-    double *d_s1 = nullptr, *d_s2 = nullptr;
-    uint32_t* d_cnt = nullptr;
-    uint32_t* d_active[2] = {nullptr, nullptr};
+    rt::DevBuf<double> d_s1, d_s2;
+    rt::DevBuf<uint32_t> d_cnt, d_active[2];
     int cur = 0;
     uint32_t n_active = 0;
-    uint8_t *d_state = nullptr, *d_keep = nullptr;
-    uint32_t *d_block = nullptr, *d_n_out = nullptr;
+    rt::DevBuf<uint8_t> d_state, d_keep;
+    rt::DevBuf<uint32_t> d_block, d_n_out;
+    ~RtAccum() { (void)hipSetDevice(device); }  // before the members go: the owners do not switch devices
     size_t n_doubles() const { return size_t(owned) * camera.image_width * 4; }
     size_t npix() const { return size_t(owned) * camera.image_width; }
     bool decision_point(uint32_t kk) const { return adaptive && kk >= ap.min_replicas && kk < T && (kk - ap.min_replicas) % ap.check_interval == 0; }
@@ -2078,40 +2000,18 @@ int rt_scene_create(const RtSceneDesc* desc, int device, RtScene** out) {
     if (device < 0 || device >= n) return set_err(RT_E_INVALID, "device index out of range");
     s->device = device;
     HIP_TRY(hipSetDevice(device));
-    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreate(&s->ev0));
-    HIP_TRY(hipEventCreate(&s->ev1));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&s->d_counters), sizeof(DeviceCounters)));
+    if ((st = s->stream.create_non_blocking()) || (st = s->ev0.ensure()) || (st = s->ev1.ensure()) || (st = s->d_counters.reserve(sizeof(DeviceCounters))))
+        return st;
     *out = s.release();
     return RT_OK;
 }
 
-void rt_scene_destroy(RtScene* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->device);
-    s->f64.reset();
-    s->f32.reset();
-    for (rt::RefitMesh& rm : s->refit) rm.release();
-    rt::rq_destroy(s->rq);
-    rt::bake_destroy(s->bake);
-    rt::wf_release_pool(s->wf);
-    if (s->wf.mesh_spill) (void)hipFree(s->wf.mesh_spill);
-    if (s->wf.d_ctr) (void)hipFree(s->wf.d_ctr);
-    if (s->wf.h_ctr) (void)hipHostFree(s->wf.h_ctr);
-    if (s->wf.sample_L) (void)hipFree(s->wf.sample_L);
-    if (s->wf.acc) (void)hipFree(s->wf.acc);
-    if (s->wf.sample_G) (void)hipFree(s->wf.sample_G);
-    if (s->wf.acc_g) (void)hipFree(s->wf.acc_g);
-    if (s->wf.lg_table) (void)hipFree(s->wf.lg_table);
-    for (hipEvent_t e : s->wf.ev_res)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : s->wf.events)
-        if (e) (void)hipEventDestroy(e);
-    if (s->d_counters) (void)hipFree(s->d_counters);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+void rt_scene_destroy(RtScene* s) { delete s; }  // ~RtScene sets the device
+
+int rt_debug_live_resources(uint64_t out[4]) {
+    if (!out) return rt::set_err(RT_E_INVALID, "rt_debug_live_resources: NULL argument");
+    for (int k = 0; k < 4; k++) out[k] = rt::g_live[k].load();
+    return RT_OK;
 }
 
 uint32_t rt_owned_rows(uint32_t image_height, const RtRenderParams* params) {
@@ -2144,24 +2044,10 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
         if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
         wavefront = true;
     }
-    if (params->precision == RT_PRECISION_F32) {
-        if (!s->f32) {
-            auto ds = std::make_unique<DeviceScene<float>>();
-            int r = ds->build(s->compiled);
-            if (r != RT_OK) return r;
-            s->f32 = std::move(ds);
-        }
-        if (wavefront) return render_wavefront<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st, ad);
-        return render_typed<float>(s, *s->f32, *camera, *params, owned, t_first, n, d_rgba_out, st);
-    }
-    if (!s->f64) {
-        auto ds = std::make_unique<DeviceScene<double>>();
-        int r = ds->build(s->compiled);
-        if (r != RT_OK) return r;
-        s->f64 = std::move(ds);
-    }
-    if (wavefront) return render_wavefront<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st, ad);
-    return render_typed<double>(s, *s->f64, *camera, *params, owned, t_first, n, d_rgba_out, st);
+    return with_tables(s, params->precision, [&](auto& ds) -> int {
+        if (wavefront) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, ad);
+        return render_typed(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st);
+    });
 }
 
 int rt_render_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
@@ -2186,15 +2072,7 @@ static int render_host_impl(const RtScene* scene, const RtCameraDesc* camera, co
     uint32_t owned = owned_rows(camera->image_height, params);
     size_t bytes = size_t(owned) * camera->image_width * 4 * sizeof(double);
     if (bytes == 0) return RT_OK;
-    double* d_out = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), bytes));
-    int st = rt_render_device(scene, camera, params, d_out, nullptr);
-    if (st == RT_OK) {
-        hipError_t e = hipMemcpy(rgba_out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_out);
-    return st;
+    return with_device_frame(bytes, rgba_out, bytes, [&](double* d_out) { return rt_render_device(scene, camera, params, d_out, nullptr); });
 }
 
 int rt_render(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, double* rgba_out) {
@@ -2208,11 +2086,10 @@ int rt_debug_fuzzy_reflection(int device, uint32_t n, const double* reflected, c
     if (!n || !reflected || !fuzz || !state || !out || !state_out) return set_err(RT_E_INVALID, "rt_debug_fuzzy_reflection: NULL argument");
     HIP_TRY(hipSetDevice(device));
     DeviceBuffers buf;
-    auto alloc = [&](size_t bytes, void** p) -> int { HIP_TRY(hipMalloc(p, bytes)); buf.allocs.push_back(*p); return RT_OK; };
     void *d_r = nullptr, *d_f = nullptr, *d_s = nullptr, *d_o = nullptr, *d_so = nullptr;
     int st;
-    if ((st = alloc(size_t(n) * 24, &d_r)) || (st = alloc(size_t(n) * 8, &d_f)) || (st = alloc(size_t(n) * 8, &d_s)) ||
-        (st = alloc(size_t(n) * 48, &d_o)) || (st = alloc(size_t(n) * 16, &d_so))) return st;
+    if ((st = buf.alloc(size_t(n) * 24, &d_r)) || (st = buf.alloc(size_t(n) * 8, &d_f)) || (st = buf.alloc(size_t(n) * 8, &d_s)) ||
+        (st = buf.alloc(size_t(n) * 48, &d_o)) || (st = buf.alloc(size_t(n) * 16, &d_so))) return st;
     HIP_TRY(hipMemcpy(d_r, reflected, size_t(n) * 24, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_f, fuzz, size_t(n) * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_s, state, size_t(n) * 8, hipMemcpyHostToDevice));
@@ -2234,27 +2111,23 @@ int rt_debug_trace_sample(const RtScene* scene, const RtCameraDesc* camera, cons
     if (!scene || !camera || !params || !rgb_out || !trace_out) return set_err(RT_E_INVALID, "NULL argument");
     RtScene* s = const_cast<RtScene*>(scene);
     HIP_TRY(hipSetDevice(s->device));
-    double* d_buf = nullptr;
+    DevBuf<double> d_buf;
     size_t n_d = 3 + size_t(max_bounces) * 17 + 1;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_buf), n_d * sizeof(double)));
+    if (int st = d_buf.reserve(n_d * sizeof(double))) return st;
     HIP_TRY(hipMemset(d_buf, 0, n_d * sizeof(double)));
     uint32_t* d_n = reinterpret_cast<uint32_t*>(d_buf + 3 + size_t(max_bounces) * 17);
-    if (params->precision == RT_PRECISION_F32) {
-        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
-        size_t lds = size_t(s->f32->view.stack_entries) * 64 * sizeof(int);
-        hipLaunchKernelGGL((k_trace_sample<float>), dim3(1), dim3(64), lds, s->stream, s->f32->view, make_camera_view<float>(*camera, *params),
-                           make_params_view<float>(*params, camera->image_height), tid, x, y, sx, sy, d_buf, d_buf + 3, max_bounces, d_n);
-    } else {
-        if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
-        size_t lds = size_t(s->f64->view.stack_entries) * 64 * sizeof(int);
-        hipLaunchKernelGGL((k_trace_sample<double>), dim3(1), dim3(64), lds, s->stream, s->f64->view, make_camera_view<double>(*camera, *params),
-                           make_params_view<double>(*params, camera->image_height), tid, x, y, sx, sy, d_buf, d_buf + 3, max_bounces, d_n);
-    }
+    if (int st = with_tables(s, params->precision, [&](auto& ds) -> int {
+            using R = typename std::decay_t<decltype(ds)>::Real;
+            size_t lds = size_t(ds.view.stack_entries) * 64 * sizeof(int);
+            hipLaunchKernelGGL((k_trace_sample<R>), dim3(1), dim3(64), lds, s->stream, ds.view, make_camera_view<R>(*camera, *params),
+                               make_params_view<R>(*params, camera->image_height), tid, x, y, sx, sy, d_buf.get(), d_buf + 3, max_bounces, d_n);
+            return RT_OK;
+        }))
+        return st;
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->stream));
     std::vector<double> h(n_d);
     HIP_TRY(hipMemcpy(h.data(), d_buf, n_d * sizeof(double), hipMemcpyDeviceToHost));
-    (void)hipFree(d_buf);
     std::memcpy(rgb_out, h.data(), 3 * sizeof(double));
     std::memcpy(trace_out, h.data() + 3, size_t(max_bounces) * 17 * sizeof(double));
     uint32_t n;
@@ -2405,12 +2278,7 @@ int rt_debug_scene_mesh(const RtScene* scene, uint32_t mesh, uint32_t f32, int32
     const CompiledScene::MeshGeom* g = nullptr;
     if (!mesh_export_range(s->compiled, mesh, &g)) return set_err(RT_E_INVALID, "rt_debug_scene_mesh: mesh index out of range");
     const MeshExportOut o{children_out, cones_out, boxes_out, node_capacity, n_nodes_out, tris_out, tri_order_out, tri_capacity, n_tris_out};
-    if (f32) {
-        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
-        return mesh_export_device<float>(s->compiled, *g, *s->f32, o);
-    }
-    if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
-    return mesh_export_device<double>(s->compiled, *g, *s->f64, o);
+    return with_tables(s, f32 ? RT_PRECISION_F32 : RT_PRECISION_F64, [&](auto& ds) { return mesh_export_device(s->compiled, *g, ds, o); });
 }
 
 int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[8]) {
@@ -2429,23 +2297,18 @@ int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[
         return RT_OK;
     };
     for (int k = 0; k < 8; k++) out[k] = 0;
-    int st;
-#define RT_DIGEST_TABLES(DS, R)                                                                                     \
-    if ((st = digest_of(DS.view.nodes, cs.nodes.size() * sizeof(BvhNode<R>), &out[0])) != RT_OK) return st;        \
-    if ((st = digest_of(DS.view.nodes4, cs.nodes4.size() * sizeof(BvhNode4f), &out[1])) != RT_OK) return st;       \
-    if ((st = digest_of(DS.view.nodes4q, cs.nodes4.size() * sizeof(MeshNode4qc), &out[2])) != RT_OK) return st;    \
-    if ((st = digest_of(DS.view.tris, cs.tris.size() * sizeof(TriRec<R>), &out[3])) != RT_OK) return st;           \
-    if ((st = digest_of(DS.view.attrs, cs.attrs.size() * sizeof(TriAttr<R>), &out[4])) != RT_OK) return st;        \
-    if ((st = digest_of(DS.view.mesh_bounds, cs.mesh_bounds.size() * sizeof(Bounds<R>), &out[5])) != RT_OK) return st; \
-    if ((st = digest_of(DS.view.mesh_op_recs, cs.mesh_ops.size() * sizeof(MeshOpRec<R>), &out[6])) != RT_OK) return st;
-    if (f32) {
-        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
-        RT_DIGEST_TABLES((*s->f32), float)
-    } else {
-        if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
-        RT_DIGEST_TABLES((*s->f64), double)
-    }
-#undef RT_DIGEST_TABLES
+    if (int st = with_tables(s, f32 ? RT_PRECISION_F32 : RT_PRECISION_F64, [&](auto& ds) -> int {
+            using R = typename std::decay_t<decltype(ds)>::Real;
+            const std::pair<const void*, size_t> tables[7] = {
+                {ds.view.nodes, cs.nodes.size() * sizeof(BvhNode<R>)},        {ds.view.nodes4, cs.nodes4.size() * sizeof(BvhNode4f)},
+                {ds.view.nodes4q, cs.nodes4.size() * sizeof(MeshNode4qc)},    {ds.view.tris, cs.tris.size() * sizeof(TriRec<R>)},
+                {ds.view.attrs, cs.attrs.size() * sizeof(TriAttr<R>)},        {ds.view.mesh_bounds, cs.mesh_bounds.size() * sizeof(Bounds<R>)},
+                {ds.view.mesh_op_recs, cs.mesh_ops.size() * sizeof(MeshOpRec<R>)}};
+            for (int k = 0; k < 7; k++)
+                if (int st = digest_of(tables[k].first, tables[k].second, &out[k])) return st;
+            return RT_OK;
+        }))
+        return st;
     out[7] = s->generation;
     return RT_OK;
 }
@@ -2613,34 +2476,22 @@ int rt_accum_create(const RtScene* scene, const RtCameraDesc* camera, const RtRe
     a->T = params->thread_count;
     a->frame_digest = frame_digest(*camera, *params);
     HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_sum), a->n_doubles() * sizeof(double)));
+    if (int st = a->d_sum.reserve(a->n_doubles() * sizeof(double))) return st;
     HIP_TRY(hipMemset(a->d_sum, 0, a->n_doubles() * sizeof(double)));
     HIP_TRY(hipDeviceSynchronize());
     *out = a.release();
     return RT_OK;
 }
 
-void rt_accum_destroy(RtAccum* acc) {
-    if (!acc) return;
-    (void)hipSetDevice(acc->device);
-    if (acc->d_sum) (void)hipFree(acc->d_sum);
-    if (acc->d_est) (void)hipFree(acc->d_est);
-    if (acc->d_rgb) (void)hipFree(acc->d_rgb);
-    if (acc->d_aov) (void)hipFree(acc->d_aov);
-    for (void* q : {(void*)acc->d_s1, (void*)acc->d_s2, (void*)acc->d_cnt, (void*)acc->d_active[0], (void*)acc->d_active[1], (void*)acc->d_state,
-                    (void*)acc->d_keep, (void*)acc->d_block, (void*)acc->d_n_out})
-        if (q) (void)hipFree(q);
-    rt::denoise_scratch_release(acc->dn);
-    delete acc;
-}
+void rt_accum_destroy(RtAccum* acc) { delete acc; }  // ~RtAccum sets the device
 
 // Scan + scatter of the decision step: entries of `src` (n_src of them) with keep != 0 go, in order, to the other list, which
 // becomes the active list; 4 bytes come back to the host.
 static int adaptive_compact(RtAccum* a, const uint32_t* src, uint32_t n_src, hipStream_t st) {
     using namespace rt;
     const uint32_t n_blocks = (n_src + AD_CHUNK - 1) / AD_CHUNK;
-    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(64), 0, st, a->d_block, n_blocks, a->d_n_out);
-    hipLaunchKernelGGL(k_ad_scatter, dim3(n_blocks), dim3(256), 0, st, src, n_src, a->d_keep, a->d_block, a->d_active[a->cur ^ 1], a->d_state);
+    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(64), 0, st, a->d_block.get(), n_blocks, a->d_n_out.get());
+    hipLaunchKernelGGL(k_ad_scatter, dim3(n_blocks), dim3(256), 0, st, src, n_src, a->d_keep.get(), a->d_block.get(), a->d_active[a->cur ^ 1].get(), a->d_state.get());
     HIP_TRY(hipGetLastError());
     uint32_t n_new = 0;
     HIP_TRY(hipMemcpyAsync(&n_new, a->d_n_out, 4, hipMemcpyDeviceToHost, st));
@@ -2657,8 +2508,8 @@ static int adaptive_decide(RtAccum* a, hipStream_t st) {
     if (a->n_active == 0) return RT_OK;
     const uint32_t n = a->n_active, n_blocks = (n + AD_CHUNK - 1) / AD_CHUNK;
     const uint32_t* list = a->d_active[a->cur];
-    hipLaunchKernelGGL(k_ad_quiet, dim3((n + 255) / 256), dim3(256), 0, st, list, n, a->d_s1, a->d_s2, a->k, a->ap.threshold, a->ap.floor, a->d_state);
-    hipLaunchKernelGGL(k_ad_window, dim3(n_blocks), dim3(256), 0, st, list, n, a->d_state, a->camera.image_width, a->owned, int(a->ap.radius), a->d_keep, a->d_block);
+    hipLaunchKernelGGL(k_ad_quiet, dim3((n + 255) / 256), dim3(256), 0, st, list, n, a->d_s1.get(), a->d_s2.get(), a->k, a->ap.threshold, a->ap.floor, a->d_state.get());
+    hipLaunchKernelGGL(k_ad_window, dim3(n_blocks), dim3(256), 0, st, list, n, a->d_state.get(), a->camera.image_width, a->owned, int(a->ap.radius), a->d_keep.get(), a->d_block.get());
     return adaptive_compact(a, list, n, st);
 }
 
@@ -2667,7 +2518,7 @@ static int adaptive_decide(RtAccum* a, hipStream_t st) {
 static int adaptive_rebuild(RtAccum* a, hipStream_t st) {
     using namespace rt;
     const uint32_t n = uint32_t(a->npix()), n_blocks = (n + AD_CHUNK - 1) / AD_CHUNK;
-    hipLaunchKernelGGL(k_ad_flags_from_counts, dim3(n_blocks), dim3(256), 0, st, a->d_cnt, n, a->k, a->d_active[a->cur], a->d_keep, a->d_state, a->d_block);
+    hipLaunchKernelGGL(k_ad_flags_from_counts, dim3(n_blocks), dim3(256), 0, st, a->d_cnt.get(), n, a->k, a->d_active[a->cur].get(), a->d_keep.get(), a->d_state.get(), a->d_block.get());
     if (int r = adaptive_compact(a, a->d_active[a->cur], n, st)) return r;
     if (a->decision_point(a->k)) return adaptive_decide(a, st);
     return RT_OK;
@@ -2753,13 +2604,13 @@ static int accum_estimate_to(const RtAccum* acc, double* d_out, hipStream_t stre
     using namespace rt;
     const size_t n = acc->n_doubles();
     if (acc->adaptive) {
-        hipLaunchKernelGGL(k_accum_estimate_adaptive, dim3(uint32_t((n / 4 + 255) / 256)), dim3(256), 0, stream, acc->d_sum, acc->d_cnt, uint64_t(n / 4),
+        hipLaunchKernelGGL(k_accum_estimate_adaptive, dim3(uint32_t((n / 4 + 255) / 256)), dim3(256), 0, stream, acc->d_sum.get(), acc->d_cnt.get(), uint64_t(n / 4),
                            double(acc->T), d_out);
         HIP_TRY(hipGetLastError());
     } else if (acc->k == acc->T) {  // factor 1: the estimate is the frame, bit for bit
         HIP_TRY(hipMemcpyAsync(d_out, acc->d_sum, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
     } else {
-        hipLaunchKernelGGL(k_accum_estimate, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, acc->d_sum, uint64_t(n),
+        hipLaunchKernelGGL(k_accum_estimate, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, acc->d_sum.get(), uint64_t(n),
                            double(acc->T) / double(acc->k), d_out);
         HIP_TRY(hipGetLastError());
     }
@@ -2783,9 +2634,8 @@ int rt_accum_estimate_device(const RtAccum* acc, double* d_rgba_out, void* strea
 
 static int accum_scratch(RtAccum* a) {
     using namespace rt;
-    if (!a->d_est) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_est), a->n_doubles() * sizeof(double)));
-    if (!a->d_rgb) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_rgb), a->n_doubles() / 4 * 3));
-    return RT_OK;
+    if (int st = a->d_est.reserve(a->n_doubles() * sizeof(double))) return st;
+    return a->d_rgb.reserve(a->n_doubles() / 4 * 3);
 }
 
 int rt_accum_estimate(const RtAccum* acc, double* rgba_out) {
@@ -2924,12 +2774,7 @@ static int render_aov_impl(const RtScene* scene, const RtCameraDesc* camera, con
     const uint32_t owned = owned_rows(camera->image_height, params);
     if (owned == 0) return RT_OK;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    if (params->precision == RT_PRECISION_F32) {
-        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
-        return aov_typed<float>(s, *s->f32, *camera, *params, owned, n_replicas, d_out, st);
-    }
-    if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
-    return aov_typed<double>(s, *s->f64, *camera, *params, owned, n_replicas, d_out, st);
+    return with_tables(s, params->precision, [&](auto& ds) { return aov_typed(s, ds, *camera, *params, owned, n_replicas, d_out, st); });
 }
 
 int rt_render_aov_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
@@ -2945,15 +2790,7 @@ int rt_render_aov(const RtScene* scene, const RtCameraDesc* camera, const RtRend
     HIP_TRY(hipSetDevice(scene->device));
     const size_t bytes = size_t(owned_rows(camera->image_height, params)) * camera->image_width * kAovChannels * sizeof(double);
     if (bytes == 0) return render_aov_impl(scene, camera, params, n_replicas, aov_out, nullptr);  // argument checks only
-    double* d_out = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_out), bytes));
-    int st = render_aov_impl(scene, camera, params, n_replicas, d_out, nullptr);
-    if (st == RT_OK) {
-        const hipError_t e = hipMemcpy(aov_out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_out);
-    return st;
+    return with_device_frame(bytes, aov_out, bytes, [&](double* d_out) { return render_aov_impl(scene, camera, params, n_replicas, d_out, nullptr); });
 }
 
 int rt_denoise_default_params(RtDenoiseParams* out) {
@@ -2987,11 +2824,10 @@ static int denoise_run(const double* d_rgba, const double* d_aov, uint32_t w, ui
     using namespace rt;
     DenoiseScratch own;
     DenoiseScratch& scr = scratch ? *scratch : own;
-    hipError_t e = dp.iterations ? denoise_scratch_reserve(scr, size_t(w) * h) : hipSuccess;
-    if (e == hipSuccess) e = denoise_launch(d_rgba, d_aov, w, h, dp, d_out, scr, stream);
+    if (dp.iterations)
+        if (int st = denoise_scratch_reserve(scr, size_t(w) * h)) return st;
+    hipError_t e = denoise_launch(d_rgba, d_aov, w, h, dp, d_out, scr, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    denoise_scratch_release(own);
-    if (e == hipErrorOutOfMemory) return set_err(RT_E_NOMEM, "denoiser scratch does not fit in device memory");
     if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("denoise: ") + hipGetErrorString(e));
     return RT_OK;
 }
@@ -3015,10 +2851,9 @@ int rt_denoise(int device, const double* rgba, const double* aov, uint32_t w, ui
     if (npix == 0) return RT_OK;
     HIP_TRY(hipSetDevice(device));
     DeviceBuffers buf;
-    auto alloc = [&](size_t bytes, double** out) -> int { HIP_TRY(hipMalloc(reinterpret_cast<void**>(out), bytes)); buf.allocs.push_back(*out); return RT_OK; };
     double *d_rgba = nullptr, *d_aov = nullptr;
-    if (int st = alloc(npix * 4 * sizeof(double), &d_rgba)) return st;
-    if (int st = alloc(npix * kAovChannels * sizeof(double), &d_aov)) return st;
+    if (int st = buf.alloc(npix * 4 * sizeof(double), &d_rgba)) return st;
+    if (int st = buf.alloc(npix * kAovChannels * sizeof(double), &d_aov)) return st;
     HIP_TRY(hipMemcpy(d_rgba, rgba, npix * 4 * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_aov, aov, npix * kAovChannels * sizeof(double), hipMemcpyHostToDevice));
     if (int st = denoise_run(d_rgba, d_aov, w, h, p, d_rgba, nullptr, nullptr)) return st;  // in place
@@ -3038,7 +2873,7 @@ static int accum_denoise(RtAccum* a, const RtDenoiseParams* dp, const char* who)
     if (int st = accum_scratch(a)) return st;
     const uint32_t w = a->camera.image_width;
     if (a->aov_replicas != p.aov_replicas) {
-        if (!a->d_aov) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&a->d_aov), size_t(a->owned) * w * kAovChannels * sizeof(double)));
+        if (int st = a->d_aov.reserve(size_t(a->owned) * w * kAovChannels * sizeof(double))) return st;
         a->aov_replicas = 0;
         if (int st = render_aov_impl(a->scene, &a->camera, &a->params, p.aov_replicas, a->d_aov, nullptr)) return st;
         a->aov_replicas = p.aov_replicas;
@@ -3093,23 +2928,28 @@ int rt_accum_set_adaptive(RtAccum* acc, const RtAdaptiveParams* ap) {
     if (acc->npix() >= (1ull << 31)) return set_err(RT_E_UNSUPPORTED, "rt_accum_set_adaptive: more than 2^31 pixels");
     HIP_TRY(hipSetDevice(acc->device));
     const size_t np = acc->npix(), n_blocks = (np + AD_CHUNK - 1) / AD_CHUNK;
-    DeviceBuffers buf;  // frees what was allocated if a later allocation fails
-    auto alloc = [&](size_t bytes, void** q) -> int { HIP_TRY(hipMalloc(q, bytes)); buf.allocs.push_back(*q); HIP_TRY(hipMemset(*q, 0, bytes)); return RT_OK; };
-    void *s1 = nullptr, *s2 = nullptr, *cnt = nullptr, *a0 = nullptr, *a1 = nullptr, *state = nullptr, *keep = nullptr, *block = nullptr, *n_out = nullptr;
+    // local owners first: a failure half way leaves the accumulator as it was
+    DevBuf<double> s1, s2;
+    DevBuf<uint32_t> cnt, a0, a1, block, n_out;
+    DevBuf<uint8_t> state, keep;
+    auto zeroed = [](auto& buf, size_t bytes) -> int {
+        if (int st = buf.reserve(bytes)) return st;
+        HIP_TRY(hipMemset(buf, 0, bytes));
+        return RT_OK;
+    };
     int st;
-    if ((st = alloc(np * 8, &s1)) || (st = alloc(np * 8, &s2)) || (st = alloc(np * 4, &cnt)) || (st = alloc(np * 4, &a0)) || (st = alloc(np * 4, &a1)) ||
-        (st = alloc(np, &state)) || (st = alloc(np, &keep)) || (st = alloc(n_blocks * 4, &block)) || (st = alloc(4, &n_out))) return st;
+    if ((st = zeroed(s1, np * 8)) || (st = zeroed(s2, np * 8)) || (st = zeroed(cnt, np * 4)) || (st = zeroed(a0, np * 4)) || (st = zeroed(a1, np * 4)) ||
+        (st = zeroed(state, np)) || (st = zeroed(keep, np)) || (st = zeroed(block, n_blocks * 4)) || (st = zeroed(n_out, 4))) return st;
     {  // every pixel is active, in ascending order
         std::vector<uint32_t> identity(np);
         for (size_t i = 0; i < np; i++) identity[i] = uint32_t(i);
         HIP_TRY(hipMemcpy(a0, identity.data(), np * 4, hipMemcpyHostToDevice));
     }
     HIP_TRY(hipDeviceSynchronize());
-    buf.allocs.clear();
-    acc->d_s1 = static_cast<double*>(s1); acc->d_s2 = static_cast<double*>(s2); acc->d_cnt = static_cast<uint32_t*>(cnt);
-    acc->d_active[0] = static_cast<uint32_t*>(a0); acc->d_active[1] = static_cast<uint32_t*>(a1);
-    acc->d_state = static_cast<uint8_t*>(state); acc->d_keep = static_cast<uint8_t*>(keep);
-    acc->d_block = static_cast<uint32_t*>(block); acc->d_n_out = static_cast<uint32_t*>(n_out);
+    acc->d_s1 = std::move(s1); acc->d_s2 = std::move(s2); acc->d_cnt = std::move(cnt);
+    acc->d_active[0] = std::move(a0); acc->d_active[1] = std::move(a1);
+    acc->d_state = std::move(state); acc->d_keep = std::move(keep);
+    acc->d_block = std::move(block); acc->d_n_out = std::move(n_out);
     acc->cur = 0;
     acc->n_active = uint32_t(np);  // all pixels: the dense kernels run until the first pixel stops (the list is not read)
     acc->ap = *ap;
@@ -3238,22 +3078,7 @@ static int light_groups_impl(const RtScene* scene, const RtCameraDesc* camera, c
     lg.d_groups_out = d_groups_out;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
     const uint32_t T = params->thread_count;
-    if (params->precision == RT_PRECISION_F32) {
-        if (!s->f32) {
-            auto ds = std::make_unique<DeviceScene<float>>();
-            int r = ds->build(s->compiled);
-            if (r != RT_OK) return r;
-            s->f32 = std::move(ds);
-        }
-        return render_wavefront<float>(s, *s->f32, *camera, *params, owned, 0, T, d_rgba_out, st, nullptr, &lg);
-    }
-    if (!s->f64) {
-        auto ds = std::make_unique<DeviceScene<double>>();
-        int r = ds->build(s->compiled);
-        if (r != RT_OK) return r;
-        s->f64 = std::move(ds);
-    }
-    return render_wavefront<double>(s, *s->f64, *camera, *params, owned, 0, T, d_rgba_out, st, nullptr, &lg);
+    return with_tables(s, params->precision, [&](auto& ds) { return render_wavefront(s, ds, *camera, *params, owned, 0, T, d_rgba_out, st, nullptr, &lg); });
 }
 
 int rt_render_light_groups_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, const RtLightGroups* groups,
@@ -3272,17 +3097,14 @@ int rt_render_light_groups(const RtScene* scene, const RtCameraDesc* camera, con
     HIP_TRY(hipSetDevice(scene->device));
     const size_t frame = size_t(owned_rows(camera->image_height, params)) * camera->image_width * 4 * sizeof(double);
     if (frame == 0) return RT_OK;
-    double* d_buf = nullptr;  // the group frames, then the ordinary frame
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_buf), frame * (size_t(groups->n_groups) + 1)));
-    double* d_frame = d_buf + (frame / sizeof(double)) * groups->n_groups;
-    int st = rt_render_light_groups_device(scene, camera, params, groups, d_buf, rgba_out_or_null ? d_frame : nullptr, nullptr);
-    if (st == RT_OK) {
-        hipError_t e = hipMemcpy(groups_out, d_buf, frame * groups->n_groups, hipMemcpyDeviceToHost);
-        if (e == hipSuccess && rgba_out_or_null) e = hipMemcpy(rgba_out_or_null, d_frame, frame, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_buf);
-    return st;
+    // the group frames, then the ordinary frame
+    return with_device_frame(frame * (size_t(groups->n_groups) + 1), groups_out, frame * groups->n_groups, [&](double* d_buf) -> int {
+        double* d_frame = d_buf + (frame / sizeof(double)) * groups->n_groups;
+        if (int st = rt_render_light_groups_device(scene, camera, params, groups, d_buf, rgba_out_or_null ? d_frame : nullptr, nullptr)) return st;
+        if (!rgba_out_or_null) return RT_OK;
+        const hipError_t e = hipMemcpy(rgba_out_or_null, d_frame, frame, hipMemcpyDeviceToHost);
+        return e == hipSuccess ? int(RT_OK) : set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    });
 }
 
 int rt_light_mix_device(int device, const double* d_groups, uint32_t n_groups, uint32_t w, uint32_t h, const double* tints,
@@ -3309,62 +3131,36 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
     const size_t frame = size_t(w) * h * 4 * sizeof(double);
     if (frame == 0) return RT_OK;
     HIP_TRY(hipSetDevice(device));
-    double* d_buf = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_buf), frame * (size_t(n_groups) + 1)));
+    DevBuf<double> d_buf;  // the group frames, then the mix
+    if (int st = d_buf.reserve(frame * (size_t(n_groups) + 1))) return st;
     double* d_out = d_buf + (frame / sizeof(double)) * n_groups;
-    int st = RT_OK;
     hipError_t e = hipMemcpy(d_buf, groups, frame * n_groups, hipMemcpyHostToDevice);
-    if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    if (st == RT_OK) st = rt_light_mix_device(device, d_buf, n_groups, w, h, tints, d_out, nullptr);
-    if (st == RT_OK) {
-        e = hipMemcpy(rgba_out, d_out, frame, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) st = set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
-    }
-    (void)hipFree(d_buf);
-    return st;
-}
-
-// ---- Ray queries (rt_query.hip) -----------------------------------------------------------------------------------------
-// Argument checks shared by the four entry points; *s_out = the scene with its tables of `precision` on the device.
-static int ray_query_begin(const RtScene* scene, uint32_t precision, const char* who, RtScene** s_out) {
-    using namespace rt;
-    if (!scene) return set_err(RT_E_INVALID, std::string(who) + ": NULL scene");
-    if (precision != RT_PRECISION_F64 && precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, std::string(who) + ": precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
-    if (!scene->compiled.volumes.empty())
-        return set_err(RT_E_UNSUPPORTED, std::string(who) + ": ray queries do not support scenes with volumes (a medium gives no deterministic surface)");
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    if (precision == RT_PRECISION_F32) {
-        if (!s->f32) { auto ds = std::make_unique<DeviceScene<float>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f32 = std::move(ds); }
-    } else {
-        if (!s->f64) { auto ds = std::make_unique<DeviceScene<double>>(); int r = ds->build(s->compiled); if (r != RT_OK) return r; s->f64 = std::move(ds); }
-    }
-    *s_out = s;
+    if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    if (int st = rt_light_mix_device(device, d_buf, n_groups, w, h, tints, d_out, nullptr)) return st;
+    e = hipMemcpy(rgba_out, d_out, frame, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
     return RT_OK;
 }
 
+// ---- Ray queries (rt_query.hip) -----------------------------------------------------------------------------------------
 static int trace_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* out,
                            bool host, void* stream, const char* who) {
     using namespace rt;
-    RtScene* s = nullptr;
-    if (int st = ray_query_begin(scene, precision, who, &s)) return st;
-    if (n == 0) return RT_OK;
-    if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    if (precision == RT_PRECISION_F32) return trace_rays_typed<float>(s, *s->f32, n, origins, dirs, out, host, st);
-    return trace_rays_typed<double>(s, *s->f64, n, origins, dirs, out, host, st);
+    return ray_query_run(scene, precision, who, [&](RtScene* s, auto& ds) -> int {
+        if (n == 0) return RT_OK;
+        if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+        return trace_rays_typed(s, ds, n, origins, dirs, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
+    });
 }
 
 static int occluded_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
                          uint32_t precision, uint8_t* out, bool host, void* stream, const char* who) {
     using namespace rt;
-    RtScene* s = nullptr;
-    if (int st = ray_query_begin(scene, precision, who, &s)) return st;
-    if (n == 0) return RT_OK;
-    if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    if (precision == RT_PRECISION_F32) return occluded_typed<float>(s, *s->f32, n, origins, dirs, t_min, t_max, out, host, st);
-    return occluded_typed<double>(s, *s->f64, n, origins, dirs, t_min, t_max, out, host, st);
+    return ray_query_run(scene, precision, who, [&](RtScene* s, auto& ds) -> int {
+        if (n == 0) return RT_OK;
+        if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+        return occluded_typed(s, ds, n, origins, dirs, t_min, t_max, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
+    });
 }
 
 int rt_trace_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* hits_out) {
@@ -3401,16 +3197,14 @@ static int bake_impl(const RtScene* scene, uint64_t n, const double* positions, 
         bp.bias = 0.001;
         bp.max_distance = HUGE_VAL;
     }
-    RtScene* s = nullptr;
-    if (int st = ray_query_begin(scene, bp.precision, who, &s)) return st;
-    if (bp.samples < 1 || bp.samples > 4096) return set_err(RT_E_INVALID, std::string(who) + ": samples must be in 1 .. 4096");
-    if (!(bp.bias >= 0.0)) return set_err(RT_E_INVALID, std::string(who) + ": bias must be >= 0");
-    if (!(bp.max_distance > bp.bias)) return set_err(RT_E_INVALID, std::string(who) + ": max_distance must be greater than bias");
-    if (n == 0) return RT_OK;
-    if (!out || (hits ? false : (!positions || !normals))) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    if (bp.precision == RT_PRECISION_F32) return bake_typed<float>(s, *s->f32, n, positions, normals, hits, bp, out, host, st);
-    return bake_typed<double>(s, *s->f64, n, positions, normals, hits, bp, out, host, st);
+    return ray_query_run(scene, bp.precision, who, [&](RtScene* s, auto& ds) -> int {
+        if (bp.samples < 1 || bp.samples > 4096) return set_err(RT_E_INVALID, std::string(who) + ": samples must be in 1 .. 4096");
+        if (!(bp.bias >= 0.0)) return set_err(RT_E_INVALID, std::string(who) + ": bias must be >= 0");
+        if (!(bp.max_distance > bp.bias)) return set_err(RT_E_INVALID, std::string(who) + ": max_distance must be greater than bias");
+        if (n == 0) return RT_OK;
+        if (!out || (hits ? false : (!positions || !normals))) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+        return bake_typed(s, ds, n, positions, normals, hits, bp, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
+    });
 }
 
 int rt_bake_visibility(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtBakeParams* params,

@@ -19,6 +19,8 @@
 
 #if defined(__HIP__)
 #include <hip/hip_runtime.h>
+
+#include "rt_owned.h"
 #define RT_HD __host__ __device__
 #else
 #define RT_HD
@@ -207,18 +209,17 @@ RT_HD inline uint32_t rf_cone_word(const double* normal, uint32_t lo, uint32_t h
 // last update and the scratch of the passes.  Shared by both arithmetic types.
 struct RefitMesh {
     uint32_t n_tris = 0, n_nodes = 0, n_nodes4 = 0, n_positions = 0, n_normals = 0, n_uvs = 0;
-    uint32_t *tri_order = nullptr, *tri_pos = nullptr, *tri_nrm = nullptr;
-    int32_t* tri_uv = nullptr;             // NULL: the mesh has none
-    int32_t *child2 = nullptr, *child4 = nullptr;    // 2 / 4 per node; inner: node inside the mesh; leaf: ~(slot inside the mesh << 3 | count - 1)
-    int32_t *parent2 = nullptr, *parent4 = nullptr;  // -1: root
-    uint32_t *inner2 = nullptr, *inner4 = nullptr;   // inner children per node
-    uint32_t *arrived2 = nullptr, *arrived4 = nullptr;
-    double *positions = nullptr, *normals = nullptr, *uvs = nullptr;
-    double *tri_box = nullptr, *tri_normal = nullptr;  // per slot: lo xyz hi xyz / unit normal or NaN
-    double *box2 = nullptr, *box4 = nullptr;           // per node and child: lo xyz hi xyz (exact)
-    double* sum4 = nullptr;                            // per node and child: sum of the normals below
-    uint32_t* run4 = nullptr;                          // per node and child: first slot, end slot, count
-    void release();
+    DevBuf<uint32_t> tri_order, tri_pos, tri_nrm;
+    DevBuf<int32_t> tri_uv;             // NULL: the mesh has none
+    DevBuf<int32_t> child2, child4;     // 2 / 4 per node; inner: node inside the mesh; leaf: ~(slot inside the mesh << 3 | count - 1)
+    DevBuf<int32_t> parent2, parent4;   // -1: root
+    DevBuf<uint32_t> inner2, inner4;    // inner children per node
+    DevBuf<uint32_t> arrived2, arrived4;
+    DevBuf<double> positions, normals, uvs;
+    DevBuf<double> tri_box, tri_normal;  // per slot: lo xyz hi xyz / unit normal or NaN
+    DevBuf<double> box2, box4;           // per node and child: lo xyz hi xyz (exact)
+    DevBuf<double> sum4;                 // per node and child: sum of the normals below
+    DevBuf<uint32_t> run4;               // per node and child: first slot, end slot, count
 };
 
 // Where the mesh's reader tables stand in the scene's device arrays of arithmetic type R.

@@ -196,12 +196,13 @@ __global__ void k_refit_nodes4(uint32_t n_nodes, double pad, const int32_t* __re
 }
 
 template <typename T>
-bool dev_alloc(T** p, size_t n, std::string* err) {
-    REFIT_TRY(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(n, 1) * sizeof(T)));
-    return true;
+bool dev_alloc(DevBuf<T>& p, size_t n, std::string* err) {
+    if (p.reserve(std::max<size_t>(n, 1) * sizeof(T)) == RT_OK) return true;
+    *err = "scene refit: " + g_err;
+    return false;
 }
 template <typename T>
-bool dev_put(T* dst, const T* src, size_t n, hipStream_t stream, uint64_t* bytes, std::string* err) {
+bool dev_put(DevBuf<T>& dst, const T* src, size_t n, hipStream_t stream, uint64_t* bytes, std::string* err) {
     if (n) REFIT_TRY(hipMemcpyAsync(dst, src, n * sizeof(T), hipMemcpyHostToDevice, stream));
     *bytes += n * sizeof(T);
     return true;
@@ -211,14 +212,6 @@ inline dim3 grid_for(uint32_t n) { return dim3((n + 255u) / 256u); }
 
 }  // namespace
 
-void RefitMesh::release() {
-    for (void* p : {(void*)tri_order, (void*)tri_pos, (void*)tri_nrm, (void*)tri_uv, (void*)child2, (void*)child4, (void*)parent2, (void*)parent4,
-                    (void*)inner2, (void*)inner4, (void*)arrived2, (void*)arrived4, (void*)positions, (void*)normals, (void*)uvs, (void*)tri_box,
-                    (void*)tri_normal, (void*)box2, (void*)box4, (void*)sum4, (void*)run4})
-        if (p) (void)hipFree(p);
-    *this = RefitMesh();
-}
-
 bool refit_mesh_upload(RefitMesh& rm, const RtMesh& m, const uint32_t* tri_order, const int32_t* child2, uint32_t n_nodes, const int32_t* child4,
                        uint32_t n_nodes4, hipStream_t stream, uint64_t* bytes, std::string* err) {
     if (!rm.tri_order) {  // first update of this mesh
@@ -226,26 +219,26 @@ bool refit_mesh_upload(RefitMesh& rm, const RtMesh& m, const uint32_t* tri_order
         r.n_tris = m.n_triangles; r.n_nodes = n_nodes; r.n_nodes4 = n_nodes4;
         r.n_positions = m.n_positions; r.n_normals = m.n_normals; r.n_uvs = m.uvs && m.tri_uv ? m.n_uvs : 0;
         const size_t nt = r.n_tris;
-        bool ok = dev_alloc(&r.tri_order, nt, err) && dev_alloc(&r.tri_pos, 3 * nt, err) && dev_alloc(&r.tri_nrm, 3 * nt, err) &&
-                  (!m.tri_uv || dev_alloc(&r.tri_uv, 3 * nt, err)) && dev_alloc(&r.child2, 2 * size_t(n_nodes), err) &&
-                  dev_alloc(&r.child4, 4 * size_t(n_nodes4), err) && dev_alloc(&r.parent2, n_nodes, err) && dev_alloc(&r.parent4, n_nodes4, err) &&
-                  dev_alloc(&r.inner2, n_nodes, err) && dev_alloc(&r.inner4, n_nodes4, err) && dev_alloc(&r.arrived2, n_nodes, err) &&
-                  dev_alloc(&r.arrived4, n_nodes4, err) && dev_alloc(&r.positions, 3 * size_t(r.n_positions), err) &&
-                  dev_alloc(&r.normals, 3 * size_t(r.n_normals), err) && (!r.n_uvs || dev_alloc(&r.uvs, 3 * size_t(r.n_uvs), err)) &&
-                  dev_alloc(&r.tri_box, 6 * nt, err) && dev_alloc(&r.tri_normal, 3 * nt, err) && dev_alloc(&r.box2, 12 * size_t(n_nodes), err) &&
-                  dev_alloc(&r.box4, 24 * size_t(n_nodes4), err) && dev_alloc(&r.sum4, 12 * size_t(n_nodes4), err) &&
-                  dev_alloc(&r.run4, 12 * size_t(n_nodes4), err);
+        bool ok = dev_alloc(r.tri_order, nt, err) && dev_alloc(r.tri_pos, 3 * nt, err) && dev_alloc(r.tri_nrm, 3 * nt, err) &&
+                  (!m.tri_uv || dev_alloc(r.tri_uv, 3 * nt, err)) && dev_alloc(r.child2, 2 * size_t(n_nodes), err) &&
+                  dev_alloc(r.child4, 4 * size_t(n_nodes4), err) && dev_alloc(r.parent2, n_nodes, err) && dev_alloc(r.parent4, n_nodes4, err) &&
+                  dev_alloc(r.inner2, n_nodes, err) && dev_alloc(r.inner4, n_nodes4, err) && dev_alloc(r.arrived2, n_nodes, err) &&
+                  dev_alloc(r.arrived4, n_nodes4, err) && dev_alloc(r.positions, 3 * size_t(r.n_positions), err) &&
+                  dev_alloc(r.normals, 3 * size_t(r.n_normals), err) && (!r.n_uvs || dev_alloc(r.uvs, 3 * size_t(r.n_uvs), err)) &&
+                  dev_alloc(r.tri_box, 6 * nt, err) && dev_alloc(r.tri_normal, 3 * nt, err) && dev_alloc(r.box2, 12 * size_t(n_nodes), err) &&
+                  dev_alloc(r.box4, 24 * size_t(n_nodes4), err) && dev_alloc(r.sum4, 12 * size_t(n_nodes4), err) &&
+                  dev_alloc(r.run4, 12 * size_t(n_nodes4), err);
         ok = ok && dev_put(r.tri_order, tri_order, nt, stream, bytes, err) && dev_put(r.tri_pos, m.tri_pos, 3 * nt, stream, bytes, err) &&
              dev_put(r.tri_nrm, m.tri_nrm, 3 * nt, stream, bytes, err) && (!m.tri_uv || dev_put(r.tri_uv, m.tri_uv, 3 * nt, stream, bytes, err)) &&
              dev_put(r.child2, child2, 2 * size_t(n_nodes), stream, bytes, err) && dev_put(r.child4, child4, 4 * size_t(n_nodes4), stream, bytes, err);
-        if (!ok) { r.release(); return false; }
+        if (!ok) return false;
         // the source arrays of the copies above are the caller's temporaries: finish before returning
-        hipLaunchKernelGGL(k_refit_parents<2>, grid_for(n_nodes), dim3(256), 0, stream, n_nodes, r.child2, r.parent2, r.inner2);
-        hipLaunchKernelGGL(k_refit_parents<4>, grid_for(n_nodes4), dim3(256), 0, stream, n_nodes4, r.child4, r.parent4, r.inner4);
+        hipLaunchKernelGGL(k_refit_parents<2>, grid_for(n_nodes), dim3(256), 0, stream, n_nodes, r.child2.get(), r.parent2.get(), r.inner2.get());
+        hipLaunchKernelGGL(k_refit_parents<4>, grid_for(n_nodes4), dim3(256), 0, stream, n_nodes4, r.child4.get(), r.parent4.get(), r.inner4.get());
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) { *err = std::string("scene refit: ") + hipGetErrorString(e); r.release(); return false; }
-        rm = r;
+        if (e != hipSuccess) { *err = std::string("scene refit: ") + hipGetErrorString(e); return false; }
+        rm = std::move(r);
     }
     if (rm.n_tris != m.n_triangles || rm.n_positions != m.n_positions || rm.n_normals != m.n_normals || rm.n_nodes != n_nodes || rm.n_nodes4 != n_nodes4) {
         *err = "scene refit: the mesh has another structure than at its first update";
@@ -262,15 +255,15 @@ bool refit_mesh_launch(RefitMesh& rm, const RefitTarget<R>& t, hipStream_t strea
     const dim3 block(256);
     REFIT_TRY(hipMemsetAsync(rm.arrived2, 0, size_t(rm.n_nodes) * sizeof(uint32_t), stream));
     REFIT_TRY(hipMemsetAsync(rm.arrived4, 0, size_t(rm.n_nodes4) * sizeof(uint32_t), stream));
-    hipLaunchKernelGGL((k_refit_tris<R>), grid_for(rm.n_tris), block, 0, stream, rm.n_tris, rm.tri_order, rm.tri_pos, rm.tri_nrm, rm.uvs ? rm.tri_uv : nullptr,
-                       rm.positions, rm.normals, rm.uvs, cone_limits(sizeof(R) == 4), t.tris, t.attrs, rm.tri_box, rm.tri_normal);
-    hipLaunchKernelGGL((k_refit_up<2>), grid_for(rm.n_nodes), block, 0, stream, rm.n_nodes, rm.n_tris, rm.child2, rm.parent2, rm.inner2, rm.arrived2,
-                       rm.tri_box, rm.tri_normal, rm.box2, static_cast<double*>(nullptr), static_cast<uint32_t*>(nullptr));
-    hipLaunchKernelGGL((k_refit_up<4>), grid_for(rm.n_nodes4), block, 0, stream, rm.n_nodes4, rm.n_tris, rm.child4, rm.parent4, rm.inner4, rm.arrived4,
-                       rm.tri_box, rm.tri_normal, rm.box4, rm.sum4, rm.run4);
-    hipLaunchKernelGGL((k_refit_nodes2<R>), grid_for(rm.n_nodes), block, 0, stream, rm.n_nodes, rm.box2, t.nodes);
-    hipLaunchKernelGGL(k_refit_nodes4, grid_for(rm.n_nodes4), block, 0, stream, rm.n_nodes4, t.pad4, rm.child4, rm.box4, rm.sum4, rm.run4,
-                       rm.tri_normal, t.nodes4, t.nodes4q);
+    hipLaunchKernelGGL((k_refit_tris<R>), grid_for(rm.n_tris), block, 0, stream, rm.n_tris, rm.tri_order.get(), rm.tri_pos.get(), rm.tri_nrm.get(), rm.uvs ? rm.tri_uv.get() : nullptr,
+                       rm.positions.get(), rm.normals.get(), rm.uvs.get(), cone_limits(sizeof(R) == 4), t.tris, t.attrs, rm.tri_box.get(), rm.tri_normal.get());
+    hipLaunchKernelGGL((k_refit_up<2>), grid_for(rm.n_nodes), block, 0, stream, rm.n_nodes, rm.n_tris, rm.child2.get(), rm.parent2.get(), rm.inner2.get(), rm.arrived2.get(),
+                       rm.tri_box.get(), rm.tri_normal.get(), rm.box2.get(), static_cast<double*>(nullptr), static_cast<uint32_t*>(nullptr));
+    hipLaunchKernelGGL((k_refit_up<4>), grid_for(rm.n_nodes4), block, 0, stream, rm.n_nodes4, rm.n_tris, rm.child4.get(), rm.parent4.get(), rm.inner4.get(), rm.arrived4.get(),
+                       rm.tri_box.get(), rm.tri_normal.get(), rm.box4.get(), rm.sum4.get(), rm.run4.get());
+    hipLaunchKernelGGL((k_refit_nodes2<R>), grid_for(rm.n_nodes), block, 0, stream, rm.n_nodes, rm.box2.get(), t.nodes);
+    hipLaunchKernelGGL(k_refit_nodes4, grid_for(rm.n_nodes4), block, 0, stream, rm.n_nodes4, t.pad4, rm.child4.get(), rm.box4.get(), rm.sum4.get(), rm.run4.get(),
+                       rm.tri_normal.get(), t.nodes4, t.nodes4q);
     REFIT_TRY(hipGetLastError());
     return true;
 }

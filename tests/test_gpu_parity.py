@@ -776,7 +776,10 @@ def test_tail_compaction_does_not_change_the_frame(dev, name, monkeypatch):
 def test_a_pool_that_does_not_fit_is_halved(dev, monkeypatch):
     """The path pool is sized for speed (128 M slots at the headline's work).  When device memory is short - other scenes of a
     frame pipeline, other processes on the card - the scheduler halves it until it fits instead of failing; the frame is the
-    same (RT_WF_FAKE_OOM_ABOVE makes every pool above that many slots fail like hipErrorOutOfMemory)."""
+    same (RT_WF_FAKE_OOM_ABOVE makes the last allocation of every pool above that many slots fail like hipErrorOutOfMemory, so
+    what is released before the next try is a pool that was fully allocated).  A render in the other precision builds the pool
+    anew, through the same failures; and when all is closed nothing the library allocated is left (rt_debug_live_resources)."""
+    live0 = api.live_resources()
     hs = api.HostScene(["scenes/cornell", "-w=400", "-s=64", "--seed=3"])
     scene = api.DeviceScene(hs.desc, 0)
     p = hs.params.copy()
@@ -788,8 +791,18 @@ def test_a_pool_that_does_not_fit_is_halved(dev, monkeypatch):
     out = scene2.render(hs.camera, p)
     assert scene2.stats().n_iterations > it_ref        # a smaller pool: more iterations
     assert ((out == ref) | (np.isnan(out) & np.isnan(ref))).all()
+    p32 = p.copy()
+    p32.precision = api.RT_PRECISION_F32               # the pool changes its type, and back: each time failing, then halving
+    scene2.render(hs.camera, p32)
+    assert scene2.stats().n_iterations > it_ref
+    out = scene2.render(hs.camera, p)
+    assert scene2.stats().n_iterations > it_ref
+    assert out.tobytes() == ref.tobytes()
     monkeypatch.setenv("RT_WF_POOL", str(1 << 23))      # an explicit size is taken as given: the error surfaces
     scene3 = api.DeviceScene(hs.desc, 0)
     with pytest.raises(api.RtError) as e:
         scene3.render(hs.camera, p)
     assert e.value.status == api.RT_E_NOMEM
+    for s in (scene, scene2, scene3):
+        s.close()
+    assert api.live_resources() == live0
