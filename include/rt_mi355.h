@@ -351,6 +351,14 @@ int rt_scene_mesh_stats(const RtSceneDesc* desc, uint64_t out[8]);
  * output arrays may be NULL. */
 int rt_scene_mesh_cones(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out,
                         uint32_t node_capacity, uint32_t* n_nodes_out, double* tris_out, uint32_t tri_capacity, uint32_t* n_tris_out);
+
+/* The normal slabs that k_wf_mesh tests beside the cones, for node i of rt_scene_mesh_cones' order: slabs_out[4 i + k] the
+ * word of child k (two signed 16-bit integers: lo | hi << 16; 0x7FFF8000 on a child without a cone), bounds_out[8 i + 2 k + {0, 1}] its decoded [lo, hi],
+ * frames_out[4 i + {0, 1, 2}] the node's grid origin and [4 i + 3] its 1 / s: the slab bounds q . (x - org) / s with q the
+ * child's three cone axis bytes.  *pad_out: the pad m of the mesh's boxes; the builder widens a slab by |q|_1 (2 m / s + 2^-12).
+ * slabs_out NULL: the count only. */
+int rt_scene_mesh_slabs(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, uint32_t* slabs_out, float* bounds_out, float* frames_out,
+                        double* pad_out, uint32_t node_capacity, uint32_t* n_nodes_out);
 /* The hand-out policy of the persistent search kernels (csrc/rt_handout.h), replayed on the host (tests without a GPU): `waves`
  * waves share a queue of `n` entries and ask for ranges in the order `order` (wave indices; walked round and round, every
  * wave must appear) until each has been told that the queue is exhausted and has asked once more after that.  policy = {mode,

@@ -321,6 +321,10 @@ def load_device_lib() -> C.CDLL:
             lib.rt_scene_mesh_cones.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
             lib.rt_scene_mesh_cones.restype = C.c_int
+        if hasattr(lib, "rt_scene_mesh_slabs"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_scene_mesh_slabs.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_uint32)]
+            lib.rt_scene_mesh_slabs.restype = C.c_int
         if hasattr(lib, "rt_debug_handout_replay"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_debug_handout_replay.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
                                                     C.POINTER(C.c_uint32), C.c_void_p]
@@ -498,6 +502,25 @@ def scene_mesh_cones(desc, mesh: int = 0, f32: bool = False) -> tuple:
     if st != RT_OK:
         raise RtError(st, lib.rt_last_error().decode())
     return children, cones.view(np.int8).reshape(-1, 4, 4), tris
+
+
+def scene_mesh_slabs(desc, mesh: int = 0, f32: bool = False) -> dict:
+    """rt_scene_mesh_slabs, for the nodes of scene_mesh_cones in the same order: {"words" (n, 4) uint32, "bounds" (n, 4, 2)
+    float32 as (lo, hi), "org" (n, 3) float32, "inv_s" (n,) float32, "pad" float}; host only."""
+    import numpy as np
+    lib = load_device_lib()
+    nn, pad = C.c_uint32(), C.c_double()
+    st = lib.rt_scene_mesh_slabs(desc, mesh, int(f32), None, None, None, C.byref(pad), 0, C.byref(nn))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    words = np.zeros((nn.value, 4), dtype=np.uint32)
+    bounds = np.zeros((nn.value, 4, 2), dtype=np.float32)
+    frames = np.zeros((nn.value, 4), dtype=np.float32)
+    st = lib.rt_scene_mesh_slabs(desc, mesh, int(f32), words.ctypes.data, bounds.ctypes.data, frames.ctypes.data, C.byref(pad),
+                                 nn.value, C.byref(nn))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return {"words": words, "bounds": bounds, "org": frames[:, :3].copy(), "inv_s": frames[:, 3].copy(), "pad": float(pad.value)}
 
 
 def scene_update_check(a, b) -> None:

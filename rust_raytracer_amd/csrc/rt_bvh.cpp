@@ -347,4 +347,81 @@ void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<T
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Normal slabs of the 4-wide mesh nodes.
+//
+// A child box is axis-aligned around a thin, tilted patch of surface: most rays that enter the box miss the patch.  Per child
+// with a cone: q = the three axis bytes of its cone word as integers (no normalisation), s = 4 x the node's largest cell,
+// P(x) = q . (x - org) / s, and [lo, hi] = the exact min / max of P over the corners v0, v0 + e1, v0 + e2 of every triangle
+// below the child (over the triangles themselves, never a merge of the children's slabs), widened by the margin
+// M = |q|_1 (2 m / s + 2^-12) (m = 2^-19 S, the pad of the mesh's boxes, S = its largest |coordinate|) and rounded outward to two
+// signed 16-bit integers.  Inside the node |x_i - org_i| / s <= 63.75, so |P| <= 381 x 63.75 = 24 289: the scale holds every slab.
+// P is linear, so every point of every triangle below lies in the slab.  k_wf_mesh evaluates, in f32,
+//   r = (oc - org) / s, e = d / s, A = q . r, B = q . e, pn = fma(tn, B, A), pf = fma(tf, B, A)
+// for the culling ray (oc, d) and the span [tn, tf] of the ray inside the child's box, and drops the child if pn and pf are
+// both below lo or both above hi (rt_traverse.h node4q_cull_slabs).  Only a ray that the exact test would let hit a triangle
+// below the child matters; for such a ray, with X the hit point and tau its parameter on the culling ray, u = 2^-24 and
+// G = max_i(|org_i| / s, |r_i|, 128), in units of u |q|_1 G (1 / s is a power of two: scaling is exact):
+//
+//  1. oc in f32 is off by <= 2 u |oc_i| (one rounding in R, one to f32) and |oc_i| / s <= |org_i| / s + |r_i| <= 2 G: 4; the
+//     subtraction of org adds u |r_i|: 1; the three-term chain of A adds 3 roundings of partial sums <= |q|_1 G: 3.  A: 8.
+//  2. e is d rounded to f32 (u |e_i|), the chain of B adds 3 u sum |q_i e_i|; times t, where t |e_i| = |X_i - oc_i| / s
+//     <= 64 + G <= 1.5 G for every t in [tn, tf] (both ends lie in the node's box): (1 + 3) x 1.5 = 6.
+//  3. The last fma rounds a value <= |A| + |t B| <= 2.5 |q|_1 G: 2.5.
+//  4. The culling ray itself (oc and d in f32) passes X within 2 u |oc_i| + u t |d_i|, over s: 4 + 1.5 = 5.5.
+//     The step forms oc as fma(d, t_shift, o) (one rounding in R), make_cull_ray forms the origin that tn and tf are measured
+//     from as o + d t_shift (two): the two starts differ by at most one rounding of R, u |oc_i| / s <= 2 more.
+//  Together 24 u |q|_1 G.  For a ray that hits, oc and X lie in the mesh's box: |org_i| <= S, |r_i| <= 2 S / s, so
+//  G <= max(2 S / s, 128) and 24 u |q|_1 G <= |q|_1 max(48 u S / s, 2^-12.4) <= M (2 m = 64 u S).  The 16 u S / s left over
+//  cover tn and tf: the child's box holds X with the margin m on every side and the box test's own rounding is below
+//  2.5 x 2^-23 S |iv| per plane (rt_kernels.hip), so tn <= tau <= tf; tau >= 0 up to one rounding of t_shift and
+//  tau <= tmax32 by f32_at_least.  The function L(t) = A + t B with the COMPUTED A and B is exactly linear, so L(tau) lies
+//  between L(tn) and L(tf), and L(tau) is within M of P(X), which lies in the unwidened slab: pn and pf cannot both be on the
+//  same side outside [lo, hi].
+//  This holds for R = double, where the exact test's own error (10 u_64, see the cones) is nothing against M.  It does NOT hold
+//  for R = float: the f32 triangle test accepts rays whose u, v are off by an amount that grows with the distance of the ray's
+//  origin from the triangle, that is, rays that pass the triangle farther off than M, and the slab - far tighter than the box -
+//  drops them: 2 pixels of the f32 headline frame changed (profiles/mesh_slabs/README.md).  k_wf_mesh therefore has the step in
+//  its f64 forms only; a slab for f32 needs a per-ray bound on that error first.  (The words are built for both types.)
+//  5. Range: the kernel turns e into NaN unless 1e-20 < max |e_i| < 1e30 and G < 2^16, so no product overflows
+//     (|B| <= 381 x 1e30), a flushed component of e moves t e_i by less than 2^17 x 1.2e-38 / 1e-20, and a bound clamped to
+//     -32768 or 32767 is out of reach: |L(tau)| <= 24 289 + 24 u 381 x 2^16 < 24 325.  fmaxf / fminf drop a NaN operand: with
+//     both ends NaN the comparisons fail; ONE NaN only arises as 0 x inf from tf = +inf and B = 0, where the true pf equals pn.
+// The test does not read the direction word: it holds for meshes that hit back faces and with RT_WF_CONES=0.
+// A child without a cone (kNeutralCone: empty, above an ill-conditioned triangle, too wide) carries kNeutralSlab; its q is 0,
+// so the kernel sees A = B = 0 (or NaN) inside [-32768, 32767] and never drops it.
+// ---------------------------------------------------------------------------------------------
+void build_mesh_slabs(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const std::vector<uint32_t>& cones,
+                      const BvhNode4q* qnodes, const double* node_pad, std::vector<uint32_t>* out) {
+    const size_t n_tris = tris.size();
+    struct Run { uint32_t lo = UINT32_MAX, hi = 0, count = 0; };
+    auto tri_at = [&](uint32_t t, double* v) {
+        const TriRec<double>& r = tris[t];
+        for (int a = 0; a < 3; a++) { v[a] = r.v0[a]; v[3 + a] = r.e1[a]; v[6 + a] = r.e2[a]; }
+    };
+    out->assign(4 * nodes4.size(), kNeutralSlab);
+    std::vector<Run> below(nodes4.size());
+    for (size_t i = nodes4.size(); i-- > 0;) {  // as build_mesh_cones
+        const BuildNode4& nd = nodes4[i];
+        Run all;
+        for (int k = 0; k < 4; k++) {
+            const int32_t ch = nd.child[k];
+            if (ch == kEmptyChild) continue;
+            Run b;
+            if (ch >= 0) {
+                if (size_t(ch) <= i || size_t(ch) >= nodes4.size()) continue;  // build_mesh_cones leaves no cone above: no slab either
+                b = below[size_t(ch)];
+            } else {
+                const uint32_t code = uint32_t(~ch), first = code >> 3, count = (code & 7u) + 1u;
+                if (size_t(first) + count > n_tris) continue;
+                b.lo = first; b.hi = first + count; b.count = count;
+            }
+            (*out)[4 * i + size_t(k)] = rf_slab_word(cones[4 * i + size_t(k)], qnodes[i].org, qnodes[i].cell, node_pad[i], b.lo, b.hi, b.count, tri_at);
+            all.lo = std::min(all.lo, b.lo); all.hi = std::max(all.hi, b.hi);
+            all.count += b.count;
+        }
+        below[i] = all;
+    }
+}
+
 }  // namespace rt

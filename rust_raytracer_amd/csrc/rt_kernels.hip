@@ -294,6 +294,7 @@ struct DeviceScene {
         // of a value bounded by 2 S |iv|; with it the error is < 2.5 x 2^-23 S |iv| per plane, inside the padding.
         std::vector<BvhNode4q> nodes4q(mesh_tables ? cs.nodes4.size() : 0);
         std::vector<BvhNode4q> group_nodes;
+        std::vector<double> node_pad;  // per mesh node: the pad of its mesh
         {
             auto pad_of = [&]() {
                 std::vector<std::pair<uint32_t, double>> pads;
@@ -312,11 +313,13 @@ struct DeviceScene {
             };
             const auto pads4 = pad_of();
             size_t pi = 0;
+            node_pad.resize(nodes4q.size());
             for (size_t i = 0; i < nodes4q.size(); i++) {
                 while (pi + 1 < pads4.size() && pads4[pi + 1].first <= i) pi++;
                 const BuildNode4& sn = cs.nodes4[i];
                 BvhNode4q& qn = nodes4q[i];
-                if (!quantise(sn, pads4.empty() ? 0.0 : pads4[pi].second, qn))
+                node_pad[i] = pads4.empty() ? 0.0 : pads4[pi].second;
+                if (!quantise(sn, node_pad[i], qn))
                     return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
             }
             // the primitive groups' BVHs: same node format, same padding rule (2^-19 x the largest |coordinate| of the group's box)
@@ -338,10 +341,14 @@ struct DeviceScene {
         // back-face cone words of the mesh nodes' children, with the conditioning limits of this arithmetic type (rt_bvh.cpp)
         std::vector<uint32_t> cone_words;
         if (mesh_tables) build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &cone_words);
+        // and their normal slabs, on the cones' axes
+        std::vector<uint32_t> slab_words;
+        if (mesh_tables) build_mesh_slabs(cs.nodes4, cs.tris, cone_words, nodes4q.data(), node_pad.data(), &slab_words);
         std::vector<MeshNode4qc> nodes4qc(mesh_tables ? cs.nodes4.size() : 0);
         for (size_t i = 0; i < nodes4qc.size(); i++) {
             nodes4qc[i].node = nodes4q[i];
             for (int k = 0; k < 4; k++) nodes4qc[i].cones.word[k] = cone_words[4 * i + size_t(k)];
+            for (int k = 0; k < 4; k++) nodes4qc[i].slabs.word[k] = slab_words[4 * i + size_t(k)];
             for (uint32_t& x : nodes4qc[i]._pad) x = 0;
         }
         std::vector<Bounds<R>> mesh_bounds(cs.mesh_bounds.size());
@@ -778,6 +785,7 @@ int aov_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtR
 // ---------------------------------------------------------------------------------------------
 // Wavefront pipeline driver
 // ---------------------------------------------------------------------------------------------
+constexpr size_t kSlabsMinTriangles = 131072;  // RT_WF_SLABS unset: the f64 kernels run the slab step if the scene's largest mesh has at least this many triangles
 static uint32_t env_u32(const char* name, uint32_t dflt) {
     const char* v = std::getenv(name);
     if (!v || !*v) return dflt;
@@ -811,13 +819,16 @@ PrimsKernel<R> pick_prims(bool stats, bool vol, bool groups, int lds) {
 }
 
 template <typename R, bool ST>
-MeshKernel<R> pick_mesh_st(int node_kind, bool multi) {
+MeshKernel<R> pick_mesh_st(int node_kind, bool multi, bool slabs) {
+    if constexpr (sizeof(R) == 8) {  // the form with the slab step: f64, quantised nodes
+        if (node_kind == 1 && slabs) return multi ? &k_wf_mesh<R, ST, 1, true, true> : &k_wf_mesh<R, ST, 1, false, true>;
+    }
     if (node_kind == 1) return multi ? &k_wf_mesh<R, ST, 1, true> : &k_wf_mesh<R, ST, 1, false>;
     return multi ? &k_wf_mesh<R, ST, 0, true> : &k_wf_mesh<R, ST, 0, false>;
 }
 template <typename R>
-MeshKernel<R> pick_mesh(bool stats, int node_kind, bool multi) {
-    return stats ? pick_mesh_st<R, true>(node_kind, multi) : pick_mesh_st<R, false>(node_kind, multi);
+MeshKernel<R> pick_mesh(bool stats, int node_kind, bool multi, bool slabs) {
+    return stats ? pick_mesh_st<R, true>(node_kind, multi, slabs) : pick_mesh_st<R, false>(node_kind, multi, slabs);
 }
 
 // The lean k_wf_shade of any group type (WfGroup, WfGroupSparse: restarts through the active list, WfGroupLG: the terminal's
@@ -847,6 +858,7 @@ struct SearchSetup {
     bool multi_mesh;
     int node_kind;
     uint32_t cones_on;
+    uint32_t slabs_on;  // RT_WF_SLABS: 0 off, 1 every child (default), 2 leaf children only
     int mesh_levels, lds_levels;        // k_wf_mesh's stack: levels in all / in LDS (the rest in the workspace's spill buffer)
     uint32_t refill_min, inner_min;
     HandoutPolicy handout;              // how the persistent kernels' waves share their queue (rt_handout.h)
@@ -898,6 +910,20 @@ int make_search_setup(RtScene* s, DeviceScene<R>& ds, bool stats, bool vol, Sear
     su.node_kind = env_u32("RT_WF_NODES", 1) != 0 ? 1 : 0;
     // Back-face cone test of the quantised node step: 0 = off (A/B control: the same code object, never-culling direction word).
     su.cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    // Normal-slab test behind the box test (the SLABS forms of k_wf_mesh): RT_WF_SLABS = 0 off, 1 every child, 2 leaf children only.
+    // f64 and quantised nodes only: in f32 the step is not result-preserving (the f32 triangle test accepts a few rays per 10^9
+    // that pass a triangle farther off than the slab's margin: 2 pixels of the headline frame changed), so there is no f32 form and
+    // the variable is ignored there.  Unset: every child if the scene's LARGEST mesh has at least kSlabsMinTriangles triangles, off
+    // otherwise.  Measured (profiles/mesh_slabs/README.md), k_wf_mesh against the parent's: -11.9 % on the 871 200-triangle headline
+    // mesh, -16 % on the 3.5 M-triangle one, -1.6 % and -3 % on Suzanne (15.7 k, c3 and c1), +3.7 % on the 1 k-triangle meshes of
+    // two_meshes (shallow trees: few visits to save, the step's instructions on every one).  On Suzanne the frame does not move
+    // (inside its spread), so the threshold stays above it, where the frame gains: between 15.7 k and 871 k nothing is measured.
+    // The setting is one per launch: a scene with one large and many small meshes runs the
+    // step on all of them.
+    size_t largest_mesh = 0;
+    for (const MeshInst& mi : s->compiled.meshes) largest_mesh = std::max(largest_mesh, size_t(mi.n_tris));
+    const uint32_t slabs_dflt = largest_mesh >= kSlabsMinTriangles ? 1u : 0u;
+    su.slabs_on = (sizeof(R) == 8 && su.node_kind == 1) ? std::min(env_u32("RT_WF_SLABS", slabs_dflt), 2u) : 0u;
     su.mesh_levels = int(s->compiled.max_bvh4_stack) + 1;
     su.lds_levels = std::min<int>(su.mesh_levels, int(env_u32("RT_WF_LDS_LEVELS", 12)));
     su.lds_mesh = size_t(su.lds_levels) * 256 * sizeof(uint2) + 4 * kMeshWaveLds<R>;
@@ -922,7 +948,7 @@ int make_search_setup(RtScene* s, DeviceScene<R>& ds, bool stats, bool vol, Sear
     su.lds_prims_launch = (vol ? size_t(0) : size_t(su.staged_prims) + su.lds_groups) + (WF_CHUNK + 4) * 4;
     su.k_intersect = pick_intersect<R>(stats, vol);
     su.k_prims = pick_prims<R>(stats, vol, su.groups, su.lds_prims);
-    su.k_mesh = pick_mesh<R>(stats, su.node_kind, su.multi_mesh);
+    su.k_mesh = pick_mesh<R>(stats, su.node_kind, su.multi_mesh, su.slabs_on != 0u);
     // persistent grids: as many workgroups as stay resident.  The combined kernel's grid is the lean variant's at either
     // setting of `stats`; k_wf_mesh's is the launched variant's own.
     int n_cu = 0, blocks_per_cu = 0;
@@ -956,7 +982,7 @@ void launch_prims(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPo
 template <typename R>
 void launch_mesh(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq) {
     hipLaunchKernelGGL(su.k_mesh, dim3(su.isect_blocks), dim3(256), su.lds_mesh, sq.stream, ds.view, pool, sq.mesh_queue, sq.ctr, sq.counters,
-                       su.refill_min, su.inner_min, static_cast<uint2*>(sq.mesh_spill), su.lds_levels, &sq.ctr->n_mesh, &sq.ctr->cursor, su.cones_on, su.handout.mode, su.handout.left256, su.handout.left128);
+                       su.refill_min, su.inner_min, static_cast<uint2*>(sq.mesh_spill), su.lds_levels, &sq.ctr->n_mesh, &sq.ctr->cursor, su.cones_on, su.slabs_on, su.handout.mode, su.handout.left256, su.handout.left128);
 }
 template <typename R>
 void launch_intersect(const SearchSetup<R>& su, const DeviceScene<R>& ds, const WfPool<R>& pool, const SearchQueues& sq) {
@@ -2428,6 +2454,53 @@ int rt_scene_mesh_cones(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, in
             const TriRec<double>& r = cs.tris[mi.tri_base + t];
             for (int a = 0; a < 3; a++) { tris_out[9 * t + size_t(a)] = r.v0[a]; tris_out[9 * t + 3 + size_t(a)] = r.e1[a]; tris_out[9 * t + 6 + size_t(a)] = r.e2[a]; }
         }
+    return RT_OK;
+}
+
+int rt_scene_mesh_slabs(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, uint32_t* slabs_out, float* bounds_out, float* frames_out,
+                        double* pad_out, uint32_t node_capacity, uint32_t* n_nodes_out) {
+    using namespace rt;
+    if (!desc || !n_nodes_out) return set_err(RT_E_INVALID, "rt_scene_mesh_slabs: NULL argument");
+    CompiledScene cs;
+    std::string err;
+    int st = compile_scene(desc, &cs, &err, CompileOptions());
+    if (st != RT_OK) return set_err(st, err);
+    if (mesh >= cs.meshes.size()) return set_err(RT_E_INVALID, "rt_scene_mesh_slabs: mesh index out of range");
+    const MeshInst& mi = cs.meshes[mesh];
+    size_t node_end = cs.nodes4.size();  // as rt_scene_mesh_cones
+    for (const MeshInst& o : cs.meshes)
+        if (o.node4_base > mi.node4_base) node_end = std::min(node_end, size_t(o.node4_base));
+    const size_t n_nodes = node_end - mi.node4_base;
+    *n_nodes_out = uint32_t(n_nodes);
+    const double pad = rf_pad_of_box(cs.mesh_bounds[mesh].lo, cs.mesh_bounds[mesh].hi);
+    if (pad_out) *pad_out = pad;
+    if (!slabs_out) return RT_OK;
+    // the tables as DeviceScene<R>::build derives them; the other meshes' children get no cone here and so no slab
+    std::vector<uint32_t> cones, slabs;
+    build_mesh_cones(cs.nodes4, cs.tris, cone_limits(f32 != 0), &cones);
+    std::vector<BvhNode4q> qn(cs.nodes4.size());
+    std::vector<double> pads(cs.nodes4.size(), pad);
+    for (size_t i = 0; i < cs.nodes4.size(); i++) {
+        const bool own = i >= mi.node4_base && i < node_end;
+        const BuildNode4& sn = cs.nodes4[i];
+        if (own && !rf_quantise4(sn.lo, sn.hi, sn.child, pad, qn[i].org, qn[i].cell, qn[i].qlo, qn[i].qhi))
+            return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
+        if (!own)
+            for (int k = 0; k < 4; k++) cones[4 * i + size_t(k)] = kNeutralCone;
+    }
+    build_mesh_slabs(cs.nodes4, cs.tris, cones, qn.data(), pads.data(), &slabs);
+    for (size_t i = 0; i < n_nodes && i < node_capacity; i++) {
+        const size_t n = mi.node4_base + i;
+        for (int k = 0; k < 4; k++) {
+            const uint32_t w = slabs[4 * n + size_t(k)];
+            slabs_out[4 * i + size_t(k)] = w;
+            if (bounds_out) { bounds_out[8 * i + 2 * size_t(k)] = float(int16_t(w & 0xFFFFu)); bounds_out[8 * i + 2 * size_t(k) + 1] = float(int16_t(w >> 16)); }
+        }
+        if (frames_out) {
+            for (int a = 0; a < 3; a++) frames_out[4 * i + size_t(a)] = qn[n].org[a];
+            frames_out[4 * i + 3] = float(rf_slab_inv_scale(qn[n].cell));
+        }
+    }
     return RT_OK;
 }
 

@@ -202,6 +202,48 @@ RT_HD inline uint32_t rf_cone_word(const double* normal, uint32_t lo, uint32_t h
     return word;
 }
 
+// ---- normal slabs (the argument stands in rt_bvh.cpp) ----
+// 1 / s of a node: s = 4 x its largest cell (cells are powers of two: exact), so that |x - org| / s <= 63.75 inside the node.
+RT_HD inline double rf_slab_inv_scale(const float* cell) {
+    const double cmax = rf_max(double(cell[0]), rf_max(double(cell[1]), double(cell[2])));
+    return 0.25 / cmax;
+}
+// The margin of a slab in its own units: |q|_1 (2 pad / s + 2^-12), pad = rf_pad_of_box of the mesh.
+RT_HD inline double rf_slab_margin(const int* q, double pad, double inv_s) {
+    const double l1 = double((q[0] < 0 ? -q[0] : q[0]) + (q[1] < 0 ? -q[1] : q[1]) + (q[2] < 0 ? -q[2] : q[2]));
+    return l1 * (2.0 * pad * inv_s + 1.0 / 4096.0);
+}
+
+// The slab word of a child with cone word `cone` over the slots [lo, hi), `count` triangles, in a node with grid origin
+// `org` and cells `cell`: the exact interval of q . (x - org) / s over the three corners v0, v0 + e1, v0 + e2 of every
+// triangle below, widened by rf_slab_margin and rounded outward to two signed 16-bit integers (lo | hi << 16).
+// tri_at(slot, v) gives v0 e1 e2 in v[0..9).
+template <typename TriAt>
+RT_HD inline uint32_t rf_slab_word(uint32_t cone, const float* org, const float* cell, double pad, uint32_t lo, uint32_t hi, uint32_t count, TriAt tri_at) {
+    if (cone == kNeutralCone || count == 0 || hi - lo != count) return kNeutralSlab;
+    const int q[3] = {int(int8_t(cone & 0xFFu)), int(int8_t((cone >> 8) & 0xFFu)), int(int8_t((cone >> 16) & 0xFFu))};
+    const double inv_s = rf_slab_inv_scale(cell);
+    if (!(inv_s > 0.0) || !std::isfinite(inv_s) || !std::isfinite(pad)) return kNeutralSlab;
+    double plo = INFINITY, phi = -INFINITY;
+    for (uint32_t t = lo; t < hi; t++) {
+        double v[9];
+        tri_at(t, v);
+        for (int c = 0; c < 3; c++) {
+            double x[3];
+            for (int a = 0; a < 3; a++) x[a] = c == 0 ? v[a] : v[a] + v[3 * c + a];
+            const double p = double(q[0]) * ((x[0] - double(org[0])) * inv_s) + double(q[1]) * ((x[1] - double(org[1])) * inv_s) +
+                             double(q[2]) * ((x[2] - double(org[2])) * inv_s);
+            plo = rf_min(plo, p);
+            phi = rf_max(phi, p);
+        }
+    }
+    if (!(plo <= phi) || !std::isfinite(plo) || !std::isfinite(phi)) return kNeutralSlab;  // a NaN compares false
+    const double margin = rf_slab_margin(q, pad, inv_s);
+    const double l = rf_max(std::floor(plo - margin), -32768.0), h = rf_min(std::ceil(phi + margin), 32767.0);
+    if (!(l <= 32767.0 && h >= -32768.0)) return kNeutralSlab;  // off the scale (a vertex outside the node's grid): no slab
+    return (uint32_t(int32_t(l)) & 0xFFFFu) | (uint32_t(int32_t(h)) << 16);
+}
+
 #if defined(__HIP__)
 // ---- the device refit (rt_refit.hip) ----
 // Everything one distinct mesh needs on the device to be refitted again and again: the leaf order, the index arrays and the

@@ -11,7 +11,7 @@
 //                        are added in the host's order (a leaf's triangles in slot order, a node's children in k order)
 //                        by ONE thread each: no float atomics, so the sums do not depend on the arrival order.
 //   3. k_refit_nodes2<R> / k_refit_nodes4   per node: the reader formats, by the formulas of rt_refit.h that the host
-//                        builder uses (BvhNode<R>, BvhNode4f, BvhNode4q, cone words).
+//                        builder uses (BvhNode<R>, BvhNode4f, BvhNode4q, cone and slab words).
 // The kernels write the fields that depend on the vertices and nothing else: child references and padding keep the bytes
 // the host builder gave them, so a refitted table equals, byte for byte, the one DeviceScene<R>::build uploads for the same
 // tree and vertices (tests/test_gpu_scene_update.py compares them).
@@ -165,6 +165,7 @@ __global__ void k_refit_nodes2(uint32_t n_nodes, const double* __restrict__ box,
 
 __global__ void k_refit_nodes4(uint32_t n_nodes, double pad, const int32_t* __restrict__ child, const double* __restrict__ box,
                                const double* __restrict__ sum, const uint32_t* __restrict__ run, const double* __restrict__ tri_normal,
+                               const uint32_t* __restrict__ tri_order, const uint32_t* __restrict__ tri_pos, const double* __restrict__ positions,
                                BvhNode4f* __restrict__ nodes4, MeshNode4qc* __restrict__ nodes4q) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_nodes) return;
@@ -180,7 +181,7 @@ __global__ void k_refit_nodes4(uint32_t n_nodes, double pad, const int32_t* __re
         rf_pad_box4f(lo[k][1], hi[k][1], pad, &f.loy[k], &f.hiy[k]);
         rf_pad_box4f(lo[k][2], hi[k][2], pad, &f.loz[k], &f.hiz[k]);
     }
-    float org[3], cell[3];
+    float org[3] = {0.f, 0.f, 0.f}, cell[3] = {0.f, 0.f, 0.f};  // a node off the grid: no slabs
     uint32_t qlo[3], qhi[3];
     MeshNode4qc& q = nodes4q[i];
     if (rf_quantise4(lo, hi, ch, pad, org, cell, qlo, qhi))  // never false: the host has checked the coordinates
@@ -192,6 +193,19 @@ __global__ void k_refit_nodes4(uint32_t n_nodes, double pad, const int32_t* __re
             word = rf_cone_word(tri_normal, r[0], r[1], r[2], sum + 3 * (4 * size_t(i) + k));
         }
         q.cones.word[k] = word;
+        // the slab over the same run of slots: the corners as k_refit_tris forms the records (v0, p1 - p0, p2 - p0 in f64)
+        uint32_t slab = kNeutralSlab;
+        if (word != kNeutralCone) {
+            const uint32_t* r = run + 3 * (4 * size_t(i) + k);
+            slab = rf_slab_word(word, org, cell, pad, r[0], r[1], r[2], [&](uint32_t slot, double* v) {
+                const size_t t = tri_order[slot];
+                const double* p0 = positions + 3 * size_t(tri_pos[3 * t]);
+                const double* p1 = positions + 3 * size_t(tri_pos[3 * t + 1]);
+                const double* p2 = positions + 3 * size_t(tri_pos[3 * t + 2]);
+                for (int a = 0; a < 3; a++) { v[a] = p0[a]; v[3 + a] = p1[a] - p0[a]; v[6 + a] = p2[a] - p0[a]; }
+            });
+        }
+        q.slabs.word[k] = slab;
     }
 }
 
@@ -263,7 +277,7 @@ bool refit_mesh_launch(RefitMesh& rm, const RefitTarget<R>& t, hipStream_t strea
                        rm.tri_box.get(), rm.tri_normal.get(), rm.box4.get(), rm.sum4.get(), rm.run4.get());
     hipLaunchKernelGGL((k_refit_nodes2<R>), grid_for(rm.n_nodes), block, 0, stream, rm.n_nodes, rm.box2.get(), t.nodes);
     hipLaunchKernelGGL(k_refit_nodes4, grid_for(rm.n_nodes4), block, 0, stream, rm.n_nodes4, t.pad4, rm.child4.get(), rm.box4.get(), rm.sum4.get(), rm.run4.get(),
-                       rm.tri_normal.get(), t.nodes4, t.nodes4q);
+                       rm.tri_normal.get(), rm.tri_order.get(), rm.tri_pos.get(), rm.positions.get(), t.nodes4, t.nodes4q);
     REFIT_TRY(hipGetLastError());
     return true;
 }

@@ -169,16 +169,25 @@ static_assert(sizeof(BvhNode4q) == 64, "BvhNode4q must be 64 bytes");
 struct alignas(16) NodeCones4 {
     uint32_t word[4];
 };
-// What k_wf_mesh reads per node visit: the unchanged 64-B node and the cone words in ONE 128-B line (64 + 16 bytes read, five
-// 16-B loads).  The cone words as a second array parallel to the nodes (a second line request per visit) were 2.5 % of the
+// Normal slabs of the four children: per child the interval [lo, hi] of q . (x - org) / s over every vertex x below it, as two
+// signed 16-bit integers (lo in the low half), q = the integer axis bytes of the child's cone word, org the node's grid
+// origin and s = 4 max(cell).  k_wf_mesh skips an entered child when the part of the ray inside its box lies wholly on one
+// side of the slab (rt_traverse.h node4q_cull_slabs).  Builder and proof: rt_bvh.cpp.
+struct alignas(16) NodeSlabs4 {
+    uint32_t word[4];
+};
+// What k_wf_mesh reads per node visit: the unchanged 64-B node, the cone words and the slab words in ONE 128-B line (96 bytes
+// read, six 16-B loads).  The cone words as a second array parallel to the nodes (a second line request per visit) were 2.5 % of the
 // kernel slower on the headline mesh and 5 % on the 3.5 M-triangle one: profiles/r04/ab/backface_cones.txt.
 struct alignas(128) MeshNode4qc {
     BvhNode4q node;
     NodeCones4 cones;
-    uint32_t _pad[12];
+    NodeSlabs4 slabs;
+    uint32_t _pad[8];
 };
 static_assert(sizeof(MeshNode4qc) == 128, "one cache line per mesh node");
 constexpr uint32_t kNeutralCone = 0x7F000000u;  // (0, 0, 0, 127): never culls
+constexpr uint32_t kNeutralSlab = 0x7FFF8000u;  // [-32768, 32767], the word of a child without a cone (q = 0: the test sees 0)
 constexpr uint32_t kNoCullDir = 0x81000000u;    // (0, 0, 0, -127): the direction word of a ray that culls nothing
 
 // Triangle record for the intersection test: v0 and the two edges (mesh.rs:69-70 computes the

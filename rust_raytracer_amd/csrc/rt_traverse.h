@@ -152,8 +152,9 @@ constexpr float kNoEntry = __builtin_huge_valf();  // entry distance of a child 
 // plane = org + q * cell, so t = q * (cell * iv) + (org * iv - o * iv).  Explicit FMAs: the translation unit is built with
 // -ffp-contract=off for the f64 parity arithmetic, but this f32 test only culls (its rounding is inside the boxes' padding
 // either way).
+// fr[k] = the exit distance of child k (what the entry was compared with), for node4q_cull_slabs.
 template <typename R>
-RT_DEV uint32_t node4q_entries(uint4 h0, uint4 h1, uint4 h2, const CullRay<R>& cr, float tmax32, const int32_t (&ch)[4], float (&nr)[4]) {
+RT_DEV uint32_t node4q_spans(uint4 h0, uint4 h1, uint4 h2, const CullRay<R>& cr, float tmax32, const int32_t (&ch)[4], float (&nr)[4], float (&fr)[4]) {
     const float ax = __uint_as_float(h0.w) * cr.ivx, ay = __uint_as_float(h1.x) * cr.ivy, az = __uint_as_float(h1.y) * cr.ivz;
     const float bx = fmaf(__uint_as_float(h0.x), cr.ivx, -cr.oix), by = fmaf(__uint_as_float(h0.y), cr.ivy, -cr.oiy), bz = fmaf(__uint_as_float(h0.z), cr.ivz, -cr.oiz);
     // with lo <= hi the nearer plane of an axis is `lo` for a non-negative inverse direction, `hi` otherwise:
@@ -171,9 +172,51 @@ RT_DEV uint32_t node4q_entries(uint4 h0, uint4 h1, uint4 h2, const CullRay<R>& c
         const float tf = fminf(fminf(fmaf(fxk, ax, bx), fmaf(fyk, ay, by)), fminf(fmaf(fzk, az, bz), tmax32));
         const bool h = (tn <= tf) && ch[k] != kEmptyChild;
         nr[k] = h ? tn : kNoEntry;
+        fr[k] = tf;
         entered |= uint32_t(h) << k;
     }
     return entered;
+}
+template <typename R>
+RT_DEV uint32_t node4q_entries(uint4 h0, uint4 h1, uint4 h2, const CullRay<R>& cr, float tmax32, const int32_t (&ch)[4], float (&nr)[4]) {
+    float fr[4];
+    return node4q_spans(h0, h1, h2, cr, tmax32, ch, nr, fr);
+}
+
+// Normal slabs of a MeshNode4qc (cn: its cone words, sl: its sixth 16 bytes; builder and proof: rt_bvh.cpp): an entered child
+// whose span [nr, fr] of the culling ray lies wholly below or wholly above its slab becomes "not entered".  (o, d, t_shift):
+// the exact ray and where the culling ray starts on it.  leaves_only: RT_WF_SLABS=2.  nr[] of the children that stay, their
+// order and everything behind this step are untouched.  Explicit FMAs, as in node4q_spans.
+template <typename R>
+RT_DEV void node4q_cull_slabs(uint4 h0, uint4 h1, uint4 cn, uint4 sl, V3<R> o, V3<R> d, R t_shift, bool leaves_only, const int32_t (&ch)[4],
+                              const float (&fr)[4], float (&nr)[4]) {
+    const float cmax = fmaxf(fmaxf(__uint_as_float(h0.w), __uint_as_float(h1.x)), __uint_as_float(h1.y));
+    const float inv_s = __uint_as_float(0x7E000000u - __float_as_uint(cmax));  // 1 / (4 cmax): cmax = 2^e, e in [-100, 120]
+    const float rx = (float(fma(d.x, t_shift, o.x)) - __uint_as_float(h0.x)) * inv_s;
+    const float ry = (float(fma(d.y, t_shift, o.y)) - __uint_as_float(h0.y)) * inv_s;
+    const float rz = (float(fma(d.z, t_shift, o.z)) - __uint_as_float(h0.z)) * inv_s;
+    float ex = float(d.x) * inv_s;
+    const float ey = float(d.y) * inv_s, ez = float(d.z) * inv_s;
+    // the range the proof covers: direction 1e-20 < max |e| < 1e30, node no farther than 2^16 s from the origin and from the ray's
+    // start.  Outside it every pn, pf is NaN and nothing is culled.
+    const float em = fmaxf(fmaxf(fabsf(ex), fabsf(ey)), fabsf(ez));
+    const float gm = fmaxf(fmaxf(fmaxf(fabsf(__uint_as_float(h0.x)), fabsf(__uint_as_float(h0.y))), fabsf(__uint_as_float(h0.z))) * inv_s,
+                           fmaxf(fmaxf(fabsf(rx), fabsf(ry)), fabsf(rz)));
+    if (!(em > 1e-20f && em < 1e30f && gm < 65536.0f)) ex = __builtin_nanf("");
+    const uint32_t cw[4] = {cn.x, cn.y, cn.z, cn.w}, sw[4] = {sl.x, sl.y, sl.z, sl.w};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float qx = float(int(cw[k] << 24) >> 24), qy = float(int(cw[k] << 16) >> 24), qz = float(int(cw[k] << 8) >> 24);
+        const float A = fmaf(qx, rx, fmaf(qy, ry, qz * rz));
+        const float B = fmaf(qx, ex, fmaf(qy, ey, qz * ez));
+        const float pn = fmaf(nr[k], B, A), pf = fmaf(fr[k], B, A);
+        const float lo = float(int(sw[k] << 16) >> 16), hi = float(int(sw[k]) >> 16);
+        // both ends below lo or both above hi, without branches: fmaxf / fminf drop a NaN operand, and the only way to ONE NaN
+        // is tf = +inf with B = 0, where the true pf equals pn; with both NaN the comparisons fail
+        const bool out = bool(int(fmaxf(pn, pf) < lo) | int(fminf(pn, pf) > hi));
+        const bool may = bool(int(!leaves_only) | int(ch[k] < 0));
+        nr[k] = bool(int(out) & int(may)) ? kNoEntry : nr[k];
+    }
 }
 
 // Sorts the four (entry distance, child) pairs of the arrays nr / ch in place, nearest first (5 compare-exchanges); kNoEntry

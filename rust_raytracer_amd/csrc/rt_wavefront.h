@@ -817,16 +817,22 @@ template <typename R> constexpr uint32_t kMeshWaveLds = 1024u + 3u * 64u * uint3
 // The f32 form with quantised nodes fitted 95-96 VGPRs = 5 waves per SIMD on its own before the cone test added two registers;
 // it now asks the allocator for those 5 waves (no scratch: tools/kernel_regs.py).  At 4 waves its kernel was 4 % slower with the
 // cones than without them.
-template <typename R, bool STATS, int NODE, bool MULTI>
-__global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ? 5 : RT_MESH_WAVES) k_wf_mesh(SceneView<R> sc, WfPool<R> pool, const uint32_t* __restrict__ mesh_queue,
+// SLABS: the form with the normal-slab step behind the box test (node4q_cull_slabs), f64 and quantised nodes only: the step is not
+// result-preserving in f32 (rt_bvh.cpp).  It is a form of its own, not a branch: kept in one code object the step cost the runs that
+// skip it 0.6-0.9 % of the kernel (four exit distances live, one branch; profiles/mesh_slabs/README.md).  Its counting form needs 3 VGPRs
+// more than four waves leave (12 B of scratch) and asks for three waves; its time is no measurement.
+template <typename R, bool STATS, int NODE, bool MULTI, bool SLABS = false>
+__global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ? 5 : ((SLABS && STATS) ? 3 : RT_MESH_WAVES)) k_wf_mesh(SceneView<R> sc, WfPool<R> pool, const uint32_t* __restrict__ mesh_queue,
                                                                  WfCounters* __restrict__ ctr, DeviceCounters* counters,
                                                                  uint32_t refill_min, uint32_t inner_min,
                                                                  uint2* __restrict__ spill, int lds_levels,
                                                                  const uint32_t* __restrict__ n_ptr, uint32_t* __restrict__ cursor_ptr,
-                                                                 uint32_t cones_on, uint32_t handout_mode, uint32_t handout_256, uint32_t handout_128) {
+                                                                 uint32_t cones_on, uint32_t slabs_on, uint32_t handout_mode, uint32_t handout_256, uint32_t handout_128) {
     const HandoutPolicy handout{handout_mode, handout_256, handout_128};  // how the waves share the queue: rt_handout.h
     // n_ptr / cursor_ptr: length and hand-out cursor of `mesh_queue` (&ctr->n_mesh / &ctr->cursor)
     // cones_on: 0 = every ray gets the direction word that culls nothing (RT_WF_CONES=0, the A/B control)
+    // slabs_on (SLABS forms only): 2 = the step culls leaf children only (RT_WF_SLABS=2), otherwise every child
+    static_assert(!SLABS || (sizeof(R) == 8 && NODE == 1), "the slab step exists for f64 and quantised nodes");
     extern __shared__ uint2 lds_stack2[];
     MeshStack stk;
     stk.lds = (LdsByte*)lds_stack2;
@@ -1044,12 +1050,19 @@ __global__ void __launch_bounds__(256, (sizeof(R) == 4 && !STATS && NODE == 1) ?
                 float nr[4];
                 int32_t ch[4];
                 if constexpr (NODE == 1) {
-                    // five 16-B loads from one line
+                    // five 16-B loads from one line, six with the slab step
                     const uint4* nd = reinterpret_cast<const uint4*>(nodesq + node);
                     const uint4 h0 = nd[0], h1 = nd[1], h2 = nd[2];
                     const int4 cc = *reinterpret_cast<const int4*>(nd + 3);
-                    node4q_cull_cones(dirq, nd[4], cc, ch);
-                    node4q_entries(h0, h1, h2, cr, tmax32, ch, nr);
+                    const uint4 cn = nd[4];
+                    node4q_cull_cones(dirq, cn, cc, ch);
+                    if constexpr (SLABS) {
+                        float fr[4];
+                        node4q_spans(h0, h1, h2, cr, tmax32, ch, nr, fr);
+                        node4q_cull_slabs(h0, h1, cn, nd[5], o, d, cr.t_shift, slabs_on == 2u, ch, fr, nr);
+                    } else {
+                        node4q_entries(h0, h1, h2, cr, tmax32, ch, nr);
+                    }
                 } else {
                     const float4* nd = reinterpret_cast<const float4*>(nodes + node);
                     const uint32_t nearx = cr.negx() ? 3u : 0u, neary = cr.negy() ? 4u : 1u, nearz = cr.negz() ? 5u : 2u;  // float4 index of the near planes

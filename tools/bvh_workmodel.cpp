@@ -1,10 +1,14 @@
 // CPU work model of k_wf_mesh: node visits and triangle tests per mesh ray of the 4-wide BVH the kernel walks, with and
-// without the back-face cone test, on a small path tracer of scenes/cornell_dragon.  Host only; built by hand:
+// without the back-face cone test and the normal-slab test, on a small path tracer of scenes/cornell_dragon.  Host only; built by hand:
 //
 //   g++ -std=c++17 -O2 -Irust_raytracer_amd/csrc -o tools/bvh_workmodel tools/bvh_workmodel.cpp rust_raytracer_amd/csrc/rt_bvh.cpp
-//   tools/bvh_workmodel scenes/resource/dragon_high.obj [paths = 150000]
+//   tools/bvh_workmodel scenes/resource/dragon_high.obj [paths = 150000] [pad0]
 //
-// It links the repository's own build_bvh / collapse_bvh4 / build_mesh_cones and walks the tree exactly as the kernel
+// pad0: the slab words are built with the mesh pad m = 0, which leaves of the margin |q|_1 (2 m / s + 2^-12) only the constant
+// term (below 0.1 of the 16-bit step): what the slabs could be worth with no margin at all.  Such words are NOT safe for the kernel.
+//
+// It links the repository's own build_bvh / collapse_bvh4 / build_mesh_cones / build_mesh_slabs (the slab words are the
+// library's: same axis bytes, same 16-bit encoding, same margin; the step is node4q_cull_slabs restated in f32) and walks the tree exactly as the kernel
 // does: four slab tests per node, children sorted by entry distance, far children pushed, entries culled on pop, every
 // triangle of a leaf tested with the reference's front-face rule.  The boxes are exact here (the kernel's 8-bit boxes
 // add about 2 % to the visits of every tree alike).  With exact boxes it reproduces the counters of the headline
@@ -19,7 +23,10 @@
 #include <limits>
 #include <vector>
 
+#include <cstring>
+
 #include "rt_bvh.h"
+#include "rt_refit.h"
 #include "rt_scene.h"
 
 using namespace rt;
@@ -61,8 +68,37 @@ static bool load_obj(const char* path, Mesh* m) {
 
 struct Counters { unsigned long long rays = 0, visits = 0, tests = 0, hits = 0; };
 
-// Closest hit in (0.001, tmax) as k_wf_mesh finds it.  cones: 4 words per node, or nullptr.
-static bool traverse(const Bvh4Build& b, const std::vector<TriRec<double>>& tris, const uint32_t* cones, V o, V d, double tmax,
+// The slab tables of the tree: words and quantised nodes (grid origin, cells); mode 0 off, 1 every child, 2 leaf children only.
+struct Slabs { const uint32_t* words; const BvhNode4q* qnodes; int mode; double t_shift; };
+
+// node4q_cull_slabs of rt_traverse.h for one child, in f32: true if the span [tn, tf] (measured from o + d t_shift) lies
+// wholly outside the child's slab.
+static bool slab_culls(const Slabs& sl, size_t node, int k, uint32_t cone, V o, V d, float tn, float tf) {
+    const BvhNode4q& q = sl.qnodes[node];
+    const float cmax = std::fmax(std::fmax(q.cell[0], q.cell[1]), q.cell[2]);
+    uint32_t cb;
+    std::memcpy(&cb, &cmax, 4);
+    cb = 0x7E000000u - cb;
+    float inv_s;
+    std::memcpy(&inv_s, &cb, 4);
+    const float rx = (float(std::fma(d.x, sl.t_shift, o.x)) - q.org[0]) * inv_s, ry = (float(std::fma(d.y, sl.t_shift, o.y)) - q.org[1]) * inv_s,
+                rz = (float(std::fma(d.z, sl.t_shift, o.z)) - q.org[2]) * inv_s;
+    float ex = float(d.x) * inv_s;
+    const float ey = float(d.y) * inv_s, ez = float(d.z) * inv_s;
+    const float em = std::fmax(std::fmax(std::fabs(ex), std::fabs(ey)), std::fabs(ez));
+    const float gm = std::fmax(std::fmax(std::fmax(std::fabs(q.org[0]), std::fabs(q.org[1])), std::fabs(q.org[2])) * inv_s,
+                               std::fmax(std::fmax(std::fabs(rx), std::fabs(ry)), std::fabs(rz)));
+    if (!(em > 1e-20f && em < 1e30f && gm < 65536.0f)) ex = NAN;
+    const float qx = float(int8_t(cone & 0xFF)), qy = float(int8_t((cone >> 8) & 0xFF)), qz = float(int8_t((cone >> 16) & 0xFF));
+    const float A = std::fmaf(qx, rx, std::fmaf(qy, ry, qz * rz)), B = std::fmaf(qx, ex, std::fmaf(qy, ey, qz * ez));
+    const float pn = std::fmaf(tn, B, A), pf = std::fmaf(tf, B, A);
+    const uint32_t w = sl.words[4 * node + size_t(k)];
+    const float lo = float(int16_t(w & 0xFFFFu)), hi = float(int16_t(w >> 16));
+    return std::fmax(pn, pf) < lo || std::fmin(pn, pf) > hi;
+}
+
+// Closest hit in (0.001, tmax) as k_wf_mesh finds it.  cones: 4 words per node, or nullptr; sl: the slab test, or nullptr.
+static bool traverse(const Bvh4Build& b, const std::vector<TriRec<double>>& tris, const uint32_t* cones, const Slabs* sl, V o, V d, double tmax,
                      Counters& c, double* t_out, int* tri_out) {
     const V du = unit(d);
     const int dq[3] = {int(std::lround(du.x * 127)), int(std::lround(du.y * 127)), int(std::lround(du.z * 127))};
@@ -93,6 +129,9 @@ static bool traverse(const Bvh4Build& b, const std::vector<TriRec<double>>& tris
                 double t0z = (n.lo[k][2] - o.z) * iv.z, t1z = (n.hi[k][2] - o.z) * iv.z; if (t0z > t1z) std::swap(t0z, t1z);
                 const double tn = std::max(std::max(t0x, t0y), std::max(t0z, 0.0)), tf = std::min(std::min(t1x, t1y), std::min(t1z, tmax));
                 if (tn <= tf) nr[k] = tn;
+                if (tn <= tf && sl && sl->mode != 0 && (sl->mode == 1 || ch[k] < 0) &&
+                    slab_culls(*sl, size_t(node), k, cones[4 * size_t(node) + size_t(k)], o, d, float(tn - sl->t_shift), float(tf - sl->t_shift)))
+                    nr[k] = kInf;  // the entry distances of the others stay what they are
             }
             auto ce = [&](int a, int bb) { if (nr[a] > nr[bb]) { std::swap(nr[a], nr[bb]); std::swap(ch[a], ch[bb]); } };
             ce(0, 1); ce(2, 3); ce(0, 2); ce(1, 3); ce(1, 2);
@@ -177,6 +216,19 @@ int main(int argc, char** argv) {
     }
     std::vector<uint32_t> cones;
     build_mesh_cones(b4.nodes, tris, cone_limits(false), &cones);
+    // the quantised nodes and slab words as DeviceScene<R>::build derives them
+    const double pad = rf_pad_of_box(b4.root_lo, b4.root_hi);
+    std::vector<BvhNode4q> qnodes(b4.nodes.size());
+    const bool pad0 = argc > 3 && std::strcmp(argv[3], "pad0") == 0;
+    std::vector<double> pads(b4.nodes.size(), pad0 ? 0.0 : pad);
+    for (size_t i = 0; i < b4.nodes.size(); i++) {
+        const BuildNode4& sn = b4.nodes[i];
+        if (!rf_quantise4(sn.lo, sn.hi, sn.child, pad, qnodes[i].org, qnodes[i].cell, qnodes[i].qlo, qnodes[i].qhi)) { std::fprintf(stderr, "node off the grid\n"); return 1; }
+    }
+    std::vector<uint32_t> slab_words;
+    build_mesh_slabs(b4.nodes, tris, cones, qnodes.data(), pads.data(), &slab_words);
+    size_t with_slab = 0, with_cone = 0;
+    for (size_t i = 0; i < slab_words.size(); i++) { with_slab += slab_words[i] != kNeutralSlab; with_cone += cones[i] != kNeutralCone; }
     size_t leaf = 0, leaf_cone = 0, inner = 0, inner_cone = 0;
     for (size_t i = 0; i < b4.nodes.size(); i++)
         for (int k = 0; k < 4; k++) {
@@ -196,8 +248,9 @@ int main(int argc, char** argv) {
     auto to_obj_p = [&](V p) { const V q = p - T; return V{cs * q.x - sn * q.z, q.y, sn * q.x + cs * q.z} * (1.0 / S); };
     auto to_obj_d = [&](V d) { return V{cs * d.x - sn * d.z, d.y, sn * d.x + cs * d.z} * (1.0 / S); };
     auto to_world_d = [&](V d) { return V{cs * d.x + sn * d.z, d.y, -sn * d.x + cs * d.z}; };
-    Counters plain, coned, plain_hit, plain_miss;
-    unsigned long long total_rays = 0, mesh_rays = 0, changed = 0;
+    std::printf("slabs on %zu of the %zu children with a cone%s\n", with_slab, with_cone, pad0 ? " (pad0: margin without the mesh pad)" : "");
+    Counters plain, coned, plain_hit, plain_miss, slab_leaf, slab_all;
+    unsigned long long total_rays = 0, mesh_rays = 0, changed = 0, changed_leaf = 0, changed_all = 0;
     Rng rng{12345};
     for (int p = 0; p < n_paths; p++) {
         V o = {277.5, 277.5, -800};
@@ -231,13 +284,20 @@ int main(int argc, char** argv) {
             if (t0 <= t1) {
                 mesh_rays++;
                 Counters one;
-                mesh_hit = traverse(b4, tris, nullptr, oo, od, tw, one, &t_hit, &tri);
+                mesh_hit = traverse(b4, tris, nullptr, nullptr, oo, od, tw, one, &t_hit, &tri);
                 Counters& split = mesh_hit ? plain_hit : plain_miss;
                 for (Counters* dst : {&plain, &split}) { dst->rays++; dst->visits += one.visits; dst->tests += one.tests; dst->hits += one.hits; }
                 double t2 = tw;
                 int tri2 = -1;
-                const bool h2 = traverse(b4, tris, cones.data(), oo, od, tw, coned, &t2, &tri2);
+                const bool h2 = traverse(b4, tris, cones.data(), nullptr, oo, od, tw, coned, &t2, &tri2);
                 if (h2 != mesh_hit || (h2 && (tri2 != tri || t2 != t_hit))) changed++;
+                for (int mode = 2; mode >= 1; mode--) {
+                    const Slabs sl{slab_words.data(), qnodes.data(), mode, std::max(t0, 0.0)};  // the culling ray starts where the ray enters the box
+                    double t3 = tw;
+                    int tri3 = -1;
+                    const bool h3 = traverse(b4, tris, cones.data(), &sl, oo, od, tw, mode == 2 ? slab_leaf : slab_all, &t3, &tri3);
+                    if (h3 != mesh_hit || (h3 && (tri3 != tri || t3 != t_hit))) (mode == 2 ? changed_leaf : changed_all)++;
+                }
             }
             if (mesh_hit) {
                 const TriRec<double>& tr = tris[size_t(tri)];
@@ -262,5 +322,11 @@ int main(int argc, char** argv) {
                 per(plain_miss.tests, plain_miss.rays));
     std::printf("with cones:    %6.2f visits (%+.1f %%), %6.2f tests (%+.1f %%) per mesh ray; rays whose closest hit changed: %llu\n", per(coned.visits, coned.rays),
                 100.0 * (per(coned.visits, plain.visits) - 1.0), per(coned.tests, coned.rays), 100.0 * (per(coned.tests, plain.tests) - 1.0), changed);
-    return changed ? 2 : 0;
+    std::printf("+ slabs, leaf children: %6.2f visits (%+.1f %% of cones), %6.2f tests (%+.1f %%) per mesh ray; rays whose closest hit changed: %llu\n",
+                per(slab_leaf.visits, slab_leaf.rays), 100.0 * (per(slab_leaf.visits, coned.visits) - 1.0), per(slab_leaf.tests, slab_leaf.rays),
+                100.0 * (per(slab_leaf.tests, coned.tests) - 1.0), changed_leaf);
+    std::printf("+ slabs, every child:   %6.2f visits (%+.1f %% of cones), %6.2f tests (%+.1f %%) per mesh ray; rays whose closest hit changed: %llu\n",
+                per(slab_all.visits, slab_all.rays), 100.0 * (per(slab_all.visits, coned.visits) - 1.0), per(slab_all.tests, slab_all.rays),
+                100.0 * (per(slab_all.tests, coned.tests) - 1.0), changed_all);
+    return (changed || changed_leaf || changed_all) ? 2 : 0;
 }
