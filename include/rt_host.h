@@ -27,7 +27,8 @@ typedef struct RtHost RtHost;
  * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
  * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations>, --noise-threshold=<x>,
  * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>, --light-groups[=<max>],
- * --light-mix=<w0>,<w1>,... (unknown keys are ignored by the reference, config.rs:146, so these
+ * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>]
+ * (unknown keys are ignored by the reference, config.rs:146, so these
  * are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
  * the reference (main.rs:43, golden_monkey.rs:77). */
@@ -75,6 +76,17 @@ uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity);
  * (no ACES); the hit records stay on the device.  rth_load rejects malformed values, and --ao with --gpus > 1,
  * --progressive, --noise-threshold or --pick; rtrace refuses a scene with volumes before it renders anything.  rth_ao returns the samples (0: no flag) and the distance (+inf: unlimited). */
 uint32_t rth_ao(const RtHost* host, double* max_distance_out);
+/* Light probe (rt_render_rays): --probe=<x>,<y>,<z>[:<width>] (a finite position; width 2 .. 65536, default 512; the height
+ * is width / 2): rtrace renders the equirectangular panorama of rth_probe_rays at that point with the run's -s, -t, depth,
+ * bias, seed and precision and writes out_probe.png INSTEAD of the frame.  No pixel filter: every sample of a texel goes along
+ * its centre ray.  rth_load rejects malformed values, and --probe with --gpus > 1, --progressive, --noise-threshold, --pick,
+ * --ao, --light-groups, --denoise or --pipeline=mega.  rth_probe returns the width (0: no flag) and copies the position. */
+uint32_t rth_probe(const RtHost* host, double position_out[3]);
+/* The rays of an equirectangular light probe at `position`, +y up: width * height origins (= position) and directions,
+ * 3 doubles each, row-major with row 0 at the top.  Pixel (x, y): phi = ((2 pi) (x + 0.5)) / width - pi,
+ * theta = (pi (y + 0.5)) / height, direction = (sin theta sin phi, cos theta, -(sin theta cos phi)) with det_sin / det_cos
+ * of rt_detmath.h; f64, every operation rounded once, in this order.  The centre column looks along -z. */
+int rth_probe_rays(const double position[3], uint32_t width, uint32_t height, double* origins_out, double* dirs_out);
 uint32_t rth_samples_per_pixel(const RtHost* host); /* Camera::samples_per_pixel() */
 /* Row partition of `rtrace --gpus=N` (replaces the per-thread full-frame buffers of src/camera.rs:243-255): band height
  * for `height` image rows over `n_parts` GPUs = the largest of 16, 8, 4, 2, 1 rows that gives the most loaded part as few

@@ -674,6 +674,35 @@ int rt_bake_visibility_hits_device(const RtScene* scene, uint64_t n, const RtRay
 /* Of the last bake on this scene: rays = n * samples (skipped records included), kernel_ms of the bake kernel alone. */
 int rt_bake_stats(const RtScene* scene, RtRayQueryStats* out);
 
+/* ---- Rendering along caller-supplied rays -----------------------------------------------------
+ * Radiance per ray: light probes and environment captures, panoramic / orthographic / fisheye views, radiance towards surface
+ * points (lightmap and irradiance bakes), reflection captures.  The full path tracer - materials, the light-biased mixture
+ * sampler, volumes, every texture - started from n rays of the caller's instead of Camera::get_ray's.
+ * origins / dirs: n x 3 doubles each; directions need not be unit length.  rgba_out: n x 4 doubles, (r, g, b, 0) per ray.
+ * Of `params`: sqrt_spt (S), thread_count (T), max_depth, has_background / background, light_bias, seed and precision are used.
+ * Ray i behaves as pixel i of a frame whose camera sends every sample of that pixel along ray i: sample (t, i, st), t < T,
+ * st < S^2, uses the generator keyed (seed, t, i, st) as a render keys (seed, replica, pixel, stratum); its first two uniform
+ * draws - a camera's jitter - are drawn and discarded; the path then starts at (origins[i], dirs[i]) with max_depth.  In f32
+ * the ray is the table entry rounded to f32.  out[i] is the ordered sum a frame's pixel is: per replica the strata in order,
+ * / spp, then the replicas in order; f64, no atomics.  Hence, in f64: out[i] is pixel i of the reference's render with a
+ * camera of pixel deltas 0, position = o, first_pixel = o + d (where o + d and (o + d) - o are exact); with S = T = 1 and a
+ * camera without aperture the table of that camera's own rays gives rt_render's frame bit for bit; out[i] does not depend on
+ * n, the chunk size, the pool size, replica grouping or tail compaction.
+ * n = 0 is a no-op.  RT_E_INVALID with a message naming the field: a NULL array, n >= 2^31, n_parts > 1, a bad precision,
+ * sqrt_spt or thread_count of 0.  RT_E_UNSUPPORTED, as for light groups: RT_PIPELINE_MEGAKERNEL, collect_stats, max_depth = 0
+ * (RT_PIPELINE_AUTO runs the wavefront scheduler).  A scene with volumes is supported.  Non-finite ray components are not an
+ * error.  On any error the output is untouched.  rt_get_stats and the tail flag: as rt_render_device, samples = n T S^2.
+ * Synchronous; must not overlap a render or an update of the same scene (the render's workspace is used); sees the scene as
+ * rt_scene_update left it.  Rays run in chunks of RT_RAYS_CHUNK (environment variable, default 2^22 rays, at most 2^28), each
+ * rendered like a frame of that many pixels: inside a chunk the replicas are grouped by the per-sample buffer budget; the
+ * generators are keyed by the global index i.  The host variant's staging buffer belongs to the scene, grows only and is
+ * freed by rt_scene_destroy.                                                                                            */
+int rt_render_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params,
+                   double* rgba_out);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_render_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs,
+                          const RtRenderParams* params, double* d_rgba_out, void* stream);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

@@ -253,6 +253,10 @@ def load_host_lib() -> C.CDLL:
         lib.rth_pick.restype = C.c_uint32
         lib.rth_ao.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.rth_ao.restype = C.c_uint32
+        lib.rth_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        lib.rth_probe.restype = C.c_uint32
+        lib.rth_probe_rays.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+        lib.rth_probe_rays.restype = C.c_int
         lib.rth_log.argtypes = [C.c_void_p]
         lib.rth_log.restype = C.c_char_p
         lib.rth_make_camera.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double,
@@ -420,6 +424,12 @@ def load_device_lib() -> C.CDLL:
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
+        if hasattr(lib, "rt_render_rays"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_render_rays.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p]
+            lib.rt_render_rays.restype = C.c_int
+            lib.rt_render_rays_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p,
+                                                  C.c_void_p]
+            lib.rt_render_rays_device.restype = C.c_int
         if hasattr(lib, "rt_debug_live_resources"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
             lib.rt_debug_live_resources.restype = C.c_int
@@ -666,6 +676,9 @@ class HostScene:
         self.pick = [(int(x), int(y)) for x, y in xy]  # --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
         dist = C.c_double()
         self.ao = (int(lib.rth_ao(handle, C.byref(dist))), dist.value)  # --ao=<samples>[:<max_distance>]: (0, inf) without the flag
+        pos = (C.c_double * 3)()
+        width = int(lib.rth_probe(handle, pos))
+        self.probe = (width, tuple(pos)) if width else None  # --probe=<x>,<y>,<z>[:<width>]: (width, position), None without the flag
 
     @property
     def width(self) -> int:
@@ -736,6 +749,18 @@ def denoise_device(d_rgba: int, d_aov: int, width: int, height: int, d_out: int,
                                C.c_void_p(stream))
     if st != RT_OK:
         raise RtError(st, lib.rt_last_error().decode())
+
+
+def probe_rays(position, width: int, height: int) -> tuple:
+    """rth_probe_rays: the rays of an equirectangular light probe at `position` (+y up, row 0 at the top, the centre column
+    looking along -z) as (origins, dirs), (width * height, 3) float64 each, row-major; DeviceScene.render_rays takes them."""
+    lib = load_host_lib()
+    o = np.empty((int(width) * int(height), 3), dtype=np.float64)
+    d = np.empty_like(o)
+    st = lib.rth_probe_rays((C.c_double * 3)(*[float(x) for x in position]), width, height, o.ctypes.data, d.ctypes.data)
+    if st != RT_OK:
+        raise RtError(st, lib.rth_last_error().decode())
+    return o, d
 
 
 def save_png(path: str, rgba: np.ndarray) -> None:
@@ -908,6 +933,25 @@ class DeviceScene:
         st = self._lib.rt_occluded_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None),
                                           C.c_void_p(d_t_min_ptr or None), C.c_void_p(d_t_max_ptr or None), precision,
                                           C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def render_rays(self, origins, dirs, params: RtRenderParams) -> np.ndarray:
+        """rt_render_rays: the radiance along every ray as (n, 4) float64, (r, g, b, 0): ray i is rendered as pixel i of a frame
+        whose camera sends every sample along it (sqrt_spt, thread_count, max_depth, background, light_bias, seed and precision
+        of `params`).  origins / dirs: (n, 3) or (3,) (broadcast); directions need not be unit length."""
+        o, d = self._rays(origins, dirs)
+        out = np.empty((len(o), 4), dtype=np.float64)
+        st = self._lib.rt_render_rays(self._h, len(o), o.ctypes.data, d.ctypes.data, C.byref(params), out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out
+
+    def render_rays_device(self, n: int, d_origins_ptr: int, d_dirs_ptr: int, params: RtRenderParams, d_out_ptr: int,
+                           stream: int = 0) -> None:
+        """rt_render_rays_device: n x 3 doubles each in HBM -> n x 4 doubles in HBM."""
+        st = self._lib.rt_render_rays_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None),
+                                             C.byref(params), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
 

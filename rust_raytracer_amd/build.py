@@ -66,9 +66,10 @@ def build_host(force: bool = False) -> str:
     hdir = os.path.join(CSRC, "host")
     srcs = [os.path.join(hdir, s) for s in HOST_SRC]
     deps = srcs + [os.path.join(hdir, h) for h in ("hmath.h", "scene_builder.h", "host_internal.h")] + \
-        [os.path.join(REPO_DIR, "include", h) for h in ("rt_mi355.h", "rt_host.h")]
+        [os.path.join(REPO_DIR, "include", h) for h in ("rt_mi355.h", "rt_host.h", "rt_detmath.h")]
     if force or _newer(out, deps):
-        _run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-Wall", "-Wextra", "-o", out] + srcs + ["-lz"])
+        # -ffp-contract=off: rth_probe_rays promises one rounding per operation, whatever the target's instruction set
+        _run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-ffp-contract=off", "-Wall", "-Wextra", "-o", out] + srcs + ["-lz"])
         _stamp(out, deps)
     return out
 

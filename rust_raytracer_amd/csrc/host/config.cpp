@@ -259,6 +259,18 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             }
             cfg.ao_samples = uint32_t(samples);
             cfg.ao_max_distance = dist;
+        } else if (key == "-probe") {  // new: an equirectangular light probe at a point (rt_render_rays) instead of the frame
+            const size_t colon = value.find(':');
+            size_t width = 512;
+            if (!parse_vec3(value.substr(0, colon), v3, err)) return false;
+            if (!std::isfinite(v3[0]) || !std::isfinite(v3[1]) || !std::isfinite(v3[2]) ||
+                (colon != std::string::npos && (!parse_usize(value.substr(colon + 1), &width) || width < 2 || width > 65536))) {
+                *err = "Probe must be <x>,<y>,<z>[:<width>] (a finite position, a width from 2 to 65536)";
+                return false;
+            }
+            cfg.has_probe = true;
+            for (int a = 0; a < 3; a++) cfg.probe_position[a] = v3[a];
+            cfg.probe_width = uint32_t(width);
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -306,6 +318,12 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
     if (cfg.ao_samples && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty())) {
         *err = "--ao bakes the whole frame on one GPU after a one-shot render: it cannot be combined with --gpus > 1, --progressive, "
                "--noise-threshold or --pick";
+        return false;
+    }
+    if (cfg.has_probe && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.light_groups || cfg.denoise ||
+                          cfg.pipeline == RT_PIPELINE_MEGAKERNEL)) {
+        *err = "--probe renders a panorama on one GPU with the wavefront scheduler instead of the frame: it cannot be combined with --gpus > 1, "
+               "--progressive, --noise-threshold, --pick, --ao, --light-groups, --denoise or --pipeline=mega";
         return false;
     }
     if (cfg.thread_count == 0) {

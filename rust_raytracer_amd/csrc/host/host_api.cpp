@@ -3,6 +3,7 @@
 #include <cstring>
 
 #include "host_internal.h"
+#include "../../../include/rt_detmath.h"
 
 static thread_local std::string g_err;
 
@@ -99,6 +100,33 @@ uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity) {
 uint32_t rth_ao(const RtHost* host, double* max_distance_out) {
     if (max_distance_out) *max_distance_out = host->config.ao_max_distance;
     return host->config.ao_samples;
+}
+uint32_t rth_probe(const RtHost* host, double position_out[3]) {
+    if (!host->config.has_probe) return 0;
+    if (position_out)
+        for (int a = 0; a < 3; a++) position_out[a] = host->config.probe_position[a];
+    return host->config.probe_width;
+}
+// Equirectangular panorama, +y up, row 0 at the top, the centre column looking along -z.  Every product and sum below is one
+// f64 operation in the order written (the library is built without contraction): a test restates it in numpy.
+int rth_probe_rays(const double position[3], uint32_t width, uint32_t height, double* origins_out, double* dirs_out) {
+    if (!position || !origins_out || !dirs_out) return fail("rth_probe_rays: NULL argument");
+    if (width == 0 || height == 0) return fail("rth_probe_rays: width and height must be positive");
+    const double pi = 3.14159265358979323846;
+    for (uint32_t y = 0; y < height; y++) {
+        const double theta = (pi * (double(y) + 0.5)) / double(height);
+        const double st = det_sin(theta), ct = det_cos(theta);
+        for (uint32_t x = 0; x < width; x++) {
+            const double phi = ((2.0 * pi) * (double(x) + 0.5)) / double(width) - pi;
+            const double sp = det_sin(phi), cp = det_cos(phi);
+            const size_t i = 3 * (size_t(y) * width + x);
+            origins_out[i] = position[0]; origins_out[i + 1] = position[1]; origins_out[i + 2] = position[2];
+            dirs_out[i] = st * sp;
+            dirs_out[i + 1] = ct;
+            dirs_out[i + 2] = -(st * cp);
+        }
+    }
+    return RT_OK;
 }
 double rth_noise_threshold(const RtHost* host) { return host->config.noise_threshold; }
 int32_t rth_adaptive_min(const RtHost* host) { return host->config.adaptive_min; }

@@ -8,7 +8,11 @@
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 //   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
-//   --ao=<samples>[:<max_distance>]
+//   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]
+// --probe=<x>,<y>,<z>[:<width>] renders no frame: an equirectangular light probe at that point (+y up, the centre column looking
+// along -z; width 512 by default, height = width / 2) is rendered with rt_render_rays along the rays of rth_probe_rays, with the
+// run's -s, -t, depth, bias, seed and precision, and written to out_probe.png through the output stage of out.png.  There is no
+// pixel filter: every sample of a texel goes along the texel's centre ray.
 // --pick=<x>,<y>[:...] renders nothing: the ray through the centre of each named pixel (no lens, no jitter) is cast with
 // rt_trace_rays and one line per pixel is printed: node, node type, material, triangle, t, position.
 // --ao=<samples>[:<max_distance>] also writes out_ao.png: the --pick ray of every pixel is cast on the device
@@ -230,6 +234,25 @@ static int pick_pixels(RtHost* host) {
     return 0;
 }
 
+// --probe: the panorama at the named point to out_probe.png; returns the process exit status.
+static int render_probe(RtHost* host, const std::function<double()>& since) {
+    double position[3];
+    const uint32_t W = rth_probe(host, position), H = W / 2;
+    const size_t n = size_t(W) * H;
+    std::vector<double> o(3 * n), d(3 * n), frame(4 * n);
+    if (rth_probe_rays(position, W, H, o.data(), d.data()) != RT_OK) return fail(rth_last_error());
+    RtScene* scene = nullptr;
+    if (rt_scene_create(rth_scene(host), 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    if (rt_render_rays(scene, n, o.data(), d.data(), rth_params(host), frame.data()) != RT_OK) return fail(rt_last_error());
+    std::printf("Probe at %.17g %.17g %.17g: %ux%u texels, no pixel filter (every sample along the texel's centre ray)\n", position[0], position[1],
+                position[2], W, H);
+    std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());
+    if (rth_save_png("out_probe.png", frame.data(), W, H) != RT_OK) return fail(rth_last_error());
+    std::printf("Done! Took %s. Goodbye :)\n", fmt_duration(since()).c_str());
+    return 0;
+}
+
 // --ao: visibility of every pixel's first hit (w * h values, row-major; 1 where the pixel sees no surface); false with *err
 // set on failure.
 static bool bake_ao(const RtScene* scene, const RtCameraDesc* cam, const RtRenderParams* params, uint32_t samples, double max_distance,
@@ -318,6 +341,12 @@ int main(int argc, char** argv) {
     }
     if (rth_pick(host, nullptr, 0) != 0) {
         const int rc = pick_pixels(host);
+        rth_destroy(host);
+        return rc;
+    }
+    if (rth_probe(host, nullptr) != 0) {
+        if (!sequence.empty()) return fail("--probe renders a panorama instead of the frame: it cannot be combined with --sequence");
+        const int rc = render_probe(host, since);
         rth_destroy(host);
         return rc;
     }

@@ -684,6 +684,10 @@ struct RtScene {
         rt::ChunkStage stage;
         RtRayQueryStats stats{};
     } bake;
+    // renders along ray tables (rt_render_rays): the host variant's staging buffer; the kernels run on the render's workspace (wf)
+    struct Rays {
+        rt::ChunkStage stage;
+    } rays;
     ~RtScene() { if (device >= 0) (void)hipSetDevice(device); }  // before the members go: the owners do not switch devices
 };
 
@@ -837,6 +841,12 @@ template <typename R, typename G>
 ShadeKernel<R, G> pick_shade_lean(int lds, bool tex) {
     if (tex) return &k_wf_shade<R, false, 0, true, G>;
     return lds == 1 ? &k_wf_shade<R, false, 1, false, G> : (lds == 2 ? &k_wf_shade<R, false, 2, false, G> : &k_wf_shade<R, false, 0, false, G>);
+}
+// Ray tables (WfGroupRays): the lean variants, and the fused one where a plain render of the scene would run it.
+template <typename R>
+ShadeKernel<R, WfGroupRays<R>> pick_shade_rays(int lds, bool tex, bool fuse) {
+    if (fuse) return &k_wf_shade<R, false, 1, false, WfGroupRays<R>, true>;
+    return pick_shade_lean<R, WfGroupRays<R>>(lds, tex);
 }
 // Dense groups also have the counting variants and the one fused kernel (+ k_wf_prims' search as phase 4).
 template <typename R>
@@ -1067,6 +1077,14 @@ struct LightGroupPass {
     double* d_groups_out = nullptr;
 };
 
+// A render along a ray table (rt_render_rays): one chunk of the caller's table.  The "frame" is n x 1
+// pixels, pixel i = ray first + i; origins / dirs are device pointers to the chunk's first ray.
+struct RayTablePass {
+    const double* origins = nullptr;
+    const double* dirs = nullptr;
+    uint64_t first = 0;
+};
+
 // Pool size of a render.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
 // dependent fetches) and the streaming kernels run better in few large launches, so fewer, larger launches win; against that
 // stands the tail: the pool is what drains at the end of a replica group, over ~20 ever smaller iterations.  Round 2 (tail at
@@ -1209,8 +1227,9 @@ int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, const
 template <typename R>
 int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
                      uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr,
-                     const LightGroupPass* lg = nullptr) {
+                     const LightGroupPass* lg = nullptr, const RayTablePass* rays = nullptr) {
     CameraView<R> cv = make_camera_view<R>(cam, p);
+    if (rays) cv.has_aperture = 1;  // every sample has an origin of its own: k_wf_shade's restarts store it (phase 2)
     ParamsView<R> pv = make_params_view<R>(p, owned);
     const uint64_t npix_frame = uint64_t(cam.image_width) * owned;
     const bool sparse = ad && ad->sparse;
@@ -1218,6 +1237,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     if (ad && p.collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
     if (npix == 0) return set_err(RT_E_INVALID, "adaptive pass without active pixels");
     if (lg && (ad || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "light groups have no adaptive or counting kernels (collect_stats)");
+    if (rays && (ad || lg || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "ray tables have no adaptive, light-group or counting kernels (collect_stats)");
     const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
     const uint32_t T = p.thread_count;
     const uint32_t t_end = t_first + n;
@@ -1264,7 +1284,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // k_wf_prims as phase 4 of k_wf_shade (rt_wavefront.h): the lean dense variant with BOTH table sets staged whole in LDS, the
     // prims set within what the shade kernel may ask for at five workgroups per CU.  With the tables in global memory the fused
     // kernel needs scratch (f64 32 B, f32 80 B; tools/kernel_regs.py), so those scenes - and volumes, re-built groups, the texture
-    // interpreter, sparse adaptive passes, light-group renders and the counting variants - keep the stand-alone kernel.
+    // interpreter, sparse adaptive passes, light-group renders and the counting variants - keep the stand-alone kernel.  A ray
+    // table runs the form a plain render of the scene runs.
     // Programs with more than one mesh op keep it too: tests/scenes/two_meshes lost 2.4 % of its frame fused (DESIGN.md section 6,
     // round 5).  RT_WF_FUSE=0: the unfused pipeline (A/B control, reference of the tests); 2: fused wherever the kernel exists,
     // whatever the plan says (tests, A/B).
@@ -1277,6 +1298,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     const ShadeKernel<R, WfGroup<R>> shade_dense = pick_shade<R>(stats, lds_shade, tex, fuse);
     const ShadeKernel<R, WfGroupSparse<R>> shade_sparse = pick_shade_lean<R, WfGroupSparse<R>>(lds_shade, tex);
     const ShadeKernel<R, WfGroupLG<R>> shade_lg = pick_shade_lean<R, WfGroupLG<R>>(lds_shade, tex);
+    const ShadeKernel<R, WfGroupRays<R>> shade_rays = pick_shade_rays<R>(lds_shade, tex, fuse);
 
     HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DeviceCounters), stream));
     HIP_TRY(hipEventRecord(s->ev0, stream));
@@ -1302,6 +1324,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         grp_lg.sample_G = w.sample_G;
         grp_lg.table = w.lg_table;
         grp_lg.n_materials = lg ? lg->n_materials : 0u;
+        WfGroupRays<R> grp_r{};
+        static_cast<WfGroup<R>&>(grp_r) = grp;
+        if (rays) { grp_r.origins = rays->origins; grp_r.dirs = rays->dirs; grp_r.first = rays->first; }
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
         uint32_t first = uint32_t(std::min<uint64_t>(capacity, grp.total));
         pool = pool_a;
@@ -1316,7 +1341,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         init.next_sample = first;
         *w.h_ctr = init;
         HIP_TRY(hipMemcpyAsync(w.d_ctr, w.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-        if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, queue[0]);
+        if (rays) hipLaunchKernelGGL((k_wf_generate<R, WfGroupRays<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_r, cv, pv, queue[0]);
+        else if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, queue[0]);
         else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, queue[0]);
         int qi = 0;
         bool hits_ready = false;  // the hit records and the mesh queue of the current queue exist already (phase 4 of a fused k_wf_shade)
@@ -1350,7 +1376,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                     ty.search_launches++;
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 }
-                if (lg) launch_shade(shade_lg, grp_lg);
+                if (rays) launch_shade(shade_rays, grp_r);
+                else if (lg) launch_shade(shade_lg, grp_lg);
                 else if (sparse) launch_shade(shade_sparse, grp_s);
                 else launch_shade(shade_dense, grp);
                 if (fuse) hits_ready = true;  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
@@ -1634,6 +1661,50 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
     if (int st = run_chunks(b.stage, n, bake_chunk(), host, in, out, sizeof(RtBakeResult), stream, launch, &t)) return st;
     record_query_stats<R>(b.stats, t, n * bp.samples);
     return RT_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Renders along ray tables (include/rt_mi355.h)
+// ---------------------------------------------------------------------------------------------
+// Rays per chunk.  A chunk is rendered like a frame of that many pixels (pool, per-sample buffer, replica groups), so the
+// default is a frame's order of magnitude, 2^22 = a 2048 x 2048 image; it is a guess, not a measurement.  At most 2^28: the
+// kernels index the table with 32-bit element offsets.
+static uint32_t rays_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(1u, env_u32("RT_RAYS_CHUNK", 1u << 22))); }
+
+// n rays in chunks through render_wavefront, each chunk a frame of m x 1 pixels whose pixel i is ray off + i.  host: the
+// arrays are the caller's host memory and go through the scene's staging buffer.  The scene's stats are the sums over the chunks;
+// the tail flag belongs to the last chunk.
+template <typename R>
+int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const RtRenderParams& p,
+                      double* out, bool host, hipStream_t stream) {
+    const uint32_t chunk = rays_chunk();
+    RtCameraDesc cam{};  // only the width is read: a ray table has no camera arithmetic
+    cam.image_height = 1;
+    RtRenderStats sum{};
+    int32_t* const tail_flag = s->tail_flag;
+    ChunkTimes t;
+    auto launch = [&](uint64_t off, uint32_t m, const void* const* d_in, void* d_out) -> int {
+        RayTablePass rp;
+        rp.origins = static_cast<const double*>(d_in[0]);
+        rp.dirs = static_cast<const double*>(d_in[1]);
+        rp.first = off;
+        cam.image_width = m;
+        s->tail_flag = off + m >= n ? tail_flag : nullptr;
+        const int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, static_cast<double*>(d_out), stream, nullptr, nullptr, &rp);
+        s->tail_flag = tail_flag;
+        if (st != RT_OK) return st;
+        const RtRenderStats c = s->stats;
+        RtRenderStats acc = c;  // what describes the kernels is the same in every chunk; times and counts add up
+        acc.kernel_ms += sum.kernel_ms; acc.traversal_kernel_ms += sum.traversal_kernel_ms;
+        acc.prims_kernel_ms += sum.prims_kernel_ms; acc.shade_kernel_ms += sum.shade_kernel_ms;
+        acc.n_launches += sum.n_launches; acc.samples += sum.samples; acc.n_iterations += sum.n_iterations;
+        acc.n_replica_groups += sum.n_replica_groups; acc.n_tail_compactions += sum.n_tail_compactions;
+        sum = acc;
+        return RT_OK;
+    };
+    const int st = run_chunks(s->rays.stage, n, chunk, host, {{origins, 24}, {dirs, 24}}, out, 4 * sizeof(double), stream, launch, &t);
+    if (st == RT_OK) s->stats = sum;
+    return st;
 }
 
 // Makes sure the scene's tables in the arithmetic of `precision` are on the device (built on first use), then f(tables).
@@ -3213,6 +3284,47 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
     e = hipMemcpy(rgba_out, d_out, frame, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
     return RT_OK;
+}
+
+// ---- Renders along ray tables -----------------------------------------------------------------------------------------------
+static int render_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params,
+                            double* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    const std::string w = std::string(who) + ": ";
+    if (!scene) return set_err(RT_E_INVALID, w + "scene is NULL");
+    if (!params) return set_err(RT_E_INVALID, w + "params is NULL");
+    if (params->sqrt_spt == 0) return set_err(RT_E_INVALID, w + "sqrt_spt must be positive");
+    if (params->thread_count == 0) return set_err(RT_E_INVALID, w + "thread_count must be positive");
+    if (params->precision != RT_PRECISION_F64 && params->precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, w + "precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
+    if (params->n_parts > 1) return set_err(RT_E_INVALID, w + "n_parts > 1: a ray table has no row partition");
+    if (n >= (1ull << 31)) return set_err(RT_E_INVALID, w + "n must be below 2^31");
+    if (uint64_t(params->sqrt_spt) * params->sqrt_spt * params->thread_count > 0xFFFFFFFFull) return set_err(RT_E_UNSUPPORTED, w + "more than 2^32 samples per ray (sqrt_spt, thread_count)");
+    if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, w + "ray tables run the wavefront scheduler: pipeline = RT_PIPELINE_MEGAKERNEL is not supported");
+    if (params->pipeline != RT_PIPELINE_AUTO && params->pipeline != RT_PIPELINE_WAVEFRONT) return set_err(RT_E_INVALID, w + "unknown pipeline");
+    if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, w + "max_depth = 0 is not supported");
+    if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, w + "ray tables have no counting kernels (collect_stats)");
+    if (n == 0) return RT_OK;
+    if (!origins) return set_err(RT_E_INVALID, w + "origins is NULL");
+    if (!dirs) return set_err(RT_E_INVALID, w + "dirs is NULL");
+    if (!out) return set_err(RT_E_INVALID, w + "rgba_out is NULL");
+    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
+    HIP_TRY(hipSetDevice(s->device));
+    RtRenderParams p = *params;
+    p.band_rows = p.n_parts = p.part = 0;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    return with_tables(s, p.precision, [&](auto& ds) -> int { return render_rays_typed(s, ds, n, origins, dirs, p, out, host, st); });
+}
+
+int rt_render_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params, double* rgba_out) {
+    const int r = render_rays_impl(scene, n, origins, dirs, params, rgba_out, true, nullptr, "rt_render_rays");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
+    return r;
+}
+int rt_render_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const RtRenderParams* params,
+                          double* d_rgba_out, void* stream) {
+    const int r = render_rays_impl(scene, n, d_origins, d_dirs, params, d_rgba_out, false, stream, "rt_render_rays_device");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
+    return r;
 }
 
 // ---- Ray queries (rt_query.hip) -----------------------------------------------------------------------------------------

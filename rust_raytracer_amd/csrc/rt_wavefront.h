@@ -80,6 +80,7 @@ struct WfGroup {
     uint32_t strata;       // S*S
     static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = false;
+    static constexpr bool kRays = false;
 };
 
 // Replica group of an adaptive pass over a SUBSET of the pixels: `npix` counts the active pixels and
@@ -92,6 +93,7 @@ struct WfGroupSparse : WfGroup<R> {
     const uint32_t* active;
     static constexpr bool kSparse = true;
     static constexpr bool kLightGroups = false;
+    static constexpr bool kRays = false;
 };
 
 // Replica group of a light-group render (include/rt_mi355.h): k_wf_shade also stores the group of every
@@ -106,6 +108,22 @@ struct WfGroupLG : WfGroup<R> {
     uint32_t n_materials;
     static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = true;
+    static constexpr bool kRays = false;
+};
+
+// Replica group of a render along a ray table (rt_render_rays): "pixel" i of the group is ray i of a chunk
+// of the caller's table, and a sample's first ray is that entry instead of a camera's.  `origins` / `dirs` point at the chunk's
+// first ray (3 doubles per ray each), `first` is that ray's index in the whole table: the generators are keyed by the global
+// index, so a ray's samples do not depend on the chunk it falls into.  `npix` is the chunk's ray count.  A type of its own for
+// the reason WfGroupSparse is one.
+template <typename R>
+struct WfGroupRays : WfGroup<R> {
+    const double* origins;
+    const double* dirs;
+    uint64_t first;
+    static constexpr bool kSparse = false;
+    static constexpr bool kLightGroups = false;
+    static constexpr bool kRays = true;
 };
 
 // floor(a / b) and the remainder for a < 2^51: the reciprocal estimate is off by at most one, the remainder test makes it
@@ -126,6 +144,18 @@ RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, co
     uint64_t rem, pix, px64;
     const uint32_t tid_local = uint32_t(div_by(s, grp.per_replica, grp.inv_per_replica, rem));
     const uint32_t st = uint32_t(div_by(rem, grp.npix, grp.inv_npix, pix));
+    if constexpr (G::kRays) {
+        // The stream of ray i is the stream of pixel i: keyed alike, and a camera's two jitter draws are made and dropped, so
+        // that the path's own draws are the ones a frame's sample would make.  No camera arithmetic, no row partition.  The
+        // six doubles are loaded last: they live from here to the caller's pool stores and no longer.
+        rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
+        rng.next();
+        rng.next();
+        const uint32_t at3 = uint32_t(pix) * 3u;  // the driver keeps a chunk below 2^28 rays
+        o = mk<R>(R(grp.origins[at3]), R(grp.origins[at3 + 1u]), R(grp.origins[at3 + 2u]));
+        d = mk<R>(R(grp.dirs[at3]), R(grp.dirs[at3 + 1u]), R(grp.dirs[at3 + 2u]));
+        return;
+    }
     if constexpr (G::kSparse) pix = grp.active[pix];
     const uint32_t row = uint32_t(div_by(pix, cam.width, grp.inv_width, px64));
     const uint32_t px = uint32_t(px64);
@@ -1221,8 +1251,9 @@ __device__ unsigned long long g_shade_stamps[16];
 #define RT_STAMP(k) do { } while (0)
 #endif
 
-// G: WfGroup<R>, WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels, or WfGroupLG<R> to record the
-// light group of every terminal
+// G: WfGroup<R>, WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels, WfGroupLG<R> to record the
+// light group of every terminal, or WfGroupRays<R> for restarts on a ray table (the driver then passes a camera WITH aperture:
+// the origin of a restarted slot is phase 2's to store)
 // FUSED: the workgroup then runs k_wf_prims' search over the slots it has just put into the next queue (phase 4 below), so that
 // the next iteration starts at k_wf_mesh.  The prims tables are staged whole over the shade tables.  The two codes share no
 // live value: the kernel needs the larger of the two register counts, not their sum (the round-2 fusion inlined the search
