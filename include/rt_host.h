@@ -27,7 +27,7 @@ typedef struct RtHost RtHost;
  * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
  * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations>, --noise-threshold=<x>,
  * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>, --light-groups[=<max>],
- * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>]
+ * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>], --irradiance
  * (unknown keys are ignored by the reference, config.rs:146, so these
  * are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
@@ -76,6 +76,13 @@ uint32_t rth_pick(const RtHost* host, uint32_t* xy_out, uint32_t capacity);
  * (no ACES); the hit records stay on the device.  rth_load rejects malformed values, and --ao with --gpus > 1,
  * --progressive, --noise-threshold or --pick; rtrace refuses a scene with volumes before it renders anything.  rth_ao returns the samples (0: no flag) and the distance (+inf: unlimited). */
 uint32_t rth_ao(const RtHost* host, double* max_distance_out);
+/* Irradiance bake (rt_bake_irradiance_hits_device): --irradiance (no value): rtrace also writes out_irradiance.png, the
+ * cosine-weighted mean of the radiance arriving at the first hit of the ray through every pixel's centre (the --pick ray),
+ * with the run's -s, -t, depth, bias, seed and precision, through the output stage of out.png; a pixel that sees no surface is
+ * black; the hit records stay on the device.  rth_load rejects --irradiance with --gpus > 1, --progressive, --noise-threshold,
+ * --pick, --ao or --probe; rtrace refuses a scene with volumes (the ray queries have none) and --sequence before it renders
+ * anything.  rth_irradiance returns 1 with the flag, 0 without.                                                              */
+int rth_irradiance(const RtHost* host);
 /* Light probe (rt_render_rays): --probe=<x>,<y>,<z>[:<width>] (a finite position; width 2 .. 65536, default 512; the height
  * is width / 2): rtrace renders the equirectangular panorama of rth_probe_rays at that point with the run's -s, -t, depth,
  * bias, seed and precision and writes out_probe.png INSTEAD of the frame.  No pixel filter: every sample of a texel goes along

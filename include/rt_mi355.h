@@ -703,6 +703,44 @@ int rt_render_rays(const RtScene* scene, uint64_t n, const double* origins, cons
 int rt_render_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs,
                           const RtRenderParams* params, double* d_rgba_out, void* stream);
 
+/* ---- Irradiance at surface points ---------------------------------------------------------------
+ * Lightmap and vertex-colour bakes, irradiance caches, "clay" previews: the full path tracer - materials, the light-biased
+ * mixture sampler, volumes, every texture - started from n surface points in cosine-weighted directions about their normals.
+ * One fused pass: the directions are formed in registers, 48 B in and 32 B out per POINT, no ray table.
+ * positions / normals: n x 3 doubles each; normals need not be unit length.  rgba_out: n x 4 doubles, (r, g, b, 0) per point.
+ * Of `params`: sqrt_spt (S), thread_count (T), max_depth, has_background / background, light_bias, seed and precision are used;
+ * R = double or float by the precision.  For point i (its index in the whole call), replica t < T, stratum st = sy S + sx:
+ *     Rng g keyed (seed, t, i, st) as a render keys (seed, replica, pixel, stratum);
+ *     r1, r2 = the generator's first two uniforms - the two draws a camera spends on its jitter;
+ *     u1 = (R(sx) + r1) * inv_S,  u2 = (R(sy) + r2) * inv_S              (inv_S = R(1.0 / double(S)), as the camera forms it)
+ *     c = (cos(phi) sqrt(u2), sin(phi) sqrt(u2), sqrt(1 - u2)),  phi = u1 * 2 * pi       (vec4.rs:50-61 with u1, u2 for its draws)
+ *     w = R(normal_i) / |R(normal_i)|,  (u, v) the reference's basis about w (utils.rs:17-28),  d = u c.x + v c.y + w c.z + 0 * 0
+ *     o = R(pos_i),  d' = (o + d) - o     (two roundings per component: what the reference's camera returns for position = o,
+ *                                          first_pixel = o + d, pixel deltas 0, no aperture)
+ *     the path starts at (o, d') with max_depth, on g as it now stands: its first draw is the third of the stream, as in a frame.
+ * The first segment has the path's usual t_min = 0.001, like a scattered ray leaving a hit; there is no bias parameter.
+ * out[i] is the ordered sum a frame's pixel is: per replica the strata in order, / (S^2 T), then the replicas in order; f64, no
+ * atomics.  It is the cosine-weighted mean of the incoming radiance: irradiance = pi * out, the outgoing radiance of a
+ * Lambertian texel = albedo * out; no factor is applied on the device.  Hence, in f64, sample (t, i, st) is the reference's
+ * sample (t, pixel i, st) with that camera, and out[i] does not depend on n, the chunk size, the pool size, replica grouping or
+ * tail compaction.  A zero or non-finite normal is not an error: the result is what the arithmetic gives.
+ * Rules, stats and the tail flag: rt_render_rays's.  n = 0 is a no-op.  RT_E_INVALID with a message naming the field: a NULL
+ * array, n >= 2^31, n_parts > 1, a bad precision, sqrt_spt or thread_count of 0.  RT_E_UNSUPPORTED: RT_PIPELINE_MEGAKERNEL,
+ * collect_stats, max_depth = 0.  Everything is checked before the device is touched; on any error the output is untouched.
+ * A scene with volumes is supported.  rt_get_stats: samples = n T S^2.  Synchronous; must not overlap a render or an update of
+ * the same scene; sees the scene as rt_scene_update left it.  Points run in chunks of RT_RAYS_CHUNK, like rays.             */
+int rt_bake_irradiance(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRenderParams* params,
+                       double* rgba_out);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_bake_irradiance_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals,
+                              const RtRenderParams* params, double* d_rgba_out, void* stream);
+/* The points are hit records on the device (rt_trace_rays_device): pos (offset 8) and normal (offset 32) of record i, flags at
+ * offset 84, 96 bytes apart.  A record without RT_RAY_HIT or with RT_RAY_ENVIRONMENT has no surface point: (0, 0, 0, 0) exactly
+ * (written after the resolve; samples = n T S^2 counts such records too).  Scenes with volumes have no ray queries, so no
+ * records to pass.                                                                                                      */
+int rt_bake_irradiance_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtRenderParams* params,
+                                   double* d_rgba_out, void* stream);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

@@ -253,6 +253,8 @@ def load_host_lib() -> C.CDLL:
         lib.rth_pick.restype = C.c_uint32
         lib.rth_ao.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.rth_ao.restype = C.c_uint32
+        lib.rth_irradiance.argtypes = [C.c_void_p]
+        lib.rth_irradiance.restype = C.c_int
         lib.rth_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.rth_probe.restype = C.c_uint32
         lib.rth_probe_rays.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -430,6 +432,14 @@ def load_device_lib() -> C.CDLL:
             lib.rt_render_rays_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p,
                                                   C.c_void_p]
             lib.rt_render_rays_device.restype = C.c_int
+        if hasattr(lib, "rt_bake_irradiance"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_bake_irradiance.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p]
+            lib.rt_bake_irradiance.restype = C.c_int
+            lib.rt_bake_irradiance_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p,
+                                                      C.c_void_p]
+            lib.rt_bake_irradiance_device.restype = C.c_int
+            lib.rt_bake_irradiance_hits_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p, C.c_void_p]
+            lib.rt_bake_irradiance_hits_device.restype = C.c_int
         if hasattr(lib, "rt_debug_live_resources"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
             lib.rt_debug_live_resources.restype = C.c_int
@@ -676,6 +686,7 @@ class HostScene:
         self.pick = [(int(x), int(y)) for x, y in xy]  # --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
         dist = C.c_double()
         self.ao = (int(lib.rth_ao(handle, C.byref(dist))), dist.value)  # --ao=<samples>[:<max_distance>]: (0, inf) without the flag
+        self.irradiance = bool(lib.rth_irradiance(handle))  # --irradiance: also bake out_irradiance.png
         pos = (C.c_double * 3)()
         width = int(lib.rth_probe(handle, pos))
         self.probe = (width, tuple(pos)) if width else None  # --probe=<x>,<y>,<z>[:<width>]: (width, position), None without the flag
@@ -952,6 +963,35 @@ class DeviceScene:
         """rt_render_rays_device: n x 3 doubles each in HBM -> n x 4 doubles in HBM."""
         st = self._lib.rt_render_rays_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None),
                                              C.byref(params), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def bake_irradiance(self, positions, normals, params: RtRenderParams) -> np.ndarray:
+        """rt_bake_irradiance: the cosine-weighted mean of the radiance arriving at every surface point as (n, 4) float64,
+        (r, g, b, 0): S^2 x T paths per point from the full path tracer, their first directions drawn about the normal on the
+        device (sqrt_spt, thread_count, max_depth, background, light_bias, seed and precision of `params`).  Irradiance is
+        pi * out, a Lambertian texel's outgoing radiance albedo * out.  positions / normals: (n, 3) or (3,) (a single normal or
+        position broadcasts); normals need not be unit length."""
+        p, nr = self._rays(positions, normals)
+        out = np.empty((len(p), 4), dtype=np.float64)
+        st = self._lib.rt_bake_irradiance(self._h, len(p), p.ctypes.data, nr.ctypes.data, C.byref(params), out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out
+
+    def bake_irradiance_device(self, n: int, d_positions_ptr: int, d_normals_ptr: int, params: RtRenderParams, d_out_ptr: int,
+                               stream: int = 0) -> None:
+        """rt_bake_irradiance_device: n x 3 doubles each in HBM -> n x 4 doubles in HBM."""
+        st = self._lib.rt_bake_irradiance_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.c_void_p(d_normals_ptr or None),
+                                                 C.byref(params), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def bake_irradiance_hits_device(self, n: int, d_hits_ptr: int, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
+        """rt_bake_irradiance_hits_device: n RtRayHit records in HBM (trace_rays_device) -> n x 4 doubles in HBM; a miss or an
+        environment hit gives (0, 0, 0, 0)."""
+        st = self._lib.rt_bake_irradiance_hits_device(self._h, n, C.c_void_p(d_hits_ptr or None), C.byref(params),
+                                                      C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
 

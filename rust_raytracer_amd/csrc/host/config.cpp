@@ -109,8 +109,12 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             cfg.scene_name = arg;  // config.rs:150 (last one wins)
             continue;
         }
-        if (arg == "--light-groups") {  // new: the one flag without a value (= as many groups as the library allows)
+        if (arg == "--light-groups") {  // new: a flag without a value (= as many groups as the library allows)
             cfg.light_groups = RT_LIGHT_GROUPS_MAX;
+            continue;
+        }
+        if (arg == "--irradiance") {  // new: also write out_irradiance.png (rt_bake_irradiance_hits_device at every pixel's first hit)
+            cfg.irradiance = true;
             continue;
         }
         std::string key, value;
@@ -318,6 +322,11 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
     if (cfg.ao_samples && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty())) {
         *err = "--ao bakes the whole frame on one GPU after a one-shot render: it cannot be combined with --gpus > 1, --progressive, "
                "--noise-threshold or --pick";
+        return false;
+    }
+    if (cfg.irradiance && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.has_probe)) {
+        *err = "--irradiance bakes the whole frame on one GPU after a one-shot render: it cannot be combined with --gpus > 1, --progressive, "
+               "--noise-threshold, --pick, --ao or --probe";
         return false;
     }
     if (cfg.has_probe && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.light_groups || cfg.denoise ||

@@ -101,6 +101,7 @@ uint32_t rth_ao(const RtHost* host, double* max_distance_out) {
     if (max_distance_out) *max_distance_out = host->config.ao_max_distance;
     return host->config.ao_samples;
 }
+int rth_irradiance(const RtHost* host) { return host->config.irradiance ? 1 : 0; }
 uint32_t rth_probe(const RtHost* host, double position_out[3]) {
     if (!host->config.has_probe) return 0;
     if (position_out)

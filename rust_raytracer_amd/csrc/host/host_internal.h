@@ -50,6 +50,7 @@ struct Config {
     std::vector<std::pair<uint32_t, uint32_t>> pick;  // --pick=<x>,<y>[:<x>,<y>...]: pixels to query instead of rendering
     uint32_t ao_samples = 0;                          // --ao=<samples>[:<max_distance>]: also write out_ao.png (0: off)
     double ao_max_distance = HUGE_VAL;                // +inf: unlimited
+    bool irradiance = false;                          // --irradiance: also write out_irradiance.png (rt_bake_irradiance_hits_device)
     bool has_probe = false;                           // --probe=<x>,<y>,<z>[:<width>]: a light probe panorama instead of the frame
     double probe_position[3] = {0.0, 0.0, 0.0};
     uint32_t probe_width = 512;                       // height = width / 2

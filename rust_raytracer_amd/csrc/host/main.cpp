@@ -8,7 +8,12 @@
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 //   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
-//   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]
+//   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]  --irradiance
+// --irradiance also writes out_irradiance.png: the --pick ray of every pixel is cast on the device (rt_trace_rays_device) and the
+// cosine-weighted mean of the radiance arriving at every first hit is baked with the run's -s, -t, depth, bias, seed and
+// precision (rt_bake_irradiance_hits_device; the hit records never leave the device) and written through the output stage of
+// out.png; a pixel that sees no surface is black.  A scene with volumes is refused before anything is rendered.  One more console
+// line; out.png and the other console lines are those of a run without the flag.
 // --probe=<x>,<y>,<z>[:<width>] renders no frame: an equirectangular light probe at that point (+y up, the centre column looking
 // along -z; width 512 by default, height = width / 2) is rendered with rt_render_rays along the rays of rth_probe_rays, with the
 // run's -s, -t, depth, bias, seed and precision, and written to out_probe.png through the output stage of out.png.  There is no
@@ -253,47 +258,63 @@ static int render_probe(RtHost* host, const std::function<double()>& since) {
     return 0;
 }
 
+// --ao, --irradiance: the first hits of the --pick ray of every pixel, row-major, as hit records on the device, and room for
+// `out_each` bytes of results per pixel.  Everything is freed with the object.
+struct PixelHits {
+    size_t n = 0;
+    void *d_rays = nullptr, *d_hits = nullptr, *d_out = nullptr;
+    std::string what;  // the flag, for messages
+    ~PixelHits() {
+        (void)hipFree(d_rays);
+        (void)hipFree(d_hits);
+        (void)hipFree(d_out);
+    }
+    bool hip_ok(hipError_t e, std::string* err) const {
+        if (e != hipSuccess) *err = what + ": " + hipGetErrorString(e);
+        return e == hipSuccess;
+    }
+    static bool rt_ok(int st, std::string* err) {
+        if (st != RT_OK) *err = rt_last_error();
+        return st == RT_OK;
+    }
+    bool trace(const RtScene* scene, const RtCameraDesc* cam, uint32_t precision, size_t out_each, const char* flag, std::string* err) {
+        what = flag;
+        const uint32_t W = cam->image_width, H = cam->image_height;
+        n = size_t(W) * H;
+        std::vector<double> rays(6 * n);  // origins, then directions
+        for (uint32_t y = 0; y < H; y++)
+            for (uint32_t x = 0; x < W; x++)
+                for (int a = 0; a < 3; a++) {
+                    const size_t i = size_t(y) * W + x;
+                    rays[3 * i + a] = cam->position[a];
+                    rays[3 * (n + i) + a] = cam->first_pixel[a] + double(x) * cam->pixel_delta_u[a] + double(y) * cam->pixel_delta_v[a] - cam->position[a];
+                }
+        return hip_ok(hipMalloc(&d_rays, rays.size() * sizeof(double)), err) && hip_ok(hipMalloc(&d_hits, n * sizeof(RtRayHit)), err) &&
+               hip_ok(hipMalloc(&d_out, n * out_each), err) &&
+               hip_ok(hipMemcpy(d_rays, rays.data(), rays.size() * sizeof(double), hipMemcpyHostToDevice), err) &&
+               rt_ok(rt_trace_rays_device(scene, n, static_cast<const double*>(d_rays), static_cast<const double*>(d_rays) + 3 * n, precision,
+                                          static_cast<RtRayHit*>(d_hits), nullptr), err);
+    }
+    const RtRayHit* hits() const { return static_cast<const RtRayHit*>(d_hits); }
+};
+
 // --ao: visibility of every pixel's first hit (w * h values, row-major; 1 where the pixel sees no surface); false with *err
 // set on failure.
 static bool bake_ao(const RtScene* scene, const RtCameraDesc* cam, const RtRenderParams* params, uint32_t samples, double max_distance,
                     std::vector<double>* visibility, double* mean_out, std::string* err) {
-    const uint32_t W = cam->image_width, H = cam->image_height;
-    const size_t n = size_t(W) * H;
-    std::vector<double> rays(6 * n);  // origins, then directions: the --pick ray of every pixel, row-major
-    for (uint32_t y = 0; y < H; y++)
-        for (uint32_t x = 0; x < W; x++)
-            for (int a = 0; a < 3; a++) {
-                const size_t i = size_t(y) * W + x;
-                rays[3 * i + a] = cam->position[a];
-                rays[3 * (n + i) + a] = cam->first_pixel[a] + double(x) * cam->pixel_delta_u[a] + double(y) * cam->pixel_delta_v[a] - cam->position[a];
-            }
-    void *d_rays = nullptr, *d_hits = nullptr, *d_out = nullptr;
-    std::vector<RtBakeResult> out(n);
-    auto hip_ok = [&](hipError_t e) {
-        if (e != hipSuccess) *err = std::string("--ao: ") + hipGetErrorString(e);
-        return e == hipSuccess;
-    };
-    auto rt_ok = [&](int st) {
-        if (st != RT_OK) *err = rt_last_error();
-        return st == RT_OK;
-    };
+    PixelHits px;
     RtBakeParams bp{};
     bp.samples = samples;
     bp.precision = params->precision;
     bp.seed = params->seed;
     bp.bias = 0.001;
     bp.max_distance = max_distance;
-    const bool ok = hip_ok(hipMalloc(&d_rays, rays.size() * sizeof(double))) && hip_ok(hipMalloc(&d_hits, n * sizeof(RtRayHit))) &&
-                    hip_ok(hipMalloc(&d_out, n * sizeof(RtBakeResult))) &&
-                    hip_ok(hipMemcpy(d_rays, rays.data(), rays.size() * sizeof(double), hipMemcpyHostToDevice)) &&
-                    rt_ok(rt_trace_rays_device(scene, n, static_cast<const double*>(d_rays), static_cast<const double*>(d_rays) + 3 * n,
-                                               params->precision, static_cast<RtRayHit*>(d_hits), nullptr)) &&
-                    rt_ok(rt_bake_visibility_hits_device(scene, n, static_cast<const RtRayHit*>(d_hits), &bp, static_cast<RtBakeResult*>(d_out), nullptr)) &&
-                    hip_ok(hipMemcpy(out.data(), d_out, n * sizeof(RtBakeResult), hipMemcpyDeviceToHost));
-    (void)hipFree(d_rays);
-    (void)hipFree(d_hits);
-    (void)hipFree(d_out);
-    if (!ok) return false;
+    if (!px.trace(scene, cam, params->precision, sizeof(RtBakeResult), "--ao", err)) return false;
+    const size_t n = px.n;
+    std::vector<RtBakeResult> out(n);
+    if (!PixelHits::rt_ok(rt_bake_visibility_hits_device(scene, n, px.hits(), &bp, static_cast<RtBakeResult*>(px.d_out), nullptr), err) ||
+        !px.hip_ok(hipMemcpy(out.data(), px.d_out, n * sizeof(RtBakeResult), hipMemcpyDeviceToHost), err))
+        return false;
     visibility->resize(n);
     double sum = 0.0;
     for (size_t i = 0; i < n; i++) {
@@ -301,6 +322,31 @@ static bool bake_ao(const RtScene* scene, const RtCameraDesc* cam, const RtRende
         sum += out[i].visibility;
     }
     *mean_out = n ? sum / double(n) : 0.0;
+    return true;
+}
+
+// --irradiance: the bake at every pixel's first hit (w * h x 4 values, row-major; 0 where the pixel sees no surface); false with
+// *err set on failure.
+static bool bake_irradiance(const RtScene* scene, const RtCameraDesc* cam, const RtRenderParams* params, std::vector<double>* rgba, double* mean_out,
+                            std::string* err) {
+    PixelHits px;
+    RtRenderParams bp = *params;  // S, T, depth, background, bias, seed, precision of the run; the bake has one scheduler and no partition
+    bp.pipeline = RT_PIPELINE_AUTO;
+    bp.collect_stats = 0;
+    bp.band_rows = bp.n_parts = bp.part = 0;
+    if (!px.trace(scene, cam, params->precision, 4 * sizeof(double), "--irradiance", err)) return false;
+    const size_t n = px.n;
+    rgba->assign(4 * n, 0.0);
+    if (!PixelHits::rt_ok(rt_bake_irradiance_hits_device(scene, n, px.hits(), &bp, static_cast<double*>(px.d_out), nullptr), err) ||
+        !px.hip_ok(hipMemcpy(rgba->data(), px.d_out, 4 * n * sizeof(double), hipMemcpyDeviceToHost), err))
+        return false;
+    double sum = 0.0;  // mean luminance over the finite pixels, as the light groups report theirs
+    size_t finite = 0;
+    for (size_t i = 0; i < n; i++) {
+        const double y = (0.2126 * (*rgba)[4 * i] + 0.7152 * (*rgba)[4 * i + 1]) + 0.0722 * (*rgba)[4 * i + 2];
+        if (y - y == 0.0) { sum += y; finite++; }
+    }
+    *mean_out = finite ? sum / double(finite) : 0.0;
     return true;
 }
 
@@ -351,9 +397,10 @@ int main(int argc, char** argv) {
         return rc;
     }
     if (!sequence.empty()) {
-        if (gpus > 1 || rth_progressive(host) || rth_noise_threshold(host) > 0.0 || rth_light_groups(host) || rth_denoise(host) || rth_ao(host, nullptr))
+        if (gpus > 1 || rth_progressive(host) || rth_noise_threshold(host) > 0.0 || rth_light_groups(host) || rth_denoise(host) || rth_ao(host, nullptr) ||
+            rth_irradiance(host))
             return fail("--sequence renders whole frames on one GPU: it cannot be combined with --gpus > 1, --progressive, --noise-threshold, "
-                        "--light-groups, --denoise or --ao");
+                        "--light-groups, --denoise, --ao or --irradiance");
         const int rc = render_sequence(host, argc, argv, sequence, since);
         rth_destroy(host);
         return rc;
@@ -392,6 +439,15 @@ int main(int argc, char** argv) {
         if (rt_scene_info(rth_scene(host), &info) != RT_OK) return fail(rt_last_error());
         if (info & RT_SCENE_INFO_VOLUMES) return fail("--ao does not support scenes with volumes (a medium gives no deterministic surface)");
     }
+    const bool irradiance = rth_irradiance(host) != 0;  // one GPU (rth_load refuses --irradiance with --gpus > 1)
+    if (irradiance) {  // refused BEFORE the render, like --ao's
+        uint32_t info = 0;
+        if (rt_scene_info(rth_scene(host), &info) != RT_OK) return fail(rt_last_error());
+        if (info & RT_SCENE_INFO_VOLUMES) return fail("--irradiance does not support scenes with volumes (the ray queries that find the surface points have none)");
+        if (params->max_depth == 0) return fail("--irradiance needs a depth of at least 1");
+    }
+    std::vector<double> irr_rgba;
+    double irr_mean = 0.0, irr_seconds = 0.0;
     std::vector<double> ao_visibility;
     double ao_mean = 0.0, ao_seconds = 0.0;
     std::vector<std::string> errors(gpus);
@@ -449,6 +505,11 @@ int main(int argc, char** argv) {
                 if (!bake_ao(scene, cam, &p, ao_samples, ao_distance, &ao_visibility, &ao_mean, &errors[g])) return;
                 ao_seconds = std::chrono::duration<double>(clock::now() - ta).count();
             }
+            if (irradiance && errors[g].empty()) {
+                auto ta = clock::now();
+                if (!bake_irradiance(scene, cam, &p, &irr_rgba, &irr_mean, &errors[g])) return;
+                irr_seconds = std::chrono::duration<double>(clock::now() - ta).count();
+            }
         });
     }
     for (auto& t : workers) t.join();
@@ -482,6 +543,11 @@ int main(int argc, char** argv) {
     if (ao_samples) {
         if (rth_save_png_grey("out_ao.png", ao_visibility.data(), W, H) != RT_OK) return fail(rth_last_error());
         std::printf("Ambient occlusion: %u samples per pixel, mean visibility %.6g, baked in %s\n", ao_samples, ao_mean, fmt_duration(ao_seconds).c_str());
+    }
+    if (irradiance) {
+        if (rth_save_png("out_irradiance.png", irr_rgba.data(), W, H) != RT_OK) return fail(rth_last_error());
+        std::printf("Irradiance: %u paths per pixel, mean luminance of the cosine-weighted incoming radiance %.6g, baked in %s\n", spp, irr_mean,
+                    fmt_duration(irr_seconds).c_str());
     }
     if (denoise && rth_save_png("out_denoised.png", denoised.data(), W, H) != RT_OK) {
         std::fprintf(stderr, "Error: %s\n", rth_last_error());

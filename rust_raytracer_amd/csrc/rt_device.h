@@ -16,7 +16,12 @@
 
 namespace rt {
 
+#ifndef RT_DEV  // tools/point_ray_host.cpp builds the sampling code for the host as well
 #define RT_DEV __device__ __forceinline__
+#endif
+#ifndef RT_DEV_NOINLINE
+#define RT_DEV_NOINLINE __device__ __attribute__((noinline))
+#endif
 // Notes from tuning: (1) a single `__noinline__` helper (to_unit) raised the shade kernel
 // from 129 to 217 VGPRs through the call ABI; (2) restructuring shade() so that every heavy routine has one
 // call site halved its code (71 KB -> 36 KB) but also raised it to 211 VGPRs and bought no time.  Everything

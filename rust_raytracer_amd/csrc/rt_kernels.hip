@@ -684,7 +684,7 @@ struct RtScene {
         rt::ChunkStage stage;
         RtRayQueryStats stats{};
     } bake;
-    // renders along ray tables (rt_render_rays): the host variant's staging buffer; the kernels run on the render's workspace (wf)
+    // renders along ray tables and irradiance bakes (rt_render_rays, rt_bake_irradiance): the host variants' staging buffer; the kernels run on the render's workspace (wf)
     struct Rays {
         rt::ChunkStage stage;
     } rays;
@@ -847,6 +847,12 @@ template <typename R>
 ShadeKernel<R, WfGroupRays<R>> pick_shade_rays(int lds, bool tex, bool fuse) {
     if (fuse) return &k_wf_shade<R, false, 1, false, WfGroupRays<R>, true>;
     return pick_shade_lean<R, WfGroupRays<R>>(lds, tex);
+}
+// Point tables of an irradiance bake (WfGroupPoints): the same set.
+template <typename R>
+ShadeKernel<R, WfGroupPoints<R>> pick_shade_points(int lds, bool tex, bool fuse) {
+    if (fuse) return &k_wf_shade<R, false, 1, false, WfGroupPoints<R>, true>;
+    return pick_shade_lean<R, WfGroupPoints<R>>(lds, tex);
 }
 // Dense groups also have the counting variants and the one fused kernel (+ k_wf_prims' search as phase 4).
 template <typename R>
@@ -1085,6 +1091,16 @@ struct RayTablePass {
     uint64_t first = 0;
 };
 
+// An irradiance bake (rt_bake_irradiance): one chunk of the caller's points.  The "frame" is n x 1 pixels,
+// pixel i = point first + i; pos / nrm are device pointers to the chunk's first position and normal, `stride` bytes apart
+// from point to point (24: plain arrays; sizeof(RtRayHit): hit records).
+struct PointTablePass {
+    const unsigned char* pos = nullptr;
+    const unsigned char* nrm = nullptr;
+    uint32_t stride = 24;
+    uint64_t first = 0;
+};
+
 // Pool size of a render.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
 // dependent fetches) and the streaming kernels run better in few large launches, so fewer, larger launches win; against that
 // stands the tail: the pool is what drains at the end of a replica group, over ~20 ever smaller iterations.  Round 2 (tail at
@@ -1227,9 +1243,9 @@ int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, const
 template <typename R>
 int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
                      uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr,
-                     const LightGroupPass* lg = nullptr, const RayTablePass* rays = nullptr) {
+                     const LightGroupPass* lg = nullptr, const RayTablePass* rays = nullptr, const PointTablePass* points = nullptr) {
     CameraView<R> cv = make_camera_view<R>(cam, p);
-    if (rays) cv.has_aperture = 1;  // every sample has an origin of its own: k_wf_shade's restarts store it (phase 2)
+    if (rays || points) cv.has_aperture = 1;  // every sample has an origin of its own: k_wf_shade's restarts store it (phase 2)
     ParamsView<R> pv = make_params_view<R>(p, owned);
     const uint64_t npix_frame = uint64_t(cam.image_width) * owned;
     const bool sparse = ad && ad->sparse;
@@ -1238,6 +1254,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     if (npix == 0) return set_err(RT_E_INVALID, "adaptive pass without active pixels");
     if (lg && (ad || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "light groups have no adaptive or counting kernels (collect_stats)");
     if (rays && (ad || lg || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "ray tables have no adaptive, light-group or counting kernels (collect_stats)");
+    if (points && (ad || lg || rays || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "point tables have no adaptive, light-group or counting kernels (collect_stats)");
     const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
     const uint32_t T = p.thread_count;
     const uint32_t t_end = t_first + n;
@@ -1285,7 +1302,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     // prims set within what the shade kernel may ask for at five workgroups per CU.  With the tables in global memory the fused
     // kernel needs scratch (f64 32 B, f32 80 B; tools/kernel_regs.py), so those scenes - and volumes, re-built groups, the texture
     // interpreter, sparse adaptive passes, light-group renders and the counting variants - keep the stand-alone kernel.  A ray
-    // table runs the form a plain render of the scene runs.
+    // table and a point table run the form a plain render of the scene runs.
     // Programs with more than one mesh op keep it too: tests/scenes/two_meshes lost 2.4 % of its frame fused (DESIGN.md section 6,
     // round 5).  RT_WF_FUSE=0: the unfused pipeline (A/B control, reference of the tests); 2: fused wherever the kernel exists,
     // whatever the plan says (tests, A/B).
@@ -1299,6 +1316,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
     const ShadeKernel<R, WfGroupSparse<R>> shade_sparse = pick_shade_lean<R, WfGroupSparse<R>>(lds_shade, tex);
     const ShadeKernel<R, WfGroupLG<R>> shade_lg = pick_shade_lean<R, WfGroupLG<R>>(lds_shade, tex);
     const ShadeKernel<R, WfGroupRays<R>> shade_rays = pick_shade_rays<R>(lds_shade, tex, fuse);
+    const ShadeKernel<R, WfGroupPoints<R>> shade_points = pick_shade_points<R>(lds_shade, tex, fuse);
 
     HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DeviceCounters), stream));
     HIP_TRY(hipEventRecord(s->ev0, stream));
@@ -1327,6 +1345,9 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         WfGroupRays<R> grp_r{};
         static_cast<WfGroup<R>&>(grp_r) = grp;
         if (rays) { grp_r.origins = rays->origins; grp_r.dirs = rays->dirs; grp_r.first = rays->first; }
+        WfGroupPoints<R> grp_p{};
+        static_cast<WfGroup<R>&>(grp_p) = grp;
+        if (points) { grp_p.pos = points->pos; grp_p.nrm = points->nrm; grp_p.stride = points->stride; grp_p.first = points->first; }
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
         uint32_t first = uint32_t(std::min<uint64_t>(capacity, grp.total));
         pool = pool_a;
@@ -1341,7 +1362,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         init.next_sample = first;
         *w.h_ctr = init;
         HIP_TRY(hipMemcpyAsync(w.d_ctr, w.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-        if (rays) hipLaunchKernelGGL((k_wf_generate<R, WfGroupRays<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_r, cv, pv, queue[0]);
+        if (points) hipLaunchKernelGGL((k_wf_generate<R, WfGroupPoints<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_p, cv, pv, queue[0]);
+        else if (rays) hipLaunchKernelGGL((k_wf_generate<R, WfGroupRays<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_r, cv, pv, queue[0]);
         else if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, queue[0]);
         else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, queue[0]);
         int qi = 0;
@@ -1376,7 +1398,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
                     ty.search_launches++;
                     HIP_TRY(hipEventRecord(w.events[ev++], stream));
                 }
-                if (rays) launch_shade(shade_rays, grp_r);
+                if (points) launch_shade(shade_points, grp_p);
+                else if (rays) launch_shade(shade_rays, grp_r);
                 else if (lg) launch_shade(shade_lg, grp_lg);
                 else if (sparse) launch_shade(shade_sparse, grp_s);
                 else launch_shade(shade_dense, grp);
@@ -1666,31 +1689,28 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
 // ---------------------------------------------------------------------------------------------
 // Renders along ray tables (include/rt_mi355.h)
 // ---------------------------------------------------------------------------------------------
-// Rays per chunk.  A chunk is rendered like a frame of that many pixels (pool, per-sample buffer, replica groups), so the
+// Rays (or bake points) per chunk.  A chunk is rendered like a frame of that many pixels (pool, per-sample buffer, replica groups), so the
 // default is a frame's order of magnitude, 2^22 = a 2048 x 2048 image; it is a guess, not a measurement.  At most 2^28: the
 // kernels index the table with 32-bit element offsets.
 static uint32_t rays_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(1u, env_u32("RT_RAYS_CHUNK", 1u << 22))); }
 
-// n rays in chunks through render_wavefront, each chunk a frame of m x 1 pixels whose pixel i is ray off + i.  host: the
-// arrays are the caller's host memory and go through the scene's staging buffer.  The scene's stats are the sums over the chunks;
-// the tail flag belongs to the last chunk.
-template <typename R>
-int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const RtRenderParams& p,
-                      double* out, bool host, hipStream_t stream) {
+// n table entries (rays, or the points of an irradiance bake) in chunks through render_wavefront, each chunk a frame of m x 1
+// pixels whose pixel i is entry off + i: render(cam, off, m, d_in, d_out) runs render_wavefront for one chunk.  host: the arrays
+// are the caller's host memory and go through `stage`.  The scene's stats are the sums over the chunks; the tail flag belongs to
+// the last chunk.
+template <typename F>
+int render_table_chunks(RtScene* s, ChunkStage& stage, uint64_t n, const std::vector<ChunkArray>& in, double* out, bool host, hipStream_t stream,
+                        F&& render) {
     const uint32_t chunk = rays_chunk();
-    RtCameraDesc cam{};  // only the width is read: a ray table has no camera arithmetic
+    RtCameraDesc cam{};  // only the width is read: a table has no camera arithmetic
     cam.image_height = 1;
     RtRenderStats sum{};
     int32_t* const tail_flag = s->tail_flag;
     ChunkTimes t;
     auto launch = [&](uint64_t off, uint32_t m, const void* const* d_in, void* d_out) -> int {
-        RayTablePass rp;
-        rp.origins = static_cast<const double*>(d_in[0]);
-        rp.dirs = static_cast<const double*>(d_in[1]);
-        rp.first = off;
         cam.image_width = m;
         s->tail_flag = off + m >= n ? tail_flag : nullptr;
-        const int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, static_cast<double*>(d_out), stream, nullptr, nullptr, &rp);
+        const int st = render(cam, off, m, d_in, static_cast<double*>(d_out));
         s->tail_flag = tail_flag;
         if (st != RT_OK) return st;
         const RtRenderStats c = s->stats;
@@ -1702,9 +1722,55 @@ int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* 
         sum = acc;
         return RT_OK;
     };
-    const int st = run_chunks(s->rays.stage, n, chunk, host, {{origins, 24}, {dirs, 24}}, out, 4 * sizeof(double), stream, launch, &t);
+    const int st = run_chunks(stage, n, chunk, host, in, out, 4 * sizeof(double), stream, launch, &t);
     if (st == RT_OK) s->stats = sum;
     return st;
+}
+
+template <typename R>
+int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const RtRenderParams& p,
+                      double* out, bool host, hipStream_t stream) {
+    auto render = [&](const RtCameraDesc& cam, uint64_t off, uint32_t, const void* const* d_in, double* d_out) -> int {
+        RayTablePass rp;
+        rp.origins = static_cast<const double*>(d_in[0]);
+        rp.dirs = static_cast<const double*>(d_in[1]);
+        rp.first = off;
+        return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, nullptr, nullptr, &rp);
+    };
+    return render_table_chunks(s, s->rays.stage, n, {{origins, 24}, {dirs, 24}}, out, host, stream, render);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Irradiance bake (include/rt_mi355.h): the points of the caller, chunked like a ray table
+// ---------------------------------------------------------------------------------------------
+// hits: the points are RtRayHit records on the device (positions / normals unused); records without a surface point are
+// zeroed after the chunk's resolve (k_wf_points_mask).
+template <typename R>
+int bake_irradiance_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
+                          const RtRenderParams& p, double* out, bool host, hipStream_t stream) {
+    auto render = [&](const RtCameraDesc& cam, uint64_t off, uint32_t m, const void* const* d_in, double* d_out) -> int {
+        PointTablePass pp;
+        pp.first = off;
+        if (hits) {
+            const unsigned char* base = reinterpret_cast<const unsigned char*>(hits + off);
+            pp.pos = base + offsetof(RtRayHit, pos);
+            pp.nrm = base + offsetof(RtRayHit, normal);
+            pp.stride = uint32_t(sizeof(RtRayHit));
+        } else {
+            pp.pos = static_cast<const unsigned char*>(d_in[0]);
+            pp.nrm = static_cast<const unsigned char*>(d_in[1]);
+            pp.stride = 24u;
+        }
+        if (int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, nullptr, nullptr, nullptr, &pp)) return st;
+        if (hits) {
+            hipLaunchKernelGGL(k_wf_points_mask, dim3((m + 255) / 256), dim3(256), 0, stream,
+                               reinterpret_cast<const unsigned char*>(hits + off) + offsetof(RtRayHit, flags), uint32_t(sizeof(RtRayHit)), m, d_out);
+            HIP_TRY(hipGetLastError());
+        }
+        return RT_OK;
+    };
+    const std::vector<ChunkArray> in = hits ? std::vector<ChunkArray>{} : std::vector<ChunkArray>{{positions, 24}, {normals, 24}};
+    return render_table_chunks(s, s->rays.stage, n, in, out, host, stream, render);
 }
 
 // Makes sure the scene's tables in the arithmetic of `precision` are on the device (built on first use), then f(tables).
@@ -3286,27 +3352,35 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
     return RT_OK;
 }
 
-// ---- Renders along ray tables -----------------------------------------------------------------------------------------------
-static int render_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params,
-                            double* out, bool host, void* stream, const char* who) {
+// ---- Renders along ray tables, irradiance bakes --------------------------------------------------------------------------------
+// The rules the two share, checked before the device is touched; a/b/out name the arrays in messages (a, b NULL: no such array).
+static int table_render_check(const RtScene* scene, uint64_t n, const void* a, const char* a_name, const void* b, const char* b_name,
+                              const RtRenderParams* params, const void* out, const char* out_name, const std::string& w, const char* what, const char* unit) {
     using namespace rt;
-    const std::string w = std::string(who) + ": ";
     if (!scene) return set_err(RT_E_INVALID, w + "scene is NULL");
     if (!params) return set_err(RT_E_INVALID, w + "params is NULL");
     if (params->sqrt_spt == 0) return set_err(RT_E_INVALID, w + "sqrt_spt must be positive");
     if (params->thread_count == 0) return set_err(RT_E_INVALID, w + "thread_count must be positive");
     if (params->precision != RT_PRECISION_F64 && params->precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, w + "precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
-    if (params->n_parts > 1) return set_err(RT_E_INVALID, w + "n_parts > 1: a ray table has no row partition");
+    if (params->n_parts > 1) return set_err(RT_E_INVALID, w + "n_parts > 1: a " + what + " has no row partition");
     if (n >= (1ull << 31)) return set_err(RT_E_INVALID, w + "n must be below 2^31");
-    if (uint64_t(params->sqrt_spt) * params->sqrt_spt * params->thread_count > 0xFFFFFFFFull) return set_err(RT_E_UNSUPPORTED, w + "more than 2^32 samples per ray (sqrt_spt, thread_count)");
-    if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, w + "ray tables run the wavefront scheduler: pipeline = RT_PIPELINE_MEGAKERNEL is not supported");
+    if (uint64_t(params->sqrt_spt) * params->sqrt_spt * params->thread_count > 0xFFFFFFFFull) return set_err(RT_E_UNSUPPORTED, w + "more than 2^32 samples per " + unit + " (sqrt_spt, thread_count)");
+    if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, w + what + "s run the wavefront scheduler: pipeline = RT_PIPELINE_MEGAKERNEL is not supported");
     if (params->pipeline != RT_PIPELINE_AUTO && params->pipeline != RT_PIPELINE_WAVEFRONT) return set_err(RT_E_INVALID, w + "unknown pipeline");
     if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, w + "max_depth = 0 is not supported");
-    if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, w + "ray tables have no counting kernels (collect_stats)");
+    if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, w + what + "s have no counting kernels (collect_stats)");
     if (n == 0) return RT_OK;
-    if (!origins) return set_err(RT_E_INVALID, w + "origins is NULL");
-    if (!dirs) return set_err(RT_E_INVALID, w + "dirs is NULL");
-    if (!out) return set_err(RT_E_INVALID, w + "rgba_out is NULL");
+    if (a_name && !a) return set_err(RT_E_INVALID, w + a_name + " is NULL");
+    if (b_name && !b) return set_err(RT_E_INVALID, w + b_name + " is NULL");
+    if (!out) return set_err(RT_E_INVALID, w + out_name + " is NULL");
+    return RT_OK;
+}
+
+static int render_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params,
+                            double* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    if (int st = table_render_check(scene, n, origins, "origins", dirs, "dirs", params, out, "rgba_out", std::string(who) + ": ", "ray table", "ray")) return st;
+    if (n == 0) return RT_OK;
     RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
     HIP_TRY(hipSetDevice(s->device));
     RtRenderParams p = *params;
@@ -3323,6 +3397,38 @@ int rt_render_rays(const RtScene* scene, uint64_t n, const double* origins, cons
 int rt_render_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const RtRenderParams* params,
                           double* d_rgba_out, void* stream) {
     const int r = render_rays_impl(scene, n, d_origins, d_dirs, params, d_rgba_out, false, stream, "rt_render_rays_device");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
+    return r;
+}
+
+static int bake_irradiance_impl(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits, bool by_hits,
+                                const RtRenderParams* params, double* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    const int chk = by_hits ? table_render_check(scene, n, hits, "hits", nullptr, nullptr, params, out, "rgba_out", std::string(who) + ": ", "point table", "point")
+                            : table_render_check(scene, n, positions, "positions", normals, "normals", params, out, "rgba_out", std::string(who) + ": ", "point table", "point");
+    if (chk != RT_OK || n == 0) return chk;
+    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
+    HIP_TRY(hipSetDevice(s->device));
+    RtRenderParams p = *params;
+    p.band_rows = p.n_parts = p.part = 0;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    return with_tables(s, p.precision, [&](auto& ds) -> int { return bake_irradiance_typed(s, ds, n, positions, normals, hits, p, out, host, st); });
+}
+
+int rt_bake_irradiance(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRenderParams* params, double* rgba_out) {
+    const int r = bake_irradiance_impl(scene, n, positions, normals, nullptr, false, params, rgba_out, true, nullptr, "rt_bake_irradiance");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
+    return r;
+}
+int rt_bake_irradiance_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals, const RtRenderParams* params,
+                              double* d_rgba_out, void* stream) {
+    const int r = bake_irradiance_impl(scene, n, d_positions, d_normals, nullptr, false, params, d_rgba_out, false, stream, "rt_bake_irradiance_device");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
+    return r;
+}
+int rt_bake_irradiance_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtRenderParams* params, double* d_rgba_out,
+                                   void* stream) {
+    const int r = bake_irradiance_impl(scene, n, nullptr, nullptr, d_hits, true, params, d_rgba_out, false, stream, "rt_bake_irradiance_hits_device");
     if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
     return r;
 }

@@ -81,6 +81,7 @@ struct WfGroup {
     static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = false;
     static constexpr bool kRays = false;
+    static constexpr bool kPoints = false;
 };
 
 // Replica group of an adaptive pass over a SUBSET of the pixels: `npix` counts the active pixels and
@@ -94,6 +95,7 @@ struct WfGroupSparse : WfGroup<R> {
     static constexpr bool kSparse = true;
     static constexpr bool kLightGroups = false;
     static constexpr bool kRays = false;
+    static constexpr bool kPoints = false;
 };
 
 // Replica group of a light-group render (include/rt_mi355.h): k_wf_shade also stores the group of every
@@ -109,6 +111,7 @@ struct WfGroupLG : WfGroup<R> {
     static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = true;
     static constexpr bool kRays = false;
+    static constexpr bool kPoints = false;
 };
 
 // Replica group of a render along a ray table (rt_render_rays): "pixel" i of the group is ray i of a chunk
@@ -124,7 +127,51 @@ struct WfGroupRays : WfGroup<R> {
     static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = false;
     static constexpr bool kRays = true;
+    static constexpr bool kPoints = false;
 };
+
+// Replica group of an irradiance bake (rt_bake_irradiance): "pixel" i of the group is surface point i of a
+// chunk of the caller's points, and a sample's first ray leaves that point in a cosine-weighted direction about its normal,
+// formed from the two uniforms a camera spends on its jitter.  `pos` / `nrm` point at the chunk's first position and normal
+// (3 doubles each), `stride` bytes apart from point to point: 24 for plain arrays, sizeof(RtRayHit) for hit records.  `first`:
+// as in WfGroupRays.  A type of its own for the reason WfGroupSparse is one.
+template <typename R>
+struct WfGroupPoints : WfGroup<R> {
+    const unsigned char* pos;
+    const unsigned char* nrm;
+    uint64_t first;
+    uint32_t stride;
+    static constexpr bool kSparse = false;
+    static constexpr bool kLightGroups = false;
+    static constexpr bool kRays = false;
+    static constexpr bool kPoints = true;
+};
+
+// First ray of a bake sample: the cosine-weighted direction of (u1, u2) about the point's normal (random_cosine's formulas,
+// vec4.rs:50-61, with u1, u2 for its two draws; cosine.rs:31-33 for the basis), returned the way the reference's camera would
+// form it from position = o and first_pixel = o + d: d' = (o + d) - o, two roundings per component.  That is what gives the bake
+// a bit-exact oracle.  OUT of line on purpose, like uv_acos: inlined into the restart of k_wf_shade the
+// sincos polynomial, two square roots and the basis cost registers the kernel does not have at five waves per SIMD.
+// Both vectors come back by value (twelve VGPRs at most): reference arguments of a real call would live in scratch.
+template <typename R>
+struct WfPointRay {
+    V3<R> o, d;
+};
+template <typename R>
+RT_DEV_NOINLINE WfPointRay<R> wf_point_ray(const double* pp, const double* pn, R u1, R u2) {
+    const R phi = u1 * R(2) * pi<R>();
+    const R sqrt_u2 = sqrt(u2);
+    R sn, cs;
+    sincos_r(phi, sn, cs);
+    const V3<R> c = mk<R>(cs * sqrt_u2, sn * sqrt_u2, sqrt(R(1) - u2));
+    const V3<R> w = to_unit(mk<R>(R(pn[0]), R(pn[1]), R(pn[2])));
+    V3<R> u, v;
+    onb_from_vec(w, u, v);
+    const V3<R> dir = basis_apply(u, v, w, c);
+    const V3<R> o = mk<R>(R(pp[0]), R(pp[1]), R(pp[2]));
+    const V3<R> tgt = o + dir;
+    return {o, tgt - o};
+}
 
 // floor(a / b) and the remainder for a < 2^51: the reciprocal estimate is off by at most one, the remainder test makes it
 // exact (integers throughout: nothing here can move a pixel).  A generic 64-bit division is ~120 instructions on gfx950
@@ -156,6 +203,22 @@ RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, co
         d = mk<R>(R(grp.dirs[at3]), R(grp.dirs[at3 + 1u]), R(grp.dirs[at3 + 2u]));
         return;
     }
+    if constexpr (G::kPoints) {
+        // The stream of point i is the stream of pixel i, and the two draws a camera spends on its jitter are the hemisphere
+        // sample: stratified over the S x S cells as the jitter is, so the path's own first draw is the third of the stream.
+        rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
+        const uint32_t S = cam.sqrt_spt;
+        const uint32_t sy = st / S, sx = st - sy * S;
+        const R r1 = rng_uniform<R>(rng);
+        const R r2 = rng_uniform<R>(rng);
+        const R u1 = (R(sx) + r1) * cam.inv_sqrt_spt;
+        const R u2 = (R(sy) + r2) * cam.inv_sqrt_spt;
+        const uint64_t at = pix * grp.stride;
+        const WfPointRay<R> ray = wf_point_ray<R>(reinterpret_cast<const double*>(grp.pos + at), reinterpret_cast<const double*>(grp.nrm + at), u1, u2);
+        o = ray.o;
+        d = ray.d;
+        return;
+    }
     if constexpr (G::kSparse) pix = grp.active[pix];
     const uint32_t row = uint32_t(div_by(pix, cam.width, grp.inv_width, px64));
     const uint32_t px = uint32_t(px64);
@@ -183,6 +246,19 @@ __global__ void __launch_bounds__(256) k_wf_generate(WfPool<R> pool, uint32_t co
     at(pool.sample, i) = uint64_t(i);
     at(pool.depth, i) = cam.max_depth;
     queue[i] = i;
+}
+
+// Irradiance bake on hit records (rt_bake_irradiance_hits_device): a record without RT_RAY_HIT or with RT_RAY_ENVIRONMENT has
+// no surface point, and its answer is (0, 0, 0, 0) exactly.  Runs after the chunk's last resolve; `flags` points at the flags
+// word of the chunk's first record.  (Such a record's samples are started like any other: its position and normal give
+// a non-finite ray that ends at its first search, or an environment's far point one path; k_wf_shade's restart reads no flags.)
+__global__ void __launch_bounds__(256) k_wf_points_mask(const unsigned char* __restrict__ flags, uint32_t stride, uint32_t n, double* __restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t f = *reinterpret_cast<const uint32_t*>(flags + uint64_t(i) * stride);
+    if (!(f & RT_RAY_HIT) || (f & RT_RAY_ENVIRONMENT)) {
+        out[4ull * i] = 0.0; out[4ull * i + 1u] = 0.0; out[4ull * i + 2u] = 0.0; out[4ull * i + 3u] = 0.0;
+    }
 }
 
 // Tail compaction.  Once every sample of a replica group has been started, finished slots stay empty and the queue is a
@@ -1252,8 +1328,8 @@ __device__ unsigned long long g_shade_stamps[16];
 #endif
 
 // G: WfGroup<R>, WfGroupSparse<R> for the restarts of an adaptive pass over the active pixels, WfGroupLG<R> to record the
-// light group of every terminal, or WfGroupRays<R> for restarts on a ray table (the driver then passes a camera WITH aperture:
-// the origin of a restarted slot is phase 2's to store)
+// light group of every terminal, or WfGroupRays<R> / WfGroupPoints<R> for restarts on a ray table / on the points of a bake (the
+// driver then passes a camera WITH aperture: the origin of a restarted slot is phase 2's to store)
 // FUSED: the workgroup then runs k_wf_prims' search over the slots it has just put into the next queue (phase 4 below), so that
 // the next iteration starts at k_wf_mesh.  The prims tables are staged whole over the shade tables.  The two codes share no
 // live value: the kernel needs the larger of the two register counts, not their sum (the round-2 fusion inlined the search
