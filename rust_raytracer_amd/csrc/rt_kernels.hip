@@ -835,32 +835,21 @@ MeshKernel<R> pick_mesh(bool stats, int node_kind, bool multi, bool slabs) {
     return stats ? pick_mesh_st<R, true>(node_kind, multi, slabs) : pick_mesh_st<R, false>(node_kind, multi, slabs);
 }
 
-// The lean k_wf_shade of any group type (WfGroup, WfGroupSparse: restarts through the active list, WfGroupLG: the terminal's
-// light group beside the radiance).  Interpreter variant: tables from global memory (rare scenes, fewer instantiations).
+// k_wf_shade of a group type G.  Every G has the lean variants (interpreter variant: tables from global memory - rare scenes,
+// fewer instantiations).  The fused kernel (+ k_wf_prims' search as phase 4) exists for the groups whose restarts leave it the
+// registers: WfGroup, WfGroupRays, WfGroupPoints.  The counting variants exist for WfGroup alone; a caller whose G has none
+// refuses collect_stats before it comes here.
+template <typename G> constexpr bool kShadeFused = !G::kSparse && !G::kLightGroups;
+template <typename R, typename G, bool ST>
+ShadeKernel<R, G> pick_shade_st(int lds, bool tex) {
+    if (tex) return &k_wf_shade<R, ST, 0, true, G>;
+    return lds == 1 ? &k_wf_shade<R, ST, 1, false, G> : (lds == 2 ? &k_wf_shade<R, ST, 2, false, G> : &k_wf_shade<R, ST, 0, false, G>);
+}
 template <typename R, typename G>
-ShadeKernel<R, G> pick_shade_lean(int lds, bool tex) {
-    if (tex) return &k_wf_shade<R, false, 0, true, G>;
-    return lds == 1 ? &k_wf_shade<R, false, 1, false, G> : (lds == 2 ? &k_wf_shade<R, false, 2, false, G> : &k_wf_shade<R, false, 0, false, G>);
-}
-// Ray tables (WfGroupRays): the lean variants, and the fused one where a plain render of the scene would run it.
-template <typename R>
-ShadeKernel<R, WfGroupRays<R>> pick_shade_rays(int lds, bool tex, bool fuse) {
-    if (fuse) return &k_wf_shade<R, false, 1, false, WfGroupRays<R>, true>;
-    return pick_shade_lean<R, WfGroupRays<R>>(lds, tex);
-}
-// Point tables of an irradiance bake (WfGroupPoints): the same set.
-template <typename R>
-ShadeKernel<R, WfGroupPoints<R>> pick_shade_points(int lds, bool tex, bool fuse) {
-    if (fuse) return &k_wf_shade<R, false, 1, false, WfGroupPoints<R>, true>;
-    return pick_shade_lean<R, WfGroupPoints<R>>(lds, tex);
-}
-// Dense groups also have the counting variants and the one fused kernel (+ k_wf_prims' search as phase 4).
-template <typename R>
-ShadeKernel<R, WfGroup<R>> pick_shade(bool stats, int lds, bool tex, bool fuse) {
-    if (fuse) return &k_wf_shade<R, false, 1, false, WfGroup<R>, true>;
-    if (!stats) return pick_shade_lean<R, WfGroup<R>>(lds, tex);
-    if (tex) return &k_wf_shade<R, true, 0, true>;
-    return lds == 1 ? &k_wf_shade<R, true, 1, false> : (lds == 2 ? &k_wf_shade<R, true, 2, false> : &k_wf_shade<R, true, 0, false>);
+ShadeKernel<R, G> pick_shade(bool stats, int lds, bool tex, bool fuse) {
+    if constexpr (kShadeFused<G>) if (fuse) return &k_wf_shade<R, false, 1, false, G, true>;
+    if (!stats) return pick_shade_st<R, G, false>(lds, tex);
+    return pick_shade_st<R, G, std::is_same_v<G, WfGroup<R>>>(lds, tex);  // no counting variants for the other groups: their modes refuse collect_stats
 }
 
 // ---- Search setup: which of k_wf_prims / k_wf_mesh / k_wf_intersect serve a scene, and with which grid, LDS and
@@ -1064,8 +1053,42 @@ int wf_ensure(RtScene* s, uint32_t capacity) {
     return RT_OK;
 }
 
+// ---- Render modes.  A call of render_wavefront has exactly one: a plain frame, a dense or a sparse adaptive pass, a light-group
+// render, a ray table or a point table.  The mode type says what the driver must not know: its replica-group type Group<R>
+// (k_wf_generate and k_wf_shade are instantiated per group type) and how one is completed from the common base the driver
+// fills (`complete`); how many pixels a group covers (`npix`); the refusal collect_stats meets (`kNoCounting`; null: the mode
+// has counting kernels); whether every sample has an origin of its own (`kOwnOrigins`); what a sample takes in device memory
+// and what else the call needs there (`kSampleBytes`, `reserve`); whether several groups keep running sums in
+// w.acc (`kRunningSums`); and how a finished replica group is resolved (`resolve`).  PassBase answers as a plain frame does. ----
+// A finished replica group as `resolve` sees it: nrep replicas of npix pixels in w.sample_L.  first / last: the call's first /
+// last group; resumed: the call continues a running sum in d_out.
+struct WfResolve {
+    RtScene::Wavefront& w;
+    uint64_t npix;
+    uint32_t strata, nrep, T;
+    double spp, *d_out;
+    int first, resumed, last;
+    hipStream_t stream;
+};
+struct PassBase {
+    template <typename R> using Group = WfGroup<R>;
+    static constexpr const char* kNoCounting = nullptr;
+    static constexpr bool kOwnOrigins = false, kRunningSums = true;
+    static constexpr uint32_t kSampleBytes = 24;  // radiance; what a mode adds to it lives in w.sample_G
+    uint64_t npix(uint64_t frame) const { return frame; }
+    int reserve(RtScene::Wavefront&, uint64_t, uint64_t, uint32_t, uint32_t, hipStream_t) const { return RT_OK; }  // (w, per_replica, npix, group, n, stream)
+    template <typename G> void complete(G&, RtScene::Wavefront&) const {}
+    int resolve(const WfResolve& a) const {
+        hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((a.npix + 255) / 256)), dim3(256), 0, a.stream, a.w.sample_L.get(), a.w.acc.get(), a.npix, a.strata,
+                           a.nrep, a.spp, a.first, a.resumed, a.d_out, a.last);
+        return RT_OK;
+    }
+};
+struct FramePass : PassBase {};
+
 // One segment of an adaptive accumulator's render (rt_accum_render): the resolve step goes through
-// k_wf_resolve_moments; sparse: the replica groups cover the n_active pixels of `active` instead of the frame.
+// k_wf_resolve_moments; sparse: the replica groups cover the n_active pixels of `active` instead of the frame.  The caller
+// dispatches on `sparse`: AdaptiveMode<false> / <true> are the two modes.
 struct AdaptivePass {
     const uint32_t* active = nullptr;
     uint32_t n_active = 0;
@@ -1073,32 +1096,86 @@ struct AdaptivePass {
     double *s1 = nullptr, *s2 = nullptr;
     uint32_t* cnt = nullptr;
 };
+template <bool SPARSE>
+struct AdaptiveMode : AdaptivePass, PassBase {
+    template <typename R> using Group = std::conditional_t<SPARSE, WfGroupSparse<R>, WfGroup<R>>;
+    static constexpr const char* kNoCounting = "adaptive passes have no counting kernels (collect_stats)";
+    static constexpr bool kRunningSums = false;  // every group resolves into the accumulator's sums
+    uint64_t npix(uint64_t frame) const { return SPARSE ? uint64_t(n_active) : frame; }
+    template <typename G> void complete(G& g, RtScene::Wavefront&) const { if constexpr (SPARSE) g.active = active; }
+    int resolve(const WfResolve& a) const {
+        hipLaunchKernelGGL(k_wf_resolve_moments<SPARSE>, dim3(uint32_t((a.npix + 255) / 256)), dim3(256), 0, a.stream, a.w.sample_L.get(), a.npix, a.strata,
+                           a.nrep, a.spp, double(a.T), active, a.d_out, s1, s2, cnt);
+        return RT_OK;
+    }
+};
 
 // A light-group render (rt_render_light_groups): k_wf_shade records the group of every terminal and
 // k_wf_resolve_groups sums per group.  `table` (host): n_materials + 2 bytes as WfGroupLG describes them.  d_out (the
 // ordinary frame, through the unchanged k_wf_resolve) may be NULL.
-struct LightGroupPass {
+struct LightGroupPass : PassBase {
     uint32_t n_groups = 0, n_materials = 0;
     const uint8_t* table = nullptr;
     double* d_groups_out = nullptr;
+    mutable double resolve_ms = 0;  // both resolve kernels, summed over the call's groups (RT_LG_LOG)
+    template <typename R> using Group = WfGroupLG<R>;
+    static constexpr const char* kNoCounting = "light groups have no adaptive or counting kernels (collect_stats)";
+    static constexpr uint32_t kSampleBytes = 25;  // + the group byte
+    int reserve(RtScene::Wavefront& w, uint64_t per_replica, uint64_t npix, uint32_t group, uint32_t n, hipStream_t stream) const {
+        if (int st = w.sample_G.reserve(size_t(per_replica) * group)) return st;
+        if (int st = w.acc_g.reserve(group < n ? size_t(npix) * 24 * n_groups : size_t(0))) return st;
+        const size_t need_t = size_t(n_materials) + 2;
+        if (int st = w.lg_table.reserve(need_t)) return st;
+        HIP_TRY(hipMemcpyAsync(w.lg_table, table, need_t, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));  // the host table may be the caller's stack
+        for (Event& e : w.ev_res)
+            if (int st = e.ensure()) return st;
+        return RT_OK;
+    }
+    template <typename G> void complete(G& g, RtScene::Wavefront& w) const { g.sample_G = w.sample_G; g.table = w.lg_table; g.n_materials = n_materials; }
+    int resolve(const WfResolve& a) const {
+        HIP_TRY(hipEventRecord(a.w.ev_res[0], a.stream));
+        if (a.d_out) PassBase::resolve(a);
+        const uint64_t blocks = ((a.npix + 63) / 64) * ((n_groups + 3u) / 4u);
+        if (blocks > 0x7FFFFFFFull) return set_err(RT_E_UNSUPPORTED, "frame too large for the light-group resolve");
+        hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, a.stream, a.w.sample_L.get(), a.w.sample_G.get(), a.w.acc_g.get(), a.npix,
+                           n_groups, a.strata, a.nrep, a.spp, a.first, d_groups_out, a.last);
+        HIP_TRY(hipEventRecord(a.w.ev_res[1], a.stream));
+        HIP_TRY(hipStreamSynchronize(a.stream));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, a.w.ev_res[0], a.w.ev_res[1]));
+        resolve_ms += ms;
+        if (a.last && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
+            std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", n_groups, resolve_ms,
+                         a.w.sample_G.bytes(), a.w.acc_g.bytes());
+        return RT_OK;
+    }
 };
 
 // A render along a ray table (rt_render_rays): one chunk of the caller's table.  The "frame" is n x 1
 // pixels, pixel i = ray first + i; origins / dirs are device pointers to the chunk's first ray.
-struct RayTablePass {
+struct RayTablePass : PassBase {
     const double* origins = nullptr;
     const double* dirs = nullptr;
     uint64_t first = 0;
+    template <typename R> using Group = WfGroupRays<R>;
+    static constexpr const char* kNoCounting = "ray tables have no adaptive, light-group or counting kernels (collect_stats)";
+    static constexpr bool kOwnOrigins = true;
+    template <typename G> void complete(G& g, RtScene::Wavefront&) const { g.origins = origins; g.dirs = dirs; g.first = first; }
 };
 
 // An irradiance bake (rt_bake_irradiance): one chunk of the caller's points.  The "frame" is n x 1 pixels,
 // pixel i = point first + i; pos / nrm are device pointers to the chunk's first position and normal, `stride` bytes apart
 // from point to point (24: plain arrays; sizeof(RtRayHit): hit records).
-struct PointTablePass {
+struct PointTablePass : PassBase {
     const unsigned char* pos = nullptr;
     const unsigned char* nrm = nullptr;
     uint32_t stride = 24;
     uint64_t first = 0;
+    template <typename R> using Group = WfGroupPoints<R>;
+    static constexpr const char* kNoCounting = "point tables have no adaptive, light-group or counting kernels (collect_stats)";
+    static constexpr bool kOwnOrigins = true;
+    template <typename G> void complete(G& g, RtScene::Wavefront&) const { g.pos = pos; g.nrm = nrm; g.stride = stride; g.first = first; }
 };
 
 // Pool size of a render.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
@@ -1121,31 +1198,22 @@ static uint32_t wf_pool_capacity(uint32_t strata, uint64_t npix_frame, uint32_t 
     return std::max<uint32_t>(capacity, 64u);
 }
 
-// The per-sample radiance buffer of a call that renders n replicas of per_replica samples each: *group_out = replicas per
-// group, as many as the memory budget allows, and every buffer the resolve kernels need for that (grow only).
-static int wf_plan_samples(RtScene::Wavefront& w, uint64_t per_replica, uint64_t npix, uint32_t n, bool adaptive, const LightGroupPass* lg,
-                           hipStream_t stream, uint32_t* group_out) {
+// The per-sample buffers' plan of a call that renders n replicas of per_replica samples each: *group_out = replicas per group,
+// as many as the memory budget allows at sample_bytes per sample (24 of radiance in sample_L; a mode's own bytes in sample_G),
+// sample_L for them, and the running sums between several groups if the mode keeps any (grow only).
+static int wf_plan_samples(RtScene::Wavefront& w, uint64_t per_replica, uint64_t npix, uint32_t n, uint32_t sample_bytes, bool running_sums,
+                           uint32_t* group_out) {
     size_t free_b = 0, total_b = 0;
     HIP_TRY(hipMemGetInfo(&free_b, &total_b));
     size_t budget = size_t(env_u32("RT_WF_SAMPLE_GB", 64)) << 30;
-    size_t avail = free_b + w.sample_L.bytes() + (lg ? w.sample_G.bytes() : size_t(0));
+    size_t avail = free_b + w.sample_L.bytes() + (sample_bytes > 24 ? w.sample_G.bytes() : size_t(0));
     if (budget > avail / 2) budget = avail / 2;
-    uint64_t bytes_per_replica = per_replica * (lg ? 25ull : 24ull);  // radiance, + the group byte of a light-group render
+    uint64_t bytes_per_replica = per_replica * sample_bytes;
     uint32_t group = uint32_t(std::min<uint64_t>(n, std::max<uint64_t>(1, budget / bytes_per_replica)));
     group = (n + (n + group - 1) / group - 1) / ((n + group - 1) / group);  // same number of groups, equal sizes (9 + 1 -> 5 + 5)
     if (bytes_per_replica > avail) return set_err(RT_E_NOMEM, "per-sample radiance buffer of one replica does not fit in device memory");
     if (int st = w.sample_L.reserve(size_t(per_replica) * 24 * group)) return st;
-    if (lg) {
-        if (int st = w.sample_G.reserve(size_t(per_replica) * group)) return st;
-        if (int st = w.acc_g.reserve(group < n ? size_t(npix) * 24 * lg->n_groups : size_t(0))) return st;
-        const size_t need_t = size_t(lg->n_materials) + 2;
-        if (int st = w.lg_table.reserve(need_t)) return st;
-        HIP_TRY(hipMemcpyAsync(w.lg_table, lg->table, need_t, hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));  // the host table may be the caller's stack
-        for (Event& e : w.ev_res)
-            if (int st = e.ensure()) return st;
-    }
-    if (group < n && !adaptive)  // several groups: running sums between them (adaptive: every group resolves into the accumulator's sums)
+    if (group < n && running_sums)  // several groups: running sums between them
         if (int st = w.acc.reserve(size_t(npix) * 24)) return st;
     *group_out = group;
     return RT_OK;
@@ -1181,14 +1249,13 @@ int wf_trace_dump(const WfPool<R>& pool, uint32_t first, const uint32_t* queue, 
 // intersect), 2 = shade.
 struct WfTally {
     double phase_ms[3];
-    double resolve_ms;           // light-group renders: both resolve kernels
     uint32_t search_launches;    // stand-alone k_wf_prims / k_wf_intersect launches
     uint32_t iterations, n_groups, n_compactions;
 };
 
 // RtRenderStats of a wavefront render that has ended (ev0 .. ev1 of the scene span it), and its debug lines.
 template <typename R>
-int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, const LightGroupPass* lg, bool fusable, uint64_t samples) {
+int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, bool fusable, uint64_t samples) {
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, s->ev0, s->ev1));
     DeviceCounters hc{};
@@ -1203,9 +1270,6 @@ int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, const
     st.n_iterations = ty.iterations;
     st.n_replica_groups = ty.n_groups;
     st.n_tail_compactions = ty.n_compactions;
-    if (lg && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
-        std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", lg->n_groups, ty.resolve_ms,
-                     s->wf.sample_G.bytes(), s->wf.acc_g.bytes());
     if (su.stats && su.split && env_u32("RT_WF_DEBUG", 0)) {
         std::fprintf(stderr, "[k_wf_mesh] grid %u workgroups, %d per CU, %zu B of LDS each; hand-out mode %u, 256 / 128 entries above %u / %u left per wave\n",
                      su.isect_blocks, su.blocks_per_cu, su.lds_mesh, su.handout.mode, su.handout.left256, su.handout.left128);
@@ -1240,26 +1304,23 @@ int wf_fill_stats(RtScene* s, const SearchSetup<R>& su, const WfTally& ty, const
     return RT_OK;
 }
 
+// What a call of render_wavefront settles before its first replica group, whatever its mode: the pool's size, the replicas per
+// group, the search setup, the LDS forms of k_wf_shade and the environment switches of the loop.
 template <typename R>
-int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
-                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const AdaptivePass* ad = nullptr,
-                     const LightGroupPass* lg = nullptr, const RayTablePass* rays = nullptr, const PointTablePass* points = nullptr) {
-    CameraView<R> cv = make_camera_view<R>(cam, p);
-    if (rays || points) cv.has_aperture = 1;  // every sample has an origin of its own: k_wf_shade's restarts store it (phase 2)
-    ParamsView<R> pv = make_params_view<R>(p, owned);
-    const uint64_t npix_frame = uint64_t(cam.image_width) * owned;
-    const bool sparse = ad && ad->sparse;
-    const uint64_t npix = sparse ? uint64_t(ad->n_active) : npix_frame;  // pixels a replica group covers
-    if (ad && p.collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
-    if (npix == 0) return set_err(RT_E_INVALID, "adaptive pass without active pixels");
-    if (lg && (ad || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "light groups have no adaptive or counting kernels (collect_stats)");
-    if (rays && (ad || lg || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "ray tables have no adaptive, light-group or counting kernels (collect_stats)");
-    if (points && (ad || lg || rays || p.collect_stats)) return set_err(RT_E_UNSUPPORTED, "point tables have no adaptive, light-group or counting kernels (collect_stats)");
+struct WfRun {
+    SearchSetup<R> su;
+    uint32_t capacity, group, staged_shade, shade_tables_max, compact_min, compact_pct, check_every, shade_lds_pad;
+    int lds_shade;
+    bool tex, compact_tail, iter_log, trace_pool, fusable;  // fusable: the scene and the switches allow the fused k_wf_shade; the mode's group type has the other say
+    template <typename G> ShadeKernel<R, G> shade(bool fuse) const { return pick_shade<R, G>(su.stats, lds_shade, tex, fuse); }
+};
+
+// npix_frame, T: the whole frame's, for the pool; the rest describes this call's samples (wf_plan_samples).
+template <typename R>
+int wf_prepare(RtScene* s, DeviceScene<R>& ds, const RtRenderParams& p, uint64_t npix_frame, uint64_t npix, uint32_t n, uint32_t sample_bytes,
+               bool running_sums, WfRun<R>& run) {
     const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
-    const uint32_t T = p.thread_count;
-    const uint32_t t_end = t_first + n;
-    const uint64_t per_replica = uint64_t(strata) * npix;
-    uint32_t capacity = wf_pool_capacity(strata, npix_frame, T);
+    uint32_t capacity = wf_pool_capacity(strata, npix_frame, p.thread_count);
     // the pool is a matter of speed, not of correctness: when device memory is short (other scenes of a frame pipeline, other
     // processes on the card) a smaller one renders the same frame
     for (;;) {
@@ -1268,206 +1329,177 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         if (st != RT_E_NOMEM || capacity <= (1u << 20) || std::getenv("RT_WF_POOL")) return st;
         capacity = std::max<uint32_t>(1u << 20, (capacity / 2) & ~0xFFFFFu);
     }
+    run.capacity = capacity;
+    if (int st = wf_plan_samples(s->wf, uint64_t(strata) * npix, npix, n, sample_bytes, running_sums, &run.group)) return st;
+    const bool vol = !s->compiled.volumes.empty();  // volume ops: combined intersect kernel, VOL variant
+    SearchSetup<R>& su = run.su;
+    if (int st = make_search_setup<R>(s, ds, p.collect_stats != 0, vol, &su)) return st;
+    if (int st = s->wf.mesh_spill.reserve(su.spill_bytes)) return st;
+    run.staged_shade = staged_prefix(ds.view.lay_shade, su.lds_tables, su.lds_budget);
+    // k_wf_shade: all or nothing (a staged prefix read through flat instructions was 3 % slower than global memory on the default scene),
+    // and only while five workgroups still fit a CU's 160 KB next to its lists (<= 23 KB of tables; RT_LDS_SHADE_MAX overrides)
+    run.shade_tables_max = env_u32("RT_LDS_SHADE_MAX", 32u * 1024u - kShadeListBytes);
+    run.lds_shade = (run.staged_shade != 0 && run.staged_shade == ds.view.lay_shade.total_bytes && run.staged_shade <= run.shade_tables_max) ? 1 : (env_u32("RT_LDS_SHADE_PREFIX", 0) && run.staged_shade ? 2 : 0);
+    // tail compaction: RT_WF_COMPACT=0 keeps the paths where they are (A/B, tests), RT_WF_COMPACT_MIN = fewest paths worth a launch
+    run.compact_tail = env_u32("RT_WF_COMPACT", 1) != 0;
+    run.compact_min = std::max<uint32_t>(1u, env_u32("RT_WF_COMPACT_MIN", 1024));
+    run.compact_pct = std::min<uint32_t>(75u, std::max<uint32_t>(1u, env_u32("RT_WF_COMPACT_PCT", 50)));  // ... when at most this share of the addressed slots is alive.  50 / 62 / 75: the tail's iterations of C2 take 13.0 / 12.4 / 11.9 ms, but the paths thin out by ~22 % per iteration, so 75 compacts after nearly every one (13 copies of 0.3 ms per C2 frame, 6 with 50); whole frames are equal within the noise
+    run.iter_log = env_u32("RT_WF_ITER_LOG", 0) != 0;
+    run.trace_pool = env_u32("RT_WF_TRACE", 0) != 0;  // debug: dump the first pool slots after every iteration
+    run.check_every = run.trace_pool ? 1u : std::min<uint32_t>(32u, std::max<uint32_t>(1u, env_u32("RT_WF_CHECK", 8)));  // 4 timing events per iteration, 128 events
+    run.tex = s->compiled.needs_tex_interpreter;
+    run.shade_lds_pad = env_u32("RT_WF_SHADE_LDS_PAD", 0);  // experiments: fewer resident blocks of the shade kernel
+    // k_wf_prims as phase 4 of k_wf_shade (rt_wavefront.h): the lean dense variant with BOTH table sets staged whole in LDS, the
+    // prims set within what the shade kernel may ask for at five workgroups per CU.  With the tables in global memory the fused
+    // kernel needs scratch (f64 32 B, f32 80 B; tools/kernel_regs.py), so those scenes - and volumes, re-built groups, the texture
+    // interpreter and the counting variants - keep the stand-alone kernel; so do the group types without a fused kernel
+    // (kShadeFused: sparse adaptive passes, light-group renders), which is the caller's to add.
+    // Programs with more than one mesh op keep it too: tests/scenes/two_meshes lost 2.4 % of its frame fused (DESIGN.md section 6,
+    // round 5).  RT_WF_FUSE=0: the unfused pipeline (A/B control, reference of the tests); 2: fused wherever the kernel exists,
+    // whatever the plan says (tests, A/B).
+    const uint32_t fuse_mode = env_u32("RT_WF_FUSE", 1);
+    run.fusable = (su.split || su.prims_only) && !vol && !su.groups && !run.tex && su.lds_prims == 1 && run.lds_shade == 1 &&
+                  su.staged_prims <= run.shade_tables_max && fuse_mode != 0 && (!su.plan.multi_mesh || fuse_mode == 2);
+    // Every kernel the modes instantiate for R, named once, behind the search kernels.  The compiler emits a kernel where it is
+    // first named, so this list - in the order the code object has had since the driver was one function that named them all -
+    // keeps the library's device code byte for byte the same whichever mode's driver is instantiated first
+    // (profiles/wavefront_modes/README.md); WfRun::shade, not pick_shade itself, is what the driver calls for the same reason.
+    (void)&pick_shade<R, WfGroup<R>>, (void)&pick_shade<R, WfGroupSparse<R>>, (void)&pick_shade<R, WfGroupLG<R>>;
+    (void)&pick_shade<R, WfGroupRays<R>>, (void)&pick_shade<R, WfGroupPoints<R>>;
+    (void)&k_wf_generate<R, WfGroupPoints<R>>, (void)&k_wf_generate<R, WfGroupRays<R>>, (void)&k_wf_generate<R, WfGroupSparse<R>>, (void)&k_wf_generate<R, WfGroup<R>>;
+    (void)&k_wf_compact<R>, (void)&k_wf_resolve_moments<true>, (void)&k_wf_resolve_moments<false>;
+    return RT_OK;
+}
+
+// One replica group through the pool: k_wf_generate, then search and k_wf_shade until the queue is empty, tail compaction
+// included.  The group type G is all this knows of the call's mode: G's generate kernel, and the k_wf_shade picked for G.
+template <typename R, typename G>
+int wf_run_group(RtScene* s, DeviceScene<R>& ds, const WfRun<R>& run, const G& grp, ShadeKernel<R, G> shade, bool fuse, const CameraView<R>& cv,
+                 const ParamsView<R>& pv, bool last_group, hipStream_t stream, WfTally& ty) {
     RtScene::Wavefront& w = s->wf;
+    const SearchSetup<R>& su = run.su;
     const PoolPair<R>& pools = std::get<PoolPair<R>>(w.pools);
     const WfPool<R> pool_a = pools[0].view, pool_b = pools[1].view;
     WfPool<R> pool = pool_a;  // the pool the kernels are working on (changes at a tail compaction)
     const WfPool<R>* pool_dev_cur = pools[0].dev;
     uint32_t* const queue[2] = {pools[0].queue[0], pools[0].queue[1]};
     uint32_t* const mesh_queue = pools[0].mesh_queue;
+    const size_t shade_tables_lds = run.lds_shade == 0 ? size_t(0) : (fuse ? size_t(std::max(run.staged_shade, su.staged_prims)) : size_t(run.staged_shade));
+    bool prims_ran[32];  // per iteration of a batch (check_every <= 32): k_wf_prims was launched
+    uint32_t first = uint32_t(std::min<uint64_t>(run.capacity, grp.total));
+    bool on_b = false;
+    pool.capacity = first;  // slots in use by this group: the kernels address slots directly while all of them are queued
+    *w.h_ctr = WfCounters{first, 0, 0, 0, first, 0};  // n_in, n_out, cursor, n_mesh, next_sample, n_mesh_next
+    HIP_TRY(hipMemcpyAsync(w.d_ctr, w.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
+    // k_wf_generate is the group type's own wherever the group's first rays are (active list, ray table, point table); a
+    // light-group render starts its samples as a plain frame does, through WfGroup's kernel: no instantiation of its own
+    hipLaunchKernelGGL((k_wf_generate<R, std::conditional_t<G::kLightGroups, WfGroup<R>, G>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, queue[0]);
+    int qi = 0;
+    bool hits_ready = false;  // the hit records and the mesh queue of the current queue exist already (phase 4 of a fused k_wf_shade)
+    uint32_t upper = first;  // upper bound of the queue length (never grows: slots are reused in place)
+    for (;;) {
+        size_t ev = 0;
+        // near the end of the call's last group the host looks after every second iteration, so that the tail is seen when it starts
+        const bool near_end = s->tail_flag && last_group && w.h_ctr->next_sample + 4ull * pool.capacity >= grp.total;
+        // tail compaction wants to see the queue length of every iteration once the samples have run out, and to notice
+        // within two iterations that they have (a quarter of the slots restarts per iteration)
+        const bool all_started = w.h_ctr->next_sample >= grp.total;
+        const bool closing = run.compact_tail && w.h_ctr->next_sample + 2ull * pool.capacity >= grp.total;
+        const uint32_t check_now = (run.compact_tail && all_started) ? 1u : ((near_end || closing) ? std::min<uint32_t>(run.check_every, 2u) : run.check_every);
+        for (uint32_t k = 0; k < check_now; k++) {
+            HIP_TRY(hipEventRecord(w.events[ev++], stream));
+            const SearchQueues sq{queue[qi], mesh_queue, w.mesh_spill, w.d_ctr, s->d_counters, stream};
+            prims_ran[k] = (su.split || su.prims_only) && !hits_ready;
+            if (prims_ran[k]) launch_prims(su, ds, pool, sq, upper);
+            HIP_TRY(hipEventRecord(w.events[ev++], stream));
+            if (su.split) launch_mesh(su, ds, pool, sq);
+            else if (!su.prims_only) launch_intersect(su, ds, pool, sq);  // the combined kernel
+            if (prims_ran[k] || !(su.split || su.prims_only)) ty.search_launches++;
+            HIP_TRY(hipEventRecord(w.events[ev++], stream));
+            hipLaunchKernelGGL(shade, dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), shade_tables_lds + kShadeListBytes + run.shade_lds_pad, stream,
+                               ds.view, cv, pv, pool, grp, queue[qi], queue[qi ^ 1], w.d_ctr.get(), w.sample_L.get(), s->d_counters.get(),
+                               pool_dev_cur, run.staged_shade, mesh_queue);
+            if (fuse) hits_ready = true;  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
+            hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr.get());
+            HIP_TRY(hipEventRecord(w.events[ev++], stream));
+            qi ^= 1;
+            ty.iterations++;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(w.h_ctr, w.d_ctr, sizeof(WfCounters), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        for (size_t e = 0; e + 3 < ev; e += 4) {
+            float it_ms[3];
+            for (int ph = 0; ph < 3; ph++) {
+                it_ms[ph] = 0.f;
+                HIP_TRY(hipEventElapsedTime(&it_ms[ph], w.events[e + ph], w.events[e + ph + 1]));
+                if (ph == 0 && (su.split || su.prims_only) && !prims_ran[e / 4]) it_ms[ph] = 0.f;  // no launch between the two events
+                ty.phase_ms[ph] += it_ms[ph];
+            }
+            if (run.iter_log)  // RT_WF_ITER_LOG=1 (with RT_WF_CHECK=1 the queue length printed is the one of this very iteration)
+                std::fprintf(stderr, "[wf iter] group %u: <= %u paths queued: prims %.3f ms, traversal %.3f ms, shade %.3f ms\n", ty.n_groups, upper,
+                             it_ms[0], it_ms[1], it_ms[2]);
+        }
+        if (run.trace_pool)
+            if (int st = wf_trace_dump(pool, first, queue[qi], w.h_ctr->n_in, ty.iterations)) return st;
+        upper = w.h_ctr->n_in;
+        // every sample of the call's last group has been started and slots are running empty: from here on this render
+        // cannot fill the GPU any more, the next frame's render (another RtScene, another stream) may start underneath it
+        if (s->tail_flag && last_group && upper < first) __atomic_store_n(s->tail_flag, 1, __ATOMIC_RELEASE);
+        if (upper == 0) break;
+        // ---- tail compaction (rt_wavefront.h k_wf_compact): fewer than half of the addressed slots are alive and none will
+        //      restart: the live paths move to slots 0 .. upper-1 of the other pool, which becomes the pool ----
+        if (run.compact_tail && w.h_ctr->next_sample >= grp.total && upper >= run.compact_min && uint64_t(upper) * 100 <= uint64_t(pool.capacity) * run.compact_pct) {
+            WfPool<R> dst = on_b ? pool_a : pool_b;
+            hipLaunchKernelGGL((k_wf_compact<R>), dim3((upper + 255) / 256), dim3(256), 0, stream, pool, dst, queue[qi], upper);
+            on_b = !on_b;
+            pool = dst;
+            pool.capacity = upper;  // n_in == capacity: the kernels address slot i for entry i again
+            pool_dev_cur = pools[on_b ? 1 : 0].dev;
+            ty.n_compactions++;
+            if (hits_ready) {  // the hit records stayed behind and the mesh queue names the old slots: stand-alone k_wf_prims next
+                HIP_TRY(hipMemsetAsync(&w.d_ctr->n_mesh, 0, sizeof(uint32_t), stream));
+                hits_ready = false;
+            }
+        }
+    }
+    return RT_OK;
+}
 
-    uint32_t group = 0;  // replicas per group
-    if (int st = wf_plan_samples(w, per_replica, npix, n, ad != nullptr, lg, stream, &group)) return st;
-
-    const bool stats = p.collect_stats != 0;
-    const bool vol = !s->compiled.volumes.empty();  // volume ops: combined intersect kernel, VOL variant
-    SearchSetup<R> su;
-    if (int st = make_search_setup<R>(s, ds, stats, vol, &su)) return st;
-    if (int st = w.mesh_spill.reserve(su.spill_bytes)) return st;
-    const uint32_t staged_shade = staged_prefix(ds.view.lay_shade, su.lds_tables, su.lds_budget);
-    // k_wf_shade: all or nothing (a staged prefix read through flat instructions was 3 % slower than global memory on the default scene),
-    // and only while five workgroups still fit a CU's 160 KB next to its lists (<= 23 KB of tables; RT_LDS_SHADE_MAX overrides)
-    const uint32_t shade_tables_max = env_u32("RT_LDS_SHADE_MAX", 32u * 1024u - kShadeListBytes);
-    const int lds_shade = (staged_shade != 0 && staged_shade == ds.view.lay_shade.total_bytes && staged_shade <= shade_tables_max) ? 1 : (env_u32("RT_LDS_SHADE_PREFIX", 0) && staged_shade ? 2 : 0);
-    // tail compaction: RT_WF_COMPACT=0 keeps the paths where they are (A/B, tests), RT_WF_COMPACT_MIN = fewest paths worth a launch
-    const bool compact_tail = env_u32("RT_WF_COMPACT", 1) != 0;
-    const uint32_t compact_min = std::max<uint32_t>(1u, env_u32("RT_WF_COMPACT_MIN", 1024));
-    const uint32_t compact_pct = std::min<uint32_t>(75u, std::max<uint32_t>(1u, env_u32("RT_WF_COMPACT_PCT", 50)));  // ... when at most this share of the addressed slots is alive.  50 / 62 / 75: the tail's iterations of C2 take 13.0 / 12.4 / 11.9 ms, but the paths thin out by ~22 % per iteration, so 75 compacts after nearly every one (13 copies of 0.3 ms per C2 frame, 6 with 50); whole frames are equal within the noise
-    const bool iter_log = env_u32("RT_WF_ITER_LOG", 0) != 0;
-    const bool trace_pool = env_u32("RT_WF_TRACE", 0) != 0;  // debug: dump the first pool slots after every iteration
-    const uint32_t check_every = trace_pool ? 1u : std::min<uint32_t>(32u, std::max<uint32_t>(1u, env_u32("RT_WF_CHECK", 8)));  // 4 timing events per iteration, 128 events
-    const bool tex = s->compiled.needs_tex_interpreter;
-    const size_t shade_lds_pad = env_u32("RT_WF_SHADE_LDS_PAD", 0);  // experiments: fewer resident blocks of the shade kernel
-    // k_wf_prims as phase 4 of k_wf_shade (rt_wavefront.h): the lean dense variant with BOTH table sets staged whole in LDS, the
-    // prims set within what the shade kernel may ask for at five workgroups per CU.  With the tables in global memory the fused
-    // kernel needs scratch (f64 32 B, f32 80 B; tools/kernel_regs.py), so those scenes - and volumes, re-built groups, the texture
-    // interpreter, sparse adaptive passes, light-group renders and the counting variants - keep the stand-alone kernel.  A ray
-    // table and a point table run the form a plain render of the scene runs.
-    // Programs with more than one mesh op keep it too: tests/scenes/two_meshes lost 2.4 % of its frame fused (DESIGN.md section 6,
-    // round 5).  RT_WF_FUSE=0: the unfused pipeline (A/B control, reference of the tests); 2: fused wherever the kernel exists,
-    // whatever the plan says (tests, A/B).
-    const uint32_t fuse_mode = env_u32("RT_WF_FUSE", 1);
-    const bool fusable = (su.split || su.prims_only) && !vol && !su.groups && !tex && !lg && !sparse && su.lds_prims == 1 && lds_shade == 1 &&
-                         su.staged_prims <= shade_tables_max && fuse_mode != 0 && (!su.plan.multi_mesh || fuse_mode == 2);
-    const bool fuse = fusable && !stats;
-    const size_t shade_tables_lds = lds_shade == 0 ? size_t(0) : (fuse ? size_t(std::max(staged_shade, su.staged_prims)) : size_t(staged_shade));
-    // the shade kernel of each group type (a render uses one of them; all exist in the library anyway)
-    const ShadeKernel<R, WfGroup<R>> shade_dense = pick_shade<R>(stats, lds_shade, tex, fuse);
-    const ShadeKernel<R, WfGroupSparse<R>> shade_sparse = pick_shade_lean<R, WfGroupSparse<R>>(lds_shade, tex);
-    const ShadeKernel<R, WfGroupLG<R>> shade_lg = pick_shade_lean<R, WfGroupLG<R>>(lds_shade, tex);
-    const ShadeKernel<R, WfGroupRays<R>> shade_rays = pick_shade_rays<R>(lds_shade, tex, fuse);
-    const ShadeKernel<R, WfGroupPoints<R>> shade_points = pick_shade_points<R>(lds_shade, tex, fuse);
+template <typename R, typename Pass>
+int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtRenderParams& p, uint32_t owned,
+                     uint32_t t_first, uint32_t n, double* d_out, hipStream_t stream, const Pass& pass) {
+    using G = typename Pass::template Group<R>;
+    CameraView<R> cv = make_camera_view<R>(cam, p);
+    if (Pass::kOwnOrigins) cv.has_aperture = 1;  // k_wf_shade's restarts store the origin (phase 2)
+    ParamsView<R> pv = make_params_view<R>(p, owned);
+    const uint64_t npix_frame = uint64_t(cam.image_width) * owned;
+    const uint64_t npix = pass.npix(npix_frame);  // pixels a replica group covers
+    if (Pass::kNoCounting && p.collect_stats) return set_err(RT_E_UNSUPPORTED, Pass::kNoCounting);
+    if (npix == 0) return set_err(RT_E_INVALID, "adaptive pass without active pixels");
+    const uint32_t strata = p.sqrt_spt * p.sqrt_spt;
+    const uint32_t t_end = t_first + n;
+    const uint64_t per_replica = uint64_t(strata) * npix;
+    WfRun<R> run;
+    if (int st = wf_prepare<R>(s, ds, p, npix_frame, npix, n, Pass::kSampleBytes, Pass::kRunningSums, run)) return st;
+    if (int st = pass.reserve(s->wf, per_replica, npix, run.group, n, stream)) return st;
+    const bool fusable = run.fusable && kShadeFused<G>;
+    const bool fuse = fusable && !run.su.stats;
+    const ShadeKernel<R, G> shade = run.template shade<G>(fuse);
 
     HIP_TRY(hipMemsetAsync(s->d_counters, 0, sizeof(DeviceCounters), stream));
     HIP_TRY(hipEventRecord(s->ev0, stream));
     WfTally ty{};
-    bool prims_ran[32];  // per iteration of a batch (check_every <= 32): k_wf_prims was launched
-    for (uint32_t t0 = t_first; t0 < t_end; t0 += group) {
+    for (uint32_t t0 = t_first; t0 < t_end; t0 += run.group) {
         ty.n_groups++;
-        uint32_t nrep = std::min(group, t_end - t0);
-        WfGroup<R> grp{};
-        grp.total = per_replica * nrep;
-        grp.npix = npix;
-        grp.per_replica = per_replica;
-        grp.inv_per_replica = 1.0 / double(per_replica);
-        grp.inv_npix = 1.0 / double(npix);
-        grp.inv_width = 1.0 / double(cam.image_width);
-        grp.tid0 = t0;
-        grp.strata = strata;
-        WfGroupSparse<R> grp_s{};
-        static_cast<WfGroup<R>&>(grp_s) = grp;
-        grp_s.active = sparse ? ad->active : nullptr;
-        WfGroupLG<R> grp_lg{};
-        static_cast<WfGroup<R>&>(grp_lg) = grp;
-        grp_lg.sample_G = w.sample_G;
-        grp_lg.table = w.lg_table;
-        grp_lg.n_materials = lg ? lg->n_materials : 0u;
-        WfGroupRays<R> grp_r{};
-        static_cast<WfGroup<R>&>(grp_r) = grp;
-        if (rays) { grp_r.origins = rays->origins; grp_r.dirs = rays->dirs; grp_r.first = rays->first; }
-        WfGroupPoints<R> grp_p{};
-        static_cast<WfGroup<R>&>(grp_p) = grp;
-        if (points) { grp_p.pos = points->pos; grp_p.nrm = points->nrm; grp_p.stride = points->stride; grp_p.first = points->first; }
+        const uint32_t nrep = std::min(run.group, t_end - t0);
+        const bool last_group = t0 + nrep >= t_end;
+        G grp{};  // the base: total, npix, per_replica, their reciprocals and the width's, tid0, strata; the rest is the mode's
+        static_cast<WfGroup<R>&>(grp) = WfGroup<R>{per_replica * nrep, npix, per_replica, 1.0 / double(per_replica), 1.0 / double(npix), 1.0 / double(cam.image_width), t0, strata};
+        pass.complete(grp, s->wf);
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
-        uint32_t first = uint32_t(std::min<uint64_t>(capacity, grp.total));
-        pool = pool_a;
-        pool_dev_cur = pools[0].dev;
-        bool on_b = false;
-        pool.capacity = first;  // slots in use by this group: the kernels address slots directly while all of them are queued
-        WfCounters init{};
-        init.n_in = first;
-        init.n_out = 0;
-        init.cursor = 0;
-        init.n_mesh = 0;
-        init.next_sample = first;
-        *w.h_ctr = init;
-        HIP_TRY(hipMemcpyAsync(w.d_ctr, w.h_ctr, sizeof(WfCounters), hipMemcpyHostToDevice, stream));
-        if (points) hipLaunchKernelGGL((k_wf_generate<R, WfGroupPoints<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_p, cv, pv, queue[0]);
-        else if (rays) hipLaunchKernelGGL((k_wf_generate<R, WfGroupRays<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_r, cv, pv, queue[0]);
-        else if (sparse) hipLaunchKernelGGL((k_wf_generate<R, WfGroupSparse<R>>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp_s, cv, pv, queue[0]);
-        else hipLaunchKernelGGL((k_wf_generate<R>), dim3((first + 255) / 256), dim3(256), 0, stream, pool, first, grp, cv, pv, queue[0]);
-        int qi = 0;
-        bool hits_ready = false;  // the hit records and the mesh queue of the current queue exist already (phase 4 of a fused k_wf_shade)
-        uint32_t upper = first;  // upper bound of the queue length (never grows: slots are reused in place)
-        auto launch_shade = [&](auto kernel, const auto& g) {
-            hipLaunchKernelGGL(kernel, dim3((upper + WF_CHUNK - 1) / WF_CHUNK), dim3(256), shade_tables_lds + kShadeListBytes + shade_lds_pad, stream,
-                               ds.view, cv, pv, pool, g, queue[qi], queue[qi ^ 1], w.d_ctr.get(), w.sample_L.get(), s->d_counters.get(),
-                               pool_dev_cur, staged_shade, mesh_queue);
-        };
-        for (;;) {
-            size_t ev = 0;
-            // near the end of the call's last group the host looks after every second iteration, so that the tail is seen when it starts
-            const bool near_end = s->tail_flag && t0 + nrep >= t_end && w.h_ctr->next_sample + 4ull * pool.capacity >= grp.total;
-            // tail compaction wants to see the queue length of every iteration once the samples have run out, and to notice
-            // within two iterations that they have (a quarter of the slots restarts per iteration)
-            const bool all_started = w.h_ctr->next_sample >= grp.total;
-            const bool closing = compact_tail && w.h_ctr->next_sample + 2ull * pool.capacity >= grp.total;
-            const uint32_t check_now = (compact_tail && all_started) ? 1u : ((near_end || closing) ? std::min<uint32_t>(check_every, 2u) : check_every);
-            for (uint32_t k = 0; k < check_now; k++) {
-                HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                const SearchQueues sq{queue[qi], mesh_queue, w.mesh_spill, w.d_ctr, s->d_counters, stream};
-                prims_ran[k] = (su.split || su.prims_only) && !hits_ready;
-                if (su.split || su.prims_only) {
-                    if (!hits_ready) { launch_prims(su, ds, pool, sq, upper); ty.search_launches++; }
-                    HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                    if (su.split) launch_mesh(su, ds, pool, sq);
-                    HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                } else {
-                    HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                    launch_intersect(su, ds, pool, sq);
-                    ty.search_launches++;
-                    HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                }
-                if (points) launch_shade(shade_points, grp_p);
-                else if (rays) launch_shade(shade_rays, grp_r);
-                else if (lg) launch_shade(shade_lg, grp_lg);
-                else if (sparse) launch_shade(shade_sparse, grp_s);
-                else launch_shade(shade_dense, grp);
-                if (fuse) hits_ready = true;  // + k_wf_prims' search for the next queue: the next iteration starts at k_wf_mesh
-                hipLaunchKernelGGL(k_wf_advance, dim3(1), dim3(1), 0, stream, w.d_ctr.get());
-                HIP_TRY(hipEventRecord(w.events[ev++], stream));
-                qi ^= 1;
-                ty.iterations++;
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(w.h_ctr, w.d_ctr, sizeof(WfCounters), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            for (size_t e = 0; e + 3 < ev; e += 4) {
-                float it_ms[3];
-                for (int ph = 0; ph < 3; ph++) {
-                    it_ms[ph] = 0.f;
-                    HIP_TRY(hipEventElapsedTime(&it_ms[ph], w.events[e + ph], w.events[e + ph + 1]));
-                    if (ph == 0 && (su.split || su.prims_only) && !prims_ran[e / 4]) it_ms[ph] = 0.f;  // no launch between the two events
-                    ty.phase_ms[ph] += it_ms[ph];
-                }
-                if (iter_log)  // RT_WF_ITER_LOG=1 (with RT_WF_CHECK=1 the queue length printed is the one of this very iteration)
-                    std::fprintf(stderr, "[wf iter] group %u: <= %u paths queued: prims %.3f ms, traversal %.3f ms, shade %.3f ms\n", ty.n_groups, upper,
-                                 it_ms[0], it_ms[1], it_ms[2]);
-            }
-            if (trace_pool)
-                if (int st = wf_trace_dump(pool, first, queue[qi], w.h_ctr->n_in, ty.iterations)) return st;
-            upper = w.h_ctr->n_in;
-            // every sample of the call's last group has been started and slots are running empty: from here on this render
-            // cannot fill the GPU any more, the next frame's render (another RtScene, another stream) may start underneath it
-            if (s->tail_flag && t0 + nrep >= t_end && upper < first) __atomic_store_n(s->tail_flag, 1, __ATOMIC_RELEASE);
-            if (upper == 0) break;
-            // ---- tail compaction (rt_wavefront.h k_wf_compact): fewer than half of the addressed slots are alive and none will
-            //      restart: the live paths move to slots 0 .. upper-1 of the other pool, which becomes the pool ----
-            if (compact_tail && w.h_ctr->next_sample >= grp.total && upper >= compact_min && uint64_t(upper) * 100 <= uint64_t(pool.capacity) * compact_pct) {
-                WfPool<R> dst = on_b ? pool_a : pool_b;
-                hipLaunchKernelGGL((k_wf_compact<R>), dim3((upper + 255) / 256), dim3(256), 0, stream, pool, dst, queue[qi], upper);
-                on_b = !on_b;
-                pool = dst;
-                pool.capacity = upper;  // n_in == capacity: the kernels address slot i for entry i again
-                pool_dev_cur = pools[on_b ? 1 : 0].dev;
-                ty.n_compactions++;
-                if (hits_ready) {  // the hit records stayed behind and the mesh queue names the old slots: stand-alone k_wf_prims next
-                    HIP_TRY(hipMemsetAsync(&w.d_ctr->n_mesh, 0, sizeof(uint32_t), stream));
-                    hits_ready = false;
-                }
-            }
-        }
-        if (ad) {
-            const dim3 rgrid(uint32_t((npix + 255) / 256));
-            if (sparse) hipLaunchKernelGGL(k_wf_resolve_moments<true>, rgrid, dim3(256), 0, stream, w.sample_L.get(), npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
-            else hipLaunchKernelGGL(k_wf_resolve_moments<false>, rgrid, dim3(256), 0, stream, w.sample_L.get(), npix, strata, nrep, pv.spp, double(T), ad->active, d_out, ad->s1, ad->s2, ad->cnt);
-        } else {
-            if (lg) HIP_TRY(hipEventRecord(w.ev_res[0], stream));
-            if (d_out)
-                hipLaunchKernelGGL(k_wf_resolve, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, w.sample_L.get(), w.acc.get(), npix, strata, nrep,
-                                   pv.spp, int(t0 == t_first), int(t_first > 0), d_out, int(t0 + nrep >= t_end));
-            if (lg) {
-                const uint64_t blocks = ((npix + 63) / 64) * ((lg->n_groups + 3u) / 4u);
-                if (blocks > 0x7FFFFFFFull) return set_err(RT_E_UNSUPPORTED, "frame too large for the light-group resolve");
-                hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, stream, w.sample_L.get(), w.sample_G.get(), w.acc_g.get(), npix,
-                                   lg->n_groups, strata, nrep, pv.spp, int(t0 == t_first), lg->d_groups_out, int(t0 + nrep >= t_end));
-                HIP_TRY(hipEventRecord(w.ev_res[1], stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                float ms = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms, w.ev_res[0], w.ev_res[1]));
-                ty.resolve_ms += ms;
-            }
-        }
+        if (int st = wf_run_group(s, ds, run, grp, shade, fuse, cv, pv, last_group, stream, ty)) return st;
+        if (int st = pass.resolve(WfResolve{s->wf, npix, strata, nrep, p.thread_count, pv.spp, d_out, int(t0 == t_first), int(t_first > 0), int(last_group), stream})) return st;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, stream));
@@ -1483,7 +1515,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         for (int k = 0; k < 7; k++) std::fprintf(stderr, "  %-40s %10.0f clk per wave-trip\n", names[k], double(h[k]) / trips);
     }
 #endif
-    return wf_fill_stats(s, su, ty, lg, fusable, npix * strata * n);
+    return wf_fill_stats(s, run.su, ty, fusable, npix * strata * n);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1735,7 +1767,7 @@ int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* 
         rp.origins = static_cast<const double*>(d_in[0]);
         rp.dirs = static_cast<const double*>(d_in[1]);
         rp.first = off;
-        return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, nullptr, nullptr, &rp);
+        return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, rp);
     };
     return render_table_chunks(s, s->rays.stage, n, {{origins, 24}, {dirs, 24}}, out, host, stream, render);
 }
@@ -1761,7 +1793,7 @@ int bake_irradiance_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const doub
             pp.nrm = static_cast<const unsigned char*>(d_in[1]);
             pp.stride = 24u;
         }
-        if (int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, nullptr, nullptr, nullptr, &pp)) return st;
+        if (int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, pp)) return st;
         if (hits) {
             hipLaunchKernelGGL(k_wf_points_mask, dim3((m + 255) / 256), dim3(256), 0, stream,
                                reinterpret_cast<const unsigned char*>(hits + off) + offsetof(RtRayHit, flags), uint32_t(sizeof(RtRayHit)), m, d_out);
@@ -2204,11 +2236,12 @@ static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, 
     if (ad) {  // adaptive passes exist in the wavefront scheduler only
         if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "adaptive passes run the wavefront scheduler: RT_PIPELINE_MEGAKERNEL is not supported");
         if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, "adaptive sampling with max_depth = 0");
-        if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, "adaptive passes have no counting kernels (collect_stats)");
-        wavefront = true;
+        wavefront = true;  // collect_stats: refused by the mode
     }
     return with_tables(s, params->precision, [&](auto& ds) -> int {
-        if (wavefront) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, ad);
+        if (ad && ad->sparse) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, AdaptiveMode<true>{*ad});
+        if (ad) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, AdaptiveMode<false>{*ad});
+        if (wavefront) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, FramePass{});
         return render_typed(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st);
     });
 }
@@ -3288,7 +3321,7 @@ static int light_groups_impl(const RtScene* scene, const RtCameraDesc* camera, c
     lg.d_groups_out = d_groups_out;
     hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
     const uint32_t T = params->thread_count;
-    return with_tables(s, params->precision, [&](auto& ds) { return render_wavefront(s, ds, *camera, *params, owned, 0, T, d_rgba_out, st, nullptr, &lg); });
+    return with_tables(s, params->precision, [&](auto& ds) { return render_wavefront(s, ds, *camera, *params, owned, 0, T, d_rgba_out, st, lg); });
 }
 
 int rt_render_light_groups_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, const RtLightGroups* groups,

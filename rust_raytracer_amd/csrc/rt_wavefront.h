@@ -78,6 +78,7 @@ struct WfGroup {
     double inv_per_replica, inv_npix, inv_width;  // reciprocals rounded to nearest: quotient ESTIMATES, made exact in div_by
     uint32_t tid0;         // first replica of the group
     uint32_t strata;       // S*S
+    // what a derived group adds (each sets its own flag): wf_new_sample and k_wf_shade branch on these at compile time
     static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = false;
     static constexpr bool kRays = false;
@@ -93,9 +94,6 @@ template <typename R>
 struct WfGroupSparse : WfGroup<R> {
     const uint32_t* active;
     static constexpr bool kSparse = true;
-    static constexpr bool kLightGroups = false;
-    static constexpr bool kRays = false;
-    static constexpr bool kPoints = false;
 };
 
 // Replica group of a light-group render (include/rt_mi355.h): k_wf_shade also stores the group of every
@@ -108,10 +106,7 @@ struct WfGroupLG : WfGroup<R> {
     uint8_t* sample_G;
     const uint8_t* table;
     uint32_t n_materials;
-    static constexpr bool kSparse = false;
     static constexpr bool kLightGroups = true;
-    static constexpr bool kRays = false;
-    static constexpr bool kPoints = false;
 };
 
 // Replica group of a render along a ray table (rt_render_rays): "pixel" i of the group is ray i of a chunk
@@ -124,10 +119,7 @@ struct WfGroupRays : WfGroup<R> {
     const double* origins;
     const double* dirs;
     uint64_t first;
-    static constexpr bool kSparse = false;
-    static constexpr bool kLightGroups = false;
     static constexpr bool kRays = true;
-    static constexpr bool kPoints = false;
 };
 
 // Replica group of an irradiance bake (rt_bake_irradiance): "pixel" i of the group is surface point i of a
@@ -141,9 +133,6 @@ struct WfGroupPoints : WfGroup<R> {
     const unsigned char* nrm;
     uint64_t first;
     uint32_t stride;
-    static constexpr bool kSparse = false;
-    static constexpr bool kLightGroups = false;
-    static constexpr bool kRays = false;
     static constexpr bool kPoints = true;
 };
 
