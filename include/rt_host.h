@@ -27,7 +27,8 @@ typedef struct RtHost RtHost;
  * --precision=f64|f32, --pipeline=auto|mega|wavefront, --bvh=host|device, --progressive=<n>,
  * --checkpoint=<file>, --time-limit=<seconds>, --denoise=<iterations>, --noise-threshold=<x>,
  * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>, --light-groups[=<max>],
- * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>], --irradiance
+ * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>], --irradiance,
+ * --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]
  * (unknown keys are ignored by the reference, config.rs:146, so these
  * are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
@@ -83,6 +84,12 @@ uint32_t rth_ao(const RtHost* host, double* max_distance_out);
  * --pick, --ao or --probe; rtrace refuses a scene with volumes (the ray queries have none) and --sequence before it renders
  * anything.  rth_irradiance returns 1 with the flag, 0 without.                                                              */
 int rth_irradiance(const RtHost* host);
+/* SH radiance probes (rt_bake_probes): --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...] (finite positions): rtrace renders nothing and
+ * prints the nine RGB coefficients of every probe, baked with the run's -s, -t, depth, bias, seed and precision, the way --pick
+ * prints its hits.  rth_load rejects malformed values, and --sh-probe with --gpus > 1, --progressive, --noise-threshold, --pick,
+ * --ao, --probe, --irradiance or --pipeline=mega; rtrace refuses --sequence and a depth of 0 before a device is touched.
+ * rth_sh_probes returns the number of probes and writes up to `capacity` positions (3 doubles each; positions_out may be NULL). */
+uint32_t rth_sh_probes(const RtHost* host, double* positions_out, uint32_t capacity);
 /* Light probe (rt_render_rays): --probe=<x>,<y>,<z>[:<width>] (a finite position; width 2 .. 65536, default 512; the height
  * is width / 2): rtrace renders the equirectangular panorama of rth_probe_rays at that point with the run's -s, -t, depth,
  * bias, seed and precision and writes out_probe.png INSTEAD of the frame.  No pixel filter: every sample of a texel goes along

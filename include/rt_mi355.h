@@ -741,6 +741,56 @@ int rt_bake_irradiance_device(const RtScene* scene, uint64_t n, const double* d_
 int rt_bake_irradiance_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtRenderParams* params,
                                    double* d_rgba_out, void* stream);
 
+/* ---- SH radiance probes ---------------------------------------------------------------------------
+ * Irradiance volumes for what is not a surface of the scene - moving objects, particles, volumetric effects: the full path
+ * tracer - materials, the light-biased mixture sampler, volumes, every texture - started from n positions in free space in
+ * directions uniform over the sphere, and projected onto the nine real spherical harmonics of bands 0-2 on the device.
+ * One fused pass: the directions are formed in registers, 24 B in and 288 B out per PROBE, no ray table, nothing stored per path.
+ * positions: n x 3 doubles.  sh_out: n x 9 x 4 doubles, (r, g, b, 0) per coefficient.
+ * Of `params`: sqrt_spt (S), thread_count (T), max_depth, has_background / background, light_bias, seed and precision are used;
+ * R = double or float by the precision.  For probe i (its index in the whole call), replica t < T, stratum st = sy S + sx:
+ *     Rng g keyed (seed, t, i, st) as a render keys (seed, replica, pixel, stratum);
+ *     r1, r2 = the generator's first two uniforms - the two draws a camera spends on its jitter;
+ *     u1 = (R(sx) + r1) * inv_S,  u2 = (R(sy) + r2) * inv_S              (inv_S = R(1.0 / double(S)), exactly as rt_bake_irradiance forms them)
+ *     z = 1 - 2 u2,  r = sqrt(1 - z z),  phi = u1 * 2 * pi,  d = (cos(phi) r, sin(phi) r, z)       (the uniform sphere; sine and cosine
+ *         from the project's deterministic sincos; no contraction; 1 - z z cannot go negative in either format, so no clamp)
+ *     o = R(pos_i),  d' = (o + d) - o     (two roundings per component: what the reference's camera returns for position = o,
+ *                                          first_pixel = o + d, pixel deltas 0, no aperture)
+ *     the path starts at (o, d') with max_depth, on g as it now stands, with the path's usual t_min = 0.001; L is its radiance.
+ *     Y_0 .. Y_8 = the real L2 basis evaluated on d (NOT on d'), in R, positive signs (no Condon-Shortley phase), the constants
+ *     f64 literals rounded to R, (x, y, z) = d:
+ *         Y0 = 0.28209479177387814
+ *         Y1 = 0.4886025119029199 y             Y2 = 0.4886025119029199 z             Y3 = 0.4886025119029199 x
+ *         Y4 = 1.0925484305920792 (x y)         Y5 = 1.0925484305920792 (y z)         Y6 = 0.31539156525252005 (3 (z z) - 1)
+ *         Y7 = 1.0925484305920792 (x z)         Y8 = 0.5462742152960396 (x x - y y)
+ * out[i][k] is the ordered sum a frame's pixel is: per replica the strata in order of double(Y_k) * L, each product rounded before
+ * it is added, / (S^2 T), then the replicas in order; f64, no atomics.  No factor is applied on the device: out is the mean of
+ * L Y_k over the sphere's samples, and the radiance coefficients are 4 pi * out.  Hence, in f64, sample (t, i, st) is the
+ * reference's sample (t, pixel i, st) with that camera, and out[i] does not depend on n, the chunk size, the pool size, replica
+ * grouping or tail compaction.
+ * Rules, stats and the tail flag: rt_bake_irradiance's.  n = 0 is a no-op.  RT_E_INVALID with a message naming the field: a NULL
+ * array, n >= 2^31, n_parts > 1, a bad precision, sqrt_spt or thread_count of 0.  RT_E_UNSUPPORTED: RT_PIPELINE_MEGAKERNEL,
+ * collect_stats, max_depth = 0.  Everything is checked before the device is touched; on any error the output is untouched.
+ * A scene with volumes is supported.  rt_get_stats: samples = n T S^2.  Synchronous; must not overlap a render or an update of
+ * the same scene; sees the scene as rt_scene_update left it.  Probes run in chunks of RT_RAYS_CHUNK, like rays.             */
+int rt_bake_probes(const RtScene* scene, uint64_t n, const double* positions, const RtRenderParams* params, double* sh_out);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_bake_probes_device(const RtScene* scene, uint64_t n, const double* d_positions, const RtRenderParams* params, double* d_sh_out,
+                          void* stream);
+/* Lighting from probes: m queries; query j names probe[j] < n_probes of `sh` (n_probes x 9 x 4 doubles, rt_bake_probes's layout)
+ * and a normal (m x 3 doubles, need not be unit length).  With w the unit normal (n / sqrt(x x + y y + z z)) and a_k = sh[probe[j]][k]:
+ *     out[j] = 4 pi * ((a_0 Y0 + (2/3) * (a_1 Y1(w) + a_2 Y2(w) + a_3 Y3(w))) + (1/4) * (a_4 Y4(w) + ... + a_8 Y8(w)))
+ * per channel, every sum left to right, f64 throughout (2/3 = 2.0 / 3.0), the fourth value 0: the clamped-cosine convolution of
+ * the probe's radiance divided by pi - the unit of rt_bake_irradiance's output, so irradiance = pi * out.  rgba_out: m x 4 doubles.
+ * m = 0 is a no-op.  RT_E_INVALID: a NULL array, m or n_probes >= 2^31, and - host variant only, checked before the device is
+ * touched - an index out of range; the device variant gives (0, 0, 0, 0) for such a query.  No scene is needed: `device` is
+ * the HIP device to run on.                                                                                                */
+int rt_sh_irradiance(int device, const double* sh, uint64_t n_probes, const uint32_t* probe, const double* normals, uint64_t m,
+                     double* rgba_out);
+/* Device pointers on `device`; returns after the kernel completes. */
+int rt_sh_irradiance_device(int device, const double* d_sh, uint64_t n_probes, const uint32_t* d_probe, const double* d_normals, uint64_t m,
+                            double* d_rgba_out, void* stream);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

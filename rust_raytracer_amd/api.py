@@ -255,6 +255,8 @@ def load_host_lib() -> C.CDLL:
         lib.rth_ao.restype = C.c_uint32
         lib.rth_irradiance.argtypes = [C.c_void_p]
         lib.rth_irradiance.restype = C.c_int
+        lib.rth_sh_probes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.rth_sh_probes.restype = C.c_uint32
         lib.rth_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.rth_probe.restype = C.c_uint32
         lib.rth_probe_rays.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -440,6 +442,15 @@ def load_device_lib() -> C.CDLL:
             lib.rt_bake_irradiance_device.restype = C.c_int
             lib.rt_bake_irradiance_hits_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p, C.c_void_p]
             lib.rt_bake_irradiance_hits_device.restype = C.c_int
+        if hasattr(lib, "rt_bake_probes"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_bake_probes.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p]
+            lib.rt_bake_probes.restype = C.c_int
+            lib.rt_bake_probes_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(RtRenderParams), C.c_void_p, C.c_void_p]
+            lib.rt_bake_probes_device.restype = C.c_int
+            lib.rt_sh_irradiance.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+            lib.rt_sh_irradiance.restype = C.c_int
+            lib.rt_sh_irradiance_device.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+            lib.rt_sh_irradiance_device.restype = C.c_int
         if hasattr(lib, "rt_debug_live_resources"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
             lib.rt_debug_live_resources.restype = C.c_int
@@ -650,6 +661,53 @@ def light_mix(groups: np.ndarray, tints, device: int = 0) -> np.ndarray:
     return out
 
 
+def probe_grid(lo, hi, counts) -> np.ndarray:
+    """Cell-centred positions of an irradiance volume: the box lo .. hi cut into counts = (nx, ny, nz) cells, x fastest; position
+    (ix, iy, iz) = lo + (hi - lo) * ((i + 0.5) / counts) per axis, at index (iz * ny + iy) * nx + ix.  (nx * ny * nz, 3) float64."""
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    counts = np.asarray(counts)
+    if lo.shape != (3,) or hi.shape != (3,) or counts.shape != (3,) or counts.dtype.kind not in "iu" or (counts < 1).any():
+        raise ValueError("probe_grid: lo and hi must be (3,), counts three positive integers")
+    axes = [lo[a] + (hi[a] - lo[a]) * ((np.arange(int(counts[a]), dtype=np.float64) + 0.5) / float(counts[a])) for a in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x, y, z], axis=-1).reshape(-1, 3))
+
+
+def sh_irradiance(sh, probe, normals, device: int = 0) -> np.ndarray:
+    """rt_sh_irradiance: lighting from SH probes.  sh: (n, 9, 4) from DeviceScene.bake_probes; probe: (m,) indices below n (or one
+    index); normals: (m, 3) or (3,), need not be unit length.  Returns (m, 4) float64, (r, g, b, 0): the clamped-cosine
+    convolution of the probe's radiance divided by pi - the unit of bake_irradiance, irradiance = pi * out."""
+    lib = load_device_lib()
+    sh = np.ascontiguousarray(sh, dtype=np.float64)
+    if sh.ndim != 3 or sh.shape[1:] != (9, 4):
+        raise ValueError(f"sh_irradiance: expected an (n, 9, 4) array, got {sh.shape}")
+    idx = np.asarray(probe)
+    if idx.dtype.kind not in "iu" or ((idx < 0) | (idx > 0xFFFFFFFF)).any():
+        raise ValueError("sh_irradiance: probe indices must be integers in 0 .. 2^32 - 1")
+    nr = np.asarray(normals, dtype=np.float64)
+    if nr.shape[-1:] != (3,) or nr.ndim > 2 or idx.ndim > 1:
+        raise ValueError("sh_irradiance: probe must be (m,) or a single index, normals (m, 3) or (3,)")
+    m = max(idx.size if idx.ndim else 1, len(nr) if nr.ndim == 2 else 1)
+    idx = np.ascontiguousarray(np.broadcast_to(idx.astype(np.uint32), (m,)))
+    nr = np.ascontiguousarray(np.broadcast_to(nr, (m, 3)))
+    out = np.empty((m, 4), dtype=np.float64)
+    st = lib.rt_sh_irradiance(device, sh.ctypes.data, len(sh), idx.ctypes.data, nr.ctypes.data, m, out.ctypes.data)
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+    return out
+
+
+def sh_irradiance_device(d_sh_ptr: int, n_probes: int, d_probe_ptr: int, d_normals_ptr: int, m: int, d_out_ptr: int, device: int = 0,
+                         stream: int = 0) -> None:
+    """rt_sh_irradiance_device: n_probes x 9 x 4 doubles, m uint32 indices and m x 3 doubles in HBM -> m x 4 doubles in HBM; an index
+    out of range gives (0, 0, 0, 0)."""
+    lib = load_device_lib()
+    st = lib.rt_sh_irradiance_device(device, C.c_void_p(d_sh_ptr or None), n_probes, C.c_void_p(d_probe_ptr or None), C.c_void_p(d_normals_ptr or None),
+                                     m, C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+    if st != RT_OK:
+        raise RtError(st, lib.rt_last_error().decode())
+
+
 def owned_rows(height: int, params: RtRenderParams) -> list:
     """Rows of the frame that the partition in `params` assigns to this part (rt_owned_rows)."""
     if params.band_rows == 0 or params.n_parts <= 1:
@@ -687,6 +745,8 @@ class HostScene:
         dist = C.c_double()
         self.ao = (int(lib.rth_ao(handle, C.byref(dist))), dist.value)  # --ao=<samples>[:<max_distance>]: (0, inf) without the flag
         self.irradiance = bool(lib.rth_irradiance(handle))  # --irradiance: also bake out_irradiance.png
+        self.sh_probes = np.zeros((lib.rth_sh_probes(handle, None, 0), 3))  # --sh-probe=<x>,<y>,<z>[:...]: (n, 3) positions to bake instead of rendering
+        lib.rth_sh_probes(handle, self.sh_probes.ctypes.data, len(self.sh_probes))
         pos = (C.c_double * 3)()
         width = int(lib.rth_probe(handle, pos))
         self.probe = (width, tuple(pos)) if width else None  # --probe=<x>,<y>,<z>[:<width>]: (width, position), None without the flag
@@ -992,6 +1052,29 @@ class DeviceScene:
         environment hit gives (0, 0, 0, 0)."""
         st = self._lib.rt_bake_irradiance_hits_device(self._h, n, C.c_void_p(d_hits_ptr or None), C.byref(params),
                                                       C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+
+    def bake_probes(self, positions, params: RtRenderParams) -> np.ndarray:
+        """rt_bake_probes: SH radiance probes at positions in free space as (n, 9, 4) float64, (r, g, b, 0) per coefficient of
+        the real L2 basis: the mean of L * Y_k over S^2 x T paths of the full path tracer per probe, their first directions
+        uniform over the sphere and drawn on the device (sqrt_spt, thread_count, max_depth, background, light_bias, seed and
+        precision of `params`).  The radiance coefficients are 4 pi * out; api.sh_irradiance lights a normal from them.
+        positions: (n, 3) or (3,)."""
+        p = np.asarray(positions, dtype=np.float64)
+        if p.shape[-1:] != (3,) or p.ndim > 2:
+            raise ValueError("positions must be (n, 3) or (3,)")
+        p = np.ascontiguousarray(np.atleast_2d(p))
+        out = np.empty((len(p), 9, 4), dtype=np.float64)
+        st = self._lib.rt_bake_probes(self._h, len(p), p.ctypes.data, C.byref(params), out.ctypes.data)
+        if st != RT_OK:
+            raise RtError(st, self._lib.rt_last_error().decode())
+        return out
+
+    def bake_probes_device(self, n: int, d_positions_ptr: int, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
+        """rt_bake_probes_device: n x 3 doubles in HBM -> n x 9 x 4 doubles in HBM."""
+        st = self._lib.rt_bake_probes_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.byref(params), C.c_void_p(d_out_ptr or None),
+                                             C.c_void_p(stream))
         if st != RT_OK:
             raise RtError(st, self._lib.rt_last_error().decode())
 

@@ -275,6 +275,21 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
             cfg.has_probe = true;
             for (int a = 0; a < 3; a++) cfg.probe_position[a] = v3[a];
             cfg.probe_width = uint32_t(width);
+        } else if (key == "-sh-probe") {  // new: SH radiance probes at points (rt_bake_probes) instead of a render
+            cfg.sh_probes.clear();
+            size_t pos = 0;
+            for (;;) {
+                const size_t colon = value.find(':', pos);
+                std::string ignored;
+                if (!parse_vec3(value.substr(pos, colon == std::string::npos ? std::string::npos : colon - pos), v3, &ignored) ||
+                    !std::isfinite(v3[0]) || !std::isfinite(v3[1]) || !std::isfinite(v3[2])) {
+                    *err = "SH probes must be a list of positions <x>,<y>,<z>[:<x>,<y>,<z>...] (finite numbers)";
+                    return false;
+                }
+                cfg.sh_probes.insert(cfg.sh_probes.end(), v3, v3 + 3);
+                if (colon == std::string::npos) break;
+                pos = colon + 1;
+            }
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -327,6 +342,12 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
     if (cfg.irradiance && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.has_probe)) {
         *err = "--irradiance bakes the whole frame on one GPU after a one-shot render: it cannot be combined with --gpus > 1, --progressive, "
                "--noise-threshold, --pick, --ao or --probe";
+        return false;
+    }
+    if (!cfg.sh_probes.empty() && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.has_probe || cfg.irradiance ||
+                                   cfg.pipeline == RT_PIPELINE_MEGAKERNEL)) {
+        *err = "--sh-probe bakes probes on one GPU with the wavefront scheduler instead of the frame: it cannot be combined with --gpus > 1, "
+               "--progressive, --noise-threshold, --pick, --ao, --probe, --irradiance or --pipeline=mega";
         return false;
     }
     if (cfg.has_probe && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.light_groups || cfg.denoise ||

@@ -102,6 +102,14 @@ uint32_t rth_ao(const RtHost* host, double* max_distance_out) {
     return host->config.ao_samples;
 }
 int rth_irradiance(const RtHost* host) { return host->config.irradiance ? 1 : 0; }
+uint32_t rth_sh_probes(const RtHost* host, double* positions_out, uint32_t capacity) {
+    const auto& p = host->config.sh_probes;
+    const uint32_t n = uint32_t(p.size() / 3);
+    if (positions_out)
+        for (uint32_t i = 0; i < n && i < capacity; i++)
+            for (int a = 0; a < 3; a++) positions_out[3 * size_t(i) + a] = p[3 * size_t(i) + a];
+    return n;
+}
 uint32_t rth_probe(const RtHost* host, double position_out[3]) {
     if (!host->config.has_probe) return 0;
     if (position_out)

@@ -8,7 +8,9 @@
 //   --progressive=<n>  --checkpoint=<file>  --time-limit=<seconds>  --denoise=<iterations>
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 //   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
-//   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]  --irradiance
+//   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]  --irradiance  --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]
+// --sh-probe=<x>,<y>,<z>[:...] renders nothing: an SH radiance probe is baked at each named position (rt_bake_probes) with the
+// run's -s, -t, depth, bias, seed and precision and its nine RGB coefficients are printed, one line per coefficient.
 // --irradiance also writes out_irradiance.png: the --pick ray of every pixel is cast on the device (rt_trace_rays_device) and the
 // cosine-weighted mean of the radiance arriving at every first hit is baked with the run's -s, -t, depth, bias, seed and
 // precision (rt_bake_irradiance_hits_device; the hit records never leave the device) and written through the output stage of
@@ -239,6 +241,30 @@ static int pick_pixels(RtHost* host) {
     return 0;
 }
 
+// --sh-probe: the nine RGB coefficients of the SH probe at each named position, one line each; returns the process exit status.
+static int bake_sh_probes(RtHost* host) {
+    const uint32_t n = rth_sh_probes(host, nullptr, 0);
+    std::vector<double> pos(3 * size_t(n)), sh(36 * size_t(n));
+    rth_sh_probes(host, pos.data(), n);
+    RtRenderParams p = *rth_params(host);  // S, T, depth, background, bias, seed, precision of the run; a bake has one scheduler and no partition
+    p.pipeline = RT_PIPELINE_AUTO;
+    p.collect_stats = 0;
+    p.band_rows = p.n_parts = p.part = 0;
+    RtScene* scene = nullptr;
+    if (rt_scene_create(rth_scene(host), 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    if (rt_bake_probes(scene, n, pos.data(), &p, sh.data()) != RT_OK) return fail(rt_last_error());
+    for (uint32_t i = 0; i < n; i++) {
+        std::printf("SH probe %u at %.17g %.17g %.17g: %u paths\n", i, pos[3 * size_t(i)], pos[3 * size_t(i) + 1], pos[3 * size_t(i) + 2],
+                    p.sqrt_spt * p.sqrt_spt * p.thread_count);
+        for (uint32_t k = 0; k < 9; k++) {
+            const double* c = &sh[36 * size_t(i) + 4 * k];
+            std::printf("SH probe %u coefficient %u: %.17g %.17g %.17g\n", i, k, c[0], c[1], c[2]);
+        }
+    }
+    return 0;
+}
+
 // --probe: the panorama at the named point to out_probe.png; returns the process exit status.
 static int render_probe(RtHost* host, const std::function<double()>& since) {
     double position[3];
@@ -379,6 +405,10 @@ int main(int argc, char** argv) {
                 params->thread_count, spp / params->thread_count);  // main.rs:68-71
     std::fflush(stdout);
 
+    if (rth_sh_probes(host, nullptr, 0) != 0) {  // refused BEFORE a device is touched
+        if (!sequence.empty()) return fail("--sh-probe bakes probes instead of the frame: it cannot be combined with --sequence");
+        if (params->max_depth == 0) return fail("--sh-probe needs a depth of at least 1");
+    }
     uint32_t gpus = rth_gpus(host);
     int available = rt_device_count();
     if (available < 1) {
@@ -387,6 +417,11 @@ int main(int argc, char** argv) {
     }
     if (rth_pick(host, nullptr, 0) != 0) {
         const int rc = pick_pixels(host);
+        rth_destroy(host);
+        return rc;
+    }
+    if (rth_sh_probes(host, nullptr, 0) != 0) {
+        const int rc = bake_sh_probes(host);
         rth_destroy(host);
         return rc;
     }

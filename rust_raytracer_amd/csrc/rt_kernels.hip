@@ -684,7 +684,7 @@ struct RtScene {
         rt::ChunkStage stage;
         RtRayQueryStats stats{};
     } bake;
-    // renders along ray tables and irradiance bakes (rt_render_rays, rt_bake_irradiance): the host variants' staging buffer; the kernels run on the render's workspace (wf)
+    // renders along ray tables, irradiance and probe bakes (rt_render_rays, rt_bake_irradiance, rt_bake_probes): the host variants' staging buffer; the kernels run on the render's workspace (wf)
     struct Rays {
         rt::ChunkStage stage;
     } rays;
@@ -837,7 +837,7 @@ MeshKernel<R> pick_mesh(bool stats, int node_kind, bool multi, bool slabs) {
 
 // k_wf_shade of a group type G.  Every G has the lean variants (interpreter variant: tables from global memory - rare scenes,
 // fewer instantiations).  The fused kernel (+ k_wf_prims' search as phase 4) exists for the groups whose restarts leave it the
-// registers: WfGroup, WfGroupRays, WfGroupPoints.  The counting variants exist for WfGroup alone; a caller whose G has none
+// registers: WfGroup, WfGroupRays, WfGroupPoints, WfGroupProbes.  The counting variants exist for WfGroup alone; a caller whose G has none
 // refuses collect_stats before it comes here.
 template <typename G> constexpr bool kShadeFused = !G::kSparse && !G::kLightGroups;
 template <typename R, typename G, bool ST>
@@ -1054,7 +1054,7 @@ int wf_ensure(RtScene* s, uint32_t capacity) {
 }
 
 // ---- Render modes.  A call of render_wavefront has exactly one: a plain frame, a dense or a sparse adaptive pass, a light-group
-// render, a ray table or a point table.  The mode type says what the driver must not know: its replica-group type Group<R>
+// render, a ray table, a point table or a probe table.  The mode type says what the driver must not know: its replica-group type Group<R>
 // (k_wf_generate and k_wf_shade are instantiated per group type) and how one is completed from the common base the driver
 // fills (`complete`); how many pixels a group covers (`npix`); the refusal collect_stats meets (`kNoCounting`; null: the mode
 // has counting kernels); whether every sample has an origin of its own (`kOwnOrigins`); what a sample takes in device memory
@@ -1065,7 +1065,7 @@ int wf_ensure(RtScene* s, uint32_t capacity) {
 struct WfResolve {
     RtScene::Wavefront& w;
     uint64_t npix;
-    uint32_t strata, nrep, T;
+    uint32_t strata, nrep, T, tid0;  // tid0: the group's first replica
     double spp, *d_out;
     int first, resumed, last;
     hipStream_t stream;
@@ -1176,6 +1176,49 @@ struct PointTablePass : PassBase {
     static constexpr const char* kNoCounting = "point tables have no adaptive, light-group or counting kernels (collect_stats)";
     static constexpr bool kOwnOrigins = true;
     template <typename G> void complete(G& g, RtScene::Wavefront&) const { g.pos = pos; g.nrm = nrm; g.stride = stride; g.first = first; }
+};
+
+// An SH probe bake (rt_bake_probes): one chunk of the caller's positions.  The "frame" is n x 1 pixels,
+// pixel i = probe first + i; pos is a device pointer to the chunk's first position.  The resolve weights every sample by the SH
+// basis of its first direction, re-derived from the sample's key (k_wf_resolve_sh): d_out is n x 9 x 4 doubles, and several
+// replica groups carry 27 doubles per probe in w.acc instead of a pixel's 3.
+struct ProbeTablePass : PassBase {
+    const double* pos = nullptr;
+    uint64_t first = 0;
+    uint64_t seed = 0;
+    uint32_t S = 1;
+    bool f32 = false;
+    template <typename R> using Group = WfGroupProbes<R>;
+    static constexpr const char* kNoCounting = "probe tables have no adaptive, light-group or counting kernels (collect_stats)";
+    static constexpr bool kOwnOrigins = true, kRunningSums = false;  // the sums between groups are this mode's own size
+    int reserve(RtScene::Wavefront& w, uint64_t, uint64_t npix, uint32_t group, uint32_t n, hipStream_t) const {
+        return w.acc.reserve(group < n ? size_t(npix) * 27 * sizeof(double) : size_t(0));
+    }
+    template <typename G> void complete(G& g, RtScene::Wavefront&) const { g.pos = pos; g.first = first; }
+    template <typename R> void launch_resolve(const WfResolve& a, uint32_t tid0) const {
+        hipLaunchKernelGGL((k_wf_resolve_sh<R>), dim3(uint32_t(((a.npix + 63) / 64) * 3u)), dim3(256), 0, a.stream, a.w.sample_L.get(), a.w.acc.get(), a.npix, first,
+                           seed, tid0, S, R(1.0 / double(S)), a.nrep, a.spp, a.first, a.d_out, a.last);
+    }
+    mutable double resolve_ms = 0;  // k_wf_resolve_sh, summed over the chunk's groups (RT_PROBES_LOG)
+    int resolve(const WfResolve& a) const {
+        const bool log = env_u32("RT_PROBES_LOG", 0) != 0;  // tools/gpu_bake_probes_cost.py: times the resolve with events, at the price of a synchronise per group
+        if (log) {
+            for (Event& e : a.w.ev_res)
+                if (int st = e.ensure()) return st;
+            HIP_TRY(hipEventRecord(a.w.ev_res[0], a.stream));
+        }
+        if (f32) launch_resolve<float>(a, a.tid0);
+        else launch_resolve<double>(a, a.tid0);
+        if (log) {
+            HIP_TRY(hipEventRecord(a.w.ev_res[1], a.stream));
+            HIP_TRY(hipStreamSynchronize(a.stream));
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, a.w.ev_res[0], a.w.ev_res[1]));
+            resolve_ms += ms;
+            if (a.last) std::fprintf(stderr, "[probes] %llu probes from %llu on, %u paths each: k_wf_resolve_sh %.3f ms\n", (unsigned long long)a.npix, (unsigned long long)first, a.strata * a.T, resolve_ms);
+        }
+        return RT_OK;
+    }
 };
 
 // Pool size of a render.  Every launch of the persistent mesh kernel ends with a drain of ~0.4 ms (the longest remaining traversals:
@@ -1366,8 +1409,10 @@ int wf_prepare(RtScene* s, DeviceScene<R>& ds, const RtRenderParams& p, uint64_t
     // (profiles/wavefront_modes/README.md); WfRun::shade, not pick_shade itself, is what the driver calls for the same reason.
     (void)&pick_shade<R, WfGroup<R>>, (void)&pick_shade<R, WfGroupSparse<R>>, (void)&pick_shade<R, WfGroupLG<R>>;
     (void)&pick_shade<R, WfGroupRays<R>>, (void)&pick_shade<R, WfGroupPoints<R>>;
+    (void)&pick_shade<R, WfGroupProbes<R>>;
     (void)&k_wf_generate<R, WfGroupPoints<R>>, (void)&k_wf_generate<R, WfGroupRays<R>>, (void)&k_wf_generate<R, WfGroupSparse<R>>, (void)&k_wf_generate<R, WfGroup<R>>;
     (void)&k_wf_compact<R>, (void)&k_wf_resolve_moments<true>, (void)&k_wf_resolve_moments<false>;
+    (void)&k_wf_generate<R, WfGroupProbes<R>>, (void)&k_wf_resolve_sh<R>;
     return RT_OK;
 }
 
@@ -1499,7 +1544,7 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
         pass.complete(grp, s->wf);
         if (grp.total >= (1ull << 51)) return set_err(RT_E_UNSUPPORTED, "more than 2^51 samples in one replica group");
         if (int st = wf_run_group(s, ds, run, grp, shade, fuse, cv, pv, last_group, stream, ty)) return st;
-        if (int st = pass.resolve(WfResolve{s->wf, npix, strata, nrep, p.thread_count, pv.spp, d_out, int(t0 == t_first), int(t_first > 0), int(last_group), stream})) return st;
+        if (int st = pass.resolve(WfResolve{s->wf, npix, strata, nrep, p.thread_count, t0, pv.spp, d_out, int(t0 == t_first), int(t_first > 0), int(last_group), stream})) return st;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(s->ev1, stream));
@@ -1731,8 +1776,8 @@ static uint32_t rays_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint
 // are the caller's host memory and go through `stage`.  The scene's stats are the sums over the chunks; the tail flag belongs to
 // the last chunk.
 template <typename F>
-int render_table_chunks(RtScene* s, ChunkStage& stage, uint64_t n, const std::vector<ChunkArray>& in, double* out, bool host, hipStream_t stream,
-                        F&& render) {
+int render_table_chunks(RtScene* s, ChunkStage& stage, uint64_t n, const std::vector<ChunkArray>& in, double* out, size_t out_each, bool host,
+                        hipStream_t stream, F&& render) {
     const uint32_t chunk = rays_chunk();
     RtCameraDesc cam{};  // only the width is read: a table has no camera arithmetic
     cam.image_height = 1;
@@ -1754,7 +1799,7 @@ int render_table_chunks(RtScene* s, ChunkStage& stage, uint64_t n, const std::ve
         sum = acc;
         return RT_OK;
     };
-    const int st = run_chunks(stage, n, chunk, host, in, out, 4 * sizeof(double), stream, launch, &t);
+    const int st = run_chunks(stage, n, chunk, host, in, out, out_each, stream, launch, &t);
     if (st == RT_OK) s->stats = sum;
     return st;
 }
@@ -1769,7 +1814,7 @@ int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* 
         rp.first = off;
         return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, rp);
     };
-    return render_table_chunks(s, s->rays.stage, n, {{origins, 24}, {dirs, 24}}, out, host, stream, render);
+    return render_table_chunks(s, s->rays.stage, n, {{origins, 24}, {dirs, 24}}, out, 4 * sizeof(double), host, stream, render);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1802,7 +1847,26 @@ int bake_irradiance_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const doub
         return RT_OK;
     };
     const std::vector<ChunkArray> in = hits ? std::vector<ChunkArray>{} : std::vector<ChunkArray>{{positions, 24}, {normals, 24}};
-    return render_table_chunks(s, s->rays.stage, n, in, out, host, stream, render);
+    return render_table_chunks(s, s->rays.stage, n, in, out, 4 * sizeof(double), host, stream, render);
+}
+
+// ---------------------------------------------------------------------------------------------
+// SH probe bake (include/rt_mi355.h): the positions of the caller, chunked like a ray table; 24 B in and
+// 288 B out per probe, which is what the host variant's staging buffer is sized for
+// ---------------------------------------------------------------------------------------------
+template <typename R>
+int bake_probes_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const RtRenderParams& p, double* out, bool host,
+                      hipStream_t stream) {
+    auto render = [&](const RtCameraDesc& cam, uint64_t off, uint32_t, const void* const* d_in, double* d_out) -> int {
+        ProbeTablePass pp;
+        pp.pos = static_cast<const double*>(d_in[0]);
+        pp.first = off;
+        pp.seed = p.seed;
+        pp.S = p.sqrt_spt;
+        pp.f32 = sizeof(R) == 4;
+        return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, pp);
+    };
+    return render_table_chunks(s, s->rays.stage, n, {{positions, 24}}, out, 36 * sizeof(double), host, stream, render);
 }
 
 // Makes sure the scene's tables in the arithmetic of `precision` are on the device (built on first use), then f(tables).
@@ -3385,7 +3449,7 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
     return RT_OK;
 }
 
-// ---- Renders along ray tables, irradiance bakes --------------------------------------------------------------------------------
+// ---- Renders along ray tables, irradiance and probe bakes --------------------------------------------------------------------------------
 // The rules the two share, checked before the device is touched; a/b/out name the arrays in messages (a, b NULL: no such array).
 static int table_render_check(const RtScene* scene, uint64_t n, const void* a, const char* a_name, const void* b, const char* b_name,
                               const RtRenderParams* params, const void* out, const char* out_name, const std::string& w, const char* what, const char* unit) {
@@ -3464,6 +3528,70 @@ int rt_bake_irradiance_hits_device(const RtScene* scene, uint64_t n, const RtRay
     const int r = bake_irradiance_impl(scene, n, nullptr, nullptr, d_hits, true, params, d_rgba_out, false, stream, "rt_bake_irradiance_hits_device");
     if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
     return r;
+}
+
+static int bake_probes_impl(const RtScene* scene, uint64_t n, const double* positions, const RtRenderParams* params, double* out, bool host, void* stream,
+                            const char* who) {
+    using namespace rt;
+    const int chk = table_render_check(scene, n, positions, "positions", nullptr, nullptr, params, out, "sh_out", std::string(who) + ": ", "probe table", "probe");
+    if (chk != RT_OK || n == 0) return chk;
+    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
+    HIP_TRY(hipSetDevice(s->device));
+    RtRenderParams p = *params;
+    p.band_rows = p.n_parts = p.part = 0;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    return with_tables(s, p.precision, [&](auto& ds) -> int { return bake_probes_typed(s, ds, n, positions, p, out, host, st); });
+}
+
+int rt_bake_probes(const RtScene* scene, uint64_t n, const double* positions, const RtRenderParams* params, double* sh_out) {
+    const int r = bake_probes_impl(scene, n, positions, params, sh_out, true, nullptr, "rt_bake_probes");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
+    return r;
+}
+int rt_bake_probes_device(const RtScene* scene, uint64_t n, const double* d_positions, const RtRenderParams* params, double* d_sh_out, void* stream) {
+    const int r = bake_probes_impl(scene, n, d_positions, params, d_sh_out, false, stream, "rt_bake_probes_device");
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
+    return r;
+}
+
+int rt_sh_irradiance_device(int device, const double* d_sh, uint64_t n_probes, const uint32_t* d_probe, const double* d_normals, uint64_t m,
+                            double* d_rgba_out, void* stream) {
+    using namespace rt;
+    if (m == 0) return RT_OK;
+    if (!d_probe || !d_normals || !d_rgba_out || (n_probes && !d_sh)) return set_err(RT_E_INVALID, "rt_sh_irradiance_device: NULL argument");
+    if (m >= (1ull << 31) || n_probes >= (1ull << 31)) return set_err(RT_E_INVALID, "rt_sh_irradiance_device: m and n_probes must be below 2^31");
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    hipLaunchKernelGGL(k_sh_irradiance, dim3(uint32_t((m + 255) / 256)), dim3(256), 0, st, d_sh, n_probes, d_probe, d_normals, m, d_rgba_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    return RT_OK;
+}
+
+int rt_sh_irradiance(int device, const double* sh, uint64_t n_probes, const uint32_t* probe, const double* normals, uint64_t m, double* rgba_out) {
+    using namespace rt;
+    if (m == 0) return RT_OK;
+    if (!probe || !normals || !rgba_out || (n_probes && !sh)) return set_err(RT_E_INVALID, "rt_sh_irradiance: NULL argument");
+    if (m >= (1ull << 31) || n_probes >= (1ull << 31)) return set_err(RT_E_INVALID, "rt_sh_irradiance: m and n_probes must be below 2^31");
+    for (uint64_t j = 0; j < m; j++)
+        if (probe[j] >= n_probes) return set_err(RT_E_INVALID, "rt_sh_irradiance: probe[" + std::to_string(j) + "] = " + std::to_string(probe[j]) + " is not below n_probes");
+    HIP_TRY(hipSetDevice(device));
+    const size_t b_sh = size_t(n_probes) * 36 * sizeof(double), b_n = size_t(m) * 24, b_out = size_t(m) * 32, b_p = size_t(m) * 4;
+    DevBuf<double> d_buf;  // coefficients, normals, answers, then the indices
+    if (int st = d_buf.reserve(b_sh + b_n + b_out + b_p)) return st;
+    double* d_sh = d_buf;
+    double* d_n = d_sh + b_sh / sizeof(double);
+    double* d_out = d_n + b_n / sizeof(double);
+    uint32_t* d_p = reinterpret_cast<uint32_t*>(d_out + b_out / sizeof(double));
+    auto copy = [](void* dst, const void* src, size_t bytes, hipMemcpyKind kind) -> int {
+        const hipError_t e = hipMemcpy(dst, src, bytes, kind);
+        return e == hipSuccess ? int(RT_OK) : set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
+    };
+    if (int st = copy(d_sh, sh, b_sh, hipMemcpyHostToDevice)) return st;
+    if (int st = copy(d_n, normals, b_n, hipMemcpyHostToDevice)) return st;
+    if (int st = copy(d_p, probe, b_p, hipMemcpyHostToDevice)) return st;
+    if (int st = rt_sh_irradiance_device(device, d_sh, n_probes, d_p, d_n, m, d_out, nullptr)) return st;
+    return copy(rgba_out, d_out, b_out, hipMemcpyDeviceToHost);
 }
 
 // ---- Ray queries (rt_query.hip) -----------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@
 //                      ends writes its radiance to the per-sample buffer and restarts IN PLACE
 //                      on the next unrendered sample; surviving slots are compacted into the
 //                      next queue with ballot + mbcnt prefix sums (one atomic per wave)
-//   k_wf_resolve    per pixel: sum the sample radiances in the reference's order
+//   k_wf_resolve    per pixel: sum the sample radiances in the reference's order (k_wf_resolve_sh: per probe and SH coefficient)
 //                   (replica, sy, sx: camera.rs:217-229, 247-253) -> frame
 //
 // Every sample owns one slot of the per-sample radiance buffer (24 B), so the frame does not
@@ -83,6 +83,7 @@ struct WfGroup {
     static constexpr bool kLightGroups = false;
     static constexpr bool kRays = false;
     static constexpr bool kPoints = false;
+    static constexpr bool kProbes = false;
 };
 
 // Replica group of an adaptive pass over a SUBSET of the pixels: `npix` counts the active pixels and
@@ -162,6 +163,69 @@ RT_DEV_NOINLINE WfPointRay<R> wf_point_ray(const double* pp, const double* pn, R
     return {o, tgt - o};
 }
 
+// Replica group of an SH probe bake (rt_bake_probes): "pixel" i of the group is probe i of a chunk of the
+// caller's positions, and a sample's first ray leaves that position in a direction uniform over the sphere, formed from the two
+// uniforms a camera spends on its jitter.  `pos` points at the chunk's first position (3 doubles per probe); `first`: as in
+// WfGroupRays.  A type of its own for the reason WfGroupSparse is one.
+template <typename R>
+struct WfGroupProbes : WfGroup<R> {
+    const double* pos;
+    uint64_t first;
+    static constexpr bool kProbes = true;
+};
+
+// The stratified pair a table mode forms its first direction from: cell (sx, sy) of the S x S strata plus the generator's next two
+// uniforms, as a camera forms its jitter.
+template <typename R>
+RT_DEV void wf_strat_uniforms(Rng& rng, uint32_t st, uint32_t S, R inv_S, R& u1, R& u2) {
+    const uint32_t sy = st / S, sx = st - sy * S;
+    const R r1 = rng_uniform<R>(rng);
+    const R r2 = rng_uniform<R>(rng);
+    u1 = (R(sx) + r1) * inv_S;
+    u2 = (R(sy) + r2) * inv_S;
+}
+
+// Direction of a probe sample: (u1, u2) -> the uniform sphere, z = 1 - 2 u2 (1 - z z >= 0 in either format for u2 in [0, 1]: no
+// clamp).  ONE definition for the first ray (wf_probe_ray) and for the resolve that weights the sample by the SH basis of its
+// direction (k_wf_resolve_sh): the two must agree bit for bit in both precisions, and nothing is stored per sample.
+template <typename R>
+RT_DEV V3<R> wf_probe_dir(R u1, R u2) {
+    const R z = R(1) - R(2) * u2;
+    const R r = sqrt(R(1) - z * z);
+    const R phi = u1 * R(2) * pi<R>();
+    R sn, cs;
+    sincos_r(phi, sn, cs);
+    return mk<R>(cs * r, sn * r, z);
+}
+
+// First ray of a probe sample, returned the way the reference's camera would form it from position = o and first_pixel = o + d
+// (wf_point_ray has the why).  OUT of line for wf_point_ray's reason: the sincos polynomial inlined into k_wf_shade's restart
+// costs registers the kernel does not have.
+template <typename R>
+RT_DEV_NOINLINE WfPointRay<R> wf_probe_ray(const double* pp, R u1, R u2) {
+    const V3<R> dir = wf_probe_dir<R>(u1, u2);
+    const V3<R> o = mk<R>(R(pp[0]), R(pp[1]), R(pp[2]));
+    const V3<R> tgt = o + dir;
+    return {o, tgt - o};
+}
+
+// Y_k(d), k < 9: the real spherical harmonics of bands 0-2 with positive signs (no Condon-Shortley phase), in R; the constants
+// are f64 literals rounded to R.  A switch, not a table: the caller's k is uniform over a wave and nothing is indexed by it.
+template <typename R>
+RT_DEV R wf_sh_basis(uint32_t k, V3<R> d) {
+    switch (k) {
+        case 0: return R(0.28209479177387814);
+        case 1: return R(0.4886025119029199) * d.y;
+        case 2: return R(0.4886025119029199) * d.z;
+        case 3: return R(0.4886025119029199) * d.x;
+        case 4: return R(1.0925484305920792) * (d.x * d.y);
+        case 5: return R(1.0925484305920792) * (d.y * d.z);
+        case 6: return R(0.31539156525252005) * (R(3) * (d.z * d.z) - R(1));
+        case 7: return R(1.0925484305920792) * (d.x * d.z);
+        default: return R(0.5462742152960396) * (d.x * d.x - d.y * d.y);
+    }
+}
+
 // floor(a / b) and the remainder for a < 2^51: the reciprocal estimate is off by at most one, the remainder test makes it
 // exact (integers throughout: nothing here can move a pixel).  A generic 64-bit division is ~120 instructions on gfx950
 // and the restart of a finished path needs three of them.
@@ -204,6 +268,16 @@ RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, co
         const R u2 = (R(sy) + r2) * cam.inv_sqrt_spt;
         const uint64_t at = pix * grp.stride;
         const WfPointRay<R> ray = wf_point_ray<R>(reinterpret_cast<const double*>(grp.pos + at), reinterpret_cast<const double*>(grp.nrm + at), u1, u2);
+        o = ray.o;
+        d = ray.d;
+        return;
+    }
+    if constexpr (G::kProbes) {
+        // As for points: the stream of probe i is the stream of pixel i and the camera's two jitter draws are the sphere sample.
+        rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
+        R u1, u2;
+        wf_strat_uniforms<R>(rng, st, cam.sqrt_spt, cam.inv_sqrt_spt, u1, u2);
+        const WfPointRay<R> ray = wf_probe_ray<R>(grp.pos + uint32_t(pix) * 3u, u1, u2);  // the driver keeps a chunk below 2^28 probes
         o = ray.o;
         d = ray.d;
         return;
@@ -1632,6 +1706,90 @@ __global__ void __launch_bounds__(256) k_light_mix(const double* __restrict__ gr
     out[4 * p + 1] = a[1];
     out[4 * p + 2] = a[2];
     out[4 * p + 3] = 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------
+// SH probes (include/rt_mi355.h).
+// ---------------------------------------------------------------------------------------------
+// Resolve of a probe bake: k_wf_resolve's ordered sums with every sample's radiance multiplied by double(Y_k(d)), d the
+// direction the sample's first ray was formed from.  Nothing is stored per sample for it: d is re-derived from the sample's key
+// (the keyed generator, its first two uniforms, wf_probe_dir - the function wf_probe_ray called).  Laid out like
+// k_wf_resolve_groups: one thread per (probe, coefficient), a WAVE is 64 neighbouring probes of one k - unit-stride reads of
+// sample_L - and a thread keeps one coefficient's three sums in registers: no array indexed by k, no scratch.  The four waves of a
+// workgroup are four coefficients of the SAME 64 probes and the other two workgroups of those probes follow directly in the
+// grid.  Between replica groups `acc` carries 3 doubles per (coefficient, probe), 27 per probe; `out` is n x 9 x 4.
+// probe = index in the whole call of the chunk's first probe (the key), tid0 = the group's first replica.
+template <typename R>
+__global__ void __launch_bounds__(256) k_wf_resolve_sh(const double* __restrict__ sample_L, double* __restrict__ acc, uint64_t npix, uint64_t probe,
+                                                       uint64_t seed, uint32_t tid0, uint32_t S, R inv_S, uint32_t n_replicas, double spp,
+                                                       int first_group, double* __restrict__ out, int last_group) {
+#pragma clang fp contract(off)
+    const uint32_t pix_block = blockIdx.x / 3u;  // three workgroups of four coefficients per block of 64 probes
+    const uint32_t k = (blockIdx.x - pix_block * 3u) * 4u + (threadIdx.x >> 6);
+    const uint64_t pix = uint64_t(pix_block) * 64u + (threadIdx.x & 63u);
+    if (pix >= npix || k >= 9u) return;
+    const uint64_t kp = uint64_t(k) * npix + pix;
+    const uint32_t strata = S * S;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    if (!first_group) { a0 = acc[3 * kp + 0]; a1 = acc[3 * kp + 1]; a2 = acc[3 * kp + 2]; }
+    for (uint32_t t = 0; t < n_replicas; t++) {
+        double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+        for (uint32_t st = 0; st < strata; st++) {
+            const uint64_t s = (uint64_t(t) * strata + st) * npix + pix;
+            Rng rng;
+            rng.key(seed, tid0 + t, probe + pix, st);
+            R u1, u2;
+            wf_strat_uniforms<R>(rng, st, S, inv_S, u1, u2);
+            const double y = double(wf_sh_basis<R>(k, wf_probe_dir<R>(u1, u2)));
+            const double l0 = sample_L[3 * s + 0], l1 = sample_L[3 * s + 1], l2 = sample_L[3 * s + 2];
+            c0 += y * l0;
+            c1 += y * l1;
+            c2 += y * l2;
+        }
+        a0 += c0 / spp;
+        a1 += c1 / spp;
+        a2 += c2 / spp;
+    }
+    if (last_group) {
+        const uint64_t at = 4 * (pix * 9u + k);
+        out[at + 0] = a0;
+        out[at + 1] = a1;
+        out[at + 2] = a2;
+        out[at + 3] = 0.0;
+    } else {
+        acc[3 * kp + 0] = a0; acc[3 * kp + 1] = a1; acc[3 * kp + 2] = a2;
+    }
+}
+
+// rt_sh_irradiance: query j names probe[j] and a normal; out[j] = 4 pi (a_0 Y0 + (2/3) (bands 1) + (1/4) (bands 2)) per channel,
+// summed left to right in f64 - the clamped-cosine convolution of the probe's coefficients divided by pi, the unit of
+// rt_bake_irradiance.  An index out of range gives (0, 0, 0, 0).  One thread per query, streaming.
+__global__ void __launch_bounds__(256) k_sh_irradiance(const double* __restrict__ sh, uint64_t n_probes, const uint32_t* __restrict__ probe,
+                                                       const double* __restrict__ normals, uint64_t m, double* __restrict__ out) {
+#pragma clang fp contract(off)
+    const uint64_t j = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (j >= m) return;
+    const uint64_t p = probe[j];
+    double r0 = 0.0, r1 = 0.0, r2 = 0.0;
+    if (p < n_probes) {
+        const V3<double> w = to_unit(mk<double>(normals[3 * j], normals[3 * j + 1], normals[3 * j + 2]));
+        const double* a = sh + 36 * p;
+        double y[9];
+#pragma unroll
+        for (uint32_t k = 0; k < 9u; k++) y[k] = wf_sh_basis<double>(k, w);
+        const double four_pi = 4.0 * pi<double>(), b1 = 2.0 / 3.0, b2 = 0.25;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double band1 = (a[4 + c] * y[1] + a[8 + c] * y[2]) + a[12 + c] * y[3];
+            const double band2 = (((a[16 + c] * y[4] + a[20 + c] * y[5]) + a[24 + c] * y[6]) + a[28 + c] * y[7]) + a[32 + c] * y[8];
+            const double v = four_pi * ((a[c] * y[0] + b1 * band1) + b2 * band2);
+            if (c == 0) r0 = v; else if (c == 1) r1 = v; else r2 = v;
+        }
+    }
+    out[4 * j + 0] = r0;
+    out[4 * j + 1] = r1;
+    out[4 * j + 2] = r2;
+    out[4 * j + 3] = 0.0;
 }
 
 // ---------------------------------------------------------------------------------------------
