@@ -226,6 +226,20 @@ _host_lib = None
 _device_lib = None
 
 
+def _check(lib, st: int) -> None:
+    """Raises RtError with the last error text of `lib` (the device library, or the host library) unless st is RT_OK."""
+    if st != RT_OK:
+        raise RtError(st, (lib.rth_last_error if lib is _host_lib else lib.rt_last_error)().decode())
+
+
+def _table(a, name: str) -> np.ndarray:
+    """`a` as an (n, 3) float64 C-contiguous table; a single (3,) entry becomes (1, 3).  `name`: of the argument(s), in errors."""
+    a = np.asarray(a, dtype=np.float64)
+    if a.shape[-1:] != (3,) or a.ndim > 2:
+        raise ValueError(f"{name} must be (n, 3) or (3,)")
+    return np.ascontiguousarray(np.atleast_2d(a))
+
+
 def load_host_lib() -> C.CDLL:
     global _host_lib
     if _host_lib is None:
@@ -468,8 +482,7 @@ def scene_info(desc) -> int:
     lib = load_device_lib()
     flags = C.c_uint32()
     st = lib.rt_scene_info(desc, C.byref(flags))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return flags.value
 
 
@@ -478,8 +491,7 @@ def scene_mesh_stats(desc) -> dict:
     lib = load_device_lib()
     out = (C.c_uint64 * 8)()
     st = lib.rt_scene_mesh_stats(desc, out)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return dict(zip(("triangles", "bvh2_nodes", "bvh4_nodes", "bvh2_depth", "bvh4_stack", "ops", "rebuilt_groups", "rebuilt_prims"),
                     [int(x) for x in out]))
 
@@ -490,8 +502,7 @@ def live_resources() -> tuple:
     lib = load_device_lib()
     out = (C.c_uint64 * 4)()
     st = lib.rt_debug_live_resources(out)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return tuple(int(x) for x in out)
 
 
@@ -523,15 +534,13 @@ def scene_mesh_cones(desc, mesh: int = 0, f32: bool = False) -> tuple:
     lib = load_device_lib()
     nn, nt = C.c_uint32(), C.c_uint32()
     st = lib.rt_scene_mesh_cones(desc, mesh, int(f32), None, None, 0, C.byref(nn), None, 0, C.byref(nt))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     children = np.zeros((nn.value, 4), dtype=np.int32)
     cones = np.zeros((nn.value, 4), dtype=np.uint32)
     tris = np.zeros((nt.value, 3, 3), dtype=np.float64)
     st = lib.rt_scene_mesh_cones(desc, mesh, int(f32), children.ctypes.data, cones.ctypes.data, nn.value, C.byref(nn),
                                  tris.ctypes.data, nt.value, C.byref(nt))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return children, cones.view(np.int8).reshape(-1, 4, 4), tris
 
 
@@ -542,15 +551,13 @@ def scene_mesh_slabs(desc, mesh: int = 0, f32: bool = False) -> dict:
     lib = load_device_lib()
     nn, pad = C.c_uint32(), C.c_double()
     st = lib.rt_scene_mesh_slabs(desc, mesh, int(f32), None, None, None, C.byref(pad), 0, C.byref(nn))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     words = np.zeros((nn.value, 4), dtype=np.uint32)
     bounds = np.zeros((nn.value, 4, 2), dtype=np.float32)
     frames = np.zeros((nn.value, 4), dtype=np.float32)
     st = lib.rt_scene_mesh_slabs(desc, mesh, int(f32), words.ctypes.data, bounds.ctypes.data, frames.ctypes.data, C.byref(pad),
                                  nn.value, C.byref(nn))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return {"words": words, "bounds": bounds, "org": frames[:, :3].copy(), "inv_s": frames[:, 3].copy(), "pad": float(pad.value)}
 
 
@@ -559,8 +566,7 @@ def scene_update_check(a, b) -> None:
     the structure of `a`, i.e. unless DeviceScene(a).update(b) would be accepted as far as the structure goes; host only."""
     lib = load_device_lib()
     st = lib.rt_scene_update_check(a, b)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
 
 
 def _mesh_export(call) -> dict:
@@ -569,8 +575,7 @@ def _mesh_export(call) -> dict:
     lib = load_device_lib()
     nn, nt = C.c_uint32(), C.c_uint32()
     st = call(None, None, None, 0, C.byref(nn), None, None, 0, C.byref(nt))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     children = np.zeros((nn.value, 4), dtype=np.int32)
     cones = np.zeros((nn.value, 4), dtype=np.uint32)
     boxes = np.zeros((nn.value, 4, 2, 3), dtype=np.float32)
@@ -578,8 +583,7 @@ def _mesh_export(call) -> dict:
     order = np.zeros(nt.value, dtype=np.uint32)
     st = call(children.ctypes.data, cones.ctypes.data, boxes.ctypes.data, nn.value, C.byref(nn), tris.ctypes.data, order.ctypes.data,
               nt.value, C.byref(nt))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return {"children": children, "cones": cones.view(np.int8).reshape(-1, 4, 4), "boxes": boxes, "tris": tris, "order": order}
 
 
@@ -601,12 +605,10 @@ def scene_program(desc) -> tuple:
     n = C.c_uint32()
     info = (C.c_uint64 * 8)()
     st = lib.rt_scene_program(desc, None, 0, C.byref(n), info)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     ops = np.zeros((n.value, 4), dtype=np.int32)
     st = lib.rt_scene_program(desc, ops.ctypes.data_as(C.POINTER(C.c_int32)), n.value, C.byref(n), info)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     plan = int(info[6])
     return ops, {"mesh_ops": int(info[0]), "groups": int(info[1]), "group_nodes": int(info[2]), "group_stack": int(info[3]),
                  "lights": int(info[4]), "volumes": int(info[5]), "group_prims": int(info[7]),
@@ -619,12 +621,10 @@ def scene_op_nodes(desc) -> np.ndarray:
     lib = load_device_lib()
     n = C.c_uint32()
     st = lib.rt_scene_op_nodes(desc, None, 0, C.byref(n))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     nodes = np.full(n.value, -1, dtype=np.int32)
     st = lib.rt_scene_op_nodes(desc, nodes.ctypes.data, n.value, C.byref(n))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return nodes
 
 
@@ -636,8 +636,7 @@ def light_groups_auto(desc, max_groups: int = RT_LIGHT_GROUPS_MAX, has_backgroun
     table = np.zeros(d.n_materials, dtype=np.uint8)
     bg, n = C.c_uint32(), C.c_uint32()
     st = lib.rt_light_groups_auto(desc, max_groups, int(bool(has_background)), table.ctypes.data, C.byref(bg), C.byref(n))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return RtLightGroups.make(n.value, table, bg.value, 0)
 
 
@@ -656,8 +655,7 @@ def light_mix(groups: np.ndarray, tints, device: int = 0) -> np.ndarray:
         raise ValueError(f"light_mix: expected {g} x 3 tints, got {tints.shape}")
     out = np.empty((h, w, 4), dtype=np.float64)
     st = lib.rt_light_mix(device, groups.ctypes.data, g, w, h, tints.ctypes.data, out.ctypes.data)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return out
 
 
@@ -692,8 +690,7 @@ def sh_irradiance(sh, probe, normals, device: int = 0) -> np.ndarray:
     nr = np.ascontiguousarray(np.broadcast_to(nr, (m, 3)))
     out = np.empty((m, 4), dtype=np.float64)
     st = lib.rt_sh_irradiance(device, sh.ctypes.data, len(sh), idx.ctypes.data, nr.ctypes.data, m, out.ctypes.data)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return out
 
 
@@ -704,8 +701,7 @@ def sh_irradiance_device(d_sh_ptr: int, n_probes: int, d_probe_ptr: int, d_norma
     lib = load_device_lib()
     st = lib.rt_sh_irradiance_device(device, C.c_void_p(d_sh_ptr or None), n_probes, C.c_void_p(d_probe_ptr or None), C.c_void_p(d_normals_ptr or None),
                                      m, C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
 
 
 def owned_rows(height: int, params: RtRenderParams) -> list:
@@ -729,8 +725,7 @@ class HostScene:
             st = lib.rth_load(len(argv), arr, C.byref(handle))
         finally:
             os.chdir(old)
-        if st != RT_OK:
-            raise RtError(st, lib.rth_last_error().decode())
+        _check(lib, st)
         self._lib = lib
         self._h = handle
         self.desc = lib.rth_scene(handle)          # POINTER(RtSceneDesc)
@@ -778,8 +773,7 @@ def tonemap_rgb8(rgba: np.ndarray) -> np.ndarray:
     h, w = rgba.shape[:2]
     out = np.empty((h, w, 3), dtype=np.uint8)
     st = lib.rth_tonemap_rgb8(rgba.ctypes.data, w, h, out.ctypes.data)
-    if st != RT_OK:
-        raise RtError(st, lib.rth_last_error().decode())
+    _check(lib, st)
     return out
 
 
@@ -788,8 +782,7 @@ def tonemap_rgb8_device(d_rgba: int, width: int, height: int, d_rgb: int, device
     width*height*3 bytes); returns when the output is written."""
     lib = load_device_lib()
     st = lib.rt_tonemap_rgb8_device(device, C.c_void_p(d_rgba), width, height, C.c_void_p(d_rgb), C.c_void_p(stream))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
 
 
 def _dp_ref(dp: Optional[RtDenoiseParams]):
@@ -807,8 +800,7 @@ def denoise(rgba: np.ndarray, aov: np.ndarray, dp: Optional[RtDenoiseParams] = N
         raise ValueError(f"denoise: expected (H, W, 4) and (H, W, {AOV_CHANNELS}) arrays, got {rgba.shape} and {aov.shape}")
     out = np.empty_like(rgba)
     st = lib.rt_denoise(device, rgba.ctypes.data, aov.ctypes.data, w, h, _dp_ref(dp), out.ctypes.data)
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
     return out
 
 
@@ -818,8 +810,7 @@ def denoise_device(d_rgba: int, d_aov: int, width: int, height: int, d_out: int,
     lib = load_device_lib()
     st = lib.rt_denoise_device(device, C.c_void_p(d_rgba), C.c_void_p(d_aov), width, height, _dp_ref(dp), C.c_void_p(d_out),
                                C.c_void_p(stream))
-    if st != RT_OK:
-        raise RtError(st, lib.rt_last_error().decode())
+    _check(lib, st)
 
 
 def probe_rays(position, width: int, height: int) -> tuple:
@@ -829,8 +820,7 @@ def probe_rays(position, width: int, height: int) -> tuple:
     o = np.empty((int(width) * int(height), 3), dtype=np.float64)
     d = np.empty_like(o)
     st = lib.rth_probe_rays((C.c_double * 3)(*[float(x) for x in position]), width, height, o.ctypes.data, d.ctypes.data)
-    if st != RT_OK:
-        raise RtError(st, lib.rth_last_error().decode())
+    _check(lib, st)
     return o, d
 
 
@@ -839,8 +829,7 @@ def save_png(path: str, rgba: np.ndarray) -> None:
     rgba = np.ascontiguousarray(rgba, dtype=np.float64)
     h, w = rgba.shape[:2]
     st = lib.rth_save_png(path.encode(), rgba.ctypes.data, w, h)
-    if st != RT_OK:
-        raise RtError(st, lib.rth_last_error().decode())
+    _check(lib, st)
 
 
 def load_image(path: str) -> np.ndarray:
@@ -849,8 +838,7 @@ def load_image(path: str) -> np.ndarray:
     ptr = C.POINTER(C.c_float)()
     w, h = C.c_uint32(), C.c_uint32()
     st = lib.rth_load_image(path.encode(), C.byref(ptr), C.byref(w), C.byref(h))
-    if st != RT_OK:
-        raise RtError(st, lib.rth_last_error().decode())
+    _check(lib, st)
     try:
         return np.ctypeslib.as_array(ptr, shape=(h.value, w.value, 3)).copy()
     finally:
@@ -864,8 +852,7 @@ class DeviceScene:
         lib = load_device_lib()
         handle = C.c_void_p()
         st = lib.rt_scene_create(desc, device, C.byref(handle))
-        if st != RT_OK:
-            raise RtError(st, lib.rt_last_error().decode())
+        _check(lib, st)
         self._lib = lib
         self._h = handle
         self.device = device
@@ -874,15 +861,13 @@ class DeviceScene:
         rows = self._lib.rt_owned_rows(camera.image_height, C.byref(params))
         out = np.empty((rows, camera.image_width, 4), dtype=np.float64)
         st = self._lib.rt_render(self._h, C.byref(camera), C.byref(params), out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def render_device(self, camera: RtCameraDesc, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
         st = self._lib.rt_render_device(self._h, C.byref(camera), C.byref(params),
                                         C.c_void_p(d_out_ptr), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def render_light_groups(self, camera: RtCameraDesc, params: RtRenderParams, groups: RtLightGroups) -> tuple:
         """rt_render_light_groups: ((G, owned rows, W, 4) group frames, (owned rows, W, 4) ordinary frame) from one render."""
@@ -891,16 +876,14 @@ class DeviceScene:
         out = np.empty((rows, camera.image_width, 4), dtype=np.float64)
         st = self._lib.rt_render_light_groups(self._h, C.byref(camera), C.byref(params), C.byref(groups), out_g.ctypes.data,
                                               out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out_g, out
 
     def render_light_groups_device(self, camera: RtCameraDesc, params: RtRenderParams, groups: RtLightGroups, d_groups_ptr: int,
                                    d_out_ptr: int = 0, stream: int = 0) -> None:
         st = self._lib.rt_render_light_groups_device(self._h, C.byref(camera), C.byref(params), C.byref(groups),
                                                      C.c_void_p(d_groups_ptr), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def render_aov(self, camera: RtCameraDesc, params: RtRenderParams, n_replicas: Optional[int] = None) -> np.ndarray:
         """rt_render_aov: (owned rows, W, 8) first-hit albedo rgb, normal xyz, depth, coverage over the first n_replicas
@@ -909,16 +892,14 @@ class DeviceScene:
         rows = self._lib.rt_owned_rows(camera.image_height, C.byref(params))
         out = np.empty((rows, camera.image_width, AOV_CHANNELS), dtype=np.float64)
         st = self._lib.rt_render_aov(self._h, C.byref(camera), C.byref(params), n, out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def render_aov_device(self, camera: RtCameraDesc, params: RtRenderParams, d_out_ptr: int, n_replicas: Optional[int] = None,
                           stream: int = 0) -> None:
         n = params.thread_count if n_replicas is None else n_replicas
         st = self._lib.rt_render_aov_device(self._h, C.byref(camera), C.byref(params), n, C.c_void_p(d_out_ptr), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def trace_sample(self, camera, params, tid, x, y, sx, sy, max_bounces=64):
         """Diagnostic: (rgb[3], trace[n, 17]) of one sample traced on the device."""
@@ -927,7 +908,7 @@ class DeviceScene:
         n = self._lib.rt_debug_trace_sample(self._h, C.byref(camera), C.byref(params), tid, x, y, sx, sy,
                                             rgb, tr, max_bounces)
         if n < 0:
-            raise RtError(n, self._lib.rt_last_error().decode())
+            _check(self._lib, n)
         return np.array(list(rgb)), np.array(list(tr)).reshape(max_bounces, 17)[:min(n, max_bounces)]
 
     def update(self, desc) -> dict:
@@ -936,8 +917,7 @@ class DeviceScene:
         created before raise the library's error from then on."""
         info = RtSceneUpdateInfo()
         st = self._lib.rt_scene_update(self._h, desc, C.byref(info))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return {"n_meshes_refit": info.n_meshes_refit, "n_triangles_refit": info.n_triangles_refit, "bytes_uploaded": info.bytes_uploaded,
                 "refit_kernel_ms": info.refit_kernel_ms, "total_ms": info.total_ms}
 
@@ -951,8 +931,7 @@ class DeviceScene:
         nodes + cones, records, attributes, mesh boxes, mesh op records) and the number of updates so far."""
         out = (C.c_uint64 * 8)()
         st = self._lib.rt_debug_scene_mesh_digest(self._h, int(f32), out)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return tuple(int(x) for x in out)
 
     @staticmethod
@@ -961,9 +940,7 @@ class DeviceScene:
         o, d = np.asarray(origins, dtype=np.float64), np.asarray(dirs, dtype=np.float64)
         if o.shape[-1:] != (3,) or d.shape[-1:] != (3,):
             raise ValueError("origins and dirs must have a last axis of 3")
-        o, d = np.broadcast_arrays(np.atleast_2d(o), np.atleast_2d(d))
-        if o.ndim != 2:
-            raise ValueError("origins and dirs must be (n, 3) or (3,)")
+        o, d = np.broadcast_arrays(_table(o, "origins and dirs"), _table(d, "origins and dirs"))
         return np.ascontiguousarray(o), np.ascontiguousarray(d)
 
     def trace_rays(self, origins, dirs, precision: int = RT_PRECISION_F64) -> np.ndarray:
@@ -972,8 +949,7 @@ class DeviceScene:
         o, d = self._rays(origins, dirs)
         out = np.zeros(len(o), dtype=RtRayHit)
         st = self._lib.rt_trace_rays(self._h, len(o), o.ctypes.data, d.ctypes.data, precision, out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def trace_rays_device(self, n: int, d_origins_ptr: int, d_dirs_ptr: int, d_hits_ptr: int, precision: int = RT_PRECISION_F64,
@@ -981,8 +957,7 @@ class DeviceScene:
         """rt_trace_rays_device: n x 3 doubles each in HBM -> n RtRayHit records (96 B each) in HBM."""
         st = self._lib.rt_trace_rays_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None), precision,
                                             C.c_void_p(d_hits_ptr or None), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def occluded(self, origins, dirs, t_min=None, t_max=None, precision: int = RT_PRECISION_F64) -> np.ndarray:
         """rt_occluded: (n,) bool, True where a sphere, quad or triangle is hit inside (t_min, t_max).  t_min / t_max: None
@@ -994,8 +969,7 @@ class DeviceScene:
         out = np.zeros(n, dtype=np.uint8)
         st = self._lib.rt_occluded(self._h, n, o.ctypes.data, d.ctypes.data, None if lo is None else lo.ctypes.data,
                                    None if hi is None else hi.ctypes.data, precision, out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out.astype(bool)
 
     def occluded_device(self, n: int, d_origins_ptr: int, d_dirs_ptr: int, d_out_ptr: int, d_t_min_ptr: int = 0, d_t_max_ptr: int = 0,
@@ -1004,8 +978,7 @@ class DeviceScene:
         st = self._lib.rt_occluded_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None),
                                           C.c_void_p(d_t_min_ptr or None), C.c_void_p(d_t_max_ptr or None), precision,
                                           C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def render_rays(self, origins, dirs, params: RtRenderParams) -> np.ndarray:
         """rt_render_rays: the radiance along every ray as (n, 4) float64, (r, g, b, 0): ray i is rendered as pixel i of a frame
@@ -1014,8 +987,7 @@ class DeviceScene:
         o, d = self._rays(origins, dirs)
         out = np.empty((len(o), 4), dtype=np.float64)
         st = self._lib.rt_render_rays(self._h, len(o), o.ctypes.data, d.ctypes.data, C.byref(params), out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def render_rays_device(self, n: int, d_origins_ptr: int, d_dirs_ptr: int, params: RtRenderParams, d_out_ptr: int,
@@ -1023,8 +995,7 @@ class DeviceScene:
         """rt_render_rays_device: n x 3 doubles each in HBM -> n x 4 doubles in HBM."""
         st = self._lib.rt_render_rays_device(self._h, n, C.c_void_p(d_origins_ptr or None), C.c_void_p(d_dirs_ptr or None),
                                              C.byref(params), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def bake_irradiance(self, positions, normals, params: RtRenderParams) -> np.ndarray:
         """rt_bake_irradiance: the cosine-weighted mean of the radiance arriving at every surface point as (n, 4) float64,
@@ -1035,8 +1006,7 @@ class DeviceScene:
         p, nr = self._rays(positions, normals)
         out = np.empty((len(p), 4), dtype=np.float64)
         st = self._lib.rt_bake_irradiance(self._h, len(p), p.ctypes.data, nr.ctypes.data, C.byref(params), out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def bake_irradiance_device(self, n: int, d_positions_ptr: int, d_normals_ptr: int, params: RtRenderParams, d_out_ptr: int,
@@ -1044,16 +1014,14 @@ class DeviceScene:
         """rt_bake_irradiance_device: n x 3 doubles each in HBM -> n x 4 doubles in HBM."""
         st = self._lib.rt_bake_irradiance_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.c_void_p(d_normals_ptr or None),
                                                  C.byref(params), C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def bake_irradiance_hits_device(self, n: int, d_hits_ptr: int, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
         """rt_bake_irradiance_hits_device: n RtRayHit records in HBM (trace_rays_device) -> n x 4 doubles in HBM; a miss or an
         environment hit gives (0, 0, 0, 0)."""
         st = self._lib.rt_bake_irradiance_hits_device(self._h, n, C.c_void_p(d_hits_ptr or None), C.byref(params),
                                                       C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def bake_probes(self, positions, params: RtRenderParams) -> np.ndarray:
         """rt_bake_probes: SH radiance probes at positions in free space as (n, 9, 4) float64, (r, g, b, 0) per coefficient of
@@ -1061,28 +1029,22 @@ class DeviceScene:
         uniform over the sphere and drawn on the device (sqrt_spt, thread_count, max_depth, background, light_bias, seed and
         precision of `params`).  The radiance coefficients are 4 pi * out; api.sh_irradiance lights a normal from them.
         positions: (n, 3) or (3,)."""
-        p = np.asarray(positions, dtype=np.float64)
-        if p.shape[-1:] != (3,) or p.ndim > 2:
-            raise ValueError("positions must be (n, 3) or (3,)")
-        p = np.ascontiguousarray(np.atleast_2d(p))
+        p = _table(positions, "positions")
         out = np.empty((len(p), 9, 4), dtype=np.float64)
         st = self._lib.rt_bake_probes(self._h, len(p), p.ctypes.data, C.byref(params), out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def bake_probes_device(self, n: int, d_positions_ptr: int, params: RtRenderParams, d_out_ptr: int, stream: int = 0) -> None:
         """rt_bake_probes_device: n x 3 doubles in HBM -> n x 9 x 4 doubles in HBM."""
         st = self._lib.rt_bake_probes_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.byref(params), C.c_void_p(d_out_ptr or None),
                                              C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def ray_query_stats(self) -> RtRayQueryStats:
         s = RtRayQueryStats()
         st = self._lib.rt_ray_query_stats(self._h, C.byref(s))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return s
 
     def bake_visibility(self, positions, normals, samples: int = 64, seed: int = 0, bias: float = 1e-3,
@@ -1094,8 +1056,7 @@ class DeviceScene:
         out = np.zeros(len(p), dtype=RtBakeResult)
         bp = RtBakeParams.defaults(samples=samples, seed=seed, bias=bias, max_distance=max_distance, precision=precision)
         st = self._lib.rt_bake_visibility(self._h, len(p), p.ctypes.data, nr.ctypes.data, C.byref(bp), out.ctypes.data)
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return out
 
     def bake_visibility_device(self, n: int, d_positions_ptr: int, d_normals_ptr: int, d_out_ptr: int,
@@ -1104,8 +1065,7 @@ class DeviceScene:
         st = self._lib.rt_bake_visibility_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.c_void_p(d_normals_ptr or None),
                                                  C.byref(params) if params is not None else None, C.c_void_p(d_out_ptr or None),
                                                  C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def bake_visibility_hits_device(self, n: int, d_hits_ptr: int, d_out_ptr: int, params: Optional[RtBakeParams] = None,
                                     stream: int = 0) -> None:
@@ -1114,22 +1074,19 @@ class DeviceScene:
         st = self._lib.rt_bake_visibility_hits_device(self._h, n, C.c_void_p(d_hits_ptr or None),
                                                       C.byref(params) if params is not None else None, C.c_void_p(d_out_ptr or None),
                                                       C.c_void_p(stream))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def bake_stats(self) -> RtRayQueryStats:
         """rt_bake_stats: of the last bake (rays = n * samples); ray_query_stats() is not touched by a bake."""
         s = RtRayQueryStats()
         st = self._lib.rt_bake_stats(self._h, C.byref(s))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return s
 
     def stats(self) -> RtRenderStats:
         s = RtRenderStats()
         st = self._lib.rt_get_stats(self._h, C.byref(s))
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
         return s
 
     def close(self):
@@ -1159,8 +1116,7 @@ class ProgressiveRender:
         lib = load_device_lib()
         handle = C.c_void_p()
         st = lib.rt_accum_create(scene._h, C.byref(camera), C.byref(params), C.byref(handle))
-        if st != RT_OK:
-            raise RtError(st, lib.rt_last_error().decode())
+        _check(lib, st)
         self._lib = lib
         self._h = handle
         self.scene = scene  # the device scene must outlive the accumulator
@@ -1171,15 +1127,15 @@ class ProgressiveRender:
         self.adaptive = None
         if adaptive is not None:
             st = lib.rt_accum_set_adaptive(handle, C.byref(adaptive))
-            if st != RT_OK:
-                msg = lib.rt_last_error().decode()
+            try:
+                _check(lib, st)
+            except RtError:
                 self.close()
-                raise RtError(st, msg)
+                raise
             self.adaptive = RtAdaptiveParams.from_buffer_copy(adaptive)
 
     def _check(self, st: int) -> None:
-        if st != RT_OK:
-            raise RtError(st, self._lib.rt_last_error().decode())
+        _check(self._lib, st)
 
     def render(self, n: int, pipeline: Optional[int] = None, collect_stats: Optional[bool] = None) -> int:
         """Renders the next n replicas (clamped to what is left); returns replicas_done."""

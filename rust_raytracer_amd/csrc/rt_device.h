@@ -16,7 +16,7 @@
 
 namespace rt {
 
-#ifndef RT_DEV  // tools/point_ray_host.cpp builds the sampling code for the host as well
+#ifndef RT_DEV  // tools/table_ray_host.cpp builds the sampling code for the host as well
 #define RT_DEV __device__ __forceinline__
 #endif
 #ifndef RT_DEV_NOINLINE

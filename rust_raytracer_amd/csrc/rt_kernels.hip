@@ -1113,6 +1113,19 @@ struct AdaptiveMode : AdaptivePass, PassBase {
 // A light-group render (rt_render_light_groups): k_wf_shade records the group of every terminal and
 // k_wf_resolve_groups sums per group.  `table` (host): n_materials + 2 bytes as WfGroupLG describes them.  d_out (the
 // ordinary frame, through the unchanged k_wf_resolve) may be NULL.
+// launch() between the workspace's two resolve events, then a synchronise: its milliseconds are added to *ms_sum.
+template <typename F>
+int timed_resolve(const WfResolve& a, double* ms_sum, F&& launch) {
+    HIP_TRY(hipEventRecord(a.w.ev_res[0], a.stream));
+    if (int st = launch()) return st;
+    HIP_TRY(hipEventRecord(a.w.ev_res[1], a.stream));
+    HIP_TRY(hipStreamSynchronize(a.stream));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, a.w.ev_res[0], a.w.ev_res[1]));
+    *ms_sum += ms;
+    return RT_OK;
+}
+
 struct LightGroupPass : PassBase {
     uint32_t n_groups = 0, n_materials = 0;
     const uint8_t* table = nullptr;
@@ -1134,17 +1147,15 @@ struct LightGroupPass : PassBase {
     }
     template <typename G> void complete(G& g, RtScene::Wavefront& w) const { g.sample_G = w.sample_G; g.table = w.lg_table; g.n_materials = n_materials; }
     int resolve(const WfResolve& a) const {
-        HIP_TRY(hipEventRecord(a.w.ev_res[0], a.stream));
-        if (a.d_out) PassBase::resolve(a);
-        const uint64_t blocks = ((a.npix + 63) / 64) * ((n_groups + 3u) / 4u);
-        if (blocks > 0x7FFFFFFFull) return set_err(RT_E_UNSUPPORTED, "frame too large for the light-group resolve");
-        hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, a.stream, a.w.sample_L.get(), a.w.sample_G.get(), a.w.acc_g.get(), a.npix,
-                           n_groups, a.strata, a.nrep, a.spp, a.first, d_groups_out, a.last);
-        HIP_TRY(hipEventRecord(a.w.ev_res[1], a.stream));
-        HIP_TRY(hipStreamSynchronize(a.stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, a.w.ev_res[0], a.w.ev_res[1]));
-        resolve_ms += ms;
+        if (int st = timed_resolve(a, &resolve_ms, [&]() -> int {
+                if (a.d_out) PassBase::resolve(a);
+                const uint64_t blocks = ((a.npix + 63) / 64) * ((n_groups + 3u) / 4u);
+                if (blocks > 0x7FFFFFFFull) return set_err(RT_E_UNSUPPORTED, "frame too large for the light-group resolve");
+                hipLaunchKernelGGL(k_wf_resolve_groups, dim3(uint32_t(blocks)), dim3(256), 0, a.stream, a.w.sample_L.get(), a.w.sample_G.get(), a.w.acc_g.get(),
+                                   a.npix, n_groups, a.strata, a.nrep, a.spp, a.first, d_groups_out, a.last);
+                return RT_OK;
+            }))
+            return st;
         if (a.last && env_u32("RT_LG_LOG", 0))  // tools/gpu_light_groups_cost.py
             std::fprintf(stderr, "[light groups] G %u: resolve kernels %.3f ms, %zu B of group bytes, %zu B of group sums\n", n_groups, resolve_ms,
                          a.w.sample_G.bytes(), a.w.acc_g.bytes());
@@ -1152,45 +1163,43 @@ struct LightGroupPass : PassBase {
     }
 };
 
-// A render along a ray table (rt_render_rays): one chunk of the caller's table.  The "frame" is n x 1
-// pixels, pixel i = ray first + i; origins / dirs are device pointers to the chunk's first ray.
-struct RayTablePass : PassBase {
+// What the table modes share: a call renders one chunk of the caller's table as a "frame" of n x 1
+// pixels, pixel i = entry first + i, and every sample starts where its entry says.  table_render_check refuses collect_stats
+// before a pass exists.
+struct TablePass : PassBase {
+    uint64_t first = 0;
+    static constexpr const char* kNoCounting = "table modes have no adaptive, light-group or counting kernels (collect_stats)";
+    static constexpr bool kOwnOrigins = true;
+};
+
+// A render along a ray table (rt_render_rays): origins / dirs are device pointers to the chunk's first ray.
+struct RayTablePass : TablePass {
     const double* origins = nullptr;
     const double* dirs = nullptr;
-    uint64_t first = 0;
     template <typename R> using Group = WfGroupRays<R>;
-    static constexpr const char* kNoCounting = "ray tables have no adaptive, light-group or counting kernels (collect_stats)";
-    static constexpr bool kOwnOrigins = true;
     template <typename G> void complete(G& g, RtScene::Wavefront&) const { g.origins = origins; g.dirs = dirs; g.first = first; }
 };
 
-// An irradiance bake (rt_bake_irradiance): one chunk of the caller's points.  The "frame" is n x 1 pixels,
-// pixel i = point first + i; pos / nrm are device pointers to the chunk's first position and normal, `stride` bytes apart
-// from point to point (24: plain arrays; sizeof(RtRayHit): hit records).
-struct PointTablePass : PassBase {
+// An irradiance bake (rt_bake_irradiance): pos / nrm are device pointers to the chunk's first position and
+// normal, `stride` bytes apart from point to point (24: plain arrays; sizeof(RtRayHit): hit records).
+struct PointTablePass : TablePass {
     const unsigned char* pos = nullptr;
     const unsigned char* nrm = nullptr;
     uint32_t stride = 24;
-    uint64_t first = 0;
     template <typename R> using Group = WfGroupPoints<R>;
-    static constexpr const char* kNoCounting = "point tables have no adaptive, light-group or counting kernels (collect_stats)";
-    static constexpr bool kOwnOrigins = true;
     template <typename G> void complete(G& g, RtScene::Wavefront&) const { g.pos = pos; g.nrm = nrm; g.stride = stride; g.first = first; }
 };
 
-// An SH probe bake (rt_bake_probes): one chunk of the caller's positions.  The "frame" is n x 1 pixels,
-// pixel i = probe first + i; pos is a device pointer to the chunk's first position.  The resolve weights every sample by the SH
-// basis of its first direction, re-derived from the sample's key (k_wf_resolve_sh): d_out is n x 9 x 4 doubles, and several
-// replica groups carry 27 doubles per probe in w.acc instead of a pixel's 3.
-struct ProbeTablePass : PassBase {
+// An SH probe bake (rt_bake_probes): pos is a device pointer to the chunk's first position.  The resolve
+// weights every sample by the SH basis of its first direction, re-derived from the sample's key (k_wf_resolve_sh): d_out is
+// n x 9 x 4 doubles, and several replica groups carry 27 doubles per probe in w.acc instead of a pixel's 3.
+struct ProbeTablePass : TablePass {
     const double* pos = nullptr;
-    uint64_t first = 0;
     uint64_t seed = 0;
     uint32_t S = 1;
     bool f32 = false;
     template <typename R> using Group = WfGroupProbes<R>;
-    static constexpr const char* kNoCounting = "probe tables have no adaptive, light-group or counting kernels (collect_stats)";
-    static constexpr bool kOwnOrigins = true, kRunningSums = false;  // the sums between groups are this mode's own size
+    static constexpr bool kRunningSums = false;  // the sums between groups are this mode's own size
     int reserve(RtScene::Wavefront& w, uint64_t, uint64_t npix, uint32_t group, uint32_t n, hipStream_t) const {
         return w.acc.reserve(group < n ? size_t(npix) * 27 * sizeof(double) : size_t(0));
     }
@@ -1201,22 +1210,17 @@ struct ProbeTablePass : PassBase {
     }
     mutable double resolve_ms = 0;  // k_wf_resolve_sh, summed over the chunk's groups (RT_PROBES_LOG)
     int resolve(const WfResolve& a) const {
-        const bool log = env_u32("RT_PROBES_LOG", 0) != 0;  // tools/gpu_bake_probes_cost.py: times the resolve with events, at the price of a synchronise per group
-        if (log) {
-            for (Event& e : a.w.ev_res)
-                if (int st = e.ensure()) return st;
-            HIP_TRY(hipEventRecord(a.w.ev_res[0], a.stream));
-        }
-        if (f32) launch_resolve<float>(a, a.tid0);
-        else launch_resolve<double>(a, a.tid0);
-        if (log) {
-            HIP_TRY(hipEventRecord(a.w.ev_res[1], a.stream));
-            HIP_TRY(hipStreamSynchronize(a.stream));
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, a.w.ev_res[0], a.w.ev_res[1]));
-            resolve_ms += ms;
-            if (a.last) std::fprintf(stderr, "[probes] %llu probes from %llu on, %u paths each: k_wf_resolve_sh %.3f ms\n", (unsigned long long)a.npix, (unsigned long long)first, a.strata * a.T, resolve_ms);
-        }
+        auto launch = [&]() -> int {
+            if (f32) launch_resolve<float>(a, a.tid0);
+            else launch_resolve<double>(a, a.tid0);
+            return RT_OK;
+        };
+        if (!env_u32("RT_PROBES_LOG", 0)) return launch();
+        // tools/gpu_bake_probes_cost.py: times the resolve with events, at the price of a synchronise per group
+        for (Event& e : a.w.ev_res)
+            if (int st = e.ensure()) return st;
+        if (int st = timed_resolve(a, &resolve_ms, launch)) return st;
+        if (a.last) std::fprintf(stderr, "[probes] %llu probes from %llu on, %u paths each: k_wf_resolve_sh %.3f ms\n", (unsigned long long)a.npix, (unsigned long long)first, a.strata * a.T, resolve_ms);
         return RT_OK;
     }
 };
@@ -1729,6 +1733,17 @@ int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* ori
 // points per launch; the default is a guess, not a measurement
 static uint32_t bake_chunk() { return std::min<uint32_t>(1u << 26, std::max<uint32_t>(1u, env_u32("RT_BAKE_CHUNK", 1u << 20))); }
 
+// RtRayHit records as strided points: where the first record's position, normal and flags are, and the bytes from one record to
+// the next.
+struct HitPoints {
+    const unsigned char *pos, *nrm, *flags;
+    uint32_t stride;
+};
+static HitPoints hit_points(const RtRayHit* hits) {
+    const unsigned char* base = reinterpret_cast<const unsigned char*>(hits);
+    return {base + offsetof(RtRayHit, pos), base + offsetof(RtRayHit, normal), base + offsetof(RtRayHit, flags), uint32_t(sizeof(RtRayHit))};
+}
+
 // n points in chunks.  hits: the points are RtRayHit records on the device (positions = the records, normals unused);
 // host: positions / normals / out are host arrays, staged chunk by chunk.
 template <typename R>
@@ -1744,11 +1759,11 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
         pts.n = m;
         pts.first = off;
         if (hits) {
-            const unsigned char* base = reinterpret_cast<const unsigned char*>(hits + off);
-            pts.pos = base + offsetof(RtRayHit, pos);
-            pts.nrm = base + offsetof(RtRayHit, normal);
-            pts.flags = base + offsetof(RtRayHit, flags);
-            pts.pos_stride = pts.nrm_stride = pts.flags_stride = uint32_t(sizeof(RtRayHit));
+            const HitPoints h = hit_points(hits + off);
+            pts.pos = h.pos;
+            pts.nrm = h.nrm;
+            pts.flags = h.flags;
+            pts.pos_stride = pts.nrm_stride = pts.flags_stride = h.stride;
         } else {
             pts.pos = static_cast<const unsigned char*>(d_in[0]);
             pts.nrm = static_cast<const unsigned char*>(d_in[1]);
@@ -1771,14 +1786,24 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
 // kernels index the table with 32-bit element offsets.
 static uint32_t rays_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(1u, env_u32("RT_RAYS_CHUNK", 1u << 22))); }
 
-// n table entries (rays, or the points of an irradiance bake) in chunks through render_wavefront, each chunk a frame of m x 1
-// pixels whose pixel i is entry off + i: render(cam, off, m, d_in, d_out) runs render_wavefront for one chunk.  host: the arrays
-// are the caller's host memory and go through `stage`.  The scene's stats are the sums over the chunks; the tail flag belongs to
-// the last chunk.
-template <typename F>
-int render_table_chunks(RtScene* s, ChunkStage& stage, uint64_t n, const std::vector<ChunkArray>& in, double* out, size_t out_each, bool host,
-                        hipStream_t stream, F&& render) {
-    const uint32_t chunk = rays_chunk();
+static void stats_add(RtRenderStats& total, const RtRenderStats& part, bool first) {
+    if (first) { total = part; return; }
+    total.kernel_ms += part.kernel_ms; total.traversal_kernel_ms += part.traversal_kernel_ms;
+    total.prims_kernel_ms += part.prims_kernel_ms; total.shade_kernel_ms += part.shade_kernel_ms;
+    total.n_launches += part.n_launches; total.n_iterations += part.n_iterations; total.samples += part.samples;
+    total.n_replica_groups += part.n_replica_groups; total.n_tail_compactions += part.n_tail_compactions;
+}
+
+// n table entries (rays, points, probes) in chunks through render_wavefront, each chunk a frame of m x 1 pixels whose pixel i is
+// entry off + i: make_pass(p, off, m, d_in) is the chunk's pass (d_in: the chunk's part of each array of `in`, on the device), and
+// after(off, m, d_out, stream) may enqueue more work on the chunk's output.  host: the arrays are the caller's host memory and go through
+// the staging buffer.  The scene's stats are the sums over the chunks; the tail flag belongs to the last chunk.
+struct NoAfter {
+    int operator()(uint64_t, uint32_t, double*, hipStream_t) const { return RT_OK; }
+};
+template <typename R, typename MakePass, typename After>
+int render_table_chunks(RtScene* s, DeviceScene<R>& ds, const RtRenderParams& p, uint64_t n, const std::vector<ChunkArray>& in, double* out, size_t out_each,
+                        bool host, hipStream_t stream, MakePass&& make_pass, After&& after) {
     RtCameraDesc cam{};  // only the width is read: a table has no camera arithmetic
     cam.image_height = 1;
     RtRenderStats sum{};
@@ -1787,86 +1812,52 @@ int render_table_chunks(RtScene* s, ChunkStage& stage, uint64_t n, const std::ve
     auto launch = [&](uint64_t off, uint32_t m, const void* const* d_in, void* d_out) -> int {
         cam.image_width = m;
         s->tail_flag = off + m >= n ? tail_flag : nullptr;
-        const int st = render(cam, off, m, d_in, static_cast<double*>(d_out));
+        const int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, static_cast<double*>(d_out), stream, make_pass(p, off, m, d_in));
         s->tail_flag = tail_flag;
         if (st != RT_OK) return st;
-        const RtRenderStats c = s->stats;
-        RtRenderStats acc = c;  // what describes the kernels is the same in every chunk; times and counts add up
-        acc.kernel_ms += sum.kernel_ms; acc.traversal_kernel_ms += sum.traversal_kernel_ms;
-        acc.prims_kernel_ms += sum.prims_kernel_ms; acc.shade_kernel_ms += sum.shade_kernel_ms;
-        acc.n_launches += sum.n_launches; acc.samples += sum.samples; acc.n_iterations += sum.n_iterations;
-        acc.n_replica_groups += sum.n_replica_groups; acc.n_tail_compactions += sum.n_tail_compactions;
-        sum = acc;
-        return RT_OK;
+        stats_add(sum, s->stats, off == 0);
+        return after(off, m, static_cast<double*>(d_out), stream);
     };
-    const int st = run_chunks(stage, n, chunk, host, in, out, out_each, stream, launch, &t);
+    const int st = run_chunks(s->rays.stage, n, rays_chunk(), host, in, out, out_each, stream, launch, &t);
     if (st == RT_OK) s->stats = sum;
     return st;
 }
 
-template <typename R>
-int render_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const RtRenderParams& p,
-                      double* out, bool host, hipStream_t stream) {
-    auto render = [&](const RtCameraDesc& cam, uint64_t off, uint32_t, const void* const* d_in, double* d_out) -> int {
-        RayTablePass rp;
-        rp.origins = static_cast<const double*>(d_in[0]);
-        rp.dirs = static_cast<const double*>(d_in[1]);
-        rp.first = off;
-        return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, rp);
-    };
-    return render_table_chunks(s, s->rays.stage, n, {{origins, 24}, {dirs, 24}}, out, 4 * sizeof(double), host, stream, render);
+// The three table modes: what fills a chunk's pass from the call's parameters and the chunk's arrays on the device.
+static RayTablePass ray_table_pass(const RtRenderParams&, uint64_t off, uint32_t, const void* const* d_in) {
+    RayTablePass rp;
+    rp.first = off;
+    rp.origins = static_cast<const double*>(d_in[0]);
+    rp.dirs = static_cast<const double*>(d_in[1]);
+    return rp;
 }
-
-// ---------------------------------------------------------------------------------------------
-// Irradiance bake (include/rt_mi355.h): the points of the caller, chunked like a ray table
-// ---------------------------------------------------------------------------------------------
-// hits: the points are RtRayHit records on the device (positions / normals unused); records without a surface point are
-// zeroed after the chunk's resolve (k_wf_points_mask).
-template <typename R>
-int bake_irradiance_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
-                          const RtRenderParams& p, double* out, bool host, hipStream_t stream) {
-    auto render = [&](const RtCameraDesc& cam, uint64_t off, uint32_t m, const void* const* d_in, double* d_out) -> int {
-        PointTablePass pp;
-        pp.first = off;
-        if (hits) {
-            const unsigned char* base = reinterpret_cast<const unsigned char*>(hits + off);
-            pp.pos = base + offsetof(RtRayHit, pos);
-            pp.nrm = base + offsetof(RtRayHit, normal);
-            pp.stride = uint32_t(sizeof(RtRayHit));
-        } else {
-            pp.pos = static_cast<const unsigned char*>(d_in[0]);
-            pp.nrm = static_cast<const unsigned char*>(d_in[1]);
-            pp.stride = 24u;
-        }
-        if (int st = render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, pp)) return st;
-        if (hits) {
-            hipLaunchKernelGGL(k_wf_points_mask, dim3((m + 255) / 256), dim3(256), 0, stream,
-                               reinterpret_cast<const unsigned char*>(hits + off) + offsetof(RtRayHit, flags), uint32_t(sizeof(RtRayHit)), m, d_out);
-            HIP_TRY(hipGetLastError());
-        }
-        return RT_OK;
-    };
-    const std::vector<ChunkArray> in = hits ? std::vector<ChunkArray>{} : std::vector<ChunkArray>{{positions, 24}, {normals, 24}};
-    return render_table_chunks(s, s->rays.stage, n, in, out, 4 * sizeof(double), host, stream, render);
+// HITS: d_in[0] is the chunk's first RtRayHit record; else d_in[0] / d_in[1] are its first position / normal.
+template <bool HITS>
+PointTablePass point_table_pass(const RtRenderParams&, uint64_t off, uint32_t, const void* const* d_in) {
+    const HitPoints h = HITS ? hit_points(static_cast<const RtRayHit*>(d_in[0]))
+                             : HitPoints{static_cast<const unsigned char*>(d_in[0]), static_cast<const unsigned char*>(d_in[1]), nullptr, 24u};
+    PointTablePass pp;
+    pp.first = off;
+    pp.pos = h.pos;
+    pp.nrm = h.nrm;
+    pp.stride = h.stride;
+    return pp;
 }
-
-// ---------------------------------------------------------------------------------------------
-// SH probe bake (include/rt_mi355.h): the positions of the caller, chunked like a ray table; 24 B in and
-// 288 B out per probe, which is what the host variant's staging buffer is sized for
-// ---------------------------------------------------------------------------------------------
-template <typename R>
-int bake_probes_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const RtRenderParams& p, double* out, bool host,
-                      hipStream_t stream) {
-    auto render = [&](const RtCameraDesc& cam, uint64_t off, uint32_t, const void* const* d_in, double* d_out) -> int {
-        ProbeTablePass pp;
-        pp.pos = static_cast<const double*>(d_in[0]);
-        pp.first = off;
-        pp.seed = p.seed;
-        pp.S = p.sqrt_spt;
-        pp.f32 = sizeof(R) == 4;
-        return render_wavefront(s, ds, cam, p, 1u, 0u, p.thread_count, d_out, stream, pp);
-    };
-    return render_table_chunks(s, s->rays.stage, n, {{positions, 24}}, out, 36 * sizeof(double), host, stream, render);
+// Records without a surface point are zeroed after the chunk's resolve.
+static int points_mask(const RtRayHit* hits, uint32_t m, double* d_out, hipStream_t stream) {
+    const HitPoints h = hit_points(hits);
+    hipLaunchKernelGGL(k_wf_points_mask, dim3((m + 255) / 256), dim3(256), 0, stream, h.flags, h.stride, m, d_out);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+static ProbeTablePass probe_table_pass(const RtRenderParams& p, uint64_t off, uint32_t, const void* const* d_in) {
+    ProbeTablePass pp;
+    pp.first = off;
+    pp.pos = static_cast<const double*>(d_in[0]);
+    pp.seed = p.seed;
+    pp.S = p.sqrt_spt;
+    pp.f32 = p.precision == RT_PRECISION_F32;
+    return pp;
 }
 
 // Makes sure the scene's tables in the arithmetic of `precision` are on the device (built on first use), then f(tables).
@@ -1881,6 +1872,68 @@ int with_tables(RtScene* s, uint32_t precision, F&& f) {
         return f(*slot);
     };
     return precision == RT_PRECISION_F32 ? go(s->f32) : go(s->f64);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Table modes: the entry points of ray tables, irradiance and probe bakes
+// ---------------------------------------------------------------------------------------------
+// One call of a table mode's entry point `who`.  a / b: the input arrays as the caller passed them (name NULL: the entry point
+// has no such array; each: bytes per entry), out_name / out_each: the same of the output; what / unit: "ray table" / "ray".
+struct TableArray {
+    const void* p;
+    const char* name;
+    size_t each;
+};
+struct TableCall {
+    const char* who;
+    TableArray a, b;
+    const char* out_name;
+    size_t out_each;
+    const char *what, *unit;
+};
+
+// The rules the table modes share, checked before the device is touched.
+static int table_render_check(const RtScene* scene, uint64_t n, const RtRenderParams* params, const void* out, const TableCall& c) {
+    const std::string w = std::string(c.who) + ": ";
+    if (!scene) return set_err(RT_E_INVALID, w + "scene is NULL");
+    if (!params) return set_err(RT_E_INVALID, w + "params is NULL");
+    if (params->sqrt_spt == 0) return set_err(RT_E_INVALID, w + "sqrt_spt must be positive");
+    if (params->thread_count == 0) return set_err(RT_E_INVALID, w + "thread_count must be positive");
+    if (params->precision != RT_PRECISION_F64 && params->precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, w + "precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
+    if (params->n_parts > 1) return set_err(RT_E_INVALID, w + "n_parts > 1: a " + c.what + " has no row partition");
+    if (n >= (1ull << 31)) return set_err(RT_E_INVALID, w + "n must be below 2^31");
+    if (uint64_t(params->sqrt_spt) * params->sqrt_spt * params->thread_count > 0xFFFFFFFFull) return set_err(RT_E_UNSUPPORTED, w + "more than 2^32 samples per " + c.unit + " (sqrt_spt, thread_count)");
+    if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, w + c.what + "s run the wavefront scheduler: pipeline = RT_PIPELINE_MEGAKERNEL is not supported");
+    if (params->pipeline != RT_PIPELINE_AUTO && params->pipeline != RT_PIPELINE_WAVEFRONT) return set_err(RT_E_INVALID, w + "unknown pipeline");
+    if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, w + "max_depth = 0 is not supported");
+    if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, w + c.what + "s have no counting kernels (collect_stats)");
+    if (n == 0) return RT_OK;
+    for (const TableArray* t : {&c.a, &c.b})
+        if (t->name && !t->p) return set_err(RT_E_INVALID, w + t->name + " is NULL");
+    if (!out) return set_err(RT_E_INVALID, w + c.out_name + " is NULL");
+    return RT_OK;
+}
+
+// The checks, the scene's tables in params->precision, then the chunks (render_table_chunks has make_pass and after).  Whoever
+// waits for this render's tail (rt_scene_set_tail_flag) is released at the latest here, errors and early returns included.
+template <typename MakePass, typename After = NoAfter>
+int table_call(const RtScene* scene, uint64_t n, const RtRenderParams* params, double* out, bool host, void* stream, const TableCall& c,
+               MakePass&& make_pass, After&& after = After{}) {
+    const int r = [&]() -> int {
+        if (int st = table_render_check(scene, n, params, out, c)) return st;
+        if (n == 0) return RT_OK;
+        RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
+        HIP_TRY(hipSetDevice(s->device));
+        RtRenderParams p = *params;
+        p.band_rows = p.n_parts = p.part = 0;
+        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+        std::vector<ChunkArray> in;
+        for (const TableArray* t : {&c.a, &c.b})
+            if (t->name) in.push_back({t->p, t->each});
+        return with_tables(s, p.precision, [&](auto& ds) -> int { return render_table_chunks(s, ds, p, n, in, out, c.out_each, host, st, make_pass, after); });
+    }();
+    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
+    return r;
 }
 
 // Argument checks shared by the entry points, then run(scene, tables of `precision` on the device).
@@ -2831,14 +2884,6 @@ static int adaptive_rebuild(RtAccum* a, hipStream_t st) {
     return RT_OK;
 }
 
-static void stats_add(RtRenderStats& total, const RtRenderStats& part, bool first) {
-    if (first) { total = part; return; }
-    total.kernel_ms += part.kernel_ms; total.traversal_kernel_ms += part.traversal_kernel_ms;
-    total.prims_kernel_ms += part.prims_kernel_ms; total.shade_kernel_ms += part.shade_kernel_ms;
-    total.n_launches += part.n_launches; total.n_iterations += part.n_iterations; total.samples += part.samples;
-    total.n_replica_groups += part.n_replica_groups; total.n_tail_compactions += part.n_tail_compactions;
-}
-
 // rt_accum_render of an adaptive accumulator: segments that end at the decision points, a decision after each.
 static int accum_render_adaptive(RtAccum* acc, uint32_t n_replicas, RtRenderParams p, void* stream) {
     using namespace rt;
@@ -3449,109 +3494,42 @@ int rt_light_mix(int device, const double* groups, uint32_t n_groups, uint32_t w
     return RT_OK;
 }
 
-// ---- Renders along ray tables, irradiance and probe bakes --------------------------------------------------------------------------------
-// The rules the two share, checked before the device is touched; a/b/out name the arrays in messages (a, b NULL: no such array).
-static int table_render_check(const RtScene* scene, uint64_t n, const void* a, const char* a_name, const void* b, const char* b_name,
-                              const RtRenderParams* params, const void* out, const char* out_name, const std::string& w, const char* what, const char* unit) {
-    using namespace rt;
-    if (!scene) return set_err(RT_E_INVALID, w + "scene is NULL");
-    if (!params) return set_err(RT_E_INVALID, w + "params is NULL");
-    if (params->sqrt_spt == 0) return set_err(RT_E_INVALID, w + "sqrt_spt must be positive");
-    if (params->thread_count == 0) return set_err(RT_E_INVALID, w + "thread_count must be positive");
-    if (params->precision != RT_PRECISION_F64 && params->precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, w + "precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
-    if (params->n_parts > 1) return set_err(RT_E_INVALID, w + "n_parts > 1: a " + what + " has no row partition");
-    if (n >= (1ull << 31)) return set_err(RT_E_INVALID, w + "n must be below 2^31");
-    if (uint64_t(params->sqrt_spt) * params->sqrt_spt * params->thread_count > 0xFFFFFFFFull) return set_err(RT_E_UNSUPPORTED, w + "more than 2^32 samples per " + unit + " (sqrt_spt, thread_count)");
-    if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, w + what + "s run the wavefront scheduler: pipeline = RT_PIPELINE_MEGAKERNEL is not supported");
-    if (params->pipeline != RT_PIPELINE_AUTO && params->pipeline != RT_PIPELINE_WAVEFRONT) return set_err(RT_E_INVALID, w + "unknown pipeline");
-    if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, w + "max_depth = 0 is not supported");
-    if (params->collect_stats) return set_err(RT_E_UNSUPPORTED, w + what + "s have no counting kernels (collect_stats)");
-    if (n == 0) return RT_OK;
-    if (a_name && !a) return set_err(RT_E_INVALID, w + a_name + " is NULL");
-    if (b_name && !b) return set_err(RT_E_INVALID, w + b_name + " is NULL");
-    if (!out) return set_err(RT_E_INVALID, w + out_name + " is NULL");
-    return RT_OK;
-}
-
-static int render_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params,
-                            double* out, bool host, void* stream, const char* who) {
-    using namespace rt;
-    if (int st = table_render_check(scene, n, origins, "origins", dirs, "dirs", params, out, "rgba_out", std::string(who) + ": ", "ray table", "ray")) return st;
-    if (n == 0) return RT_OK;
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    RtRenderParams p = *params;
-    p.band_rows = p.n_parts = p.part = 0;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    return with_tables(s, p.precision, [&](auto& ds) -> int { return render_rays_typed(s, ds, n, origins, dirs, p, out, host, st); });
-}
-
+// ---- Renders along ray tables, irradiance and probe bakes: rt::table_call with the call's description and the mode's pass ----
 int rt_render_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const RtRenderParams* params, double* rgba_out) {
-    const int r = render_rays_impl(scene, n, origins, dirs, params, rgba_out, true, nullptr, "rt_render_rays");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
-    return r;
+    return rt::table_call(scene, n, params, rgba_out, true, nullptr,
+                          {"rt_render_rays", {origins, "origins", 24}, {dirs, "dirs", 24}, "rgba_out", 32, "ray table", "ray"}, rt::ray_table_pass);
 }
 int rt_render_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const RtRenderParams* params,
                           double* d_rgba_out, void* stream) {
-    const int r = render_rays_impl(scene, n, d_origins, d_dirs, params, d_rgba_out, false, stream, "rt_render_rays_device");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
-    return r;
-}
-
-static int bake_irradiance_impl(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits, bool by_hits,
-                                const RtRenderParams* params, double* out, bool host, void* stream, const char* who) {
-    using namespace rt;
-    const int chk = by_hits ? table_render_check(scene, n, hits, "hits", nullptr, nullptr, params, out, "rgba_out", std::string(who) + ": ", "point table", "point")
-                            : table_render_check(scene, n, positions, "positions", normals, "normals", params, out, "rgba_out", std::string(who) + ": ", "point table", "point");
-    if (chk != RT_OK || n == 0) return chk;
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    RtRenderParams p = *params;
-    p.band_rows = p.n_parts = p.part = 0;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    return with_tables(s, p.precision, [&](auto& ds) -> int { return bake_irradiance_typed(s, ds, n, positions, normals, hits, p, out, host, st); });
+    return rt::table_call(scene, n, params, d_rgba_out, false, stream,
+                          {"rt_render_rays_device", {d_origins, "origins", 24}, {d_dirs, "dirs", 24}, "rgba_out", 32, "ray table", "ray"}, rt::ray_table_pass);
 }
 
 int rt_bake_irradiance(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRenderParams* params, double* rgba_out) {
-    const int r = bake_irradiance_impl(scene, n, positions, normals, nullptr, false, params, rgba_out, true, nullptr, "rt_bake_irradiance");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
-    return r;
+    return rt::table_call(scene, n, params, rgba_out, true, nullptr,
+                          {"rt_bake_irradiance", {positions, "positions", 24}, {normals, "normals", 24}, "rgba_out", 32, "point table", "point"},
+                          rt::point_table_pass<false>);
 }
 int rt_bake_irradiance_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals, const RtRenderParams* params,
                               double* d_rgba_out, void* stream) {
-    const int r = bake_irradiance_impl(scene, n, d_positions, d_normals, nullptr, false, params, d_rgba_out, false, stream, "rt_bake_irradiance_device");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
-    return r;
+    return rt::table_call(scene, n, params, d_rgba_out, false, stream,
+                          {"rt_bake_irradiance_device", {d_positions, "positions", 24}, {d_normals, "normals", 24}, "rgba_out", 32, "point table", "point"},
+                          rt::point_table_pass<false>);
 }
 int rt_bake_irradiance_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtRenderParams* params, double* d_rgba_out,
                                    void* stream) {
-    const int r = bake_irradiance_impl(scene, n, nullptr, nullptr, d_hits, true, params, d_rgba_out, false, stream, "rt_bake_irradiance_hits_device");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
-    return r;
-}
-
-static int bake_probes_impl(const RtScene* scene, uint64_t n, const double* positions, const RtRenderParams* params, double* out, bool host, void* stream,
-                            const char* who) {
-    using namespace rt;
-    const int chk = table_render_check(scene, n, positions, "positions", nullptr, nullptr, params, out, "sh_out", std::string(who) + ": ", "probe table", "probe");
-    if (chk != RT_OK || n == 0) return chk;
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    RtRenderParams p = *params;
-    p.band_rows = p.n_parts = p.part = 0;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    return with_tables(s, p.precision, [&](auto& ds) -> int { return bake_probes_typed(s, ds, n, positions, p, out, host, st); });
+    return rt::table_call(scene, n, params, d_rgba_out, false, stream,
+                          {"rt_bake_irradiance_hits_device", {d_hits, "hits", sizeof(RtRayHit)}, {}, "rgba_out", 32, "point table", "point"},
+                          rt::point_table_pass<true>, [=](uint64_t off, uint32_t m, double* d_out, hipStream_t st) { return rt::points_mask(d_hits + off, m, d_out, st); });
 }
 
 int rt_bake_probes(const RtScene* scene, uint64_t n, const double* positions, const RtRenderParams* params, double* sh_out) {
-    const int r = bake_probes_impl(scene, n, positions, params, sh_out, true, nullptr, "rt_bake_probes");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device
-    return r;
+    return rt::table_call(scene, n, params, sh_out, true, nullptr,
+                          {"rt_bake_probes", {positions, "positions", 24}, {}, "sh_out", 288, "probe table", "probe"}, rt::probe_table_pass);
 }
 int rt_bake_probes_device(const RtScene* scene, uint64_t n, const double* d_positions, const RtRenderParams* params, double* d_sh_out, void* stream) {
-    const int r = bake_probes_impl(scene, n, d_positions, params, d_sh_out, false, stream, "rt_bake_probes_device");
-    if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
-    return r;
+    return rt::table_call(scene, n, params, d_sh_out, false, stream,
+                          {"rt_bake_probes_device", {d_positions, "positions", 24}, {}, "sh_out", 288, "probe table", "probe"}, rt::probe_table_pass);
 }
 
 int rt_sh_irradiance_device(int device, const double* d_sh, uint64_t n_probes, const uint32_t* d_probe, const double* d_normals, uint64_t m,

@@ -244,11 +244,12 @@ RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, co
     uint64_t rem, pix, px64;
     const uint32_t tid_local = uint32_t(div_by(s, grp.per_replica, grp.inv_per_replica, rem));
     const uint32_t st = uint32_t(div_by(rem, grp.npix, grp.inv_npix, pix));
+    // A table mode: the stream of entry i is the stream of pixel i, keyed by the entry's index in the caller's whole table.
+    if constexpr (G::kRays || G::kPoints || G::kProbes) rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
     if constexpr (G::kRays) {
-        // The stream of ray i is the stream of pixel i: keyed alike, and a camera's two jitter draws are made and dropped, so
-        // that the path's own draws are the ones a frame's sample would make.  No camera arithmetic, no row partition.  The
-        // six doubles are loaded last: they live from here to the caller's pool stores and no longer.
-        rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
+        // A camera's two jitter draws are made and dropped, so that the path's own draws are the ones a frame's sample would
+        // make.  No camera arithmetic, no row partition.  The six doubles are loaded last: they live from here to the caller's
+        // pool stores and no longer.
         rng.next();
         rng.next();
         const uint32_t at3 = uint32_t(pix) * 3u;  // the driver keeps a chunk below 2^28 rays
@@ -257,15 +258,10 @@ RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, co
         return;
     }
     if constexpr (G::kPoints) {
-        // The stream of point i is the stream of pixel i, and the two draws a camera spends on its jitter are the hemisphere
-        // sample: stratified over the S x S cells as the jitter is, so the path's own first draw is the third of the stream.
-        rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
-        const uint32_t S = cam.sqrt_spt;
-        const uint32_t sy = st / S, sx = st - sy * S;
-        const R r1 = rng_uniform<R>(rng);
-        const R r2 = rng_uniform<R>(rng);
-        const R u1 = (R(sx) + r1) * cam.inv_sqrt_spt;
-        const R u2 = (R(sy) + r2) * cam.inv_sqrt_spt;
+        // The two draws a camera spends on its jitter are the hemisphere sample: stratified over the S x S cells as the jitter
+        // is, so the path's own first draw is the third of the stream.
+        R u1, u2;
+        wf_strat_uniforms<R>(rng, st, cam.sqrt_spt, cam.inv_sqrt_spt, u1, u2);
         const uint64_t at = pix * grp.stride;
         const WfPointRay<R> ray = wf_point_ray<R>(reinterpret_cast<const double*>(grp.pos + at), reinterpret_cast<const double*>(grp.nrm + at), u1, u2);
         o = ray.o;
@@ -273,8 +269,7 @@ RT_DEV void wf_new_sample(uint64_t s, const G& grp, const CameraView<R>& cam, co
         return;
     }
     if constexpr (G::kProbes) {
-        // As for points: the stream of probe i is the stream of pixel i and the camera's two jitter draws are the sphere sample.
-        rng.key(prm.seed, grp.tid0 + tid_local, grp.first + pix, st);
+        // As for points: the camera's two jitter draws are the sphere sample.
         R u1, u2;
         wf_strat_uniforms<R>(rng, st, cam.sqrt_spt, cam.inv_sqrt_spt, u1, u2);
         const WfPointRay<R> ray = wf_probe_ray<R>(grp.pos + uint32_t(pix) * 3u, u1, u2);  // the driver keeps a chunk below 2^28 probes

@@ -2,7 +2,7 @@
 header's offsets, `rtrace --irradiance` is checked while the command line is read, the reference the GPU tests hold the
 kernels to (tests/bake_irradiance_ref.py) draws what it says and is worth testing against, and the device's own code for a
 sample's first ray - the WfGroupPoints branch of wf_new_sample, built for the host as a stand-alone program with the address
-and undefined-behaviour sanitizers (tools/point_ray_host.cpp) - gives the reference's (o, d') bit for bit."""
+and undefined-behaviour sanitizers (tools/table_ray_host.cpp) - gives the reference's (o, d') bit for bit."""
 import ctypes as C
 import inspect
 import os
@@ -154,12 +154,12 @@ def test_reference_is_keyed_by_the_global_index():
 # ---- the device's code for the first ray, on the host, under sanitizers ----
 @pytest.mark.parametrize("stride", [24, 96])
 def test_device_code_on_the_host_gives_the_reference_rays(tmp_path, stride):
-    """tools/point_ray_host.cpp: wf_new_sample<double, WfGroupPoints<double>> compiled for the host (sanitizers on the host side
+    """tools/table_ray_host.cpp: wf_new_sample<double, WfGroupPoints<double>> compiled for the host (sanitizers on the host side
     only; the program touches no GPU).  Points: cornell's and two_meshes', as plain arrays and as hit records, at index 5 onwards."""
-    exe = tmp_path / "point_ray_host"
+    exe = tmp_path / "table_ray_host"
     cmd = [rt_build.hipcc_path(), "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-ffp-contract=off",
            "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I" + os.path.join(REPO, "include"), "-o", str(exe), os.path.join(REPO, "tools", "point_ray_host.cpp")]
+           "-I" + os.path.join(REPO, "include"), "-o", str(exe), os.path.join(REPO, "tools", "table_ray_host.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     first = 5

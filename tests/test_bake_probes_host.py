@@ -3,7 +3,7 @@
 (tests/bake_probes_ref.py) draws what it says and is worth testing against, api.probe_grid is the grid numpy gives, and the
 device's own code for a sample's first ray and SH weights - the WfGroupProbes branch of wf_new_sample and what k_wf_resolve_sh
 evaluates per sample, built for the host as a stand-alone program with the address and undefined-behaviour sanitizers
-(tools/probe_ray_host.cpp) - gives the reference's (o, d') and the nine Y_k bit for bit."""
+(tools/table_ray_host.cpp) - gives the reference's (o, d') and the nine Y_k bit for bit."""
 import ctypes as C
 import inspect
 import os
@@ -172,13 +172,13 @@ def test_reference_is_keyed_by_the_global_index():
 
 # ---- the device's code for the first ray and the SH weights, on the host, under sanitizers ----
 def test_device_code_on_the_host_gives_the_reference_rays_and_basis(tmp_path):
-    """tools/probe_ray_host.cpp: wf_new_sample<double, WfGroupProbes<double>> and the per-sample arithmetic of k_wf_resolve_sh
+    """tools/table_ray_host.cpp: wf_new_sample<double, WfGroupProbes<double>> and the per-sample arithmetic of k_wf_resolve_sh
     compiled for the host (sanitizers on the host side only; the program touches no GPU).  Probes: cornell's and two_meshes', at
     index 5 onwards."""
-    exe = tmp_path / "probe_ray_host"
+    exe = tmp_path / "table_ray_host"
     cmd = [rt_build.hipcc_path(), "--offload-arch=gfx950", "-std=c++17", "-O1", "-g", "-ffp-contract=off",
            "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
-           "-I" + os.path.join(REPO, "include"), "-o", str(exe), os.path.join(REPO, "tools", "probe_ray_host.cpp")]
+           "-I" + os.path.join(REPO, "include"), "-o", str(exe), os.path.join(REPO, "tools", "table_ray_host.cpp")]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     first = 5
