@@ -330,6 +330,21 @@ int rt_debug_trace_sample(const RtScene* scene, const RtCameraDesc* camera, cons
  * after each.  The two must agree bit for bit. */
 int rt_debug_fuzzy_reflection(int device, uint32_t n, const double* reflected, const double* fuzz, const uint64_t* state, double* out, uint64_t* state_out);
 
+/* Diagnostic probe (tests): ONE path vertex for each of n rays, one ray per lane - what one loop trip of the megakernel does
+ * to a path with throughput (1,1,1) and radiance 0: the closest-hit search from t_min = 0.001 (with the volumes' free-flight
+ * draws), then the shade step, called as the render kernels call them.  rays[6 n]: origin and direction; states[n]: the
+ * generator's 64-bit state before the vertex; params: precision and light_bias (and the background) are read.
+ * variant 0: the kernel variant the render picks for this scene; 1: the full variant (texture interpreter, volumes, nested
+ * light lists); 2: the simple variant, RT_E_INVALID on a scene that needs the full one.
+ * out[RT_SHADE_RAYS_STRIDE n], widened to double: [0] t; [1..3] hit position; [4..6] shading normal (after a normal map);
+ * [7] u; [8] v ((u, v) stay 0 where no texture of the material reads them); [9] front face; [10] material (-1: a miss);
+ * [11] scene-program op type (-1: a miss); [12..14] tex_a; [15] tex_b; [16] 1 if the path continues; [17..19] the
+ * continuation direction as computed (not normalised; 0 unless it continues); [20..22] the throughput after the vertex;
+ * [23..25] the radiance; [26] the number of draws the search made; [27] 0.  state_out[n]: the generator after the vertex. */
+#define RT_SHADE_RAYS_STRIDE 28
+int rt_debug_shade_rays(const RtScene* scene, const RtRenderParams* params, uint32_t variant, uint32_t n, const double* rays,
+                        const uint64_t* states, double* out, uint64_t* state_out);
+
 /* Diagnostic (host only, needs no device): compiles `desc` like rt_scene_create and reports how the scene
  * compiler classified it.  RT_SCENE_INFO_ZERO_WEIGHT_STOP: the light set cannot give an infinite or NaN weight,
  * so paths whose weight is exactly 0 are ended early (otherwise they are traced to the end like

@@ -104,6 +104,7 @@ struct Counters {
 };
 struct Rng {
     uint64_t s = 0;
+    bool draws24 = false;  // uniform() keeps the top 24 bits of a draw, like the device's rng_uniform<float> (oracle_shade_rays)
     Counters cnt;  // the rng object is threaded through every test() like in the reference
     static uint64_t mix(uint64_t z) {
         z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -120,7 +121,10 @@ struct Rng {
         s += 0x9E3779B97F4A7C15ull;
         return mix(s);
     }
-    double uniform() { return double(next() >> 11) * (1.0 / 9007199254740992.0); }  // U and R
+    double uniform() {  // U and R
+        if (draws24) return double(next() >> 40) * (1.0 / 16777216.0);
+        return double(next() >> 11) * (1.0 / 9007199254740992.0);
+    }
     double normal() {                                                               // N
         double u1 = uniform();
         double u2 = uniform();
@@ -394,13 +398,15 @@ struct MixPDF : PDF {  // mix.rs:23-36
     const PDF* first;
     const PDF* second;
     double mix;
+    mutable bool took_second = false;  // which branch generate() took (reported by oracle_shade_rays)
     double value(const Vec4& dir, Rng& rng) const override {
         double first_val = first->value(dir, rng);
         double second_val = second->value(dir, rng);
         return first_val * (1.0 - mix) + second_val * mix;
     }
     Vec4 generate(Rng& rng) const override {
-        if (rng.uniform() < mix) return second->generate(rng);
+        took_second = rng.uniform() < mix;
+        if (took_second) return second->generate(rng);
         return first->generate(rng);
     }
 };
@@ -418,6 +424,9 @@ struct Material {  // material.rs:38-47
     virtual ScatterResult scatter(const Ray& ray, const HitRecord& hit, Rng& rng) const = 0;
     virtual Vec4 emit(const HitRecord&) const { return vec(0.0, 0.0, 0.0); }
     virtual double scattering_pdf(const Ray& ray_in, const Ray& scattered, const HitRecord& hit) const = 0;
+    // reporting only (oracle_shade_rays): the normal the material shades with, its colour and float texture at the hit
+    virtual Vec4 shading_normal(const HitRecord& hit) const { return hit.normal; }
+    virtual void textures(const HitRecord&, Vec4& a, double& b) const { a = vec(0, 0, 0); b = 0.0; }
 };
 using ColorTex = std::shared_ptr<Sampler<Vec4>>;
 using FloatTex = std::shared_ptr<Sampler<double>>;
@@ -433,6 +442,7 @@ struct LambertianDiffuse : Material {  // lambertian.rs:25-43
         double cos_theta = dot(hit.normal, to_unit(scattered.dir));
         return cos_theta < 0.0 ? 0.0 : cos_theta / PI;
     }
+    void textures(const HitRecord& hit, Vec4& a, double& b) const override { a = albedo->sample(hit.u, hit.v, hit.hit_pos); b = 0.0; }
 };
 struct Metal : Material {  // metal.rs:28-48
     ColorTex albedo;
@@ -446,6 +456,10 @@ struct Metal : Material {  // metal.rs:28-48
         return {ScatterKind::Absorbed, vec(0, 0, 0), nullptr, {}};
     }
     double scattering_pdf(const Ray&, const Ray&, const HitRecord&) const override { return 1.0; }
+    void textures(const HitRecord& hit, Vec4& a, double& b) const override {
+        a = albedo->sample(hit.u, hit.v, hit.hit_pos);
+        b = roughness->sample(hit.u, hit.v, hit.hit_pos);
+    }
 };
 struct Dielectric : Material {  // dielectric.rs:29-58
     double ior;
@@ -497,6 +511,11 @@ struct Glossy : Material {  // glossy.rs:54-95
         double cos_theta = dot(normal, to_unit(scattered.dir));
         return cos_theta < 0.0 ? 0.0 : cos_theta / PI;
     }
+    Vec4 shading_normal(const HitRecord& hit) const override { return mapped_normal(normal_map, hit); }
+    void textures(const HitRecord& hit, Vec4& a, double& b) const override {
+        a = albedo->sample(hit.u, hit.v, hit.hit_pos);
+        b = roughness->sample(hit.u, hit.v, hit.hit_pos);
+    }
 };
 struct Emissive : Material {  // emissive.rs:24-38
     ColorTex emission_map;
@@ -507,6 +526,7 @@ struct Emissive : Material {  // emissive.rs:24-38
         return hit.front_face ? emission_map->sample(hit.u, hit.v, hit.hit_pos) : vec(0.0, 0.0, 0.0);
     }
     double scattering_pdf(const Ray&, const Ray&, const HitRecord&) const override { return 1.0; }
+    void textures(const HitRecord& hit, Vec4& a, double& b) const override { a = emission_map->sample(hit.u, hit.v, hit.hit_pos); b = 0.0; }
 };
 struct Isotropic : Material {  // isotropic.rs:25-37
     ColorTex albedo;
@@ -516,6 +536,7 @@ struct Isotropic : Material {  // isotropic.rs:25-37
         return r;
     }
     double scattering_pdf(const Ray&, const Ray&, const HitRecord&) const override { return 1.0 / (4.0 * PI); }
+    void textures(const HitRecord& hit, Vec4& a, double& b) const override { a = albedo->sample(hit.u, hit.v, hit.hit_pos); b = 0.0; }
 };
 struct NormalDebug : Material {  // normal_debug.rs:42-52
     ColorTex normal_map;
@@ -523,6 +544,7 @@ struct NormalDebug : Material {  // normal_debug.rs:42-52
         return {ScatterKind::Emissive, vec(0, 0, 0), nullptr, {}};
     }
     Vec4 emit(const HitRecord& hit) const override { return mapped_normal(normal_map, hit) * 0.5 + vec(0.5, 0.5, 0.5); }
+    Vec4 shading_normal(const HitRecord& hit) const override { return mapped_normal(normal_map, hit); }
     double scattering_pdf(const Ray&, const Ray&, const HitRecord&) const override { return 1.0; }
 };
 
@@ -1304,46 +1326,71 @@ struct Camera {
         Vec4 ray_direction = pixel_sample - ray_origin;
         return Ray(ray_origin, ray_direction);
     }
+    // One level of ray_color (camera.rs:282-332) without the recursion: the closest hit, emit, scatter and, for
+    // ScatteredWithPDF, the MixPDF generate / value / scattering_pdf lines.  ray_color and oracle_shade_rays share it.
+    struct Vertex {
+        bool hit = false;
+        HitRecord rec;
+        Vec4 from_emission;
+        ScatterKind kind = ScatterKind::Absorbed;
+        Vec4 attenuation;
+        Ray scattered;                 // WithPDF and WithRay
+        double pdf = 0.0, scattering_pdf = 0.0;  // WithPDF
+        bool from_light = false;       // WithPDF: MixPDF::generate took the light list
+        uint64_t state_after_test = 0; // the generator behind object->test (the volumes' free-flight draws)
+    };
+    void vertex(const Ray& ray, const Hit* object, HittablePDF& lights_pdf, Rng& rng, Vertex& vx) const {
+        rng.cnt.rays++;
+        vx.hit = object->test(ray, {0.001, INF}, rng, vx.rec);
+        vx.state_after_test = rng.s;
+        if (!vx.hit) return;
+        const HitRecord& hit = vx.rec;
+        vx.from_emission = hit.material->emit(hit);
+        ScatterResult sr = hit.material->scatter(ray, hit, rng);
+        vx.kind = sr.kind;
+        vx.attenuation = sr.attenuation;
+        if (sr.kind == ScatterKind::WithPDF) {
+            lights_pdf.origin = hit.hit_pos;
+            MixPDF mix_pdf;
+            mix_pdf.first = sr.pdf.get();
+            mix_pdf.second = &lights_pdf;
+            mix_pdf.mix = p.light_bias;
+            vx.scattered = Ray(hit.hit_pos, mix_pdf.generate(rng));
+            vx.from_light = mix_pdf.took_second;
+            vx.pdf = mix_pdf.value(vx.scattered.dir, rng);
+            vx.scattering_pdf = hit.material->scattering_pdf(ray, vx.scattered, hit);
+        } else if (sr.kind == ScatterKind::WithRay) {
+            vx.scattered = sr.scattered;
+        }
+    }
     Vec4 ray_color(const Ray& ray, const Hit* object, HittablePDF& lights_pdf, size_t depth, Rng& rng) const {  // camera.rs:282-332
         if (depth == 0) return vec(0.0, 0.0, 0.0);
-        rng.cnt.rays++;
-        HitRecord hit;
-        if (object->test(ray, {0.001, INF}, rng, hit)) {
-            Vec4 from_emission = hit.material->emit(hit);
-            ScatterResult sr = hit.material->scatter(ray, hit, rng);
-            size_t trace_at = 0;
+        Vertex vx;
+        vertex(ray, object, lights_pdf, rng, vx);
+        if (vx.hit) {
+            const HitRecord& hit = vx.rec;
             if (g_trace) {
-                trace_at = g_trace->size();
                 g_trace->insert(g_trace->end(), {hit.t, hit.hit_pos[0], hit.hit_pos[1], hit.hit_pos[2],
-                                                 double(hit.material_index), double(int(sr.kind)), 0.0, 0.0,
+                                                 double(hit.material_index), double(int(vx.kind)), vx.pdf, vx.scattering_pdf,
                                                  hit.normal[0], hit.normal[1], hit.normal[2],
                                                  ray.origin[0], ray.origin[1], ray.origin[2], ray.dir[0], ray.dir[1]});
                 g_trace->push_back(ray.dir[2]);
             }
-            switch (sr.kind) {
+            switch (vx.kind) {
                 case ScatterKind::WithPDF: {
-                    lights_pdf.origin = hit.hit_pos;
-                    MixPDF mix_pdf;
-                    mix_pdf.first = sr.pdf.get();
-                    mix_pdf.second = &lights_pdf;
-                    mix_pdf.mix = p.light_bias;
-                    Ray scattered(hit.hit_pos, mix_pdf.generate(rng));
-                    double pdf = mix_pdf.value(scattered.dir, rng);
-                    double scattering_pdf = hit.material->scattering_pdf(ray, scattered, hit);
-                    if (g_trace) { (*g_trace)[trace_at + 6] = pdf; (*g_trace)[trace_at + 7] = scattering_pdf; }
-                    Vec4 scatter_color = ray_color(scattered, object, lights_pdf, depth - 1, rng);
-                    Vec4 from_scatter = (scatter_color * sr.attenuation * scattering_pdf) / pdf;
-                    return from_emission + from_scatter;
+                    Vec4 scatter_color = ray_color(vx.scattered, object, lights_pdf, depth - 1, rng);
+                    Vec4 from_scatter = (scatter_color * vx.attenuation * vx.scattering_pdf) / vx.pdf;
+                    return vx.from_emission + from_scatter;
                 }
                 case ScatterKind::WithRay: {
-                    Vec4 scatter_color = ray_color(sr.scattered, object, lights_pdf, depth - 1, rng);
-                    Vec4 from_scatter = scatter_color * sr.attenuation;
-                    return from_emission + from_scatter;
+                    Vec4 scatter_color = ray_color(vx.scattered, object, lights_pdf, depth - 1, rng);
+                    Vec4 from_scatter = scatter_color * vx.attenuation;
+                    return vx.from_emission + from_scatter;
                 }
                 case ScatterKind::Absorbed:
                     return vec(0.0, 0.0, 0.0);
                 case ScatterKind::Emissive:
-                    return from_emission;
+                    return vx.from_emission;
             }
         }
         if (g_trace) g_trace->insert(g_trace->end(), {INF, 0, 0, 0, -1, -1, 0, 0, 0, 0, 0,
@@ -1596,6 +1643,67 @@ int oracle_trace_sample(const RtSceneDesc* scene, const RtCameraDesc* camera, co
     for (uint32_t i = 0; i < n && i < max_bounces; i++)
         for (int k = 0; k < 17; k++) trace_out[17 * i + k] = trace[17 * i + k];
     return int(n);
+}
+
+int oracle_shade_rays(const RtSceneDesc* scene, const RtRenderParams* params, uint32_t n, const double* rays,
+                      const uint64_t* states, int draws24, double* out, uint64_t* state_out) {
+    g_err.clear();
+    if (!scene || !params || !rays || !states || !out || !state_out) { g_err = "NULL argument"; return RT_E_INVALID; }
+    auto world = build_world(scene);  // once for the whole batch
+    if (!world) return RT_E_INVALID;
+    RtCameraDesc no_camera{};
+    Camera cam(no_camera, *params);
+    HittablePDF lights_pdf;
+    lights_pdf.object = world->lights;
+    lights_pdf.origin = point(0.0, 0.0, 0.0);
+    const uint64_t inv_step = 0xF1DE83E19937733Dull;  // the inverse of Rng::next's increment modulo 2^64
+    for (uint32_t i = 0; i < n; i++) {
+        const double* r = rays + 6 * size_t(i);
+        double* o = out + ORACLE_SHADE_STRIDE * size_t(i);
+        for (int k = 0; k < ORACLE_SHADE_STRIDE; k++) o[k] = 0.0;
+        Rng rng;
+        rng.s = states[i];
+        rng.draws24 = draws24 != 0;
+        Ray ray(point(r[0], r[1], r[2]), vec(r[3], r[4], r[5]));
+        Camera::Vertex vx;
+        cam.vertex(ray, world->world, lights_pdf, rng, vx);
+        state_out[i] = rng.s;
+        o[26] = double((vx.state_after_test - states[i]) * inv_step);  // draws of object->test
+        Vec4 weight = vec(1.0, 1.0, 1.0), radiance = vec(0.0, 0.0, 0.0);
+        if (!vx.hit) {
+            o[0] = INF; o[10] = -1.0; o[11] = double(ORACLE_SHADE_BACKGROUND);
+            radiance = cam.background;
+        } else {
+            const HitRecord& h = vx.rec;
+            Vec4 sn = h.material->shading_normal(h), ta;
+            double tb;
+            h.material->textures(h, ta, tb);
+            o[0] = h.t;
+            for (int k = 0; k < 3; k++) { o[1 + k] = h.hit_pos[k]; o[4 + k] = sn[k]; o[12 + k] = ta[k]; }
+            o[7] = h.u; o[8] = h.v; o[9] = h.front_face ? 1.0 : 0.0; o[10] = double(h.material_index); o[15] = tb;
+            int klass = ORACLE_SHADE_ABSORBED;
+            switch (vx.kind) {
+                case ScatterKind::Emissive: klass = ORACLE_SHADE_EMITTED; radiance = vx.from_emission; break;
+                case ScatterKind::Absorbed: break;
+                case ScatterKind::WithRay:
+                    klass = dot(vx.scattered.dir, sn) < 0.0 ? ORACLE_SHADE_REFRACT : ORACLE_SHADE_REFLECT;
+                    weight = vx.attenuation;
+                    break;
+                case ScatterKind::WithPDF:
+                    klass = dynamic_cast<const Isotropic*>(h.material) ? ORACLE_SHADE_VOLUME
+                                                                       : (vx.from_light ? ORACLE_SHADE_PDF_LIGHT : ORACLE_SHADE_PDF_MATERIAL);
+                    weight = (vx.attenuation * vx.scattering_pdf) / vx.pdf;  // the factor of camera.rs:312
+                    break;
+            }
+            o[11] = double(klass);
+            if (vx.kind == ScatterKind::WithRay || vx.kind == ScatterKind::WithPDF) {
+                o[16] = 1.0;
+                for (int k = 0; k < 3; k++) o[17 + k] = vx.scattered.dir[k];
+            }
+        }
+        for (int k = 0; k < 3; k++) { o[20 + k] = weight[k]; o[23 + k] = radiance[k]; }
+    }
+    return RT_OK;
 }
 
 void oracle_get_ray(const RtCameraDesc* camera, const RtRenderParams* params, uint32_t tid, uint32_t x, uint32_t y,

@@ -89,6 +89,20 @@ int oracle_trace_sample(const RtSceneDesc* scene, const RtCameraDesc* camera, co
                         uint32_t tid, uint32_t x, uint32_t y, uint32_t sx, uint32_t sy, double* rgb_out,
                         double* trace_out, uint32_t max_bounces);
 
+/* ONE level of ray_color for each of n rays (rays[6n]: origin, direction), the world built once for the batch: object->test,
+ * emit, scatter and, for ScatteredWithPDF, the MixPDF generate / value / scattering_pdf lines - the code ray_color itself runs.
+ * Ray i starts from a generator whose state is states[i]; state_out[i] is the state behind the vertex.  draws24 != 0: every
+ * uniform draw keeps its top 24 bits only, like the device's f32 draws.  params: light_bias and the background are read.
+ * out: ORACLE_SHADE_STRIDE doubles per ray, the layout of rt_debug_shade_rays (include/rt_mi355.h) except slot 11, which
+ * holds the outcome class below.  continues (slot 16) is 1 for a scattered ray, whatever its weight. */
+#define ORACLE_SHADE_STRIDE 28
+enum {
+    ORACLE_SHADE_BACKGROUND = 0, ORACLE_SHADE_EMITTED = 1, ORACLE_SHADE_ABSORBED = 2, ORACLE_SHADE_REFLECT = 3,
+    ORACLE_SHADE_REFRACT = 4, ORACLE_SHADE_PDF_LIGHT = 5, ORACLE_SHADE_PDF_MATERIAL = 6, ORACLE_SHADE_VOLUME = 7
+};
+int oracle_shade_rays(const RtSceneDesc* scene, const RtRenderParams* params, uint32_t n, const double* rays,
+                      const uint64_t* states, int draws24, double* out, uint64_t* state_out);
+
 const char* oracle_last_error(void);
 
 #ifdef __cplusplus

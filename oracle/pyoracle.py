@@ -76,6 +76,9 @@ def load() -> C.CDLL:
                                             C.POINTER(api.RtRenderParams), C.c_uint32, C.c_uint32, C.c_uint32,
                                             C.c_uint32, C.c_uint32, dp, dp, C.c_uint32]
         lib.oracle_trace_sample.restype = C.c_int
+        lib.oracle_shade_rays.argtypes = [C.POINTER(api.RtSceneDesc), C.POINTER(api.RtRenderParams), C.c_uint32, C.c_void_p,
+                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        lib.oracle_shade_rays.restype = C.c_int
         lib.oracle_last_error.argtypes = []
         lib.oracle_last_error.restype = C.c_char_p
         _lib = lib
@@ -174,6 +177,27 @@ def trace_sample(desc, camera, params, tid, x, y, sx, sy, max_bounces=64):
     if n < 0:
         raise api.RtError(n, lib.oracle_last_error().decode())
     return np.array(list(rgb)), np.array(list(tr)).reshape(max_bounces, 17)[:min(n, max_bounces)]
+
+
+SHADE_STRIDE = 28
+SHADE_CLASSES = ("background", "emitted", "absorbed", "reflect", "refract", "pdf_light", "pdf_material", "volume")
+
+
+def shade_rays(desc, params, origins, dirs, states, draws24=False):
+    """One level of ray_color per ray, the world built once: (out[n, 28], state_out[n]); see oracle.h oracle_shade_rays."""
+    lib = load()
+    rays = np.ascontiguousarray(np.concatenate([np.asarray(origins, dtype=np.float64).reshape(-1, 3),
+                                                np.asarray(dirs, dtype=np.float64).reshape(-1, 3)], axis=1))
+    st_in = np.ascontiguousarray(states, dtype=np.uint64)
+    n = len(rays)
+    assert len(st_in) == n
+    out = np.zeros((n, SHADE_STRIDE), dtype=np.float64)
+    st_out = np.zeros(n, dtype=np.uint64)
+    r = lib.oracle_shade_rays(desc, C.byref(params), n, rays.ctypes.data, st_in.ctypes.data, int(bool(draws24)), out.ctypes.data,
+                              st_out.ctypes.data)
+    if r != 0:
+        raise api.RtError(r, lib.oracle_last_error().decode())
+    return out, st_out
 
 
 def lights_random(desc, origin, seed, n) -> np.ndarray:

@@ -331,6 +331,9 @@ def load_device_lib() -> C.CDLL:
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                               C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32]
         lib.rt_debug_trace_sample.restype = C.c_int
+        if hasattr(lib, "rt_debug_shade_rays"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_debug_shade_rays.argtypes = [C.c_void_p, C.POINTER(RtRenderParams), C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+            lib.rt_debug_shade_rays.restype = C.c_int
         lib.rt_scene_info.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(C.c_uint32)]
         lib.rt_scene_info.restype = C.c_int
         if hasattr(lib, "rt_scene_set_tail_flag"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
@@ -845,6 +848,9 @@ def load_image(path: str) -> np.ndarray:
         lib.rth_free_image(ptr)
 
 
+SHADE_RAYS_STRIDE = 28  # RT_SHADE_RAYS_STRIDE
+
+
 class DeviceScene:
     """RtScene on one GPU: the drop-in for `camera.render(world, lights, &mut buf)`."""
 
@@ -910,6 +916,22 @@ class DeviceScene:
         if n < 0:
             _check(self._lib, n)
         return np.array(list(rgb)), np.array(list(tr)).reshape(max_bounces, 17)[:min(n, max_bounces)]
+
+    def shade_rays(self, params, origins, dirs, states, variant: int = 0) -> tuple:
+        """rt_debug_shade_rays: one path vertex per ray on the device, (out[n, SHADE_RAYS_STRIDE], state_out[n]); variant 0 =
+        the kernel variant the render picks, 1 = the full one, 2 = the simple one."""
+        rays = np.ascontiguousarray(np.concatenate([np.asarray(origins, dtype=np.float64).reshape(-1, 3),
+                                                    np.asarray(dirs, dtype=np.float64).reshape(-1, 3)], axis=1))
+        st_in = np.ascontiguousarray(states, dtype=np.uint64)
+        n = len(rays)
+        if len(st_in) != n:
+            raise ValueError("shade_rays: one generator state per ray")
+        out = np.zeros((n, SHADE_RAYS_STRIDE), dtype=np.float64)
+        st_out = np.zeros(n, dtype=np.uint64)
+        st = self._lib.rt_debug_shade_rays(self._h, C.byref(params), variant, n, rays.ctypes.data, st_in.ctypes.data, out.ctypes.data,
+                                           st_out.ctypes.data)
+        _check(self._lib, st)
+        return out, st_out
 
     def update(self, desc) -> dict:
         """rt_scene_update: gives the scene the numbers of `desc` (same structure: see include/rt_mi355.h); the mesh BVHs keep

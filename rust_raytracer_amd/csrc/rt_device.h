@@ -898,15 +898,46 @@ template <typename R, bool STATS> RT_DEV R plane_pdf_value(const PlanePrim<R>& p
     }
     return R(0);
 }
+// 1 - cos_theta_max of the cone a sphere of radius^2 = radius_squared subtends from distance^2 = distance_squared, with
+// cos_theta_max = sqrt(1 - radius_squared / distance_squared) (sphere.rs:111, 133).  f64 subtracts as the reference does.  In
+// f32 that subtraction cancels: from r / d < 2.4e-4 on (a lamp of radius 0.01 at distance 100) cos_theta_max rounds to 1, the
+// solid angle to 0, the pdf to infinity and the weight of every sample of that light to 0 - the light goes dark.
+// (1 - c) = (1 - c^2) / (1 + c) = q / (1 + c) is the same number without the cancellation.
+template <typename R> RT_DEV R one_minus_cos_theta_max(R radius_squared, R distance_squared, R& cos_theta_max) {
+    const R q = radius_squared / distance_squared;
+    cos_theta_max = sqrt(R(1) - q);
+    if constexpr (sizeof(R) == 8) return R(1) - cos_theta_max;
+    else return q / (R(1) + cos_theta_max);
+}
 // sphere.rs:106-121
 template <typename R, bool STATS> RT_DEV R sphere_pdf_value(const SpherePrim<R>& s, V3<R> origin, V3<R> dir, LaneCounters& cnt) {
     Ray<R> ray = make_ray(origin, dir);
     R t;
     if (STATS) cnt.prim_tests++;
-    if (sphere_test(s, ray, R(0.001), Lim<R>::inf(), t)) {
+    bool hit;
+    if constexpr (sizeof(R) == 8) {
+        hit = sphere_test(s, ray, R(0.001), Lim<R>::inf(), t);
+    } else {
+        // f32: sphere_test's c = |oc|^2 - r^2 loses the radius of a small far light (1e4 - 1e-4 is 1e4), so the light that was
+        // just sampled is missed and its term of the mixture pdf is 0.  The same discriminant from the perpendicular distance
+        // of the centre from the ray: half_b^2 - a c = a (r^2 - |oc - (d . oc / a) d|^2); the roots and the interval
+        // (0.001, inf) are sphere_test's.
+        const V3<R> oc = ld3(s.center) - origin;
+        const R a = length_squared(dir);
+        const R hb = dot(dir, oc);
+        const V3<R> perp = oc - dir * (hb / a);
+        const R discriminant = a * (s.radius * s.radius - length_squared(perp));
+        hit = false;
+        if (!(discriminant < R(0))) {
+            const R d_sqrt = sqrt(discriminant);
+            const R near = (hb - d_sqrt) / a, far = (hb + d_sqrt) / a;
+            hit = !(near <= R(0.001) || Lim<R>::inf() <= near) || !(far <= R(0.001) || Lim<R>::inf() <= far);  // as sphere_test compares
+        }
+    }
+    if (hit) {
         R radius_squared = s.radius * s.radius;
-        R cos_theta_max = sqrt(R(1) - radius_squared / length_squared(ld3(s.center) - origin));
-        R solid_angle = R(2) * pi<R>() * (R(1) - cos_theta_max);
+        R cos_theta_max;
+        R solid_angle = R(2) * pi<R>() * one_minus_cos_theta_max(radius_squared, length_squared(ld3(s.center) - origin), cos_theta_max);
         return R(1) / solid_angle;
     }
     return R(0);
@@ -975,16 +1006,26 @@ template <typename R> RT_DEV V3<R> light_random(const SceneView<R>& sc, const Li
             V3<R> bu, bv;
             onb_from_vec(dir, bu, bv);
             R radius_squared = s.radius * s.radius;
-            R cos_theta_max = sqrt(R(1) - radius_squared / length_squared(dir));
+            R cos_theta_max;
+            const R omc = one_minus_cos_theta_max(radius_squared, length_squared(dir), cos_theta_max);
             R r1 = rng_uniform<R>(rng);
             R r2 = rng_uniform<R>(rng);
             R phi = r1 * R(2) * pi<R>();
-            R z = R(1) + r2 * (cos_theta_max - R(1));
             R sn, cs;
             sincos_r(phi, sn, cs);
-            R x = cs * sqrt(R(1) - z * z);
-            R y = sn * sqrt(R(1) - z * z);
-            return basis_apply(bu, bv, dir, mk<R>(x, y, z));
+            if constexpr (sizeof(R) == 8) {
+                R z = R(1) + r2 * (cos_theta_max - R(1));
+                R x = cs * sqrt(R(1) - z * z);
+                R y = sn * sqrt(R(1) - z * z);
+                return basis_apply(bu, bv, dir, mk<R>(x, y, z));
+            } else {
+                // f32: 1 - z = r2 (1 - cos_theta_max) exactly as above, and sqrt(1 - z^2) = sqrt((1 - z) (1 + z)) without
+                // squaring a z that is within a few ulps of 1
+                const R h = r2 * omc;
+                const R z = R(1) - h;
+                const R sin_theta = sqrt(h * (R(1) + z));
+                return basis_apply(bu, bv, dir, mk<R>(cs * sin_theta, sn * sin_theta, z));
+            }
         }
         case LIGHT_SKY: return random_unit<R>(rng);           // sky.rs:65-67
         case LIGHT_SUN: return ld3(sc.suns[l.index].direction);  // sun.rs:74-76

@@ -168,6 +168,55 @@ __global__ void k_trace_sample(SceneView<R> sc, CameraView<R> cam, ParamsView<R>
     *n_out = n;
 }
 
+// Diagnostic probe: ONE path vertex per lane, what one loop trip of k_megakernel does to a path with throughput (1,1,1) and
+// radiance 0 - world_test (with the generator: the volumes' free-flight draws), then shade - from a caller-supplied ray and
+// generator state.  RT_SHADE_RAYS_STRIDE doubles per ray (include/rt_mi355.h, rt_debug_shade_rays).  The hit is resolved a
+// second time for the record; shade() resolves its own.
+template <typename R, bool TEX>
+__global__ void __launch_bounds__(256) k_shade_rays(SceneView<R> sc, ParamsView<R> prm, uint32_t n, const double* __restrict__ rays,
+                                                    const unsigned long long* __restrict__ states, double* __restrict__ out,
+                                                    unsigned long long* __restrict__ state_out) {
+    extern __shared__ int lds_stack[];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* r = rays + 6 * size_t(i);
+    double* o = out + RT_SHADE_RAYS_STRIDE * size_t(i);
+    for (int k = 0; k < RT_SHADE_RAYS_STRIDE; k++) o[k] = 0.0;
+    LaneCounters cnt;
+    Rng rng;
+    rng.s = states[i];
+    PathState<R> ps;
+    ps.ray = make_ray(mk<R>(R(r[0]), R(r[1]), R(r[2])), mk<R>(R(r[3]), R(r[4]), R(r[5])));
+    ps.throughput = mk<R>(1, 1, 1);
+    ps.radiance = mk<R>(0, 0, 0);
+    ps.depth = 1;
+    Best<R> best;
+    world_test<R, false, TEX>(sc, ps.ray, R(0.001), best, lds_stack + threadIdx.x, int(blockDim.x), cnt, &rng);
+    o[0] = double(best.t);
+    o[10] = -1.0;
+    o[11] = -1.0;
+    o[26] = double((rng.s - states[i]) * 0xF1DE83E19937733Dull);  // draws of the search: times the inverse of Rng::next's increment
+    if (best.pc >= 0) {
+        const HitInfo<R> h = resolve_hit<R, TEX>(sc, ps.ray, best);
+        o[1] = double(h.pos.x); o[2] = double(h.pos.y); o[3] = double(h.pos.z);
+        o[4] = double(h.normal.x); o[5] = double(h.normal.y); o[6] = double(h.normal.z);
+        o[7] = double(h.u); o[8] = double(h.v);
+        o[9] = h.front_face ? 1.0 : 0.0;
+        o[10] = double(h.material);
+        o[11] = double(sc.ops[best.pc].type);
+        o[12] = double(h.tex_a.x); o[13] = double(h.tex_a.y); o[14] = double(h.tex_a.z);
+        o[15] = double(h.tex_b);
+    }
+    const bool cont = shade<R, false, TEX>(sc, prm, ps, best, rng, cnt);
+    if (cont) {
+        o[16] = 1.0;
+        o[17] = double(ps.ray.d.x); o[18] = double(ps.ray.d.y); o[19] = double(ps.ray.d.z);
+    }
+    o[20] = double(ps.throughput.x); o[21] = double(ps.throughput.y); o[22] = double(ps.throughput.z);
+    o[23] = double(ps.radiance.x); o[24] = double(ps.radiance.y); o[25] = double(ps.radiance.z);
+    state_out[i] = rng.s;
+}
+
 // ---------------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------------
@@ -2446,6 +2495,45 @@ int rt_debug_trace_sample(const RtScene* scene, const RtCameraDesc* camera, cons
     uint32_t n;
     std::memcpy(&n, h.data() + 3 + size_t(max_bounces) * 17, sizeof n);
     return int(n);
+}
+
+// Diagnostic: one path vertex per ray on the device (k_shade_rays).
+int rt_debug_shade_rays(const RtScene* scene, const RtRenderParams* params, uint32_t variant, uint32_t n, const double* rays,
+                        const uint64_t* states, double* out, uint64_t* state_out) {
+    using namespace rt;
+    if (!scene || !params || !rays || !states || !out || !state_out) return set_err(RT_E_INVALID, "rt_debug_shade_rays: NULL argument");
+    if (variant > 2) return set_err(RT_E_INVALID, "rt_debug_shade_rays: variant is 0 (the render's), 1 (full) or 2 (simple)");
+    if (n == 0) return RT_OK;
+    RtScene* s = const_cast<RtScene*>(scene);
+    const bool needs_full = s->compiled.needs_tex_interpreter || !s->compiled.volumes.empty();  // as render_typed picks
+    if (variant == 2 && needs_full)
+        return set_err(RT_E_INVALID, "rt_debug_shade_rays: the scene needs the full variant (texture interpreter or volumes)");
+    const bool tex = variant == 1 || (variant == 0 && needs_full);
+    HIP_TRY(hipSetDevice(s->device));
+    DevBuf<double> d_rays, d_out;
+    DevBuf<unsigned long long> d_states, d_state_out;
+    const size_t out_bytes = size_t(n) * RT_SHADE_RAYS_STRIDE * sizeof(double);
+    int st;
+    if ((st = d_rays.reserve(size_t(n) * 6 * sizeof(double))) || (st = d_out.reserve(out_bytes)) ||
+        (st = d_states.reserve(size_t(n) * 8)) || (st = d_state_out.reserve(size_t(n) * 8))) return st;
+    HIP_TRY(hipMemcpy(d_rays, rays, size_t(n) * 6 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_states, states, size_t(n) * 8, hipMemcpyHostToDevice));
+    if ((st = with_tables(s, params->precision, [&](auto& ds) -> int {
+            using R = typename std::decay_t<decltype(ds)>::Real;
+            const size_t lds = size_t(ds.view.stack_entries) * 256 * sizeof(int);  // as k_megakernel's
+            if (lds > 160 * 1024) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the LDS traversal stack");
+            const dim3 grid((n + 255u) / 256u), block(256);
+            const ParamsView<R> pv = make_params_view<R>(*params, 0);
+            if (tex) hipLaunchKernelGGL((k_shade_rays<R, true>), grid, block, lds, s->stream, ds.view, pv, n, d_rays.get(), d_states.get(), d_out.get(), d_state_out.get());
+            else hipLaunchKernelGGL((k_shade_rays<R, false>), grid, block, lds, s->stream, ds.view, pv, n, d_rays.get(), d_states.get(), d_out.get(), d_state_out.get());
+            return RT_OK;
+        })))
+        return st;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(state_out, d_state_out, size_t(n) * 8, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 int rt_scene_update_check(const RtSceneDesc* a, const RtSceneDesc* b) {

@@ -11,6 +11,7 @@ Tolerances (stated here, used below):
     statistical: image mean within 1 %, >= 95 % of values within max(5 % relative, 0.02).
 Everything here needs the GPU."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
@@ -223,19 +224,56 @@ def test_f64_matches_committed_golden_frames(dev, name):
     assert_f64_parity(gpu, GOLD[name])
 
 
-@pytest.mark.parametrize("name", ["cornell", "light_test", "default", "nested_transform", "sun_sky", "texture_mix"])
-def test_f32_is_statistically_equivalent(dev, name):
-    args = [a for a in SCENES[name] if not a.startswith("-s=")] + ["-s=64"]
+F32_FRAME_SPP = {}  # scene: samples per pixel axis where 64 does not reach the bar (path divergence, see the test)
+
+
+@functools.lru_cache(maxsize=None)
+def _f32_frame_reference(name):
+    args = [a for a in SCENES[name] if not a.startswith("-s=")] + [f"-s={F32_FRAME_SPP.get(name, 64)}"]
     hs = api.HostScene(args)
-    ref, _ = pyoracle.render(hs.desc, hs.camera, hs.params)
-    p = hs.params.copy()
-    p.precision = api.RT_PRECISION_F32
-    gpu = api.DeviceScene(hs.desc, 0).render(hs.camera, p)
-    a, b = gpu[..., :3], ref[..., :3]
-    assert not np.isnan(a).any()
-    assert abs(a.mean() - b.mean()) <= 0.01 * b.mean()
-    close = np.abs(a - b) <= np.maximum(0.05 * np.abs(b), 0.02)
-    assert close.mean() >= 0.95, f"only {close.mean():.3%} of f32 values are close to the f64 oracle"
+    return hs, pyoracle.render(hs.desc, hs.camera, hs.params)[0]
+
+
+@pytest.mark.parametrize("name", ["cornell", "light_test", "default", "nested_transform", "sun_sky", "texture_mix",
+                                  "hollow_glass", "smoke", "cornell_smoke", "nested_volumes", "earth", "perlin", "texture_test",
+                                  "polished", "box_light", "deep_texture"])
+def test_f32_is_statistically_equivalent(dev, name):
+    """Whole f32 frames of both pipelines (k_wf_shade<float> and the volume kernels, which the per-vertex probe of
+    tests/test_gpu_f32_shade.py does not instantiate) at the statistical bar: the image mean within 1 %, 95 % of the values
+    within max(5 %, 0.02).  The oracle frame is rendered once per scene.
+
+    The bar is taken over the values that are finite in the ORACLE's frame.  The oracle's own frames of hollow_glass and
+    box_light hold NaN values (72 and 3 at -s=64: the reference's 0/0 at vertices that sample a member of the light list from
+    its own surface), so over all values the image means are NaN and the oracle's frame itself would miss the bar.  Where the
+    oracle is finite the f32 frame must hold no NaN; where the oracle is NaN the f32 value may be NaN or not, but the frame holds no
+    infinity and at most twice the oracle's count of values that are not finite (measured: the f32 frames hold their NaN values
+    in exactly those places).  On a scene without NaN in the oracle's frame this is the bar
+    as it was."""
+    hs, ref = _f32_frame_reference(name)
+    scene = api.DeviceScene(hs.desc, 0)
+    b = ref[..., :3]
+    fin = ~np.isnan(b)
+    frames = {}
+    for pipeline in (api.RT_PIPELINE_MEGAKERNEL, api.RT_PIPELINE_WAVEFRONT):
+        p = hs.params.copy()
+        p.precision = api.RT_PRECISION_F32
+        p.pipeline = pipeline
+        a = scene.render(hs.camera, p)[..., :3]
+        assert scene.stats().pipeline_used == pipeline
+        af, bf = a[fin], b[fin]
+        close = np.abs(af - bf) <= np.maximum(0.05 * np.abs(bf), 0.02)
+        frames[pipeline] = (a, af, close)
+        print(f"{name} f32 pipeline {pipeline}: mean {af.mean():.6f} against {bf.mean():.6f} ({abs(af.mean() / bf.mean() - 1):.3%}), "
+              f"{close.mean():.3%} of values close, NaN values {int(np.isnan(a).sum())} against {int((~fin).sum())}, "
+              f"{int((np.isnan(a) & ~fin).sum())} in the same place")      # both lines before any assertion
+    bf = b[fin]
+    assert fin.mean() >= 0.95 and not np.isinf(b).any()       # the oracle's frame is finite but for a few 0/0 values
+    for a, af, close in frames.values():
+        # no infinity anywhere, and no NaN sprayed around the oracle's: at most twice as many values that are not finite
+        assert not np.isinf(a).any() and (~np.isfinite(a)).sum() <= 2 * (~fin).sum()
+        assert not np.isnan(af).any()
+        assert abs(af.mean() - bf.mean()) <= 0.01 * bf.mean()
+        assert close.mean() >= 0.95, f"only {close.mean():.3%} of f32 values are close to the f64 oracle"
 
 
 @pytest.mark.parametrize("name", ["cornell", "hollow_glass", "default", "light_test", "two_meshes", "texture_mix", "smoke", "cornell_smoke", "nested_volumes"])
