@@ -29,6 +29,7 @@ typedef struct RtHost RtHost;
  * --adaptive-min=<k>, --adaptive-check=<m>, --adaptive-radius=<r>, --light-groups[=<max>],
  * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>], --irradiance,
  * --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]
+ * --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]
  * (unknown keys are ignored by the reference, config.rs:146, so these
  * are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
@@ -90,6 +91,11 @@ int rth_irradiance(const RtHost* host);
  * --ao, --probe, --irradiance or --pipeline=mega; rtrace refuses --sequence and a depth of 0 before a device is touched.
  * rth_sh_probes returns the number of probes and writes up to `capacity` positions (3 doubles each; positions_out may be NULL). */
 uint32_t rth_sh_probes(const RtHost* host, double* positions_out, uint32_t capacity);
+/* Point queries (rt_closest_points): --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...] (finite numbers): rtrace renders nothing and prints, per
+ * point, the distance, position and normal of the closest surface point (%.17g each), then node, triangle, material and flags.
+ * rth_load rejects malformed values, and --nearest in the combinations --sh-probe is rejected in, and with --sh-probe itself.
+ * rth_nearest_points returns the number of points and writes up to `capacity` of them (3 doubles each; points_out may be NULL). */
+uint32_t rth_nearest_points(const RtHost* host, double* points_out, uint32_t capacity);
 /* Light probe (rt_render_rays): --probe=<x>,<y>,<z>[:<width>] (a finite position; width 2 .. 65536, default 512; the height
  * is width / 2): rtrace renders the equirectangular panorama of rth_probe_rays at that point with the run's -s, -t, depth,
  * bias, seed and precision and writes out_probe.png INSTEAD of the frame.  No pixel filter: every sample of a texel goes along

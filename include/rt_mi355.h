@@ -646,6 +646,44 @@ int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out);   /* of the 
  * *n_ops_out = the program's length; nodes_out may be NULL.                                                            */
 int rt_scene_op_nodes(const RtSceneDesc* desc, int32_t* nodes_out, uint32_t capacity, uint32_t* n_ops_out);
 
+/* ---- Point queries: the closest surface point and its distance ---------------------------------
+ * Probe clearance, snapping points onto a surface, proximity tests, distance fields: for n points q the nearest candidate
+ * primitive of the scene as it stands.  Candidates: every Sphere, every Plane (the parallelogram center +- u +- v) and
+ * every mesh triangle reachable from the world root, each under its transform chain; Sky and Sun never; the facing flags
+ * (RT_MESH_HIT_BACK_FACES, RT_PLANE_RENDER_BACKFACE) do not matter.  The answer is the candidate with the smallest
+ * Euclidean world distance, if that distance is strictly below max_distance[i]; at equal distance any of the tied
+ * primitives (a mesh vertex is shared by several triangles).  General rules as for the ray queries: n = 0 is a no-op,
+ * NULL points / out or a bad precision is RT_E_INVALID, non-finite inputs are not an error, synchronous, must not
+ * overlap a render or an update of the scene, rt_get_stats and the tail flag are left alone, chunks of RT_RQ_CHUNK.
+ * RT_E_UNSUPPORTED, decided on the host before anything is allocated: a scene with volumes; a scene in which the composed
+ * linear part L of the transform chain over a candidate is not a similarity (max|L^T L - s^2 I| <= 1e-9 s^2 with
+ * s^2 = tr(L^T L) / 3 is one: only then are object-space distances world distances / s); a mesh BVH deeper than the
+ * kernel's LDS stack (64 levels).                                                                                     */
+#define RT_POINT_FOUND      1u   /* a primitive lies closer than max_distance */
+#define RT_POINT_BACK_SIDE  2u   /* (q - pos) . normal < 0 for the reported primitive */
+typedef struct RtPointHit {      /* 80 bytes */
+    double   distance;           /* world units; nothing found: +inf, flags 0, ids -1, other reals 0 */
+    double   pos[3];             /* the closest point, world space */
+    double   normal[3];          /* GEOMETRIC unit normal of the primitive at pos, world space, not flipped towards q: Sphere
+                                    away from the centre, (pos - c) / |r|, also for the negative radius of a hollow sphere (the
+                                    object-space +x direction when q is the centre), Plane its own normal,
+                                    triangle normalize(e1 x e2) (a zero-area triangle: 0) */
+    int32_t  material, node, prim;   /* as in RtRayHit: RtSceneDesc indices; prim = triangle in RtMesh.tri_pos order, else -1 */
+    uint32_t flags;              /* RT_POINT_* */
+    uint64_t _reserved;          /* zero */
+} RtPointHit;
+/* points: n x 3 doubles; max_distance: n doubles, or NULL = +inf for every point. */
+int rt_closest_points(const RtScene* scene, uint64_t n, const double* points, const double* max_distance, uint32_t precision,
+                      RtPointHit* out);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_closest_points_device(const RtScene* scene, uint64_t n, const double* d_points, const double* d_max_distance, uint32_t precision,
+                             RtPointHit* d_out, void* stream);
+int rt_point_query_stats(const RtScene* scene, RtRayQueryStats* out);   /* of the last point query on this scene; rays = points */
+/* Diagnostic, host arrays: counts_out[2i] = BVH nodes visited, counts_out[2i + 1] = triangles tested for point i (the counting
+ * variant of the kernel; rt_point_query_stats is left alone). */
+int rt_debug_closest_points_counts(const RtScene* scene, uint64_t n, const double* points, const double* max_distance, uint32_t precision,
+                                   uint32_t* counts_out);
+
 /* ---- Ambient occlusion at surface points --------------------------------------------------------
  * For point i with position p_i and normal n_i, and sample s = 0 .. samples-1:
  *     generator keyed (seed, 0, i, s) as a render keys (seed, replica, pixel, stratum);

@@ -195,6 +195,12 @@ RtRayHit = np.dtype([("t", "<f8"), ("pos", "<f8", (3,)), ("normal", "<f8", (3,))
                      ("node", "<i4"), ("prim", "<i4"), ("flags", "<u4"), ("_reserved", "<u8")])
 assert RtRayHit.itemsize == 96
 
+# RtPointHit (include/rt_mi355.h) as a numpy structured dtype: DeviceScene.closest_points returns an array of it
+RT_POINT_FOUND, RT_POINT_BACK_SIDE = 1, 2
+RtPointHit = np.dtype([("distance", "<f8"), ("pos", "<f8", (3,)), ("normal", "<f8", (3,)), ("material", "<i4"), ("node", "<i4"),
+                       ("prim", "<i4"), ("flags", "<u4"), ("_reserved", "<u8")])
+assert RtPointHit.itemsize == 80
+
 
 class RtBakeParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("precision", C.c_uint32), ("seed", C.c_uint64), ("bias", C.c_double),
@@ -271,6 +277,8 @@ def load_host_lib() -> C.CDLL:
         lib.rth_irradiance.restype = C.c_int
         lib.rth_sh_probes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         lib.rth_sh_probes.restype = C.c_uint32
+        lib.rth_nearest_points.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        lib.rth_nearest_points.restype = C.c_uint32
         lib.rth_probe.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         lib.rth_probe.restype = C.c_uint32
         lib.rth_probe_rays.argtypes = [C.POINTER(C.c_double), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -431,6 +439,15 @@ def load_device_lib() -> C.CDLL:
                                                      C.c_void_p, C.c_void_p]),
                     ("rt_ray_query_stats", C.c_int, [C.c_void_p, C.POINTER(RtRayQueryStats)]),
                     ("rt_scene_op_nodes", C.c_int, [C.POINTER(RtSceneDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
+        if hasattr(lib, "rt_closest_points"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            for name, res, args in (
+                    ("rt_closest_points", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+                    ("rt_closest_points_device", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+                    ("rt_point_query_stats", C.c_int, [C.c_void_p, C.POINTER(RtRayQueryStats)]),
+                    ("rt_debug_closest_points_counts", C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p])):
                 fn = getattr(lib, name)
                 fn.argtypes = args
                 fn.restype = res
@@ -745,6 +762,8 @@ class HostScene:
         self.irradiance = bool(lib.rth_irradiance(handle))  # --irradiance: also bake out_irradiance.png
         self.sh_probes = np.zeros((lib.rth_sh_probes(handle, None, 0), 3))  # --sh-probe=<x>,<y>,<z>[:...]: (n, 3) positions to bake instead of rendering
         lib.rth_sh_probes(handle, self.sh_probes.ctypes.data, len(self.sh_probes))
+        self.nearest = np.zeros((lib.rth_nearest_points(handle, None, 0), 3))  # --nearest=<x>,<y>,<z>[:...]: (n, 3) points to query instead of rendering
+        lib.rth_nearest_points(handle, self.nearest.ctypes.data, len(self.nearest))
         pos = (C.c_double * 3)()
         width = int(lib.rth_probe(handle, pos))
         self.probe = (width, tuple(pos)) if width else None  # --probe=<x>,<y>,<z>[:<width>]: (width, position), None without the flag
@@ -1062,6 +1081,46 @@ class DeviceScene:
         st = self._lib.rt_bake_probes_device(self._h, n, C.c_void_p(d_positions_ptr or None), C.byref(params), C.c_void_p(d_out_ptr or None),
                                              C.c_void_p(stream))
         _check(self._lib, st)
+
+    @staticmethod
+    def _points(points, max_distance) -> tuple:
+        """(n, 3) float64 points and their (n,) limits (None: no limit; a scalar broadcasts)."""
+        p = _table(points, "points")
+        lim = None if max_distance is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, dtype=np.float64), (len(p),)))
+        return p, lim
+
+    def closest_points(self, points, max_distance=None, precision: int = RT_PRECISION_F64) -> np.ndarray:
+        """rt_closest_points: the nearest sphere, parallelogram or mesh triangle of the scene to every point as an (n,) array of
+        api.RtPointHit (distance, closest point, geometric normal, ids, RT_POINT_* flags).  points: (n, 3) or (3,);
+        max_distance: None (no limit), a scalar or (n,): a primitive counts only if it is strictly nearer."""
+        p, lim = self._points(points, max_distance)
+        out = np.zeros(len(p), dtype=RtPointHit)
+        st = self._lib.rt_closest_points(self._h, len(p), p.ctypes.data, None if lim is None else lim.ctypes.data, precision, out.ctypes.data)
+        _check(self._lib, st)
+        return out
+
+    def closest_points_device(self, n: int, d_points_ptr: int, d_out_ptr: int, d_max_distance_ptr: int = 0,
+                              precision: int = RT_PRECISION_F64, stream: int = 0) -> None:
+        """rt_closest_points_device: n x 3 doubles in HBM -> n RtPointHit records (80 B each) in HBM; d_max_distance_ptr 0 = no limit."""
+        st = self._lib.rt_closest_points_device(self._h, n, C.c_void_p(d_points_ptr or None), C.c_void_p(d_max_distance_ptr or None), precision,
+                                                C.c_void_p(d_out_ptr or None), C.c_void_p(stream))
+        _check(self._lib, st)
+
+    def point_query_stats(self) -> RtRayQueryStats:
+        """rt_point_query_stats: of the last closest_points call (rays = points)."""
+        s = RtRayQueryStats()
+        st = self._lib.rt_point_query_stats(self._h, C.byref(s))
+        _check(self._lib, st)
+        return s
+
+    def closest_points_counts(self, points, max_distance=None, precision: int = RT_PRECISION_F64) -> np.ndarray:
+        """rt_debug_closest_points_counts: (n, 2) uint32, per point the BVH nodes visited and the triangles tested."""
+        p, lim = self._points(points, max_distance)
+        out = np.zeros((len(p), 2), dtype=np.uint32)
+        st = self._lib.rt_debug_closest_points_counts(self._h, len(p), p.ctypes.data, None if lim is None else lim.ctypes.data, precision,
+                                                      out.ctypes.data)
+        _check(self._lib, st)
+        return out
 
     def ray_query_stats(self) -> RtRayQueryStats:
         s = RtRayQueryStats()

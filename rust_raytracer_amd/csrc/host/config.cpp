@@ -290,6 +290,21 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
                 if (colon == std::string::npos) break;
                 pos = colon + 1;
             }
+        } else if (key == "-nearest") {  // new: closest surface point to each listed point (rt_closest_points) instead of a render
+            cfg.nearest.clear();
+            size_t pos = 0;
+            for (;;) {
+                const size_t colon = value.find(':', pos);
+                std::string ignored;
+                if (!parse_vec3(value.substr(pos, colon == std::string::npos ? std::string::npos : colon - pos), v3, &ignored) ||
+                    !std::isfinite(v3[0]) || !std::isfinite(v3[1]) || !std::isfinite(v3[2])) {
+                    *err = "Nearest must be a list of points <x>,<y>,<z>[:<x>,<y>,<z>...] (finite numbers)";
+                    return false;
+                }
+                cfg.nearest.insert(cfg.nearest.end(), v3, v3 + 3);
+                if (colon == std::string::npos) break;
+                pos = colon + 1;
+            }
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -348,6 +363,12 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
                                    cfg.pipeline == RT_PIPELINE_MEGAKERNEL)) {
         *err = "--sh-probe bakes probes on one GPU with the wavefront scheduler instead of the frame: it cannot be combined with --gpus > 1, "
                "--progressive, --noise-threshold, --pick, --ao, --probe, --irradiance or --pipeline=mega";
+        return false;
+    }
+    if (!cfg.nearest.empty() && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.has_probe || cfg.irradiance ||
+                                 !cfg.sh_probes.empty() || cfg.pipeline == RT_PIPELINE_MEGAKERNEL)) {
+        *err = "--nearest queries points on one GPU instead of rendering the frame: it cannot be combined with --gpus > 1, "
+               "--progressive, --noise-threshold, --pick, --ao, --probe, --irradiance, --sh-probe or --pipeline=mega";
         return false;
     }
     if (cfg.has_probe && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.light_groups || cfg.denoise ||

@@ -110,6 +110,14 @@ uint32_t rth_sh_probes(const RtHost* host, double* positions_out, uint32_t capac
             for (int a = 0; a < 3; a++) positions_out[3 * size_t(i) + a] = p[3 * size_t(i) + a];
     return n;
 }
+uint32_t rth_nearest_points(const RtHost* host, double* points_out, uint32_t capacity) {
+    const auto& p = host->config.nearest;
+    const uint32_t n = uint32_t(p.size() / 3);
+    if (points_out)
+        for (uint32_t i = 0; i < n && i < capacity; i++)
+            for (int a = 0; a < 3; a++) points_out[3 * size_t(i) + a] = p[3 * size_t(i) + a];
+    return n;
+}
 uint32_t rth_probe(const RtHost* host, double position_out[3]) {
     if (!host->config.has_probe) return 0;
     if (position_out)

@@ -54,6 +54,7 @@ struct Config {
     bool has_probe = false;                           // --probe=<x>,<y>,<z>[:<width>]: a light probe panorama instead of the frame
     double probe_position[3] = {0.0, 0.0, 0.0};
     uint32_t probe_width = 512;                       // height = width / 2
+    std::vector<double> nearest;                      // --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]: 3 doubles per point, queried instead of rendering
     std::vector<double> sh_probes;                    // --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]: 3 doubles per probe, baked instead of rendering
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176

@@ -9,6 +9,7 @@
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 //   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
 //   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]  --irradiance  --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]
+//   --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]
 // --sh-probe=<x>,<y>,<z>[:...] renders nothing: an SH radiance probe is baked at each named position (rt_bake_probes) with the
 // run's -s, -t, depth, bias, seed and precision and its nine RGB coefficients are printed, one line per coefficient.
 // --irradiance also writes out_irradiance.png: the --pick ray of every pixel is cast on the device (rt_trace_rays_device) and the
@@ -265,6 +266,24 @@ static int bake_sh_probes(RtHost* host) {
     return 0;
 }
 
+// --nearest: the closest surface point of the scene to each listed point, one line each; returns the process exit status.
+static int nearest_points(RtHost* host) {
+    const uint32_t n = rth_nearest_points(host, nullptr, 0);
+    std::vector<double> q(3 * size_t(n));
+    rth_nearest_points(host, q.data(), n);
+    std::vector<RtPointHit> hits(n);
+    RtScene* scene = nullptr;
+    if (rt_scene_create(rth_scene(host), 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    if (rt_closest_points(scene, n, q.data(), nullptr, rth_params(host)->precision, hits.data()) != RT_OK) return fail(rt_last_error());
+    for (uint32_t i = 0; i < n; i++) {
+        const RtPointHit& h = hits[i];
+        std::printf("Nearest %u: distance %.17g position %.17g %.17g %.17g normal %.17g %.17g %.17g node %d triangle %d material %d flags %u\n", i,
+                    h.distance, h.pos[0], h.pos[1], h.pos[2], h.normal[0], h.normal[1], h.normal[2], h.node, h.prim, h.material, h.flags);
+    }
+    return 0;
+}
+
 // --probe: the panorama at the named point to out_probe.png; returns the process exit status.
 static int render_probe(RtHost* host, const std::function<double()>& since) {
     double position[3];
@@ -409,6 +428,8 @@ int main(int argc, char** argv) {
         if (!sequence.empty()) return fail("--sh-probe bakes probes instead of the frame: it cannot be combined with --sequence");
         if (params->max_depth == 0) return fail("--sh-probe needs a depth of at least 1");
     }
+    if (rth_nearest_points(host, nullptr, 0) != 0 && !sequence.empty())
+        return fail("--nearest queries points instead of rendering the frame: it cannot be combined with --sequence");
     uint32_t gpus = rth_gpus(host);
     int available = rt_device_count();
     if (available < 1) {
@@ -422,6 +443,11 @@ int main(int argc, char** argv) {
     }
     if (rth_sh_probes(host, nullptr, 0) != 0) {
         const int rc = bake_sh_probes(host);
+        rth_destroy(host);
+        return rc;
+    }
+    if (rth_nearest_points(host, nullptr, 0) != 0) {
+        const int rc = nearest_points(host);
         rth_destroy(host);
         return rc;
     }

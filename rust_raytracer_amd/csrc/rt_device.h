@@ -352,6 +352,14 @@ template <typename R> RT_DEV Ray<R> ray_in_chain(const SceneView<R>& sc, const R
     return make_ray(o, d);
 }
 
+// The point twin of ray_in_chain (point queries, rt_point.h): a world-space point in the object space of `chain`, through the
+// same inverse matrices in the same order.
+template <typename R> RT_DEV V3<R> point_in_chain(const SceneView<R>& sc, V3<R> p, int32_t chain) {
+    const int32_t b = sc.chain_offsets[chain], e = sc.chain_offsets[chain + 1];
+    for (int32_t i = b; i < e; i++) p = xform_apply(sc.xforms[sc.chain_items[i]].inv, p, R(1));
+    return p;
+}
+
 // Scene tables are never written by a kernel.  Reading them through a CONSTANT-address-space pointer tells the compiler so:
 // a load whose address is wave-uniform then becomes a scalar load (s_load into SGPRs, scalar cache) even behind the kernel's
 // own stores to other buffers, where it otherwise has to assume a clobber and issues a vector load.

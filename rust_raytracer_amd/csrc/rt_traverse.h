@@ -1,7 +1,9 @@
 // rt_traverse.h — the steps of a BVH search, each written ONCE: the clamped inverse direction, the exact triangle test, the
-// two-child node step, the f32 culling ray, and the decode, cone cull and ordering of a 4-wide node's children.  This is the only
-// place that reads a BvhNode4q / MeshNode4qc header or a TriRec for intersection; a change of a node format starts here.
-// Users: mesh_traverse (rt_device.h), k_wf_intersect, group_search and k_wf_mesh (rt_wavefront.h), mesh_any_hit (rt_query.h).
+// two-child node step, the f32 culling ray, and the decode, cone cull and ordering of a 4-wide node's children, and the distance
+// step of the point queries.  This is the only place that reads a BvhNode4q / MeshNode4qc header or a TriRec for intersection; a
+// change of a node format starts here.
+// Users: mesh_traverse (rt_device.h), k_wf_intersect, group_search and k_wf_mesh (rt_wavefront.h), mesh_any_hit (rt_query.h),
+// mesh_closest (rt_point.h).
 // The stacks and the loops around the steps stay with the kernels: they differ for measured reasons given there.
 //
 // Included by rt_device.h behind V3 / Lim / Ray, which everything here is written in.
@@ -217,6 +219,42 @@ RT_DEV void node4q_cull_slabs(uint4 h0, uint4 h1, uint4 cn, uint4 sl, V3<R> o, V
         const bool may = bool(int(!leaves_only) | int(ch[k] < 0));
         nr[k] = bool(int(out) & int(may)) ? kNoEntry : nr[k];
     }
+}
+
+// Lower bound on the squared distance from the point q to the box [lo, hi], all three in R, whatever roundings produced them:
+// per axis the gap max(lo - q, q - hi, 0) is taken in R and then shrunk by 2 eps (|q| + max(|lo|, |hi|)), eps = Lim<R>::eps()
+// = two unit roundoffs, which covers a rounding of q (the f64 point rounded to R, one unit roundoff of |q|), a rounding of
+// the plane (one of |plane|) and the subtraction's own (one of the gap, itself at most |q| + |plane|) with a unit roundoff
+// of each to spare; the sum of the three squares is shrunk by 4 eps for its five roundings.  Nothing here leans on the
+// boxes' padding (DESIGN.md section 20 has the argument in full).  A NaN anywhere gives NaN: the caller's `lb < r2` is false.
+template <typename R> RT_DEV R box_dist2_below(V3<R> lo, V3<R> hi, V3<R> q) {
+    const R e2 = Lim<R>::eps() * R(2);
+    const R gx = fmax(fmax(lo.x - q.x, q.x - hi.x), R(0)) - e2 * (fabs(q.x) + fmax(fabs(lo.x), fabs(hi.x)));
+    const R gy = fmax(fmax(lo.y - q.y, q.y - hi.y), R(0)) - e2 * (fabs(q.y) + fmax(fabs(lo.y), fabs(hi.y)));
+    const R gz = fmax(fmax(lo.z - q.z, q.z - hi.z), R(0)) - e2 * (fabs(q.z) + fmax(fabs(lo.z), fabs(hi.z)));
+    const R ax = gx > R(0) ? gx : R(0), ay = gy > R(0) ? gy : R(0), az = gz > R(0) ? gz : R(0);
+    return (ax * ax + ay * ay + az * az) * (R(1) - Lim<R>::eps() * R(4));
+}
+
+// Distance step of a point query over a BvhNode4q (h0..h2: its first 48 bytes): lb[k] = a lower bound on the squared
+// object-space distance from q to child k's decoded box (box_dist2_below on planes decoded in R: org + q * cell, the product
+// exact, the sum rounded once in f32 and exact or rounded once in f64), kNoEntry for ch[k] == kEmptyChild.  No cone or slab
+// word is read: facing does not matter to a distance.
+template <typename R> RT_DEV void node4q_dist2(uint4 h0, uint4 h1, uint4 h2, V3<R> q, const int32_t (&ch)[4], R (&lb)[4]) {
+    const R ox = R(__uint_as_float(h0.x)), oy = R(__uint_as_float(h0.y)), oz = R(__uint_as_float(h0.z));
+    const R cx = R(__uint_as_float(h0.w)), cy = R(__uint_as_float(h1.x)), cz = R(__uint_as_float(h1.y));
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const V3<R> lo = {ox + R((h1.z >> (8 * k)) & 0xFFu) * cx, oy + R((h1.w >> (8 * k)) & 0xFFu) * cy, oz + R((h2.x >> (8 * k)) & 0xFFu) * cz};
+        const V3<R> hi = {ox + R((h2.y >> (8 * k)) & 0xFFu) * cx, oy + R((h2.z >> (8 * k)) & 0xFFu) * cy, oz + R((h2.w >> (8 * k)) & 0xFFu) * cz};
+        lb[k] = ch[k] != kEmptyChild ? box_dist2_below(lo, hi, q) : R(kNoEntry);
+    }
+}
+
+// f32 value that is certainly <= x for x >= 0 (finite or +inf; +inf and values beyond the f32 range give FLT_MAX).
+template <typename R> RT_DEV float f32_at_most(R x) {
+    const float f = fminf(float(x), 3.402823466e+38f);
+    return f < 1e-30f ? 0.0f : f - f * 9.5367431640625e-7f;  // 2^-20 relative; below the range where that is 8 ulps: 0
 }
 
 // Sorts the four (entry distance, child) pairs of the arrays nr / ch in place, nearest first (5 compare-exchanges); kNoEntry

@@ -2,7 +2,9 @@
 """Per-kernel register / scratch / occupancy table of the device library, from hipcc's own
 `-Rpass-analysis=kernel-resource-usage` remarks (cross-compiles for gfx950: no GPU needed).
 
-    python tools/kernel_resources.py [extra hipcc flags ...]      e.g.  -DRT_SHADE_WAVES=3
+    python tools/kernel_resources.py [--src=<file in csrc>] [extra hipcc flags ...]      e.g.  -DRT_SHADE_WAVES=3
+
+--src names another translation unit than rt_kernels.hip, e.g. --src=rt_point.hip.
 """
 import os
 import re
@@ -16,10 +18,11 @@ CXXFILT = "c++filt"
 
 
 def main():
-    extra = sys.argv[1:]
+    extra = [a for a in sys.argv[1:] if not a.startswith("--src=")]
+    src = ([os.path.join(os.path.dirname(SRC), a.split("=", 1)[1]) for a in sys.argv[1:] if a.startswith("--src=")] or [SRC])[-1]
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-               "--offload-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", SRC,
+               "--offload-device-only", "-c", "-Rpass-analysis=kernel-resource-usage", src,
                "-o", os.path.join(tmp, "k.o")] + extra
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
