@@ -292,6 +292,9 @@ int rt_debug_scene_mesh(const RtScene* scene, uint32_t mesh, uint32_t f32, int32
  * out[7] = number of updates so far.  A scene refitted by kernels and one whose tables the host derived from the same
  * tree and vertices give equal digests.                                                                               */
 int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[8]);
+/* The same seven digests of the tables as the host derives them for rt_scene_create(desc) (host only unless the scene
+ * asks for the device BVH builder, which runs on the current device); out[7] = 0.  What a fresh scene uploads. */
+int rt_scene_tables_digest(const RtSceneDesc* desc, uint32_t f32, uint64_t out[8]);
 /* Diagnostic: what the library holds through HIP in this process, over all scenes and accumulators: out[0] = live device
  * buffers, out[1] = their bytes, out[2] = live pinned host buffers, out[3] = live events + streams.  Counted where the
  * library allocates, so other users of the card do not show.                                                          */

@@ -350,6 +350,9 @@ def load_device_lib() -> C.CDLL:
         if hasattr(lib, "rt_scene_mesh_stats"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_scene_mesh_stats.argtypes = [C.POINTER(RtSceneDesc), C.POINTER(C.c_uint64)]
             lib.rt_scene_mesh_stats.restype = C.c_int
+        if hasattr(lib, "rt_scene_tables_digest"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            lib.rt_scene_tables_digest.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.POINTER(C.c_uint64)]
+            lib.rt_scene_tables_digest.restype = C.c_int
         if hasattr(lib, "rt_scene_mesh_cones"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_scene_mesh_cones.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32,
                                                 C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
@@ -516,6 +519,17 @@ def scene_mesh_stats(desc) -> dict:
                     [int(x) for x in out]))
 
 
+def scene_tables_digest(desc, f32: bool = False) -> tuple:
+    """rt_scene_tables_digest: digests of the seven mesh tables as the host derives them for DeviceScene(desc), in the order
+    of DeviceScene.debug_mesh_digest (whose first seven entries they equal once the tables are on the device); the eighth is
+    0.  Host only."""
+    lib = load_device_lib()
+    out = (C.c_uint64 * 8)()
+    st = lib.rt_scene_tables_digest(desc, int(f32), out)
+    _check(lib, st)
+    return tuple(int(x) for x in out)
+
+
 def live_resources() -> tuple:
     """rt_debug_live_resources: (live device buffers, their bytes, live pinned host buffers, live events + streams) that the
     library holds in this process."""
@@ -608,7 +622,7 @@ def _mesh_export(call) -> dict:
 
 
 def scene_refit_mesh(a, b, mesh: int = 0, f32: bool = False) -> dict:
-    """rt_scene_refit_mesh: the refit restated on the CPU (host only): the tree DeviceScene(a) builds for mesh instance
+    """rt_scene_refit_mesh: the refit on the CPU (host only, through the derivation that fills the device): the tree DeviceScene(a) builds for mesh instance
     `mesh`, carrying the geometry of `b`.  {"children" (n, 4) int32, "cones" (n, 4, 4) int8, "boxes" (n, 4, 2, 3) float32
     decoded quantised child boxes (lo, hi; empty child: lo > hi), "tris" (t, 3, 3) float64 (v0, e1, e2 in the kernels'
     arithmetic type), "order" (t,) uint32 leaf slot -> original triangle}."""

@@ -374,7 +374,7 @@ void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<T
 //  Together 24 u |q|_1 G.  For a ray that hits, oc and X lie in the mesh's box: |org_i| <= S, |r_i| <= 2 S / s, so
 //  G <= max(2 S / s, 128) and 24 u |q|_1 G <= |q|_1 max(48 u S / s, 2^-12.4) <= M (2 m = 64 u S).  The 16 u S / s left over
 //  cover tn and tf: the child's box holds X with the margin m on every side and the box test's own rounding is below
-//  2.5 x 2^-23 S |iv| per plane (rt_kernels.hip), so tn <= tau <= tf; tau >= 0 up to one rounding of t_shift and
+//  2.5 x 2^-23 S |iv| per plane (rt_tables.cpp), so tn <= tau <= tf; tau >= 0 up to one rounding of t_shift and
 //  tau <= tmax32 by f32_at_least.  The function L(t) = A + t B with the COMPUTED A and B is exactly linear, so L(tau) lies
 //  between L(tn) and L(tf), and L(tau) is within M of P(X), which lies in the unwidened slab: pn and pf cannot both be on the
 //  same side outside [lo, hi].

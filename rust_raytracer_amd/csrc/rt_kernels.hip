@@ -24,6 +24,7 @@
 #include "rt_point.h"
 #include "rt_query.h"
 #include "rt_refit.h"
+#include "rt_tables.h"
 #include "rt_wavefront.h"
 
 namespace rt {
@@ -250,10 +251,6 @@ struct DeviceBuffers {
     }
 };
 
-template <typename R, size_t N> void cast_arr(R (&dst)[N], const double (&src)[N]) {
-    for (size_t i = 0; i < N; i++) dst[i] = R(src[i]);
-}
-
 // Scene tables in arithmetic type R on the device.
 template <typename R>
 struct DeviceScene {
@@ -261,285 +258,55 @@ struct DeviceScene {
     DeviceBuffers buf;
     SceneView<R> view{};
 
+    // The tables are derived on the host (rt_tables.cpp); this uploads them, one buffer each.
     // keep != NULL (rt_scene_update): the mesh tables (BVH nodes of every format, triangle records, attributes) are not
     // derived and uploaded but stay the arrays of `keep`, which the refit kernels rewrite; take_mesh_tables() moves their
     // ownership over once the update is certain.
     int build(const CompiledScene& cs, const DeviceScene<R>* keep = nullptr) {
-        const bool mesh_tables = keep == nullptr;
-        std::vector<Bounds<R>> bounds(cs.bounds.size());
-        for (size_t i = 0; i < bounds.size(); i++) {
-            // list/bvh bounds are part of the reference's semantics (inverted boxes cull, B-8): nearest rounding
-            cast_arr(bounds[i].lo, cs.bounds[i].lo);
-            cast_arr(bounds[i].hi, cs.bounds[i].hi);
-        }
-        std::vector<Xform<R>> xforms(cs.xforms.size());
-        for (size_t i = 0; i < xforms.size(); i++) {
-            cast_arr(xforms[i].m, cs.xforms[i].m);
-            cast_arr(xforms[i].inv, cs.xforms[i].inv);
-        }
-        std::vector<SpherePrim<R>> spheres(cs.spheres.size());
-        for (size_t i = 0; i < spheres.size(); i++) {
-            cast_arr(spheres[i].center, cs.spheres[i].center);
-            spheres[i].radius = R(cs.spheres[i].radius);
-            spheres[i].material = cs.spheres[i].material;
-            spheres[i]._pad = 0;
-        }
-        std::vector<PlanePrim<R>> planes(cs.planes.size());
-        for (size_t i = 0; i < planes.size(); i++) {
-            const auto& s = cs.planes[i];
-            cast_arr(planes[i].corner, s.corner); cast_arr(planes[i].normal, s.normal);
-            cast_arr(planes[i].u, s.u); cast_arr(planes[i].v, s.v);
-            cast_arr(planes[i].inv_u, s.inv_u); cast_arr(planes[i].inv_v, s.inv_v);
-            planes[i].area = R(s.area);
-            planes[i].material = s.material;
-            planes[i].backface = s.backface;
-        }
-        std::vector<SunPrim<R>> suns(cs.suns.size());
-        for (size_t i = 0; i < suns.size(); i++) {
-            cast_arr(suns[i].direction, cs.suns[i].direction);
-            suns[i].material = cs.suns[i].material;
-            suns[i]._pad = 0;
-        }
-        std::vector<BvhNode<R>> nodes(mesh_tables ? cs.nodes.size() : 0);
-        for (size_t i = 0; i < nodes.size(); i++) {
-            const BuildNode& s = cs.nodes[i];
-            BvhNode<R>& n = nodes[i];
-            // Conservative boxes: outward rounding plus a few ulps so that the slab arithmetic
-            // never culls a triangle the exact test would hit.
-            for (int a = 0; a < 3; a++) {  // the formula: rt_refit.h
-                rf_pad_box2<R>(s.lo0[a], s.hi0[a], &n.lo0[a], &n.hi0[a]);
-                rf_pad_box2<R>(s.lo1[a], s.hi1[a], &n.lo1[a], &n.hi1[a]);
-            }
-            n.c0 = s.c0;
-            n.c1 = s.c1;
-        }
-        // 4-wide f32 nodes: pad by 2^-19 x (largest |coordinate| of the mesh), round outward
-        std::vector<BvhNode4f> nodes4(mesh_tables ? cs.nodes4.size() : 0);
-        {
-            size_t inst = 0;
-            std::vector<std::pair<uint32_t, double>> pads;  // (node4_base, pad) per distinct mesh, ascending base
-            for (const MeshInst& mi : cs.meshes) {
-                const Bounds<double>& b = cs.mesh_bounds[inst++];
-                pads.emplace_back(mi.node4_base, rf_pad_of_box(b.lo, b.hi));
-            }
-            std::sort(pads.begin(), pads.end());
-            size_t pi = 0;
-            for (size_t i = 0; i < nodes4.size(); i++) {
-                while (pi + 1 < pads.size() && pads[pi + 1].first <= i) pi++;
-                const double m = pads.empty() ? 0.0 : pads[pi].second;
-                const BuildNode4& sn = cs.nodes4[i];
-                BvhNode4f& dn = nodes4[i];
-                for (int k = 0; k < 4; k++) {
-                    float* lo[3] = {&dn.lox[k], &dn.loy[k], &dn.loz[k]};
-                    float* hi[3] = {&dn.hix[k], &dn.hiy[k], &dn.hiz[k]};
-                    for (int a = 0; a < 3; a++) rf_pad_box4f(sn.lo[k][a], sn.hi[k][a], m, lo[a], hi[a]);
-                    dn.child[k] = sn.child[k];
-                    dn._pad[k] = 0;
-                }
-            }
-        }
-        // Quantised nodes: the padded child boxes (as in BvhNode4f: 2^-19 S, rounded outward to f32) on a per-node 8-bit
-        // grid, rounded outward on the grid.  k_wf_mesh evaluates t = fma(q, cell * iv, fma(org, iv, -o * iv)): cell is a
-        // power of two (cell * iv exact), so against the f32-node test (fma(plane, iv, -o * iv)) there is one more rounding,
-        // of a value bounded by 2 S |iv|; with it the error is < 2.5 x 2^-23 S |iv| per plane, inside the padding.
-        std::vector<BvhNode4q> nodes4q(mesh_tables ? cs.nodes4.size() : 0);
-        std::vector<BvhNode4q> group_nodes;
-        std::vector<double> node_pad;  // per mesh node: the pad of its mesh
-        {
-            auto pad_of = [&]() {
-                std::vector<std::pair<uint32_t, double>> pads;
-                size_t inst = 0;
-                for (const MeshInst& mi : cs.meshes) {
-                    const Bounds<double>& b = cs.mesh_bounds[inst++];
-                    pads.emplace_back(mi.node4_base, rf_pad_of_box(b.lo, b.hi));
-                }
-                std::sort(pads.begin(), pads.end());
-                return pads;
-            };
-            // one node (the formula: rt_refit.h)
-            auto quantise = [](const BuildNode4& sn, double m, BvhNode4q& qn) -> bool {
-                for (int k = 0; k < 4; k++) qn.child[k] = sn.child[k];
-                return rf_quantise4(sn.lo, sn.hi, sn.child, m, qn.org, qn.cell, qn.qlo, qn.qhi);
-            };
-            const auto pads4 = pad_of();
-            size_t pi = 0;
-            node_pad.resize(nodes4q.size());
-            for (size_t i = 0; i < nodes4q.size(); i++) {
-                while (pi + 1 < pads4.size() && pads4[pi + 1].first <= i) pi++;
-                const BuildNode4& sn = cs.nodes4[i];
-                BvhNode4q& qn = nodes4q[i];
-                node_pad[i] = pads4.empty() ? 0.0 : pads4[pi].second;
-                if (!quantise(sn, node_pad[i], qn))
-                    return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
-            }
-            // the primitive groups' BVHs: same node format, same padding rule (2^-19 x the largest |coordinate| of the group's box)
-            group_nodes.resize(cs.group_nodes4.size());
-            for (size_t g = 0; g < cs.groups.size(); g++) {
-                const GroupRec<double>& gr = cs.groups[g];
-                double S = 0.0;
-                for (int a = 0; a < 3; a++) S = std::fmax(S, std::fmax(std::fabs(gr.lo[a]), std::fabs(gr.hi[a])));
-                if (!std::isfinite(S)) return set_err(RT_E_UNSUPPORTED, "primitive group with an unbounded box");
-                const size_t end = g + 1 < cs.groups.size() ? cs.groups[g + 1].root : cs.group_nodes4.size();
-                for (size_t i = gr.root; i < end; i++) {
-                    const BuildNode4& sn = cs.group_nodes4[i];
-                    BvhNode4q& qn = group_nodes[i];
-                    if (!quantise(sn, S * (1.0 / 524288.0), qn))
-                        return set_err(RT_E_UNSUPPORTED, "group BVH node does not fit the 8-bit grid");
-                }
-            }
-        }
-        // back-face cone words of the mesh nodes' children, with the conditioning limits of this arithmetic type (rt_bvh.cpp)
-        std::vector<uint32_t> cone_words;
-        if (mesh_tables) build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &cone_words);
-        // and their normal slabs, on the cones' axes
-        std::vector<uint32_t> slab_words;
-        if (mesh_tables) build_mesh_slabs(cs.nodes4, cs.tris, cone_words, nodes4q.data(), node_pad.data(), &slab_words);
-        std::vector<MeshNode4qc> nodes4qc(mesh_tables ? cs.nodes4.size() : 0);
-        for (size_t i = 0; i < nodes4qc.size(); i++) {
-            nodes4qc[i].node = nodes4q[i];
-            for (int k = 0; k < 4; k++) nodes4qc[i].cones.word[k] = cone_words[4 * i + size_t(k)];
-            for (int k = 0; k < 4; k++) nodes4qc[i].slabs.word[k] = slab_words[4 * i + size_t(k)];
-            for (uint32_t& x : nodes4qc[i]._pad) x = 0;
-        }
-        std::vector<Bounds<R>> mesh_bounds(cs.mesh_bounds.size());
-        for (size_t i = 0; i < mesh_bounds.size(); i++)
-            for (int a = 0; a < 3; a++) {  // outward: this box only decides which rays are queued for the mesh
-                mesh_bounds[i].lo[a] = round_down<R>(cs.mesh_bounds[i].lo[a]);
-                mesh_bounds[i].hi[a] = round_up<R>(cs.mesh_bounds[i].hi[a]);
-            }
-        std::vector<TriRec<R>> tris(mesh_tables ? cs.tris.size() : 0);
-        for (size_t i = 0; i < tris.size(); i++) {
-            cast_arr(tris[i].v0, cs.tris[i].v0); cast_arr(tris[i].e1, cs.tris[i].e1); cast_arr(tris[i].e2, cs.tris[i].e2);
-            tris[i]._pad = R(0);
-        }
-        std::vector<TriAttr<R>> attrs(mesh_tables ? cs.attrs.size() : 0);
-        for (size_t i = 0; i < attrs.size(); i++) {
-            const auto& s = cs.attrs[i];
-            cast_arr(attrs[i].n0, s.n0); cast_arr(attrs[i].n1, s.n1); cast_arr(attrs[i].n2, s.n2);
-            cast_arr(attrs[i].uv0, s.uv0); cast_arr(attrs[i].uv1, s.uv1); cast_arr(attrs[i].uv2, s.uv2);
-            attrs[i].has_uv = s.has_uv;
-            attrs[i]._pad = 0;
-        }
-        std::vector<MaterialParams<R>> mparams(cs.material_params.size());
-        for (size_t i = 0; i < mparams.size(); i++) {
-            mparams[i].ior = R(cs.material_params[i].ior);
-            mparams[i].inv_ior = R(cs.material_params[i].inv_ior);
-            auto r0_of = [](R x) { R r0 = (R(1) - x) / (R(1) + x); return r0 * r0; };  // utils.rs:32-33, in R like reflectance()
-            mparams[i].inv_ior_r = R(1) / mparams[i].ior;
-            mparams[i].r0_glossy = r0_of(mparams[i].inv_ior);
-            mparams[i].r0_front = r0_of(mparams[i].inv_ior_r);
-            mparams[i].r0_back = r0_of(mparams[i].ior);
-        }
-        std::vector<TextureRec<R>> textures(cs.textures.size());
-        for (size_t i = 0; i < textures.size(); i++) {
-            const auto& s = cs.textures[i];
-            textures[i].type = s.type; textures[i].aux = s.aux; textures[i].data = s.data;
-            textures[i].width = s.width; textures[i].height = s.height; textures[i]._pad = 0;
-            cast_arr(textures[i].v, s.v);
-            textures[i].scale = R(s.scale);
-        }
-        std::vector<VolumeRec<R>> volumes(cs.volumes.size());
-        for (size_t i = 0; i < volumes.size(); i++) {
-            volumes[i].neg_inv_density = R(cs.volumes[i].neg_inv_density);
-            volumes[i].material = cs.volumes[i].material;
-            volumes[i]._pad = 0;
-        }
-        std::vector<R> perlin_vec(cs.perlin_vec.size());
-        for (size_t i = 0; i < perlin_vec.size(); i++) perlin_vec[i] = R(cs.perlin_vec[i]);
+        MeshTables<R> m;
+        SceneTables<R> t;
+        std::string err;
         int st;
+        if (!keep && (st = derive_mesh_tables(cs, &m, &err)) != RT_OK) return set_err(st, err);
+        if ((st = derive_scene_tables(cs, &t, &err)) != RT_OK) return set_err(st, err);
+        view = t.view;  // the scalars and the blobs' layouts; then every table into a buffer of its own
         if ((st = buf.upload(cs.ops, &view.ops)) != RT_OK) return st;
-        if ((st = buf.upload(bounds, &view.bounds)) != RT_OK) return st;
+        if ((st = buf.upload(t.bounds, &view.bounds)) != RT_OK) return st;
         if ((st = buf.upload(cs.chain_offsets, &view.chain_offsets)) != RT_OK) return st;
         if ((st = buf.upload(cs.chain_items, &view.chain_items)) != RT_OK) return st;
-        if ((st = buf.upload(xforms, &view.xforms)) != RT_OK) return st;
-        if ((st = buf.upload(spheres, &view.spheres)) != RT_OK) return st;
-        if ((st = buf.upload(planes, &view.planes)) != RT_OK) return st;
-        if ((st = buf.upload(suns, &view.suns)) != RT_OK) return st;
+        if ((st = buf.upload(t.xforms, &view.xforms)) != RT_OK) return st;
+        if ((st = buf.upload(t.spheres, &view.spheres)) != RT_OK) return st;
+        if ((st = buf.upload(t.planes, &view.planes)) != RT_OK) return st;
+        if ((st = buf.upload(t.suns, &view.suns)) != RT_OK) return st;
         if ((st = buf.upload(cs.meshes, &view.meshes)) != RT_OK) return st;
-        if ((st = buf.upload(volumes, &view.volumes)) != RT_OK) return st;
-        if (mesh_tables) {
-            if ((st = buf.upload(nodes, &view.nodes)) != RT_OK) return st;
-            if ((st = buf.upload(nodes4, &view.nodes4)) != RT_OK) return st;
-            if ((st = buf.upload(nodes4qc, &view.nodes4q)) != RT_OK) return st;
-            if ((st = buf.upload(tris, &view.tris)) != RT_OK) return st;
-            if ((st = buf.upload(attrs, &view.attrs)) != RT_OK) return st;
+        if ((st = buf.upload(t.volumes, &view.volumes)) != RT_OK) return st;
+        if (!keep) {
+            if ((st = buf.upload(m.nodes, &view.nodes)) != RT_OK) return st;
+            if ((st = buf.upload(m.nodes4, &view.nodes4)) != RT_OK) return st;
+            if ((st = buf.upload(m.nodes4qc, &view.nodes4q)) != RT_OK) return st;
+            if ((st = buf.upload(m.tris, &view.tris)) != RT_OK) return st;
+            if ((st = buf.upload(m.attrs, &view.attrs)) != RT_OK) return st;
         } else {
             view.nodes = keep->view.nodes; view.nodes4 = keep->view.nodes4; view.nodes4q = keep->view.nodes4q;
             view.tris = keep->view.tris; view.attrs = keep->view.attrs;
         }
-        if ((st = buf.upload(mesh_bounds, &view.mesh_bounds)) != RT_OK) return st;
+        if ((st = buf.upload(t.mesh_bounds, &view.mesh_bounds)) != RT_OK) return st;
         if ((st = buf.upload(cs.mesh_ops, &view.mesh_ops)) != RT_OK) return st;
-        view.n_mesh_ops = int32_t(cs.mesh_ops.size());
-        std::vector<MeshOpRec<R>> mesh_op_recs(cs.mesh_ops.size());
-        for (size_t m = 0; m < mesh_op_recs.size(); m++) {
-            const Op& op = cs.ops[size_t(cs.mesh_ops[m])];
-            const MeshInst& mi = cs.meshes[size_t(op.arg)];
-            MeshOpRec<R>& r = mesh_op_recs[m];
-            r.pc = cs.mesh_ops[m];
-            r.chain = op.chain;
-            r.node4_base = mi.node4_base;
-            const int32_t cb = cs.chain_offsets[size_t(op.chain)], ce = cs.chain_offsets[size_t(op.chain) + 1];
-            r.flags = (mi.flags & 0xFFFFu) | (uint32_t(std::min(ce - cb, 0xFFFF)) << 16);
-            for (int a = 0; a < 3; a++) { r.lo[a] = mesh_bounds[size_t(op.arg)].lo[a]; r.hi[a] = mesh_bounds[size_t(op.arg)].hi[a]; }
-            for (int k = 0; k < 12; k++) r.inv[k] = ce - cb == 1 ? xforms[size_t(cs.chain_items[size_t(cb)])].inv[k] : R(0);
-        }
-        if ((st = buf.upload(mesh_op_recs, &view.mesh_op_recs)) != RT_OK) return st;
-        std::vector<GroupRec<R>> groups(cs.groups.size());
-        for (size_t g = 0; g < groups.size(); g++) {
-            groups[g].root = cs.groups[g].root;
-            for (int a = 0; a < 3; a++) { groups[g].lo[a] = round_down<R>(cs.groups[g].lo[a]); groups[g].hi[a] = round_up<R>(cs.groups[g].hi[a]); }
-        }
-        if ((st = buf.upload(groups, &view.groups)) != RT_OK) return st;
-        if ((st = buf.upload(group_nodes, &view.group_nodes)) != RT_OK) return st;
+        if ((st = buf.upload(t.mesh_op_recs, &view.mesh_op_recs)) != RT_OK) return st;
+        if ((st = buf.upload(t.groups, &view.groups)) != RT_OK) return st;
+        if ((st = buf.upload(t.group_nodes, &view.group_nodes)) != RT_OK) return st;
         if ((st = buf.upload(cs.group_prims, &view.group_prims)) != RT_OK) return st;
         if ((st = buf.upload(cs.group_guards, &view.group_guards)) != RT_OK) return st;
-        view.n_group_nodes = int32_t(group_nodes.size());
-        view.group_stack_levels = int32_t(cs.max_group_stack);
         if ((st = buf.upload(cs.materials, &view.materials)) != RT_OK) return st;
-        if ((st = buf.upload(mparams, &view.material_params)) != RT_OK) return st;
-        if ((st = buf.upload(textures, &view.textures)) != RT_OK) return st;
+        if ((st = buf.upload(t.material_params, &view.material_params)) != RT_OK) return st;
+        if ((st = buf.upload(t.textures, &view.textures)) != RT_OK) return st;
         if ((st = buf.upload(cs.texels, &view.texels)) != RT_OK) return st;
-        if ((st = buf.upload(perlin_vec, &view.perlin_vec)) != RT_OK) return st;
+        if ((st = buf.upload(t.perlin_vec, &view.perlin_vec)) != RT_OK) return st;
         if ((st = buf.upload(cs.perlin_perm, &view.perlin_perm)) != RT_OK) return st;
         if ((st = buf.upload(cs.lights, &view.lights)) != RT_OK) return st;
-        // the same small tables once more, packed for LDS staging: once in k_wf_prims' order, once in k_wf_shade's
-        {
-            struct Tbl { const void* data; size_t bytes; };
-            const Tbl tbl[ST_COUNT] = {
-                {cs.ops.data(), cs.ops.size() * sizeof(Op)}, {bounds.data(), bounds.size() * sizeof(Bounds<R>)},
-                {cs.chain_offsets.data(), cs.chain_offsets.size() * 4}, {cs.chain_items.data(), cs.chain_items.size() * 4},
-                {xforms.data(), xforms.size() * sizeof(Xform<R>)}, {spheres.data(), spheres.size() * sizeof(SpherePrim<R>)},
-                {planes.data(), planes.size() * sizeof(PlanePrim<R>)}, {suns.data(), suns.size() * sizeof(SunPrim<R>)},
-                {cs.meshes.data(), cs.meshes.size() * sizeof(MeshInst)}, {cs.materials.data(), cs.materials.size() * sizeof(MaterialRec)},
-                {mparams.data(), mparams.size() * sizeof(MaterialParams<R>)}, {textures.data(), textures.size() * sizeof(TextureRec<R>)},
-                {cs.lights.data(), cs.lights.size() * sizeof(LightRec)}};
-            auto pack = [&](const int (&order)[ST_COUNT], SmallLayout& L, const char** out) -> int {
-                std::vector<char> blob;
-                for (int k : order) {
-                    const size_t off = (blob.size() + 15) & ~size_t(15);
-                    blob.resize(off + tbl[k].bytes);
-                    if (tbl[k].bytes) std::memcpy(blob.data() + off, tbl[k].data, tbl[k].bytes);
-                    L.begin[k] = uint32_t(off);
-                    L.end[k] = uint32_t(off + tbl[k].bytes);
-                }
-                blob.resize((blob.size() + 15) & ~size_t(15));
-                L.total_bytes = uint32_t(blob.size());
-                return buf.upload(blob, out);
-            };
-            const int order_prims[ST_COUNT] = {ST_OPS, ST_CHAIN_OFFSETS, ST_CHAIN_ITEMS, ST_XFORMS, ST_MESHES, ST_SUNS, ST_PLANES, ST_BOUNDS, ST_SPHERES,
-                                               ST_MATERIALS, ST_MATERIAL_PARAMS, ST_LIGHTS, ST_TEXTURES};
-            const int order_shade[ST_COUNT] = {ST_OPS, ST_CHAIN_OFFSETS, ST_CHAIN_ITEMS, ST_XFORMS, ST_MESHES, ST_SUNS, ST_LIGHTS, ST_PLANES, ST_MATERIALS,
-                                               ST_MATERIAL_PARAMS, ST_TEXTURES, ST_SPHERES, ST_BOUNDS};
-            if ((st = pack(order_prims, view.lay, &view.small_blob)) != RT_OK) return st;
-            if ((st = pack(order_shade, view.lay_shade, &view.small_blob_shade)) != RT_OK) return st;
-        }
-        view.n_lights = cs.n_top_lights;
-        view.inv_n_lights = R(1) / R(cs.n_top_lights);
-        view.lights_is_list = cs.lights_is_list;
-        view.stop_on_zero_weight = cs.zero_weight_stop ? 1 : 0;
+        if ((st = buf.upload(t.blob_prims, &view.small_blob)) != RT_OK) return st;
+        if ((st = buf.upload(t.blob_shade, &view.small_blob_shade)) != RT_OK) return st;
         if (const char* e = std::getenv("RT_ZERO_WEIGHT_STOP")) view.stop_on_zero_weight = std::atoi(e) != 0;  // experiments
-        view.stack_entries = int32_t(std::max(cs.max_bvh_depth + 2, cs.max_bvh4_stack + 1));
-        view.n_ops = int32_t(cs.ops.size());
         // The uploads above went through the null stream (small pageable copies may return once
         // staged); the render kernels run on a NON-BLOCKING stream that is not ordered against it.
         HIP_TRY(hipDeviceSynchronize());
@@ -2168,26 +1935,6 @@ __global__ void __launch_bounds__(256) k_tonemap_rgb8(const double* __restrict__
     }
 }
 
-// 64-bit digest of byte strings (checkpoint identity, not security): 8-byte words through a multiply-rotate round
-struct Digest {
-    uint64_t h = 0x243F6A8885A308D3ull;
-    void word(uint64_t w) {
-        w *= 0x9E3779B97F4A7C15ull;
-        w ^= w >> 29;
-        h = ((h ^ w) * 0xBF58476D1CE4E5B9ull);
-        h = (h << 27) | (h >> 37);
-    }
-    void bytes(const void* p, size_t n) {
-        const unsigned char* b = static_cast<const unsigned char*>(p);
-        word(n);
-        if (!b) return;
-        for (; n >= 8; n -= 8, b += 8) { uint64_t w; std::memcpy(&w, b, 8); word(w); }
-        if (n) { uint64_t w = 0; std::memcpy(&w, b, n); word(w); }
-    }
-    template <typename T> void val(const T& v) { bytes(&v, sizeof v); }
-    uint64_t value() const { uint64_t x = h ^ (h >> 31); x *= 0x94D049BB133111EBull; return x ^ (x >> 29); }
-};
-
 // Everything an RtSceneDesc points at, field by field (never a pointer value, never padding).  Not the flags: the BVH
 // builder only culls, a frame does not depend on it.
 static uint64_t scene_digest(const RtSceneDesc& d) {
@@ -2320,12 +2067,7 @@ static void mesh_export(const CompiledScene::MeshGeom& g, const MeshNode4qc* nod
     for (uint32_t i = 0; i < g.n_nodes4 && i < o.node_capacity; i++) {
         const MeshNode4qc& n = nodes[i];
         for (int k = 0; k < 4; k++) {
-            int32_t ch = n.node.child[k];
-            if (ch != kEmptyChild) {
-                if (ch >= 0) ch -= int32_t(g.node4_base);
-                else { const uint32_t code = uint32_t(~ch); ch = ~int32_t((((code >> 3) - g.tri_base) << 3) | (code & 7u)); }
-            }
-            if (o.children) o.children[4 * size_t(i) + size_t(k)] = ch;
+            if (o.children) o.children[4 * size_t(i) + size_t(k)] = mesh_relative_child(n.node.child[k], g);
             if (o.cones) o.cones[4 * size_t(i) + size_t(k)] = n.cones.word[k];
             if (o.boxes)
                 for (int a = 0; a < 3; a++) {
@@ -2344,25 +2086,13 @@ static void mesh_export(const CompiledScene::MeshGeom& g, const MeshNode4qc* nod
         if (o.tri_order) o.tri_order[t] = order[t];
     }
 }
-// The host builder's tables of one mesh in arithmetic type R (as DeviceScene<R>::build derives them)
+// The same from the tables the host derives in arithmetic type R (rt_tables.cpp): what DeviceScene<R>::build uploads
 template <typename R>
-static int mesh_export_host(const CompiledScene& cs, const CompiledScene::MeshGeom& g, uint32_t mesh, const MeshExportOut& o) {
-    std::vector<uint32_t> words;
-    build_mesh_cones(cs.nodes4, cs.tris, cone_limits(sizeof(R) == 4), &words);
-    const double pad = rf_pad_of_box(cs.mesh_bounds[mesh].lo, cs.mesh_bounds[mesh].hi);
-    std::vector<MeshNode4qc> nodes(g.n_nodes4);
-    for (uint32_t i = 0; i < g.n_nodes4; i++) {
-        const BuildNode4& sn = cs.nodes4[g.node4_base + i];
-        BvhNode4q& q = nodes[i].node;
-        if (!rf_quantise4(sn.lo, sn.hi, sn.child, pad, q.org, q.cell, q.qlo, q.qhi)) return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
-        for (int k = 0; k < 4; k++) { q.child[k] = sn.child[k]; nodes[i].cones.word[k] = words[4 * size_t(g.node4_base + i) + size_t(k)]; }
-    }
-    std::vector<TriRec<R>> tris(g.n_tris);
-    for (uint32_t t = 0; t < g.n_tris; t++) {
-        const TriRec<double>& r = cs.tris[g.tri_base + t];
-        cast_arr(tris[t].v0, r.v0); cast_arr(tris[t].e1, r.e1); cast_arr(tris[t].e2, r.e2);
-    }
-    mesh_export<R>(g, nodes.data(), tris.data(), cs.tri_order.data() + g.tri_base, o);
+static int mesh_export_host(const CompiledScene& cs, const CompiledScene::MeshGeom& g, const MeshExportOut& o) {
+    MeshTables<R> m;
+    std::string err;
+    if (int st = derive_mesh_tables(cs, &m, &err)) return set_err(st, err);
+    mesh_export<R>(g, m.nodes4qc.data() + g.node4_base, m.tris.data() + g.tri_base, cs.tri_order.data() + g.tri_base, o);
     return RT_OK;
 }
 template <typename R>
@@ -2386,9 +2116,7 @@ static int refit_typed(RtScene* s, const CompiledScene& cs, const std::vector<ui
         t.nodes4q = const_cast<MeshNode4qc*>(ds.view.nodes4q) + g.node4_base;
         t.tris = const_cast<TriRec<R>*>(ds.view.tris) + g.tri_base;
         t.attrs = const_cast<TriAttr<R>*>(ds.view.attrs) + g.tri_base;
-        t.pad4 = 0.0;
-        for (size_t i = 0; i < cs.meshes.size(); i++)  // any instance of the mesh carries its box
-            if (cs.meshes[i].node4_base == g.node4_base) { t.pad4 = rf_pad_of_box(cs.mesh_bounds[i].lo, cs.mesh_bounds[i].hi); break; }
+        t.pad4 = mesh_pad(cs, g);
         std::string err;
         if (!refit_mesh_launch<R>(s->refit[gi], t, s->stream, &err)) return set_err(RT_E_DEVICE, err);
     }
@@ -2400,6 +2128,33 @@ static CompileOptions compile_options_from_env() {
     CompileOptions opt;
     if (const char* e = std::getenv("RT_PRIM_REBUILD")) opt.rebuild_prim_groups = std::atoi(e) != 0;  // A/B, tests
     return opt;
+}
+// ... and the BVH builder of a scene that is created from `desc`: its flag, which RT_BVH_BUILDER = "device" / "host" overrides.
+static CompileOptions compile_options_for_create(const RtSceneDesc* desc) {
+    CompileOptions opt = compile_options_from_env();
+    const char* builder = std::getenv("RT_BVH_BUILDER");
+    opt.bvh_on_device = desc && (desc->flags & RT_SCENE_BVH_ON_DEVICE) != 0;
+    if (builder && !std::strcmp(builder, "device")) opt.bvh_on_device = true;
+    if (builder && !std::strcmp(builder, "host")) opt.bvh_on_device = false;
+    return opt;
+}
+
+// rt_scene_tables_digest for one arithmetic type: the digests of digest_tables() over the derived vectors.
+template <typename R>
+static int tables_digest_host(const CompiledScene& cs, uint64_t out[8]) {
+    MeshTables<R> m;
+    SceneTables<R> t;
+    std::string err;
+    int st;
+    if ((st = derive_mesh_tables(cs, &m, &err)) != RT_OK || (st = derive_scene_tables(cs, &t, &err)) != RT_OK) return set_err(st, err);
+    const auto tables = digest_tables(cs, m, t);
+    for (int k = 0; k < 7; k++) {
+        Digest g;
+        g.bytes(tables[k].first, tables[k].second);
+        out[k] = g.value();
+    }
+    out[7] = 0;
+    return RT_OK;
 }
 }  // namespace rt
 
@@ -2424,11 +2179,7 @@ int rt_scene_create(const RtSceneDesc* desc, int device, RtScene** out) {
     std::unique_ptr<RtScene> s(new (std::nothrow) RtScene);
     if (!s) return set_err(RT_E_NOMEM, "out of memory");
     std::string err;
-    CompileOptions opt = compile_options_from_env();
-    const char* builder = std::getenv("RT_BVH_BUILDER");  // "device" / "host" override the scene's flag
-    opt.bvh_on_device = desc && (desc->flags & RT_SCENE_BVH_ON_DEVICE) != 0;
-    if (builder && !std::strcmp(builder, "device")) opt.bvh_on_device = true;
-    if (builder && !std::strcmp(builder, "host")) opt.bvh_on_device = false;
+    const CompileOptions opt = compile_options_for_create(desc);
     int n = 0;
     if (opt.bvh_on_device) {  // the device builder needs its device before the scene is compiled
         if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return set_err(RT_E_DEVICE, "no HIP device available");
@@ -2675,14 +2426,7 @@ int rt_scene_update(RtScene* s, const RtSceneDesc* desc, RtSceneUpdateInfo* info
             if (!s->refit[gi].tri_order) {  // relative references, once
                 for (uint32_t i = 0; i < g.n_nodes; i++) { child2[2 * size_t(i)] = cs.nodes[g.node_base + i].c0; child2[2 * size_t(i) + 1] = cs.nodes[g.node_base + i].c1; }
                 for (uint32_t i = 0; i < g.n_nodes4; i++)
-                    for (int k = 0; k < 4; k++) {
-                        int32_t c = cs.nodes4[g.node4_base + i].child[k];
-                        if (c != kEmptyChild) {
-                            if (c >= 0) c -= int32_t(g.node4_base);
-                            else { const uint32_t code = uint32_t(~c); c = ~int32_t((((code >> 3) - g.tri_base) << 3) | (code & 7u)); }
-                        }
-                        child4[4 * size_t(i) + size_t(k)] = c;
-                    }
+                    for (int k = 0; k < 4; k++) child4[4 * size_t(i) + size_t(k)] = mesh_relative_child(cs.nodes4[g.node4_base + i].child[k], g);
             }
             if (!refit_mesh_upload(s->refit[gi], desc->meshes[g.mesh], cs.tri_order.data() + g.tri_base, child2.data(), g.n_nodes, child4.data(), g.n_nodes4,
                                    s->stream, &bytes, &err))
@@ -2748,7 +2492,7 @@ int rt_scene_refit_mesh(const RtSceneDesc* a, const RtSceneDesc* b, uint32_t mes
     const CompiledScene::MeshGeom* g = nullptr;
     if (!mesh_export_range(cb, mesh, &g)) return set_err(RT_E_INVALID, "rt_scene_refit_mesh: mesh index out of range");
     const MeshExportOut o{children_out, cones_out, boxes_out, node_capacity, n_nodes_out, tris_out, tri_order_out, tri_capacity, n_tris_out};
-    return f32 ? mesh_export_host<float>(cb, *g, mesh, o) : mesh_export_host<double>(cb, *g, mesh, o);
+    return f32 ? mesh_export_host<float>(cb, *g, o) : mesh_export_host<double>(cb, *g, o);
 }
 
 int rt_debug_scene_mesh(const RtScene* scene, uint32_t mesh, uint32_t f32, int32_t* children_out, uint32_t* cones_out, float* boxes_out,
@@ -2782,11 +2526,8 @@ int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[
     for (int k = 0; k < 8; k++) out[k] = 0;
     if (int st = with_tables(s, f32 ? RT_PRECISION_F32 : RT_PRECISION_F64, [&](auto& ds) -> int {
             using R = typename std::decay_t<decltype(ds)>::Real;
-            const std::pair<const void*, size_t> tables[7] = {
-                {ds.view.nodes, cs.nodes.size() * sizeof(BvhNode<R>)},        {ds.view.nodes4, cs.nodes4.size() * sizeof(BvhNode4f)},
-                {ds.view.nodes4q, cs.nodes4.size() * sizeof(MeshNode4qc)},    {ds.view.tris, cs.tris.size() * sizeof(TriRec<R>)},
-                {ds.view.attrs, cs.attrs.size() * sizeof(TriAttr<R>)},        {ds.view.mesh_bounds, cs.mesh_bounds.size() * sizeof(Bounds<R>)},
-                {ds.view.mesh_op_recs, cs.mesh_ops.size() * sizeof(MeshOpRec<R>)}};
+            const auto tables = digest_tables<R>(cs, ds.view.nodes, ds.view.nodes4, ds.view.nodes4q, ds.view.tris, ds.view.attrs, ds.view.mesh_bounds,
+                                                 ds.view.mesh_op_recs);
             for (int k = 0; k < 7; k++)
                 if (int st = digest_of(tables[k].first, tables[k].second, &out[k])) return st;
             return RT_OK;
@@ -2794,6 +2535,17 @@ int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[
         return st;
     out[7] = s->generation;
     return RT_OK;
+}
+
+int rt_scene_tables_digest(const RtSceneDesc* desc, uint32_t f32, uint64_t out[8]) {
+    using namespace rt;
+    if (!desc || !out) return set_err(RT_E_INVALID, "rt_scene_tables_digest: NULL argument");
+    const CompileOptions opt = compile_options_for_create(desc);  // the device builder runs on the current device
+    CompiledScene cs;
+    std::string err;
+    int st = compile_scene(desc, &cs, &err, opt);
+    if (st != RT_OK) return set_err(st, err);
+    return f32 ? tables_digest_host<float>(cs, out) : tables_digest_host<double>(cs, out);
 }
 
 int rt_scene_info(const RtSceneDesc* desc, uint32_t* flags_out) {
@@ -2881,34 +2633,17 @@ int rt_scene_mesh_cones(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, in
     std::string err;
     int st = compile_scene(desc, &cs, &err, CompileOptions());
     if (st != RT_OK) return set_err(st, err);
-    if (mesh >= cs.meshes.size()) return set_err(RT_E_INVALID, "rt_scene_mesh_cones: mesh index out of range");
-    const MeshInst& mi = cs.meshes[mesh];
-    size_t node_end = cs.nodes4.size();  // this mesh's nodes end where the next distinct mesh's begin
-    for (const MeshInst& o : cs.meshes)
-        if (o.node4_base > mi.node4_base) node_end = std::min(node_end, size_t(o.node4_base));
-    const size_t n_nodes = node_end - mi.node4_base;
-    *n_nodes_out = uint32_t(n_nodes);
-    *n_tris_out = mi.n_tris;
+    const CompiledScene::MeshGeom* g = nullptr;
+    if (!mesh_export_range(cs, mesh, &g)) return set_err(RT_E_INVALID, "rt_scene_mesh_cones: mesh index out of range");
+    *n_nodes_out = g->n_nodes4;
+    *n_tris_out = g->n_tris;
     if (children_out && cones_out) {
-        std::vector<uint32_t> words;
-        build_mesh_cones(cs.nodes4, cs.tris, cone_limits(f32 != 0), &words);
-        for (size_t i = 0; i < n_nodes && i < node_capacity; i++)
-            for (int k = 0; k < 4; k++) {
-                int32_t ch = cs.nodes4[mi.node4_base + i].child[k];
-                if (ch != kEmptyChild) {
-                    if (ch >= 0) ch -= int32_t(mi.node4_base);
-                    else {
-                        const uint32_t code = uint32_t(~ch);
-                        ch = ~int32_t((((code >> 3) - mi.tri_base) << 3) | (code & 7u));
-                    }
-                }
-                children_out[4 * i + size_t(k)] = ch;
-                cones_out[4 * i + size_t(k)] = words[4 * (mi.node4_base + i) + size_t(k)];
-            }
+        const MeshExportOut o{children_out, cones_out, nullptr, node_capacity, n_nodes_out, nullptr, nullptr, 0, n_tris_out};
+        if ((st = f32 ? mesh_export_host<float>(cs, *g, o) : mesh_export_host<double>(cs, *g, o)) != RT_OK) return st;
     }
     if (tris_out)
-        for (size_t t = 0; t < mi.n_tris && t < tri_capacity; t++) {
-            const TriRec<double>& r = cs.tris[mi.tri_base + t];
+        for (size_t t = 0; t < g->n_tris && t < tri_capacity; t++) {
+            const TriRec<double>& r = cs.tris[g->tri_base + t];
             for (int a = 0; a < 3; a++) { tris_out[9 * t + size_t(a)] = r.v0[a]; tris_out[9 * t + 3 + size_t(a)] = r.e1[a]; tris_out[9 * t + 6 + size_t(a)] = r.e2[a]; }
         }
     return RT_OK;
@@ -2922,40 +2657,25 @@ int rt_scene_mesh_slabs(const RtSceneDesc* desc, uint32_t mesh, uint32_t f32, ui
     std::string err;
     int st = compile_scene(desc, &cs, &err, CompileOptions());
     if (st != RT_OK) return set_err(st, err);
-    if (mesh >= cs.meshes.size()) return set_err(RT_E_INVALID, "rt_scene_mesh_slabs: mesh index out of range");
-    const MeshInst& mi = cs.meshes[mesh];
-    size_t node_end = cs.nodes4.size();  // as rt_scene_mesh_cones
-    for (const MeshInst& o : cs.meshes)
-        if (o.node4_base > mi.node4_base) node_end = std::min(node_end, size_t(o.node4_base));
-    const size_t n_nodes = node_end - mi.node4_base;
-    *n_nodes_out = uint32_t(n_nodes);
-    const double pad = rf_pad_of_box(cs.mesh_bounds[mesh].lo, cs.mesh_bounds[mesh].hi);
-    if (pad_out) *pad_out = pad;
+    const CompiledScene::MeshGeom* g = nullptr;
+    if (!mesh_export_range(cs, mesh, &g)) return set_err(RT_E_INVALID, "rt_scene_mesh_slabs: mesh index out of range");
+    *n_nodes_out = g->n_nodes4;
+    if (pad_out) *pad_out = mesh_pad(cs, *g);
     if (!slabs_out) return RT_OK;
-    // the tables as DeviceScene<R>::build derives them; the other meshes' children get no cone here and so no slab
-    std::vector<uint32_t> cones, slabs;
-    build_mesh_cones(cs.nodes4, cs.tris, cone_limits(f32 != 0), &cones);
-    std::vector<BvhNode4q> qn(cs.nodes4.size());
-    std::vector<double> pads(cs.nodes4.size(), pad);
-    for (size_t i = 0; i < cs.nodes4.size(); i++) {
-        const bool own = i >= mi.node4_base && i < node_end;
-        const BuildNode4& sn = cs.nodes4[i];
-        if (own && !rf_quantise4(sn.lo, sn.hi, sn.child, pad, qn[i].org, qn[i].cell, qn[i].qlo, qn[i].qhi))
-            return set_err(RT_E_UNSUPPORTED, "BVH node does not fit the 8-bit grid");
-        if (!own)
-            for (int k = 0; k < 4; k++) cones[4 * i + size_t(k)] = kNeutralCone;
-    }
-    build_mesh_slabs(cs.nodes4, cs.tris, cones, qn.data(), pads.data(), &slabs);
-    for (size_t i = 0; i < n_nodes && i < node_capacity; i++) {
-        const size_t n = mi.node4_base + i;
+    std::vector<MeshNode4qc> nodes;  // the cone limits are all that depends on the arithmetic type
+    if (f32) { MeshTables<float> m; st = derive_mesh_tables(cs, &m, &err); nodes.swap(m.nodes4qc); }
+    else { MeshTables<double> m; st = derive_mesh_tables(cs, &m, &err); nodes.swap(m.nodes4qc); }
+    if (st != RT_OK) return set_err(st, err);
+    for (size_t i = 0; i < g->n_nodes4 && i < node_capacity; i++) {
+        const MeshNode4qc& n = nodes[g->node4_base + i];
         for (int k = 0; k < 4; k++) {
-            const uint32_t w = slabs[4 * n + size_t(k)];
+            const uint32_t w = n.slabs.word[k];
             slabs_out[4 * i + size_t(k)] = w;
             if (bounds_out) { bounds_out[8 * i + 2 * size_t(k)] = float(int16_t(w & 0xFFFFu)); bounds_out[8 * i + 2 * size_t(k) + 1] = float(int16_t(w >> 16)); }
         }
         if (frames_out) {
-            for (int a = 0; a < 3; a++) frames_out[4 * i + size_t(a)] = qn[n].org[a];
-            frames_out[4 * i + 3] = float(rf_slab_inv_scale(qn[n].cell));
+            for (int a = 0; a < 3; a++) frames_out[4 * i + size_t(a)] = n.node.org[a];
+            frames_out[4 * i + 3] = float(rf_slab_inv_scale(n.node.cell));
         }
     }
     return RT_OK;

@@ -2,7 +2,7 @@
 //
 // The reader formats of a mesh BVH (BvhNode<R>, BvhNode4f, BvhNode4q, the back-face cone words) are derived from the exact
 // f64 child boxes and the triangle records by the per-node formulas below.  They are written ONCE, __host__ __device__:
-// DeviceScene<R>::build and build_mesh_cones (the host builder) and the refit kernels of rt_refit.hip (rt_scene_update)
+// derive_mesh_tables (rt_tables.cpp) and build_mesh_cones (the host builder) and the refit kernels of rt_refit.hip (rt_scene_update)
 // call the same functions, compiled with -ffp-contract=off on both sides, in f64 with IEEE operations only (+ - * /
 // sqrt, floor / ceil / lround, frexp / ldexp), so the two sides give the same bits.
 #pragma once

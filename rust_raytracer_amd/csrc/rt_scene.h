@@ -152,7 +152,7 @@ struct alignas(128) BvhNode4f {
 // (tools/ubench/micro_l1.hip: 64 clk per 16-B wave load, 449 clk per visit of a 7-load record, 291 of a 4-load one), which is
 // what bounds k_wf_mesh.  Decoded plane = org + q * cell, q_lo rounded down and q_hi up on the grid from the boxes
 // of BvhNode4f (padding included), so the quantised box contains the padded f32 box; the decode's own rounding
-// (one fma per plane) stays inside that padding (see the node builder in rt_kernels.hip).
+// (one fma per plane) stays inside that padding (see the node builder in rt_tables.cpp).
 struct alignas(64) BvhNode4q {
     float org[3];      // grid origin (<= every child's lo)
     float cell[3];     // 2^e per axis

@@ -1,8 +1,8 @@
 """rt_scene_update on the GPU: a scene updated in place (mesh BVHs refitted by the kernels of rt_refit.hip, everything else
 recompiled on the host) must behave as a scene freshly created from the new description.  Frames are compared bit for bit
 ("same bits": equal as uint64 everywhere, NaN pixels included) against a fresh DeviceScene, f64 frames against the oracle at
-the bar of tests/test_gpu_parity.py, and the device's mesh tables against the refit restated on the CPU
-(api.scene_refit_mesh, chained to the host builder by tests/test_scene_update_host.py)."""
+the bar of tests/test_gpu_parity.py, and the device's mesh tables against the refit on the CPU (api.scene_refit_mesh: the
+reused tree with the new vertices, through the derivation of rt_tables.cpp that DeviceScene<R>::build uploads)."""
 import os
 import subprocess
 

@@ -6,7 +6,8 @@ cell), widened by the builder's margin |q|_1 (2 m / s + 2^-12) with m the pad of
 entered child when the culling ray's span [tn, tf] inside the child's box evaluates wholly below lo or wholly above hi.
 
 The words come from the diagnostic export rt_scene_mesh_slabs, the tree and the triangle records from rt_scene_mesh_cones
-and the decoded child boxes from rt_scene_refit_mesh.  Checked here:
+and the decoded child boxes from rt_scene_refit_mesh: all three read the tables that rt_tables.cpp derives for the device
+itself, not a second computation of them (tests/test_gpu_scene_tables.py holds the upload to those tables).  Checked here:
  1. every vertex below a child lies inside the decoded slab by at least the stated margin;
  2. the device step, restated in numpy float32 (fmaf as the correctly rounded float64 product plus addend, rounded once more to
     float32: the product of two float32 is exact in float64), never drops a child for a ray aimed at a point of a triangle

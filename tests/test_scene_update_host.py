@@ -1,5 +1,6 @@
-"""rt_scene_update without a GPU: the structure check (rt_scene_update_check) and the refit restated on the CPU
-(rt_scene_refit_mesh): the tree of description a carrying the geometry of description b.  With b = a the restatement must give
+"""rt_scene_update without a GPU: the structure check (rt_scene_update_check) and the refit on the CPU
+(rt_scene_refit_mesh): the tree of description a carrying the geometry of description b, in the tables that rt_tables.cpp
+derives from it - the function that fills the device, not a restatement of it.  With b = a the refit must give
 the host builder's own tables bit for bit; with b != a the tree stays, the records are b's, every decoded child box holds what
 lies below it and every cone passes the brute-force back-face check of tests/test_mesh_cones.py."""
 import os

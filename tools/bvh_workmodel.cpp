@@ -1,7 +1,7 @@
 // CPU work model of k_wf_mesh: node visits and triangle tests per mesh ray of the 4-wide BVH the kernel walks, with and
 // without the back-face cone test and the normal-slab test, on a small path tracer of scenes/cornell_dragon.  Host only; built by hand:
 //
-//   g++ -std=c++17 -O2 -Irust_raytracer_amd/csrc -o tools/bvh_workmodel tools/bvh_workmodel.cpp rust_raytracer_amd/csrc/rt_bvh.cpp
+//   g++ -std=c++17 -O2 -Irust_raytracer_amd/csrc -o tools/bvh_workmodel tools/bvh_workmodel.cpp rust_raytracer_amd/csrc/rt_bvh.cpp rust_raytracer_amd/csrc/rt_tables.cpp
 //   tools/bvh_workmodel scenes/resource/dragon_high.obj [paths = 150000] [pad0]
 //
 // pad0: the slab words are built with the mesh pad m = 0, which leaves of the margin |q|_1 (2 m / s + 2^-12) only the constant
@@ -28,6 +28,7 @@
 #include "rt_bvh.h"
 #include "rt_refit.h"
 #include "rt_scene.h"
+#include "rt_tables.h"
 
 using namespace rt;
 static const double kInf = std::numeric_limits<double>::infinity();
@@ -214,19 +215,27 @@ int main(int argc, char** argv) {
         const double* p2 = &m.pos[3 * size_t(m.tri[3 * size_t(t) + 2])];
         for (int a = 0; a < 3; a++) { tris[s].v0[a] = p0[a]; tris[s].e1[a] = p1[a] - p0[a]; tris[s].e2[a] = p2[a] - p0[a]; }
     }
-    std::vector<uint32_t> cones;
-    build_mesh_cones(b4.nodes, tris, cone_limits(false), &cones);
-    // the quantised nodes and slab words as DeviceScene<R>::build derives them
-    const double pad = rf_pad_of_box(b4.root_lo, b4.root_hi);
+    // the quantised nodes with their cone and slab words: the library's own derivation (rt_tables.cpp) over a one-mesh scene
+    CompiledScene scene;
+    scene.nodes4 = b4.nodes;
+    scene.tris = tris;
+    scene.meshes.push_back(MeshInst{});
+    Bounds<double> box;
+    for (int a = 0; a < 3; a++) { box.lo[a] = b4.root_lo[a]; box.hi[a] = b4.root_hi[a]; }
+    scene.mesh_bounds.push_back(box);
+    scene.mesh_geoms.push_back(CompiledScene::MeshGeom{0, 0, 0, 0, uint32_t(b4.nodes.size()), 0, nt, bvh.max_depth, b4.max_stack});
+    MeshTables<double> tables;
+    std::string err;
+    if (derive_mesh_tables(scene, &tables, &err) != RT_OK) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
     std::vector<BvhNode4q> qnodes(b4.nodes.size());
-    const bool pad0 = argc > 3 && std::strcmp(argv[3], "pad0") == 0;
-    std::vector<double> pads(b4.nodes.size(), pad0 ? 0.0 : pad);
+    std::vector<uint32_t> cones(4 * b4.nodes.size()), slab_words(4 * b4.nodes.size());
     for (size_t i = 0; i < b4.nodes.size(); i++) {
-        const BuildNode4& sn = b4.nodes[i];
-        if (!rf_quantise4(sn.lo, sn.hi, sn.child, pad, qnodes[i].org, qnodes[i].cell, qnodes[i].qlo, qnodes[i].qhi)) { std::fprintf(stderr, "node off the grid\n"); return 1; }
+        qnodes[i] = tables.nodes4qc[i].node;
+        for (int k = 0; k < 4; k++) { cones[4 * i + size_t(k)] = tables.nodes4qc[i].cones.word[k]; slab_words[4 * i + size_t(k)] = tables.nodes4qc[i].slabs.word[k]; }
     }
-    std::vector<uint32_t> slab_words;
-    build_mesh_slabs(b4.nodes, tris, cones, qnodes.data(), pads.data(), &slab_words);
+    const bool pad0 = argc > 3 && std::strcmp(argv[3], "pad0") == 0;
+    if (pad0)  // the experiment: leaves the library's margin on purpose
+        build_mesh_slabs(b4.nodes, tris, cones, qnodes.data(), std::vector<double>(b4.nodes.size(), 0.0).data(), &slab_words);
     size_t with_slab = 0, with_cone = 0;
     for (size_t i = 0; i < slab_words.size(); i++) { with_slab += slab_words[i] != kNeutralSlab; with_cone += cones[i] != kNeutralCone; }
     size_t leaf = 0, leaf_cone = 0, inner = 0, inner_cone = 0;
