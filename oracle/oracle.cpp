@@ -345,7 +345,11 @@ struct UvDebugTexture : Sampler<Vec4> {  // uv_debug.rs:11-13
 };
 
 // ------------------------------------------------------------------ object.rs
+// oracle_world_hits_unculled: TriangleMesh::test visits every triangle in index order and tests no octree box
+thread_local bool g_unculled = false;
+
 struct Material;
+struct Hit;
 struct HitRecord {  // object.rs:32-41
     Vec4 hit_pos, normal, tangent, bitangent;
     double t;
@@ -353,12 +357,16 @@ struct HitRecord {  // object.rs:32-41
     bool front_face;
     const Material* material;
     int material_index;
+    // reporting only (oracle_world_hits_unculled): the primitive object that accepted the hit and the ray as it saw it
+    const Hit* object;
+    Vec4 object_origin, object_dir;
 };
 inline HitRecord make_hit(const Ray& ray, Vec4 hit_pos, double t, double u, double v, Vec4 outward_normal,
-                          Vec4 tangent, Vec4 bitangent, const Material* material, int material_index) {  // object.rs:45-72
+                          Vec4 tangent, Vec4 bitangent, const Material* material, int material_index,
+                          const Hit* object = nullptr) {  // object.rs:45-72
     bool front_face = dot(ray.dir, outward_normal) < 0.0;
     Vec4 normal = front_face ? outward_normal : -outward_normal;
-    return {hit_pos, normal, tangent, bitangent, t, u, v, front_face, material, material_index};
+    return {hit_pos, normal, tangent, bitangent, t, u, v, front_face, material, material_index, object, ray.origin, ray.dir};
 }
 struct Hit {  // object.rs:107-115
     virtual ~Hit() = default;
@@ -366,6 +374,9 @@ struct Hit {  // object.rs:107-115
     virtual Aabb get_bounding_box() const = 0;
     virtual double pdf_value(Vec4 origin, Vec4 dir, Rng& rng) const = 0;
     virtual Vec4 random(Vec4 origin, Rng& rng) const = 0;
+    // reporting only (oracle_world_hits_unculled): how many primitives of this object, each tested alone over `t`, have a hit
+    // within 1e-12 relative of t_win
+    virtual uint32_t count_near(const Ray&, Interval, double) const { return 1; }
 };
 
 // ------------------------------------------------------------------ pdf/*.rs
@@ -596,7 +607,7 @@ struct Sphere : Hit {
             u = phi / (2.0 * PI);
             v = theta / PI;
         }
-        out = make_hit(ray, hit_pos, root, u, v, normal, tangent, bitangent, material, material_index);
+        out = make_hit(ray, hit_pos, root, u, v, normal, tangent, bitangent, material, material_index, this);
         return true;
     }
     bool test(const Ray& ray, Interval t, Rng& rng, HitRecord& out) const override { return test_impl(ray, t, false, rng, out); }
@@ -650,7 +661,7 @@ struct Plane : Hit {
         double uu = dot(local_pos, inv_u);
         double vv = dot(local_pos, inv_v);
         if (uu < 0.0 || uu > 1.0 || vv < 0.0 || vv > 1.0) return false;
-        out = make_hit(ray, hit_pos, hit_t, uu, vv, normal, to_unit(u), to_unit(v), material, material_index);
+        out = make_hit(ray, hit_pos, hit_t, uu, vv, normal, to_unit(u), to_unit(v), material, material_index, this);
         return true;
     }
     Aabb get_bounding_box() const override { return bounds; }
@@ -788,6 +799,7 @@ struct TriangleMesh : Hit {
     std::unique_ptr<OctreeNode> octree;
     void finish() {  // mesh.rs:38-59
         bounds = ::get_bounding_box(vertices.data(), vertices.size());
+        if (g_unculled) return;  // oracle_world_hits_unculled never reads the octree
         octree = octree_new(vertices, triangles, nullptr, bounds, 0);
     }
     bool test_tri(const Triangle& triangle, const Ray& ray, Interval t_int, Rng& rng, HitRecord& out) const {  // mesh.rs:62-163
@@ -838,7 +850,7 @@ struct TriangleMesh : Hit {
             bitangent = bitangent * inv_max;
             tex = uv0 * w + uv1 * u + uv2 * v;
         }
-        out = make_hit(ray, hit_pos, t, tex[0], tex[1], normal, tangent, bitangent, material, material_index);
+        out = make_hit(ray, hit_pos, t, tex[0], tex[1], normal, tangent, bitangent, material, material_index, this);
         return true;
     }
     bool test_octree_node(const OctreeNode& node, const Ray& ray, Interval t, Rng& rng, HitRecord& out) const {  // mesh.rs:165-197
@@ -866,7 +878,33 @@ struct TriangleMesh : Hit {
         }
         return any;
     }
-    bool test(const Ray& ray, Interval t, Rng& rng, HitRecord& out) const override { return test_octree_node(*octree, ray, t, rng, out); }  // mesh.rs:201
+    // The reference's primitive test on every triangle in index order, the interval narrowed as mesh.rs:165-197 narrows it,
+    // and no octree box tested, the root's included (oracle_world_hits_unculled).
+    bool test_all_triangles(const Ray& ray, Interval t, Rng& rng, HitRecord& out) const {
+        bool any = false;
+        double closest_t = t.max;
+        HitRecord h;
+        for (const Triangle& tri : triangles) {
+            if (test_tri(tri, ray, {t.min, closest_t}, rng, h)) {
+                closest_t = h.t;
+                out = h;
+                any = true;
+            }
+        }
+        return any;
+    }
+    uint32_t count_near(const Ray& ray, Interval t, double t_win) const override {
+        Rng rng;
+        HitRecord h;
+        uint32_t n = 0;
+        for (const Triangle& tri : triangles)
+            if (test_tri(tri, ray, t, rng, h) && std::fabs(h.t - t_win) <= 1e-12 * std::fabs(t_win)) n++;
+        return n;
+    }
+    bool test(const Ray& ray, Interval t, Rng& rng, HitRecord& out) const override {  // mesh.rs:201
+        if (g_unculled) return test_all_triangles(ray, t, rng, out);
+        return test_octree_node(*octree, ray, t, rng, out);
+    }
     Aabb get_bounding_box() const override { return bounds; }
     double pdf_value(Vec4, Vec4, Rng&) const override { return 0.0; }
     Vec4 random(Vec4, Rng&) const override { return vec(1.0, 0.0, 0.0); }
@@ -1541,6 +1579,45 @@ int oracle_world_hit(const RtSceneDesc* scene, const double o[3], const double d
     for (int i = 0; i < 3; i++) { out[1 + i] = h.hit_pos[i]; out[4 + i] = h.normal[i]; }
     out[7] = h.u; out[8] = h.v; out[9] = h.front_face ? 1.0 : 0.0; out[10] = double(h.material_index);
     return 1;
+}
+
+static int world_hits(const RtSceneDesc* scene, bool unculled, uint32_t n, const double* origins, const double* dirs, const double* t_min,
+                      const double* t_max, double* out11, uint32_t* near) {
+    g_err.clear();
+    struct Scope {
+        explicit Scope(bool u) { g_unculled = u; }
+        ~Scope() { g_unculled = false; }
+    } scope(unculled);
+    auto world = build_world(scene);  // unculled: without the octrees (TriangleMesh::finish)
+    if (!world) return RT_E_INVALID;
+    for (uint32_t i = 0; i < n; i++) {
+        const double *o = origins + 3 * size_t(i), *d = dirs + 3 * size_t(i);
+        double* out = out11 + 11 * size_t(i);
+        Rng rng;
+        Ray r(point(o[0], o[1], o[2]), vec(d[0], d[1], d[2]));
+        Interval t = {t_min[i], t_max[i]};
+        HitRecord h;
+        h.object = nullptr;
+        near[i] = 0;
+        for (int k = 0; k < 11; k++) out[k] = 0.0;
+        out[10] = -1.0;
+        if (!world->world->test(r, t, rng, h)) continue;
+        out[0] = h.t;
+        for (int k = 0; k < 3; k++) { out[1 + k] = h.hit_pos[k]; out[4 + k] = h.normal[k]; }
+        out[7] = h.u; out[8] = h.v; out[9] = h.front_face ? 1.0 : 0.0; out[10] = double(h.material_index);
+        near[i] = h.object ? h.object->count_near(Ray(h.object_origin, h.object_dir), t, h.t) : 1;
+    }
+    return RT_OK;
+}
+
+int oracle_world_hits(const RtSceneDesc* scene, uint32_t n, const double* origins, const double* dirs, const double* t_min,
+                      const double* t_max, double* out11, uint32_t* near) {
+    return world_hits(scene, false, n, origins, dirs, t_min, t_max, out11, near);
+}
+
+int oracle_world_hits_unculled(const RtSceneDesc* scene, uint32_t n, const double* origins, const double* dirs, const double* t_min,
+                               const double* t_max, double* out11, uint32_t* near) {
+    return world_hits(scene, true, n, origins, dirs, t_min, t_max, out11, near);
 }
 
 int oracle_lights_pdf_value(const RtSceneDesc* scene, const double o[3], const double d[3], double* out) {

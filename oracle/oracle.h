@@ -57,6 +57,20 @@ int oracle_test_bounding_box(const double bounds6[6], const double origin[3], co
  * out[0]=t, [1..3]=pos, [4..6]=normal, [7]=u, [8]=v, [9]=front_face, [10]=material index */
 int oracle_world_hit(const RtSceneDesc* scene, const double origin[3], const double dir[3],
                      double t_min, double t_max, double* out11);
+/* The same for n rays with the world built once: origins / dirs 3n doubles, one interval per ray.  out11: the layout above per
+ * ray, a miss is eleven zeros except out[10] = -1.  near[i] (0 for a miss): the number of primitives of the winning object
+ * (triangles of that mesh; 1 for a sphere, quad, sky or sun) whose own t, each tested alone over the caller's interval with
+ * the ray as the object saw it, lies within 1e-12 relative of the winner's.  near > 1 marks a tie: which of those primitives
+ * wins depends on the order they are visited in, which the reference's octree decides and the project's trees do not copy. */
+int oracle_world_hits(const RtSceneDesc* scene, uint32_t n, const double* origins, const double* dirs, const double* t_min,
+                      const double* t_max, double* out11, uint32_t* near);
+/* oracle_world_hits with the octree dropped and nothing else changed: every TriangleMesh is searched by test_tri
+ * (mesh.rs:62-163) over all its triangles in index order, the interval narrowed after every accepted hit as
+ * mesh.rs:165-197 narrows it, and no octree node box is tested, the root's included.  Lists, transforms, object BVHs and
+ * their boxes (list.rs:58-74, bvh.rs:84-101, aabb.rs:50-87) are those of the reference.  This is the yardstick for rays in
+ * special position, where aabb.rs turns 0 * inf into a NaN that rejects an octree node. */
+int oracle_world_hits_unculled(const RtSceneDesc* scene, uint32_t n, const double* origins, const double* dirs, const double* t_min,
+                               const double* t_max, double* out11, uint32_t* near);
 /* lights.pdf_value(origin, dir) (list.rs:80-89, plane.rs:107-118, sphere.rs:106-121) */
 int oracle_lights_pdf_value(const RtSceneDesc* scene, const double origin[3], const double dir[3], double* out);
 /* n draws of lights.random(origin) (list.rs:91-100, plane.rs:120-126, sphere.rs:123-128) from one

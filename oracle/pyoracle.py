@@ -48,6 +48,9 @@ def load() -> C.CDLL:
         lib.oracle_test_bounding_box.restype = C.c_int
         lib.oracle_world_hit.argtypes = [C.POINTER(api.RtSceneDesc), dp, dp, C.c_double, C.c_double, dp]
         lib.oracle_world_hit.restype = C.c_int
+        for f in (lib.oracle_world_hits, lib.oracle_world_hits_unculled):
+            f.argtypes = [C.POINTER(api.RtSceneDesc), C.c_uint32] + [C.c_void_p] * 6
+            f.restype = C.c_int
         lib.oracle_lights_pdf_value.argtypes = [C.POINTER(api.RtSceneDesc), dp, dp, dp]
         lib.oracle_lights_pdf_value.restype = C.c_int
         lib.oracle_lights_random.argtypes = [C.POINTER(api.RtSceneDesc), dp, C.c_uint64, C.c_uint32, dp]
@@ -136,6 +139,26 @@ def world_hit(desc, origin, dir, t_min=0.001, t_max=float("inf")):
     o = list(out)
     return {"t": o[0], "pos": o[1:4], "normal": o[4:7], "uv": (o[7], o[8]), "front_face": bool(o[9]),
             "material": int(o[10])}
+
+
+def world_hits(desc, origins, dirs, t_min=0.001, t_max=float("inf"), unculled=False):
+    """Closest hits of n rays, the world built once: (out[n, 11], near[n]); see oracle.h oracle_world_hits.  A miss has
+    out[:, 10] == -1 and near == 0.  t_min / t_max: a scalar or (n,).  unculled=True: oracle_world_hits_unculled, the reference's
+    primitive tests and list / transform / object-BVH boxes without its octree."""
+    lib = load()
+    o = np.ascontiguousarray(np.asarray(origins, dtype=np.float64).reshape(-1, 3))
+    d = np.ascontiguousarray(np.asarray(dirs, dtype=np.float64).reshape(-1, 3))
+    n = len(o)
+    assert len(d) == n
+    lo = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, dtype=np.float64), (n,)))
+    hi = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n,)))
+    out = np.zeros((n, 11), dtype=np.float64)
+    near = np.zeros(n, dtype=np.uint32)
+    f = lib.oracle_world_hits_unculled if unculled else lib.oracle_world_hits
+    st = f(desc, n, o.ctypes.data, d.ctypes.data, lo.ctypes.data, hi.ctypes.data, out.ctypes.data, near.ctypes.data)
+    if st != 0:
+        raise api.RtError(st, lib.oracle_last_error().decode())
+    return out, near
 
 
 def lights_pdf_value(desc, origin, dir) -> float:

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <algorithm>
 #include <map>
 
@@ -80,7 +81,7 @@ struct Compiler {
     // emitted as the same kind of ops (OP_BOUNDS with skip pointers; no kernel change):
     //   * boxes of the new tree = unions of the primitives' GEOMETRIC boxes (sphere: centre -+ |r|; quad: the
     //     reference's own box), min / max of the reference's numbers only;
-    //   * a reference ancestor box that does not contain a primitive's geometric box can cull real hits (SURVEY B-8:
+    //   * a reference ancestor box that does not strictly contain a primitive's geometric box can cull real hits (SURVEY B-8:
     //     a negative-radius sphere has an inverted box, and the union with it is only partial): such boxes stay in
     //     front of that primitive as GUARD ops (a box test only asks whether the ray meets the box ahead of t_lo, so it
     //     gives the same verdict wherever in the order it is asked); a primitive behind a box no ray can pass
@@ -97,8 +98,12 @@ struct Compiler {
         for (int a = 0; a < 3; a++) if (!(b.lo[a] <= b.hi[a])) return false;  // inverted or NaN: the slab test never passes
         return true;
     }
+    // STRICTLY: a reference box that shares a plane with the primitive's geometric box (a BVH node above one sphere has the
+    // sphere's own box, bvh.rs:52-56) culls real hits too - aabb.rs turns 0 * inf into a NaN that rejects the node for a ray
+    // that lies on that plane with a zero direction component, and such a ray can touch the primitive there (tangent to the
+    // sphere).  On a plane strictly outside the primitive's box no such ray meets the primitive, so those boxes still go.
     static bool box_contains(const BoxD& outer, const double* lo, const double* hi) {
-        for (int a = 0; a < 3; a++) if (!(outer.lo[a] <= lo[a] && hi[a] <= outer.hi[a])) return false;
+        for (int a = 0; a < 3; a++) if (!(outer.lo[a] < lo[a] && hi[a] < outer.hi[a])) return false;
         return true;
     }
     // Collects the primitives under `node` in the reference's order; false if the subtree holds anything else.
@@ -218,8 +223,17 @@ struct Compiler {
     void emit_group_ops(const std::vector<GroupPrim>& prims, const std::vector<uint32_t>& idx, const std::vector<GNode>& nodes, int ni,
                         int32_t rank_base, std::vector<int32_t>& prim_pc) {
         const GNode& g = nodes[size_t(ni)];
+        // This box is the project's own, but the interpreters ask it with the reference's box test, which rejects a ray that
+        // lies ON a box plane with a zero direction component (aabb.rs: 0 * inf = NaN) - a ray tangent to the outermost sphere
+        // below this node, which the reference hits.  Moved outward by 2^-40 of its size, far beyond the primitive tests'
+        // own rounding, the planes are where no ray on them can touch a primitive below, and the NaN drops nothing.
         Bounds<double> b;
-        for (int a = 0; a < 3; a++) { b.lo[a] = g.box.lo[a]; b.hi[a] = g.box.hi[a]; }
+        for (int a = 0; a < 3; a++) {
+            const double pad = std::ldexp(std::fmax(std::fmax(std::fabs(g.box.lo[a]), std::fabs(g.box.hi[a])), g.box.hi[a] - g.box.lo[a]), -40)
+                               + std::numeric_limits<double>::min();
+            b.lo[a] = g.box.lo[a] - pad;
+            b.hi[a] = g.box.hi[a] + pad;
+        }
         out.bounds.push_back(b);
         const size_t bounds_op = out.ops.size();
         emit(OP_BOUNDS, int32_t(out.bounds.size()) - 1);

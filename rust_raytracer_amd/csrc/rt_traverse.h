@@ -14,7 +14,10 @@ namespace rt {
 // Slab tests as t = b * inv - o * inv (culling only, any conservative test is admissible).
 // A zero direction component gives inv = +-inf and inf - inf = NaN in that form, so the
 // inverse used for them is clamped to a huge finite value: a ray parallel to a slab is then
-// "inside forever" or "outside forever", which is exact.
+// "inside forever" or "outside forever" - except ON one of the slab's planes: (plane - o) * inv is +-0 for that plane and
+// -+huge for the other, so the slab comes out as (0, +huge) or as (-huge, 0), whichever the sign of the zero and the plane
+// give.  On a padded box that is harmless (a ray on a padded plane is outside the true box); the tests that decide about a
+// box with EXACT planes (span_misses, the scene program's mesh op) do not take an exit at exactly 0 for a miss.
 template <typename R> RT_DEV V3<R> clamped_inv(const Ray<R>& ray) {
     const R big = sizeof(R) == 8 ? R(1e150) : R(1e18);
     return {fabs(ray.inv.x) > big ? copysign(big, ray.inv.x) : ray.inv.x,
@@ -118,9 +121,13 @@ template <typename R> RT_DEV CullRay<R> make_cull_ray(const Ray<R>& ray, const R
 }
 // The miss rule of the callers that have one: the ray leaves the box before it enters it, or enters it behind t_max - a miss
 // only if it is one with a few ulps of slack on both ends (a NaN compares false: the tree is searched).
+// An exit at exactly 0 is no miss either: the origin lies ON a plane of the box, and if the ray runs parallel to that plane
+// (clamped_inv) it stays on the closed box and hits what lies there - the border of a grid straight down, a face of a cube
+// along it, the outermost sphere of a group on a tangent.  Half of those rays came out as (-huge, 0) and were dropped.  The
+// other rays with that exit leave the box where they start; searching the tree for them costs a visit of the root.
 template <typename R> RT_DEV bool span_misses(R t_enter, R t_exit, R t_max) {
     const R eps = Lim<R>::eps() * R(16);
-    return (t_enter - fabs(t_enter) * eps > t_exit + fabs(t_exit) * eps) || (t_enter - fabs(t_enter) * eps > t_max);
+    return (t_enter - fabs(t_enter) * eps > t_exit + fabs(t_exit) * eps && t_exit != R(0)) || (t_enter - fabs(t_enter) * eps > t_max);
 }
 
 // Object-space direction as four signed bytes (round(127 d / |d|), -127) for the back-face cone test (rt_bvh.cpp has the

@@ -815,7 +815,8 @@ RT_DEV bool prims_search(const SceneView<R>& sc, const Ray<R>& wray, Best<R>& be
                 R tn = fmax(fmax(fmin(t0x, t1x), fmin(t0y, t1y)), fmax(fmin(t0z, t1z), t_lo));
                 R tf = fmin(fmin(fmax(t0x, t1x), fmax(t0y, t1y)), fmin(fmax(t0z, t1z), best.t));
                 tf = tf + fabs(tf) * eps;
-                to_mesh = to_mesh || ((tn <= tf) && rb.lo[0] <= rb.hi[0]);
+                // tf == 0: the origin lies ON a box plane that gets no slack (coordinate 0); see span_misses
+                to_mesh = to_mesh || ((tn <= tf || tf == R(0)) && rb.lo[0] <= rb.hi[0]);
                 break;
             }
             case OP_SKY:

@@ -326,29 +326,31 @@ def check_closest(geom, o, d, got, want, extent, label, t_min=T_MIN, oracle=None
     return rep
 
 
-def segment_scale(geom, o, d, occluded, t_min, t_max, t_end):
+def segment_scale(geom, o, d, occluded, t_min, t_max, t_end, oracle=oracle_hits):
     """L of a segment: its end points and the primitives it starts on, ends on and (oracle) is blocked by."""
     end = o + t_end * d
     L = max(float(np.abs(o).max()), float(np.abs(end).max()))
     pts = [o, end]
     if occluded:
-        pts.append(oracle_hits(geom.desc, o[None], d[None], t_min, t_max)["pos"][0])
+        pts.append(oracle(geom.desc, o[None], d[None], t_min, t_max)["pos"][0])
     for p in pts:
         e, prim, _ = geom.locate(p)
         L = max(L, float(np.abs(geom.numbers(e, prim)).max()))
     return L
 
 
-def check_occlusion(geom, o, d, got, want, label, t_min=T_MIN, t_max=T_MAX, t_end=1.0):
+def check_occlusion(geom, o, d, got, want, label, t_min=T_MIN, t_max=T_MAX, t_end=1.0, oracle=oracle_hits):
     """The yardstick on occlusion answers (bool arrays) to the segments (o, d) over (t_min, t_max); o + t_end d is a
-    segment's end point."""
+    segment's end point.  t_max and t_end: one number, or one per segment.  oracle: the yardstick, called like
+    ray_query_cases.oracle_hits (the default; tests/special_ray_cases.py passes the unculled one)."""
+    t_max, t_end = np.broadcast_to(np.asarray(t_max, dtype=np.float64), (len(o),)), np.broadcast_to(np.asarray(t_end, dtype=np.float64), (len(o),))
     desc = geom.desc
     rep = Report(label, len(got))
     assert got.dtype == bool and len(got) == len(want) == len(o)
     for i in np.nonzero(got != want)[0]:
-        L = segment_scale(geom, o[i], d[i], want[i], t_min, t_max, t_end)
-        co, cd = copies(o[i], d[i], t_end, DELTA * U * L)
-        alt = oracle_hits(desc, co, cd, t_min, t_max)["klass"] != MISS
+        L = segment_scale(geom, o[i], d[i], want[i], t_min, t_max[i], t_end[i], oracle)
+        co, cd = copies(o[i], d[i], t_end[i], DELTA * U * L)
+        alt = oracle(desc, co, cd, t_min, t_max[i])["klass"] != MISS
         if (alt == got[i]).any():
             rep.excused.append(int(i))
         else:
@@ -356,7 +358,7 @@ def check_occlusion(geom, o, d, got, want, label, t_min=T_MIN, t_max=T_MAX, t_en
     return rep
 
 
-def fragile_share_closest(geom, o, d, want, extent, t_min=T_MIN):
+def fragile_share_closest(geom, o, d, want, extent, t_min=T_MIN, oracle=oracle_hits):
     """Share of rays with a copy whose oracle answer differs in class, material or face: an upper bound on what can be excused."""
     n = 0
     for i in range(len(o)):
@@ -365,16 +367,17 @@ def fragile_share_closest(geom, o, d, want, extent, t_min=T_MIN):
         t_point = float(w["t"]) if w["klass"] == SURFACE else extent / np.linalg.norm(d[i])
         co, cd = copies(o[i], d[i], t_point, DELTA * U * L)
         key = _key(w["klass"], w["material"], w["front"])
-        n += any(key != _key(a["klass"], a["material"], a["front"]) for a in oracle_hits(geom.desc, co, cd, t_min))
+        n += any(key != _key(a["klass"], a["material"], a["front"]) for a in oracle(geom.desc, co, cd, t_min))
     return n / max(len(o), 1)
 
 
-def fragile_share_segments(geom, o, d, want, t_min=T_MIN, t_max=T_MAX, t_end=1.0):
+def fragile_share_segments(geom, o, d, want, t_min=T_MIN, t_max=T_MAX, t_end=1.0, oracle=oracle_hits):
     n = 0
+    t_max, t_end = np.broadcast_to(np.asarray(t_max, dtype=np.float64), (len(o),)), np.broadcast_to(np.asarray(t_end, dtype=np.float64), (len(o),))
     for i in range(len(o)):
-        L = segment_scale(geom, o[i], d[i], want[i], t_min, t_max, t_end)
-        co, cd = copies(o[i], d[i], t_end, DELTA * U * L)
-        n += ((oracle_hits(geom.desc, co, cd, t_min, t_max)["klass"] != MISS) != want[i]).any()
+        L = segment_scale(geom, o[i], d[i], want[i], t_min, t_max[i], t_end[i], oracle)
+        co, cd = copies(o[i], d[i], t_end[i], DELTA * U * L)
+        n += ((oracle(geom.desc, co, cd, t_min, t_max[i])["klass"] != MISS) != want[i]).any()
     return n / max(len(o), 1)
 
 
