@@ -388,8 +388,11 @@ void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<T
 //     -32768 or 32767 is out of reach: |L(tau)| <= 24 289 + 24 u 381 x 2^16 < 24 325.  fmaxf / fminf drop a NaN operand: with
 //     both ends NaN the comparisons fail; ONE NaN only arises as 0 x inf from tf = +inf and B = 0, where the true pf equals pn.
 // The test does not read the direction word: it holds for meshes that hit back faces and with RT_WF_CONES=0.
-// A child without a cone (kNeutralCone: empty, above an ill-conditioned triangle, too wide) carries kNeutralSlab; its q is 0,
-// so the kernel sees A = B = 0 (or NaN) inside [-32768, 32767] and never drops it.
+// Nothing above depends on how q was chosen: it uses |q_i| <= 127 (the bytes), |q|_1 in the margin and in the scale bound, and
+// the exact interval of P over the corners.  The axis need not be a normal at all, which is what build_mesh_slab_axes below uses.
+// A child with kNeutralCone (empty, above an ill-conditioned triangle, a leaf without a cone, an inner child for which no axis of
+// the table was worth taking) carries kNeutralSlab; its q is 0, so the kernel sees A = B = 0 (or NaN) inside [-32768, 32767] and
+// never drops it.
 // ---------------------------------------------------------------------------------------------
 void build_mesh_slabs(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const std::vector<uint32_t>& cones,
                       const BvhNode4q* qnodes, const double* node_pad, std::vector<uint32_t>* out) {
@@ -422,6 +425,158 @@ void build_mesh_slabs(const std::vector<BuildNode4>& nodes4, const std::vector<T
         }
         below[i] = all;
     }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Slab-only axes: a slab for inner children that have no back-face cone.
+//
+// The children of the top levels of a closed surface hold normals that go all the way round: no cone, so no axis, so no slab,
+// although every mesh ray passes them and their boxes around bent pieces of surface are the loosest of the tree.  Such a child
+// gets the word (qx, qy, qz, 127) with q from the table of rf_slab_axis (rt_refit.h): per candidate the exact extent of
+// q . x over the corners below (v0, v0 + e1, v0 + e2, as the slabs form them) over the extent of the child's exact box along
+// q, sum_a |q_a| (hi_a - lo_a); the candidate with the smallest ratio, the first of equals, if that ratio is below
+// kSlabAxisMaxRatio.  build_mesh_slabs then gives it the slab of that axis like any other.
+//
+// The word never culls as a cone.  The kernel culls on D . (q, 127) > 0 with D = (dq, -127), that is dq . q > 127 x 127 = 16 129.
+// Every byte of dq is round(127 d^_i) of a unit vector: |dq|_2 <= 127 + sqrt(3) / 2 < 127.87; every table entry has
+// |q|_2 <= 126; so dq . q <= 127.87 x 126 < 16 112 < 16 129.  kNoCullDir has dq = 0: the product is -16 129.  The axis of a real
+// cone is round(127 a), |a| = 1, of length >= 127 - sqrt(3) / 2 > 126: the two kinds of word cannot be confused, and
+// rf_is_slab_only tells them apart.
+// The slab proof above holds as it stands (it never asked where q came from).  Its scale bound: |P| <= |q|_1 x 63.75 with
+// |q|_1 <= 216 for the table (72 + 72 + 72), below the 381 of a cone axis.
+//
+// Kept neutral: leaves (a leaf without a cone is a fold or a coincident pair; a slab there saves tests, not visits, and the
+// work model shows none saved), children above an ill-conditioned triangle, children whose triangles are not one run of slots,
+// children whose box is flat or not finite, and children whose slab on the chosen axis would be kNeutralSlab.
+//
+// Cost.  The supports are minima and maxima of identically computed numbers, so they merge exactly: a child's support is the
+// merge of the supports of its own children, each of which is either computed by the recursion (it is eligible itself) or
+// projected directly.  Every triangle is projected once per candidate however deep the stack of cone-less ancestors above it
+// is (a triangle soup included), and the memory is one support per level of that stack.  (Skipping subtrees whose box cannot
+// widen a support was tried: the deepest eligible children are small, most of their triangles are near their hull, 59 % of the
+// headline mesh was still projected and the box tests cost what was saved.)  The refit kernel (rt_refit.hip k_refit_slab_axes)
+// reduces over all corners of each eligible child instead; both give the exact minima and maxima, so the same words.
+// ---------------------------------------------------------------------------------------------
+bool slab_axes_enabled() {
+    const char* e = std::getenv("RT_SLAB_AXES");
+    return !(e && *e && std::atoi(e) == 0);
+}
+
+namespace {
+struct AxisSupport {
+    double lo[kSlabAxes], hi[kSlabAxes];
+    AxisSupport() { for (int c = 0; c < kSlabAxes; c++) { lo[c] = INFINITY; hi[c] = -INFINITY; } }
+    void merge(const AxisSupport& o) { for (int c = 0; c < kSlabAxes; c++) { lo[c] = rf_min(lo[c], o.lo[c]); hi[c] = rf_max(hi[c], o.hi[c]); } }
+};
+
+struct AxisPass {
+    const std::vector<BuildNode4>& nodes4;
+    const std::vector<TriRec<double>>& tris;
+    const BvhNode4q* qnodes;
+    const double* node_pad;
+    std::vector<uint32_t>& cones;
+    struct Run { uint32_t lo = UINT32_MAX, hi = 0, count = 0; };
+    std::vector<Run> run;            // per node and child
+    std::vector<uint8_t> eligible;   // per node and child
+    std::vector<uint8_t> done;
+    double ax[kSlabAxes], ay[kSlabAxes], az[kSlabAxes];  // the table as doubles (exact), one array per component
+
+    // rf_axis_project of every corner of the slots [lo, hi) against every candidate, into *s.  The loop over the candidates is the
+    // inner one, over plain arrays, so that the compiler can keep it in vector registers; the operations are rf_axis_project's
+    // and rf_min / rf_max's, in their order.
+    void project(uint32_t lo, uint32_t hi, AxisSupport* s) const {
+        double mn[kSlabAxes], mx[kSlabAxes];
+        for (int c = 0; c < kSlabAxes; c++) { mn[c] = s->lo[c]; mx[c] = s->hi[c]; }
+        for (uint32_t t = lo; t < hi; t++) {
+            const TriRec<double>& r = tris[t];
+            double v[9];
+            for (int a = 0; a < 3; a++) { v[a] = r.v0[a]; v[3 + a] = r.e1[a]; v[6 + a] = r.e2[a]; }
+            for (int c3 = 0; c3 < 3; c3++) {
+                double x[3];
+                rf_tri_corner(v, c3, x);
+                const double x0 = x[0], x1 = x[1], x2 = x[2];
+                for (int c = 0; c < kSlabAxes; c++) {
+                    const double p = ax[c] * x0 + ay[c] * x1 + az[c] * x2;
+                    mn[c] = p < mn[c] ? p : mn[c];
+                    mx[c] = p > mx[c] ? p : mx[c];
+                }
+            }
+        }
+        for (int c = 0; c < kSlabAxes; c++) { s->lo[c] = mn[c]; s->hi[c] = mx[c]; }
+    }
+    // the support of the eligible child k of node i, and its word
+    void visit(size_t i, int k, AxisSupport* s) {
+        const size_t id = 4 * i + size_t(k), c = size_t(nodes4[i].child[k]);
+        done[id] = 1;
+        for (int j = 0; j < 4; j++) {
+            if (nodes4[c].child[j] == kEmptyChild) continue;
+            if (eligible[4 * c + size_t(j)]) {
+                AxisSupport below;
+                visit(c, j, &below);
+                s->merge(below);
+            } else {
+                project(run[4 * c + size_t(j)].lo, run[4 * c + size_t(j)].hi, s);
+            }
+        }
+        const int pick = rf_slab_axis_pick(nodes4[i].lo[k], nodes4[i].hi[k], s->lo, s->hi);
+        if (pick < 0) return;
+        const uint32_t word = rf_slab_axis_word(pick);
+        const Run& r = run[id];
+        const uint32_t slab = rf_slab_word(word, qnodes[i].org, qnodes[i].cell, node_pad[i], r.lo, r.hi, r.count, [&](uint32_t t, double* v) {
+            for (int a = 0; a < 3; a++) { v[a] = tris[t].v0[a]; v[3 + a] = tris[t].e1[a]; v[6 + a] = tris[t].e2[a]; }
+        });
+        if (slab != kNeutralSlab) cones[id] = word;
+    }
+};
+}  // namespace
+
+void build_mesh_slab_axes(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const ConeLimits& lim,
+                          const BvhNode4q* qnodes, const double* node_pad, std::vector<uint32_t>* cones) {
+    const size_t n = nodes4.size(), n_tris = tris.size();
+    if (n == 0 || cones->size() != 4 * n) return;
+    AxisPass p{nodes4, tris, qnodes, node_pad, *cones, {}, {}, {}, {}, {}, {}};
+    for (int c = 0; c < kSlabAxes; c++) {
+        int q[3];
+        rf_slab_axis(c, q);
+        p.ax[c] = double(q[0]); p.ay[c] = double(q[1]); p.az[c] = double(q[2]);
+    }
+    // ill-conditioned triangles before each slot, by the rule of build_mesh_cones
+    std::vector<uint32_t> bad_before(n_tris + 1, 0);
+    for (size_t t = 0; t < n_tris; t++) {
+        double nrm[3];
+        rf_tri_normal(tris[t].v0, tris[t].e1, tris[t].e2, lim, nrm);
+        bad_before[t + 1] = bad_before[t] + (std::isfinite(nrm[0]) ? 0u : 1u);
+    }
+    p.run.resize(4 * n);
+    p.eligible.assign(4 * n, 0);
+    p.done.assign(4 * n, 0);
+    for (size_t i = n; i-- > 0;) {  // runs, bottom-up as in build_mesh_slabs
+        for (int k = 0; k < 4; k++) {
+            const int32_t ch = nodes4[i].child[k];
+            AxisPass::Run& b = p.run[4 * i + size_t(k)];
+            if (ch == kEmptyChild) continue;
+            if (ch >= 0) {
+                if (size_t(ch) <= i || size_t(ch) >= n) continue;
+                for (int j = 0; j < 4; j++) {
+                    const AxisPass::Run& o = p.run[4 * size_t(ch) + size_t(j)];
+                    b.lo = std::min(b.lo, o.lo); b.hi = std::max(b.hi, o.hi); b.count += o.count;
+                }
+                if (b.count == 0 || b.hi - b.lo != b.count || b.hi > n_tris) continue;
+                const double clean[3] = {bad_before[b.hi] == bad_before[b.lo] ? 0.0 : std::numeric_limits<double>::quiet_NaN(), 0.0, 0.0};
+                p.eligible[4 * i + size_t(k)] = rf_slab_axis_eligible(0, 1, (*cones)[4 * i + size_t(k)], b.lo, b.hi, b.count, clean) ? 1 : 0;
+            } else {
+                const uint32_t code = uint32_t(~ch), first = code >> 3, count = (code & 7u) + 1u;
+                if (size_t(first) + count > n_tris) continue;
+                b.lo = first; b.hi = first + count; b.count = count;
+            }
+        }
+    }
+    for (size_t i = 0; i < n; i++)  // parents stand before their children: an eligible child below an eligible one is done by then
+        for (int k = 0; k < 4; k++)
+            if (p.eligible[4 * i + size_t(k)] && !p.done[4 * i + size_t(k)]) {
+                AxisSupport s;
+                p.visit(i, k, &s);
+            }
 }
 
 }  // namespace rt

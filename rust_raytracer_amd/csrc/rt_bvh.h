@@ -69,7 +69,12 @@ ConeLimits cone_limits(bool f32);
 // tris: the f64 records in leaf order.  out: 4 words per node.
 void build_mesh_cones(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const ConeLimits& lim,
                       std::vector<uint32_t>* out);
-// The normal slabs of the same children (rt_scene.h NodeSlabs4).  cones: what build_mesh_cones gave; qnodes: the quantised
+// Slab-only axes: an inner child that build_mesh_cones left without a cone gets the word (qx, qy, qz, 127), |q|_2 <= 126, of the
+// table direction along which the surface below it is thinnest against its box, if that pays (rt_refit.h rf_slab_axis_pick).
+// The word never culls as a cone; build_mesh_slabs reads its axis.  Called between the two; cones: in and out.
+void build_mesh_slab_axes(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const ConeLimits& lim,
+                          const BvhNode4q* qnodes, const double* node_pad, std::vector<uint32_t>* cones);
+// The normal slabs of the same children (rt_scene.h NodeSlabs4).  cones: what the two above gave; qnodes: the quantised
 // nodes (grid origin and cells); node_pad: per node the pad of its mesh (rf_pad_of_box).  out: 4 words per node.
 void build_mesh_slabs(const std::vector<BuildNode4>& nodes4, const std::vector<TriRec<double>>& tris, const std::vector<uint32_t>& cones,
                       const BvhNode4q* qnodes, const double* node_pad, std::vector<uint32_t>* out);

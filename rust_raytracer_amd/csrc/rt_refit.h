@@ -214,6 +214,28 @@ RT_HD inline double rf_slab_margin(const int* q, double pad, double inv_s) {
     return l1 * (2.0 * pad * inv_s + 1.0 / 4096.0);
 }
 
+// The three axis bytes of a cone word as integers.
+RT_HD inline void rf_cone_axis(uint32_t cone, int* q) {
+    q[0] = int(int8_t(cone & 0xFFu)); q[1] = int(int8_t((cone >> 8) & 0xFFu)); q[2] = int(int8_t((cone >> 16) & 0xFFu));
+}
+// Corner c (0: v0, 1: v0 + e1, 2: v0 + e2) of the record v = v0 e1 e2, as the slabs and the slab axes see it.
+RT_HD inline void rf_tri_corner(const double* v, int c, double* x) {
+    for (int a = 0; a < 3; a++) x[a] = c == 0 ? v[a] : v[a] + v[3 * c + a];
+}
+// P(x) = q . (x - org) / s of one corner, in this order of operations.
+RT_HD inline double rf_slab_project(const int* q, const float* org, double inv_s, const double* x) {
+    return double(q[0]) * ((x[0] - double(org[0])) * inv_s) + double(q[1]) * ((x[1] - double(org[1])) * inv_s) +
+           double(q[2]) * ((x[2] - double(org[2])) * inv_s);
+}
+// The word of the exact interval [plo, phi] of P over the corners below a child: widened by rf_slab_margin, rounded outward.
+RT_HD inline uint32_t rf_slab_finish(const int* q, double pad, double inv_s, double plo, double phi) {
+    if (!(plo <= phi) || !std::isfinite(plo) || !std::isfinite(phi)) return kNeutralSlab;  // a NaN compares false
+    const double margin = rf_slab_margin(q, pad, inv_s);
+    const double l = rf_max(std::floor(plo - margin), -32768.0), h = rf_min(std::ceil(phi + margin), 32767.0);
+    if (!(l <= 32767.0 && h >= -32768.0)) return kNeutralSlab;  // off the scale (a vertex outside the node's grid): no slab
+    return (uint32_t(int32_t(l)) & 0xFFFFu) | (uint32_t(int32_t(h)) << 16);
+}
+
 // The slab word of a child with cone word `cone` over the slots [lo, hi), `count` triangles, in a node with grid origin
 // `org` and cells `cell`: the exact interval of q . (x - org) / s over the three corners v0, v0 + e1, v0 + e2 of every
 // triangle below, widened by rf_slab_margin and rounded outward to two signed 16-bit integers (lo | hi << 16).
@@ -221,7 +243,8 @@ RT_HD inline double rf_slab_margin(const int* q, double pad, double inv_s) {
 template <typename TriAt>
 RT_HD inline uint32_t rf_slab_word(uint32_t cone, const float* org, const float* cell, double pad, uint32_t lo, uint32_t hi, uint32_t count, TriAt tri_at) {
     if (cone == kNeutralCone || count == 0 || hi - lo != count) return kNeutralSlab;
-    const int q[3] = {int(int8_t(cone & 0xFFu)), int(int8_t((cone >> 8) & 0xFFu)), int(int8_t((cone >> 16) & 0xFFu))};
+    int q[3];
+    rf_cone_axis(cone, q);
     const double inv_s = rf_slab_inv_scale(cell);
     if (!(inv_s > 0.0) || !std::isfinite(inv_s) || !std::isfinite(pad)) return kNeutralSlab;
     double plo = INFINITY, phi = -INFINITY;
@@ -230,19 +253,94 @@ RT_HD inline uint32_t rf_slab_word(uint32_t cone, const float* org, const float*
         tri_at(t, v);
         for (int c = 0; c < 3; c++) {
             double x[3];
-            for (int a = 0; a < 3; a++) x[a] = c == 0 ? v[a] : v[a] + v[3 * c + a];
-            const double p = double(q[0]) * ((x[0] - double(org[0])) * inv_s) + double(q[1]) * ((x[1] - double(org[1])) * inv_s) +
-                             double(q[2]) * ((x[2] - double(org[2])) * inv_s);
+            rf_tri_corner(v, c, x);
+            const double p = rf_slab_project(q, org, inv_s, x);
             plo = rf_min(plo, p);
             phi = rf_max(phi, p);
         }
     }
-    if (!(plo <= phi) || !std::isfinite(plo) || !std::isfinite(phi)) return kNeutralSlab;  // a NaN compares false
-    const double margin = rf_slab_margin(q, pad, inv_s);
-    const double l = rf_max(std::floor(plo - margin), -32768.0), h = rf_min(std::ceil(phi + margin), 32767.0);
-    if (!(l <= 32767.0 && h >= -32768.0)) return kNeutralSlab;  // off the scale (a vertex outside the node's grid): no slab
-    return (uint32_t(int32_t(l)) & 0xFFFFu) | (uint32_t(int32_t(h)) << 16);
+    return rf_slab_finish(q, pad, inv_s, plo, phi);
 }
+
+// ---- slab-only axes (the argument stands in rt_bvh.cpp) ----
+// An inner child without a back-face cone (its normals go round too far) still profits from a slab if its surface is thin
+// along SOME direction.  Such a child gets the cone word (qx, qy, qz, 127) with |q|_2 <= 126, which the cone test can never
+// cull with, and the slab step reads q from it like any other axis.  q comes from a fixed table: the integer directions
+// with components in -2..2 and at least two of them non-zero, one of every +- pair, reduced, each times the largest integer
+// that keeps |q|_2 <= 126.  The six face diagonals stand first, then the four body diagonals: the first index wins ties.
+// RT_SLAB_AXIS_COUNT (a prefix of the table: 10, 22 or 46) and RT_SLAB_AXIS_MAX_RATIO exist for the sweeps of
+// profiles/slab_axes/README.md (tools/bvh_workmodel.cpp built with -D...); the library is built with the defaults.
+#ifndef RT_SLAB_AXIS_COUNT
+#define RT_SLAB_AXIS_COUNT 46
+#endif
+#ifndef RT_SLAB_AXIS_MAX_RATIO
+#define RT_SLAB_AXIS_MAX_RATIO 0.9
+#endif
+constexpr int kSlabAxes = RT_SLAB_AXIS_COUNT;
+static_assert(kSlabAxes >= 1 && kSlabAxes <= 46, "a prefix of the table");
+constexpr double kSlabAxisMaxRatio = RT_SLAB_AXIS_MAX_RATIO;  // an axis is taken if the surface spans less than this share of its box along it
+RT_HD inline void rf_slab_axis(int c, int* q) {
+    static constexpr int8_t kTable[46][3] = {
+        {0, 89, -89},   {0, 89, 89},    {89, -89, 0},   {89, 0, -89},    {89, 0, 89},    {89, 89, 0},    {72, -72, -72},  {72, -72, 72},
+        {72, 72, -72},  {72, 72, 72},   {0, 56, -112},  {0, 56, 112},    {0, 112, -56},  {0, 112, 56},   {56, -112, 0},   {56, 0, -112},
+        {56, 0, 112},   {56, 112, 0},   {112, -56, 0},  {112, 0, -56},   {112, 0, 56},   {112, 56, 0},   {42, -84, -84},  {51, -102, -51},
+        {51, -102, 51}, {42, -84, 84},  {51, -51, -102}, {51, -51, 102}, {51, 51, -102}, {51, 51, 102},  {42, 84, -84},   {51, 102, -51},
+        {51, 102, 51},  {42, 84, 84},   {84, -84, -42}, {84, -84, 42},   {84, -42, -84}, {102, -51, -51}, {102, -51, 51}, {84, -42, 84},
+        {84, 42, -84},  {102, 51, -51}, {102, 51, 51},  {84, 42, 84},    {84, 84, -42},  {84, 84, 42}};
+    q[0] = kTable[c][0]; q[1] = kTable[c][1]; q[2] = kTable[c][2];
+}
+// The support of a corner along a candidate: q . x in this order of operations.  Minima and maxima of it merge exactly.
+RT_HD inline double rf_axis_project(const int* q, const double* x) { return double(q[0]) * x[0] + double(q[1]) * x[1] + double(q[2]) * x[2]; }
+
+// May the child `ch` of a mesh with n_nodes 4-wide nodes (ch relative to the mesh's first node) get a slab-only axis?  An
+// INNER child without a cone whose triangles are one run of slots [lo, hi), none of them ill-conditioned (`sum`, the sum of
+// the normals below, is NaN otherwise).  Leaves keep their neutral words: a leaf without a cone is a fold or a coincident
+// pair of a few triangles, and what a slab could save there is their tests, not a node visit.
+RT_HD inline bool rf_slab_axis_eligible(int32_t ch, uint32_t n_nodes, uint32_t cone, uint32_t lo, uint32_t hi, uint32_t count, const double* sum) {
+    if (ch < 0 || uint32_t(ch) >= n_nodes || cone != kNeutralCone) return false;  // kEmptyChild < 0
+    if (count == 0 || hi - lo != count) return false;
+    return std::isfinite(sum[0]) && std::isfinite(sum[1]) && std::isfinite(sum[2]);
+}
+
+// The candidate for a child with the exact box (blo, bhi), given smin / smax[c] = the exact min / max of rf_axis_project
+// over the corners below: the one with the smallest (smax - smin) / sum_a |q_a| (bhi_a - blo_a), the first such, if that ratio
+// is below kSlabAxisMaxRatio; else, or for a box that is flat or not finite, -1.
+RT_HD inline int rf_slab_axis_pick(const double* blo, const double* bhi, const double* smin, const double* smax) {
+    double ext[3];
+    for (int a = 0; a < 3; a++) {
+        ext[a] = bhi[a] - blo[a];
+        if (!(ext[a] > 0.0) || !std::isfinite(ext[a])) return -1;
+    }
+    int best = -1;
+    double best_ratio = kSlabAxisMaxRatio;
+    for (int c = 0; c < kSlabAxes; c++) {
+        int q[3];
+        rf_slab_axis(c, q);
+        const double den = double(q[0] < 0 ? -q[0] : q[0]) * ext[0] + double(q[1] < 0 ? -q[1] : q[1]) * ext[1] + double(q[2] < 0 ? -q[2] : q[2]) * ext[2];
+        const double num = smax[c] - smin[c];
+        if (!(num >= 0.0) || !std::isfinite(num) || !(den > 0.0) || !std::isfinite(den)) return -1;
+        const double ratio = num / den;
+        if (ratio < best_ratio) { best_ratio = ratio; best = c; }
+    }
+    return best;
+}
+// The slab-only cone word of candidate c.
+RT_HD inline uint32_t rf_slab_axis_word(int c) {
+    int q[3];
+    rf_slab_axis(c, q);
+    return uint32_t(q[0] & 0xFF) | (uint32_t(q[1] & 0xFF) << 8) | (uint32_t(q[2] & 0xFF) << 16) | (127u << 24);
+}
+// Is `cone` a slab-only word?  w = 127 and 0 < |q|_2 <= 126; the axis of a real cone is round(127 a) of a unit vector a, whose
+// length is at least 127 - sqrt(3) / 2 > 126.
+RT_HD inline bool rf_is_slab_only(uint32_t cone) {
+    int q[3];
+    rf_cone_axis(cone, q);
+    const int l2 = q[0] * q[0] + q[1] * q[1] + q[2] * q[2];
+    return (cone >> 24) == 127u && l2 > 0 && l2 <= 126 * 126;
+}
+
+// RT_SLAB_AXES=0: no slab-only axes, the words of a child without a cone stay neutral (A/B control; read at every derivation).
+bool slab_axes_enabled();
 
 #if defined(__HIP__)
 // ---- the device refit (rt_refit.hip) ----

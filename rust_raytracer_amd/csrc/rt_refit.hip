@@ -12,6 +12,7 @@
 //                        by ONE thread each: no float atomics, so the sums do not depend on the arrival order.
 //   3. k_refit_nodes2<R> / k_refit_nodes4   per node: the reader formats, by the formulas of rt_refit.h that the host
 //                        builder uses (BvhNode<R>, BvhNode4f, BvhNode4q, cone and slab words).
+//   4. k_refit_slab_axes per inner child without a cone, one block each: the slab-only axis and its slab (unless RT_SLAB_AXES=0).
 // The kernels write the fields that depend on the vertices and nothing else: child references and padding keep the bytes
 // the host builder gave them, so a refitted table equals, byte for byte, the one DeviceScene<R>::build uploads for the same
 // tree and vertices (tests/test_gpu_scene_update.py compares them).
@@ -209,6 +210,119 @@ __global__ void k_refit_nodes4(uint32_t n_nodes, double pad, const int32_t* __re
     }
 }
 
+// Slab-only axes (rt_bvh.cpp build_mesh_slab_axes), after k_refit_nodes4: ONE BLOCK per (node, child); the blocks of children
+// that are not eligible leave at once.  The block reduces, over the child's whole run of slots, the supports of the candidate
+// axes kAxisGroup at a time (minima and maxima: the order of the reduction cannot show), thread 0 picks by the host's rule, and
+// a second reduction gives the exact interval of P on the chosen axis, finished by rf_slab_finish as rf_slab_word does.
+constexpr int kAxisGroup = 8;
+constexpr int kAxisBlock = 256;
+constexpr int kAxisWaves = kAxisBlock / 64;
+
+__device__ inline double wave_min(double v) {
+    for (int off = 32; off >= 1; off >>= 1) v = rf_min(v, __shfl_xor(v, off, 64));
+    return v;
+}
+__device__ inline double wave_max(double v) {
+    for (int off = 32; off >= 1; off >>= 1) v = rf_max(v, __shfl_xor(v, off, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(kAxisBlock) void k_refit_slab_axes(uint32_t n_nodes, double pad, const int32_t* __restrict__ child, const double* __restrict__ box,
+                                                                const double* __restrict__ sum, const uint32_t* __restrict__ run,
+                                                                const uint32_t* __restrict__ tri_order, const uint32_t* __restrict__ tri_pos,
+                                                                const double* __restrict__ positions, MeshNode4qc* __restrict__ nodes4q) {
+    const size_t id = blockIdx.x;  // 4 x node + child
+    const size_t i = id >> 2;
+    const int k = int(id & 3u);
+    if (i >= n_nodes) return;
+    const uint32_t lo = run[3 * id], hi = run[3 * id + 1], count = run[3 * id + 2];
+    if (!rf_slab_axis_eligible(child[id], n_nodes, nodes4q[i].cones.word[k], lo, hi, count, sum + 3 * id)) return;  // the whole block
+    __shared__ double s_lo[kAxisWaves][kSlabAxes], s_hi[kAxisWaves][kSlabAxes];
+    __shared__ double s_p[kAxisWaves][2];
+    __shared__ int s_pick;
+    const int tid = int(threadIdx.x), wave = tid >> 6, lane = tid & 63;
+    auto corners = [&](uint32_t slot, double* v) {  // as k_refit_tris forms the records
+        const size_t t = tri_order[slot];
+        const double* p0 = positions + 3 * size_t(tri_pos[3 * t]);
+        const double* p1 = positions + 3 * size_t(tri_pos[3 * t + 1]);
+        const double* p2 = positions + 3 * size_t(tri_pos[3 * t + 2]);
+        for (int a = 0; a < 3; a++) { v[a] = p0[a]; v[3 + a] = p1[a] - p0[a]; v[6 + a] = p2[a] - p0[a]; }
+    };
+    for (int g = 0; g < kSlabAxes; g += kAxisGroup) {
+        int q[kAxisGroup][3];
+        double mn[kAxisGroup], mx[kAxisGroup];
+#pragma unroll
+        for (int c = 0; c < kAxisGroup; c++) {
+            rf_slab_axis(g + c < kSlabAxes ? g + c : kSlabAxes - 1, q[c]);
+            mn[c] = INFINITY;
+            mx[c] = -INFINITY;
+        }
+        for (uint32_t slot = lo + uint32_t(tid); slot < hi; slot += uint32_t(kAxisBlock)) {
+            double v[9];
+            corners(slot, v);
+            for (int c3 = 0; c3 < 3; c3++) {
+                double x[3];
+                rf_tri_corner(v, c3, x);
+#pragma unroll
+                for (int c = 0; c < kAxisGroup; c++) {
+                    const double p = rf_axis_project(q[c], x);
+                    mn[c] = rf_min(mn[c], p);
+                    mx[c] = rf_max(mx[c], p);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < kAxisGroup; c++) {
+            const double a = wave_min(mn[c]), b = wave_max(mx[c]);
+            if (lane == 0 && g + c < kSlabAxes) { s_lo[wave][g + c] = a; s_hi[wave][g + c] = b; }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double smin[kSlabAxes], smax[kSlabAxes];
+        for (int c = 0; c < kSlabAxes; c++) {
+            smin[c] = s_lo[0][c];
+            smax[c] = s_hi[0][c];
+            for (int w = 1; w < kAxisWaves; w++) { smin[c] = rf_min(smin[c], s_lo[w][c]); smax[c] = rf_max(smax[c], s_hi[w][c]); }
+        }
+        s_pick = rf_slab_axis_pick(box + 6 * id, box + 6 * id + 3, smin, smax);
+    }
+    __syncthreads();
+    const int pick = s_pick;
+    if (pick < 0) return;
+    const uint32_t word = rf_slab_axis_word(pick);
+    int q[3];
+    rf_cone_axis(word, q);
+    float org[3], cell[3];
+    for (int a = 0; a < 3; a++) { org[a] = nodes4q[i].node.org[a]; cell[a] = nodes4q[i].node.cell[a]; }
+    const double inv_s = rf_slab_inv_scale(cell);
+    if (!(inv_s > 0.0) || !std::isfinite(inv_s) || !std::isfinite(pad)) return;  // rf_slab_word: no slab, so no axis
+    double plo = INFINITY, phi = -INFINITY;
+    for (uint32_t slot = lo + uint32_t(tid); slot < hi; slot += uint32_t(kAxisBlock)) {
+        double v[9];
+        corners(slot, v);
+        for (int c3 = 0; c3 < 3; c3++) {
+            double x[3];
+            rf_tri_corner(v, c3, x);
+            const double p = rf_slab_project(q, org, inv_s, x);
+            plo = rf_min(plo, p);
+            phi = rf_max(phi, p);
+        }
+    }
+    plo = wave_min(plo);
+    phi = wave_max(phi);
+    if (lane == 0) { s_p[wave][0] = plo; s_p[wave][1] = phi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < kAxisWaves; w++) { plo = rf_min(plo, s_p[w][0]); phi = rf_max(phi, s_p[w][1]); }
+        const uint32_t slab = rf_slab_finish(q, pad, inv_s, plo, phi);
+        if (slab != kNeutralSlab) {
+            nodes4q[i].cones.word[k] = word;
+            nodes4q[i].slabs.word[k] = slab;
+        }
+    }
+}
+
 template <typename T>
 bool dev_alloc(DevBuf<T>& p, size_t n, std::string* err) {
     if (p.reserve(std::max<size_t>(n, 1) * sizeof(T)) == RT_OK) return true;
@@ -278,6 +392,9 @@ bool refit_mesh_launch(RefitMesh& rm, const RefitTarget<R>& t, hipStream_t strea
     hipLaunchKernelGGL((k_refit_nodes2<R>), grid_for(rm.n_nodes), block, 0, stream, rm.n_nodes, rm.box2.get(), t.nodes);
     hipLaunchKernelGGL(k_refit_nodes4, grid_for(rm.n_nodes4), block, 0, stream, rm.n_nodes4, t.pad4, rm.child4.get(), rm.box4.get(), rm.sum4.get(), rm.run4.get(),
                        rm.tri_normal.get(), rm.tri_order.get(), rm.tri_pos.get(), rm.positions.get(), t.nodes4, t.nodes4q);
+    if (slab_axes_enabled() && rm.n_nodes4 > 0)
+        hipLaunchKernelGGL(k_refit_slab_axes, dim3(4u * rm.n_nodes4), dim3(kAxisBlock), 0, stream, rm.n_nodes4, t.pad4, rm.child4.get(), rm.box4.get(), rm.sum4.get(),
+                           rm.run4.get(), rm.tri_order.get(), rm.tri_pos.get(), rm.positions.get(), t.nodes4q);
     REFIT_TRY(hipGetLastError());
     return true;
 }

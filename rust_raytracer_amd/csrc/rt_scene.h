@@ -186,8 +186,11 @@ struct alignas(128) MeshNode4qc {
     uint32_t _pad[8];
 };
 static_assert(sizeof(MeshNode4qc) == 128, "one cache line per mesh node");
-constexpr uint32_t kNeutralCone = 0x7F000000u;  // (0, 0, 0, 127): never culls
-constexpr uint32_t kNeutralSlab = 0x7FFF8000u;  // [-32768, 32767], the word of a child without a cone (q = 0: the test sees 0)
+// A cone word is one of three things: a back-face cone (|q|_2 > 126, w in 1..127), a slab-only axis (0 < |q|_2 <= 126, w = 127:
+// dir . cone stays negative for every packed direction, so it never culls as a cone and only hands the slab step its axis;
+// rt_bvh.cpp build_mesh_slab_axes), or kNeutralCone.
+constexpr uint32_t kNeutralCone = 0x7F000000u;  // (0, 0, 0, 127): never culls, and no axis for a slab
+constexpr uint32_t kNeutralSlab = 0x7FFF8000u;  // [-32768, 32767], the word of a child with kNeutralCone (q = 0: the test sees 0)
 constexpr uint32_t kNoCullDir = 0x81000000u;    // (0, 0, 0, -127): the direction word of a ray that culls nothing
 
 // Triangle record for the intersection test: v0 and the two edges (mesh.rs:69-70 computes the

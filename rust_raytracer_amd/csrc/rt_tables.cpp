@@ -71,13 +71,14 @@ static bool quantise(const BuildNode4& sn, double m, BvhNode4q& qn) {
 // power of two (cell * iv exact), so against the f32-node test (fma(plane, iv, -o * iv)) there is one more rounding,
 // of a value bounded by 2 S |iv|; with it the error is < 2.5 x 2^-23 S |iv| per plane, inside the padding.
 // With them the back-face cone words of the children, with the conditioning limits of the arithmetic type (rt_bvh.cpp),
-// and their normal slabs, on the cones' axes.
+// the slab-only axes of inner children without a cone (unless RT_SLAB_AXES=0), and the normal slabs on all those axes.
 static int derive_nodes4qc(const CompiledScene& cs, const std::vector<double>& node_pad, bool f32, std::vector<MeshNode4qc>* out, std::string* err) {
     std::vector<BvhNode4q> nodes4q(cs.nodes4.size());
     for (size_t i = 0; i < nodes4q.size(); i++)
         if (!quantise(cs.nodes4[i], node_pad[i], nodes4q[i])) return refuse(err, "BVH node does not fit the 8-bit grid");
     std::vector<uint32_t> cone_words, slab_words;
     build_mesh_cones(cs.nodes4, cs.tris, cone_limits(f32), &cone_words);
+    if (slab_axes_enabled()) build_mesh_slab_axes(cs.nodes4, cs.tris, cone_limits(f32), nodes4q.data(), node_pad.data(), &cone_words);
     build_mesh_slabs(cs.nodes4, cs.tris, cone_words, nodes4q.data(), node_pad.data(), &slab_words);
     out->resize(cs.nodes4.size());
     for (size_t i = 0; i < out->size(); i++) {

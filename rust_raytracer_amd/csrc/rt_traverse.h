@@ -195,7 +195,9 @@ RT_DEV uint32_t node4q_entries(uint4 h0, uint4 h1, uint4 h2, const CullRay<R>& c
 // Normal slabs of a MeshNode4qc (cn: its cone words, sl: its sixth 16 bytes; builder and proof: rt_bvh.cpp): an entered child
 // whose span [nr, fr] of the culling ray lies wholly below or wholly above its slab becomes "not entered".  (o, d, t_shift):
 // the exact ray and where the culling ray starts on it.  leaves_only: RT_WF_SLABS=2.  nr[] of the children that stay, their
-// order and everything behind this step are untouched.  Explicit FMAs, as in node4q_spans.
+// order and everything behind this step are untouched.  Explicit FMAs, as in node4q_spans.  The axis is whatever the three axis
+// bytes of the cone word say: a back-face cone's, or the slab-only axis of a child without a cone (w = 127, never culls as a
+// cone); only kNeutralCone has q = 0 and with it no slab.
 template <typename R>
 RT_DEV void node4q_cull_slabs(uint4 h0, uint4 h1, uint4 cn, uint4 sl, V3<R> o, V3<R> d, R t_shift, bool leaves_only, const int32_t (&ch)[4],
                               const float (&fr)[4], float (&nr)[4]) {

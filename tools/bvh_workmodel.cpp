@@ -4,6 +4,11 @@
 //   g++ -std=c++17 -O2 -Irust_raytracer_amd/csrc -o tools/bvh_workmodel tools/bvh_workmodel.cpp rust_raytracer_amd/csrc/rt_bvh.cpp rust_raytracer_amd/csrc/rt_tables.cpp
 //   tools/bvh_workmodel scenes/resource/dragon_high.obj [paths = 150000] [pad0]
 //
+// The tables are derived twice by the library itself: with RT_SLAB_AXES=0 (cones and the slabs on their axes: the rows "with
+// cones" and "+ slabs") and with the slab-only axes of inner children without a cone (rt_bvh.cpp build_mesh_slab_axes: the row
+// "+ fitted axes").  For the last row it also prints the visits per depth of the tree and the split of the mesh rays by where
+// they start (on the mesh: the ray leaves a mesh hit; elsewhere) and whether they hit.
+//
 // pad0: the slab words are built with the mesh pad m = 0, which leaves of the margin |q|_1 (2 m / s + 2^-12) only the constant
 // term (below 0.1 of the 16-bit step): what the slabs could be worth with no margin at all.  Such words are NOT safe for the kernel.
 //
@@ -17,6 +22,7 @@
 // kernel is touched: change the tree or the traversal here and compare the two numbers.  The cone test must also leave
 // every ray's closest hit unchanged (same triangle, same t): the model counts the rays for which it does not.
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -67,7 +73,16 @@ static bool load_obj(const char* path, Mesh* m) {
     return !m->tri.empty();
 }
 
-struct Counters { unsigned long long rays = 0, visits = 0, tests = 0, hits = 0; };
+constexpr int kDepths = 12;  // deeper nodes count into the last bin
+struct Counters {
+    unsigned long long rays = 0, visits = 0, tests = 0, hits = 0;
+    unsigned long long by_depth[kDepths] = {};
+    void add(const Counters& o) {
+        rays += o.rays; visits += o.visits; tests += o.tests; hits += o.hits;
+        for (int i = 0; i < kDepths; i++) by_depth[i] += o.by_depth[i];
+    }
+};
+static std::vector<uint8_t> g_depth;  // per node: levels below the root
 
 // The slab tables of the tree: words and quantised nodes (grid origin, cells); mode 0 off, 1 every child, 2 leaf children only.
 struct Slabs { const uint32_t* words; const BvhNode4q* qnodes; int mode; double t_shift; };
@@ -113,6 +128,7 @@ static bool traverse(const Bvh4Build& b, const std::vector<TriRec<double>>& tris
         bool descend = false;
         if (node >= 0) {
             c.visits++;
+            c.by_depth[std::min<int>(g_depth[size_t(node)], kDepths - 1)]++;
             const BuildNode4& n = b.nodes[size_t(node)];
             double nr[4];
             int32_t ch[4];
@@ -224,18 +240,43 @@ int main(int argc, char** argv) {
     for (int a = 0; a < 3; a++) { box.lo[a] = b4.root_lo[a]; box.hi[a] = b4.root_hi[a]; }
     scene.mesh_bounds.push_back(box);
     scene.mesh_geoms.push_back(CompiledScene::MeshGeom{0, 0, 0, 0, uint32_t(b4.nodes.size()), 0, nt, bvh.max_depth, b4.max_stack});
-    MeshTables<double> tables;
+    MeshTables<double> tables, tables_fit;
     std::string err;
-    if (derive_mesh_tables(scene, &tables, &err) != RT_OK) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    double derive_ms[2][3];  // derive_mesh_tables without / with the slab-only axes, three times each, alternating
+    for (int rep = 0; rep < 3; rep++) {
+        setenv("RT_SLAB_AXES", "0", 1);
+        double t0 = now_ms();
+        if (derive_mesh_tables(scene, &tables, &err) != RT_OK) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+        derive_ms[0][rep] = now_ms() - t0;
+        unsetenv("RT_SLAB_AXES");
+        t0 = now_ms();
+        if (derive_mesh_tables(scene, &tables_fit, &err) != RT_OK) { std::fprintf(stderr, "%s\n", err.c_str()); return 1; }
+        derive_ms[1][rep] = now_ms() - t0;
+    }
     std::vector<BvhNode4q> qnodes(b4.nodes.size());
-    std::vector<uint32_t> cones(4 * b4.nodes.size()), slab_words(4 * b4.nodes.size());
+    std::vector<uint32_t> cones(4 * b4.nodes.size()), slab_words(4 * b4.nodes.size()), cones_fit(4 * b4.nodes.size()), slab_words_fit(4 * b4.nodes.size());
     for (size_t i = 0; i < b4.nodes.size(); i++) {
         qnodes[i] = tables.nodes4qc[i].node;
-        for (int k = 0; k < 4; k++) { cones[4 * i + size_t(k)] = tables.nodes4qc[i].cones.word[k]; slab_words[4 * i + size_t(k)] = tables.nodes4qc[i].slabs.word[k]; }
+        for (int k = 0; k < 4; k++) {
+            cones[4 * i + size_t(k)] = tables.nodes4qc[i].cones.word[k]; slab_words[4 * i + size_t(k)] = tables.nodes4qc[i].slabs.word[k];
+            cones_fit[4 * i + size_t(k)] = tables_fit.nodes4qc[i].cones.word[k]; slab_words_fit[4 * i + size_t(k)] = tables_fit.nodes4qc[i].slabs.word[k];
+        }
     }
     const bool pad0 = argc > 3 && std::strcmp(argv[3], "pad0") == 0;
-    if (pad0)  // the experiment: leaves the library's margin on purpose
-        build_mesh_slabs(b4.nodes, tris, cones, qnodes.data(), std::vector<double>(b4.nodes.size(), 0.0).data(), &slab_words);
+    if (pad0) {  // the experiment: leaves the library's margin on purpose
+        const std::vector<double> zero(b4.nodes.size(), 0.0);
+        build_mesh_slabs(b4.nodes, tris, cones, qnodes.data(), zero.data(), &slab_words);
+        build_mesh_slabs(b4.nodes, tris, cones_fit, qnodes.data(), zero.data(), &slab_words_fit);
+    }
+    g_depth.assign(b4.nodes.size(), 0);
+    for (size_t i = 0; i < b4.nodes.size(); i++)  // children stand behind their parent
+        for (int k = 0; k < 4; k++) {
+            const int32_t c = b4.nodes[i].child[k];
+            if (c >= 0 && size_t(c) < b4.nodes.size()) g_depth[size_t(c)] = uint8_t(std::min(255, g_depth[i] + 1));
+        }
+    size_t fitted = 0;
+    for (size_t i = 0; i < cones_fit.size(); i++) fitted += rf_is_slab_only(cones_fit[i]) ? 1 : 0;
     size_t with_slab = 0, with_cone = 0;
     for (size_t i = 0; i < slab_words.size(); i++) { with_slab += slab_words[i] != kNeutralSlab; with_cone += cones[i] != kNeutralCone; }
     size_t leaf = 0, leaf_cone = 0, inner = 0, inner_cone = 0;
@@ -257,12 +298,17 @@ int main(int argc, char** argv) {
     auto to_obj_p = [&](V p) { const V q = p - T; return V{cs * q.x - sn * q.z, q.y, sn * q.x + cs * q.z} * (1.0 / S); };
     auto to_obj_d = [&](V d) { return V{cs * d.x - sn * d.z, d.y, sn * d.x + cs * d.z} * (1.0 / S); };
     auto to_world_d = [&](V d) { return V{cs * d.x + sn * d.z, d.y, -sn * d.x + cs * d.z}; };
-    std::printf("slabs on %zu of the %zu children with a cone%s\n", with_slab, with_cone, pad0 ? " (pad0: margin without the mesh pad)" : "");
-    Counters plain, coned, plain_hit, plain_miss, slab_leaf, slab_all;
-    unsigned long long total_rays = 0, mesh_rays = 0, changed = 0, changed_leaf = 0, changed_all = 0;
+    std::printf("slabs on %zu of the %zu children with a cone%s; slab-only axes on %zu of the %zu inner children without a cone (%d candidates, ratio below %.2f)\n",
+                with_slab, with_cone, pad0 ? " (pad0: margin without the mesh pad)" : "", fitted, inner - inner_cone, kSlabAxes, kSlabAxisMaxRatio);
+    std::printf("derive_mesh_tables<double>: %.0f / %.0f / %.0f ms with RT_SLAB_AXES=0, %.0f / %.0f / %.0f ms with the axes\n", derive_ms[0][0], derive_ms[0][1],
+                derive_ms[0][2], derive_ms[1][0], derive_ms[1][1], derive_ms[1][2]);
+    Counters plain, coned, plain_hit, plain_miss, slab_leaf, slab_all, slab_fit, fit_split[2][2];
+    unsigned long long total_rays = 0, mesh_rays = 0, changed = 0, changed_leaf = 0, changed_all = 0, changed_fit = 0;
+    bool on_mesh = false;  // the ray starts at a mesh hit
     Rng rng{12345};
     for (int p = 0; p < n_paths; p++) {
         V o = {277.5, 277.5, -800};
+        on_mesh = false;
         V d = unit(V{rng.u() * 555.0, rng.u() * 555.0, 0} - o);
         for (int depth = 0; depth < 12; depth++) {
             total_rays++;
@@ -307,17 +353,29 @@ int main(int argc, char** argv) {
                     const bool h3 = traverse(b4, tris, cones.data(), &sl, oo, od, tw, mode == 2 ? slab_leaf : slab_all, &t3, &tri3);
                     if (h3 != mesh_hit || (h3 && (tri3 != tri || t3 != t_hit))) (mode == 2 ? changed_leaf : changed_all)++;
                 }
+                {
+                    const Slabs sl{slab_words_fit.data(), qnodes.data(), 1, std::max(t0, 0.0)};
+                    double t4 = tw;
+                    int tri4 = -1;
+                    Counters one_fit;
+                    const bool h4 = traverse(b4, tris, cones_fit.data(), &sl, oo, od, tw, one_fit, &t4, &tri4);
+                    if (h4 != mesh_hit || (h4 && (tri4 != tri || t4 != t_hit))) changed_fit++;
+                    slab_fit.add(one_fit);
+                    fit_split[on_mesh ? 1 : 0][mesh_hit ? 1 : 0].add(one_fit);
+                }
             }
             if (mesh_hit) {
                 const TriRec<double>& tr = tris[size_t(tri)];
                 V n = unit(to_world_d(cross(V{tr.e1[0], tr.e1[1], tr.e1[2]}, V{tr.e2[0], tr.e2[1], tr.e2[2]})));
                 if (dot(n, d) > 0) n = n * -1.0;
                 o = o + d * t_hit;
+                on_mesh = true;
                 d = rng.u() < 0.5 ? unit(d - n * (2 * dot(d, n))) : cosine_dir(n, rng);
             } else if (tw < kInf) {
                 const V h = o + d * tw;
                 if (nw.y < 0 && std::fabs(h.x - 277.5) < 130 && std::fabs(h.z - 277.5) < 105) break;  // the light
                 o = h;
+                on_mesh = false;
                 d = cosine_dir(nw, rng);
             } else {
                 break;
@@ -337,5 +395,17 @@ int main(int argc, char** argv) {
     std::printf("+ slabs, every child:   %6.2f visits (%+.1f %% of cones), %6.2f tests (%+.1f %%) per mesh ray; rays whose closest hit changed: %llu\n",
                 per(slab_all.visits, slab_all.rays), 100.0 * (per(slab_all.visits, coned.visits) - 1.0), per(slab_all.tests, slab_all.rays),
                 100.0 * (per(slab_all.tests, coned.tests) - 1.0), changed_all);
-    return (changed || changed_leaf || changed_all) ? 2 : 0;
+    std::printf("+ fitted axes, every child: %6.2f visits (%+.1f %% of slabs on every child), %6.2f tests (%+.1f %%) per mesh ray; rays whose closest hit changed: %llu\n",
+                per(slab_fit.visits, slab_fit.rays), 100.0 * (per(slab_fit.visits, slab_all.visits) - 1.0), per(slab_fit.tests, slab_fit.rays),
+                100.0 * (per(slab_fit.tests, slab_all.tests) - 1.0), changed_fit);
+    std::printf("visits per mesh ray by depth (root = 0), slabs on every child -> + fitted axes:");
+    for (int i = 0; i < kDepths; i++) std::printf(" %d: %.2f -> %.2f;", i, per(slab_all.by_depth[i], slab_all.rays), per(slab_fit.by_depth[i], slab_fit.rays));
+    std::printf("\nmesh rays with fitted axes by origin and outcome (share, visits, tests per ray):\n");
+    const char* names[2][2] = {{"origin elsewhere, miss", "origin elsewhere, hit"}, {"origin on the mesh, miss", "origin on the mesh, hit"}};
+    for (int a = 0; a < 2; a++)
+        for (int h = 0; h < 2; h++)
+            std::printf("  %-26s %5.1f %%  %6.2f  %6.2f   (%.1f %% of the visits)\n", names[a][h], 100.0 * per(fit_split[a][h].rays, slab_fit.rays),
+                        per(fit_split[a][h].visits, fit_split[a][h].rays), per(fit_split[a][h].tests, fit_split[a][h].rays),
+                        100.0 * per(fit_split[a][h].visits, slab_fit.visits));
+    return (changed || changed_leaf || changed_all || changed_fit) ? 2 : 0;
 }
