@@ -392,6 +392,19 @@ int rt_debug_handout_replay(const uint32_t* policy, uint32_t n, uint32_t waves, 
  * intersect (k_wf_prims + k_wf_mesh), bit 1 volumes inside k_wf_prims, bit 2 multi-mesh form of k_wf_mesh, bit 3 group
  * BVHs in k_wf_prims; [7] primitives in group BVHs. */
 int rt_scene_program(const RtSceneDesc* desc, int32_t* ops_out, uint32_t capacity, uint32_t* n_ops_out, uint64_t info[8]);
+/* Same, for the 4-wide BVHs of the re-built primitive groups (OP_GROUP) as k_wf_prims reads them, from the derivation that
+ * fills the device, in the f64 tables (f32 = 0) or the f32 tables (f32 != 0).  Per group g: roots_out[g] = its root in the
+ * scene-wide node array (its nodes run to the next group's root), group_boxes_out[6 g ..] = lo xyz, hi xyz of its box.
+ * Per node i: children_out[4 i + k] = child k as the kernel reads it, ABSOLUTE: >= 0 a node of the scene-wide array, < 0 a
+ * leaf with ~child = (first position in the scene-wide primitive array << 3) | (count - 1), INT32_MIN no child;
+ * boxes_out[24 i + 6 k ..] = that child's decoded quantised box (lo xyz, hi xyz; no child: lo > hi).  Per position j of the
+ * primitive array: prims_out[3 j ..] = pc of the primitive's op in the scene program, first entry and length of its run in
+ * the guard array; guards_out[] = the guard array (indices of the bounds table).  Every array may be NULL and is written up to
+ * its capacity; counts_out[0..5] = groups, nodes, primitive positions, guard entries, stack levels per lane that k_wf_prims
+ * is given, entries of the bounds table. */
+int rt_scene_groups(const RtSceneDesc* desc, uint32_t f32, uint32_t* roots_out, double* group_boxes_out, uint32_t group_capacity,
+                    int32_t* children_out, float* boxes_out, uint32_t node_capacity, int32_t* prims_out, uint32_t prim_capacity,
+                    int32_t* guards_out, uint32_t guard_capacity, uint32_t counts_out[6]);
 
 /* Frame pipelining (no counterpart in the reference, which renders one image per process run): while `flag` is set
  * (non-NULL), every rt_render / rt_render_device of this scene object stores 1 to `*flag` as soon as the render can no

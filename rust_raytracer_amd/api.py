@@ -649,6 +649,30 @@ def scene_program(desc) -> tuple:
                  "split": bool(plan & 1), "vol_prims": bool(plan & 2), "multi_mesh": bool(plan & 4), "group_bvh": bool(plan & 8)}
 
 
+def scene_groups(desc, f32: bool = False) -> dict:
+    """rt_scene_groups: the 4-wide BVHs of the re-built primitive groups as k_wf_prims reads them (host only, through the
+    derivation that fills the device).  {"roots" (g,) uint32 and "group_boxes" (g, 2, 3) float64 (lo, hi) per group; "children"
+    (n, 4) int32 absolute child references and "boxes" (n, 4, 2, 3) float32 decoded quantised child boxes (lo, hi; no child:
+    lo > hi) per node; "prims" (p, 3) int32 as (pc, guard_first, guard_count) per position of the primitive array; "guards" (q,)
+    int32, the guard array; "stack_levels": levels per lane that k_wf_prims is given; "n_bounds": entries of the bounds table}."""
+    lib = load_device_lib()
+    lib.rt_scene_groups.argtypes = [C.POINTER(RtSceneDesc), C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                    C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+    lib.rt_scene_groups.restype = C.c_int
+    counts = (C.c_uint32 * 6)()
+    st = lib.rt_scene_groups(desc, int(f32), None, None, 0, None, None, 0, None, 0, None, 0, counts)
+    _check(lib, st)
+    ng, nn, npr, nq = (int(counts[k]) for k in range(4))
+    roots, gboxes = np.zeros(ng, dtype=np.uint32), np.zeros((ng, 2, 3), dtype=np.float64)
+    children, boxes = np.zeros((nn, 4), dtype=np.int32), np.zeros((nn, 4, 2, 3), dtype=np.float32)
+    prims, guards = np.zeros((npr, 3), dtype=np.int32), np.zeros(nq, dtype=np.int32)
+    st = lib.rt_scene_groups(desc, int(f32), roots.ctypes.data, gboxes.ctypes.data, ng, children.ctypes.data, boxes.ctypes.data, nn,
+                             prims.ctypes.data, npr, guards.ctypes.data, nq, counts)
+    _check(lib, st)
+    return {"roots": roots, "group_boxes": gboxes, "children": children, "boxes": boxes, "prims": prims, "guards": guards,
+            "stack_levels": int(counts[4]), "n_bounds": int(counts[5])}
+
+
 def scene_op_nodes(desc) -> np.ndarray:
     """rt_scene_op_nodes: per op of the compiled program (api.scene_program order) the RtSceneDesc.nodes index it came from,
     -1 for ops that belong to no single node; host only."""

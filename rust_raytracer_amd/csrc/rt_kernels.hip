@@ -2156,6 +2156,51 @@ static int tables_digest_host(const CompiledScene& cs, uint64_t out[8]) {
     out[7] = 0;
     return RT_OK;
 }
+
+// rt_scene_groups for one arithmetic type: the group tables of derive_scene_tables, the rest from the CompiledScene as
+// DeviceScene<R>::build uploads it.
+struct GroupExportOut {
+    uint32_t* roots; double* group_boxes; uint32_t group_capacity;
+    int32_t* children; float* boxes; uint32_t node_capacity;
+    int32_t* prims; uint32_t prim_capacity;
+    int32_t* guards; uint32_t guard_capacity;
+    uint32_t* counts;
+};
+template <typename R>
+static int group_export_host(const CompiledScene& cs, const GroupExportOut& o) {
+    SceneTables<R> t;
+    std::string err;
+    if (int st = derive_scene_tables(cs, &t, &err)) return set_err(st, err);
+    o.counts[0] = uint32_t(t.groups.size());
+    o.counts[1] = uint32_t(t.group_nodes.size());
+    o.counts[2] = uint32_t(cs.group_prims.size());
+    o.counts[3] = uint32_t(cs.group_guards.size());
+    o.counts[4] = uint32_t(t.view.group_stack_levels);
+    o.counts[5] = uint32_t(t.bounds.size());
+    for (size_t g = 0; g < t.groups.size() && g < o.group_capacity; g++) {
+        if (o.roots) o.roots[g] = t.groups[g].root;
+        if (o.group_boxes)
+            for (int a = 0; a < 3; a++) { o.group_boxes[6 * g + size_t(a)] = double(t.groups[g].lo[a]); o.group_boxes[6 * g + 3 + size_t(a)] = double(t.groups[g].hi[a]); }
+    }
+    for (size_t i = 0; i < t.group_nodes.size() && i < o.node_capacity; i++) {
+        const BvhNode4q& n = t.group_nodes[i];
+        for (int k = 0; k < 4; k++) {
+            if (o.children) o.children[4 * i + size_t(k)] = n.child[k];
+            if (o.boxes)
+                for (int a = 0; a < 3; a++) {
+                    o.boxes[24 * i + 6 * size_t(k) + size_t(a)] = n.org[a] + float((n.qlo[a] >> (8 * k)) & 255u) * n.cell[a];
+                    o.boxes[24 * i + 6 * size_t(k) + 3 + size_t(a)] = n.org[a] + float((n.qhi[a] >> (8 * k)) & 255u) * n.cell[a];
+                }
+        }
+    }
+    if (o.prims)
+        for (size_t j = 0; j < cs.group_prims.size() && j < o.prim_capacity; j++) {
+            o.prims[3 * j] = cs.group_prims[j].pc; o.prims[3 * j + 1] = cs.group_prims[j].guard_first; o.prims[3 * j + 2] = cs.group_prims[j].guard_count;
+        }
+    if (o.guards)
+        for (size_t j = 0; j < cs.group_guards.size() && j < o.guard_capacity; j++) o.guards[j] = cs.group_guards[j];
+    return RT_OK;
+}
 }  // namespace rt
 
 // An accumulator belongs to the scene as it was when the accumulator was created.
@@ -2705,6 +2750,21 @@ int rt_scene_program(const RtSceneDesc* desc, int32_t* ops_out, uint32_t capacit
     info[6] = (plan.split ? 1u : 0u) | (plan.vol_prims ? 2u : 0u) | (plan.multi_mesh ? 4u : 0u) | (plan.groups ? 8u : 0u);
     info[7] = cs.group_prims.size();
     return RT_OK;
+}
+
+int rt_scene_groups(const RtSceneDesc* desc, uint32_t f32, uint32_t* roots_out, double* group_boxes_out, uint32_t group_capacity,
+                    int32_t* children_out, float* boxes_out, uint32_t node_capacity, int32_t* prims_out, uint32_t prim_capacity,
+                    int32_t* guards_out, uint32_t guard_capacity, uint32_t counts_out[6]) {
+    using namespace rt;
+    if (!desc || !counts_out) return set_err(RT_E_INVALID, "rt_scene_groups: NULL argument");
+    CompiledScene cs;
+    std::string err;
+    const CompileOptions opt = compile_options_from_env();
+    int st = compile_scene(desc, &cs, &err, opt);
+    if (st != RT_OK) return set_err(st, err);
+    const GroupExportOut o{roots_out, group_boxes_out, group_capacity, children_out, boxes_out, node_capacity, prims_out, prim_capacity,
+                           guards_out, guard_capacity, counts_out};
+    return f32 ? group_export_host<float>(cs, o) : group_export_host<double>(cs, o);
 }
 
 int rt_accum_create(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, RtAccum** out) {
