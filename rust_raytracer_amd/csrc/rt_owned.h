@@ -1,8 +1,8 @@
 // rt_owned.h — host only: the owners of everything the library allocates through HIP (device buffers, pinned host buffers,
-// events, streams) and the library's error channel.  This is the one file that calls the HIP allocation and creation
-// functions; every struct that holds a device resource holds one of these, so a destructor releases it and no release list
-// has to remember it.  The owners do not switch devices: whoever destroys them on another device than the current one calls
-// hipSetDevice first (~RtScene, ~RtAccum).
+// events, streams), and how a HIP failure reaches the error channel (rt_error.h).  This is the one file that calls the HIP
+// allocation and creation functions; every struct that holds a device resource holds one of these, so a destructor releases
+// it and no release list has to remember it.  The owners do not switch devices: whoever destroys them on another device
+// than the current one calls hipSetDevice first (~RtScene, ~RtAccum).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -12,15 +12,10 @@
 #include <utility>
 
 #include "../../include/rt_mi355.h"
+#include "rt_error.h"
 
 namespace rt {
 
-// ---- the error of the calling thread's last failed call (rt_last_error) ----
-inline thread_local std::string g_err;
-inline int set_err(int st, const std::string& msg) {
-    g_err = msg;
-    return st;
-}
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \

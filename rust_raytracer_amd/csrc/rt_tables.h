@@ -1,7 +1,7 @@
 // rt_tables.h — every table the kernels read, derived from a CompiledScene on the host (plain C++, no HIP).
 //
-// DeviceScene<R>::build (rt_kernels.hip) uploads these vectors as they stand; the host exports (rt_scene_refit_mesh,
-// rt_scene_mesh_cones, rt_scene_mesh_slabs, rt_scene_tables_digest) read the same vectors.  The per-node formulas are
+// DeviceScene<R>::build (rt_kernels.hip) uploads these vectors as they stand; the host exports of rt_desc.cpp
+// (rt_scene_refit_mesh, rt_scene_mesh_cones, rt_scene_mesh_slabs, rt_scene_tables_digest) read the same vectors.  The per-node formulas are
 // those of rt_refit.h and rt_bvh.cpp; compiled with -ffp-contract=off like the rest of the library.
 #pragma once
 #include <array>
