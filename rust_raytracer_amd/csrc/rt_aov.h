@@ -1,5 +1,6 @@
-// rt_aov.h — launchers of the first-hit AOV pass and of the a-trous denoiser (rt_aov.hip), called by the C ABI in
-// rt_kernels.hip.  Definitions of the outputs: include/rt_mi355.h (rt_render_aov, RtDenoiseParams), DESIGN.md §10.
+// rt_aov.h — launchers of the first-hit AOV pass (called by the C ABI in rt_kernels.hip) and of the a-trous denoiser, whose
+// entry points are in rt_aov.hip itself and whose other caller is the accumulator (rt_accum.hip).  Definitions of the
+// outputs: include/rt_mi355.h (rt_render_aov, RtDenoiseParams), DESIGN.md §10.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,5 +35,11 @@ int denoise_scratch_reserve(DenoiseScratch& s, size_t npix);
 // `stream`; the caller synchronises.
 hipError_t denoise_launch(const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams& dp,
                           double* d_out, DenoiseScratch& scratch, hipStream_t stream);
+
+// dp (NULL = the defaults) -> *out, checked; `who` names the entry point in the message.
+int denoise_params(const RtDenoiseParams* dp, RtDenoiseParams* out, const char* who);
+// Runs the filter on HBM buffers of the current device and waits for it; scratch: the caller's, or (NULL) one of its own.
+int denoise_run(const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams& dp, double* d_out,
+                DenoiseScratch* scratch, hipStream_t stream);
 
 }  // namespace rt

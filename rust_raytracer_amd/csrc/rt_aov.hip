@@ -1,8 +1,10 @@
 // rt_aov.hip — first-hit AOV pass and the edge-avoiding a-trous denoiser (include/rt_mi355.h: rt_render_aov,
-// rt_denoise).  A translation unit of its own: the render kernels in rt_kernels.hip are not touched.
+// rt_denoise), with the denoiser's entry points.  A translation unit of its own: the render kernels in
+// rt_kernels.hip are not touched.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <string>
 
 #include "rt_aov.h"
 #include "rt_device.h"
@@ -214,4 +216,75 @@ hipError_t denoise_launch(const double* d_rgba, const double* d_aov, uint32_t w,
     return hipGetLastError();
 }
 
+// dp (NULL = the defaults) -> *out, checked.
+int denoise_params(const RtDenoiseParams* dp, RtDenoiseParams* out, const char* who) {
+    if (dp) *out = *dp;
+    else rt_denoise_default_params(out);
+    if (out->iterations > RT_DENOISE_MAX_ITERATIONS)
+        return rt::set_err(RT_E_INVALID, std::string(who) + ": iterations must be at most " + std::to_string(RT_DENOISE_MAX_ITERATIONS));
+    for (double sg : {out->sigma_color, out->sigma_normal, out->sigma_albedo, out->sigma_depth})
+        if (!(sg > 0.0) || !std::isfinite(sg) || !std::isfinite(float(sg)) || !(float(sg) > 0.0f))
+            return rt::set_err(RT_E_INVALID, std::string(who) + ": every sigma must be a positive, finite f32 number");
+    return RT_OK;
+}
+
+// Runs the filter on HBM buffers of the current device and waits for it; scratch: the caller's, or (NULL) one of its own.
+int denoise_run(const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams& dp,
+                double* d_out, rt::DenoiseScratch* scratch, hipStream_t stream) {
+    using namespace rt;
+    DenoiseScratch own;
+    DenoiseScratch& scr = scratch ? *scratch : own;
+    if (dp.iterations)
+        if (int st = denoise_scratch_reserve(scr, size_t(w) * h)) return st;
+    hipError_t e = denoise_launch(d_rgba, d_aov, w, h, dp, d_out, scr, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("denoise: ") + hipGetErrorString(e));
+    return RT_OK;
+}
+
 }  // namespace rt
+
+extern "C" {
+
+int rt_denoise_default_params(RtDenoiseParams* out) {
+    if (!out) return rt::set_err(RT_E_INVALID, "rt_denoise_default_params: NULL argument");
+    *out = RtDenoiseParams{};
+    out->iterations = 4;  // tuned on 1-replica estimates against the full frame
+    out->aov_replicas = 1;
+    out->flags = RT_DENOISE_DEMODULATE;
+    out->sigma_color = 8.0;
+    out->sigma_normal = 0.3;
+    out->sigma_albedo = 0.3;
+    out->sigma_depth = 0.1;
+    return RT_OK;
+}
+
+int rt_denoise_device(int device, const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp,
+                      double* d_rgba_out, void* stream) {
+    using namespace rt;
+    if (!d_rgba || !d_aov || !d_rgba_out) return set_err(RT_E_INVALID, "rt_denoise_device: NULL argument");
+    RtDenoiseParams p;
+    if (int v = denoise_params(dp, &p, "rt_denoise_device")) return v;
+    HIP_TRY(hipSetDevice(device));
+    return denoise_run(d_rgba, d_aov, w, h, p, d_rgba_out, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rt_denoise(int device, const double* rgba, const double* aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp, double* rgba_out) {
+    using namespace rt;
+    if (!rgba || !aov || !rgba_out) return set_err(RT_E_INVALID, "rt_denoise: NULL argument");
+    RtDenoiseParams p;
+    if (int v = denoise_params(dp, &p, "rt_denoise")) return v;
+    const size_t npix = size_t(w) * h;
+    if (npix == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(device));
+    DevBuf<double> d_rgba, d_aov;
+    if (int st = d_rgba.reserve(npix * 4 * sizeof(double))) return st;
+    if (int st = d_aov.reserve(npix * kAovChannels * sizeof(double))) return st;
+    HIP_TRY(hipMemcpy(d_rgba, rgba, npix * 4 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_aov, aov, npix * kAovChannels * sizeof(double), hipMemcpyHostToDevice));
+    if (int st = denoise_run(d_rgba, d_aov, w, h, p, d_rgba, nullptr, nullptr)) return st;  // in place
+    HIP_TRY(hipMemcpy(rgba_out, d_rgba, npix * 4 * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -46,6 +46,11 @@ template <> struct Lim<float> {
 
 template <typename R> RT_DEV R pi() { return R(3.14159265358979323846264338327950288); }
 
+// Number of lanes below `lane` whose bit is set in `mask` (v_mbcnt_lo/hi).
+RT_DEV uint32_t lane_prefix(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
+}
+
 // ------------------------------------------------------------------ vec4.rs (xyz part)
 template <typename R>
 struct V3 {

@@ -1,5 +1,6 @@
-// rt_kernels.hip — render kernels, the wavefront / query / point / bake driver, the accumulators, and every entry point of the
-// C ABI (include/rt_mi355.h) that takes a scene or a device; those that take a description alone are in rt_desc.cpp.
+// rt_kernels.hip — render kernels, the wavefront / query / point / bake driver, and the entry points of the C ABI
+// (include/rt_mi355.h) that take a scene or a device, but for the progressive accumulator's (rt_accum.hip, a client of this
+// file through rt_render.h) and the denoiser's (rt_aov.hip); those that take a description alone are in rt_desc.cpp.
 // gfx950 only: 64-lane waves, per-lane traversal stack in LDS, HIP events on the launch stream.
 #include <hip/hip_runtime.h>
 
@@ -26,6 +27,7 @@
 #include "rt_point.h"
 #include "rt_query.h"
 #include "rt_refit.h"
+#include "rt_render.h"
 #include "rt_tables.h"
 #include "rt_wavefront.h"
 
@@ -802,16 +804,7 @@ struct PassBase {
 };
 struct FramePass : PassBase {};
 
-// One segment of an adaptive accumulator's render (rt_accum_render): the resolve step goes through
-// k_wf_resolve_moments; sparse: the replica groups cover the n_active pixels of `active` instead of the frame.  The caller
-// dispatches on `sparse`: AdaptiveMode<false> / <true> are the two modes.
-struct AdaptivePass {
-    const uint32_t* active = nullptr;
-    uint32_t n_active = 0;
-    bool sparse = false;
-    double *s1 = nullptr, *s2 = nullptr;
-    uint32_t* cnt = nullptr;
-};
+// The two modes of an AdaptivePass (rt_render.h), dense and sparse.
 template <bool SPARSE>
 struct AdaptiveMode : AdaptivePass, PassBase {
     template <typename R> using Group = std::conditional_t<SPARSE, WfGroupSparse<R>, WfGroup<R>>;
@@ -1574,7 +1567,7 @@ int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positio
 // kernels index the table with 32-bit element offsets.
 static uint32_t rays_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(1u, env_u32("RT_RAYS_CHUNK", 1u << 22))); }
 
-static void stats_add(RtRenderStats& total, const RtRenderStats& part, bool first) {
+void stats_add(RtRenderStats& total, const RtRenderStats& part, bool first) {
     if (first) { total = part; return; }
     total.kernel_ms += part.kernel_ms; total.traversal_kernel_ms += part.traversal_kernel_ms;
     total.prims_kernel_ms += part.prims_kernel_ms; total.shade_kernel_ms += part.shade_kernel_ms;
@@ -1747,7 +1740,7 @@ int with_device_frame(size_t bytes, void* host_out, size_t bytes_back, F&& run) 
     return e == hipSuccess ? int(RT_OK) : set_err(RT_E_DEVICE, std::string("hipMemcpy: ") + hipGetErrorString(e));
 }
 
-static int validate_render_args(const RtCameraDesc* camera, const RtRenderParams* params) {
+int validate_render_args(const RtCameraDesc* camera, const RtRenderParams* params) {
     if (params->sqrt_spt == 0 || params->thread_count == 0) return set_err(RT_E_INVALID, "sqrt_spt and thread_count must be positive");
     if (params->band_rows != 0 && params->n_parts > 1 && params->part >= params->n_parts) return set_err(RT_E_INVALID, "part >= n_parts");
     if (camera->image_width == 0 || camera->image_height == 0) return set_err(RT_E_INVALID, "empty image");
@@ -1776,120 +1769,6 @@ __global__ void k_debug_fuzzy_reflection(uint32_t n, const double* __restrict__ 
     state_out[2 * i] = a.s; state_out[2 * i + 1] = b.s;
 }
 }  // namespace rt
-
-// ---------------------------------------------------------------------------------------------
-// Progressive rendering (RtAccum, include/rt_mi355.h): estimate scaling, device output stage, digests
-// ---------------------------------------------------------------------------------------------
-namespace rt {
-
-// estimate = sum_k * (T / k), every double of the (owned_rows x width x 4) layout (w stays 0)
-__global__ void __launch_bounds__(256) k_accum_estimate(const double* __restrict__ sum, uint64_t n, double scale, double* __restrict__ out) {
-    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = sum[i] * scale;
-}
-
-// The host output stage (csrc/host/output.cpp tonemap_rgb8: ACES fit, clamp, sRGB OETF, saturating u8) on the device,
-// operation for operation and without contraction (the host build never fuses a*b+c); only pow may differ from the host's
-// in the last bit.  Input pixel i is rgba[4 i ..] * scale: the estimate of an accumulator is tone-mapped without a second
-// pass over HBM (scale 1 for a plain frame: x * 1 == x, and a NaN maps to 0 whatever its payload).
-__global__ void __launch_bounds__(256) k_tonemap_rgb8(const double* __restrict__ rgba, uint64_t npix, double scale, uint8_t* __restrict__ rgb) {
-#pragma clang fp contract(off)
-    const uint64_t i = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const double kIn[9] = {0.59719, 0.35458, 0.04823, 0.07600, 0.90834, 0.01566, 0.02840, 0.13383, 0.83777};
-    const double kOut[9] = {1.60475, -0.53108, -0.07367, -0.10208, 1.10813, -0.00605, -0.00327, -0.07276, 1.07602};
-    const double gamma = 1.0 / 2.4;
-    double p[4], c[3], f[3];
-    for (int k = 0; k < 4; k++) p[k] = rgba[4 * i + k] * scale;
-    for (int r = 0; r < 3; r++) c[r] = kIn[3 * r] * p[0] + kIn[3 * r + 1] * p[1] + kIn[3 * r + 2] * p[2] + 0.0 * p[3];
-    for (int k = 0; k < 3; k++) {
-        const double a = c[k] * (c[k] + 0.0245786) - 0.000090537;
-        const double b = c[k] * (c[k] * 0.983729 + 0.4329510) + 0.238081;
-        f[k] = a / b;
-    }
-    for (int r = 0; r < 3; r++) {
-        double x = kOut[3 * r] * f[0] + kOut[3 * r + 1] * f[1] + kOut[3 * r + 2] * f[2] + 0.0 * 0.0;
-        if (x < 0.0) x = 0.0;  // clamp01: NaN stays NaN
-        if (x > 1.0) x = 1.0;
-        const double v = x < 0.0031308 ? x * 12.92 : pow(x, gamma) * 1.055 - 0.055;
-        const double q = v * 255.999;
-        rgb[3 * i + r] = !(q > 0.0) ? uint8_t(0) : (q >= 255.0 ? uint8_t(255) : uint8_t(q));  // saturating `as u8`, NaN -> 0
-    }
-}
-
-// The camera and every params field that changes the frame (all but pipeline and collect_stats).
-static RtRenderParams frame_fields(const RtRenderParams& p) {
-    RtRenderParams q = p;
-    q.pipeline = 0;
-    q.collect_stats = 0;
-    return q;
-}
-static uint64_t frame_digest(const RtCameraDesc& c, const RtRenderParams& p) {
-    Digest g;
-    g.val(c.image_width); g.val(c.image_height); g.val(c.position); g.val(c.first_pixel); g.val(c.pixel_delta_u);
-    g.val(c.pixel_delta_v); g.val(c.basis_u); g.val(c.basis_v); g.val(c.has_aperture); g.val(c.aperture_radius);
-    const RtRenderParams q = frame_fields(p);
-    g.val(q.sqrt_spt); g.val(q.thread_count); g.val(q.max_depth); g.val(q.has_background); g.val(q.light_bias);
-    g.val(q.background); g.val(q.seed); g.val(q.band_rows); g.val(q.n_parts); g.val(q.part); g.val(q.precision);
-    return g.value();
-}
-
-// State blob: this header (little-endian), then owned_rows * width * 4 doubles of sum_k
-struct AccumHeader {
-    char magic[8];
-    uint32_t version, precision, width, owned_rows, thread_count, replicas_done;
-    uint64_t scene_digest, frame_digest;
-};
-static_assert(sizeof(AccumHeader) == 48, "state header layout");
-static const char kAccumMagic[8] = {'R', 'T', 'A', 'C', 'C', 'U', 'M', '\0'};
-static const uint32_t kAccumVersion = 1;
-static const uint32_t kAccumVersionAdaptive = 2;  // header, AdaptiveBlobParams, sum, s1, s2, n
-struct AdaptiveBlobParams {
-    double threshold, floor;
-    uint32_t min_replicas, check_interval, radius, zero;
-};
-static_assert(sizeof(AdaptiveBlobParams) == 32, "state parameter block layout");
-static AdaptiveBlobParams blob_params(const RtAdaptiveParams& p) { return AdaptiveBlobParams{p.threshold, p.floor, p.min_replicas, p.check_interval, p.radius, 0u}; }
-
-static int tonemap_launch(const double* d_rgba, uint64_t npix, double scale, uint8_t* d_rgb, hipStream_t stream) {
-    if (npix == 0) return RT_OK;
-    hipLaunchKernelGGL(k_tonemap_rgb8, dim3(uint32_t((npix + 255) / 256)), dim3(256), 0, stream, d_rgba, npix, scale, d_rgb);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    return RT_OK;
-}
-
-}  // namespace rt
-
-struct RtAccum {
-    RtScene* scene = nullptr;      // not owned: must outlive every call but rt_accum_destroy
-    uint64_t generation = 0;       // RtScene::generation at rt_accum_create: an accumulator does not outlive an rt_scene_update
-    int device = 0;                // the scene's device (rt_accum_destroy does not touch the scene)
-    RtCameraDesc camera{};
-    RtRenderParams params{};       // as created (pipeline / collect_stats: the defaults of rt_accum_render)
-    uint32_t owned = 0, T = 0, k = 0;
-    uint64_t frame_digest = 0;
-    rt::DevBuf<double> d_sum;      // sum_k, owned x width x 4 doubles: the accumulator's own buffer
-    rt::DevBuf<double> d_est;      // estimate scratch (lazy)
-    rt::DevBuf<uint8_t> d_rgb;     // preview scratch (lazy)
-    rt::DevBuf<double> d_aov;      // first-hit AOVs of the denoised previews (lazy, owned x width x 8; not in the state blob)
-    uint32_t aov_replicas = 0;     // replicas d_aov was rendered with (0: none yet)
-    rt::DenoiseScratch dn;         // denoiser scratch (lazy)
-    // adaptive mode (rt_accum_set_adaptive): moments, replica counts, the ascending list of active pixels (two buffers that
-    // take turns at a compaction) and the decision step's scratch
-    bool adaptive = false, touched = false;  // touched: a state has been loaded
-    RtAdaptiveParams ap{};
-    rt::DevBuf<double> d_s1, d_s2;
-    rt::DevBuf<uint32_t> d_cnt, d_active[2];
-    int cur = 0;
-    uint32_t n_active = 0;
-    rt::DevBuf<uint8_t> d_state, d_keep;
-    rt::DevBuf<uint32_t> d_block, d_n_out;
-    ~RtAccum() { (void)hipSetDevice(device); }  // before the members go: the owners do not switch devices
-    size_t n_doubles() const { return size_t(owned) * camera.image_width * 4; }
-    size_t npix() const { return size_t(owned) * camera.image_width; }
-    bool decision_point(uint32_t kk) const { return adaptive && kk >= ap.min_replicas && kk < T && (kk - ap.min_replicas) % ap.check_interval == 0; }
-};
 
 namespace rt {
 // The mesh export (rt_desc.h) from the tables a scene holds on the device
@@ -1920,11 +1799,64 @@ static int refit_typed(RtScene* s, const CompiledScene& cs, const std::vector<ui
     }
     return RT_OK;
 }
-}  // namespace rt
 
-// An accumulator belongs to the scene as it was when the accumulator was created.
-static bool accum_is_stale(const RtAccum* acc) { return acc->generation != acc->scene->generation; }
-static int accum_stale_error() { return rt::set_err(RT_E_INVALID, "the scene was updated after this accumulator was created"); }
+// ---------------------------------------------------------------------------------------------
+// What a client of the renderer uses (rt_render.h; the accumulator in rt_accum.hip)
+// ---------------------------------------------------------------------------------------------
+int render_replicas(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
+                    uint32_t t_first, uint32_t n, double* d_rgba_out, void* stream, const AdaptivePass* ad) {
+    if (!scene || !camera || !params || !d_rgba_out) return set_err(RT_E_INVALID, "rt_render_device: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    if (n == 0 || t_first + uint64_t(n) > params->thread_count) return set_err(RT_E_INVALID, "replica range outside [0, thread_count)");
+    RtScene* s = const_cast<RtScene*>(scene);  // stats + lazily built tables; the scene data itself is immutable
+    HIP_TRY(hipSetDevice(s->device));
+    uint32_t owned = owned_rows(camera->image_height, params);
+    if (owned == 0) return RT_OK;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    // AUTO: the wavefront scheduler (since its state accesses are coalesced streams it beats the per-pixel
+    // megakernel on every scene measured, with or without meshes); RT_AUTO_MEGA_NO_MESH=1 restores the old rule
+    bool has_mesh = !s->compiled.meshes.empty();
+    bool wavefront = params->pipeline == RT_PIPELINE_WAVEFRONT ||
+                     (params->pipeline == RT_PIPELINE_AUTO && (has_mesh || env_u32("RT_AUTO_MEGA_NO_MESH", 0) == 0));
+    if (params->max_depth == 0) wavefront = false;  // every sample is black (camera.rs:290): nothing to schedule
+    if (ad) {  // adaptive passes exist in the wavefront scheduler only
+        if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "adaptive passes run the wavefront scheduler: RT_PIPELINE_MEGAKERNEL is not supported");
+        if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, "adaptive sampling with max_depth = 0");
+        wavefront = true;  // collect_stats: refused by the mode
+    }
+    return with_tables(s, params->precision, [&](auto& ds) -> int {
+        if (ad && ad->sparse) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, AdaptiveMode<true>{*ad});
+        if (ad) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, AdaptiveMode<false>{*ad});
+        if (wavefront) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, FramePass{});
+        return render_typed(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st);
+    });
+}
+
+int render_aov_replicas(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
+                        double* d_out, void* stream) {
+    if (!scene || !camera || !params || !d_out) return set_err(RT_E_INVALID, "rt_render_aov: NULL argument");
+    if (int v = validate_render_args(camera, params)) return v;
+    if (n_replicas == 0 || n_replicas > params->thread_count) return set_err(RT_E_INVALID, "rt_render_aov: n_replicas must be in 1 .. thread_count");
+    RtScene* s = const_cast<RtScene*>(scene);  // lazily built tables only
+    HIP_TRY(hipSetDevice(s->device));
+    const uint32_t owned = owned_rows(camera->image_height, params);
+    if (owned == 0) return RT_OK;
+    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
+    return with_tables(s, params->precision, [&](auto& ds) { return aov_typed(s, ds, *camera, *params, owned, n_replicas, d_out, st); });
+}
+
+int scene_device(const RtScene* s) { return s->device; }
+hipStream_t scene_stream(const RtScene* s) { return s->stream; }
+uint64_t scene_generation(const RtScene* s) { return s->generation; }
+uint64_t scene_content_digest(const RtScene* s) { return s->content_digest; }
+const RtRenderStats& scene_stats(const RtScene* s) { return s->stats; }
+void scene_set_stats(RtScene* s, const RtRenderStats& stats) { s->stats = stats; }
+int32_t* scene_tail_flag(const RtScene* s) { return s->tail_flag; }
+void scene_set_tail_flag(RtScene* s, int32_t* flag) { s->tail_flag = flag; }
+void scene_release_tail(const RtScene* s) {
+    if (s->tail_flag) __atomic_store_n(s->tail_flag, 1, __ATOMIC_RELEASE);
+}
+}  // namespace rt
 
 extern "C" {
 
@@ -1970,41 +1902,9 @@ int rt_debug_live_resources(uint64_t out[4]) {
     return RT_OK;
 }
 
-// Renders the replicas [t_first, t_first + n) of the frame into d_rgba_out (running sum of [0, t_first) on entry):
-// rt_render_device is [0, T), rt_accum_render the next n of an accumulator.
-static int render_device_impl(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
-                              uint32_t t_first, uint32_t n, double* d_rgba_out, void* stream, const rt::AdaptivePass* ad = nullptr) {
-    using namespace rt;
-    if (!scene || !camera || !params || !d_rgba_out) return set_err(RT_E_INVALID, "rt_render_device: NULL argument");
-    if (int v = validate_render_args(camera, params)) return v;
-    if (n == 0 || t_first + uint64_t(n) > params->thread_count) return set_err(RT_E_INVALID, "replica range outside [0, thread_count)");
-    RtScene* s = const_cast<RtScene*>(scene);  // stats + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    uint32_t owned = owned_rows(camera->image_height, params);
-    if (owned == 0) return RT_OK;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    // AUTO: the wavefront scheduler (since its state accesses are coalesced streams it beats the per-pixel
-    // megakernel on every scene measured, with or without meshes); RT_AUTO_MEGA_NO_MESH=1 restores the old rule
-    bool has_mesh = !s->compiled.meshes.empty();
-    bool wavefront = params->pipeline == RT_PIPELINE_WAVEFRONT ||
-                     (params->pipeline == RT_PIPELINE_AUTO && (has_mesh || env_u32("RT_AUTO_MEGA_NO_MESH", 0) == 0));
-    if (params->max_depth == 0) wavefront = false;  // every sample is black (camera.rs:290): nothing to schedule
-    if (ad) {  // adaptive passes exist in the wavefront scheduler only
-        if (params->pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "adaptive passes run the wavefront scheduler: RT_PIPELINE_MEGAKERNEL is not supported");
-        if (params->max_depth == 0) return set_err(RT_E_UNSUPPORTED, "adaptive sampling with max_depth = 0");
-        wavefront = true;  // collect_stats: refused by the mode
-    }
-    return with_tables(s, params->precision, [&](auto& ds) -> int {
-        if (ad && ad->sparse) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, AdaptiveMode<true>{*ad});
-        if (ad) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, AdaptiveMode<false>{*ad});
-        if (wavefront) return render_wavefront(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st, FramePass{});
-        return render_typed(s, ds, *camera, *params, owned, t_first, n, d_rgba_out, st);
-    });
-}
-
 int rt_render_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params,
                      double* d_rgba_out, void* stream) {
-    int r = render_device_impl(scene, camera, params, 0, params ? params->thread_count : 0, d_rgba_out, stream);
+    int r = rt::render_replicas(scene, camera, params, 0, params ? params->thread_count : 0, d_rgba_out, stream);
     // whoever waits for this render's tail (rt_scene_set_tail_flag) is released at the latest here, errors included
     if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
     return r;
@@ -2243,321 +2143,10 @@ int rt_debug_scene_mesh_digest(const RtScene* scene, uint32_t f32, uint64_t out[
     return RT_OK;
 }
 
-int rt_accum_create(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, RtAccum** out) {
-    using namespace rt;
-    if (!out) return set_err(RT_E_INVALID, "rt_accum_create: out is NULL");
-    *out = nullptr;
-    if (!scene || !camera || !params) return set_err(RT_E_INVALID, "rt_accum_create: NULL argument");
-    if (int v = validate_render_args(camera, params)) return v;
-    const uint32_t owned = owned_rows(camera->image_height, params);
-    if (owned == 0) return set_err(RT_E_INVALID, "rt_accum_create: the row partition gives this part no rows");
-    std::unique_ptr<RtAccum> a(new (std::nothrow) RtAccum);
-    if (!a) return set_err(RT_E_NOMEM, "out of memory");
-    a->scene = const_cast<RtScene*>(scene);
-    a->generation = scene->generation;
-    a->device = scene->device;
-    a->camera = *camera;
-    a->params = *params;
-    a->owned = owned;
-    a->T = params->thread_count;
-    a->frame_digest = frame_digest(*camera, *params);
-    HIP_TRY(hipSetDevice(scene->device));
-    if (int st = a->d_sum.reserve(a->n_doubles() * sizeof(double))) return st;
-    HIP_TRY(hipMemset(a->d_sum, 0, a->n_doubles() * sizeof(double)));
-    HIP_TRY(hipDeviceSynchronize());
-    *out = a.release();
-    return RT_OK;
-}
-
-void rt_accum_destroy(RtAccum* acc) { delete acc; }  // ~RtAccum sets the device
-
-// Scan + scatter of the decision step: entries of `src` (n_src of them) with keep != 0 go, in order, to the other list, which
-// becomes the active list; 4 bytes come back to the host.
-static int adaptive_compact(RtAccum* a, const uint32_t* src, uint32_t n_src, hipStream_t st) {
-    using namespace rt;
-    const uint32_t n_blocks = (n_src + AD_CHUNK - 1) / AD_CHUNK;
-    hipLaunchKernelGGL(k_ad_scan, dim3(1), dim3(64), 0, st, a->d_block.get(), n_blocks, a->d_n_out.get());
-    hipLaunchKernelGGL(k_ad_scatter, dim3(n_blocks), dim3(256), 0, st, src, n_src, a->d_keep.get(), a->d_block.get(), a->d_active[a->cur ^ 1].get(), a->d_state.get());
-    HIP_TRY(hipGetLastError());
-    uint32_t n_new = 0;
-    HIP_TRY(hipMemcpyAsync(&n_new, a->d_n_out, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (n_new > n_src) return set_err(RT_E_DEVICE, "adaptive compaction returned more pixels than it was given");
-    a->cur ^= 1;
-    a->n_active = n_new;
-    return RT_OK;
-}
-
-// The decision at k = acc->k (a decision point): quiet flags, window rule, compaction of the active list.
-static int adaptive_decide(RtAccum* a, hipStream_t st) {
-    using namespace rt;
-    if (a->n_active == 0) return RT_OK;
-    const uint32_t n = a->n_active, n_blocks = (n + AD_CHUNK - 1) / AD_CHUNK;
-    const uint32_t* list = a->d_active[a->cur];
-    hipLaunchKernelGGL(k_ad_quiet, dim3((n + 255) / 256), dim3(256), 0, st, list, n, a->d_s1.get(), a->d_s2.get(), a->k, a->ap.threshold, a->ap.floor, a->d_state.get());
-    hipLaunchKernelGGL(k_ad_window, dim3(n_blocks), dim3(256), 0, st, list, n, a->d_state.get(), a->camera.image_width, a->owned, int(a->ap.radius), a->d_keep.get(), a->d_block.get());
-    return adaptive_compact(a, list, n, st);
-}
-
-// Active list from the counts (after a state load): n[p] == k, then the decision at k again if k is a decision point - it sees
-// the sums it saw before the save, so it stops the same pixels.
-static int adaptive_rebuild(RtAccum* a, hipStream_t st) {
-    using namespace rt;
-    const uint32_t n = uint32_t(a->npix()), n_blocks = (n + AD_CHUNK - 1) / AD_CHUNK;
-    hipLaunchKernelGGL(k_ad_flags_from_counts, dim3(n_blocks), dim3(256), 0, st, a->d_cnt.get(), n, a->k, a->d_active[a->cur].get(), a->d_keep.get(), a->d_state.get(), a->d_block.get());
-    if (int r = adaptive_compact(a, a->d_active[a->cur], n, st)) return r;
-    if (a->decision_point(a->k)) return adaptive_decide(a, st);
-    return RT_OK;
-}
-
-// rt_accum_render of an adaptive accumulator: segments that end at the decision points, a decision after each.
-static int accum_render_adaptive(RtAccum* acc, uint32_t n_replicas, RtRenderParams p, void* stream) {
-    using namespace rt;
-    if (p.pipeline == RT_PIPELINE_MEGAKERNEL) return set_err(RT_E_UNSUPPORTED, "rt_accum_render: adaptive passes run the wavefront scheduler, RT_PIPELINE_MEGAKERNEL is not supported");
-    if (p.collect_stats) return set_err(RT_E_UNSUPPORTED, "rt_accum_render: collect_stats is not supported on an adaptive accumulator");
-    p.pipeline = RT_PIPELINE_WAVEFRONT;
-    RtScene* s = acc->scene;
-    HIP_TRY(hipSetDevice(acc->device));
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    uint32_t left = std::min(n_replicas, acc->T - acc->k);
-    RtRenderStats total{};
-    bool first = true;
-    int32_t* const flag = s->tail_flag;  // the call's end releases a waiting frame (rt_accum_render), not a segment's
-    s->tail_flag = nullptr;
-    int r = RT_OK;
-    while (left > 0 && acc->n_active > 0) {
-        uint32_t next = acc->T;
-        if (acc->k < acc->ap.min_replicas) next = std::min(acc->T, acc->ap.min_replicas);
-        else if (acc->k < acc->T) next = uint32_t(std::min<uint64_t>(acc->T, uint64_t(acc->k) + acc->ap.check_interval - (acc->k - acc->ap.min_replicas) % acc->ap.check_interval));
-        const uint32_t m = std::min(left, next - acc->k);
-        AdaptivePass ad;
-        ad.active = acc->d_active[acc->cur];
-        ad.n_active = acc->n_active;
-        ad.sparse = acc->n_active < acc->npix();
-        ad.s1 = acc->d_s1; ad.s2 = acc->d_s2; ad.cnt = acc->d_cnt;
-        r = render_device_impl(s, &acc->camera, &p, acc->k, m, acc->d_sum, st, &ad);
-        if (r != RT_OK) break;
-        stats_add(total, s->stats, first);
-        first = false;
-        acc->k += m;
-        left -= m;
-        if (acc->decision_point(acc->k) && (r = adaptive_decide(acc, st)) != RT_OK) break;
-    }
-    s->tail_flag = flag;
-    if (!first) s->stats = total;
-    else if (r == RT_OK) { s->stats = RtRenderStats{}; s->stats.pipeline_used = RT_PIPELINE_WAVEFRONT; }  // nothing rendered
-    return r;
-}
-
-static int accum_render_impl(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream) {
-    using namespace rt;
-    if (!acc) return set_err(RT_E_INVALID, "rt_accum_render: NULL accumulator");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    RtRenderParams p = acc->params;
-    if (params_or_null) {
-        const RtRenderParams a = frame_fields(acc->params), b = frame_fields(*params_or_null);
-        if (std::memcmp(&a, &b, sizeof a) != 0)
-            return set_err(RT_E_INVALID, "rt_accum_render: params differ from the accumulator's in more than pipeline / collect_stats");
-        p.pipeline = params_or_null->pipeline;
-        p.collect_stats = params_or_null->collect_stats;
-    }
-    if (acc->adaptive) return accum_render_adaptive(acc, n_replicas, p, stream);
-    const uint32_t n = std::min(n_replicas, acc->T - acc->k);
-    if (n == 0) return RT_OK;
-    const int r = render_device_impl(acc->scene, &acc->camera, &p, acc->k, n, acc->d_sum, stream);
-    if (r == RT_OK) acc->k += n;
-    return r;
-}
-
-int rt_accum_render(RtAccum* acc, uint32_t n_replicas, const RtRenderParams* params_or_null, void* stream) {
-    const int r = accum_render_impl(acc, n_replicas, params_or_null, stream);
-    if (acc && acc->scene->tail_flag) __atomic_store_n(acc->scene->tail_flag, 1, __ATOMIC_RELEASE);  // as rt_render_device does
-    return r;
-}
-
-uint32_t rt_accum_replicas_done(const RtAccum* acc) { return acc ? acc->k : 0; }
-
-// The estimate of sum_k into the device buffer d_out (stream: NULL = the scene's stream; returns after it is complete).
-static int accum_estimate_to(const RtAccum* acc, double* d_out, hipStream_t stream) {
-    using namespace rt;
-    const size_t n = acc->n_doubles();
-    if (acc->adaptive) {
-        hipLaunchKernelGGL(k_accum_estimate_adaptive, dim3(uint32_t((n / 4 + 255) / 256)), dim3(256), 0, stream, acc->d_sum.get(), acc->d_cnt.get(), uint64_t(n / 4),
-                           double(acc->T), d_out);
-        HIP_TRY(hipGetLastError());
-    } else if (acc->k == acc->T) {  // factor 1: the estimate is the frame, bit for bit
-        HIP_TRY(hipMemcpyAsync(d_out, acc->d_sum, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    } else {
-        hipLaunchKernelGGL(k_accum_estimate, dim3(uint32_t((n + 255) / 256)), dim3(256), 0, stream, acc->d_sum.get(), uint64_t(n),
-                           double(acc->T) / double(acc->k), d_out);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    return RT_OK;
-}
-
-static int accum_check_estimate(const RtAccum* acc, const void* out, const char* who) {
-    if (!acc || !out) return rt::set_err(RT_E_INVALID, std::string(who) + ": NULL argument");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    if (acc->k == 0) return rt::set_err(RT_E_INVALID, std::string(who) + ": no replica rendered yet (k = 0)");
-    return RT_OK;
-}
-
-int rt_accum_estimate_device(const RtAccum* acc, double* d_rgba_out, void* stream) {
-    using namespace rt;
-    if (int v = accum_check_estimate(acc, d_rgba_out, "rt_accum_estimate_device")) return v;
-    HIP_TRY(hipSetDevice(acc->device));
-    return accum_estimate_to(acc, d_rgba_out, stream ? static_cast<hipStream_t>(stream) : acc->scene->stream);
-}
-
-static int accum_scratch(RtAccum* a) {
-    using namespace rt;
-    if (int st = a->d_est.reserve(a->n_doubles() * sizeof(double))) return st;
-    return a->d_rgb.reserve(a->n_doubles() / 4 * 3);
-}
-
-int rt_accum_estimate(const RtAccum* acc, double* rgba_out) {
-    using namespace rt;
-    if (int v = accum_check_estimate(acc, rgba_out, "rt_accum_estimate")) return v;
-    HIP_TRY(hipSetDevice(acc->device));
-    RtAccum* a = const_cast<RtAccum*>(acc);  // scratch buffers only
-    if (int st = accum_scratch(a)) return st;
-    if (int st = accum_estimate_to(a, a->d_est, a->scene->stream)) return st;
-    HIP_TRY(hipMemcpy(rgba_out, a->d_est, a->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_accum_preview_rgb8(const RtAccum* acc, uint8_t* rgb_out) {
-    using namespace rt;
-    if (int v = accum_check_estimate(acc, rgb_out, "rt_accum_preview_rgb8")) return v;
-    HIP_TRY(hipSetDevice(acc->device));
-    RtAccum* a = const_cast<RtAccum*>(acc);
-    if (int st = accum_scratch(a)) return st;
-    const double scale = a->k == a->T ? 1.0 : double(a->T) / double(a->k);  // the estimate, formed inside the kernel
-    if (a->adaptive) {  // per-pixel factors: the estimate first
-        if (int st = accum_estimate_to(a, a->d_est, a->scene->stream)) return st;
-        if (int st = tonemap_launch(a->d_est, a->n_doubles() / 4, 1.0, a->d_rgb, a->scene->stream)) return st;
-    } else if (int st = tonemap_launch(a->d_sum, a->n_doubles() / 4, scale, a->d_rgb, a->scene->stream)) {
-        return st;
-    }
-    HIP_TRY(hipMemcpy(rgb_out, a->d_rgb, a->n_doubles() / 4 * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_tonemap_rgb8_device(int device, const double* d_rgba, uint32_t width, uint32_t height, uint8_t* d_rgb, void* stream) {
-    using namespace rt;
-    if (!d_rgba || !d_rgb) return set_err(RT_E_INVALID, "rt_tonemap_rgb8_device: NULL argument");
-    HIP_TRY(hipSetDevice(device));
-    return tonemap_launch(d_rgba, uint64_t(width) * height, 1.0, d_rgb, static_cast<hipStream_t>(stream));
-}
-
-size_t rt_accum_state_size(const RtAccum* acc) {
-    if (!acc) return 0;
-    if (acc->adaptive) return sizeof(rt::AccumHeader) + sizeof(rt::AdaptiveBlobParams) + acc->npix() * (4 * 8 + 8 + 8 + 4);
-    return sizeof(rt::AccumHeader) + acc->n_doubles() * sizeof(double);
-}
-
-int rt_accum_save_state(const RtAccum* acc, void* buf, size_t size) {
-    using namespace rt;
-    if (!acc || !buf) return set_err(RT_E_INVALID, "rt_accum_save_state: NULL argument");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    if (size < rt_accum_state_size(acc)) return set_err(RT_E_INVALID, "rt_accum_save_state: buffer smaller than rt_accum_state_size");
-    AccumHeader h{};
-    std::memcpy(h.magic, kAccumMagic, 8);
-    h.version = acc->adaptive ? kAccumVersionAdaptive : kAccumVersion;
-    h.precision = acc->params.precision;
-    h.width = acc->camera.image_width;
-    h.owned_rows = acc->owned;
-    h.thread_count = acc->T;
-    h.replicas_done = acc->k;
-    h.scene_digest = acc->scene->content_digest;
-    h.frame_digest = acc->frame_digest;
-    HIP_TRY(hipSetDevice(acc->device));
-    char* body = static_cast<char*>(buf) + sizeof h;
-    if (acc->adaptive) {
-        const AdaptiveBlobParams bp = blob_params(acc->ap);
-        std::memcpy(body, &bp, sizeof bp);
-        body += sizeof bp;
-    }
-    HIP_TRY(hipMemcpy(body, acc->d_sum, acc->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
-    if (acc->adaptive) {
-        const size_t np = acc->npix();
-        body += np * 32;
-        HIP_TRY(hipMemcpy(body, acc->d_s1, np * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(body + np * 8, acc->d_s2, np * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(body + np * 16, acc->d_cnt, np * 4, hipMemcpyDeviceToHost));
-    }
-    std::memcpy(buf, &h, sizeof h);
-    return RT_OK;
-}
-
-int rt_accum_load_state(RtAccum* acc, const void* buf, size_t size) {
-    using namespace rt;
-    if (!acc || !buf) return set_err(RT_E_INVALID, "rt_accum_load_state: NULL argument");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    AccumHeader h;
-    if (size < sizeof h) return set_err(RT_E_INVALID, "rt_accum_load_state: state truncated (shorter than its header)");
-    std::memcpy(&h, buf, sizeof h);
-    auto bad = [](const std::string& what) { return set_err(RT_E_INVALID, "rt_accum_load_state: " + what); };
-    if (std::memcmp(h.magic, kAccumMagic, 8) != 0) return bad("not an accumulator state (wrong magic)");
-    const uint32_t want_version = acc->adaptive ? kAccumVersionAdaptive : kAccumVersion;
-    if (h.version != want_version)
-        return bad("state format version " + std::to_string(h.version) + ", expected " + std::to_string(want_version) +
-                   (acc->adaptive ? " (an adaptive accumulator)" : " (a plain accumulator)"));
-    if (h.precision != acc->params.precision) return bad("precision mismatch (state " + std::to_string(h.precision) + ", accumulator " + std::to_string(acc->params.precision) + ")");
-    if (h.width != acc->camera.image_width || h.owned_rows != acc->owned)
-        return bad("image size mismatch (state " + std::to_string(h.width) + " x " + std::to_string(h.owned_rows) + " rows, accumulator " +
-                   std::to_string(acc->camera.image_width) + " x " + std::to_string(acc->owned) + ")");
-    if (h.thread_count != acc->T) return bad("thread_count mismatch (state " + std::to_string(h.thread_count) + ", accumulator " + std::to_string(acc->T) + ")");
-    if (h.replicas_done > h.thread_count) return bad("state claims more replicas than thread_count");
-    if (h.scene_digest != acc->scene->content_digest) return bad("scene mismatch (the state was rendered from another scene description)");
-    if (h.frame_digest != acc->frame_digest) return bad("camera / render parameter mismatch (seed, camera, depth, light bias, background or row partition)");
-    if (size != rt_accum_state_size(acc)) return bad("state truncated or oversized (" + std::to_string(size) + " bytes, expected " + std::to_string(rt_accum_state_size(acc)) + ")");
-    const char* body = static_cast<const char*>(buf) + sizeof h;
-    const size_t np = acc->npix();
-    if (acc->adaptive) {
-        const AdaptiveBlobParams mine = blob_params(acc->ap);
-        if (std::memcmp(body, &mine, sizeof mine) != 0) return bad("adaptive parameter mismatch (threshold, floor, min_replicas, check_interval or radius)");
-        body += sizeof mine;
-        const char* cnt = body + np * 48;
-        for (size_t i = 0; i < np; i++) {
-            uint32_t c;
-            std::memcpy(&c, cnt + 4 * i, 4);
-            if (c > h.replicas_done || (c < h.replicas_done && !acc->decision_point(c))) return bad("a pixel's replica count is neither the state's nor a decision point");
-        }
-    }
-    HIP_TRY(hipSetDevice(acc->device));
-    HIP_TRY(hipMemcpy(acc->d_sum, body, acc->n_doubles() * sizeof(double), hipMemcpyHostToDevice));
-    if (acc->adaptive) {
-        HIP_TRY(hipMemcpy(acc->d_s1, body + np * 32, np * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(acc->d_s2, body + np * 40, np * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(acc->d_cnt, body + np * 48, np * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipDeviceSynchronize());  // the render kernels run on a non-blocking stream, not ordered against this copy
-    acc->k = h.replicas_done;
-    acc->touched = true;
-    if (acc->adaptive) return adaptive_rebuild(acc, acc->scene->stream);
-    return RT_OK;
-}
-
-// ---- First-hit AOVs and the denoiser (rt_aov.hip) ----------------------------------------------------------------
-static int render_aov_impl(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
-                           double* d_out, void* stream) {
-    using namespace rt;
-    if (!scene || !camera || !params || !d_out) return set_err(RT_E_INVALID, "rt_render_aov: NULL argument");
-    if (int v = validate_render_args(camera, params)) return v;
-    if (n_replicas == 0 || n_replicas > params->thread_count) return set_err(RT_E_INVALID, "rt_render_aov: n_replicas must be in 1 .. thread_count");
-    RtScene* s = const_cast<RtScene*>(scene);  // lazily built tables only
-    HIP_TRY(hipSetDevice(s->device));
-    const uint32_t owned = owned_rows(camera->image_height, params);
-    if (owned == 0) return RT_OK;
-    hipStream_t st = stream ? static_cast<hipStream_t>(stream) : s->stream;
-    return with_tables(s, params->precision, [&](auto& ds) { return aov_typed(s, ds, *camera, *params, owned, n_replicas, d_out, st); });
-}
-
+// ---- First-hit AOVs (kernel, denoiser and its entry points: rt_aov.hip) ------------------------------------------------
 int rt_render_aov_device(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
                          double* d_aov_out, void* stream) {
-    return render_aov_impl(scene, camera, params, n_replicas, d_aov_out, stream);
+    return rt::render_aov_replicas(scene, camera, params, n_replicas, d_aov_out, stream);
 }
 
 int rt_render_aov(const RtScene* scene, const RtCameraDesc* camera, const RtRenderParams* params, uint32_t n_replicas,
@@ -2567,219 +2156,8 @@ int rt_render_aov(const RtScene* scene, const RtCameraDesc* camera, const RtRend
     if (int v = validate_render_args(camera, params)) return v;
     HIP_TRY(hipSetDevice(scene->device));
     const size_t bytes = size_t(owned_rows(camera->image_height, params)) * camera->image_width * kAovChannels * sizeof(double);
-    if (bytes == 0) return render_aov_impl(scene, camera, params, n_replicas, aov_out, nullptr);  // argument checks only
-    return with_device_frame(bytes, aov_out, bytes, [&](double* d_out) { return render_aov_impl(scene, camera, params, n_replicas, d_out, nullptr); });
-}
-
-int rt_denoise_default_params(RtDenoiseParams* out) {
-    if (!out) return rt::set_err(RT_E_INVALID, "rt_denoise_default_params: NULL argument");
-    *out = RtDenoiseParams{};
-    out->iterations = 4;  // tuned on 1-replica estimates against the full frame
-    out->aov_replicas = 1;
-    out->flags = RT_DENOISE_DEMODULATE;
-    out->sigma_color = 8.0;
-    out->sigma_normal = 0.3;
-    out->sigma_albedo = 0.3;
-    out->sigma_depth = 0.1;
-    return RT_OK;
-}
-
-// dp (NULL = the defaults) -> *out, checked.
-static int denoise_params(const RtDenoiseParams* dp, RtDenoiseParams* out, const char* who) {
-    if (dp) *out = *dp;
-    else rt_denoise_default_params(out);
-    if (out->iterations > RT_DENOISE_MAX_ITERATIONS)
-        return rt::set_err(RT_E_INVALID, std::string(who) + ": iterations must be at most " + std::to_string(RT_DENOISE_MAX_ITERATIONS));
-    for (double sg : {out->sigma_color, out->sigma_normal, out->sigma_albedo, out->sigma_depth})
-        if (!(sg > 0.0) || !std::isfinite(sg) || !std::isfinite(float(sg)) || !(float(sg) > 0.0f))
-            return rt::set_err(RT_E_INVALID, std::string(who) + ": every sigma must be a positive, finite f32 number");
-    return RT_OK;
-}
-
-// Runs the filter on HBM buffers of the current device and waits for it; scratch: the caller's, or (NULL) one of its own.
-static int denoise_run(const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams& dp,
-                       double* d_out, rt::DenoiseScratch* scratch, hipStream_t stream) {
-    using namespace rt;
-    DenoiseScratch own;
-    DenoiseScratch& scr = scratch ? *scratch : own;
-    if (dp.iterations)
-        if (int st = denoise_scratch_reserve(scr, size_t(w) * h)) return st;
-    hipError_t e = denoise_launch(d_rgba, d_aov, w, h, dp, d_out, scr, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return set_err(RT_E_DEVICE, std::string("denoise: ") + hipGetErrorString(e));
-    return RT_OK;
-}
-
-int rt_denoise_device(int device, const double* d_rgba, const double* d_aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp,
-                      double* d_rgba_out, void* stream) {
-    using namespace rt;
-    if (!d_rgba || !d_aov || !d_rgba_out) return set_err(RT_E_INVALID, "rt_denoise_device: NULL argument");
-    RtDenoiseParams p;
-    if (int v = denoise_params(dp, &p, "rt_denoise_device")) return v;
-    HIP_TRY(hipSetDevice(device));
-    return denoise_run(d_rgba, d_aov, w, h, p, d_rgba_out, nullptr, static_cast<hipStream_t>(stream));
-}
-
-int rt_denoise(int device, const double* rgba, const double* aov, uint32_t w, uint32_t h, const RtDenoiseParams* dp, double* rgba_out) {
-    using namespace rt;
-    if (!rgba || !aov || !rgba_out) return set_err(RT_E_INVALID, "rt_denoise: NULL argument");
-    RtDenoiseParams p;
-    if (int v = denoise_params(dp, &p, "rt_denoise")) return v;
-    const size_t npix = size_t(w) * h;
-    if (npix == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(device));
-    DeviceBuffers buf;
-    double *d_rgba = nullptr, *d_aov = nullptr;
-    if (int st = buf.alloc(npix * 4 * sizeof(double), &d_rgba)) return st;
-    if (int st = buf.alloc(npix * kAovChannels * sizeof(double), &d_aov)) return st;
-    HIP_TRY(hipMemcpy(d_rgba, rgba, npix * 4 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_aov, aov, npix * kAovChannels * sizeof(double), hipMemcpyHostToDevice));
-    if (int st = denoise_run(d_rgba, d_aov, w, h, p, d_rgba, nullptr, nullptr)) return st;  // in place
-    HIP_TRY(hipMemcpy(rgba_out, d_rgba, npix * 4 * sizeof(double), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-// The denoised estimate of `a` into a->d_est (scene's stream, complete on return).  Renders the AOVs on first use.
-static int accum_denoise(RtAccum* a, const RtDenoiseParams* dp, const char* who) {
-    using namespace rt;
-    RtDenoiseParams p;
-    if (int v = denoise_params(dp, &p, who)) return v;
-    if (a->params.band_rows != 0 && a->params.n_parts > 1)
-        return set_err(RT_E_INVALID, std::string(who) + ": the accumulator has a row partition (the filter needs contiguous rows)");
-    if (p.aov_replicas == 0 || p.aov_replicas > a->T) return set_err(RT_E_INVALID, std::string(who) + ": aov_replicas must be in 1 .. thread_count");
-    HIP_TRY(hipSetDevice(a->device));
-    if (int st = accum_scratch(a)) return st;
-    const uint32_t w = a->camera.image_width;
-    if (a->aov_replicas != p.aov_replicas) {
-        if (int st = a->d_aov.reserve(size_t(a->owned) * w * kAovChannels * sizeof(double))) return st;
-        a->aov_replicas = 0;
-        if (int st = render_aov_impl(a->scene, &a->camera, &a->params, p.aov_replicas, a->d_aov, nullptr)) return st;
-        a->aov_replicas = p.aov_replicas;
-    }
-    if (int st = accum_estimate_to(a, a->d_est, a->scene->stream)) return st;
-    return denoise_run(a->d_est, a->d_aov, w, a->owned, p, a->d_est, &a->dn, a->scene->stream);
-}
-
-int rt_accum_estimate_denoised(const RtAccum* acc, const RtDenoiseParams* dp, double* rgba_out) {
-    using namespace rt;
-    if (int v = accum_check_estimate(acc, rgba_out, "rt_accum_estimate_denoised")) return v;
-    RtAccum* a = const_cast<RtAccum*>(acc);  // scratch buffers and the AOV cache only
-    if (int st = accum_denoise(a, dp, "rt_accum_estimate_denoised")) return st;
-    HIP_TRY(hipMemcpy(rgba_out, a->d_est, a->n_doubles() * sizeof(double), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_accum_preview_denoised_rgb8(const RtAccum* acc, const RtDenoiseParams* dp, uint8_t* rgb_out) {
-    using namespace rt;
-    if (int v = accum_check_estimate(acc, rgb_out, "rt_accum_preview_denoised_rgb8")) return v;
-    RtAccum* a = const_cast<RtAccum*>(acc);
-    if (int st = accum_denoise(a, dp, "rt_accum_preview_denoised_rgb8")) return st;
-    if (int st = tonemap_launch(a->d_est, a->n_doubles() / 4, 1.0, a->d_rgb, a->scene->stream)) return st;
-    HIP_TRY(hipMemcpy(rgb_out, a->d_rgb, a->n_doubles() / 4 * 3, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_adaptive_default_params(RtAdaptiveParams* out) {
-    if (!out) return rt::set_err(RT_E_INVALID, "rt_adaptive_default_params: NULL argument");
-    *out = RtAdaptiveParams{};
-    out->floor = 0.01;  // the values of the oracle experiment; the threshold has no default
-    out->min_replicas = 4;
-    out->check_interval = 2;
-    out->radius = 1;
-    return RT_OK;
-}
-
-int rt_accum_set_adaptive(RtAccum* acc, const RtAdaptiveParams* ap) {
-    using namespace rt;
-    if (!acc || !ap) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: NULL argument");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    if (acc->adaptive) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: the accumulator is adaptive already");
-    if (acc->k != 0 || acc->touched) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: only before the first replica and before a state is loaded");
-    if (!(ap->threshold > 0.0) || !std::isfinite(ap->threshold)) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: threshold must be positive and finite (it has no default)");
-    if (!(ap->floor > 0.0) || !std::isfinite(ap->floor)) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: floor must be positive and finite");
-    if (ap->min_replicas < 2) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: min_replicas must be at least 2 (a variance needs two replicas)");
-    if (ap->check_interval < 1) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: check_interval must be at least 1");
-    if (ap->radius > 4) return set_err(RT_E_INVALID, "rt_accum_set_adaptive: radius must be in 0 .. 4");
-    if (acc->params.band_rows != 0 && acc->params.n_parts > 1)
-        return set_err(RT_E_INVALID, "rt_accum_set_adaptive: the accumulator has a row partition (the window needs contiguous rows)");
-    if (acc->params.max_depth == 0) return set_err(RT_E_UNSUPPORTED, "rt_accum_set_adaptive: max_depth = 0 (adaptive passes run the wavefront scheduler)");
-    if (acc->npix() >= (1ull << 31)) return set_err(RT_E_UNSUPPORTED, "rt_accum_set_adaptive: more than 2^31 pixels");
-    HIP_TRY(hipSetDevice(acc->device));
-    const size_t np = acc->npix(), n_blocks = (np + AD_CHUNK - 1) / AD_CHUNK;
-    // local owners first: a failure half way leaves the accumulator as it was
-    DevBuf<double> s1, s2;
-    DevBuf<uint32_t> cnt, a0, a1, block, n_out;
-    DevBuf<uint8_t> state, keep;
-    auto zeroed = [](auto& buf, size_t bytes) -> int {
-        if (int st = buf.reserve(bytes)) return st;
-        HIP_TRY(hipMemset(buf, 0, bytes));
-        return RT_OK;
-    };
-    int st;
-    if ((st = zeroed(s1, np * 8)) || (st = zeroed(s2, np * 8)) || (st = zeroed(cnt, np * 4)) || (st = zeroed(a0, np * 4)) || (st = zeroed(a1, np * 4)) ||
-        (st = zeroed(state, np)) || (st = zeroed(keep, np)) || (st = zeroed(block, n_blocks * 4)) || (st = zeroed(n_out, 4))) return st;
-    {  // every pixel is active, in ascending order
-        std::vector<uint32_t> identity(np);
-        for (size_t i = 0; i < np; i++) identity[i] = uint32_t(i);
-        HIP_TRY(hipMemcpy(a0, identity.data(), np * 4, hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    acc->d_s1 = std::move(s1); acc->d_s2 = std::move(s2); acc->d_cnt = std::move(cnt);
-    acc->d_active[0] = std::move(a0); acc->d_active[1] = std::move(a1);
-    acc->d_state = std::move(state); acc->d_keep = std::move(keep);
-    acc->d_block = std::move(block); acc->d_n_out = std::move(n_out);
-    acc->cur = 0;
-    acc->n_active = uint32_t(np);  // all pixels: the dense kernels run until the first pixel stops (the list is not read)
-    acc->ap = *ap;
-    acc->adaptive = true;
-    return RT_OK;
-}
-
-uint32_t rt_accum_active_pixels(const RtAccum* acc) {
-    if (!acc) return 0;
-    if (acc->k >= acc->T) return 0;
-    return acc->adaptive ? acc->n_active : uint32_t(acc->npix());
-}
-
-int rt_accum_finished(const RtAccum* acc) {
-    if (!acc) return 0;
-    return (acc->k >= acc->T || (acc->adaptive && acc->n_active == 0)) ? 1 : 0;
-}
-
-int rt_accum_sample_counts(const RtAccum* acc, uint32_t* counts_out) {
-    using namespace rt;
-    if (!acc || !counts_out) return set_err(RT_E_INVALID, "rt_accum_sample_counts: NULL argument");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    if (!acc->adaptive) {
-        std::fill(counts_out, counts_out + acc->npix(), acc->k);
-        return RT_OK;
-    }
-    HIP_TRY(hipSetDevice(acc->device));
-    HIP_TRY(hipMemcpy(counts_out, acc->d_cnt, acc->npix() * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-int rt_accum_noise(const RtAccum* acc, double* noise_out) {
-    using namespace rt;
-    if (!acc || !noise_out) return set_err(RT_E_INVALID, "rt_accum_noise: NULL argument");
-    if (accum_is_stale(acc)) return accum_stale_error();
-    if (!acc->adaptive) return set_err(RT_E_INVALID, "rt_accum_noise: the accumulator keeps no moments (rt_accum_set_adaptive)");
-    HIP_TRY(hipSetDevice(acc->device));
-    const size_t np = acc->npix();
-    std::vector<double> s1(np), s2(np);
-    std::vector<uint32_t> cnt(np);
-    HIP_TRY(hipMemcpy(s1.data(), acc->d_s1, np * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(s2.data(), acc->d_s2, np * 8, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cnt.data(), acc->d_cnt, np * 4, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < np; i++) {  // a few flops per pixel on 20 bytes that cross the bus anyway
-        const uint32_t k = cnt[i];
-        if (k < 2) { noise_out[i] = 0.0; continue; }
-        const double mean = s1[i] / double(k);
-        double num = s2[i] - s1[i] * mean;
-        if (num < 0.0) num = 0.0;
-        noise_out[i] = std::sqrt(num / (double(k) * double(k - 1))) / (mean + acc->ap.floor);
-    }
-    return RT_OK;
+    if (bytes == 0) return rt::render_aov_replicas(scene, camera, params, n_replicas, aov_out, nullptr);  // argument checks only
+    return with_device_frame(bytes, aov_out, bytes, [&](double* d_out) { return rt::render_aov_replicas(scene, camera, params, n_replicas, d_out, nullptr); });
 }
 
 // ---------------------------------------------------------------------------------------------

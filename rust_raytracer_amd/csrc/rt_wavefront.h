@@ -340,11 +340,6 @@ __global__ void __launch_bounds__(256) k_wf_compact(WfPool<R> src, WfPool<R> dst
     at(dst.depth, i) = at(src.depth, s);
 }
 
-// Number of lanes below `lane` whose bit is set in `mask` (v_mbcnt_lo/hi).
-RT_DEV uint32_t lane_prefix(unsigned long long mask) {
-    return __builtin_amdgcn_mbcnt_hi(uint32_t(mask >> 32), __builtin_amdgcn_mbcnt_lo(uint32_t(mask), 0u));
-}
-
 // A single global word sustains only ~90 atomics/us on MI355X (MI355X_MICROARCH.md, "dequeue"), so
 // one atomic per WAVE on a queue tail (16 M paths = 260 k waves = 3 ms per launch) was the
 // bottleneck of every kernel here.  Queue traffic is therefore aggregated per WORKGROUP through
@@ -1789,7 +1784,7 @@ __global__ void __launch_bounds__(256) k_sh_irradiance(const double* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------
-// Adaptive passes (include/rt_mi355.h).
+// Adaptive passes (include/rt_mi355.h): the render's part; the decision step is in rt_accum.hip.
 // ---------------------------------------------------------------------------------------------
 // Resolve with moments: k_wf_resolve's ordered sums for the `n_entries` pixels of the group (SPARSE: pixel active[i]), always
 // from and to the accumulator's `sum`, plus the luminance moments of the per-replica contributions and the replica count.
@@ -1827,145 +1822,6 @@ __global__ void __launch_bounds__(256) k_wf_resolve_moments(const double* __rest
     s1[p] = m1;
     s2[p] = m2;
     cnt[p] += n_replicas;
-}
-
-// Pixel states of the decision step: a stopped pixel does not hold its neighbours, so it reads as quiet.
-constexpr uint8_t AD_NOISY = 0, AD_QUIET = 1, AD_STOPPED = 2;
-
-// se2 <= (threshold (mean + floor))^2 after k replicas; any NaN makes the comparison false.
-RT_DEV bool ad_quiet(double m1, double m2, uint32_t k, double threshold, double floor_) {
-#pragma clang fp contract(off)
-    const double mean = m1 / double(k);
-    double num = m2 - m1 * mean;
-    if (num < 0.0) num = 0.0;
-    const double se2 = num / (double(k) * double(k - 1u));
-    const double lim = threshold * (mean + floor_);
-    return se2 <= lim * lim;
-}
-
-// Decision, step 1: state[p] of every active pixel (every active pixel has n = k).
-__global__ void __launch_bounds__(256) k_ad_quiet(const uint32_t* __restrict__ active, uint32_t n_active, const double* __restrict__ s1,
-                                                  const double* __restrict__ s2, uint32_t k, double threshold, double floor_,
-                                                  uint8_t* __restrict__ state) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_active) return;
-    const uint32_t p = active[i];
-    state[p] = ad_quiet(s1[p], s2[p], k, threshold, floor_) ? AD_QUIET : AD_NOISY;
-}
-
-constexpr uint32_t AD_CHUNK = 2048;  // active-list entries per workgroup of the window and scatter kernels
-
-// Decision, step 2: entry i stays (keep[i] = 1) unless its pixel is quiet and no pixel of its window is noisy; per workgroup
-// the number of entries that stay.  Reads `state` only: the new states are written by k_ad_scatter.
-__global__ void __launch_bounds__(256) k_ad_window(const uint32_t* __restrict__ active, uint32_t n_active, const uint8_t* __restrict__ state,
-                                                   uint32_t width, uint32_t height, int radius, uint8_t* __restrict__ keep,
-                                                   uint32_t* __restrict__ block_count) {
-    __shared__ uint32_t total;
-    if (threadIdx.x == 0) total = 0;
-    __syncthreads();
-    const uint32_t begin = blockIdx.x * AD_CHUNK;
-    const uint32_t end = min(n_active, begin + AD_CHUNK);
-    uint32_t mine = 0;
-    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
-        const uint32_t p = active[i];
-        const int y = int(p / width), x = int(p - uint32_t(y) * width);
-        bool stop = state[p] == AD_QUIET;
-        for (int dy = -radius; stop && dy <= radius; dy++) {
-            const int yy = y + dy;
-            if (yy < 0 || yy >= int(height)) continue;
-            for (int dx = -radius; dx <= radius; dx++) {
-                const int xx = x + dx;
-                if (xx < 0 || xx >= int(width)) continue;
-                stop = stop && state[uint32_t(yy) * width + uint32_t(xx)] != AD_NOISY;
-            }
-        }
-        keep[i] = stop ? 0 : 1;
-        mine += stop ? 0u : 1u;
-    }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
-    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(&total, mine);  // integer sum: the order does not matter
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// Decision, step 3: exclusive scan of the workgroup counts by one wave (in place), the total to *n_out.
-__global__ void __launch_bounds__(64) k_ad_scan(uint32_t* __restrict__ block_count, uint32_t n_blocks, uint32_t* __restrict__ n_out) {
-    const uint32_t lane = threadIdx.x;
-    uint32_t base = 0;
-    for (uint32_t b0 = 0; b0 < n_blocks; b0 += 64) {
-        const uint32_t b = b0 + lane;
-        const uint32_t v = b < n_blocks ? block_count[b] : 0u;
-        uint32_t incl = v;
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off);
-            if (int(lane) >= off) incl += o;
-        }
-        if (b < n_blocks) block_count[b] = base + incl - v;
-        base += __shfl(incl, 63);
-    }
-    if (lane == 0) *n_out = base;
-}
-
-// Decision, step 4: order-preserving compaction of the active list (ballot prefix inside a wave, wave totals through LDS;
-// no atomic decides a position); the pixels that leave the list become AD_STOPPED.
-__global__ void __launch_bounds__(256) k_ad_scatter(const uint32_t* __restrict__ active, uint32_t n_active, const uint8_t* __restrict__ keep,
-                                                    const uint32_t* __restrict__ block_offset, uint32_t* __restrict__ active_out,
-                                                    uint8_t* __restrict__ state) {
-    __shared__ uint32_t wave_total[4];
-    const uint32_t begin = blockIdx.x * AD_CHUNK;
-    const uint32_t end = min(n_active, begin + AD_CHUNK);
-    const uint32_t wave = threadIdx.x >> 6;
-    uint32_t base = block_offset[blockIdx.x];
-    for (uint32_t i0 = begin; i0 < end; i0 += blockDim.x) {
-        const uint32_t i = i0 + threadIdx.x;
-        const bool in = i < end;
-        const uint32_t p = in ? active[i] : 0u;
-        const bool stay = in && keep[i] != 0;
-        const unsigned long long m = __ballot(stay);
-        if ((threadIdx.x & 63u) == 0) wave_total[wave] = uint32_t(__popcll(m));
-        __syncthreads();
-        uint32_t before = 0, all = 0;
-        for (uint32_t w = 0; w < 4; w++) {
-            const uint32_t c = wave_total[w];
-            before += w < wave ? c : 0u;
-            all += c;
-        }
-        if (stay) active_out[base + before + lane_prefix(m)] = p;
-        else if (in) state[p] = AD_STOPPED;
-        base += all;
-        __syncthreads();
-    }
-}
-
-// Rebuilds the list after a state load: pixel p is active iff n[p] == k.  Same scan, flags from the counts.
-__global__ void __launch_bounds__(256) k_ad_flags_from_counts(const uint32_t* __restrict__ cnt, uint32_t npix, uint32_t k, uint32_t* __restrict__ identity,
-                                                              uint8_t* __restrict__ keep, uint8_t* __restrict__ state, uint32_t* __restrict__ block_count) {
-    __shared__ uint32_t total;
-    if (threadIdx.x == 0) total = 0;
-    __syncthreads();
-    const uint32_t begin = blockIdx.x * AD_CHUNK;
-    const uint32_t end = min(npix, begin + AD_CHUNK);
-    uint32_t mine = 0;
-    for (uint32_t i = begin + threadIdx.x; i < end; i += blockDim.x) {
-        const bool on = cnt[i] == k;
-        identity[i] = i;
-        keep[i] = on ? 1 : 0;
-        state[i] = AD_NOISY;  // k_ad_scatter marks the others AD_STOPPED
-        mine += on ? 1u : 0u;
-    }
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_down(mine, off);
-    if ((threadIdx.x & 63u) == 0 && mine) atomicAdd(&total, mine);
-    __syncthreads();
-    if (threadIdx.x == 0) block_count[blockIdx.x] = total;
-}
-
-// estimate of an adaptive accumulator: sum[p] * (T / n[p]) (w stays 0; the factor is exactly 1 at n = T)
-__global__ void __launch_bounds__(256) k_accum_estimate_adaptive(const double* __restrict__ sum, const uint32_t* __restrict__ cnt, uint64_t npix,
-                                                                 double T, double* __restrict__ out) {
-    const uint64_t p = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (p >= npix) return;
-    const double scale = T / double(cnt[p]);
-    for (int k = 0; k < 4; k++) out[4 * p + k] = sum[4 * p + k] * scale;
 }
 
 }  // namespace rt
