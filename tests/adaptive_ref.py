@@ -74,10 +74,14 @@ def contributions_from_snapshots(snapshots):
         return s[1:] - s[:-1]
 
 
-def simulate(contrib, threshold, floor=0.01, min_replicas=4, check_interval=2, radius=1):
+def simulate(contrib, threshold, floor=0.01, min_replicas=4, check_interval=2, radius=1, start=None):
     """Runs the rule over contrib (T, H, W, >= 3).  Returns a dict: n (uint32), s1, s2, sum (H, W, 3), active (bool: still
     active at the end), band (bool: se2 within BAND of lim^2 at one of the pixel's decision points), exempt (band dilated
-    by the window: pixels whose decision may depend on one in the band)."""
+    by the window: pixels whose decision may depend on one in the band).
+
+    `start` = dict(k, n, s1, s2, sum, active) resumes at replica k from that state, as a loaded accumulator does
+    (rt_accum_load_state): `active` is the set before any decision at k, and if k is a decision point the decision at k is
+    taken on the given moments first; contrib[:k] is not read."""
     contrib = np.asarray(contrib, dtype=np.float64)
     T, h, w = contrib.shape[:3]
     D = set(decision_points(T, min_replicas, check_interval))
@@ -87,8 +91,21 @@ def simulate(contrib, threshold, floor=0.01, min_replicas=4, check_interval=2, r
     total = np.zeros((h, w, 3))
     active = np.ones((h, w), dtype=bool)
     band = np.zeros((h, w), dtype=bool)
+    first = 0
+    if start is not None:
+        first = int(start["k"])
+        n = np.array(start["n"], dtype=np.uint32).reshape(h, w)
+        s1 = np.array(start["s1"], dtype=np.float64).reshape(h, w)
+        s2 = np.array(start["s2"], dtype=np.float64).reshape(h, w)
+        total = np.array(start["sum"], dtype=np.float64).reshape(h, w, -1)[..., :3]
+        active = np.array(start["active"], dtype=bool).reshape(h, w)
+        if first in D:
+            with np.errstate(all="ignore"):
+                se2, lim2, _ = se2_and_limit(s1, s2, first, threshold, floor)
+                band |= active & (np.abs(se2 - lim2) <= BAND * lim2)
+                active = active & ~stops(se2 <= lim2, active, radius)
     with np.errstate(all="ignore"):
-        for t in range(T):
+        for t in range(first, T):
             if not active.any():
                 break
             c = contrib[t, ..., :3]
