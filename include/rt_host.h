@@ -30,6 +30,7 @@ typedef struct RtHost RtHost;
  * --light-mix=<w0>,<w1>,..., --pick=<x>,<y>[:...], --ao=<samples>[:<max_distance>], --probe=<x>,<y>,<z>[:<width>], --irradiance,
  * --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]
  * --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]
+ * --lightmap=<k>:<width>[x<height>][:<passes>]
  * (unknown keys are ignored by the reference, config.rs:146, so these
  * are compatible).
  * Relative scene/asset paths resolve against the current directory, as in
@@ -96,6 +97,14 @@ uint32_t rth_sh_probes(const RtHost* host, double* positions_out, uint32_t capac
  * rth_load rejects malformed values, and --nearest in the combinations --sh-probe is rejected in, and with --sh-probe itself.
  * rth_nearest_points returns the number of points and writes up to `capacity` of them (3 doubles each; points_out may be NULL). */
 uint32_t rth_nearest_points(const RtHost* host, double* points_out, uint32_t capacity);
+/* Lightmaps (rt_bake_lightmap): --lightmap=<k>:<width>[x<height>][:<passes>] (k: the k-th mesh op of the compiled program,
+ * from 0; sizes 1 .. 16384, height = width if not given; dilation passes, default 2, at most 1024): rtrace bakes the
+ * irradiance map of that mesh over its own UVs with the run's -s, -t, depth, bias, seed and precision and writes
+ * out_lightmap.png, through the output stage of out.png, INSTEAD of the frame; row 0 of the file is v near 0, so the file can
+ * be fed back as an image texture.  rth_load rejects malformed values, and --lightmap in the combinations --sh-probe is
+ * rejected in, and with --sh-probe or --nearest; rtrace refuses --sequence and a depth of 0 before a device is touched.
+ * rth_lightmap returns the width (0: no flag) and copies k, the height and the passes (each pointer may be NULL).            */
+uint32_t rth_lightmap(const RtHost* host, uint32_t* op_out, uint32_t* height_out, uint32_t* passes_out);
 /* Light probe (rt_render_rays): --probe=<x>,<y>,<z>[:<width>] (a finite position; width 2 .. 65536, default 512; the height
  * is width / 2): rtrace renders the equirectangular panorama of rth_probe_rays at that point with the run's -s, -t, depth,
  * bias, seed and precision and writes out_probe.png INSTEAD of the frame.  No pixel filter: every sample of a texel goes along

@@ -860,6 +860,80 @@ int rt_sh_irradiance(int device, const double* sh, uint64_t n_probes, const uint
 int rt_sh_irradiance_device(int device, const double* d_sh, uint64_t n_probes, const uint32_t* d_probe, const double* d_normals, uint64_t m,
                             double* d_rgba_out, void* stream);
 
+/* ---- Lightmaps: a mesh's UV atlas rasterised into surface records, baked and dilated -----------
+ * A width x height map over the UV square [0, 1]^2 of one mesh op: texel (x, y), x < width, y < height, has the centre
+ * p = ((x + 0.5) / width, (y + 0.5) / height); no flip (row 0 is v near 0: the addressing of RT_TEX_IMAGE, so a baked map can
+ * be fed back as an image texture over the mesh's own UVs) and no repeat (UVs outside the square are clipped by it).
+ * For a triangle with UV corners a, b, c (the first two components of its three `uvs` entries), in f64, one rounding per
+ * operation:
+ *     edge(s, t, q)  = (t.u - s.u) * (q.v - s.v) - (t.v - s.v) * (q.u - s.u)
+ *     cedge(s, t, q) = edge(s, t, q) if (s.u, s.v) <= (t.u, t.v) lexicographically, else -edge(t, s, q)
+ *     A = cedge(a, b, c), w_a = cedge(b, c, p), w_b = cedge(c, a, p), w_c = cedge(a, b, p); if A < 0 all four are negated.
+ * Two triangles that share a UV edge see exactly opposite values on it: a centre can lie in both, never in neither.  A
+ * triangle covers nothing if !(A > 0) (zero area, NaN) or if it has no UV indices; otherwise it covers the texel iff
+ * w_a >= 0 && w_b >= 0 && w_c >= 0.  count(x, y) = the number of the mesh's triangles that cover the texel; the texel belongs
+ * to the covering triangle with the LOWEST index in RtMesh.tri_pos order.  Its record, in the order of mesh.rs:104-147:
+ *     bu = w_b / A, bv = w_c / A, bw = 1 - bu - bv;   pos = v0 + (e1 * bu + e2 * bv)      (object space)
+ *     normal = cross(e1, e2).to_unit() under RT_MESH_FLAT_SHADING, else n0 * bw + n1 * bu + n2 * bv
+ *     every Transform above the mesh, innermost first (transform.rs:132-133): pos = M * pos, normal = (M * normal).to_unit();
+ *     without any transform the normal is normalised once
+ *     u, v = a * bw + b * bu + c * bv;  t = 0;  flags = RT_RAY_HIT | RT_RAY_FRONT_FACE;  material, node, prim as rt_trace_rays
+ *     sets them (prim = the triangle in RtMesh.tri_pos order).
+ * An uncovered texel gets the miss record (t = +inf, flags 0, ids -1, reals 0), which the _hits_device bakes skip.  Always
+ * f64.  hits_out: width * height records, row-major; counts_out (may be NULL): width * height values of count(x, y).
+ * `node` is the RtSceneDesc.nodes index of an RT_NODE_MESH; `instance` picks the k-th op of the compiled program that came from
+ * that node (rt_scene_op_nodes), for a mesh node reached more than once.  The mesh's tables are the scene's own f64 tables
+ * (built on first use), so a scene moved by rt_scene_update rasterises its new vertices.
+ * The device bins the triangles into tiles of 16 x 16 texels; if the number of (triangle, tile) references exceeds
+ * RT_LIGHTMAP_MAX_REFS (environment variable, read at each call, default 2^28) the call is RT_E_UNSUPPORTED with both numbers
+ * in the message.  RT_E_INVALID, naming the field: a NULL array, width or height of 0 or above 16384, a node out of range or
+ * not a mesh, an instance beyond the node's ops, negative passes, a bad kind.  RT_E_UNSUPPORTED: a mesh without UVs, a mesh
+ * that is a volume's boundary, the reference cap, and for rt_bake_lightmap a scene with volumes and whatever the underlying
+ * bake refuses.  On any error the outputs are untouched.  Synchronous; must not overlap a render or an update of the same
+ * scene.  The workspace belongs to the scene, grows only and is freed by rt_scene_destroy.                                   */
+int rt_lightmap_texels(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, RtRayHit* hits_out,
+                       uint32_t* counts_out_or_null);
+/* Device pointers on the scene's device; stream NULL = the scene's own.  Returns after the kernels complete. */
+int rt_lightmap_texels_device(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, RtRayHit* d_hits_out,
+                              uint32_t* d_counts_out_or_null, void* stream);
+/* Host only, needs no device: the same rule by brute force (every triangle x every texel) from the description alone. */
+int rt_lightmap_texels_desc(const RtSceneDesc* desc, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, RtRayHit* hits_out,
+                            uint32_t* counts_out_or_null);
+/* Dilation: rgba = w * h * 4 doubles, coverage = w * h bytes (0 = uncovered).  In each of `passes` passes an uncovered texel
+ * with at least one covered 8-neighbour takes the mean of its covered neighbours - the sum formed in the order dy = -1 .. 1,
+ * dx = -1 .. 1, then divided by their number - and counts as covered (1) in the next pass; texels outside the map are not
+ * neighbours; every other texel keeps its value.  passes = 0: a copy (coverage normalised to 0 / 1).  The outputs must not be
+ * the inputs.  Runs on device `device`.                                                                                  */
+int rt_lightmap_dilate(int device, const double* rgba, const uint8_t* coverage, uint32_t w, uint32_t h, int32_t passes, double* rgba_out,
+                       uint8_t* coverage_out);
+/* The same on HBM buffers of `device`, enqueued on `stream` (NULL = the null stream); returns after the kernels complete. */
+int rt_lightmap_dilate_device(int device, const double* d_rgba, const uint8_t* d_coverage, uint32_t w, uint32_t h, int32_t passes,
+                              double* d_rgba_out, uint8_t* d_coverage_out, void* stream);
+/* A lightmap in one call, everything on the device between the stages: rt_lightmap_texels_device, then
+ * rt_bake_irradiance_hits_device with render_params (kind = RT_LIGHTMAP_IRRADIANCE) or rt_bake_visibility_hits_device with
+ * bake_params (kind = RT_LIGHTMAP_VISIBILITY, NULL = its defaults; visibility in r, g and b, w = 0, uncovered texels zeroed),
+ * then rt_lightmap_dilate_device with dilate_passes.  rgba_out: width * height * 4 doubles; coverage_out: width * height bytes,
+ * the coverage BEFORE dilation (1 = the texel has a record).                                                              */
+#define RT_LIGHTMAP_IRRADIANCE 0u
+#define RT_LIGHTMAP_VISIBILITY 1u
+int rt_bake_lightmap(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, uint32_t kind,
+                     const RtRenderParams* render_params, const RtBakeParams* bake_params, int32_t dilate_passes, double* rgba_out,
+                     uint8_t* coverage_out);
+int rt_bake_lightmap_device(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, uint32_t kind,
+                            const RtRenderParams* render_params, const RtBakeParams* bake_params, int32_t dilate_passes, double* d_rgba_out,
+                            uint8_t* d_coverage_out, void* stream);
+/* Of the last rasterisation on this scene (rt_lightmap_texels* and rt_bake_lightmap*). */
+typedef struct RtLightmapStats {
+    double   bin_ms;             /* HIP-event time of the per-tile counts, the scan and the fill */
+    double   raster_ms;          /* HIP-event time of the raster kernel */
+    uint64_t texels;             /* width * height */
+    uint64_t covered_texels;
+    uint64_t tile_refs;          /* (triangle, tile) references */
+    uint32_t width, height;
+    uint32_t _reserved[4];
+} RtLightmapStats;
+int rt_lightmap_stats(const RtScene* scene, RtLightmapStats* out);
+
 /* Message for the last non-RT_OK status on this thread ("" if none). */
 const char* rt_last_error(void);
 

@@ -22,7 +22,8 @@ RT_E_INVALID, RT_E_UNSUPPORTED, RT_E_DEVICE, RT_E_NOMEM = -1, -2, -3, -4
 RT_PRECISION_F64, RT_PRECISION_F32 = 0, 1
 RT_PIPELINE_AUTO, RT_PIPELINE_MEGAKERNEL, RT_PIPELINE_WAVEFRONT = 0, 1, 2
 RT_SCENE_BVH_ON_DEVICE = 1  # RtSceneDesc.flags
-RT_MESH_HIT_BACK_FACES = 2  # RtMesh.flags
+RT_MESH_FLAT_SHADING = 1  # RtMesh.flags
+RT_MESH_HIT_BACK_FACES = 2
 RT_DENOISE_DEMODULATE = 1  # RtDenoiseParams.flags
 RT_DENOISE_MAX_ITERATIONS = 16
 AOV_CHANNELS = 8  # rt_render_aov: albedo rgb, normal xyz, depth, coverage
@@ -217,6 +218,16 @@ class RtBakeParams(C.Structure):
 # RtBakeResult (include/rt_mi355.h) as a numpy structured dtype: DeviceScene.bake_visibility returns an array of it
 RtBakeResult = np.dtype([("visibility", "<f8"), ("bent", "<f8", (3,))])
 assert RtBakeResult.itemsize == 32
+
+
+class RtLightmapStats(C.Structure):
+    """include/rt_mi355.h RtLightmapStats: the last rasterisation of a lightmap on a scene."""
+    _fields_ = [("bin_ms", C.c_double), ("raster_ms", C.c_double), ("texels", C.c_uint64), ("covered_texels", C.c_uint64),
+                ("tile_refs", C.c_uint64), ("width", C.c_uint32), ("height", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
+
+
+RT_LIGHTMAP_IRRADIANCE, RT_LIGHTMAP_VISIBILITY = 0, 1
+_LIGHTMAP_KINDS = {"irradiance": RT_LIGHTMAP_IRRADIANCE, "visibility": RT_LIGHTMAP_VISIBILITY}
 
 
 class RtError(RuntimeError):
@@ -488,6 +499,21 @@ def load_device_lib() -> C.CDLL:
             lib.rt_sh_irradiance.restype = C.c_int
             lib.rt_sh_irradiance_device.argtypes = [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
             lib.rt_sh_irradiance_device.restype = C.c_int
+        if hasattr(lib, "rt_lightmap_texels"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
+            u32, vp = C.c_uint32, C.c_void_p
+            for name, res, args in (
+                    ("rt_lightmap_texels", C.c_int, [vp, u32, u32, u32, u32, vp, vp]),
+                    ("rt_lightmap_texels_device", C.c_int, [vp, u32, u32, u32, u32, vp, vp, vp]),
+                    ("rt_lightmap_texels_desc", C.c_int, [C.POINTER(RtSceneDesc), u32, u32, u32, u32, vp, vp]),
+                    ("rt_lightmap_dilate", C.c_int, [C.c_int, vp, vp, u32, u32, C.c_int32, vp, vp]),
+                    ("rt_lightmap_dilate_device", C.c_int, [C.c_int, vp, vp, u32, u32, C.c_int32, vp, vp, vp]),
+                    ("rt_bake_lightmap", C.c_int, [vp, u32, u32, u32, u32, u32, C.POINTER(RtRenderParams), C.POINTER(RtBakeParams), C.c_int32, vp, vp]),
+                    ("rt_bake_lightmap_device", C.c_int, [vp, u32, u32, u32, u32, u32, C.POINTER(RtRenderParams), C.POINTER(RtBakeParams), C.c_int32,
+                                                          vp, vp, vp]),
+                    ("rt_lightmap_stats", C.c_int, [vp, C.POINTER(RtLightmapStats)])):
+                fn = getattr(lib, name)
+                fn.argtypes = args
+                fn.restype = res
         if hasattr(lib, "rt_debug_live_resources"):  # absent from older A/B builds loaded through RT_DEVICE_LIB
             lib.rt_debug_live_resources.argtypes = [C.POINTER(C.c_uint64)]
             lib.rt_debug_live_resources.restype = C.c_int
@@ -528,6 +554,32 @@ def scene_tables_digest(desc, f32: bool = False) -> tuple:
     st = lib.rt_scene_tables_digest(desc, int(f32), out)
     _check(lib, st)
     return tuple(int(x) for x in out)
+
+
+def lightmap_texels_desc(desc, node: int, width: int, height: int, instance: int = 0, counts: bool = False):
+    """rt_lightmap_texels_desc: the texel rule of DeviceScene.lightmap_texels by brute force on the host, from the description
+    alone (no device needed): (height, width) api.RtRayHit records, and with counts=True also the (height, width) uint32 number
+    of covering triangles per texel."""
+    lib = load_device_lib()
+    hits = np.zeros((max(height, 0), max(width, 0)) if 0 < width <= 16384 and 0 < height <= 16384 else (1, 1), dtype=RtRayHit)
+    cnt = np.zeros(hits.shape, dtype=np.uint32) if counts else None
+    st = lib.rt_lightmap_texels_desc(desc, node, instance, width, height, hits.ctypes.data, None if cnt is None else cnt.ctypes.data)
+    _check(lib, st)
+    return (hits, cnt) if counts else hits
+
+
+def lightmap_dilate(rgba, coverage, passes: int = 2, device: int = 0) -> tuple:
+    """rt_lightmap_dilate: `passes` dilation passes of an (h, w, 4) float64 image with its (h, w) coverage (non-zero = covered):
+    an uncovered texel next to covered ones takes their mean and counts as covered from then on.  Returns (rgba, coverage)."""
+    lib = load_device_lib()
+    img = np.ascontiguousarray(rgba, dtype=np.float64)
+    cov = np.ascontiguousarray(coverage, dtype=np.uint8)
+    if img.ndim != 3 or img.shape[2] != 4 or cov.shape != img.shape[:2]:
+        raise ValueError("lightmap_dilate: rgba must be (h, w, 4) and coverage (h, w)")
+    out, out_c = np.zeros_like(img), np.zeros_like(cov)
+    st = lib.rt_lightmap_dilate(device, img.ctypes.data, cov.ctypes.data, img.shape[1], img.shape[0], passes, out.ctypes.data, out_c.ctypes.data)
+    _check(lib, st)
+    return out, out_c
 
 
 def live_resources() -> tuple:
@@ -1199,6 +1251,45 @@ class DeviceScene:
         """rt_bake_stats: of the last bake (rays = n * samples); ray_query_stats() is not touched by a bake."""
         s = RtRayQueryStats()
         st = self._lib.rt_bake_stats(self._h, C.byref(s))
+        _check(self._lib, st)
+        return s
+
+    def lightmap_texels(self, node: int, width: int, height: int, instance: int = 0, counts: bool = False):
+        """rt_lightmap_texels: the UV atlas of mesh node `node` (RtSceneDesc.nodes index; `instance`: the k-th op of the program
+        that came from it) rasterised into (height, width) api.RtRayHit records, row 0 = v near 0; an uncovered texel holds the
+        miss record.  counts=True: also the (height, width) uint32 number of triangles that cover each texel centre."""
+        ok = 0 < width <= 16384 and 0 < height <= 16384
+        hits = np.zeros((height, width) if ok else (1, 1), dtype=RtRayHit)
+        cnt = np.zeros(hits.shape, dtype=np.uint32) if counts else None
+        st = self._lib.rt_lightmap_texels(self._h, node, instance, width, height, hits.ctypes.data, None if cnt is None else cnt.ctypes.data)
+        _check(self._lib, st)
+        return (hits, cnt) if counts else hits
+
+    def lightmap_texels_device(self, node: int, width: int, height: int, d_hits_ptr: int, d_counts_ptr: int = 0, instance: int = 0,
+                               stream: int = 0) -> None:
+        """rt_lightmap_texels_device: width * height RtRayHit records (96 B each) into HBM; d_counts_ptr 0 = no counts."""
+        st = self._lib.rt_lightmap_texels_device(self._h, node, instance, width, height, C.c_void_p(d_hits_ptr or None),
+                                                 C.c_void_p(d_counts_ptr or None), C.c_void_p(stream))
+        _check(self._lib, st)
+
+    def bake_lightmap(self, node: int, width: int, height: int, params, kind: str = "irradiance", dilate: int = 2, instance: int = 0) -> tuple:
+        """rt_bake_lightmap: rasterise, bake and dilate in one call, everything on the device in between -> ((height, width, 4)
+        float64 image, (height, width) uint8 coverage before dilation).  kind "irradiance": params is an RtRenderParams
+        (rt_bake_irradiance's conventions); kind "visibility": params is an RtBakeParams or None (its defaults)."""
+        k = _LIGHTMAP_KINDS[kind] if isinstance(kind, str) else int(kind)
+        ok = 0 < width <= 16384 and 0 < height <= 16384
+        out = np.zeros((height, width, 4) if ok else (1, 1, 4), dtype=np.float64)
+        cov = np.zeros(out.shape[:2], dtype=np.uint8)
+        rp = C.byref(params) if isinstance(params, RtRenderParams) else None
+        bp = C.byref(params) if isinstance(params, RtBakeParams) else None
+        st = self._lib.rt_bake_lightmap(self._h, node, instance, width, height, k, rp, bp, dilate, out.ctypes.data, cov.ctypes.data)
+        _check(self._lib, st)
+        return out, cov
+
+    def lightmap_stats(self) -> RtLightmapStats:
+        """rt_lightmap_stats: HIP-event times of the last rasterisation (binning, raster), covered texels, tile references."""
+        s = RtLightmapStats()
+        st = self._lib.rt_lightmap_stats(self._h, C.byref(s))
         _check(self._lib, st)
         return s
 

@@ -16,7 +16,7 @@ REPO_DIR = os.path.dirname(PKG_DIR)
 CSRC = os.path.join(PKG_DIR, "csrc")
 HOST_SRC = ["scene_builder.cpp", "obj_loader.cpp", "config.cpp", "dsl_loader.cpp", "default_scene.cpp",
             "output.cpp", "host_api.cpp", "image_loader.cpp"]
-DEVICE_SRC = ["rt_kernels.hip", "rt_accum.hip", "rt_aov.hip", "rt_query.hip", "rt_bake.hip", "rt_point.hip", "rt_bvh_device.hip", "rt_refit.hip", "rt_compile.cpp", "rt_bvh.cpp", "rt_tables.cpp", "rt_desc.cpp"]
+DEVICE_SRC = ["rt_kernels.hip", "rt_accum.hip", "rt_aov.hip", "rt_query.hip", "rt_bake.hip", "rt_point.hip", "rt_lightmap.hip", "rt_bvh_device.hip", "rt_refit.hip", "rt_compile.cpp", "rt_bvh.cpp", "rt_tables.cpp", "rt_desc.cpp"]
 DEVICE_HDR = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))  # every header: a stale library can never be what the tests run
 
 

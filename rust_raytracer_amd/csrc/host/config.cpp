@@ -305,6 +305,26 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
                 if (colon == std::string::npos) break;
                 pos = colon + 1;
             }
+        } else if (key == "-lightmap") {  // new: the irradiance lightmap of one mesh op (rt_bake_lightmap) instead of a render
+            const size_t c1 = value.find(':'), c2 = c1 == std::string::npos ? c1 : value.find(':', c1 + 1);
+            size_t k = 0, w = 0, h = 0, passes = 2;
+            bool ok = c1 != std::string::npos && parse_usize(value.substr(0, c1), &k) && k <= 0x7FFFFFFFu;
+            if (ok) {
+                const std::string size = value.substr(c1 + 1, c2 == std::string::npos ? std::string::npos : c2 - c1 - 1);
+                const size_t x = size.find('x');
+                ok = parse_usize(size.substr(0, x), &w) && (x == std::string::npos ? (h = w, true) : parse_usize(size.substr(x + 1), &h)) &&
+                     w >= 1 && w <= 16384 && h >= 1 && h <= 16384;
+            }
+            if (ok && c2 != std::string::npos) ok = parse_usize(value.substr(c2 + 1), &passes) && passes <= 1024;
+            if (!ok) {
+                *err = "Lightmap must be <k>:<width>[x<height>][:<passes>] (the k-th mesh of the scene from 0, sizes from 1 to 16384, up to 1024 dilation passes)";
+                return false;
+            }
+            cfg.has_lightmap = true;
+            cfg.lightmap_op = uint32_t(k);
+            cfg.lightmap_width = uint32_t(w);
+            cfg.lightmap_height = uint32_t(h);
+            cfg.lightmap_passes = uint32_t(passes);
         }
         // unknown keys: ignored (config.rs:146)
     }
@@ -369,6 +389,12 @@ bool config_from_args(int argc, const char* const* argv, Config* out, std::strin
                                  !cfg.sh_probes.empty() || cfg.pipeline == RT_PIPELINE_MEGAKERNEL)) {
         *err = "--nearest queries points on one GPU instead of rendering the frame: it cannot be combined with --gpus > 1, "
                "--progressive, --noise-threshold, --pick, --ao, --probe, --irradiance, --sh-probe or --pipeline=mega";
+        return false;
+    }
+    if (cfg.has_lightmap && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.has_probe || cfg.irradiance ||
+                             !cfg.sh_probes.empty() || !cfg.nearest.empty() || cfg.pipeline == RT_PIPELINE_MEGAKERNEL)) {
+        *err = "--lightmap bakes a lightmap on one GPU with the wavefront scheduler instead of the frame: it cannot be combined with --gpus > 1, "
+               "--progressive, --noise-threshold, --pick, --ao, --probe, --irradiance, --sh-probe, --nearest or --pipeline=mega";
         return false;
     }
     if (cfg.has_probe && (cfg.gpus > 1 || cfg.progressive || adaptive || !cfg.pick.empty() || cfg.ao_samples || cfg.light_groups || cfg.denoise ||

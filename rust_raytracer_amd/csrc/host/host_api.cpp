@@ -118,6 +118,13 @@ uint32_t rth_nearest_points(const RtHost* host, double* points_out, uint32_t cap
             for (int a = 0; a < 3; a++) points_out[3 * size_t(i) + a] = p[3 * size_t(i) + a];
     return n;
 }
+uint32_t rth_lightmap(const RtHost* host, uint32_t* op_out, uint32_t* height_out, uint32_t* passes_out) {
+    if (!host->config.has_lightmap) return 0;
+    if (op_out) *op_out = host->config.lightmap_op;
+    if (height_out) *height_out = host->config.lightmap_height;
+    if (passes_out) *passes_out = host->config.lightmap_passes;
+    return host->config.lightmap_width;
+}
 uint32_t rth_probe(const RtHost* host, double position_out[3]) {
     if (!host->config.has_probe) return 0;
     if (position_out)

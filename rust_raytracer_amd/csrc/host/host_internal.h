@@ -56,6 +56,9 @@ struct Config {
     uint32_t probe_width = 512;                       // height = width / 2
     std::vector<double> nearest;                      // --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]: 3 doubles per point, queried instead of rendering
     std::vector<double> sh_probes;                    // --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]: 3 doubles per probe, baked instead of rendering
+    bool has_lightmap = false;                        // --lightmap=<k>:<width>[x<height>][:<passes>]: the irradiance map of the k-th mesh op instead of the frame
+    uint32_t lightmap_op = 0, lightmap_width = 0, lightmap_height = 0;
+    uint32_t lightmap_passes = 2;                     // dilation passes
 };
 bool config_from_args(int argc, const char* const* argv, Config* out, std::string* err);  // config.rs:62-176
 

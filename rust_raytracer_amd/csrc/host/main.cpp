@@ -9,7 +9,10 @@
 //   --noise-threshold=<x>  --adaptive-min=<k>  --adaptive-check=<m>  --adaptive-radius=<r>
 //   --light-groups[=<max>]  --light-mix=<w0>,<w1>,...  --sequence=<scene1>[,<scene2>...]  --pick=<x>,<y>[:<x>,<y>...]
 //   --ao=<samples>[:<max_distance>]  --probe=<x>,<y>,<z>[:<width>]  --irradiance  --sh-probe=<x>,<y>,<z>[:<x>,<y>,<z>...]
-//   --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]
+//   --nearest=<x>,<y>,<z>[:<x>,<y>,<z>...]  --lightmap=<k>:<width>[x<height>][:<passes>]
+// --lightmap=<k>:<width>[x<height>][:<passes>] renders no frame: the irradiance lightmap of the k-th mesh op of the program over
+// the mesh's own UVs (rt_bake_lightmap: rasterised, baked and dilated on the device) with the run's -s, -t, depth, bias, seed
+// and precision, written to out_lightmap.png through the output stage of out.png; row 0 of the file is v near 0.
 // --sh-probe=<x>,<y>,<z>[:...] renders nothing: an SH radiance probe is baked at each named position (rt_bake_probes) with the
 // run's -s, -t, depth, bias, seed and precision and its nine RGB coefficients are printed, one line per coefficient.
 // --irradiance also writes out_irradiance.png: the --pick ray of every pixel is cast on the device (rt_trace_rays_device) and the
@@ -284,6 +287,49 @@ static int nearest_points(RtHost* host) {
     return 0;
 }
 
+// --lightmap: the irradiance map of the k-th mesh op over its own UVs to out_lightmap.png; returns the process exit status.
+static int bake_lightmap(RtHost* host, const std::function<double()>& since) {
+    uint32_t k = 0, H = 0, passes = 0;
+    const uint32_t W = rth_lightmap(host, &k, &H, &passes);
+    const RtSceneDesc* desc = rth_scene(host);
+    uint32_t n_ops = 0;
+    if (rt_scene_op_nodes(desc, nullptr, 0, &n_ops) != RT_OK) return fail(rt_last_error());
+    std::vector<int32_t> op_node(n_ops);
+    if (rt_scene_op_nodes(desc, op_node.data(), n_ops, &n_ops) != RT_OK) return fail(rt_last_error());
+    // the k-th op that came from a mesh node, and which of that node's ops it is
+    int32_t node = -1;
+    uint32_t instance = 0, seen = 0;
+    for (uint32_t pc = 0; pc < n_ops && node < 0; pc++) {
+        const int32_t n = op_node[pc];
+        if (n < 0 || uint32_t(n) >= desc->n_nodes || desc->nodes[n].type != RT_NODE_MESH) continue;
+        if (seen++ != k) continue;
+        node = n;
+        for (uint32_t q = 0; q < pc; q++)
+            if (op_node[q] == n) instance++;
+    }
+    if (node < 0) return fail(("--lightmap: the scene has " + std::to_string(seen) + " mesh op(s), there is no mesh " + std::to_string(k)).c_str());
+    RtRenderParams p = *rth_params(host);  // S, T, depth, background, bias, seed, precision of the run; a bake has one scheduler and no partition
+    p.pipeline = RT_PIPELINE_AUTO;
+    p.collect_stats = 0;
+    p.band_rows = p.n_parts = p.part = 0;
+    RtScene* scene = nullptr;
+    if (rt_scene_create(desc, 0, &scene) != RT_OK) return fail(rt_last_error());
+    std::unique_ptr<RtScene, void (*)(RtScene*)> scene_guard(scene, rt_scene_destroy);
+    const size_t n = size_t(W) * H;
+    std::vector<double> rgba(4 * n);
+    std::vector<uint8_t> coverage(n);
+    if (rt_bake_lightmap(scene, uint32_t(node), instance, W, H, RT_LIGHTMAP_IRRADIANCE, &p, nullptr, int32_t(passes), rgba.data(), coverage.data()) != RT_OK)
+        return fail(rt_last_error());
+    RtLightmapStats st{};
+    rt_lightmap_stats(scene, &st);
+    std::printf("Lightmap of mesh %u (node %d): %ux%u texels, %llu covered, %u paths each, %u dilation passes; rasterised in %.3f ms\n", k, node, W, H,
+                (unsigned long long)st.covered_texels, p.sqrt_spt * p.sqrt_spt * p.thread_count, passes, st.bin_ms + st.raster_ms);
+    std::printf("Done: %s. Writing output to file...\n", fmt_duration(since()).c_str());
+    if (rth_save_png("out_lightmap.png", rgba.data(), W, H) != RT_OK) return fail(rth_last_error());
+    std::printf("Done! Took %s. Goodbye :)\n", fmt_duration(since()).c_str());
+    return 0;
+}
+
 // --probe: the panorama at the named point to out_probe.png; returns the process exit status.
 static int render_probe(RtHost* host, const std::function<double()>& since) {
     double position[3];
@@ -430,6 +476,10 @@ int main(int argc, char** argv) {
     }
     if (rth_nearest_points(host, nullptr, 0) != 0 && !sequence.empty())
         return fail("--nearest queries points instead of rendering the frame: it cannot be combined with --sequence");
+    if (rth_lightmap(host, nullptr, nullptr, nullptr) != 0) {  // refused BEFORE a device is touched
+        if (!sequence.empty()) return fail("--lightmap bakes a lightmap instead of the frame: it cannot be combined with --sequence");
+        if (params->max_depth == 0) return fail("--lightmap needs a depth of at least 1");
+    }
     uint32_t gpus = rth_gpus(host);
     int available = rt_device_count();
     if (available < 1) {
@@ -448,6 +498,11 @@ int main(int argc, char** argv) {
     }
     if (rth_nearest_points(host, nullptr, 0) != 0) {
         const int rc = nearest_points(host);
+        rth_destroy(host);
+        return rc;
+    }
+    if (rth_lightmap(host, nullptr, nullptr, nullptr) != 0) {
+        const int rc = bake_lightmap(host, since);
         rth_destroy(host);
         return rc;
     }

@@ -227,10 +227,79 @@ static int group_export_host(const CompiledScene& cs, const GroupExportOut& o) {
         for (size_t j = 0; j < cs.group_guards.size() && j < o.guard_capacity; j++) o.guards[j] = cs.group_guards[j];
     return RT_OK;
 }
+
+int lightmap_select(const RtSceneDesc& d, const CompiledScene& cs, uint32_t node, uint32_t instance, uint32_t width, uint32_t height,
+                    const char* who, LmMeshRef* out) {
+    const std::string w = std::string(who) + ": ";
+    if (width == 0 || width > kLmMaxDim) return set_err(RT_E_INVALID, w + "width must be in 1 .. 16384");
+    if (height == 0 || height > kLmMaxDim) return set_err(RT_E_INVALID, w + "height must be in 1 .. 16384");
+    if (node >= d.n_nodes) return set_err(RT_E_INVALID, w + "node " + std::to_string(node) + " is out of range");
+    const RtNode& n = d.nodes[node];
+    if (n.type != RT_NODE_MESH) return set_err(RT_E_INVALID, w + "node " + std::to_string(node) + " is not an RT_NODE_MESH");
+    const RtMesh& m = d.meshes[n.mesh];
+    if (!m.uvs || !m.tri_uv || m.n_uvs == 0) return set_err(RT_E_UNSUPPORTED, w + "meshes[" + std::to_string(n.mesh) + "] has no uvs / tri_uv: nothing to rasterise");
+    std::vector<int32_t> pcs;
+    int vol_depth = 0;
+    bool in_volume = false;
+    for (size_t pc = 0; pc < cs.ops.size(); pc++) {
+        const Op& op = cs.ops[pc];
+        if (op.type == OP_VOL_BEGIN) vol_depth++;
+        if (op.type == OP_VOL_END) vol_depth--;
+        if (op.type != OP_MESH || pc >= cs.op_node.size() || cs.op_node[pc] != int32_t(node)) continue;
+        if (vol_depth > 0) in_volume = true;
+        else pcs.push_back(int32_t(pc));
+    }
+    if (in_volume) return set_err(RT_E_UNSUPPORTED, w + "node " + std::to_string(node) + " is the boundary of a volume: it has no surface to bake");
+    if (instance >= pcs.size())
+        return set_err(RT_E_INVALID, w + "instance " + std::to_string(instance) + " is beyond the " + std::to_string(pcs.size()) + " op(s) of node " + std::to_string(node));
+    const Op& op = cs.ops[size_t(pcs[instance])];
+    const MeshInst& mi = cs.meshes[size_t(op.arg)];
+    *out = LmMeshRef{mi.tri_base, mi.n_tris, op.chain, mi.material, int32_t(node), (mi.flags & RT_MESH_FLAT_SHADING) ? 1u : 0u};
+    return RT_OK;
+}
 }  // namespace rt
 
 using namespace rt;
 extern "C" {
+
+// Lightmaps (include/rt_mi355.h): the rule of rt_lightmap.h, every triangle x every texel.
+int rt_lightmap_texels_desc(const RtSceneDesc* desc, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, RtRayHit* hits_out,
+                            uint32_t* counts_out) {
+    const char* who = "rt_lightmap_texels_desc";
+    if (!desc) return set_err(RT_E_INVALID, std::string(who) + ": desc is NULL");
+    if (!hits_out) return set_err(RT_E_INVALID, std::string(who) + ": hits_out is NULL");
+    CompiledScene cs;
+    if (int st = compile_desc(desc, &cs, compile_options_from_env())) return st;
+    LmMeshRef mesh;
+    if (int st = lightmap_select(*desc, cs, node, instance, width, height, who, &mesh)) return st;
+    struct Tri { LmUV a, b, c; uint32_t slot; bool live; };
+    std::vector<Tri> tris(mesh.n_tris);  // in RtMesh.tri_pos order
+    for (uint32_t slot = 0; slot < mesh.n_tris; slot++) {
+        const TriAttr<double>& at = cs.attrs[mesh.tri_base + slot];
+        tris[cs.tri_order[mesh.tri_base + slot]] = Tri{lm_uv(at.uv0), lm_uv(at.uv1), lm_uv(at.uv2), slot, at.has_uv != 0};
+    }
+    for (uint32_t y = 0; y < height; y++)
+        for (uint32_t x = 0; x < width; x++) {
+            const LmUV p = {lm_centre(x, width), lm_centre(y, height)};
+            const size_t i = size_t(y) * width + x;
+            uint32_t count = 0;
+            RtRayHit rec = lm_miss_record();
+            for (uint32_t t = 0; t < mesh.n_tris; t++) {
+                const Tri& tr = tris[t];
+                double area, wb, wc;
+                if (!tr.live || !lm_covers(tr.a, tr.b, tr.c, p, &area, &wb, &wc)) continue;
+                if (count++ == 0) {
+                    const size_t s = size_t(mesh.tri_base) + tr.slot;
+                    rec = lm_record(cs.tris[s], cs.attrs[s], mesh.flat != 0u, area, wb, wc, cs.chain_offsets.data(), cs.chain_items.data(), cs.xforms.data(),
+                                    mesh.chain, mesh.material, mesh.node, int32_t(t));
+                }
+            }
+            hits_out[i] = rec;
+            if (counts_out) counts_out[i] = count;
+        }
+    return RT_OK;
+}
+
 
 const char* rt_last_error(void) { return rt::g_err.c_str(); }
 

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "rt_error.h"
+#include "rt_lightmap.h"
 #include "rt_tables.h"
 
 namespace rt {
@@ -90,6 +91,12 @@ struct UpdatePlan {
     uint32_t n_tris_moved = 0;
 };
 int plan_scene_update(const HeldDesc& held, const CompiledScene& compiled, const RtSceneDesc* desc, UpdatePlan* out);
+
+// Lightmaps (rt_lightmap.h): the argument checks every rasterising entry point shares, host only, and the mesh op that
+// (node, instance) names: the instance-th OP_MESH of the compiled program that came from `node`.  RT_OK, or the refusal of
+// include/rt_mi355.h with a message that starts with `who` and names the field.
+int lightmap_select(const RtSceneDesc& d, const CompiledScene& cs, uint32_t node, uint32_t instance, uint32_t width, uint32_t height,
+                    const char* who, LmMeshRef* out);
 
 // Child k's box of a quantised 4-wide node (BvhNode4q), decoded in f32 as the kernels do: lo xyz, hi xyz.
 inline void decode_qbox(const BvhNode4q& n, int k, float* out) {
