@@ -1,9 +1,11 @@
-// rt_bake.h — launcher of the ambient-occlusion bake (rt_bake.hip), called by the C ABI in rt_kernels.hip.
+// rt_bake.h — launcher of the ambient-occlusion bake, called by the host side of the bake (both in rt_bake.hip), and the
+// parameter rules that rt_bake_lightmap (rt_lightmap.hip) checks too.
 // Definition of the result: include/rt_mi355.h (rt_bake_visibility), DESIGN.md §15.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <string>
 
 #include "../../include/rt_mi355.h"
 #include "rt_scene.h"
@@ -28,5 +30,8 @@ struct BakePoints {
 template <typename R>
 hipError_t bake_visibility_launch(const SceneView<R>& sc, const BakePoints& pts, uint32_t samples, uint64_t seed, double bias,
                                   double max_distance, int stack_levels, uint32_t cones_on, RtBakeResult* d_out, hipStream_t stream);
+
+// The rules of samples, bias and max_distance; prefix: what the message starts with, "<entry point>: ".
+int bake_params_check(const RtBakeParams& bp, const std::string& prefix);
 
 }  // namespace rt

@@ -1,14 +1,19 @@
 // rt_bake.hip — ambient occlusion at surface points (include/rt_mi355.h: rt_bake_visibility).  A translation
 // unit of its own: neither the render kernels nor the query kernels change.  One wave bakes one point: each lane draws its
 // sample's direction in registers, walks the scene with segment_occluded (rt_query.h, the walk of k_rq_occluded) and the wave
-// reduces; no ray is ever written to memory.
+// reduces; no ray is ever written to memory.  The kernel, its launcher, the host side (chunk loop) and the entry points.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <limits>
+#include <string>
+#include <vector>
 
 #include "rt_bake.h"
 #include "rt_device.h"
 #include "rt_query.h"
+#include "rt_scene_host.h"
 
 namespace rt {
 
@@ -99,4 +104,95 @@ template hipError_t bake_visibility_launch<double>(const SceneView<double>&, con
 template hipError_t bake_visibility_launch<float>(const SceneView<float>&, const BakePoints&, uint32_t, uint64_t, double, double, int,
                                                   uint32_t, RtBakeResult*, hipStream_t);
 
+// ---------------------------------------------------------------------------------------------
+// Host side: the bake workspace of a scene (RtScene::Bake, rt_scene_host.h), the chunk loop and the entry points
+// ---------------------------------------------------------------------------------------------
+// points per launch; the default is a guess, not a measurement
+static uint32_t bake_chunk() { return std::min<uint32_t>(1u << 26, std::max<uint32_t>(1u, env_u32("RT_BAKE_CHUNK", 1u << 20))); }
+
+int bake_params_check(const RtBakeParams& bp, const std::string& prefix) {
+    if (bp.samples < 1 || bp.samples > 4096) return set_err(RT_E_INVALID, prefix + "samples must be in 1 .. 4096");
+    if (!(bp.bias >= 0.0)) return set_err(RT_E_INVALID, prefix + "bias must be >= 0");
+    if (!(bp.max_distance > bp.bias)) return set_err(RT_E_INVALID, prefix + "max_distance must be greater than bias");
+    return RT_OK;
+}
+
+// n points in chunks.  hits: the points are RtRayHit records on the device (positions = the records, normals unused);
+// host: positions / normals / out are host arrays, staged chunk by chunk.
+template <typename R>
+int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
+               const RtBakeParams& bp, RtBakeResult* out, bool host, hipStream_t stream) {
+    RtScene::Bake& b = s->bake;
+    const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
+    if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the bake kernel's LDS traversal stack");
+    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    ChunkTimes t;
+    auto launch = [&](uint64_t off, uint32_t m, const void* const* d_in, void* d_out) -> int {
+        BakePoints pts{};
+        pts.n = m;
+        pts.first = off;
+        if (hits) {
+            const HitPoints h = hit_points(hits + off);
+            pts.pos = h.pos;
+            pts.nrm = h.nrm;
+            pts.flags = h.flags;
+            pts.pos_stride = pts.nrm_stride = pts.flags_stride = h.stride;
+        } else {
+            pts.pos = static_cast<const unsigned char*>(d_in[0]);
+            pts.nrm = static_cast<const unsigned char*>(d_in[1]);
+            pts.pos_stride = pts.nrm_stride = 24u;
+        }
+        HIP_TRY(bake_visibility_launch<R>(ds.view, pts, bp.samples, bp.seed, bp.bias, bp.max_distance, levels, cones_on, static_cast<RtBakeResult*>(d_out), stream));
+        return RT_OK;
+    };
+    const std::vector<ChunkArray> in = hits ? std::vector<ChunkArray>{} : std::vector<ChunkArray>{{positions, 24}, {normals, 24}};
+    if (int st = run_chunks(b.stage, n, bake_chunk(), host, in, out, sizeof(RtBakeResult), stream, launch, &t)) return st;
+    record_query_stats<R>(b.stats, t, n * bp.samples);
+    return RT_OK;
+}
+
 }  // namespace rt
+
+extern "C" {
+
+static int bake_impl(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
+                     const RtBakeParams* params, RtBakeResult* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    RtBakeParams bp{};
+    if (params) {
+        bp = *params;
+    } else {
+        bp.samples = 64;
+        bp.precision = RT_PRECISION_F64;
+        bp.bias = 0.001;
+        bp.max_distance = HUGE_VAL;
+    }
+    return ray_query_run(scene, bp.precision, who, [&](RtScene* s, auto& ds) -> int {
+        if (int st = bake_params_check(bp, std::string(who) + ": ")) return st;
+        if (n == 0) return RT_OK;
+        if (!out || (hits ? false : (!positions || !normals))) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+        return bake_typed(s, ds, n, positions, normals, hits, bp, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
+    });
+}
+
+int rt_bake_visibility(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtBakeParams* params,
+                       RtBakeResult* out) {
+    return bake_impl(scene, n, positions, normals, nullptr, params, out, true, nullptr, "rt_bake_visibility");
+}
+int rt_bake_visibility_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals,
+                              const RtBakeParams* params, RtBakeResult* d_out, void* stream) {
+    return bake_impl(scene, n, d_positions, d_normals, nullptr, params, d_out, false, stream, "rt_bake_visibility_device");
+}
+int rt_bake_visibility_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtBakeParams* params,
+                                   RtBakeResult* d_out, void* stream) {
+    using namespace rt;
+    if (n != 0 && !d_hits) return set_err(RT_E_INVALID, "rt_bake_visibility_hits_device: NULL array");
+    return bake_impl(scene, n, nullptr, nullptr, d_hits, params, d_out, false, stream, "rt_bake_visibility_hits_device");
+}
+int rt_bake_stats(const RtScene* scene, RtRayQueryStats* out) {
+    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_bake_stats: NULL argument");
+    *out = scene->bake.stats;
+    return RT_OK;
+}
+
+}  // extern "C"

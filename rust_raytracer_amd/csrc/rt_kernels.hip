@@ -1,6 +1,9 @@
-// rt_kernels.hip — render kernels, the wavefront / query / point / bake driver, and the entry points of the C ABI
-// (include/rt_mi355.h) that take a scene or a device, but for the progressive accumulator's (rt_accum.hip, a client of this
-// file through rt_render.h) and the denoiser's (rt_aov.hip); those that take a description alone are in rt_desc.cpp.
+// rt_kernels.hip — the megakernel, the wavefront driver and everything that names a wavefront kernel or builds the path pool
+// (build_pool, query_search_pass, the table modes), a scene's creation, update and destruction, and the entry points of the
+// C ABI (include/rt_mi355.h) of renders, light groups, AOVs and table modes.  Elsewhere: ray queries (rt_query.hip), point
+// queries (rt_point.hip), the ambient-occlusion bake (rt_bake.hip) and lightmaps (rt_lightmap.hip), host side and entry
+// points beside their kernels, on the RtScene of rt_scene_host.h; the progressive accumulator (rt_accum.hip, a client of
+// this file through rt_render.h); the denoiser (rt_aov.hip); what takes a description alone (rt_desc.cpp).
 // gfx950 only: 64-lane waves, per-lane traversal stack in LDS, HIP events on the launch stream.
 #include <hip/hip_runtime.h>
 
@@ -19,15 +22,13 @@
 #include <vector>
 
 #include "rt_aov.h"
-#include "rt_bake.h"
 #include "rt_compile.h"
 #include "rt_desc.h"
 #include "rt_device.h"
 #include "rt_owned.h"
-#include "rt_point.h"
-#include "rt_query.h"
 #include "rt_refit.h"
 #include "rt_render.h"
+#include "rt_scene_host.h"
 #include "rt_tables.h"
 #include "rt_wavefront.h"
 
@@ -224,205 +225,66 @@ __global__ void __launch_bounds__(256) k_shade_rays(SceneView<R> sc, ParamsView<
 }
 
 // ---------------------------------------------------------------------------------------------
-// Host side
+// Host side.  RtScene, its tables on the device and its workspaces: rt_scene_host.h.
 // ---------------------------------------------------------------------------------------------
-// Device copies of host tables; every table is a buffer of its own, so that rt_scene_update can move the mesh tables over.
-struct DeviceBuffers {
-    std::vector<DevBuf<char>> allocs;
-    uint64_t uploaded_bytes = 0;
-    // takes over an allocation of `from` (rt_scene_update: the mesh tables stay where they are)
-    void adopt(DeviceBuffers& from, const void* p) {
-        auto it = std::find_if(from.allocs.begin(), from.allocs.end(), [p](const DevBuf<char>& b) { return b.get() == p; });
-        if (it == from.allocs.end()) return;
-        allocs.push_back(std::move(*it));
-        from.allocs.erase(it);
-    }
-    // `bytes` of device memory that live as long as this object
-    template <typename T> int alloc(size_t bytes, T** out) {
-        allocs.emplace_back();
-        if (int st = allocs.back().reserve(bytes)) return st;
-        *out = reinterpret_cast<T*>(allocs.back().get());
-        return RT_OK;
-    }
-    template <typename T> int upload(const std::vector<T>& v, const T** out) {
-        *out = nullptr;
-        T* p = nullptr;
-        if (int st = alloc((v.empty() ? 1 : v.size()) * sizeof(T), &p)) return st;
-        if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        uploaded_bytes += v.size() * sizeof(T);
-        *out = p;
-        return RT_OK;
-    }
-};
-
-// Scene tables in arithmetic type R on the device.
 template <typename R>
-struct DeviceScene {
-    using Real = R;
-    DeviceBuffers buf;
-    SceneView<R> view{};
-
-    // The tables are derived on the host (rt_tables.cpp); this uploads them, one buffer each.
-    // keep != NULL (rt_scene_update): the mesh tables (BVH nodes of every format, triangle records, attributes) are not
-    // derived and uploaded but stay the arrays of `keep`, which the refit kernels rewrite; take_mesh_tables() moves their
-    // ownership over once the update is certain.
-    int build(const CompiledScene& cs, const DeviceScene<R>* keep = nullptr) {
-        MeshTables<R> m;
-        SceneTables<R> t;
-        std::string err;
-        int st;
-        if (!keep && (st = derive_mesh_tables(cs, &m, &err)) != RT_OK) return set_err(st, err);
-        if ((st = derive_scene_tables(cs, &t, &err)) != RT_OK) return set_err(st, err);
-        view = t.view;  // the scalars and the blobs' layouts; then every table into a buffer of its own
-        if ((st = buf.upload(cs.ops, &view.ops)) != RT_OK) return st;
-        if ((st = buf.upload(t.bounds, &view.bounds)) != RT_OK) return st;
-        if ((st = buf.upload(cs.chain_offsets, &view.chain_offsets)) != RT_OK) return st;
-        if ((st = buf.upload(cs.chain_items, &view.chain_items)) != RT_OK) return st;
-        if ((st = buf.upload(t.xforms, &view.xforms)) != RT_OK) return st;
-        if ((st = buf.upload(t.spheres, &view.spheres)) != RT_OK) return st;
-        if ((st = buf.upload(t.planes, &view.planes)) != RT_OK) return st;
-        if ((st = buf.upload(t.suns, &view.suns)) != RT_OK) return st;
-        if ((st = buf.upload(cs.meshes, &view.meshes)) != RT_OK) return st;
-        if ((st = buf.upload(t.volumes, &view.volumes)) != RT_OK) return st;
-        if (!keep) {
-            if ((st = buf.upload(m.nodes, &view.nodes)) != RT_OK) return st;
-            if ((st = buf.upload(m.nodes4, &view.nodes4)) != RT_OK) return st;
-            if ((st = buf.upload(m.nodes4qc, &view.nodes4q)) != RT_OK) return st;
-            if ((st = buf.upload(m.tris, &view.tris)) != RT_OK) return st;
-            if ((st = buf.upload(m.attrs, &view.attrs)) != RT_OK) return st;
-        } else {
-            view.nodes = keep->view.nodes; view.nodes4 = keep->view.nodes4; view.nodes4q = keep->view.nodes4q;
-            view.tris = keep->view.tris; view.attrs = keep->view.attrs;
-        }
-        if ((st = buf.upload(t.mesh_bounds, &view.mesh_bounds)) != RT_OK) return st;
-        if ((st = buf.upload(cs.mesh_ops, &view.mesh_ops)) != RT_OK) return st;
-        if ((st = buf.upload(t.mesh_op_recs, &view.mesh_op_recs)) != RT_OK) return st;
-        if ((st = buf.upload(t.groups, &view.groups)) != RT_OK) return st;
-        if ((st = buf.upload(t.group_nodes, &view.group_nodes)) != RT_OK) return st;
-        if ((st = buf.upload(cs.group_prims, &view.group_prims)) != RT_OK) return st;
-        if ((st = buf.upload(cs.group_guards, &view.group_guards)) != RT_OK) return st;
-        if ((st = buf.upload(cs.materials, &view.materials)) != RT_OK) return st;
-        if ((st = buf.upload(t.material_params, &view.material_params)) != RT_OK) return st;
-        if ((st = buf.upload(t.textures, &view.textures)) != RT_OK) return st;
-        if ((st = buf.upload(cs.texels, &view.texels)) != RT_OK) return st;
-        if ((st = buf.upload(t.perlin_vec, &view.perlin_vec)) != RT_OK) return st;
-        if ((st = buf.upload(cs.perlin_perm, &view.perlin_perm)) != RT_OK) return st;
-        if ((st = buf.upload(cs.lights, &view.lights)) != RT_OK) return st;
-        if ((st = buf.upload(t.blob_prims, &view.small_blob)) != RT_OK) return st;
-        if ((st = buf.upload(t.blob_shade, &view.small_blob_shade)) != RT_OK) return st;
-        if (const char* e = std::getenv("RT_ZERO_WEIGHT_STOP")) view.stop_on_zero_weight = std::atoi(e) != 0;  // experiments
-        // The uploads above went through the null stream (small pageable copies may return once
-        // staged); the render kernels run on a NON-BLOCKING stream that is not ordered against it.
-        HIP_TRY(hipDeviceSynchronize());
-        return RT_OK;
+int DeviceScene<R>::build(const CompiledScene& cs, const DeviceScene<R>* keep) {
+    MeshTables<R> m;
+    SceneTables<R> t;
+    std::string err;
+    int st;
+    if (!keep && (st = derive_mesh_tables(cs, &m, &err)) != RT_OK) return set_err(st, err);
+    if ((st = derive_scene_tables(cs, &t, &err)) != RT_OK) return set_err(st, err);
+    view = t.view;  // the scalars and the blobs' layouts; then every table into a buffer of its own
+    if ((st = buf.upload(cs.ops, &view.ops)) != RT_OK) return st;
+    if ((st = buf.upload(t.bounds, &view.bounds)) != RT_OK) return st;
+    if ((st = buf.upload(cs.chain_offsets, &view.chain_offsets)) != RT_OK) return st;
+    if ((st = buf.upload(cs.chain_items, &view.chain_items)) != RT_OK) return st;
+    if ((st = buf.upload(t.xforms, &view.xforms)) != RT_OK) return st;
+    if ((st = buf.upload(t.spheres, &view.spheres)) != RT_OK) return st;
+    if ((st = buf.upload(t.planes, &view.planes)) != RT_OK) return st;
+    if ((st = buf.upload(t.suns, &view.suns)) != RT_OK) return st;
+    if ((st = buf.upload(cs.meshes, &view.meshes)) != RT_OK) return st;
+    if ((st = buf.upload(t.volumes, &view.volumes)) != RT_OK) return st;
+    if (!keep) {
+        if ((st = buf.upload(m.nodes, &view.nodes)) != RT_OK) return st;
+        if ((st = buf.upload(m.nodes4, &view.nodes4)) != RT_OK) return st;
+        if ((st = buf.upload(m.nodes4qc, &view.nodes4q)) != RT_OK) return st;
+        if ((st = buf.upload(m.tris, &view.tris)) != RT_OK) return st;
+        if ((st = buf.upload(m.attrs, &view.attrs)) != RT_OK) return st;
+    } else {
+        view.nodes = keep->view.nodes; view.nodes4 = keep->view.nodes4; view.nodes4q = keep->view.nodes4q;
+        view.tris = keep->view.tris; view.attrs = keep->view.attrs;
     }
-    void take_mesh_tables(DeviceScene<R>& from) {
-        for (const void* p : {(const void*)view.nodes, (const void*)view.nodes4, (const void*)view.nodes4q, (const void*)view.tris, (const void*)view.attrs})
-            buf.adopt(from.buf, p);
-    }
-};
-
-// The arrays of a WfPool<R> and the queues over its slots (build_pool).  A render works on a pair of them (the second one,
-// 3/4 of the slots, is the destination of the first tail compaction, after which the two take turns), a ray query on the
-// first of a pair; the arithmetic type a workspace's pools were built for is the alternative its variant holds.
+    if ((st = buf.upload(t.mesh_bounds, &view.mesh_bounds)) != RT_OK) return st;
+    if ((st = buf.upload(cs.mesh_ops, &view.mesh_ops)) != RT_OK) return st;
+    if ((st = buf.upload(t.mesh_op_recs, &view.mesh_op_recs)) != RT_OK) return st;
+    if ((st = buf.upload(t.groups, &view.groups)) != RT_OK) return st;
+    if ((st = buf.upload(t.group_nodes, &view.group_nodes)) != RT_OK) return st;
+    if ((st = buf.upload(cs.group_prims, &view.group_prims)) != RT_OK) return st;
+    if ((st = buf.upload(cs.group_guards, &view.group_guards)) != RT_OK) return st;
+    if ((st = buf.upload(cs.materials, &view.materials)) != RT_OK) return st;
+    if ((st = buf.upload(t.material_params, &view.material_params)) != RT_OK) return st;
+    if ((st = buf.upload(t.textures, &view.textures)) != RT_OK) return st;
+    if ((st = buf.upload(cs.texels, &view.texels)) != RT_OK) return st;
+    if ((st = buf.upload(t.perlin_vec, &view.perlin_vec)) != RT_OK) return st;
+    if ((st = buf.upload(cs.perlin_perm, &view.perlin_perm)) != RT_OK) return st;
+    if ((st = buf.upload(cs.lights, &view.lights)) != RT_OK) return st;
+    if ((st = buf.upload(t.blob_prims, &view.small_blob)) != RT_OK) return st;
+    if ((st = buf.upload(t.blob_shade, &view.small_blob_shade)) != RT_OK) return st;
+    if (const char* e = std::getenv("RT_ZERO_WEIGHT_STOP")) view.stop_on_zero_weight = std::atoi(e) != 0;  // experiments
+    // The uploads above went through the null stream (small pageable copies may return once
+    // staged); the render kernels run on a NON-BLOCKING stream that is not ordered against it.
+    HIP_TRY(hipDeviceSynchronize());
+    return RT_OK;
+}
 template <typename R>
-struct PathPool {
-    WfPool<R> view{};                             // array bases and capacity, as the kernels take them
-    WfPool<R>* dev = nullptr;                     // the same descriptor in device memory (k_wf_shade re-reads the array bases from it)
-    uint32_t* queue[2] = {nullptr, nullptr};
-    uint32_t* mesh_queue = nullptr;
-    std::vector<DevBuf<char>> owned;              // what all of the above point at
-};
-template <typename R> using PoolPair = std::array<PathPool<R>, 2>;
-using AnyPools = std::variant<std::monostate, PoolPair<float>, PoolPair<double>>;
-
-// What run_chunks keeps between calls: the host variants' staging buffer (inputs and results of one chunk; grows only) and
-// the pair of events that times a chunk.
-struct ChunkStage {
-    DevBuf<char> staging;
-    Event ev0, ev1;
-};
-
-}  // namespace rt
-
-struct RtScene {
-    int device = -1;  // set once rt_scene_create has chosen it; nothing is allocated before
-    rt::CompiledScene compiled;
-    // Both precisions are materialised lazily on first use (with_tables).
-    std::unique_ptr<rt::DeviceScene<double>> f64;
-    std::unique_ptr<rt::DeviceScene<float>> f32;
-    rt::Stream stream;
-    rt::Event ev0, ev1;
-    rt::DevBuf<rt::DeviceCounters> d_counters;
-    RtRenderStats stats{};
-    int32_t* tail_flag = nullptr;  // rt_scene_set_tail_flag: set to 1 when a render stops filling the GPU (frame pipelining)
-    uint64_t content_digest = 0;   // of everything the description points at (rt::scene_digest): checkpoints name their scene by it
-    // rt_scene_update: the description the scene holds, a counter of its updates (accumulators belong to one generation) and
-    // the device-side refit state per distinct mesh (CompiledScene::mesh_geoms order; empty until a mesh is first moved)
-    rt::HeldDesc held;
-    uint64_t generation = 0;
-    std::vector<rt::RefitMesh> refit;
-    // wavefront pipeline resources (allocated on first use, reused between renders)
-    struct Wavefront {
-        rt::AnyPools pools;
-        rt::DevBuf<uint2> mesh_spill;      // k_wf_mesh: stack levels beyond the LDS part
-        rt::DevBuf<rt::WfCounters> d_ctr;
-        rt::PinnedBuf<rt::WfCounters> h_ctr;
-        rt::DevBuf<double> sample_L, acc;
-        // light-group renders (rt_render_light_groups): group byte per sample, running sums per (group, pixel), terminal table
-        rt::DevBuf<uint8_t> sample_G, lg_table;
-        rt::DevBuf<double> acc_g;
-        rt::Event ev_res[2];
-        std::vector<rt::Event> events;
-    } wf;
-    // ray queries (rt_trace_rays / rt_occluded): a workspace of their own, allocated by the first query, so that a query
-    // between two progressive passes never makes wf_ensure re-allocate the render's pool
-    struct Query {
-        rt::AnyPools pools;                // [0]: ray and hit-record arrays only (the search kernels read nothing else); grows only
-        rt::DevBuf<uint2> mesh_spill;
-        rt::DevBuf<rt::WfCounters> d_ctr;
-        rt::PinnedBuf<rt::WfCounters> h_ctr;
-        rt::DevBuf<int32_t> op_node;       // CompiledScene::op_node / ::tri_order of generation `tables_generation`
-        rt::DevBuf<uint32_t> tri_order;
-        uint64_t tables_generation = ~0ull;
-        rt::ChunkStage stage;
-        RtRayQueryStats stats{};
-    } rq;
-    // ambient-occlusion bakes (rt_bake_visibility): stats of their own (rt_ray_query_stats is not theirs to change)
-    struct Bake {
-        rt::ChunkStage stage;
-        RtRayQueryStats stats{};
-    } bake;
-    // renders along ray tables, irradiance and probe bakes (rt_render_rays, rt_bake_irradiance, rt_bake_probes): the host variants' staging buffer; the kernels run on the render's workspace (wf)
-    struct Rays {
-        rt::ChunkStage stage;
-    } rays;
-    // point queries (rt_closest_points): the per-chain scale table in the arithmetic type of `scale_precision`, as of generation
-    // `scale_generation`, and stats of their own; op_node / tri_order are the ray queries' tables (rq)
-    struct Points {
-        rt::DevBuf<char> chain_scale;
-        uint64_t scale_generation = ~0ull;
-        uint32_t scale_precision = 0;
-        rt::ChunkStage stage;
-        RtRayQueryStats stats{};
-    } points;
-    // lightmaps (rt_lightmap_texels, rt_bake_lightmap; kernels in rt_lightmap.hip): the bins of the rasteriser, the records and
-    // images of the stages between rasterisation and the caller's buffers, three events; op_node / tri_order are rq's
-    struct Lightmap {
-        rt::DevBuf<uint32_t> tile_count, tile_offset, tile_cursor, refs, counts;
-        rt::DevBuf<unsigned long long> totals;
-        rt::DevBuf<char> scan_temp;
-        rt::DevBuf<RtRayHit> hits;
-        rt::DevBuf<RtBakeResult> vis;
-        rt::DevBuf<double> rgba_a, rgba_b, rgba_o;
-        rt::DevBuf<uint8_t> cov_a, cov_b, cov_c;
-        rt::Event ev[3];
-        RtLightmapStats stats{};
-    } lm;
-    ~RtScene() { if (device >= 0) (void)hipSetDevice(device); }  // before the members go: the owners do not switch devices
-};
-
-namespace rt {
+void DeviceScene<R>::take_mesh_tables(DeviceScene<R>& from) {
+    for (const void* p : {(const void*)view.nodes, (const void*)view.nodes4, (const void*)view.nodes4q, (const void*)view.tris, (const void*)view.attrs})
+        buf.adopt(from.buf, p);
+}
+template struct DeviceScene<float>;
+template struct DeviceScene<double>;
 
 template <typename R> CameraView<R> make_camera_view(const RtCameraDesc& c, const RtRenderParams& p) {
     CameraView<R> v{};
@@ -521,11 +383,6 @@ int aov_typed(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, const RtR
 // Wavefront pipeline driver
 // ---------------------------------------------------------------------------------------------
 constexpr size_t kSlabsMinTriangles = 131072;  // RT_WF_SLABS unset: the f64 kernels run the slab step if the scene's largest mesh has at least this many triangles
-static uint32_t env_u32(const char* name, uint32_t dflt) {
-    const char* v = std::getenv(name);
-    if (!v || !*v) return dflt;
-    return uint32_t(std::strtoul(v, nullptr, 10));
-}
 
 // ---- Kernel selection.  Taking a kernel's address instantiates it, so each selector names exactly the variants the
 // library ships (tools/kernel_regs.py lists them) and a combination outside that set cannot be asked for.  Whoever needs a
@@ -762,6 +619,8 @@ int build_pool(PathPool<R>& pl, uint32_t capacity, bool full, int n_queues, cons
     if (st != RT_OK) pl = PathPool<R>{};
     return st;
 }
+template int build_pool<float>(PathPool<float>&, uint32_t, bool, int, const char*);  // rt_query.hip builds the query pool
+template int build_pool<double>(PathPool<double>&, uint32_t, bool, int, const char*);
 
 // The render's pools of exactly `capacity` slots in R, its counters and its timing events.
 template <typename R>
@@ -1290,41 +1149,8 @@ int render_wavefront(RtScene* s, DeviceScene<R>& ds, const RtCameraDesc& cam, co
 }
 
 // ---------------------------------------------------------------------------------------------
-// Ray queries (include/rt_mi355.h; kernels in rt_query.hip)
+// The search pass of a ray query (the query itself: rt_query.hip)
 // ---------------------------------------------------------------------------------------------
-static uint32_t rq_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(64u, env_u32("RT_RQ_CHUNK", 1u << 22))); }
-
-// Counters and (closest hit: `pool`) a pool of at least `capacity` slots in R.
-template <typename R>
-int rq_ensure(RtScene* s, uint32_t capacity, bool pool) {
-    RtScene::Query& q = s->rq;
-    if (int st = q.d_ctr.reserve(sizeof(WfCounters))) return st;
-    if (int st = q.h_ctr.reserve(sizeof(WfCounters))) return st;
-    const auto* have = std::get_if<PoolPair<R>>(&q.pools);
-    if (!pool || (have && (*have)[0].view.capacity >= capacity)) return RT_OK;
-    q.pools = std::monostate{};
-    PoolPair<R> pp;  // the arrays a query does not use stay NULL
-    if (int st = build_pool(pp[0], capacity, false, 1, "ray-query pool does not fit in device memory (RT_RQ_CHUNK sets its size)")) return st;
-    q.pools = std::move(pp);
-    return RT_OK;
-}
-
-// op -> node and leaf slot -> triangle tables of the scene as it stands (uploaded again after an rt_scene_update)
-static int rq_tables(RtScene* s, hipStream_t stream) {
-    RtScene::Query& q = s->rq;
-    if (q.tables_generation == s->generation && q.op_node) return RT_OK;
-    q.op_node.reset();
-    q.tri_order.reset();
-    const CompiledScene& cs = s->compiled;
-    if (int st = q.op_node.reserve(std::max<size_t>(1, cs.op_node.size()) * 4)) return st;
-    if (int st = q.tri_order.reserve(std::max<size_t>(1, cs.tri_order.size()) * 4)) return st;
-    if (!cs.op_node.empty()) HIP_TRY(hipMemcpyAsync(q.op_node, cs.op_node.data(), cs.op_node.size() * 4, hipMemcpyHostToDevice, stream));
-    if (!cs.tri_order.empty()) HIP_TRY(hipMemcpyAsync(q.tri_order, cs.tri_order.data(), cs.tri_order.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    q.tables_generation = s->generation;
-    return RT_OK;
-}
-
 // One pass of the scene's search kernels over slots 0 .. m-1 of the query pool: what render_wavefront launches at the head
 // of an iteration of a lean (no counters), volume-free render, from the same make_search_setup and through the same launch
 // helpers, with the query workspace's queues, counters and spill buffer.
@@ -1348,227 +1174,6 @@ int query_search_pass(RtScene* s, DeviceScene<R>& ds, const PathPool<R>& pl, uin
         launch_intersect(su, ds, pool, sq);
     }
     HIP_TRY(hipGetLastError());
-    return RT_OK;
-}
-
-// n items in chunks of at most `chunk`: launch(off, m, d_in, d_out) enqueues the kernels of the m items from `off` on.
-// `in` / out: the arrays and their bytes per item; an input array may be NULL.  host: they are host arrays and go through
-// the staging buffer, which is sized by the largest chunk and laid out inputs first, then the output (a NULL input keeps its
-// place); otherwise the kernels work on them where they are.  One synchronise per chunk; the events span the launches, not
-// the copies.
-struct ChunkArray { const void* p; size_t each; };
-struct ChunkTimes { double ms = 0.0; uint32_t n_chunks = 0; };
-template <typename F>
-int run_chunks(ChunkStage& cs, uint64_t n, uint32_t chunk, bool host, const std::vector<ChunkArray>& in, void* out, size_t out_each,
-               hipStream_t stream, F&& launch, ChunkTimes* times) {
-    const size_t cap = size_t(std::min<uint64_t>(n, chunk));
-    size_t each_all = out_each;
-    for (const ChunkArray& a : in) each_all += a.each;
-    if (host)
-        if (int st = cs.staging.reserve(cap * each_all)) return st;
-    if (int st = cs.ev0.ensure()) return st;
-    if (int st = cs.ev1.ensure()) return st;
-    std::vector<const void*> d_in(in.size());
-    for (uint64_t off = 0; off < n; off += chunk) {
-        const uint32_t m = uint32_t(std::min<uint64_t>(chunk, n - off));
-        char* const h_out = static_cast<char*>(out) + off * out_each;
-        size_t at = 0;  // in the staging buffer
-        for (size_t i = 0; i < in.size(); i++) {
-            const char* src = in[i].p ? static_cast<const char*>(in[i].p) + off * in[i].each : nullptr;
-            if (host && src) {
-                HIP_TRY(hipMemcpyAsync(cs.staging + at, src, size_t(m) * in[i].each, hipMemcpyHostToDevice, stream));
-                src = cs.staging + at;
-            }
-            d_in[i] = src;
-            at += cap * in[i].each;
-        }
-        char* const d_out = host ? cs.staging + at : h_out;
-        HIP_TRY(hipEventRecord(cs.ev0, stream));
-        if (int st = launch(off, m, d_in.data(), static_cast<void*>(d_out))) return st;
-        HIP_TRY(hipEventRecord(cs.ev1, stream));
-        if (host) HIP_TRY(hipMemcpyAsync(h_out, d_out, size_t(m) * out_each, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, cs.ev0, cs.ev1));
-        times->ms += ms;
-        times->n_chunks++;
-    }
-    return RT_OK;
-}
-
-template <typename R>
-static void record_query_stats(RtRayQueryStats& stats, const ChunkTimes& t, uint64_t rays) {
-    stats = RtRayQueryStats{};
-    stats.kernel_ms = t.ms;
-    stats.rays = rays;
-    stats.n_chunks = t.n_chunks;
-    stats.precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
-}
-
-// n rays in chunks: (host variant: through the staging buffer) k_rq_load -> search pass -> k_rq_resolve.
-template <typename R>
-int trace_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, RtRayHit* out, bool host,
-                     hipStream_t stream) {
-    RtScene::Query& q = s->rq;
-    const uint32_t chunk = rq_chunk();
-    if (int st = rq_ensure<R>(s, uint32_t(std::min<uint64_t>(n, chunk)), true)) return st;
-    if (int st = rq_tables(s, stream)) return st;
-    const PathPool<R>& pl = std::get<PoolPair<R>>(q.pools)[0];
-    const WfPool<R>& full = pl.view;
-    const RqPool<R> rp{full.ox, full.oy, full.oz, full.dx, full.dy, full.dz, full.ht, full.hu, full.hv, full.hpc, full.htri};
-    const RqTables tb{q.op_node, q.tri_order};
-    ChunkTimes t;
-    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
-        HIP_TRY(rq_load_launch<R>(rp, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), m, pl.queue[0], stream));
-        if (int st = query_search_pass<R>(s, ds, pl, m, stream)) return st;
-        HIP_TRY(rq_resolve_launch<R>(ds.view, rp, tb, m, static_cast<RtRayHit*>(d_out), stream));
-        return RT_OK;
-    };
-    if (int st = run_chunks(q.stage, n, chunk, host, {{origins, 24}, {dirs, 24}}, out, sizeof(RtRayHit), stream, launch, &t)) return st;
-    record_query_stats<R>(q.stats, t, n);
-    return RT_OK;
-}
-
-template <typename R>
-int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const double* t_min,
-                   const double* t_max, uint8_t* out, bool host, hipStream_t stream) {
-    RtScene::Query& q = s->rq;
-    const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
-    if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the occlusion kernel's LDS traversal stack");
-    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
-    const uint32_t chunk = rq_chunk();
-    if (int st = rq_ensure<R>(s, uint32_t(std::min<uint64_t>(n, chunk)), false)) return st;
-    ChunkTimes t;
-    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
-        HIP_TRY(rq_occluded_launch<R>(ds.view, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), static_cast<const double*>(d_in[2]),
-                                      static_cast<const double*>(d_in[3]), m, levels, cones_on, static_cast<uint8_t*>(d_out), stream));
-        return RT_OK;
-    };
-    if (int st = run_chunks(q.stage, n, chunk, host, {{origins, 24}, {dirs, 24}, {t_min, 8}, {t_max, 8}}, out, 1, stream, launch, &t)) return st;
-    record_query_stats<R>(q.stats, t, n);
-    return RT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Point queries (include/rt_mi355.h; kernel in rt_point.hip)
-// ---------------------------------------------------------------------------------------------
-// Host only, f64: scale[c] = s of the composed linear part L of chain c (object -> world, outermost transform first),
-// s^2 = tr(L^T L) / 3.  False, with the reason in `why`, if the chain over a sphere, plane or mesh op is not a similarity:
-// max |L^T L - s^2 I| <= 1e-9 s^2 is one.
-static bool pq_chain_scales(const CompiledScene& cs, std::vector<double>& scale, std::string& why) {
-    const size_t n_chains = cs.chain_offsets.empty() ? 0 : cs.chain_offsets.size() - 1;
-    scale.assign(std::max<size_t>(1, n_chains), 1.0);
-    std::vector<char> similar(scale.size(), 1);
-    for (size_t c = 0; c < n_chains; c++) {
-        double L[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        for (int32_t k = cs.chain_offsets[c]; k < cs.chain_offsets[c + 1]; k++) {
-            const double* m = cs.xforms[size_t(cs.chain_items[size_t(k)])].m;
-            double P[9];
-            for (int i = 0; i < 3; i++)
-                for (int j = 0; j < 3; j++) P[3 * i + j] = L[3 * i] * m[j] + L[3 * i + 1] * m[4 + j] + L[3 * i + 2] * m[8 + j];
-            std::copy(P, P + 9, L);
-        }
-        double G[9];  // L^T L
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) G[3 * i + j] = L[i] * L[j] + L[3 + i] * L[3 + j] + L[6 + i] * L[6 + j];
-        const double s2 = (G[0] + G[4] + G[8]) / 3.0;
-        double dev = 0.0;
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) dev = std::fmax(dev, std::fabs(G[3 * i + j] - (i == j ? s2 : 0.0)));
-        similar[c] = (s2 > 0.0 && std::isfinite(s2) && dev <= 1e-9 * s2) ? 1 : 0;
-        scale[c] = std::sqrt(s2);
-    }
-    for (size_t pc = 0; pc < cs.ops.size(); pc++) {
-        const Op& op = cs.ops[pc];
-        if ((op.type == OP_SPHERE || op.type == OP_PLANE || op.type == OP_MESH) && !similar[size_t(op.chain)]) {
-            why = "the transforms over node " + std::to_string(pc < cs.op_node.size() ? cs.op_node[pc] : -1) +
-                  " do not compose to a similarity (non-uniform scale or shear): object-space distances are not world distances";
-            return false;
-        }
-    }
-    return true;
-}
-
-// n points in chunks.  counts != NULL: the counting variant, `out` is then unused and the records go to a buffer of this call.
-template <typename R>
-int closest_points_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* points, const double* max_distance, RtPointHit* out,
-                         uint32_t* counts, const std::vector<double>& scale, int levels, bool host, hipStream_t stream) {
-    RtScene::Points& pw = s->points;
-    const uint32_t precision = sizeof(R) == 8 ? RT_PRECISION_F64 : RT_PRECISION_F32;
-    if (int st = rq_tables(s, stream)) return st;
-    if (!pw.chain_scale || pw.scale_generation != s->generation || pw.scale_precision != precision) {
-        std::vector<R> rounded(scale.begin(), scale.end());
-        if (int st = pw.chain_scale.reserve(rounded.size() * sizeof(R))) return st;
-        HIP_TRY(hipMemcpyAsync(pw.chain_scale, rounded.data(), rounded.size() * sizeof(R), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
-        pw.scale_generation = s->generation;
-        pw.scale_precision = precision;
-    }
-    const PqTables<R> tb{s->rq.op_node, s->rq.tri_order, reinterpret_cast<const R*>(pw.chain_scale.get())};
-    const uint32_t chunk = rq_chunk();
-    DevBuf<RtPointHit> records;  // counting variant only
-    if (counts)
-        if (int st = records.reserve(size_t(std::min<uint64_t>(n, chunk)) * sizeof(RtPointHit))) return st;
-    ChunkTimes t;
-    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
-        HIP_TRY(pq_closest_launch<R>(ds.view, tb, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), m, levels,
-                                     counts ? records.get() : static_cast<RtPointHit*>(d_out), counts ? static_cast<uint32_t*>(d_out) : nullptr, stream));
-        return RT_OK;
-    };
-    void* const dst = counts ? static_cast<void*>(counts) : static_cast<void*>(out);
-    if (int st = run_chunks(pw.stage, n, chunk, host, {{points, 24}, {max_distance, 8}}, dst, counts ? 8 : sizeof(RtPointHit), stream, launch, &t)) return st;
-    if (!counts) record_query_stats<R>(pw.stats, t, n);
-    return RT_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Ambient-occlusion bake (include/rt_mi355.h; kernel in rt_bake.hip)
-// ---------------------------------------------------------------------------------------------
-// points per launch; the default is a guess, not a measurement
-static uint32_t bake_chunk() { return std::min<uint32_t>(1u << 26, std::max<uint32_t>(1u, env_u32("RT_BAKE_CHUNK", 1u << 20))); }
-
-// RtRayHit records as strided points: where the first record's position, normal and flags are, and the bytes from one record to
-// the next.
-struct HitPoints {
-    const unsigned char *pos, *nrm, *flags;
-    uint32_t stride;
-};
-static HitPoints hit_points(const RtRayHit* hits) {
-    const unsigned char* base = reinterpret_cast<const unsigned char*>(hits);
-    return {base + offsetof(RtRayHit, pos), base + offsetof(RtRayHit, normal), base + offsetof(RtRayHit, flags), uint32_t(sizeof(RtRayHit))};
-}
-
-// n points in chunks.  hits: the points are RtRayHit records on the device (positions = the records, normals unused);
-// host: positions / normals / out are host arrays, staged chunk by chunk.
-template <typename R>
-int bake_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
-               const RtBakeParams& bp, RtBakeResult* out, bool host, hipStream_t stream) {
-    RtScene::Bake& b = s->bake;
-    const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
-    if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the bake kernel's LDS traversal stack");
-    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
-    ChunkTimes t;
-    auto launch = [&](uint64_t off, uint32_t m, const void* const* d_in, void* d_out) -> int {
-        BakePoints pts{};
-        pts.n = m;
-        pts.first = off;
-        if (hits) {
-            const HitPoints h = hit_points(hits + off);
-            pts.pos = h.pos;
-            pts.nrm = h.nrm;
-            pts.flags = h.flags;
-            pts.pos_stride = pts.nrm_stride = pts.flags_stride = h.stride;
-        } else {
-            pts.pos = static_cast<const unsigned char*>(d_in[0]);
-            pts.nrm = static_cast<const unsigned char*>(d_in[1]);
-            pts.pos_stride = pts.nrm_stride = 24u;
-        }
-        HIP_TRY(bake_visibility_launch<R>(ds.view, pts, bp.samples, bp.seed, bp.bias, bp.max_distance, levels, cones_on, static_cast<RtBakeResult*>(d_out), stream));
-        return RT_OK;
-    };
-    const std::vector<ChunkArray> in = hits ? std::vector<ChunkArray>{} : std::vector<ChunkArray>{{positions, 24}, {normals, 24}};
-    if (int st = run_chunks(b.stage, n, bake_chunk(), host, in, out, sizeof(RtBakeResult), stream, launch, &t)) return st;
-    record_query_stats<R>(b.stats, t, n * bp.samples);
     return RT_OK;
 }
 
@@ -1654,40 +1259,12 @@ static ProbeTablePass probe_table_pass(const RtRenderParams& p, uint64_t off, ui
     return pp;
 }
 
-// Makes sure the scene's tables in the arithmetic of `precision` are on the device (built on first use), then f(tables).
-template <typename F>
-int with_tables(RtScene* s, uint32_t precision, F&& f) {
-    auto go = [&](auto& slot) -> int {
-        if (!slot) {
-            auto ds = std::make_unique<typename std::decay_t<decltype(slot)>::element_type>();
-            if (int r = ds->build(s->compiled)) return r;
-            slot = std::move(ds);
-        }
-        return f(*slot);
-    };
-    return precision == RT_PRECISION_F32 ? go(s->f32) : go(s->f64);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Table modes: the entry points of ray tables, irradiance and probe bakes
 // ---------------------------------------------------------------------------------------------
-// One call of a table mode's entry point `who`.  a / b: the input arrays as the caller passed them (name NULL: the entry point
-// has no such array; each: bytes per entry), out_name / out_each: the same of the output; what / unit: "ray table" / "ray".
-struct TableArray {
-    const void* p;
-    const char* name;
-    size_t each;
-};
-struct TableCall {
-    const char* who;
-    TableArray a, b;
-    const char* out_name;
-    size_t out_each;
-    const char *what, *unit;
-};
-
-// The rules the table modes share, checked before the device is touched.
-static int table_render_check(const RtScene* scene, uint64_t n, const RtRenderParams* params, const void* out, const TableCall& c) {
+// The rules the table modes share, checked before the device is touched; a call's description (TableCall) is in
+// rt_scene_host.h, because rt_bake_lightmap runs these rules too.
+int table_render_check(const RtScene* scene, uint64_t n, const RtRenderParams* params, const void* out, const TableCall& c) {
     const std::string w = std::string(c.who) + ": ";
     if (!scene) return set_err(RT_E_INVALID, w + "scene is NULL");
     if (!params) return set_err(RT_E_INVALID, w + "params is NULL");
@@ -1728,18 +1305,6 @@ int table_call(const RtScene* scene, uint64_t n, const RtRenderParams* params, d
     }();
     if (scene && scene->tail_flag) __atomic_store_n(scene->tail_flag, 1, __ATOMIC_RELEASE);
     return r;
-}
-
-// Argument checks shared by the entry points, then run(scene, tables of `precision` on the device).
-template <typename F>
-static int ray_query_run(const RtScene* scene, uint32_t precision, const char* who, F&& run) {
-    if (!scene) return set_err(RT_E_INVALID, std::string(who) + ": NULL scene");
-    if (precision != RT_PRECISION_F64 && precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, std::string(who) + ": precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
-    if (!scene->compiled.volumes.empty())
-        return set_err(RT_E_UNSUPPORTED, std::string(who) + ": ray queries do not support scenes with volumes (a medium gives no deterministic surface)");
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    return with_tables(s, precision, [&](auto& ds) -> int { return run(s, ds); });
 }
 
 // A device buffer of `bytes` for the length of one call of a host variant: run(d) works on it, then (on success) `bytes_back`
@@ -2353,409 +1918,23 @@ int rt_sh_irradiance(int device, const double* sh, uint64_t n_probes, const uint
     return copy(rgba_out, d_out, b_out, hipMemcpyDeviceToHost);
 }
 
-// ---- Ray queries (rt_query.hip) -----------------------------------------------------------------------------------------
-static int trace_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* out,
-                           bool host, void* stream, const char* who) {
-    using namespace rt;
-    return ray_query_run(scene, precision, who, [&](RtScene* s, auto& ds) -> int {
-        if (n == 0) return RT_OK;
-        if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-        return trace_rays_typed(s, ds, n, origins, dirs, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
-    });
-}
-
-static int occluded_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
-                         uint32_t precision, uint8_t* out, bool host, void* stream, const char* who) {
-    using namespace rt;
-    return ray_query_run(scene, precision, who, [&](RtScene* s, auto& ds) -> int {
-        if (n == 0) return RT_OK;
-        if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-        return occluded_typed(s, ds, n, origins, dirs, t_min, t_max, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
-    });
-}
-
-int rt_trace_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* hits_out) {
-    return trace_rays_impl(scene, n, origins, dirs, precision, hits_out, true, nullptr, "rt_trace_rays");
-}
-int rt_trace_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, uint32_t precision,
-                         RtRayHit* d_hits_out, void* stream) {
-    return trace_rays_impl(scene, n, d_origins, d_dirs, precision, d_hits_out, false, stream, "rt_trace_rays_device");
-}
-int rt_occluded(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
-                uint32_t precision, uint8_t* out) {
-    return occluded_impl(scene, n, origins, dirs, t_min, t_max, precision, out, true, nullptr, "rt_occluded");
-}
-int rt_occluded_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const double* d_t_min,
-                       const double* d_t_max, uint32_t precision, uint8_t* d_out, void* stream) {
-    return occluded_impl(scene, n, d_origins, d_dirs, d_t_min, d_t_max, precision, d_out, false, stream, "rt_occluded_device");
-}
-int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out) {
-    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_ray_query_stats: NULL argument");
-    *out = scene->rq.stats;
-    return RT_OK;
-}
-
-// ---- Point queries (rt_point.hip) ----------------------------------------------------------------------------------------
-// Every refusal is decided here, on the host, before the tables of `precision` or any workspace exist.
-static int closest_points_impl(const RtScene* scene, uint64_t n, const double* points, const double* max_distance, uint32_t precision,
-                               RtPointHit* out, uint32_t* counts, bool host, void* stream, const char* who) {
-    using namespace rt;
-    if (!scene) return set_err(RT_E_INVALID, std::string(who) + ": NULL scene");
-    if (precision != RT_PRECISION_F64 && precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, std::string(who) + ": precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
-    const CompiledScene& cs = scene->compiled;
-    if (!cs.volumes.empty())
-        return set_err(RT_E_UNSUPPORTED, std::string(who) + ": point queries do not support scenes with volumes (a medium has no surface to be near)");
-    if (n == 0) return RT_OK;
-    if (!points || !(counts ? static_cast<const void*>(counts) : static_cast<const void*>(out))) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-    std::vector<double> scale;
-    std::string why;
-    if (!pq_chain_scales(cs, scale, why)) return set_err(RT_E_UNSUPPORTED, std::string(who) + ": " + why);
-    const int levels = cs.meshes.empty() ? 1 : int(cs.max_bvh4_stack) + 1;
-    if (levels > kPqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the point-query kernel's LDS traversal stack");
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    HIP_TRY(hipSetDevice(s->device));
-    return with_tables(s, precision, [&](auto& ds) -> int {
-        return closest_points_typed(s, ds, n, points, max_distance, out, counts, scale, levels, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
-    });
-}
-
-int rt_closest_points(const RtScene* scene, uint64_t n, const double* points, const double* max_distance, uint32_t precision, RtPointHit* out) {
-    return closest_points_impl(scene, n, points, max_distance, precision, out, nullptr, true, nullptr, "rt_closest_points");
-}
-int rt_closest_points_device(const RtScene* scene, uint64_t n, const double* d_points, const double* d_max_distance, uint32_t precision,
-                             RtPointHit* d_out, void* stream) {
-    return closest_points_impl(scene, n, d_points, d_max_distance, precision, d_out, nullptr, false, stream, "rt_closest_points_device");
-}
-int rt_debug_closest_points_counts(const RtScene* scene, uint64_t n, const double* points, const double* max_distance, uint32_t precision,
-                                   uint32_t* counts_out) {
-    return closest_points_impl(scene, n, points, max_distance, precision, nullptr, counts_out, true, nullptr, "rt_debug_closest_points_counts");
-}
-int rt_point_query_stats(const RtScene* scene, RtRayQueryStats* out) {
-    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_point_query_stats: NULL argument");
-    *out = scene->points.stats;
-    return RT_OK;
-}
-
-// ---- Ambient-occlusion bake (rt_bake.hip) -------------------------------------------------------------------------------
-static int bake_impl(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtRayHit* hits,
-                     const RtBakeParams* params, RtBakeResult* out, bool host, void* stream, const char* who) {
-    using namespace rt;
-    RtBakeParams bp{};
-    if (params) {
-        bp = *params;
-    } else {
-        bp.samples = 64;
-        bp.precision = RT_PRECISION_F64;
-        bp.bias = 0.001;
-        bp.max_distance = HUGE_VAL;
-    }
-    return ray_query_run(scene, bp.precision, who, [&](RtScene* s, auto& ds) -> int {
-        if (bp.samples < 1 || bp.samples > 4096) return set_err(RT_E_INVALID, std::string(who) + ": samples must be in 1 .. 4096");
-        if (!(bp.bias >= 0.0)) return set_err(RT_E_INVALID, std::string(who) + ": bias must be >= 0");
-        if (!(bp.max_distance > bp.bias)) return set_err(RT_E_INVALID, std::string(who) + ": max_distance must be greater than bias");
-        if (n == 0) return RT_OK;
-        if (!out || (hits ? false : (!positions || !normals))) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
-        return bake_typed(s, ds, n, positions, normals, hits, bp, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
-    });
-}
-
-int rt_bake_visibility(const RtScene* scene, uint64_t n, const double* positions, const double* normals, const RtBakeParams* params,
-                       RtBakeResult* out) {
-    return bake_impl(scene, n, positions, normals, nullptr, params, out, true, nullptr, "rt_bake_visibility");
-}
-int rt_bake_visibility_device(const RtScene* scene, uint64_t n, const double* d_positions, const double* d_normals,
-                              const RtBakeParams* params, RtBakeResult* d_out, void* stream) {
-    return bake_impl(scene, n, d_positions, d_normals, nullptr, params, d_out, false, stream, "rt_bake_visibility_device");
-}
-int rt_bake_visibility_hits_device(const RtScene* scene, uint64_t n, const RtRayHit* d_hits, const RtBakeParams* params,
-                                   RtBakeResult* d_out, void* stream) {
-    using namespace rt;
-    if (n != 0 && !d_hits) return set_err(RT_E_INVALID, "rt_bake_visibility_hits_device: NULL array");
-    return bake_impl(scene, n, nullptr, nullptr, d_hits, params, d_out, false, stream, "rt_bake_visibility_hits_device");
-}
-int rt_bake_stats(const RtScene* scene, RtRayQueryStats* out) {
-    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_bake_stats: NULL argument");
-    *out = scene->bake.stats;
-    return RT_OK;
-}
-
 int rt_get_stats(const RtScene* scene, RtRenderStats* out) {
     if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_get_stats: NULL argument");
     *out = scene->stats;
     return RT_OK;
 }
 
-// ---- Lightmaps (rt_lightmap.hip) -------------------------------------------------------------------------------------------
-// (triangle, tile) references a rasterisation may make: RT_LIGHTMAP_MAX_REFS, read at each call; the offsets are 32-bit
-static uint64_t lm_max_refs() {
-    uint64_t cap = 1ull << 28;
-    if (const char* e = std::getenv("RT_LIGHTMAP_MAX_REFS")) cap = std::strtoull(e, nullptr, 10);
-    return std::min<uint64_t>(cap, 1ull << 31);
-}
-
-// Rasterises `mesh` on `stream` into the buffers that outputs(&d_hits, &d_counts) names (d_counts may come back NULL); returns
-// after the kernels.  outputs() runs once the reference count has passed its cap: before that nothing is written or allocated
-// but the two totals and the events.
-extern "C++" {
-template <typename Outputs>
-static int lm_rasterise(RtScene* s, rt::DeviceScene<double>& ds, const rt::LmMeshRef& mesh, uint32_t w, uint32_t h, Outputs&& outputs,
-                        hipStream_t stream, const char* who) {
-    using namespace rt;
-    RtScene::Lightmap& L = s->lm;
-    if (int st = rq_tables(s, stream)) return st;
-    if (int st = L.totals.reserve(2 * sizeof(unsigned long long))) return st;
-    for (Event& e : L.ev)
-        if (int st = e.ensure()) return st;
-    const TriAttr<double>* attrs = ds.view.attrs;
-    HIP_TRY(lm_count_refs_launch(attrs, mesh, w, h, L.totals, stream));
-    unsigned long long tot[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(tot, L.totals, sizeof tot, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    const uint64_t cap = lm_max_refs();
-    if (tot[0] > cap)
-        return set_err(RT_E_UNSUPPORTED, std::string(who) + ": the map needs " + std::to_string(tot[0]) + " (triangle, tile) references, RT_LIGHTMAP_MAX_REFS allows " +
-                                             std::to_string(cap));
-    RtRayHit* d_hits = nullptr;
-    uint32_t* d_counts = nullptr;
-    if (int st = outputs(&d_hits, &d_counts)) return st;
-    const uint32_t n_tiles = ((w + kLmTile - 1u) / kLmTile) * ((h + kLmTile - 1u) / kLmTile);
-    size_t scan_bytes = 0;
-    HIP_TRY(lm_scan_temp_bytes(n_tiles + 1u, &scan_bytes));
-    if (int st = L.tile_count.reserve((size_t(n_tiles) + 1) * 4)) return st;
-    if (int st = L.tile_offset.reserve((size_t(n_tiles) + 1) * 4)) return st;
-    if (int st = L.tile_cursor.reserve(size_t(n_tiles) * 4)) return st;
-    if (int st = L.refs.reserve(std::max<size_t>(1, size_t(tot[0])) * 4, "the lightmap's tile references do not fit in device memory (RT_LIGHTMAP_MAX_REFS caps them)")) return st;
-    if (int st = L.scan_temp.reserve(std::max<size_t>(16, scan_bytes))) return st;
-    const LmWorkspace ws{L.tile_count, L.tile_offset, L.tile_cursor, L.refs, L.totals, L.scan_temp.get(), scan_bytes};
-    HIP_TRY(hipEventRecord(L.ev[0], stream));
-    HIP_TRY(lm_bin_launch(attrs, mesh, w, h, ws, stream));
-    HIP_TRY(hipEventRecord(L.ev[1], stream));
-    HIP_TRY(lm_raster_launch(ds.view, s->rq.tri_order, mesh, w, h, ws, d_hits, d_counts, stream));
-    HIP_TRY(hipEventRecord(L.ev[2], stream));
-    HIP_TRY(hipMemcpyAsync(tot, L.totals, sizeof tot, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    float bin_ms = 0.f, raster_ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&bin_ms, L.ev[0], L.ev[1]));
-    HIP_TRY(hipEventElapsedTime(&raster_ms, L.ev[1], L.ev[2]));
-    L.stats = RtLightmapStats{};
-    L.stats.bin_ms = bin_ms;
-    L.stats.raster_ms = raster_ms;
-    L.stats.texels = uint64_t(w) * h;
-    L.stats.covered_texels = tot[1];
-    L.stats.tile_refs = tot[0];
-    L.stats.width = w;
-    L.stats.height = h;
-    return RT_OK;
-}
-}
-
-// The scene's f64 tables (built as the first f64 query would), then run(tables).
-extern "C++" {
-template <typename F>
-static int lm_with_f64(RtScene* s, F&& run) {
-    using namespace rt;
-    HIP_TRY(hipSetDevice(s->device));
-    return with_tables(s, RT_PRECISION_F64, [&](auto& ds) -> int {
-        if constexpr (std::is_same_v<typename std::decay_t<decltype(ds)>::Real, double>) return run(ds);
-        else return set_err(RT_E_INVALID, "lightmaps are f64");
-    });
-}
-}
-
-static int lightmap_texels_impl(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t w, uint32_t h, RtRayHit* hits, uint32_t* counts, bool host,
-                                void* stream, const char* who) {
-    using namespace rt;
-    if (!scene) return set_err(RT_E_INVALID, std::string(who) + ": scene is NULL");
-    if (!hits) return set_err(RT_E_INVALID, std::string(who) + ": hits_out is NULL");
-    LmMeshRef mesh;
-    if (int st = lightmap_select(scene->held.d, scene->compiled, node, instance, w, h, who, &mesh)) return st;
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    const size_t n = size_t(w) * h;
-    return lm_with_f64(s, [&](DeviceScene<double>& ds) -> int {
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(s->stream);
-        RtScene::Lightmap& L = s->lm;
-        auto outputs = [&](RtRayHit** d_hits, uint32_t** d_counts) -> int {
-            if (!host) { *d_hits = hits; *d_counts = counts; return RT_OK; }
-            if (int r = L.hits.reserve(n * sizeof(RtRayHit))) return r;
-            if (counts)
-                if (int r = L.counts.reserve(n * 4)) return r;
-            *d_hits = L.hits;
-            *d_counts = counts ? L.counts.get() : nullptr;
-            return RT_OK;
-        };
-        if (int r = lm_rasterise(s, ds, mesh, w, h, outputs, st, who)) return r;
-        if (!host) return RT_OK;
-        HIP_TRY(hipMemcpy(hits, L.hits, n * sizeof(RtRayHit), hipMemcpyDeviceToHost));
-        if (counts) HIP_TRY(hipMemcpy(counts, L.counts, n * 4, hipMemcpyDeviceToHost));
-        return RT_OK;
-    });
-}
-
-int rt_lightmap_texels(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, RtRayHit* hits_out,
-                       uint32_t* counts_out_or_null) {
-    return lightmap_texels_impl(scene, node, instance, width, height, hits_out, counts_out_or_null, true, nullptr, "rt_lightmap_texels");
-}
-int rt_lightmap_texels_device(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, RtRayHit* d_hits_out,
-                              uint32_t* d_counts_out_or_null, void* stream) {
-    return lightmap_texels_impl(scene, node, instance, width, height, d_hits_out, d_counts_out_or_null, false, stream, "rt_lightmap_texels_device");
-}
-int rt_lightmap_stats(const RtScene* scene, RtLightmapStats* out) {
-    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_lightmap_stats: NULL argument");
-    *out = scene->lm.stats;
-    return RT_OK;
-}
-
-// `passes` dilation passes from (rgba, cov) to (rgba_out, cov_out), ping-pong through the two scratch pairs, which are read only
-// when passes > 1.  None of the six may be another of them.  Enqueues only.
-static int lm_dilate_enqueue(const double* rgba, const uint8_t* cov, uint32_t w, uint32_t h, int32_t passes, double* rgba_out, uint8_t* cov_out,
-                             double* rgba_tmp, uint8_t* cov_tmp, hipStream_t stream) {
-    using namespace rt;
-    const size_t n = size_t(w) * h;
-    if (passes == 0) {
-        HIP_TRY(hipMemcpyAsync(rgba_out, rgba, n * 32, hipMemcpyDeviceToDevice, stream));
-        HIP_TRY(lm_coverage_bytes_launch(cov, n, cov_out, stream));
-        return RT_OK;
-    }
-    const double* src = rgba;
-    const uint8_t* src_c = cov;
-    for (int32_t k = 1; k <= passes; k++) {
-        const bool to_out = ((passes - k) % 2) == 0;
-        double* dst = to_out ? rgba_out : rgba_tmp;
-        uint8_t* dst_c = to_out ? cov_out : cov_tmp;
-        HIP_TRY(lm_dilate_launch(src, src_c, w, h, dst, dst_c, stream));
-        src = dst;
-        src_c = dst_c;
-    }
-    return RT_OK;
-}
-
-static int lm_dilate_check(const void* a, const void* b, const void* c, const void* d, uint32_t w, uint32_t h, int32_t passes, const char* who) {
-    using namespace rt;
-    const std::string p = std::string(who) + ": ";
-    if (!a) return set_err(RT_E_INVALID, p + "rgba is NULL");
-    if (!b) return set_err(RT_E_INVALID, p + "coverage is NULL");
-    if (!c) return set_err(RT_E_INVALID, p + "rgba_out is NULL");
-    if (!d) return set_err(RT_E_INVALID, p + "coverage_out is NULL");
-    if (w == 0 || w > kLmMaxDim) return set_err(RT_E_INVALID, p + "w must be in 1 .. 16384");
-    if (h == 0 || h > kLmMaxDim) return set_err(RT_E_INVALID, p + "h must be in 1 .. 16384");
-    if (passes < 0) return set_err(RT_E_INVALID, p + "passes must not be negative");
-    if (a == c || b == d) return set_err(RT_E_INVALID, p + "the outputs must not be the inputs");
-    return RT_OK;
-}
-
-int rt_lightmap_dilate_device(int device, const double* d_rgba, const uint8_t* d_coverage, uint32_t w, uint32_t h, int32_t passes,
-                              double* d_rgba_out, uint8_t* d_coverage_out, void* stream) {
-    using namespace rt;
-    if (int st = lm_dilate_check(d_rgba, d_coverage, d_rgba_out, d_coverage_out, w, h, passes, "rt_lightmap_dilate_device")) return st;
-    HIP_TRY(hipSetDevice(device));
-    const size_t n = size_t(w) * h;
-    DevBuf<double> tmp;
-    DevBuf<uint8_t> tmp_c;
-    if (passes > 1) {
-        if (int st = tmp.reserve(n * 32)) return st;
-        if (int st = tmp_c.reserve(n)) return st;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (int r = lm_dilate_enqueue(d_rgba, d_coverage, w, h, passes, d_rgba_out, d_coverage_out, tmp, tmp_c, st)) return r;
-    HIP_TRY(hipStreamSynchronize(st));
-    return RT_OK;
-}
-
-int rt_lightmap_dilate(int device, const double* rgba, const uint8_t* coverage, uint32_t w, uint32_t h, int32_t passes, double* rgba_out,
-                       uint8_t* coverage_out) {
-    using namespace rt;
-    if (int st = lm_dilate_check(rgba, coverage, rgba_out, coverage_out, w, h, passes, "rt_lightmap_dilate")) return st;
-    HIP_TRY(hipSetDevice(device));
-    const size_t n = size_t(w) * h;
-    DevBuf<double> in, out;
-    DevBuf<uint8_t> in_c, out_c;
-    if (int st = in.reserve(n * 32)) return st;
-    if (int st = out.reserve(n * 32)) return st;
-    if (int st = in_c.reserve(n)) return st;
-    if (int st = out_c.reserve(n)) return st;
-    HIP_TRY(hipMemcpy(in, rgba, n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(in_c, coverage, n, hipMemcpyHostToDevice));
-    if (int st = rt_lightmap_dilate_device(device, in, in_c, w, h, passes, out, out_c, nullptr)) return st;
-    HIP_TRY(hipMemcpy(rgba_out, out, n * 32, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(coverage_out, out_c, n, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-
-static int bake_lightmap_impl(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t w, uint32_t h, uint32_t kind, const RtRenderParams* rp,
-                              const RtBakeParams* bp, int32_t passes, double* rgba_out, uint8_t* cov_out, bool host, void* stream, const char* who) {
-    using namespace rt;
-    const std::string p = std::string(who) + ": ";
-    if (!scene) return set_err(RT_E_INVALID, p + "scene is NULL");
-    if (!rgba_out) return set_err(RT_E_INVALID, p + "rgba_out is NULL");
-    if (!cov_out) return set_err(RT_E_INVALID, p + "coverage_out is NULL");
-    if (kind != RT_LIGHTMAP_IRRADIANCE && kind != RT_LIGHTMAP_VISIBILITY) return set_err(RT_E_INVALID, p + "kind must be RT_LIGHTMAP_IRRADIANCE or RT_LIGHTMAP_VISIBILITY");
-    if (passes < 0) return set_err(RT_E_INVALID, p + "dilate_passes must not be negative");
-    LmMeshRef mesh;
-    if (int st = lightmap_select(scene->held.d, scene->compiled, node, instance, w, h, who, &mesh)) return st;
-    if (!scene->compiled.volumes.empty()) return set_err(RT_E_UNSUPPORTED, p + "a scene with volumes has no hit-record bakes");
-    const size_t n = size_t(w) * h;
-    if (kind == RT_LIGHTMAP_IRRADIANCE) {  // what the bake would refuse, before the device is touched
-        const TableCall c{who, {scene, "hits", sizeof(RtRayHit)}, {}, "rgba_out", 32, "point table", "point"};
-        if (int st = table_render_check(scene, n, rp, rgba_out, c)) return st;
-    } else if (bp) {  // bake_impl's rules
-        if (bp->precision != RT_PRECISION_F64 && bp->precision != RT_PRECISION_F32) return set_err(RT_E_INVALID, p + "precision must be RT_PRECISION_F64 or RT_PRECISION_F32");
-        if (bp->samples < 1 || bp->samples > 4096) return set_err(RT_E_INVALID, p + "samples must be in 1 .. 4096");
-        if (!(bp->bias >= 0.0)) return set_err(RT_E_INVALID, p + "bias must be >= 0");
-        if (!(bp->max_distance > bp->bias)) return set_err(RT_E_INVALID, p + "max_distance must be greater than bias");
-    }
-    RtScene* s = const_cast<RtScene*>(scene);  // workspace + lazily built tables; the scene data itself is immutable
-    return lm_with_f64(s, [&](DeviceScene<double>& ds) -> int {
-        hipStream_t st = stream ? static_cast<hipStream_t>(stream) : static_cast<hipStream_t>(s->stream);
-        RtScene::Lightmap& L = s->lm;
-        auto outputs = [&](RtRayHit** d_hits, uint32_t** d_counts) -> int {  // the stages' buffers, once the rasteriser has not refused
-            if (int r = L.hits.reserve(n * sizeof(RtRayHit))) return r;
-            if (int r = L.rgba_a.reserve(n * 32)) return r;
-            if (int r = L.cov_a.reserve(n)) return r;
-            if (int r = L.cov_b.reserve(n)) return r;
-            if (passes > 1) {
-                if (int r = L.rgba_b.reserve(n * 32)) return r;
-                if (int r = L.cov_c.reserve(n)) return r;
-            }
-            if (host)
-                if (int r = L.rgba_o.reserve(n * 32)) return r;
-            *d_hits = L.hits;
-            *d_counts = nullptr;
-            return RT_OK;
-        };
-        if (int r = lm_rasterise(s, ds, mesh, w, h, outputs, st, who)) return r;
-        HIP_TRY(lm_coverage_launch(L.hits, n, L.cov_a, st));
-        if (kind == RT_LIGHTMAP_IRRADIANCE) {
-            if (int r = rt_bake_irradiance_hits_device(scene, n, L.hits, rp, L.rgba_a, st)) return r;
-        } else {
-            if (int r = L.vis.reserve(n * sizeof(RtBakeResult))) return r;
-            if (int r = rt_bake_visibility_hits_device(scene, n, L.hits, bp, L.vis, st)) return r;
-            HIP_TRY(lm_visibility_rgba_launch(L.vis, L.cov_a, n, L.rgba_a, st));
-        }
-        double* d_rgba = host ? L.rgba_o.get() : rgba_out;
-        if (int r = lm_dilate_enqueue(L.rgba_a, L.cov_a, w, h, passes, d_rgba, L.cov_b, L.rgba_b, L.cov_c, st)) return r;
-        if (host) {
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipMemcpy(rgba_out, L.rgba_o, n * 32, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(cov_out, L.cov_a, n, hipMemcpyDeviceToHost));
-        } else {
-            HIP_TRY(hipMemcpyAsync(cov_out, L.cov_a, n, hipMemcpyDeviceToDevice, st));
-            HIP_TRY(hipStreamSynchronize(st));
-        }
-        return RT_OK;
-    });
-}
-
-int rt_bake_lightmap(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, uint32_t kind,
-                     const RtRenderParams* render_params, const RtBakeParams* bake_params, int32_t dilate_passes, double* rgba_out,
-                     uint8_t* coverage_out) {
-    return bake_lightmap_impl(scene, node, instance, width, height, kind, render_params, bake_params, dilate_passes, rgba_out, coverage_out, true, nullptr,
-                              "rt_bake_lightmap");
-}
-int rt_bake_lightmap_device(const RtScene* scene, uint32_t node, uint32_t instance, uint32_t width, uint32_t height, uint32_t kind,
-                            const RtRenderParams* render_params, const RtBakeParams* bake_params, int32_t dilate_passes, double* d_rgba_out,
-                            uint8_t* d_coverage_out, void* stream) {
-    return bake_lightmap_impl(scene, node, instance, width, height, kind, render_params, bake_params, dilate_passes, d_rgba_out, d_coverage_out, false, stream,
-                              "rt_bake_lightmap_device");
-}
-
 }  // extern "C"
+
+// query_search_pass as rt_query.hip calls it (rt_scene_host.h): plain functions, and last in the file.  The compiler emits a
+// kernel where it is first named; named from here, make_search_setup<R> is first named inside render_wavefront's instantiation,
+// as it always was, and the search kernels keep their places in the code object.  An explicit instantiation of the template
+// would name them where it stands, float and double side by side.
+namespace rt {
+int query_search_pass(RtScene* s, DeviceScene<float>& ds, const PathPool<float>& pl, uint32_t m, hipStream_t stream) {
+    return query_search_pass<float>(s, ds, pl, m, stream);
+}
+int query_search_pass(RtScene* s, DeviceScene<double>& ds, const PathPool<double>& pl, uint32_t m, hipStream_t stream) {
+    return query_search_pass<double>(s, ds, pl, m, stream);
+}
+}  // namespace rt

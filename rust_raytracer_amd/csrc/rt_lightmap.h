@@ -186,7 +186,7 @@ struct LmTimes {
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 namespace rt {
-// Workspace of the rasteriser: owned by the scene (rt_kernels.hip), sized by lm_workspace_bytes.
+// Workspace of the rasteriser: the buffers of RtScene::Lightmap (rt_scene_host.h), reserved by lm_rasterise (rt_lightmap.hip).
 struct LmWorkspace {
     uint32_t* tile_count;   // n_tiles + 1
     uint32_t* tile_offset;  // n_tiles + 1 (exclusive scan)

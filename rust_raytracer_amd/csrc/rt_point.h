@@ -1,4 +1,4 @@
-// rt_point.h — point queries: the launcher of k_pq_closest (rt_point.hip), called by the C ABI in rt_kernels.hip, and the exact
+// rt_point.h — point queries: the launcher of k_pq_closest, called by the host side of the queries (both in rt_point.hip), and the exact
 // closest-point arithmetic, each routine written once: closest_on_triangle, the parallelogram as two triangles, the sphere,
 // and the distance-ordered search of one mesh instance (mesh_closest).
 // Definition of the result: include/rt_mi355.h (rt_closest_points), DESIGN.md §20.

@@ -1,5 +1,5 @@
-// rt_query.h — launchers of the ray-query kernels (rt_query.hip), called by the C ABI in rt_kernels.hip, and the occlusion
-// walk of the scene program (segment_occluded), one definition for every kernel that asks "is this segment blocked".
+// rt_query.h — launchers of the ray-query kernels, called by the host side of the queries (both in rt_query.hip), and the
+// occlusion walk of the scene program (segment_occluded), one definition for every kernel that asks "is this segment blocked".
 // Definitions of the results: include/rt_mi355.h (rt_trace_rays, rt_occluded), DESIGN.md §14.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,8 +12,7 @@
 
 namespace rt {
 
-// The arrays of a WfPool<R> (rt_wavefront.h) that a query touches: the ray the search kernels read and the hit record
-// they leave.  A view of its own, so that this translation unit does not need the scheduler's header.
+// The arrays of a WfPool<R> (rt_pool.h) that a query touches: the ray the search kernels read and the hit record they leave.
 template <typename R>
 struct RqPool {
     R *ox, *oy, *oz, *dx, *dy, *dz;

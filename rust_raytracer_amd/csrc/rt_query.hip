@@ -1,15 +1,21 @@
 // rt_query.hip — ray queries: closest hit and occlusion for rays the caller supplies (include/rt_mi355.h: rt_trace_rays,
-// rt_occluded).  A translation unit of its own: the render kernels in rt_kernels.hip are not touched.
+// rt_occluded): the kernels, their launchers, the host side (workspace, chunk loops) and the entry points.  A
+// translation unit of its own: the render kernels in rt_kernels.hip are not touched.
 //   closest hit:  k_rq_load writes the rays into a path pool, the scene's own search kernels run one pass over it
 //                 (rt_kernels.hip, query_search_pass), k_rq_resolve turns the hit records into RtRayHit;
 //   occlusion:    k_rq_occluded, an any-hit walk of the scene program that leaves at the first accepted primitive.
+// rq_tables and rq_chunk serve point queries (rt_point.hip) and lightmaps (rt_lightmap.hip) too.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <string>
+#include <variant>
 
 #include "rt_device.h"
 #include "rt_query.h"
+#include "rt_scene_host.h"
 
 namespace rt {
 
@@ -189,4 +195,129 @@ RT_RQ_INSTANTIATE(double)
 RT_RQ_INSTANTIATE(float)
 #undef RT_RQ_INSTANTIATE
 
+// ---------------------------------------------------------------------------------------------
+// Host side: the query workspace of a scene (RtScene::Query, rt_scene_host.h), the chunk loops and the entry points
+// ---------------------------------------------------------------------------------------------
+uint32_t rq_chunk() { return std::min<uint32_t>(1u << 28, std::max<uint32_t>(64u, env_u32("RT_RQ_CHUNK", 1u << 22))); }
+
+// Counters and (closest hit: `pool`) a pool of at least `capacity` slots in R.
+template <typename R>
+int rq_ensure(RtScene* s, uint32_t capacity, bool pool) {
+    RtScene::Query& q = s->rq;
+    if (int st = q.d_ctr.reserve(sizeof(WfCounters))) return st;
+    if (int st = q.h_ctr.reserve(sizeof(WfCounters))) return st;
+    const auto* have = std::get_if<PoolPair<R>>(&q.pools);
+    if (!pool || (have && (*have)[0].view.capacity >= capacity)) return RT_OK;
+    q.pools = std::monostate{};
+    PoolPair<R> pp;  // the arrays a query does not use stay NULL
+    if (int st = build_pool(pp[0], capacity, false, 1, "ray-query pool does not fit in device memory (RT_RQ_CHUNK sets its size)")) return st;
+    q.pools = std::move(pp);
+    return RT_OK;
+}
+
+// op -> node and leaf slot -> triangle tables of the scene as it stands (uploaded again after an rt_scene_update)
+int rq_tables(RtScene* s, hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    if (q.tables_generation == s->generation && q.op_node) return RT_OK;
+    q.op_node.reset();
+    q.tri_order.reset();
+    const CompiledScene& cs = s->compiled;
+    if (int st = q.op_node.reserve(std::max<size_t>(1, cs.op_node.size()) * 4)) return st;
+    if (int st = q.tri_order.reserve(std::max<size_t>(1, cs.tri_order.size()) * 4)) return st;
+    if (!cs.op_node.empty()) HIP_TRY(hipMemcpyAsync(q.op_node, cs.op_node.data(), cs.op_node.size() * 4, hipMemcpyHostToDevice, stream));
+    if (!cs.tri_order.empty()) HIP_TRY(hipMemcpyAsync(q.tri_order, cs.tri_order.data(), cs.tri_order.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    q.tables_generation = s->generation;
+    return RT_OK;
+}
+
+// n rays in chunks: (host variant: through the staging buffer) k_rq_load -> search pass -> k_rq_resolve.
+template <typename R>
+int trace_rays_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, RtRayHit* out, bool host,
+                     hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    const uint32_t chunk = rq_chunk();
+    if (int st = rq_ensure<R>(s, uint32_t(std::min<uint64_t>(n, chunk)), true)) return st;
+    if (int st = rq_tables(s, stream)) return st;
+    const PathPool<R>& pl = std::get<PoolPair<R>>(q.pools)[0];
+    const WfPool<R>& full = pl.view;
+    const RqPool<R> rp{full.ox, full.oy, full.oz, full.dx, full.dy, full.dz, full.ht, full.hu, full.hv, full.hpc, full.htri};
+    const RqTables tb{q.op_node, q.tri_order};
+    ChunkTimes t;
+    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
+        HIP_TRY(rq_load_launch<R>(rp, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), m, pl.queue[0], stream));
+        if (int st = query_search_pass(s, ds, pl, m, stream)) return st;
+        HIP_TRY(rq_resolve_launch<R>(ds.view, rp, tb, m, static_cast<RtRayHit*>(d_out), stream));
+        return RT_OK;
+    };
+    if (int st = run_chunks(q.stage, n, chunk, host, {{origins, 24}, {dirs, 24}}, out, sizeof(RtRayHit), stream, launch, &t)) return st;
+    record_query_stats<R>(q.stats, t, n);
+    return RT_OK;
+}
+
+template <typename R>
+int occluded_typed(RtScene* s, DeviceScene<R>& ds, uint64_t n, const double* origins, const double* dirs, const double* t_min,
+                   const double* t_max, uint8_t* out, bool host, hipStream_t stream) {
+    RtScene::Query& q = s->rq;
+    const int levels = s->compiled.meshes.empty() ? 1 : int(s->compiled.max_bvh4_stack) + 1;
+    if (levels > kRqMaxStackLevels) return set_err(RT_E_UNSUPPORTED, "mesh BVH too deep for the occlusion kernel's LDS traversal stack");
+    const uint32_t cones_on = env_u32("RT_WF_CONES", 1) != 0 ? 1u : 0u;
+    const uint32_t chunk = rq_chunk();
+    if (int st = rq_ensure<R>(s, uint32_t(std::min<uint64_t>(n, chunk)), false)) return st;
+    ChunkTimes t;
+    auto launch = [&](uint64_t, uint32_t m, const void* const* d_in, void* d_out) -> int {
+        HIP_TRY(rq_occluded_launch<R>(ds.view, static_cast<const double*>(d_in[0]), static_cast<const double*>(d_in[1]), static_cast<const double*>(d_in[2]),
+                                      static_cast<const double*>(d_in[3]), m, levels, cones_on, static_cast<uint8_t*>(d_out), stream));
+        return RT_OK;
+    };
+    if (int st = run_chunks(q.stage, n, chunk, host, {{origins, 24}, {dirs, 24}, {t_min, 8}, {t_max, 8}}, out, 1, stream, launch, &t)) return st;
+    record_query_stats<R>(q.stats, t, n);
+    return RT_OK;
+}
+
 }  // namespace rt
+
+extern "C" {
+
+static int trace_rays_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* out,
+                           bool host, void* stream, const char* who) {
+    using namespace rt;
+    return ray_query_run(scene, precision, who, [&](RtScene* s, auto& ds) -> int {
+        if (n == 0) return RT_OK;
+        if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+        return trace_rays_typed(s, ds, n, origins, dirs, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
+    });
+}
+
+static int occluded_impl(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
+                         uint32_t precision, uint8_t* out, bool host, void* stream, const char* who) {
+    using namespace rt;
+    return ray_query_run(scene, precision, who, [&](RtScene* s, auto& ds) -> int {
+        if (n == 0) return RT_OK;
+        if (!origins || !dirs || !out) return set_err(RT_E_INVALID, std::string(who) + ": NULL array");
+        return occluded_typed(s, ds, n, origins, dirs, t_min, t_max, out, host, stream ? static_cast<hipStream_t>(stream) : s->stream);
+    });
+}
+
+int rt_trace_rays(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, uint32_t precision, RtRayHit* hits_out) {
+    return trace_rays_impl(scene, n, origins, dirs, precision, hits_out, true, nullptr, "rt_trace_rays");
+}
+int rt_trace_rays_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, uint32_t precision,
+                         RtRayHit* d_hits_out, void* stream) {
+    return trace_rays_impl(scene, n, d_origins, d_dirs, precision, d_hits_out, false, stream, "rt_trace_rays_device");
+}
+int rt_occluded(const RtScene* scene, uint64_t n, const double* origins, const double* dirs, const double* t_min, const double* t_max,
+                uint32_t precision, uint8_t* out) {
+    return occluded_impl(scene, n, origins, dirs, t_min, t_max, precision, out, true, nullptr, "rt_occluded");
+}
+int rt_occluded_device(const RtScene* scene, uint64_t n, const double* d_origins, const double* d_dirs, const double* d_t_min,
+                       const double* d_t_max, uint32_t precision, uint8_t* d_out, void* stream) {
+    return occluded_impl(scene, n, d_origins, d_dirs, d_t_min, d_t_max, precision, d_out, false, stream, "rt_occluded_device");
+}
+int rt_ray_query_stats(const RtScene* scene, RtRayQueryStats* out) {
+    if (!scene || !out) return rt::set_err(RT_E_INVALID, "rt_ray_query_stats: NULL argument");
+    *out = scene->rq.stats;
+    return RT_OK;
+}
+
+}  // extern "C"

@@ -1,8 +1,7 @@
 // rt_render.h — what a client of the renderer may use (rt_accum.hip is the one client): the two replica renders, the
-// helpers it shares with the entry points of rt_kernels.hip, and the six fields of a scene it touches.  RtScene itself stays
-// defined in, and private to, rt_kernels.hip.  The boundary is functions and not a shared struct because RtScene names the
-// wavefront workspace, whose header (rt_wavefront.h) defines non-template __global__ functions: a second translation unit
-// that included it would define their host stubs a second time.
+// helpers it shares with the entry points of rt_kernels.hip, and the six fields of a scene it touches.  The boundary is
+// functions and not the struct (rt_scene_host.h, for the translation units that own a workspace of the scene) by choice: a
+// client renders and reads six fields, and the accessors say so; with RtScene in view nothing would.
 #pragma once
 #include <hip/hip_runtime.h>
 

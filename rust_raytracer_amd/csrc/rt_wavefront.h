@@ -20,6 +20,7 @@
 #pragma once
 #include "rt_device.h"
 #include "rt_handout.h"
+#include "rt_pool.h"
 
 // Minimum waves per SIMD requested from the register allocator (second __launch_bounds__
 // argument); tuned on MI355X, see DESIGN.md.
@@ -31,19 +32,7 @@
 #endif
 namespace rt {
 
-template <typename R>
-struct WfPool {
-    uint32_t capacity;
-    R *ox, *oy, *oz, *dx, *dy, *dz;  // current ray, world space
-    R *tr, *tg, *tb;                 // throughput: product of the weights so far (the radiance exists only at the terminal)
-    uint64_t* rng;                   // stream state
-    uint64_t* sample;                // sample index within the current replica group
-    uint32_t* depth;                 // remaining depth (the `depth` argument of ray_color)
-    R *ht, *hu, *hv;                 // closest hit: t, (u, v)
-    int32_t *hpc, *htri;             // op that produced it (-1 none), triangle slot
-};
-
-// Element `slot` of a pool array through a 32-bit BYTE offset.  `base + zext(offset)` lets the compiler address every
+// Element `slot` of a pool array (WfPool<R>, rt_pool.h) through a 32-bit BYTE offset.  `base + zext(offset)` lets the compiler address every
 // array of one element size with ONE offset VGPR and keep the array bases in SGPRs (global_load ... v_off, s[base:base+1]);
 // with 64-bit index arithmetic it kept a VGPR pair per array alive from the loads to the stores (22 VGPRs in k_wf_shade).
 // Pool sizes are capped at 2^28 slots by the driver, so the offset cannot wrap.
@@ -58,15 +47,6 @@ template <typename T> RT_DEV void put_global(T* base, uint32_t slot, T v) {
     typedef __attribute__((address_space(1))) T GT;
     *reinterpret_cast<GT*>(reinterpret_cast<GChar*>((GT*)base) + slot * uint32_t(sizeof(T))) = v;
 }
-
-struct WfCounters {
-    uint32_t n_in;        // entries of the current queue
-    uint32_t n_out;       // entries appended to the next queue
-    uint32_t cursor;      // next queue entry to hand out (persistent intersect / mesh kernel)
-    uint32_t n_mesh;      // entries of the mesh queue (paths whose ray enters a deferred mesh's box)
-    unsigned long long next_sample;  // next sample (within the group) to start
-    uint32_t n_mesh_next; // fused shade + prims: entries of the NEXT iteration's mesh queue (k_wf_advance moves it to n_mesh); 0 otherwise
-};
 
 // Sample s of a replica group -> (replica, stratum, owned pixel).  Pixels run fastest so that a
 // wave starts neighbouring pixels of one stratum: coherent primary rays, coalesced buffers.
